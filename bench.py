@@ -51,7 +51,45 @@ def parse():
     ap.add_argument("--ragged", action="store_true",
                     help="document lengths ~ clip(lognormal(5.3, 0.6), 16, seq_len), sorted longest first (mirrors hybrid_search.py:273-276) "
                          "instead of the fixed-length headline workload")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed legs computed in their last step (encode: the embeddings; search: the "
+                         "queries, scores and ids; sparse: the dense and sparse vectors) as DIR/<name>.npy in float32 / float64, rank 0 only, "
+                         "at most 64 MB in all (an array over its share is a fixed seeded sample of its rows, DIR/<name>_rows.npy)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BYTES = 64_000_000 - (1 << 16)        # data bytes of --dump-outputs (the rest of 64 MB covers the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """name -> tensor as out_dir/<name>.npy: floating point as float32, integers as float64 (exact below 2^53).  Smallest first, each array
+    gets an equal share of what is left of DUMP_BYTES; one over its share is replaced by a seeded sample of its rows (same rows from run to
+    run), whose indices go to <name>_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    left, written = DUMP_BYTES, {}
+    order = sorted(arrs, key=lambda n: arrs[n].nbytes)
+    for j, name in enumerate(order):
+        a = arrs[name]
+        share = left // (len(order) - j)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0]
+            n = max(1, share // (row_bytes + 8))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(n, a.shape[0]), replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def barrier_sync(distributed):
@@ -984,6 +1022,7 @@ def main():
     # them that is not liblrx's)
     _lib.check(lrx.lrx_trace_marker(0, _lib.current_stream()))
     enc_s, docs_per_s, gu_timed, prof, n_prof = None, None, None, {}, 0
+    dumps = {}                                      # --dump-outputs: name -> what a timed leg's last step returned
     if "encode" in legs:
         for i in range(args.warmup):
             encode_step(i)
@@ -994,6 +1033,9 @@ def main():
             encode_step(args.warmup + i)
         barrier_sync(distributed)
         enc_s = time.perf_counter() - t0
+        if args.dump_outputs:                       # (outside the timed region) the rows the last timed step wrote
+            last = args.warmup + args.steps - 1
+            dumps["embeddings"] = index._x[last * B:(last + 1) * B].clone()
         gu_timed = enc.get_profile()["gemm_swiglu"]
         enc_s = reduce_max(enc_s, dev, distributed)
         docs_per_s = world * B * args.steps / enc_s
@@ -1027,6 +1069,8 @@ def main():
         _lib.check(lrx.lrx_trace_marker(1, _lib.current_stream()))
         barrier_sync(distributed)
         srch_s = time.perf_counter() - t0
+        if args.dump_outputs:                       # the last timed pass: its queries and the merged global top-k
+            dumps.update(search_queries=q, search_scores=Dk, search_ids=Ik)
         srch_s = reduce_max(srch_s, dev, distributed)
         local_ms = sum(ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(n_pass)) / n_pass
         # the filter pass streams the fp16 shadow of the shard (2 B/element); the exact rescoring of the few hundred band rows per
@@ -1149,9 +1193,11 @@ def main():
         barrier_sync(distributed)
         t0 = time.perf_counter()
         for i in range(n_sp):
-            enc.encode_packed_sparse(ids_all[args.warmup + i].reshape(-1), cu, S)
+            sp_out = enc.encode_packed_sparse(ids_all[args.warmup + i].reshape(-1), cu, S)
         barrier_sync(distributed)
         sp_s = time.perf_counter() - t0
+        if args.dump_outputs:
+            dumps.update(sparse_dense=sp_out[0], sparse_vectors=sp_out[1])
         mx_ms = enc.get_profile()["gemm_maxagg"]["ms"]
         enc.set_profiling(False)
         sp_s = reduce_max(sp_s, dev, distributed)
@@ -1174,6 +1220,11 @@ def main():
             sharded_legs = sharded_config_legs(args, dev, rank, world, distributed)
         except Exception as e:  # noqa: BLE001  (never take the headline line down; a rank that fails here fails the collectives of all)
             sharded_legs = {"failed": "%r" % (e,)}
+
+    if rank == 0 and args.dump_outputs and dumps:
+        shapes = dump_outputs(args.dump_outputs, dumps)
+        sys.stderr.write("bench.py: wrote %s to %s\n" % (", ".join("%s%s" % (n, s) for n, s in shapes.items()), args.dump_outputs))
+    dumps = None
 
     if rank != 0:
         if distributed:

@@ -174,7 +174,9 @@ def _bench_line(extra_env, *flags):
     env.pop("LRX_FORCE_COLLECTIVE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--legs", "encode,search", *flags],
                          env=env, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-3000:]
+    # (an aborting process group ends stderr with a long backtrace: the lines naming the error come first)
+    errors = [l for l in out.stderr.splitlines() if "rror" in l or "xception" in l or "what()" in l]
+    assert out.returncode == 0, "\n".join(errors[:20]) + "\n...\n" + out.stderr[-3000:]
     return json.loads(out.stdout.strip().splitlines()[-1])
 
 

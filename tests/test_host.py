@@ -555,30 +555,34 @@ def test_rpc_shard_mode_is_inactive_without_an_rpc_agent():
                 rpc_shards._WORKER["model"] = saved
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/eval"), reason="reference tree not mounted (GPU box)")
 def test_reference_eval_arguments_build_on_the_import_path_shim():
-    """The reference's own eval/eval_arguments.py (read in place, never copied) subclasses lightretriever.inference.arguments
-    .InferenceArguments: with this repo's import-path shim it must import, parse the flags of eval/call_evaluate_mteb.sh and the model
-    flags of the launch scripts, and run its __post_init__."""
-    import importlib.util
+    """The reference's eval/eval_arguments.py declares EvalArguments as a dataclass subclass of lightretriever.inference.arguments
+    .InferenceArguments and parses the flags of eval/call_evaluate_mteb.sh and the model flags of the launch scripts.
+    tests/golden/eval_arguments.json (gen_eval_arguments_golden.py) holds what it parsed on the reference's own package.  Through this repo's
+    import-path shim: the shim takes every base flag of that command line and leaves exactly the flags of the fields EvalArguments adds, each
+    flag lands with the reference's value (normalize too, derived in __post_init__), and a dataclass subclass adding those fields parses the
+    whole command line and runs the shim's __post_init__."""
+    import dataclasses
+    from typing import Optional
     from transformers import HfArgumentParser
-    spec = importlib.util.spec_from_file_location("ref_eval_arguments", "/root/reference/eval/eval_arguments.py")
-    mod = importlib.util.module_from_spec(spec)
-    dont = sys.dont_write_bytecode
-    sys.dont_write_bytecode = True          # leave the read-only tree untouched
-    try:
-        spec.loader.exec_module(mod)
-    finally:
-        sys.dont_write_bytecode = dont
+    from lightretriever.inference.arguments import InferenceArguments
     import lightretriever_amd.inference as mine
-    assert issubclass(mod.EvalArguments, mine.InferenceArguments)
-    (a,) = HfArgumentParser(mod.EvalArguments).parse_args_into_dataclasses(
-        ["--model_name_or_path", "results/lightretriever-llama3.2-1b", "--benchmark_name", "BEIR", "--top_k", "1000", "--inference_arch",
-         "PytorchRPCExactSearchModel", "--output_dir", "/tmp/out", "--batch_size", "256", "--corpus_chunk_size", "100000",
-         "--model_type", "HybridModel", "--hybrid_use_emb_vector", "--noncontextual_query_embedding", "--lowercase", "--add_sep_token", "--pooling_strategy",
-         "lasttoken", "--score_function", "cos_sim", "--q_max_len", "512", "--p_max_len", "512", "--bf16"])
-    assert a.top_k == 1000 and a.corpus_chunk_size == 100000 and a.normalize is True and a.encode_sparse is False
-    assert a.model_type == "HybridModel" and a.inference_arch == "PytorchRPCExactSearchModel" and max(a.k_values) <= a.top_k
+    assert InferenceArguments is mine.InferenceArguments
+    fx = json.load(open(os.path.join(GOLDEN, "eval_arguments.json")))
+    argv, want = fx["argv"], fx["parsed"]
+    eval_flags = {"--" + n for n in fx["eval_fields"]}
+    a, rest = HfArgumentParser(InferenceArguments).parse_args_into_dataclasses(argv, return_remaining_strings=True)
+    assert rest == [t for i, t in enumerate(argv) if t in eval_flags or (i and argv[i - 1] in eval_flags)]
+    base_named = [t[2:] for t in argv if t.startswith("--") and t not in eval_flags]
+    for name in base_named + ["normalize"]:
+        assert getattr(a, name) == want[name], name
+    assert a.normalize is True and a.encode_sparse is False
+    assert a.model_type == "HybridModel" and a.inference_arch == "PytorchRPCExactSearchModel"
+    extra = [n for n in fx["eval_fields"] if "--" + n in argv]
+    EvalLike = dataclasses.make_dataclass("EvalLike", [(n, Optional[str], dataclasses.field(default=None)) for n in extra], bases=(InferenceArguments,))
+    (e,) = HfArgumentParser(EvalLike).parse_args_into_dataclasses(argv)
+    assert all(getattr(e, n) == str(want[n]) for n in extra)
+    assert all(getattr(e, f.name) == getattr(a, f.name) for f in dataclasses.fields(InferenceArguments))
 
 
 def test_bench_gpus_flag_is_checked_before_any_gpu_work():
@@ -592,6 +596,30 @@ def test_bench_gpus_flag_is_checked_before_any_gpu_work():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "64"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--gpus 64 but only" in r.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: float arrays as float32, integer ids as exact float64; an array over its share of the 64 MB budget becomes the
+    same seeded sample of its rows on every run, with the row indices next to it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("lrx_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"embeddings": torch.randn(256, 64, generator=g), "search_ids": torch.randint(0, 10_000_000, (100, 100), generator=g),
+              "sparse_vectors": torch.randn(256, 70_000, generator=g)}
+    for run in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / run), arrays)
+        assert shapes["embeddings"] == [256, 64] and shapes["search_ids"] == [100, 100] and 0 < shapes["sparse_vectors"][0] < 256
+        assert sum(os.path.getsize(p) for p in (tmp_path / run).iterdir()) <= 64_000_000
+    emb = np.load(str(tmp_path / "a" / "embeddings.npy"))
+    ids = np.load(str(tmp_path / "a" / "search_ids.npy"))
+    assert emb.dtype == np.float32 and np.array_equal(emb, arrays["embeddings"].numpy())
+    assert ids.dtype == np.float64 and np.array_equal(ids.astype(np.int64), arrays["search_ids"].numpy())
+    rows = np.load(str(tmp_path / "a" / "sparse_vectors_rows.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "sparse_vectors.npy")), arrays["sparse_vectors"].numpy()[rows])
+    for f in os.listdir(str(tmp_path / "a")):
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))), f
 
 
 def test_trained_like_synthetic_checkpoint_hits_its_regime_on_cpu():
