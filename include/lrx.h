@@ -246,23 +246,27 @@ int lrx_build_positions(const int32_t* cu_seqlens, int32_t n_seqs, int32_t total
  * utils/nested_input.py:137-146): out[T, nq*d] bf16 = softmax(q k^T / sqrt(d), causal within each sequence) v.
  * qkv [T, (nq + 2 nkv) * d] FP16 as lrx_gemm_qkv_rope writes it (probabilities are rounded to fp16 too; fp32 accumulation).
  * last_tile_only != 0: only the 64-row q tile that holds each sequence's LAST token is computed (other rows of `out`
- * are left untouched) -- all the pooled path needs from the final layer.                                          */
+ * are left untouched) -- all the pooled path needs from the final layer.
+ * A sequence's rows are addressed through one buffer descriptor: max_seqlen x (nq + 2 nkv) x d x 2 B must stay below 2 GiB
+ * (>= 174 k tokens at 32 / 8 heads of 128, beyond every supported max_positions), else LRX_ERR_INVALID.        */
 int lrx_attn_varlen_causal(const void* qkv, const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens,
                            int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
                            void* out, int32_t last_tile_only, void* stream);
 
 /* The same attention on a prebuilt WORK LIST (ABI 7): which (sequence, kv head, q tile) each persistent workgroup computes, and in which
  * order, depends on cu_seqlens and the head layout only, so the encoder builds it once per batch and every layer's launch reads it
- * (lrx_encode_* do this inside their workspace).  Results are bit-identical to lrx_attn_varlen_causal; the launch is ~10 % shorter on
- * the tiled path (head_dim 128, or head_dim 64 beyond 512 tokens: no per-item index arithmetic).
+ * (lrx_encode_* do this inside their workspace).  Results are bit-identical to lrx_attn_varlen_causal; the launch is ~5 % shorter on
+ * the tiled path at head_dim 128 (0.95 against 1.00 ms at 32 / 8 heads, 256 x 512 tokens: the items are not derived per workgroup,
+ * DESIGN.md 5.2).
  *   lrx_attn_items_bytes   size of the list; bounded by (total_tokens / 64 + n_seqs) x kv heads and non-decreasing in total_tokens and
  *                          max_seqlen (size once with the largest batch / longest sequence the caller will ever pass)
  *   lrx_attn_build_items   fills `items` (device memory, 16-byte aligned) on `stream`; one list per (cu_seqlens, max_seqlen, head
  *                          layout, last_tile_only) -- a list built with other arguments than the launch's gives wrong results.  Launches
  *                          nothing when the launch with the same arguments would not read a list (the K/V-resident geometries below).
  *                          At most 1024 persistent workgroups are planned (the builder is one block), whatever the CU count
- *   lrx_attn_varlen_causal_items   the launch (lrx_attn_varlen_causal's arguments + the list); `items` must stay untouched until it has
- *                          run.  Geometries served by the K/V-resident kernel (head_dim 64, max_seqlen <= 512) do not read the list.          */
+ *   lrx_attn_varlen_causal_items   the launch (lrx_attn_varlen_causal's arguments + the list, which must not be NULL); `items` must stay
+ *                          untouched until it has run.  Geometries served by the K/V-resident kernel (head_dim 64, max_seqlen <= 512)
+ *                          do not read the list.                                                                                          */
 size_t lrx_attn_items_bytes(int32_t n_seqs, int32_t total_tokens, int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads,
                             int32_t head_dim, int32_t last_tile_only);
 int lrx_attn_build_items(const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens, int32_t max_seqlen, int32_t num_q_heads,

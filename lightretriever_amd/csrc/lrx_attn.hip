@@ -56,436 +56,83 @@ constexpr int attn_dma_waves(int insts, int nw) {   // largest divisor of insts 
 // the 16-bit output element: bf16, or (out_f16, the precise stream's fp16 GEMM operands) fp16 -- |o| <= max |v| <= 65504: no saturation to count
 __device__ __forceinline__ __bf16 o16(float v, int out_f16) { return out_f16 ? __builtin_bit_cast(__bf16, (_Float16)v) : f2bf(v); }
 
-template <int D, int GRP>
-__global__ void __launch_bounds__(128 * GRP)
-k_attn_varlen_causal(const __bf16* __restrict__ qkv, const int32_t* __restrict__ cu, int nqt, int nq, int nkv,
-                     __bf16* __restrict__ out, float scale_log2, int last_tile_only, int nparts, int n_seqs, int n_items, int gs, int out_f16) {
-  using G = AttnGeom<D>;
-  constexpr int NW = 2 * GRP;
-  constexpr int KS = D / 16;  // k-steps of the QK^T product
-  constexpr int DT = D / 32;  // 32-row tiles of O^T
-  // K/V ring: 3 stages with a counted vmcnt (two tiles in flight; a tile's compute, ~0.5 us, is shorter than the load
-  // latency, so one tile of prefetch leaves every barrier waiting on HBM).
-  // The first DW waves (a divisor of the instruction count, e.g. 8 of the 12 waves of a GQA-6 group) issue the LDS-DMA, the same
-  // number each, so the counted wait is one immediate for everybody (waves without loads have nothing outstanding).
-  // (Tried: running the workgroup's two halves half a tile apart, two barriers per tile, so that one half's softmax sits beside
-  // the other's MFMAs -- 1.143 -> 1.173 ms at d = 128: the loop is not bound by that pairing, see the ablation in DESIGN.md.)
-  constexpr int DW = attn_dma_waves(G::INSTS, NW);
-  constexpr int NST = 3;
-  static_assert(NST * 2 * G::TILE_BYTES <= 96 * 1024, "K/V ring");
-  constexpr int PER_TILE = 2 * (G::INSTS / DW);  // LDS-DMA instructions per issuing wave per tile (K + V)
-  // Per-wave staging block (32 rows x D bf16, private to the wave): the wave's Q rows arrive in it by LDS-DMA (whole 2D-byte row
-  // segments per request instead of 32 rows x 32 B per load instruction) and its O rows leave through it (16 B per lane, whole
-  // row segments per store instruction instead of 32 rows x 16 B).  Ablation at d = 128: the 8-byte-piece stores cost 0.20 ms and
-  // the row-gather Q loads 0.16 ms of a 1.25 ms launch.
-  constexpr int QO_BYTES = 32 * G::ROW_BYTES;
-  constexpr int QINST = QO_BYTES / 1024;         // LDS-DMA instructions per Q block
-  __shared__ __attribute__((aligned(1024))) char smem[NST * 2 * G::TILE_BYTES + NW * QO_BYTES];  // [stage][K|V] | [wave] Q/O block
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: branches on it stay scalar
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t RS = (int64_t)(nq + 2 * nkv) * D;
-  const int grp_total = nq / nkv;
-
-  // Persistent workgroups: the grid is one workgroup per CU-slot, each walks a list of work items (sequence, kv head[, part], q tile).
-  // (A 96-KiB-LDS workgroup is alone on its CU; with one item per workgroup the CU sat empty a third of the time between a
-  // workgroup's exit and its successor's first instruction -- PMC: 64 workgroups x 18 us of wave lifetime per CU in a 1.85 ms launch.)
-  // The list is built for L2 reuse: the nqt q tiles of one (sequence, kv head) re-read the same K/V tiles (4.5x at S = 512), so they
-  // run at the same time on `gs` workgroups of ONE XCD (blocks b and b + 8 share an XCD: observed dispatch rule, speed only) --
-  // in q-tile-major order over the whole launch every re-read came from HBM and the load + barrier skeleton alone took 0.77 of
-  // the 1.4 ms.  Slot j of a group takes q tiles j, j + gs, ... of its group's current pair, from the long end on even steps and
-  // from the short end on odd ones, so every slot sees the same number of K/V tiles over two steps.
-  // The K/V tiles of all the items of a workgroup form ONE stream through the ring: the prefetch runs two tiles ahead of the
-  // compute across item boundaries (its own walker over the same item list), and the next item's Q fragments are requested during
-  // the current item's last tile -- an item boundary costs no load latency.
-  const int ny = nkv * nparts;
-  const int n_pairs = n_seqs * ny;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int g4 = gs > 0 ? slot / gs : 0, jslot = gs > 0 ? slot % gs : 0, gpx = gs > 0 ? (int)(gridDim.x >> 3) / gs : 1;
-  struct Walk { int step, kq, item; };
-  struct Item { int pair, qt, s0, len; };      // pair < 0: end of the list
-  auto next_item = [&](Walk& w) -> Item {
-    for (;;) {
-      int pair, qt_sel = -1;
-      if (gs > 0) {
-        // v-th (kv head of a sequence, part) of this XCD: the parts of one kv head (they read the same K/V) sit in neighbouring
-        // groups of the same XCD
-        const int v = w.step * gpx + g4;
-        pair = ((v / nparts) * 8 + xcd) * nparts + v % nparts;
-        if ((v / nparts) * 8 >= n_pairs / nparts) return Item{-1, 0, 0, 0};
-        if (pair >= n_pairs) { ++w.step; w.kq = 0; continue; }
-        const int idx = jslot + w.kq * gs;
-        if (idx >= nqt) { ++w.step; w.kq = 0; continue; }
-        qt_sel = (w.step & 1) ? idx : nqt - 1 - idx;
-        ++w.kq;
-      } else {                         // one item per (pair[, q tile]), round-robin (last-tile mode, odd grids)
-        if (w.item >= n_items) return Item{-1, 0, 0, 0};
-        pair = last_tile_only ? w.item : w.item % n_pairs;
-        if (!last_tile_only) qt_sel = nqt - 1 - w.item / n_pairs;
-        w.item += gridDim.x;
+// ---------------------------------------------------------------------------------------------------------------
+// Work items.  One item = {first token, length, q tile | part << 16, kv head}: a 64-row q tile of one (sequence, kv head[, part]);
+// length 0 ends a workgroup's items.  The grid is persistent (k_attn_stream), and attn_next_item is the ONE definition of which items a
+// workgroup computes and in which order: k_attn_build_items stores its walk as the work list, the list-less launch runs it in the kernel.
+// The order is built for L2 reuse: the nqt q tiles of one (sequence, kv head) re-read the same K/V tiles (4.5x at S = 512), so they
+// run at the same time on `gs` workgroups of ONE XCD (blocks b and b + 8 share an XCD: observed dispatch rule, speed only) --
+// in q-tile-major order over the whole launch every re-read came from HBM and the load + barrier skeleton alone took 0.77 of
+// the 1.4 ms.  Slot j of a group takes q tiles j, j + gs, ... of its group's current pair, from the long end on even steps and
+// from the short end on odd ones, so every slot sees the same number of K/V tiles over two steps.  The parts of one kv head (they read
+// the same K/V) sit in neighbouring groups of the same XCD.  gs = 0 (last-tile mode, odd grids): one item per (pair[, q tile]), round-robin.
+// ---------------------------------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+struct AttnWalk {            // one workgroup's walk: attn_walk_start, then attn_next_item per item
+  int xcd, g4, jslot, gpx;   // its XCD, its group and its slot in the group (gs > 0), groups per XCD
+  int step, kq, item;        // where it is
+  i32x4 cur;                 // (gs > 0) the current step's (sequence, kv head, part) as an item without its q tile: loaded once per step
+};
+__device__ __forceinline__ AttnWalk attn_walk_start(int wg, int n_wg, int gs) {
+  const int slot = wg >> 3;
+  return AttnWalk{wg & 7, gs > 0 ? slot / gs : 0, gs > 0 ? slot % gs : 0, gs > 0 ? (n_wg >> 3) / gs : 1, 0, 0, wg, i32x4{0, 0, 0, 0}};
+}
+// {first token, length, part << 16, kv head} of (kv head of a sequence, part) number `pair`
+__device__ __forceinline__ i32x4 attn_pair(const int32_t* __restrict__ cu, int pair, int nkv, int nparts) {
+  const int ny = nkv * nparts, sq = pair / ny, yy = pair - sq * ny, hk = yy / nparts;
+  const int s0 = cu[sq];
+  return i32x4{s0, cu[sq + 1] - s0, (yy - hk * nparts) << 16, hk};
+}
+// The next item of the walk; length 0 at its end (and after it).
+__device__ __forceinline__ i32x4 attn_next_item(AttnWalk& w, const int32_t* __restrict__ cu, int n_wg, int nqt, int nkv, int nparts, int n_seqs,
+                                                int n_items, int gs, int last_tile_only) {
+  const int n_pairs = n_seqs * nkv * nparts;
+  for (;;) {
+    i32x4 it;
+    int qt;
+    if (gs > 0) {
+      if (w.kq == 0) {                          // a new step: its pair, the v-th (kv head of a sequence, part) of this XCD
+        const int v = w.step * w.gpx + w.g4;
+        if ((v / nparts) * 8 >= n_pairs / nparts) return i32x4{0, 0, 0, 0};
+        const int pair = ((v / nparts) * 8 + w.xcd) * nparts + v % nparts;
+        if (pair >= n_pairs) { ++w.step; continue; }
+        w.cur = attn_pair(cu, pair, nkv, nparts);
       }
-      const int b = pair / ny;
-      const int s0 = cu[b], len = cu[b + 1] - s0;
-      // last_tile_only: one q tile per sequence, the one holding its last token (all the pooled path needs of the last layer)
-      const int qt = last_tile_only ? ((len - 1) >> 6) : qt_sel;
-      if (len <= 0 || qt * 64 >= len) continue;
-      return Item{pair, qt, s0, len};
-    }
-  };
-
-  // ---- staging: instruction j (0..INSTS-1) of a tile fills LDS bytes [j*1024, j*1024+1024): slot s = j*64 + lane,
-  //      row = s / CH, chunk position cs = s % CH, holding logical chunk cs ^ x(row)
-  auto stage = [&](int st, const Item& it, int kt) {
-    char* sK = smem + st * (2 * G::TILE_BYTES);
-    char* sV = sK + G::TILE_BYTES;
-    if (wave >= DW) return;
-    const int hk_ = (it.pair % ny) / nparts;
-    const __bf16* kbase = qkv + (int64_t)it.s0 * RS + (int64_t)(nq + hk_) * D;
-    const __bf16* vbase = kbase + (int64_t)nkv * D;
-#pragma unroll
-    for (int jj = 0; jj < G::INSTS / DW; ++jj) {
-      const int j = wave + jj * DW;
-      int s = j * 64 + lane;
-      int row = s / G::CH, cs = s % G::CH;
-      int grow = min(kt * 64 + row, it.len - 1);
-      const __bf16* kp = kbase + (int64_t)grow * RS + ((cs ^ G::xk(row)) << 3);
-      const __bf16* vp = vbase + (int64_t)grow * RS + ((cs ^ G::xv(row)) << 3);
-      __builtin_amdgcn_global_load_lds((gptr_t)kp, (lptr_t)(sK + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((gptr_t)vp, (lptr_t)(sV + j * 1024), 16, 0, 0);
-    }
-  };
-  // prefetch side of the stream
-  Walk wp = {0, 0, (int)blockIdx.x};
-  Item ip = next_item(wp);
-  int ktp = 0, sp_ = 0;                      // next tile of ip to request, ring slot it goes to
-  auto stage_next = [&]() -> bool {
-    if (ip.pair < 0) return false;
-    stage(sp_, ip, ktp);
-    sp_ = sp_ == NST - 1 ? 0 : sp_ + 1;
-    if (++ktp > ip.qt) { ip = next_item(wp); ktp = 0; }
-    return true;
-  };
-
-  // ---- lane-constant LDS read offsets: ONE register each, the other k-steps / d tiles by XOR (both swizzles are XORs of the 16-B chunk
-  //      index and the chunk's own k-step / d-tile bits are disjoint from the rest): at head_dim 128 this kernel sits at its 256-VGPR
-  //      budget, twelve offset registers are ten too many.
-  // K row read: row (sub*32 + r), logical chunk 2ks + h;  V transposed read: 16-lane group g = lane>>4, i = lane&15, qd = i>>2, p = i&3;
-  // block row = key_base + qd, columns dt*32 + 16*(g&1) + 4p .. +3  ->  logical chunk dt*4 + 2*(g&1) + (p>>1), byte 8*(p&1) inside it
-  const int koff0 = r * G::ROW_BYTES + ((h ^ G::xk(r)) << 4);
-  int voff0;
-  {
-    const int g = lane >> 4, i = lane & 15, qd = i >> 2, p = i & 3;
-    voff0 = qd * G::ROW_BYTES + (((2 * (g & 1) + (p >> 1)) ^ G::xv(qd)) << 4) + 8 * (p & 1);
-  }
-
-  // Q block of an item for this wave: rows q0 .. q0 + 31 of its head, requested into the wave's staging block with the K-tile
-  // swizzle (so the fragment reads are the K row reads: koff); fragments Q[q0 + r][16 ks + 8 h .. +7] (B operand)
-  char* const sW = smem + NST * 2 * G::TILE_BYTES + wave * QO_BYTES;
-  auto request_q = [&](const Item& it) {
-    const int yy = it.pair % ny;
-    const int hk_ = yy / nparts, part_ = yy - hk_ * nparts;
-    const int hig = part_ * GRP + (wave % GRP);
-    const int q0_ = it.qt * 64 + (wave / GRP) * 32;
-    if (q0_ >= it.len || hig >= grp_total) return;           // (an inactive wave of this item: nothing to fetch)
-    const __bf16* qb = qkv + (int64_t)it.s0 * RS + (int64_t)(hk_ * grp_total + hig) * D;
-#pragma unroll
-    for (int j = 0; j < QINST; ++j) {
-      const int s_ = j * 64 + lane;
-      const int row = s_ / G::CH, cs = s_ % G::CH;
-      const int grow = min(q0_ + row, it.len - 1);
-      __builtin_amdgcn_global_load_lds((gptr_t)(qb + (int64_t)grow * RS + ((cs ^ G::xk(row)) << 3)), (lptr_t)(sW + j * 1024), 16, 0, 0);
-    }
-  };
-  auto read_q = [&](bf16x8 (&dst)[KS]) {
-    int kb = koff0;
-    asm volatile("" : "+v"(kb));              // (not hoisted into KS loop-invariant registers)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) dst[ks] = *(const bf16x8*)(sW + (kb ^ (ks << 5)));
-  };
-
-  Walk wc = {0, 0, (int)blockIdx.x};
-  Item ic = next_item(wc);
-  if (ic.pair < 0) return;
-  bf16x8 qf[KS];
-  request_q(ic);
-  // prologue: two tiles of the stream in flight, the first one landed
-  const bool t0 = stage_next(), t1 = stage_next();
-  (void)t0;
-  if (t1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // waves without tile requests: the counted wait does not cover their Q block
-  __builtin_amdgcn_s_barrier();
-  read_q(qf);                                    // (requested before the first two tiles: landed with the counted wait above)
-  int cur = 0;
-
-  while (ic.pair >= 0) {
-  const Item inext = next_item(wc);
-  const int yy = ic.pair % ny;
-  const int hk = yy / nparts, part = yy - hk * nparts;
-  const int s0 = ic.s0, len = ic.len, qt = ic.qt;
-  const int qtile0 = qt * 64;
-  const int head_in_grp = part * GRP + (wave % GRP);
-  const int hq = hk * grp_total + min(head_in_grp, grp_total - 1);
-  const int q0 = qtile0 + (wave / GRP) * 32;
-  const bool active = q0 < len && head_in_grp < grp_total;
-
-  f32x16 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-    for (int t = 0; t < 16; ++t) o[dt][t] = 0.f;
-  float m = -1e30f, l = 0.f;
-
-  auto qk_product = [&](const char* kt_base, const bf16x8 (&qf_)[KS]) -> f32x16 {
-    bf16x8 kf[KS];
-    int kb = koff0;
-    asm volatile("" : "+v"(kb));
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) kf[ks] = *(const bf16x8*)(kt_base + (kb ^ (ks << 5)));
-    const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // inline-constant C operand
-    f32x16 acc = attn_mfma(kf[0], qf_[0], zero);
-#pragma unroll
-    for (int ks = 1; ks < KS; ++ks) acc = attn_mfma(kf[ks], qf_[ks], acc);
-    // (Round 3, measured and not kept: sched_group_barriers that put three fragment reads ahead of the MFMA chain and one read per MFMA
-    // after it -- left alone, hipcc walks the eight fragments of a head_dim-128 product through ONE register quad, read / lgkmcnt(0) / MFMA --
-    // 1.207 ms against 1.17-1.19: the second wave of the SIMD already covers those waits.)
-    return acc;
-  };
-  // lane <-> lane^32 exchange on the VALU (v_permlane32_swap) instead of an LDS round trip (ds_bpermute)
-  auto xhalf_max = [](float x) -> float {
-    auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  };
-  auto softmax_pv = [&](f32x16& s, const char* v_base, bool diag) {
-    // ---- V^T fragments: issued now (latency hides under the softmax VALU) as inline asm: the ds_read_tr builtin makes
-    //      hipcc drain ALL in-flight LDS-DMA (s_waitcnt vmcnt(0)) before every read, serialising the prefetch ring.
-    s16x4 vt[2][DT][2];
-    {
-      const uint32_t vb = (uint32_t)(uintptr_t)(lds_char_ptr)(v_base + 4 * h * G::ROW_BYTES);
-      int vo = voff0;
-      asm volatile("" : "+v"(vo));
-#pragma unroll
-      for (int sp = 0; sp < 2; ++sp)
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          const uint32_t a = vb + sp * 16 * G::ROW_BYTES + (vo ^ (dt << 6));
-          asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(vt[sp][dt][0]) : "v"(a));
-          asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(vt[sp][dt][1]) : "v"(a), "i"(8 * G::ROW_BYTES));
-        }
-    }
-    // ---- causal mask (diagonal sub-tile only: scalar branch); online softmax in the exp2 domain with the
-    //      1/sqrt(d)*log2(e) scale folded into the exponent FMA: p = exp2(s*c - m*c), m tracked on the raw scores
-    if (diag) {
-      const int lim = r - 4 * h;   // reg t holds key (t&3) + 8*(t>>2) + 4h (relative): masked iff that exceeds r
-#pragma unroll
-      for (int t = 0; t < 16; ++t) s[t] = ((t & 3) + 8 * (t >> 2) > lim) ? -1e30f : s[t];
-    }
-    float mloc = fmaxf(fmaxf(s[0], s[1]), s[2]);
-#pragma unroll
-    for (int t = 3; t < 15; t += 2) mloc = fmaxf(fmaxf(mloc, s[t]), s[t + 1]);
-    mloc = xhalf_max(fmaxf(mloc, s[15]));
-    // Lazy reference maximum: m moves only when the row maximum has outgrown it by more than LAZY_T in the exponent (a factor
-    // 2^LAZY_T on p); until then p = exp2((s - m) c) <= 2^LAZY_T stays far inside fp32 / bf16 range and alpha is EXACTLY 1, so the
-    // rescaling of the O accumulators (64 multiplies per sub-tile at d = 128, a third of the softmax VALU work) is skipped for
-    // the whole wave almost always after the first tile.  O / l is the same ratio whatever reference the exponentials use.
-    const bool grow = (mloc - m) * scale_log2 > LAZY_T;
-    const float mnew = grow ? mloc : m;
-    const float alpha = grow ? __builtin_amdgcn_exp2f((m - mnew) * scale_log2) : 1.0f;
-    m = mnew;
-    const float mc = -mnew * scale_log2;
-    {
-      const f32x2 c2 = {scale_log2, scale_log2}, m2 = {mc, mc};
-      f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-      for (int t = 0; t < 16; t += 2) {
-        f32x2 e = f32x2{s[t], s[t + 1]} * c2 + m2;
-        e[0] = __builtin_amdgcn_exp2f(e[0]);
-        e[1] = __builtin_amdgcn_exp2f(e[1]);
-        s[t] = e[0];
-        s[t + 1] = e[1];
-        ps2 += e;
-      }
-      l = l * alpha + (ps2[0] + ps2[1]);
-    }
-    if (!__all(alpha == 1.0f)) {  // wave-uniform: no q row of this wave raised its running max -> nothing to rescale (exact)
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) o[dt][t] *= alpha;
-    }
-    // ---- P^T -> bf16 B fragments: k-step sp uses regs 8sp .. 8sp+7
-    bf16x8 pf[2];
-#pragma unroll
-    for (int sp = 0; sp < 2; ++sp)
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) pf[sp][jj] = attn_cvt(s[8 * sp + jj]);
-    // ---- O^T += V^T P^T
-    if (DT == 2) {
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(vt[0][0][0]), "+v"(vt[0][0][1]), "+v"(vt[0][1][0]), "+v"(vt[0][1][1]), "+v"(vt[1][0][0]), "+v"(vt[1][0][1]),
-                     "+v"(vt[1][1][0]), "+v"(vt[1][1][1])
-                   :
-                   : "memory");
+      const int idx = w.jslot + w.kq * gs;
+      if (idx >= nqt) { ++w.step; w.kq = 0; continue; }
+      ++w.kq;
+      it = w.cur;
+      qt = (w.step & 1) ? idx : nqt - 1 - idx;
     } else {
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(vt[0][0][0]), "+v"(vt[0][0][1]), "+v"(vt[0][1][0]), "+v"(vt[0][1][1]), "+v"(vt[0][2 % DT][0]), "+v"(vt[0][2 % DT][1]),
-                     "+v"(vt[0][3 % DT][0]), "+v"(vt[0][3 % DT][1]), "+v"(vt[1][0][0]), "+v"(vt[1][0][1]), "+v"(vt[1][1][0]), "+v"(vt[1][1][1]),
-                     "+v"(vt[1][2 % DT][0]), "+v"(vt[1][2 % DT][1]), "+v"(vt[1][3 % DT][0]), "+v"(vt[1][3 % DT][1])
-                   :
-                   : "memory");
+      if (w.item >= n_items) return i32x4{0, 0, 0, 0};
+      it = attn_pair(cu, last_tile_only ? w.item : w.item % n_pairs, nkv, nparts);
+      qt = nqt - 1 - w.item / n_pairs;
+      w.item += n_wg;
     }
-#pragma unroll
-    for (int sp = 0; sp < 2; ++sp)
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-        u.s.a = vt[sp][dt][0]; u.s.b = vt[sp][dt][1];
-        o[dt] = attn_mfma(u.v, pf[sp], o[dt]);
-      }
-  };
-
-  const int nkt = qt + 1;
-  for (int kt = 0; kt < nkt; ++kt) {
-    if (kt == nkt - 1 && inext.pair >= 0) request_q(inext);     // the next item's Q block: requested a whole tile before it is used
-    const char* sK = smem + cur * (2 * G::TILE_BYTES);
-    const char* sV = sK + G::TILE_BYTES;
-    // Software pipeline inside the wave: the QK^T MFMAs of BOTH 32-key sub-tiles are issued first (K fragments read in
-    // one batch), so the second product runs on the matrix pipe while the VALU does the first sub-tile's softmax, and
-    // the first P.V runs under the second softmax.
-    const bool two = (kt * 64 + 32 <= q0);   // wave-uniform: second sub-tile not entirely above the diagonal
-    const bool more = stage_next();                              // tile (this + 2) of the stream, whichever item it belongs to
-    if (active) {
-      f32x16 s0_ = qk_product(sK, qf);
-      f32x16 s1_;
-      if (two) s1_ = qk_product(sK + 32 * G::ROW_BYTES, qf);
-      softmax_pv(s0_, sV, kt * 64 == q0);
-      if (two) softmax_pv(s1_, sV + 32 * G::ROW_BYTES, kt * 64 + 32 == q0);
-    }
-    if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");   // the next tile landed, the one after may stay in flight
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    cur = cur == NST - 1 ? 0 : cur + 1;
+    // last_tile_only: one q tile per sequence, the one holding its last token (all the pooled path needs of the last layer)
+    if (last_tile_only) qt = (it[1] - 1) >> 6;
+    if (it[1] <= 0 || qt * 64 >= it[1]) continue;    // (q tiles past a sequence's end are no items)
+    it[2] |= qt;
+    return it;
   }
-  // the staging block now holds the next item's Q rows (older than the tile the counted wait just covered): fragments out first,
-  // then the block is free for this item's O rows
-  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (see the prologue)
-  if (inext.pair >= 0) read_q(qf);
-  if (active) {
-    float ltot;
-    {
-      auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(l), __float_as_uint(l), false, false);
-      ltot = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
-    }
-    const float inv = 1.0f / ltot;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the Q fragment reads are done with the block
-    // O^T accumulators -> bf16 rows in the block: lane (r, h) owns row r, 4 consecutive columns dt*32 + 8*g + 4h; 16-B chunk index
-    // XOR (row mod chunks-per-row) keeps both the 8-byte writes and the 16-byte row reads off each other's banks
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4_ = 0; g4_ < 4; ++g4_) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = o16(o[dt][4 * g4_ + e] * inv, out_f16);
-        *(bf16x4*)(sW + r * G::ROW_BYTES + ((((dt * 4 + g4_) ^ (r & (G::CH - 1))) << 4) | (h << 3))) = v;
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // same wave wrote, same wave reads: no barrier
-    // Read-out: all QINST row segments into registers first, then QINST buffer stores through the sequence's descriptor (rows >= len fall
-    // outside num_records and are dropped: no branch per store).  The LDS addresses are recomputed from the lane id HERE (the empty asm
-    // keeps them from being hoisted out of the item loop): hoisted, four of them were spilled, and every scratch reload came with a
-    // vmcnt(0) that waited for the store issued just before it -- four serial store round trips, 6 us per item
-    // (tools/exp/attn_trace_tiled.py: 35 % of the launch at S = 512).
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (int64_t)s0 * ((int64_t)nq * D)), 0, len * nq * (D * 2), 0x00020000);
-    u32x4 ov[QINST];
-#pragma unroll
-    for (int j = 0; j < QINST; ++j) {
-      const int s_ = j * 64 + ln;
-      const int row = s_ / G::CH, ch = s_ % G::CH;
-      ov[j] = *(const u32x4*)(sW + row * G::ROW_BYTES + ((ch ^ (row & (G::CH - 1))) << 4));
-    }
-#pragma unroll
-    for (int j = 0; j < QINST; ++j) {
-      const int s_ = j * 64 + ln;
-      const int row = s_ / G::CH, ch = s_ % G::CH;
-      __builtin_amdgcn_raw_buffer_store_b128(ov[j], orsrc, ((q0 + row) * nq + hq) * (D * 2) + ch * 16, 0, 0);
-    }
-  }
-  ic = inext;
-  }  // items
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Round 5: the same tile arithmetic on a PREBUILT work list, with buffer addressing (lrx_attn_varlen_causal_items; 1.10 -> 1.00 ms at
-// 256 x 512 tokens, 32 / 8 heads, d = 128, bit-identical output: profiles/r05_attn_rework.txt).
-//
-// tools/exp/attn_trace_tiled.py on the kernel above: a 64-key tile step = 0.58 us of REQUESTING the next tile + 1.6 compute + 0.75
-// barrier + 0.28 loop, and an item paid another 3.7 us around its steps -- 1.5 of them in the item walker (runtime integer divisions for
-// (sequence, kv head, part, q tile), two dependent scalar loads of cu[], once per walker) and the per-lane 64-bit source addresses of
-// 4 + 8 LDS-DMA instructions (row clamp, multiply by the row stride, swizzle): VALU work that the two waves of a SIMD pay for one after
-// the other.  PMC (tools/pmc_attn.sh): 202 VALU instructions per 32 x 32 sub-tile against 16 MFMAs, VALU issue 50 % + MFMA 32 % of the
-// SIMD cycles at an effective 1.65 GHz -- the kernel is bound by what it issues, so this one issues less:
-//   * the items of every workgroup are written once per (cu_seqlens, geometry) by k_attn_build_items as 16-byte records; the stream and
-//     the compute side fetch them with one s_load_dwordx4 each, one item ahead of use;
-//   * K, V and Q rows are fetched with buffer_load_dwordx4 ... lds through a descriptor whose base is the tile's first row and whose
-//     num_records ends at the sequence's last row: rows past the end are dropped by the range check (no clamp), the per-lane offsets
-//     (row * stride + swizzled chunk) are kernel constants, the kv-head column goes into the scalar offset: a tile request is a
-//     descriptor update on the SALU plus the load instructions;
-//   * the LDS addresses of the 24 fragment reads of a sub-tile are kernel constants plus the ring-stage base, sub-tile / half / k-step
-//     offsets ride in the instructions' immediate fields (48 of the 202 were v_xor + v_add pairs in front of those reads);
-//   * the output addresses are recomputed from the hardware lane counter inside the item epilogue: nothing lane-derived is live across
-//     the tile loop, hipcc spills nothing (a reload there waits, with its vmcnt(0), for the tile requests in flight).
-// LDS is zero-filled once per workgroup: a dropped row leaves its ring bytes alone, and P = 0 times a stale NaN would poison O.
-// ---------------------------------------------------------------------------------------------------------------
-// (a free __device__ function: called from a lambda of the kernel, the host pass of hipcc drops the whole kernel stub without a diagnostic)
-__device__ __forceinline__ void attn_buf_load_lds16(__amdgpu_buffer_rsrc_t rs, lptr_t dst, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff, soff, 0, 0);
-}
-typedef __attribute__((ext_vector_type(4))) int i32x4;   // one item: {first token, length, q tile | part << 16, kv head}; length 0 ends a workgroup's list
 // The work list: int32 list_start[n_wg + 1] (padded to a multiple of 4 entries), then the workgroups' item lists back to back, each ended by a
-// zero item.  Only items that exist are stored (q tiles past a sequence's end are dropped here), so the list is bounded by
-// (total_tokens / 64 + n_seqs) x kv heads x parts + one end marker per workgroup -- known from the batch size alone.
-// One block, one thread per workgroup: count its items (the walker of k_attn_varlen_causal), scan, walk again and store.
-
+// zero item.  Only items that exist are stored, so the list is bounded by (total_tokens / 64 + n_seqs) x kv heads x parts + one end marker per
+// workgroup -- known from the batch size alone.
+// One block, one thread per workgroup: count its items, scan, walk again and store.
 __global__ void __launch_bounds__(1024)
 k_attn_build_items(const int32_t* __restrict__ cu, int32_t* __restrict__ list_start, i32x4* __restrict__ items, int cap_items, int n_wg, int nqt, int nkv,
                    int nparts, int n_seqs, int n_items, int gs, int last_tile_only, int* __restrict__ overflow) {
   __shared__ int s_scan[1024];
   const int b = threadIdx.x;
-  const int ny = nkv * nparts, n_pairs = n_seqs * ny;
-  const int xcd = b & 7, slot = b >> 3;
-  const int g4 = gs > 0 ? slot / gs : 0, jslot = gs > 0 ? slot % gs : 0, gpx = gs > 0 ? (n_wg >> 3) / gs : 1;
   auto walk = [&](i32x4* dst) -> int {          // dst == nullptr: count only
-    int n = 0;
-    auto emit = [&](int pair, int qt_sel) {
-      const int sq = pair / ny;
-      const int s0 = cu[sq], len = cu[sq + 1] - s0;
-      const int qt = last_tile_only ? ((len - 1) >> 6) : qt_sel;      // last_tile_only: the q tile holding the sequence's last token
-      if (len <= 0 || qt * 64 >= len) return;
-      if (dst) {
-        const int yy = pair - sq * ny, hk = yy / nparts, part = yy - hk * nparts;
-        dst[n] = i32x4{s0, len, qt | (part << 16), hk};
-      }
-      ++n;
-    };
-    if (gs > 0) {
-      // (the order is explained at k_attn_varlen_causal: the q tiles of one (sequence, kv head) on `gs` workgroups of one XCD; slot j of a
-      // group takes q tiles j, j + gs, ... from the long end on even steps and from the short end on odd ones)
-      for (int step = 0;; ++step) {
-        const int v = step * gpx + g4;
-        if ((v / nparts) * 8 >= n_pairs / nparts) break;
-        const int pair = ((v / nparts) * 8 + xcd) * nparts + v % nparts;
-        if (pair >= n_pairs) continue;
-        for (int idx = jslot; idx < nqt; idx += gs) emit(pair, (step & 1) ? idx : nqt - 1 - idx);
-      }
-    } else {
-      for (int item = b; item < n_items; item += n_wg)
-        emit(last_tile_only ? item : item % n_pairs, last_tile_only ? 0 : nqt - 1 - item / n_pairs);
+    AttnWalk w = attn_walk_start(b, n_wg, gs);
+    for (int n = 0;; ++n) {
+      const i32x4 it = attn_next_item(w, cu, n_wg, nqt, nkv, nparts, n_seqs, n_items, gs, last_tile_only);
+      if (it[1] == 0) return n;
+      if (dst) dst[n] = it;
     }
-    return n;
   };
   const int mine = b < n_wg ? walk(nullptr) + 1 : 0;            // + the end marker
   s_scan[b] = mine;
@@ -516,29 +163,78 @@ k_attn_build_items(const int32_t* __restrict__ cu, int32_t* __restrict__ list_st
   if (b == n_wg - 1) { items[start + n + 1] = i32x4{0, 0, 0, 0}; items[start + n + 2] = i32x4{0, 0, 0, 0}; }   // padding behind the last end marker
 }
 
-template <int D, int GRP>
+// ---------------------------------------------------------------------------------------------------------------
+// The tiled kernel: persistent workgroups, one per CU-slot, each computes its items one after the other.  (A 96-KiB-LDS workgroup is alone
+// on its CU; with one item per workgroup the CU sat empty a third of the time between a workgroup's exit and its successor's first
+// instruction -- PMC: 64 workgroups x 18 us of wave lifetime per CU in a 1.85 ms launch.)
+// The K/V tiles of all the items of a workgroup form ONE stream through the ring: the prefetch runs two tiles ahead of the compute across
+// item boundaries, and the next item's Q fragments are requested during the current item's last tile -- an item boundary costs no load
+// latency.  The items come from one of two sources, fixed at compile time: the prebuilt list (lrx_attn_varlen_causal_items: one
+// s_load_dwordx4 per item) or, WALK, attn_next_item run by the kernel itself (lrx_attn_varlen_causal, no scratch memory).  Either way the
+// compute and the prefetch side each keep their own cursor, one item ahead of use, and every value of an item is wave-uniform.
+//
+// Round 5 rewrote the tile loop for fewer issued instructions (1.10 -> 1.00 ms at 256 x 512 tokens, 32 / 8 heads, d = 128, bit-identical
+// output: profiles/r05_attn_rework.txt).  tools/exp/attn_trace_tiled.py on the kernel before it: a 64-key tile step = 0.58 us of REQUESTING
+// the next tile + 1.6 compute + 0.75 barrier + 0.28 loop, and an item paid another 3.7 us around its steps -- 1.5 of them in the item walker
+// (runtime integer divisions for (sequence, kv head, part, q tile), two dependent scalar loads of cu[], once per walker) and the per-lane
+// 64-bit source addresses of 4 + 8 LDS-DMA instructions (row clamp, multiply by the row stride, swizzle): VALU work that the two waves of a
+// SIMD pay for one after the other.  PMC (tools/pmc_attn.sh): 202 VALU instructions per 32 x 32 sub-tile against 16 MFMAs, VALU issue 50 % +
+// MFMA 32 % of the SIMD cycles at an effective 1.65 GHz -- the kernel is bound by what it issues, so this one issues less:
+//   * the items of every workgroup are written once per (cu_seqlens, geometry) by k_attn_build_items as 16-byte records; the stream and
+//     the compute side fetch them with one s_load_dwordx4 each, one item ahead of use (the list-less launch walks them there instead);
+//   * K, V and Q rows are fetched with buffer_load_dwordx4 ... lds through a descriptor whose base is the tile's first row and whose
+//     num_records ends at the sequence's last row: rows past the end are dropped by the range check (no clamp), the per-lane offsets
+//     (row * stride + swizzled chunk) are kernel constants, the kv-head column goes into the scalar offset: a tile request is a
+//     descriptor update on the SALU plus the load instructions;
+//   * the LDS addresses of the 24 fragment reads of a sub-tile are kernel constants plus the ring-stage base, sub-tile / half / k-step
+//     offsets ride in the instructions' immediate fields (48 of the 202 were v_xor + v_add pairs in front of those reads);
+//   * the output addresses are recomputed from the hardware lane counter inside the item epilogue: nothing lane-derived is live across
+//     the tile loop, hipcc spills nothing (a reload there waits, with its vmcnt(0), for the tile requests in flight).
+// LDS is zero-filled once per workgroup: a dropped row leaves its ring bytes alone, and P = 0 times a stale NaN would poison O.
+// ---------------------------------------------------------------------------------------------------------------
+// (a free __device__ function: called from a lambda of the kernel, the host pass of hipcc drops the whole kernel stub without a diagnostic)
+__device__ __forceinline__ void attn_buf_load_lds16(__amdgpu_buffer_rsrc_t rs, lptr_t dst, int voff, int soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff, soff, 0, 0);
+}
+
+template <int D, int GRP, bool WALK>
 __global__ void __launch_bounds__(128 * GRP)
 k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_start, const i32x4* __restrict__ items, int nq, int nkv,
-              __bf16* __restrict__ out, float scale_log2, int out_f16) {
+              __bf16* __restrict__ out, float scale_log2, int out_f16,
+              const int32_t* __restrict__ cu, int nqt, int nparts, int n_seqs, int n_items, int gs, int last_tile_only) {   // (WALK only)
   using G = AttnGeom<D>;
   constexpr int NW = 2 * GRP;
-  constexpr int KS = D / 16, DT = D / 32;
+  constexpr int KS = D / 16, DT = D / 32;   // k-steps of the QK^T product, 32-row tiles of O^T
+  // K/V ring: 3 stages with a counted vmcnt (two tiles in flight; a tile's compute, ~0.5 us, is shorter than the load
+  // latency, so one tile of prefetch leaves every barrier waiting on HBM).
+  // The first DW waves (a divisor of the instruction count, e.g. 8 of the 12 waves of a GQA-6 group) issue the LDS-DMA, the same
+  // number each, so the counted wait is one immediate for everybody (waves without loads have nothing outstanding).
+  // (Tried: running the workgroup's two halves half a tile apart, two barriers per tile, so that one half's softmax sits beside
+  // the other's MFMAs -- 1.143 -> 1.173 ms at d = 128: the loop is not bound by that pairing, see the ablation in DESIGN.md.)
   constexpr int DW = attn_dma_waves(G::INSTS, NW);
   constexpr int NST = 3;
-  constexpr int PER_TILE = 2 * (G::INSTS / DW);
+  constexpr int PER_TILE = 2 * (G::INSTS / DW);  // LDS-DMA instructions per issuing wave per tile (K + V)
+  // Per-wave staging block (32 rows x D bf16, private to the wave): the wave's Q rows arrive in it by LDS-DMA (whole 2D-byte row
+  // segments per request instead of 32 rows x 32 B per load instruction) and its O rows leave through it (16 B per lane, whole
+  // row segments per store instruction instead of 32 rows x 16 B).  Ablation at d = 128: the 8-byte-piece stores cost 0.20 ms and
+  // the row-gather Q loads 0.16 ms of a 1.25 ms launch.
   constexpr int QO_BYTES = 32 * G::ROW_BYTES;
-  constexpr int QINST = QO_BYTES / 1024;
+  constexpr int QINST = QO_BYTES / 1024;         // LDS-DMA instructions per Q block
   constexpr int SMEM = NST * 2 * G::TILE_BYTES + NW * QO_BYTES;
+  static_assert(NST * 2 * G::TILE_BYTES <= 96 * 1024, "K/V ring");
   __shared__ __attribute__((aligned(1024))) char smem[SMEM];  // [stage][K|V] | [wave] Q/O block
 
   const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform: branches on it stay scalar
   const int r = lane & 31, h = lane >> 5;
   const int RSB = (nq + 2 * nkv) * (D * 2);          // bytes per token row of q|k|v
   const int grp_total = nq / nkv;
-  const i32x4* const lst = items + list_start[blockIdx.x];
+  const i32x4* const lst = WALK ? nullptr : items + list_start[blockIdx.x];
+  auto walk = [&](AttnWalk& w) { return attn_next_item(w, cu, gridDim.x, nqt, nkv, nparts, n_seqs, n_items, gs, last_tile_only); };
+  AttnWalk wc = attn_walk_start(blockIdx.x, gridDim.x, gs);   // (WALK) the compute side's walk
 
-  i32x4 ic = lst[0];
+  i32x4 ic;
+  if constexpr (WALK) ic = walk(wc); else ic = lst[0];
   if (ic[1] == 0) return;
   for (int i = tid * 16; i < SMEM; i += 128 * GRP * 16) *(u32x4*)(smem + i) = u32x4{0u, 0u, 0u, 0u};
   __syncthreads();
@@ -568,20 +264,25 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
       attn_buf_load_lds16(rs, (lptr_t)(sV + j * 1024), voffV[jj], soV);
     }
   };
-  // prefetch side of the stream: its own cursor over the list, the record after the current one already loaded
-  // prefetch side of the stream: its own index into the list, the item after the current one already loaded (a load past the list's
-  // end marker reads the next workgroup's first item or the builder's padding: never used)
+  // prefetch side of the stream: its own cursor (index into the list, or walk), the item after the current one already fetched (a list load
+  // past the end marker reads the next workgroup's first item or the builder's padding, a walk past its end yields end items: never used)
   int pi = 0;
-  i32x4 ip = ic, ipn = lst[1];
-  int ktp = 0, sp_ = 0;
+  AttnWalk wp = wc;
+  i32x4 ip = ic, ipn;
+  if constexpr (WALK) ipn = walk(wp); else ipn = lst[1];
+  int ktp = 0, sp_ = 0;                      // next tile of ip to request, ring slot it goes to
   auto stage_next = [&]() -> bool {
     if (ip[1] == 0) return false;
     stage(sp_, ip, ktp);
     sp_ = sp_ == NST - 1 ? 0 : sp_ + 1;
-    if (++ktp > (ip[2] & 0xffff)) { ip = ipn; ++pi; ipn = lst[pi + 1]; ktp = 0; }
+    if (++ktp > (ip[2] & 0xffff)) { ip = ipn; ++pi; if constexpr (WALK) ipn = walk(wp); else ipn = lst[pi + 1]; ktp = 0; }
     return true;
   };
 
+  // ---- lane-constant LDS read offsets (both swizzles are XORs of the 16-B chunk index, and the chunk's own k-step / d-tile bits are
+  //      disjoint from the rest: the other k-steps / d tiles are these XOR a constant)
+  // K row read: row (sub*32 + r), logical chunk 2ks + h;  V transposed read: 16-lane group g = lane>>4, i = lane&15, qd = i>>2, p = i&3;
+  // block row = key_base + qd, columns dt*32 + 16*(g&1) + 4p .. +3  ->  logical chunk dt*4 + 2*(g&1) + (p>>1), byte 8*(p&1) inside it
   const int koff0 = r * G::ROW_BYTES + ((h ^ G::xk(r)) << 4);
   int voff0;
   {
@@ -589,15 +290,16 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
     voff0 = qd * G::ROW_BYTES + (((2 * (g & 1) + (p >> 1)) ^ G::xv(qd)) << 4) + 8 * (p & 1);
   }
 
-  // Q block of an item for this wave (rows q0 .. q0 + 31 of its head, K-tile swizzle): instruction j covers rows j*RPI .. + RPI - 1, and
-  // x(j*RPI + row) = x(j*RPI) ^ x(row) for both geometries (the two terms use disjoint bits), so its offsets are vq0 ^ const + const
+  // Q block of an item for this wave (rows q0 .. q0 + 31 of its head, K-tile swizzle, so the fragment reads are the K row reads: koff0;
+  // fragments Q[q0 + r][16 ks + 8 h .. +7], the B operand): instruction j covers rows j*RPI .. + RPI - 1, and x(j*RPI + row) = x(j*RPI) ^
+  // x(row) for both geometries (the two terms use disjoint bits), so its offsets are vq0 ^ const + const
   char* const sW = smem + NST * 2 * G::TILE_BYTES + wave * QO_BYTES;
   auto request_q = [&](const i32x4& it) {
     constexpr int RPI = G::ROWS_PER_INST;
     const int qt_ = it[2] & 0xffff, part_ = it[2] >> 16;
     const int hig = part_ * GRP + (wave % GRP);
     const int q0_ = qt_ * 64 + (wave / GRP) * 32;
-    if (q0_ >= it[1] || hig >= grp_total) return;
+    if (q0_ >= it[1] || hig >= grp_total) return;           // (an inactive wave of this item: nothing to fetch)
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)qkv + (int64_t)(it[0] + q0_) * RSB), 0, (it[1] - q0_) * RSB, 0x00020000);
     const int so = (it[3] * grp_total + hig) * (D * 2);
 #pragma unroll
@@ -606,7 +308,7 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
   };
   auto read_q = [&](bf16x8 (&dst)[KS]) {
     int kb = koff0;
-    asm volatile("" : "+v"(kb));
+    asm volatile("" : "+v"(kb));              // (not hoisted into KS loop-invariant registers)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) dst[ks] = *(const bf16x8*)(sW + (kb ^ (ks << 5)));
   };
@@ -614,18 +316,20 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
   int ci = 0;
   bf16x8 qf[KS];
   request_q(ic);
+  // prologue: two tiles of the stream in flight, the first one landed
   const bool t0 = stage_next(), t1 = stage_next();
   (void)t0;
   if (t1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // waves without tile requests: the counted wait does not cover their Q block
   __builtin_amdgcn_s_barrier();
-  read_q(qf);
+  read_q(qf);                                    // (requested before the first two tiles: landed with the counted wait above)
   int cur = 0;
 
   while (ic[1] != 0) {
   ++ci;
-  const i32x4 inext = lst[ci];
+  i32x4 inext;
+  if constexpr (WALK) inext = walk(wc); else inext = lst[ci];
   const int s0 = ic[0], len = ic[1], qt = ic[2] & 0xffff, part = ic[2] >> 16, hk = ic[3];
   const int qtile0 = qt * 64;
   const int head_in_grp = part * GRP + (wave % GRP);
@@ -665,14 +369,18 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
     f32x16 acc = attn_mfma(kf[0], qf[0], zero);
 #pragma unroll
     for (int ks = 1; ks < KS; ++ks) acc = attn_mfma(kf[ks], qf[ks], acc);
+    // (Round 3, measured and not kept: sched_group_barriers that put three fragment reads ahead of the MFMA chain and one read per MFMA
+    // after it -- left alone, hipcc walks the eight fragments of a head_dim-128 product through ONE register quad, read / lgkmcnt(0) / MFMA --
+    // 1.207 ms against 1.17-1.19: the second wave of the SIMD already covers those waits.)
     return acc;
   };
+  // lane <-> lane^32 exchange on the VALU (v_permlane32_swap) instead of an LDS round trip (ds_bpermute)
   auto xhalf_max = [](float x) -> float {
     auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(rr[0]), __uint_as_float(rr[1]));
   };
-  // (the sub-tile arithmetic below is the one documented at k_attn_varlen_causal: V^T fragments by inline-asm transposing reads, lazy
-  // reference maximum, exp2 with the scale folded in, P^T as the B operand of the second product)
+  // ---- V^T fragments of sub-tile u, issued before its softmax (latency hides under the softmax VALU) as inline asm: the ds_read_tr builtin
+  //      makes hipcc drain ALL in-flight LDS-DMA (s_waitcnt vmcnt(0)) before every read, serialising the prefetch ring
   struct VFrag { s16x4 v[2][DT][2]; };
   auto read_v = [&](int u, VFrag& f) {
 #pragma unroll
@@ -704,7 +412,7 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
                    : "memory");
     }
   };
-  auto pv = [&](const VFrag& f, const bf16x8 (&pf)[2]) {
+  auto pv = [&](const VFrag& f, const bf16x8 (&pf)[2]) {     // O^T += V^T P^T
 #pragma unroll
     for (int sp = 0; sp < 2; ++sp)
 #pragma unroll
@@ -722,12 +430,17 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
         for (int t = 0; t < 16; ++t) o[dt][t] *= alpha;
     }
   };
-  // scores -> P^T fragments; returns the factor the O accumulators are due BEFORE this sub-tile's P.V is added
   auto mask_diag = [&](f32x16& s) {          // causal mask of a sub-tile on the diagonal: reg t holds key (t&3) + 8*(t>>2) + 4h (relative), masked iff that exceeds r
     const int lim = r - 4 * h;
 #pragma unroll
     for (int t = 0; t < 16; ++t) s[t] = ((t & 3) + 8 * (t >> 2) > lim) ? -1e30f : s[t];
   };
+  // scores -> P^T fragments; returns the factor the O accumulators are due BEFORE this sub-tile's P.V is added.  Online softmax in the exp2
+  // domain with the 1/sqrt(d)*log2(e) scale folded into the exponent FMA: p = exp2(s*c - m*c), m tracked on the raw scores.
+  // Lazy reference maximum: m moves only when the row maximum has outgrown it by more than LAZY_T in the exponent (a factor 2^LAZY_T on p);
+  // until then p = exp2((s - m) c) <= 2^LAZY_T stays far inside fp32 / bf16 range and alpha is EXACTLY 1, so the rescaling of the O
+  // accumulators (64 multiplies per sub-tile at d = 128, a third of the softmax VALU work) is skipped for the whole wave almost always after
+  // the first tile.  O / l is the same ratio whatever reference the exponentials use.
   auto softmax = [&](f32x16& s, bf16x8 (&pf)[2]) -> float {
     float mloc = fmaxf(fmaxf(s[0], s[1]), s[2]);
 #pragma unroll
@@ -753,7 +466,7 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
       l = l * alpha + (ps2[0] + ps2[1]);
     }
 #pragma unroll
-    for (int sp = 0; sp < 2; ++sp)
+    for (int sp = 0; sp < 2; ++sp)           // P^T -> 16-bit B fragments: k-step sp uses regs 8sp .. 8sp+7
 #pragma unroll
       for (int jj = 0; jj < 8; ++jj) pf[sp][jj] = attn_cvt(s[8 * sp + jj]);
     return alpha;
@@ -761,11 +474,13 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
 
   const int nkt = qt + 1;
   for (int kt = 0; kt < nkt; ++kt) {
-    if (kt == nkt - 1 && inext[1] != 0) request_q(inext);
+    if (kt == nkt - 1 && inext[1] != 0) request_q(inext);     // the next item's Q block: requested a whole tile before it is used
     const bool two = (kt * 64 + 32 <= q0);   // wave-uniform: second sub-tile not entirely above the diagonal
-    const bool more = stage_next();
+    const bool more = stage_next();                              // tile (this + 2) of the stream, whichever item it belongs to
     if (active) {
-      // Both QK^T products first, each sub-tile's V^T fragments requested before its softmax.  Measured on this kernel and not kept
+      // Software pipeline inside the wave: the QK^T MFMAs of BOTH 32-key sub-tiles first (K fragments read in one batch), so the second
+      // product runs on the matrix pipe while the VALU does the first sub-tile's softmax, and the first P.V runs under the second softmax.
+      // Measured on this kernel and not kept
       // (tools/exp/README.md, round 5; 0.978 ms as it stands): the two row halves of a head -- the two waves of a SIMD -- walking the
       // sub-tiles in different orders so that one's LDS phases meet the other's VALU phases (+4 %); all eight K fragments in registers before
       // the first MFMA (+2 %); one branch-poor copy of this code in which hipcc does put the first softmax between the MFMAs of the second
@@ -790,13 +505,15 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
         pv(vf, pf);
       }
     }
-    if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");
+    if (more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");   // the next tile landed, the one after may stay in flight
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     cur = cur == NST - 1 ? 0 : cur + 1;
   }
-  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // the staging block now holds the next item's Q rows (older than the tile the counted wait just covered): fragments out first,
+  // then the block is free for this item's O rows
+  if (DW < NW && wave >= DW) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (see the prologue)
   if (inext[1] != 0) read_q(qf);
   if (active) {
     float ltot;
@@ -805,7 +522,7 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
       ltot = __uint_as_float(rr[0]) + __uint_as_float(rr[1]);
     }
     const float inv = 1.0f / ltot;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the Q fragment reads are done with the block
     // the lane id from the hardware counter, behind a volatile zero: every address below is recomputed HERE.  Derived from threadIdx they
     // are values live across the whole kernel, hipcc (at its 256 VGPRs) spills some, and a reload here comes with a vmcnt(0) that waits
     // for the tile requests in flight
@@ -813,6 +530,8 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
     asm volatile("v_mov_b32 %0, 0" : "=v"(zero_));
     const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero_));
     const unsigned r_ = ln & 31, h_ = ln >> 5;
+    // O^T accumulators -> 16-bit rows in the block: lane (r, h) owns row r, 4 consecutive columns dt*32 + 8*g + 4h; 16-B chunk index
+    // XOR (row mod chunks-per-row) keeps both the 8-byte writes and the 16-byte row reads off each other's banks
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -822,7 +541,9 @@ k_attn_stream(const __bf16* __restrict__ qkv, const int32_t* __restrict__ list_s
         for (int e = 0; e < 4; ++e) v[e] = o16(o[dt][4 * g4_ + e] * inv, out_f16);
         *(bf16x4*)(sW + r_ * G::ROW_BYTES + ((((dt * 4 + g4_) ^ (r_ & (G::CH - 1))) << 4) | (h_ << 3))) = v;
       }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // same wave wrote, same wave reads: no barrier
+    // read-out: all QINST row segments into registers first, then QINST buffer stores through the sequence's descriptor (rows >= len fall
+    // outside num_records and are dropped: no branch per store)
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (int64_t)s0 * ((int64_t)nq * D)), 0, len * nq * (D * 2), 0x00020000);
     u32x4 ov[QINST];
 #pragma unroll
@@ -872,7 +593,7 @@ k_attn_resident64(const __bf16* __restrict__ qkv, const int32_t* __restrict__ cu
   const int64_t RS = (int64_t)(nq + 2 * nkv) * D;
   const int grp = nq / nkv;
   // persistent workgroups (one per CU: 128 KiB of LDS) walk the (sequence, kv head) pairs: a workgroup's successor used to start
-  // ~10 us after its exit (see k_attn_varlen_causal)
+  // ~10 us after its exit (see k_attn_stream)
   for (int pair = blockIdx.x; pair < n_pairs; pair += gridDim.x) {
   const int b = pair / nkv, hk = pair - b * nkv;
   const int s0 = cu[b], len = cu[b + 1] - s0;
@@ -982,7 +703,7 @@ k_attn_resident64(const __bf16* __restrict__ qkv, const int32_t* __restrict__ cu
         auto rr = __builtin_amdgcn_permlane32_swap(__float_as_uint(mloc), __float_as_uint(mloc), false, false);
         mloc = fmaxf(__uint_as_float(rr[0]), __uint_as_float(rr[1]));
       }
-      const bool grow = (mloc - m) * scale_log2 > LAZY_T;     // lazy reference maximum: see k_attn_varlen_causal
+      const bool grow = (mloc - m) * scale_log2 > LAZY_T;     // lazy reference maximum: see k_attn_stream
       const float mnew = grow ? mloc : m;
       const float alpha = grow ? __builtin_amdgcn_exp2f((m - mnew) * scale_log2) : 1.0f;
       m = mnew;
@@ -1441,48 +1162,29 @@ static int attn_cu_count() {
   return n;
 }
 
-template <int D, int GRP>
-static int launch_attn(const void* qkv, const int32_t* cu, int n_seqs, int max_seqlen, int nq, int nkv, void* out, int last_tile_only,
-                       hipStream_t s, int nparts, int out_f16) {
-  int nqt = (int)lrx_cdiv(max_seqlen, 64);
-  float scale_log2 = (1.0f / sqrtf((float)D)) * 1.4426950408889634f;
-  const int64_t n_items = (int64_t)(last_tile_only ? n_seqs : n_seqs * nqt) * nkv * nparts;
-  LRX_CHECK_ARG(n_items < (1ll << 31), "attn: %lld work items", (long long)n_items);
-  // persistent workgroups, as many as the chip keeps resident at once: the d = 128 ring (96 KiB) and the 256-VGPR budget admit one
-  // per CU; d = 64 workgroups are small enough for more (2-stage 32-KiB rings), so they get a slot count that covers that
-  const int n_cu = attn_cu_count();
-  const int per_cu = D == 128 ? 1 : (GRP <= 2 ? 4 : 2);
-  const int64_t slots = (int64_t)n_cu * per_cu;
-  // grouped item list (see the kernel): needs a full grid that splits evenly over the 8 XCDs; gs = slots of one XCD that share a
-  // pair's K/V = the largest power of two <= min(q tiles, slots per XCD)
-  int gs = 0;
-  if (!last_tile_only && n_items >= slots && slots % 8 == 0) {
-    const int spx = (int)(slots / 8);
-    gs = 1;
-    while (gs * 2 <= nqt && gs * 2 <= spx && spx % (gs * 2) == 0) gs *= 2;
-  }
-  hipLaunchKernelGGL((k_attn_varlen_causal<D, GRP>), dim3((unsigned)(n_items < slots ? n_items : slots)), dim3(128 * GRP), 0, s,
-                     (const __bf16*)qkv, cu, nqt, nq, nkv, (__bf16*)out, scale_log2, last_tile_only, nparts, n_seqs, (int)n_items, gs, out_f16);
-  LRX_LAUNCH_CHECK();
-  return LRX_OK;
-}
-
-// ---- the item-list kernel: plan (shared by the list size, the list builder and the launch), builder, launch
+// ---- the tiled kernel: plan (shared by the list size, the list builder and both launches), builder, launch
 struct AttnPlan { int grp, nparts, nqt, gs, n_wg, slots; int64_t n_items; };
 static AttnPlan attn_plan(int n_seqs, int max_seqlen, int nq, int nkv, int head_dim, int last_tile_only) {
   AttnPlan p;
   const int g = nq / nkv;
+  // GRP q heads per workgroup, nparts workgroups per kv head (heads beyond the group idle).  head_dim 64 takes up to 8 heads per workgroup;
+  // head_dim 128 needs ~190 VGPRs per wave, so at most 4 (more than 8 waves per workgroup would spill): groups of 5-6 heads run as two
+  // workgroups of 3, 7-8 as two of 4 (the K/V tiles are staged twice, from L2), larger groups as ceil(grp/4).
   if (head_dim == 64) { p.grp = g <= 8 ? g : 8; p.nparts = g <= 8 ? 1 : (g + 7) / 8; }
   else if (g <= 4) { p.grp = g; p.nparts = 1; }
   else if (g <= 6) { p.grp = 3; p.nparts = 2; }
   else { p.grp = 4; p.nparts = (g + 3) / 4; }
   p.nqt = (int)lrx_cdiv(max_seqlen, 64);
   p.n_items = (int64_t)(last_tile_only ? n_seqs : (int64_t)n_seqs * p.nqt) * nkv * p.nparts;
+  // persistent workgroups, as many as the chip keeps resident at once: the d = 128 ring (96 KiB) and the 256-VGPR budget admit one
+  // per CU; d = 64 workgroups are small enough for more
   const int per_cu = head_dim == 128 ? 1 : (p.grp <= 2 ? 4 : 2);
   // (at most 1024 workgroups: the list builder is ONE 1024-thread block with a thread per workgroup -- 256 CUs x 4 on MI355X is exactly
   // that; a part with more CUs runs the same persistent walk on 1024 of its slots instead of failing)
   const int64_t slots_chip = (int64_t)attn_cu_count() * per_cu;
   const int64_t slots = slots_chip < 1024 ? slots_chip : 1024;
+  // grouped items (attn_next_item): need a full grid that splits evenly over the 8 XCDs; gs = slots of one XCD that share a pair's K/V =
+  // the largest power of two <= min(q tiles, slots per XCD)
   p.gs = 0;
   if (!last_tile_only && p.n_items >= slots && slots % 8 == 0) {
     const int spx = (int)(slots / 8);
@@ -1564,16 +1266,24 @@ static int launch_resident64(const void* qkv, const int32_t* cu_seqlens, int n_s
   LRX_LAUNCH_CHECK();
   return LRX_OK;
 }
+extern "C" int lrx_attn_varlen_causal(const void* qkv, const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens,
+                                      int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out,
+                                      int32_t last_tile_only, void* stream) {
+  return lrx_attn_varlen_causal_ex(qkv, cu_seqlens, nullptr, 0, n_seqs, total_tokens, max_seqlen, num_q_heads, num_kv_heads, head_dim, out,
+                                   last_tile_only, 0, stream);
+}
 extern "C" int lrx_attn_varlen_causal_items(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs,
                                             int32_t total_tokens, int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
                                             void* out, int32_t last_tile_only, void* stream) {
-  return lrx_attn_varlen_causal_items_ex(qkv, cu_seqlens, items, items_bytes, n_seqs, total_tokens, max_seqlen, num_q_heads, num_kv_heads, head_dim, out,
-                                         last_tile_only, 0, stream);
+  LRX_CHECK_ARG(items != nullptr, "attn: no work list (lrx_attn_varlen_causal is the launch without one)");
+  return lrx_attn_varlen_causal_ex(qkv, cu_seqlens, items, items_bytes, n_seqs, total_tokens, max_seqlen, num_q_heads, num_kv_heads, head_dim, out,
+                                   last_tile_only, 0, stream);
 }
+// items == nullptr: the tiled kernel walks its items itself (attn_next_item), otherwise it reads them from the list lrx_attn_build_items wrote.
 // (out_f16 != 0: the output rows are written as fp16 -- the O-projection's operand under lrx_encoder_config.precise_stream = 2)
-int lrx_attn_varlen_causal_items_ex(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs, int32_t total_tokens,
-                                    int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out, int32_t last_tile_only,
-                                    int out_f16, void* stream) {
+int lrx_attn_varlen_causal_ex(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs, int32_t total_tokens,
+                              int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out, int32_t last_tile_only,
+                              int out_f16, void* stream) {
   int rc = attn_check_layout(num_q_heads, num_kv_heads, head_dim);
   if (rc) return rc;
   LRX_CHECK_ARG(max_seqlen > 0 || total_tokens == 0, "attn: max_seqlen must be > 0");
@@ -1581,16 +1291,26 @@ int lrx_attn_varlen_causal_items_ex(const void* qkv, const int32_t* cu_seqlens, 
   const int nq = num_q_heads, nkv = num_kv_heads;
   hipStream_t s = (hipStream_t)stream;
   if (attn_uses_resident64(head_dim, max_seqlen, last_tile_only)) return launch_resident64(qkv, cu_seqlens, n_seqs, nq, nkv, out, s, out_f16);
-  const AttnPlan p = attn_plan(n_seqs, max_seqlen, nq, nkv, head_dim, last_tile_only);
-  const size_t need = attn_list_hdr_bytes(p) + 16 * (size_t)attn_list_item_bound(p, n_seqs, total_tokens, nkv, last_tile_only);
-  LRX_CHECK_ARG(items != nullptr && items_bytes >= need, "attn: work list %zu B < required %zu B", items_bytes, need);
   // (a sequence's rows are addressed through one buffer descriptor: 32-bit byte offsets)
-  LRX_CHECK_ARG((int64_t)max_seqlen * (nq + 2 * nkv) * head_dim * 2 < (1ll << 31), "attn: a sequence of %d rows x %d B exceeds a buffer descriptor", max_seqlen,
-                (nq + 2 * nkv) * head_dim * 2);
+  LRX_CHECK_ARG((int64_t)max_seqlen * (nq + 2 * nkv) * head_dim * 2 < (1ll << 31), "attn: a sequence of %d rows x %d B exceeds the 2 GiB of a buffer descriptor",
+                max_seqlen, (nq + 2 * nkv) * head_dim * 2);
+  const AttnPlan p = attn_plan(n_seqs, max_seqlen, nq, nkv, head_dim, last_tile_only);
+  LRX_CHECK_ARG(p.n_items < (1ll << 31), "attn: %lld work items", (long long)p.n_items);
+  const i32x4* list = nullptr;
+  if (items) {
+    const size_t need = attn_list_hdr_bytes(p) + 16 * (size_t)attn_list_item_bound(p, n_seqs, total_tokens, nkv, last_tile_only);
+    LRX_CHECK_ARG(items_bytes >= need, "attn: work list %zu B < required %zu B", items_bytes, need);
+    list = (const i32x4*)((const char*)items + attn_list_hdr_bytes(p));
+  }
   const float scale_log2 = (1.0f / sqrtf((float)head_dim)) * 1.4426950408889634f;
-#define LRX_STREAM_CASE(DD, GG)                                                                                                                       \
-  case GG: hipLaunchKernelGGL((k_attn_stream<DD, GG>), dim3((unsigned)p.n_wg), dim3(128 * GG), 0, s, (const __bf16*)qkv, (const int32_t*)items, \
-                              (const i32x4*)((const char*)items + attn_list_hdr_bytes(p)), nq, nkv, (__bf16*)out, scale_log2, out_f16); break;
+#define LRX_STREAM_ARGS(GG)                                                                                                                         \
+  dim3((unsigned)p.n_wg), dim3(128 * GG), 0, s, (const __bf16*)qkv, (const int32_t*)items, list, nq, nkv, (__bf16*)out, scale_log2, out_f16, cu_seqlens, \
+      p.nqt, p.nparts, n_seqs, (int)p.n_items, p.gs, last_tile_only
+#define LRX_STREAM_CASE(DD, GG)                                                                      \
+  case GG:                                                                                           \
+    if (list) hipLaunchKernelGGL((k_attn_stream<DD, GG, false>), LRX_STREAM_ARGS(GG));              \
+    else hipLaunchKernelGGL((k_attn_stream<DD, GG, true>), LRX_STREAM_ARGS(GG));                    \
+    break;
   if (head_dim == 64) {
     switch (p.grp) {
       LRX_STREAM_CASE(64, 1) LRX_STREAM_CASE(64, 2) LRX_STREAM_CASE(64, 3) LRX_STREAM_CASE(64, 4)
@@ -1600,51 +1320,7 @@ int lrx_attn_varlen_causal_items_ex(const void* qkv, const int32_t* cu_seqlens, 
     switch (p.grp) { LRX_STREAM_CASE(128, 1) LRX_STREAM_CASE(128, 2) LRX_STREAM_CASE(128, 3) LRX_STREAM_CASE(128, 4) }
   }
 #undef LRX_STREAM_CASE
+#undef LRX_STREAM_ARGS
   LRX_LAUNCH_CHECK();
   return LRX_OK;
-}
-
-extern "C" int lrx_attn_varlen_causal(const void* qkv, const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens,
-                                      int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out,
-                                      int32_t last_tile_only, void* stream) {
-  return lrx_attn_varlen_causal_ex(qkv, cu_seqlens, n_seqs, total_tokens, max_seqlen, num_q_heads, num_kv_heads, head_dim, out, last_tile_only, 0, stream);
-}
-int lrx_attn_varlen_causal_ex(const void* qkv, const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens, int32_t max_seqlen, int32_t num_q_heads,
-                              int32_t num_kv_heads, int32_t head_dim, void* out, int32_t last_tile_only, int out_f16, void* stream) {
-  int rc = attn_check_layout(num_q_heads, num_kv_heads, head_dim);
-  if (rc) return rc;
-  LRX_CHECK_ARG(max_seqlen > 0 || total_tokens == 0, "attn: max_seqlen must be > 0");
-  if (total_tokens == 0 || n_seqs == 0) return LRX_OK;
-  int grp = num_q_heads / num_kv_heads;
-  hipStream_t s = (hipStream_t)stream;
-  if (attn_uses_resident64(head_dim, max_seqlen, last_tile_only)) return launch_resident64(qkv, cu_seqlens, n_seqs, num_q_heads, num_kv_heads, out, s, out_f16);
-  // No work list: the walker kernel (k_attn_varlen_causal) derives every item's (sequence, kv head, q tile) itself -- the variant for
-  // callers without scratch memory; lrx_attn_varlen_causal_items is the faster launch.
-  // Tiled kernel: GRP q heads per workgroup, nparts workgroups per kv head (heads beyond the group idle).  head_dim 64 takes up to 8
-  // heads per workgroup; head_dim 128 needs ~190 VGPRs per wave, so at most 4 (more than 8 waves per workgroup would spill): groups
-  // of 5-6 heads run as two workgroups of 3, 7-8 as two of 4 (the K/V tiles are staged twice, from L2), larger groups as ceil(grp/4).
-#define LRX_ATTN_CASE(DD, GG, PARTS) \
-  return launch_attn<DD, GG>(qkv, cu_seqlens, n_seqs, max_seqlen, num_q_heads, num_kv_heads, out, last_tile_only, s, PARTS, out_f16);
-  if (head_dim == 64) {
-    switch (grp) {
-      case 1: LRX_ATTN_CASE(64, 1, 1)
-      case 2: LRX_ATTN_CASE(64, 2, 1)
-      case 3: LRX_ATTN_CASE(64, 3, 1)
-      case 4: LRX_ATTN_CASE(64, 4, 1)
-      case 5: LRX_ATTN_CASE(64, 5, 1)
-      case 6: LRX_ATTN_CASE(64, 6, 1)
-      case 7: LRX_ATTN_CASE(64, 7, 1)
-      case 8: LRX_ATTN_CASE(64, 8, 1)
-      default: LRX_ATTN_CASE(64, 8, (grp + 7) / 8)
-    }
-  }
-  switch (grp) {
-    case 1: LRX_ATTN_CASE(128, 1, 1)
-    case 2: LRX_ATTN_CASE(128, 2, 1)
-    case 3: LRX_ATTN_CASE(128, 3, 1)
-    case 4: LRX_ATTN_CASE(128, 4, 1)
-    case 5: case 6: LRX_ATTN_CASE(128, 3, 2)
-    default: LRX_ATTN_CASE(128, 4, (grp + 3) / 4)
-  }
-#undef LRX_ATTN_CASE
 }

@@ -275,9 +275,9 @@ static int batch_before_layer(void* ctx, int l, hipStream_t s) {
 }
 static int batch_attn(void* ctx, int, bool last_tile, hipStream_t s) {
   const BatchAttn& a = *(const BatchAttn*)ctx;
-  return lrx_attn_varlen_causal_items_ex(a.ws->qkv, a.cu, last_tile ? a.ws->attn_items_tail : a.ws->attn_items,
-                                         last_tile ? a.ws->attn_items_tail_bytes : a.ws->attn_items_bytes, a.n_seqs, a.T, a.max_seqlen, a.c->num_q_heads,
-                                         a.c->num_kv_heads, a.c->head_dim, a.ws->h, last_tile ? 1 : 0, a.c->precise_stream == 2, s);
+  return lrx_attn_varlen_causal_ex(a.ws->qkv, a.cu, last_tile ? a.ws->attn_items_tail : a.ws->attn_items,
+                                   last_tile ? a.ws->attn_items_tail_bytes : a.ws->attn_items_bytes, a.n_seqs, a.T, a.max_seqlen, a.c->num_q_heads,
+                                   a.c->num_kv_heads, a.c->head_dim, a.ws->h, last_tile ? 1 : 0, a.c->precise_stream == 2, s);
 }
 static int forward_layers(const lrx_encoder_config* c, const lrx_encoder_weights* w, const int32_t* ids, const int32_t* cu, int n_seqs,
                           int T, int max_seqlen, EncWs& ws, bool pooled_tail, hipStream_t s, bool sum_before_last = false) {
@@ -451,7 +451,7 @@ static int prefix_capture(void* ctx, int l, hipStream_t s) {          // K|V (po
 }
 static int prefix_attn(void* ctx, int, bool, hipStream_t s) {
   const PrefCtx& a = *(const PrefCtx*)ctx;
-  return lrx_attn_varlen_causal_ex(a.pw->e.qkv, a.pw->cu, 1, a.P1, a.P1, a.c->num_q_heads, a.c->num_kv_heads, a.c->head_dim, a.pw->e.h, 0, a.c->precise_stream == 2, s);
+  return lrx_attn_varlen_causal_ex(a.pw->e.qkv, a.pw->cu, nullptr, 0, 1, a.P1, a.P1, a.c->num_q_heads, a.c->num_kv_heads, a.c->head_dim, a.pw->e.h, 0, a.c->precise_stream == 2, s);
 }
 static int suffix_attn(void* ctx, int l, bool, hipStream_t s) {
   const PrefCtx& a = *(const PrefCtx*)ctx;

@@ -52,6 +52,8 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert l.lrx_gemm_bf16_nt(None, None, None, None, None, 4, 8, 7, 0, None) == -1
     assert b"K=7" in l.lrx_last_error()
     assert l.lrx_attn_varlen_causal(None, None, 1, 4, 4, 4, 2, 16, None, 0, None) == -1
+    # a sequence is addressed through one buffer descriptor: at 32 / 8 heads of 128, 2 GiB / 12 KiB per row = 174762 rows fit
+    assert l.lrx_attn_varlen_causal(None, None, 1, 174763, 174763, 32, 8, 128, None, 0, None) == -1 and b"2 GiB" in l.lrx_last_error()
     # the work-list variant (ABI 7): same layout checks, the list must be there and large enough
     assert l.lrx_attn_varlen_causal_items(None, None, None, 0, 1, 4, 4, 4, 2, 16, None, 0, None) == -1
     assert l.lrx_attn_varlen_causal_items(None, None, None, 0, 1, 4, 4, 32, 8, 128, None, 0, None) == -1 and b"work list" in l.lrx_last_error()

@@ -53,13 +53,21 @@ def test_resident_attention_keeps_prefetched_q_in_place(attn_isa):
     assert len(re.findall(r"buffer_store_dwordx4", body)) == 4       # always-issued stores: the count the vmcnt(4) stands on
 
 
-def test_tiled_attention_at_head_dim_128_has_no_scratch(attn_isa):
-    for grp in (1, 2, 3, 4):
-        assert "scratch_" not in kernel_body(attn_isa, "_Z20k_attn_varlen_causalILi128ELi%dE" % grp)
+def stream_kernel(d, grp, walk):
+    """Mangled-name prefix of k_attn_stream<d, grp, walk>: the work-list (walk = 0) or the list-less (walk = 1) instantiation."""
+    return "_Z13k_attn_streamILi%dELi%dELb%dEE" % (d, grp, int(walk))
+
+
+def test_tiled_attention_has_no_scratch_with_either_item_source(attn_isa):
+    # every (d, GRP) the launch dispatches, with the items read from a work list and walked by the kernel itself
+    for d, grps in ((128, (1, 2, 3, 4)), (64, (1, 2, 3, 4, 5, 6, 7, 8))):
+        for grp in grps:
+            for walk in (False, True):
+                assert "scratch_" not in kernel_body(attn_isa, stream_kernel(d, grp, walk)), (d, grp, walk)
 
 
 def test_work_list_attention_has_no_scratch_at_the_shapes_the_encoders_use(attn_isa):
     # (a spilled value reloaded inside the item loop waits, with its vmcnt(0), for every tile request in flight: DESIGN.md 5.2)
     for d, grps in ((128, (1, 2, 3, 4)), (64, (1, 2, 3, 4, 5, 6, 7, 8))):
         for grp in grps:
-            assert "scratch_" not in kernel_body(attn_isa, "_Z13k_attn_streamILi%dELi%dE" % (d, grp)), (d, grp)
+            assert "scratch_" not in kernel_body(attn_isa, stream_kernel(d, grp, walk=False)), (d, grp)
