@@ -450,7 +450,8 @@ int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, int64_t ldx,
                                     const int64_t* row_map, uint64_t* out_wire, void* workspace, size_t workspace_bytes, int32_t flags,
                                     void* stream);
 /* (ABI 5) Statistics for tools and bench legs.  lrx_search_fallback_count: queries any bounded search of this process has sent to its
- * exact six-product fallback since the last reset (list / band overflow: a performance event, the results are exact either way);
+ * exact six-product fallback since the last reset (list / band overflow: a performance event, the results are exact either way) -- and
+ * the queries a range search sent to its score-matrix path because their candidate list overflowed;
  * SYNCHRONISES like lrx_device_error_count.  lrx_flat_ip_bounded_list_counts: counts_out[n_queries] (device, uint32) = candidate-list
  * entries of each query of the last chunk of the last search that used `workspace` -- the rows that passed the filter and reached the
  * refine step; pass that search's own (n_rows, dim, n_queries of that chunk, k, flags) and whether it had a shadow; zeros when that search
@@ -462,6 +463,26 @@ int64_t lrx_search_fallback_count(int32_t reset);
 int32_t lrx_flat_ip_bounded_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags, int32_t has_shadow);
 int lrx_flat_ip_bounded_list_counts(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
                                     int32_t has_shadow, uint32_t* counts_out, void* stream);
+
+/* (added in ABI 8, additively) Exact inner-product RANGE search (faiss IndexFlatIP::range_search): every row whose exact score -- the value
+ * every search path reports, (float) of the fp64-accumulated sum of the fp32 products -- is STRICTLY greater than `radius`.  Result in faiss's
+ * layout: lims[n_queries + 1] (device, int64; lims[0] = 0), query i's hits are out_scores / out_ids [lims[i], lims[i+1]) in ascending row
+ * order, ids = id_base + row, scores bit-equal to what the top-k searches report.  Deterministic: the same arrays for any query batch size,
+ * with or without X_shadow.  lims is always written and exact.  out_scores / out_ids are written only when the results fit `capacity`
+ * (checked on the device): a call of up to one chunk of queries (256 with a shadow, 128 without) writes nothing to them when
+ * lims[n_queries] > capacity and still returns LRX_OK -- read lims[n_queries] and call again with at least that capacity (as with
+ * snprintf); a longer call checks chunk by chunk, so chunks that end within `capacity` may have been written.  Asynchronous on `stream`,
+ * no host synchronisation.  X_shadow (tiled fp16 shadow, dim % 64 == 0) selects the candidate-list path: ONE pass over the shadow with
+ * the threshold radius - eps(q), exact rescoring of the list; queries whose list overflows -- more than 64 Ki filter hits, or, at high hit density,
+ * more hits in one step than a wave's LDS list holds (so possibly far fewer than 64 Ki) -- counted by
+ * lrx_search_fallback_count -- and calls without a shadow, with dim % 64 != 0 or with <= 4096 rows take the score-matrix path (six-product
+ * or exact-fp32 scores of <= 128 queries, exact rescoring of every row within 2 eps6(q) of the radius).  row_bounds as for
+ * lrx_flat_ip_search_bounded; dim % 4 == 0; radius must not be NaN; workspace of lrx_flat_ip_range_workspace_bytes (grows with the
+ * queries up to one chunk).                                                                                                          */
+size_t lrx_flat_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t has_shadow);
+int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
+                             const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
+                             int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Shard maintenance (FaissIndex.build / IndexFlatIP.add, retriever/faiss_index.py:45-58, for rows that were not written by
  * lrx_encode_packed_shard): one read of n_rows fp32 rows writes their fp16 shadow (X_shadow may be NULL: bounds only) and raises

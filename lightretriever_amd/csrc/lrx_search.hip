@@ -3,6 +3,7 @@
 // bounded-search driver, shard maintenance, the exchange kernels -- and includes the device code in source order:
 //     lrx_search_filter.h   A. score / filter kernels          lrx_search_select.h   B. selection
 //     lrx_search_bounded.h  C. error bound, threshold, fused   lrx_search_refine.h   C. band refine, row-grouped rescoring, part merge
+//     lrx_search_range.h    F. range search: threshold from a given radius, exact rescoring, row-ordered output (host driver: lrx_flat_ip_range_search)
 // Map of the unit:
 //
 //  A. Score kernels (what a search streams the shard through)
@@ -69,6 +70,7 @@ struct FilterMode {
   bool group_max = false;                 // shadow kernels, score stores: `blkmax` receives the maxima of the 16-row wave groups
                                           // (8 per block, row stride 8 x nblk_ld) instead of one maximum per 128-row block
   const struct FusedArgs* fused = nullptr; // sample + selection + main pass in ONE launch (k_filter_fused) right after the query packing
+  bool range = false;                     // emit mode of the range search: every block (bmode 0), list overflow saturates the counter
 };
 struct FusedArgs {
   int64_t ld_s;
@@ -158,6 +160,10 @@ static int launch_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t di
 #define LRX_XP(QQ, RT_)                                                                                                                     \
   {                                                                                                                                         \
     const int64_t groups = (nwg + RT_ - 1) / RT_;                                                                                           \
+    if (fm.range)                                                                                                                           \
+      hipLaunchKernelGGL((k_filter_xreg_emit<QQ, (QQ == 8 ? 2 : XPF), RT_, true>), dim3((unsigned)(groups < n_cu ? groups : n_cu)), dim3(576), 0, s, \
+                         (const __bf16*)Xs, n_rows, dim, qsplit, nq, (int)nwg, fm.bmode, fm.ss, fm.unit, fm.thr, fm.cand, fm.cnt, fm.cap);     \
+    else                                                                                                                                    \
     hipLaunchKernelGGL((k_filter_xreg_emit<QQ, (QQ == 8 ? 2 : XPF), RT_>), dim3((unsigned)(groups < n_cu ? groups : n_cu)), dim3(576), 0, s, (const __bf16*)Xs, n_rows, \
                        dim, qsplit, nq, (int)nwg, fm.bmode, fm.ss, fm.unit, fm.thr, fm.cand, fm.cnt, fm.cap);                              \
   }
@@ -308,6 +314,7 @@ static int launch_filter_fused(const void* Xs, int64_t n_rows, int dim, const __
 }
 
 #include "lrx_search_refine.h"   // band refine, row-grouped rescoring, merge of the parts
+#include "lrx_search_range.h"    // range search: threshold, exact rescoring, row-ordered output
 
 // ---- host side: per query chunk (<= 256 queries with the shadow, <= 128 without) one pipeline over one workspace ----------------
 // flags & 3 (lrx.h LRX_SEARCH_FILTER_*): 0 = choose the filter per chunk, 1 = always the score-matrix filter, 2 = the score-free filter
@@ -721,6 +728,146 @@ extern "C" int lrx_flat_ip_bounded_list_counts(const void* workspace, int64_t n_
   const unsigned int* cnt = p.emit && !plain ? (const unsigned int*)(flg + ints_before_cnt(n_queries)) : nullptr;
   hipLaunchKernelGGL(k_copy_list_counts, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream, cnt, n_queries, counts_out);
   LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
+// ---- range search (device side: lrx_search_range.h) --------------------------------------------------------------------------------
+// Per chunk of <= 256 queries (list path) or <= 128 (score-matrix path) one plan over one workspace.  The list path needs the shadow (dim % 64
+// == 0), more than REF_CAND rows and fewer than 2^31 (the saturating list counter stays below 2^32); everything else takes the score-matrix path.
+struct RangePlan {
+  bool list;
+  int chunk;
+  int64_t ld, nblk, nblk_ld, nw;           // score row stride, 128-row blocks, blkmax row stride, 64-row bitmap words
+  size_t off_blkmax, off_qsplit, off_ints, off_cand, off_bits, off_pre, total;
+};
+static bool range_list_path(int64_t n_rows, int32_t dim, bool has_shadow) {
+  return has_shadow && dim % 64 == 0 && n_rows > REF_CAND && n_rows < (1ll << 31);
+}
+// ints: cnt[nq * CNT_STRIDE] | flags[nq] | any_flag[ANY_FLAG_GROUPS] | surv[nq] | thr[nq]
+static RangePlan range_plan(int64_t n_rows, int32_t dim, int32_t nq, bool list) {
+  RangePlan p;
+  memset(&p, 0, sizeof(p));
+  p.list = list;
+  p.chunk = list ? 256 : 128;
+  p.ld = lrx_flat_ip_score_ld(n_rows);
+  p.nblk = p.ld / SP_ROWS;
+  p.nblk_ld = (p.nblk + 3) & ~(int64_t)3;
+  p.nw = lrx_cdiv(n_rows > 0 ? n_rows : 1, 64);
+  const size_t nm = (size_t)(nq < 128 ? nq : 128);                 // queries of one score matrix
+  p.off_blkmax = align256(nm * (size_t)p.ld * sizeof(float));
+  p.off_qsplit = align256(p.off_blkmax + nm * (size_t)p.nblk_ld * sizeof(float));
+  p.off_ints = align256(p.off_qsplit + split_ws_bytes(dim));
+  p.off_cand = align256(p.off_ints + sizeof(int) * ((size_t)nq * (CNT_STRIDE + 3) + ANY_FLAG_GROUPS));
+  p.off_bits = align256(p.off_cand + (list ? (size_t)nq * RANGE_CAP * 8 : 0));
+  p.off_pre = align256(p.off_bits + (list ? (size_t)nq * p.nw * 8 : 0));
+  p.total = p.off_pre + (list ? (size_t)nq * p.nw * 4 : 0);
+  return p;
+}
+
+extern "C" size_t lrx_flat_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t has_shadow) {
+  const bool list = range_list_path(n_rows, dim, has_shadow != 0);
+  const int chunk = list ? 256 : 128;
+  const int32_t nq = n_queries < 1 ? 1 : (n_queries > chunk ? chunk : n_queries);
+  return range_plan(n_rows, dim > 0 ? dim : 1, nq, list).total + 512;
+}
+
+extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
+                                        const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
+                                        int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(row_bounds != nullptr, "flat_ip_range_search: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
+  LRX_CHECK_ARG(dim > 0 && dim % 4 == 0, "flat_ip_range_search: dim=%d must be a positive multiple of 4", dim);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "flat_ip_range_search: shard rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG(n_queries >= 0 && capacity >= 0, "flat_ip_range_search: n_queries=%d / capacity=%lld must be >= 0", n_queries, (long long)capacity);
+  LRX_CHECK_ARG(radius == radius, "flat_ip_range_search: radius is NaN");
+  LRX_CHECK_ARG(lims != nullptr, "flat_ip_range_search: null lims");
+  hipStream_t s = (hipStream_t)stream;
+  if (n_queries == 0 || n_rows == 0) {
+    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), s));
+    return LRX_OK;
+  }
+  if (workspace_bytes < lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr)) {
+    lrx_set_error("flat_ip_range_search: workspace %zu B < required %zu B", workspace_bytes,
+                  lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr));
+    return LRX_ERR_WORKSPACE;
+  }
+  const bool list = range_list_path(n_rows, dim, X_shadow != nullptr);
+  const int chunk = list ? 256 : 128;
+  const int n_cu = lrx_cu_count();
+  for (int q0 = 0; q0 < n_queries; q0 += chunk) {
+    const int nq = n_queries - q0 < chunk ? n_queries - q0 : chunk;
+    const RangePlan p = range_plan(n_rows, dim, nq, list);
+    const float* qc = q + (int64_t)q0 * dim;
+    char* ws = (char*)workspace;
+    float* scores = (float*)ws;
+    float* blkmax = (float*)(ws + p.off_blkmax);
+    __bf16* qsplit = (__bf16*)(ws + p.off_qsplit);
+    unsigned int* cnt = (unsigned int*)(ws + p.off_ints);
+    int* flg = (int*)(cnt + (size_t)nq * CNT_STRIDE);
+    int* any_flag = flg + nq;
+    unsigned int* surv = (unsigned int*)(any_flag + ANY_FLAG_GROUPS);
+    float* thr = (float*)(surv + nq);
+    unsigned long long* cand = (unsigned long long*)(ws + p.off_cand);
+    unsigned long long* bits = (unsigned long long*)(ws + p.off_bits);
+    unsigned int* pre = (unsigned int*)(ws + p.off_pre);
+    int64_t* lc = lims + q0;                                           // this chunk's lims: lc[0] was written by the chunk before
+    const int64_t* lend = lims + q0 + nq;
+    LRX_HIP(hipMemsetAsync(cnt, 0, (size_t)((char*)thr - (char*)cnt), s));
+    const int parts = (int)(nq >= 4 * n_cu ? 1 : (4 * n_cu + nq - 1) / nq > 64 ? 64 : (4 * n_cu + nq - 1) / nq);
+    int rc;
+    if (list) {
+      LRX_HIP(hipMemsetAsync(bits, 0, (size_t)nq * p.nw * 8, s));
+      hipLaunchKernelGGL(k_range_threshold, dim3(nq), dim3(256), 0, s, qc, dim, row_bounds, radius, thr);
+      LRX_LAUNCH_CHECK();
+      FilterMode fm;                                                    // every block, no sample: the given radius is the threshold
+      fm.bmode = 0; fm.thr = thr; fm.cand = cand; fm.cnt = cnt; fm.cap = RANGE_CAP; fm.range = true;
+      rc = launch_scores(X, n_rows, ldx, dim, qc, nq, nullptr, nullptr, qsplit, stream, 1, nullptr, X_shadow, p.ld, fm);
+      if (rc != LRX_OK) return rc;
+      hipLaunchKernelGGL(k_range_rescore, dim3(nq, parts), dim3(256), 0, s, X, n_rows, ldx, dim, qc, cand, (const unsigned int*)cnt, (unsigned int)RANGE_CAP,
+                         radius, bits, p.nw, surv, flg, any_flag);
+      LRX_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_range_bitmap_prefix, dim3(nq), dim3(256), 0, s, (const unsigned long long*)bits, p.nw, (const unsigned int*)cnt,
+                         (unsigned int)RANGE_CAP, pre);
+      LRX_LAUNCH_CHECK();
+    }
+    // score-matrix path, <= 128 queries at a time: the overflowed queries of a list chunk (launches gated on the group's flag), or all queries
+    auto matrix = [&](int f0, int nf) -> int {
+      const int* gate = list ? any_flag + f0 / 128 : nullptr;
+      return launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, qsplit, stream, 3, gate, nullptr, 0, FilterMode());
+    };
+    auto scan = [&](int f0, int nf, bool fill) {
+      const int* gate = list ? any_flag + f0 / 128 : nullptr;
+      const int* qf = list ? flg + f0 : nullptr;
+      if (fill)
+        hipLaunchKernelGGL(k_range_scan<true>, dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
+                           X, ldx, dim, qc + (int64_t)f0 * dim, row_bounds, radius, gate, qf, surv + f0, (const int64_t*)lc + f0, lend, capacity, id_base,
+                           out_scores, out_ids);
+      else
+        hipLaunchKernelGGL(k_range_scan<false>, dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
+                           X, ldx, dim, qc + (int64_t)f0 * dim, row_bounds, radius, gate, qf, surv + f0, (const int64_t*)lc + f0, lend, capacity, id_base,
+                           out_scores, out_ids);
+    };
+    for (int f0 = 0; f0 < nq; f0 += 128) {
+      const int nf = nq - f0 < 128 ? nq - f0 : 128;
+      if ((rc = matrix(f0, nf)) != LRX_OK) return rc;
+      scan(f0, nf, false);
+      LRX_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(1024), 0, s, (const unsigned int*)surv, nq, lc, q0 == 0 ? 1 : 0);
+    LRX_LAUNCH_CHECK();
+    if (list) {
+      hipLaunchKernelGGL(k_range_fill_list, dim3(nq, parts), dim3(256), 0, s, (const unsigned long long*)cand, (const unsigned int*)cnt, (unsigned int)RANGE_CAP,
+                         (const unsigned long long*)bits, (const unsigned int*)pre, p.nw, (const int64_t*)lc, lend, capacity, id_base, out_scores, out_ids);
+      LRX_LAUNCH_CHECK();
+    }
+    // fill passes, last group first: its matrix from the count loop is still in place; only the groups before it are scored again
+    const int last = (nq - 1) / 128 * 128;
+    for (int f0 = last; f0 >= 0; f0 -= 128) {
+      const int nf = nq - f0 < 128 ? nq - f0 : 128;
+      if (f0 != last && (rc = matrix(f0, nf)) != LRX_OK) return rc;
+      scan(f0, nf, true);
+      LRX_LAUNCH_CHECK();
+    }
+  }
   return LRX_OK;
 }
 

@@ -714,7 +714,9 @@ struct EmitLds {
 // thr_ready / thr_target (fused kernel): the thresholds are published by other workgroups of the SAME launch -- the first block step's K loop
 // runs before they are needed; each consumer wave then polls *thr_ready until it reaches thr_target (the selection items were all claimed by
 // running workgroups before this workgroup got here, so the wait ends) and loads the thresholds past the L1.  NULL: thr is final at launch.
-template <int QT, int PF, int RT>
+// SAT (range search only): a wave-list overflow raises the query's counter to AT LEAST cap + 1 (atomic max) instead of adding cap + 1, so the
+// counter stays <= cap + 1 + N however many overflows a low threshold produces (top-k search: false, its code is unchanged)
+template <int QT, int PF, int RT, bool SAT = false>
 __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, int nblocks, int bmode, int ss,
                    int unit, const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, unsigned int cap,
                    const unsigned int* thr_ready, unsigned int thr_target, unsigned long long* ts = nullptr) {
@@ -928,7 +930,8 @@ __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __res
         if ((ovf >> b) & 1u) {
           unsigned int col = b * 16 + fi;
           asm volatile("" : "+v"(col));             // (keeps the address arithmetic inside this cold branch)
-          __hip_atomic_fetch_add(&cnt[col * CNT_STRIDE], cap + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          if constexpr (SAT) __hip_atomic_fetch_max(&cnt[col * CNT_STRIDE], cap + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          else __hip_atomic_fetch_add(&cnt[col * CNT_STRIDE], cap + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       ovf = 0;
     }
@@ -965,12 +968,12 @@ __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __res
   }
 }
 
-template <int QT, int PF, int RT>
+template <int QT, int PF, int RT, bool SAT = false>
 __global__ void __launch_bounds__(576, (QT > 8 || RT > 1) ? 3 : 5)   // (second argument: waves per SIMD -> two workgroups of nine waves per CU need five)
 k_filter_xreg_emit(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, int nblocks, int bmode, int ss,
                    int unit, const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, unsigned int cap) {
   __shared__ __attribute__((aligned(1024))) char smem[EmitLds<QT>::BYTES];
-  filter_emit_body<QT, PF, RT>(smem, Xb, N, D, qs, nq, nblocks, bmode, ss, unit, thr, cand, cnt, cap, nullptr, 0u);
+  filter_emit_body<QT, PF, RT, SAT>(smem, Xb, N, D, qs, nq, nblocks, bmode, ss, unit, thr, cand, cnt, cap, nullptr, 0u);
 }
 
 // Device-scope ("sc1") loads / stores: data one workgroup writes and another workgroup of the SAME launch reads (the fused filter kernel) must

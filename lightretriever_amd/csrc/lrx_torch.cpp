@@ -254,6 +254,41 @@ std::tuple<at::Tensor, at::Tensor> merge_topk(const at::Tensor& d_parts, const a
   return {d, i};
 }
 
+// Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
+// with the exact capacity, when the first guess of 1024 hits per query was short).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
+                                                                    const at::Tensor& row_bounds, double radius, int64_t id_base) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(x, "x", at::kFloat, 2);
+  need(row_bounds, "row_bounds", at::kFloat, 1);
+  TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_range_search: q [Q,D] contiguous, x [N,D], row_bounds [2]");
+  if (x_shadow.has_value()) {
+    TORCH_CHECK(x_shadow->is_cuda() && x_shadow->scalar_type() == at::kHalf && x_shadow->dim() == 1 && x_shadow->is_contiguous() &&
+                    x_shadow->numel() >= ((x.size(0) + 127) / 128) * 128 * x.size(1),
+                "flat_ip_range_search: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  }
+  const int64_t Q = q.size(0);
+  at::Tensor lims = at::zeros({Q + 1}, q.options().dtype(at::kLong));
+  const size_t wsb = lrx_flat_ip_range_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)Q, x_shadow.has_value() ? 1 : 0);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  int64_t cap = Q * 1024;
+  at::Tensor d, i;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    d = at::empty({cap}, q.options());
+    i = at::empty({cap}, q.options().dtype(at::kLong));
+    lrx_check(lrx_flat_ip_range_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1),
+                                       x_shadow.has_value() ? x_shadow->data_ptr() : nullptr, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)Q,
+                                       (float)radius, id_base, lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap, ws.data_ptr(), wsb,
+                                       cur_stream()),
+              "flat_ip_range_search");
+    const int64_t n = lims[Q].item<int64_t>();
+    if (n <= cap) return {lims, d.narrow(0, 0, n), i.narrow(0, 0, n)};
+    cap = n;
+  }
+  TORCH_CHECK(false, "flat_ip_range_search: the result grew between two identical calls");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(lrx, m) {
@@ -270,6 +305,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("merge_topk_packed(Tensor words) -> (Tensor, Tensor)");
   m.def("shard_commit_rows(Tensor x, Tensor(a!)? x_shadow, Tensor(b!) row_bounds, int row0=0) -> ()");
   m.def("merge_topk(Tensor d_parts, Tensor i_parts) -> (Tensor, Tensor)");
+  m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HIP tensors under the CUDA key)
@@ -285,4 +321,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("merge_topk_packed", &merge_topk_packed);
   m.impl("shard_commit_rows", &shard_commit_rows);
   m.impl("merge_topk", &merge_topk);
+  m.impl("flat_ip_range_search", &flat_ip_range_search);
 }

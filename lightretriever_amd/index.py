@@ -333,6 +333,63 @@ class FlatIPIndex:
                 _lib.check(self.lib.lrx_flat_ip_search(_lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k,
                                                        self.id_base, _lib.ptr(Dc), _lib.ptr(Ic), _lib.ptr(ws), ws.numel(), stream))
 
+    def range_search(self, q, radius: float):
+        """faiss range_search for inner product -> (lims i64[Q+1], D f32[lims[Q]], I i64[lims[Q]]) device tensors: query i's hits are
+        D[lims[i]:lims[i+1]], I[lims[i]:lims[i+1]] -- every row whose exact score (the value search() reports, bit-equal) is strictly greater
+        than `radius`, ids = id_base + row, in ascending row order.  Exact, never truncated, deterministic (independent of the query batch,
+        the shadow and two_pass).  Memory: the workspace (lrx_flat_ip_range_workspace_bytes, kept under max_workspace_bytes) plus 12 bytes
+        per hit and 8 (Q + 1) for lims -- a result of n hits needs 12 n bytes; the outputs are sized by a first guess of 1024 hits per
+        query and resized once if that is short.  Synchronises with the host once per call (the length of the result; once per
+        library call when the workspace cap splits the queries); not under graph capture."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.LrxError("FlatIPIndex.range_search under graph capture: the result length is read back to the host")
+        if not isinstance(q, torch.Tensor):
+            q = torch.from_numpy(q)
+        q = q.to(device=self.device, dtype=torch.float32).contiguous()
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        radius = float(radius)
+        if radius != radius:
+            raise ValueError("range_search: radius is NaN")
+        Q = q.shape[0]
+        lims = torch.zeros(Q + 1, dtype=torch.int64, device=self.device)
+        if Q == 0 or self.ntotal == 0:
+            return lims, torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)
+        ldx = self._x.stride(0) if self._x.shape[0] else self.d
+        if self.two_pass and self.shadow_f16:
+            self._ensure_shadow()
+        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
+        ws_bytes = lambda n: int(self.lib.lrx_flat_ip_range_workspace_bytes(self.ntotal, self.d, n, int(xb is not None)))
+        chunk = Q
+        while chunk > 1 and ws_bytes(chunk) > int(self.max_workspace_bytes):
+            chunk = 256 if chunk > 256 else (128 if chunk > 128 else chunk // 2)
+        ws = self._lane_workspace(0, ws_bytes(chunk))
+        stream = _lib.current_stream()
+        parts = []
+        for s in range(0, Q, chunk):
+            qc = q[s:s + chunk]
+            lc = lims[s:s + qc.shape[0] + 1] if s == 0 else torch.empty(qc.shape[0] + 1, dtype=torch.int64, device=self.device)
+            cap = qc.shape[0] * 1024
+            for attempt in range(2):
+                Dc = torch.empty(cap, dtype=torch.float32, device=self.device)
+                Ic = torch.empty(cap, dtype=torch.int64, device=self.device)
+                _lib.check(self.lib.lrx_flat_ip_range_search(
+                    _lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(xb), _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], radius,
+                    self.id_base, _lib.ptr(lc), _lib.ptr(Dc), _lib.ptr(Ic), cap, _lib.ptr(ws), ws.numel(), stream))
+                n = int(lc[-1].item())
+                if n <= cap:
+                    break
+                cap = n                                    # (the retry's result is the same: every path is deterministic)
+            parts.append((lc, Dc[:n], Ic[:n], n))
+        if len(parts) == 1:
+            return lims, parts[0][1], parts[0][2]
+        off = 0
+        for j, (lc, _, _, n) in enumerate(parts):
+            s = j * chunk
+            lims[s + 1:s + lc.shape[0]] = lc[1:] + off
+            off += n
+        return lims, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])
+
     def last_list_counts(self) -> torch.Tensor:
         """uint32-valued int64 tensor [q]: candidate-list entries per query of the last chunk of the last two-pass search (the rows that
         passed the filter threshold and reached the refine step) -- statistics for tools and bench legs.  Zeros when the last search was

@@ -47,6 +47,13 @@ class FaissIndex:
         logger.info("Num of queries: %d\tSearch time (s): %.3f\tQPS: %.3f", n, dt, n / dt)
         return scores, ids
 
+    def range_search(self, query_embeddings, radius: float):
+        """-> (lims, D, I) of FlatIPIndex.range_search, with I mapped through the passage ids as in search()."""
+        lims, scores, ids = self.index.range_search(query_embeddings, radius)
+        if self._passage_ids is not None:
+            ids = self._passage_ids[ids]
+        return lims, scores, ids
+
     @classmethod
     def build(cls, passage_ids: list, passage_embeddings, index: Optional[FlatIPIndex] = None, buffer_size: int = 50000):
         if index is None:
