@@ -484,6 +484,30 @@ int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_
                              const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
                              int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (added in ABI 8, additively) fp16 SCALAR-QUANTISED inner-product index (faiss IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT)):
+ * the only resident copy of the rows is their codes c = fp16(x) -- round-to-nearest-even per element, saturating at +-65504 (faiss maps
+ * an overflow to inf; counted by lrx_device_saturation_count) -- in the TILED layout of the shadow below (lrx_shard_commit_rows with X_shadow
+ * writes them, and so does lrx_encode_packed_shard through shadow_out): 2 bytes per element instead of the 6 of a flat shard with shadow.
+ * dim % 64 == 0.  Score s(q, r) = (float) sum_i (double) q_i (double) c_{r,i}: fp64 accumulation, one rounding -- the flat index's score
+ * with x replaced by the decoded codes; for fp32 rows that are exactly fp16-representable both indexes return bit-identical results.
+ * Exact top-k under that score, ties to the lower row, (-FLT_MAX, -1) padding when k > n_rows, independent of the query batch and the
+ * chunking: the rules of lrx_flat_ip_search_bounded.  The search is that one's two-pass chain over the codes: the same filter (fp16(q) .
+ * c, fp32 accumulation), whose error is bounded by eps16(q) = |q - fp16(q)| R16 + (D + 32) 2^-23 |fp16(q)| R16 with R16 = R + E taken
+ * from row_bounds (the pair lrx_shard_commit_rows maintains; there is no |fp16(q)| E term), the exact rescoring from the codes, and --
+ * for queries whose candidate list or band overflows, counted by lrx_search_fallback_count -- a gated score-matrix filter over the codes
+ * with exact rescoring of the band kth - 2 eps16 (no host synchronisation).  Shards under 16 Ki rows take the score-matrix filter.
+ * out_wire / row_map: as for lrx_flat_ip_search_bounded_wire (NULL: none).  flags: LRX_SEARCH_* above.  Queries per chunk:
+ * lrx_sq_fp16_ip_chunk_queries (the role of lrx_flat_ip_bounded_chunk_queries); statistics: lrx_flat_ip_bounded_list_counts with
+ * has_shadow = 1.  Workspace: lrx_sq_fp16_ip_workspace_bytes (grows with the queries up to one chunk).                              */
+size_t lrx_sq_fp16_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags);
+int32_t lrx_sq_fp16_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags);
+int lrx_sq_fp16_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* row_bounds, const float* q, int32_t n_queries,
+                          int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, uint64_t* out_wire,
+                          void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
+/* Exact decode of rows [row0, row0 + n_rows) of the tiled codes to fp32: out[i * ldo + c] = (float) code of row row0 + i, column c
+ * (ldo >= dim).  For reconstruct_n and save; fp16 -> fp32 -> fp16 is exact, so lrx_shard_commit_rows of the decoded rows restores the codes. */
+int lrx_sq_fp16_decode_rows(const void* codes, int64_t row0, int64_t n_rows, int32_t dim, float* out, int64_t ldo, void* stream);
+
 /* Shard maintenance (FaissIndex.build / IndexFlatIP.add, retriever/faiss_index.py:45-58, for rows that were not written by
  * lrx_encode_packed_shard): one read of n_rows fp32 rows writes their fp16 shadow (X_shadow may be NULL: bounds only) and raises
  * row_bounds[0] = max |row|, row_bounds[1] = max |row - fp16(row)| (device, two floats, zero-initialised by the caller when the

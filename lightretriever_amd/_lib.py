@@ -70,6 +70,10 @@ SIGNATURES = {
     "lrx_flat_ip_bounded_list_counts": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "lrx_flat_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "lrx_flat_ip_range_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "lrx_sq_fp16_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
+    "lrx_sq_fp16_ip_chunk_queries": (_I32, [_I64, _I32, _I32, _I32, _I32]),
+    "lrx_sq_fp16_ip_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _SZ, _I32, _P]),
+    "lrx_sq_fp16_decode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P]),
     "lrx_shard_commit_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P, _P]),
     "lrx_pool_norm_shard": (_I32, [_P, _P, _P, _I32, _I32, _F, _P, _I64, _I32, _I32, _P, _I64, _P, _I32, _P]),
     "lrx_gemm_bf16_nt_resid32": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),

@@ -46,6 +46,12 @@
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
+// Row source of every exact rescoring and of the error bound (a compile-time parameter of the rescoring kernels, k_sample_threshold and
+// k_filter_fused): ROWS_F32 = fp32 row-major rows X + r * ldx (the flat index), ROWS_F16T = the tiled fp16 codes of the fp16 scalar-quantised
+// index (X = base of the tiled layout, lrx_shadow_off; ldx unused).  row_dot (lrx_search_select.h), query_eps_block (lrx_search_bounded.h).
+#define ROWS_F32 0
+#define ROWS_F16T 1
+
 #include "lrx_search_filter.h"   // score / filter kernels
 
 extern "C" int64_t lrx_flat_ip_score_ld(int64_t n_rows) { return lrx_cdiv(n_rows > 0 ? n_rows : 1, S_ROWS) * S_ROWS; }
@@ -82,6 +88,7 @@ struct FusedArgs {
   unsigned int cap;
   FusedCtl* ctl;
   int phases;                             // 7 = sample + selection + main pass (dev: LRX_FUSED_PHASES = 1 or 3 leaves the rest to the old kernels)
+  int rs;                                 // row source of the exact scores (ROWS_F32 / ROWS_F16T): which error bound the selection uses
 };
 
 // planes = 3: fp32-grade scores (six bf16 products); planes = 1: one fp16 product (filter pass of the bounded search, error bound
@@ -98,6 +105,7 @@ static int lrx_cu_count() {
 }
 
 static int filter_rows_per_wg(bool shadow) { return shadow ? 128 : 16 * SPF_RT * SPF_WV; }
+template <int RS>
 static int launch_filter_fused(const void* Xs, int64_t n_rows, int dim, const __bf16* qsplit, int nq, int qt, float* scores, float* gmax, const float* qf32,
                                const FusedArgs& fa, hipStream_t s);
 
@@ -136,7 +144,8 @@ static int launch_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t di
                            fm.zero, fm.nzero, ps);
       }
       if (fm.fused != nullptr) {   // the whole filter chain of the score-free search in one persistent launch
-        const int rc = launch_filter_fused(Xs, n_rows, dim, qsplit, nq, qt, sp, bp, qp, *fm.fused, s);
+        const int rc = fm.fused->rs == ROWS_F16T ? launch_filter_fused<ROWS_F16T>(Xs, n_rows, dim, qsplit, nq, qt, sp, bp, qp, *fm.fused, s)
+                                                 : launch_filter_fused<ROWS_F32>(Xs, n_rows, dim, qsplit, nq, qt, sp, bp, qp, *fm.fused, s);
         if (rc != LRX_OK) return rc;
         continue;
       }
@@ -275,7 +284,7 @@ extern "C" int lrx_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, i
       if (rc != LRX_OK) return rc;
       row_bounds = wb;
     }
-    hipLaunchKernelGGL(k_topk_select_rescore, dim3(n_queries), dim3(SEL_THREADS), 0, (hipStream_t)stream, (const float*)scores, ld, n_rows, k, id_base,
+    hipLaunchKernelGGL(k_topk_select_rescore<ROWS_F32>, dim3(n_queries), dim3(SEL_THREADS), 0, (hipStream_t)stream, (const float*)scores, ld, n_rows, k, id_base,
                        (const float*)blkmax, nblk, nblk_ld, X, ldx, dim, q, out_scores, out_ids, (const int*)nullptr, (const int*)nullptr, row_bounds,
                        (unsigned long long*)nullptr, (const int64_t*)nullptr);
   } else {
@@ -294,6 +303,7 @@ extern "C" int lrx_probe_fused_timestamps(uint64_t* out, int32_t n_words) {
   return LRX_OK;
 }
 
+template <int RS>
 static int launch_filter_fused(const void* Xs, int64_t n_rows, int dim, const __bf16* qsplit, int nq, int qt, float* scores, float* gmax, const float* qf32,
                                const FusedArgs& fa, hipStream_t s) {
   const int n_cu = lrx_cu_count();
@@ -301,9 +311,9 @@ static int launch_filter_fused(const void* Xs, int64_t n_rows, int dim, const __
   const bool rt2 = fa.nmain >= 8 * n_cu;
 #define LRX_FU(QQ)                                                                                                                               \
   case QQ:                                                                                                                                        \
-    if (rt2) hipLaunchKernelGGL((k_filter_fused<QQ, (QQ == 8 ? 2 : 4), 2>), dim3(n_cu), dim3(576), 0, s, (const __bf16*)Xs, n_rows, dim, qsplit, nq, scores, fa.ld_s, \
+    if (rt2) hipLaunchKernelGGL((k_filter_fused<QQ, (QQ == 8 ? 2 : 4), 2, RS>), dim3(n_cu), dim3(576), 0, s, (const __bf16*)Xs, n_rows, dim, qsplit, nq, scores, fa.ld_s, \
                                 gmax, fa.nblk_s, fa.nblk_ld_s, fa.nsamp, fa.nmain, fa.ss, fa.k, qf32, fa.bounds, fa.thr, fa.eps, fa.cand, fa.cnt, fa.cap, fa.ctl, fa.phases);  \
-    else hipLaunchKernelGGL((k_filter_fused<QQ, (QQ == 8 ? 2 : 4), 1>), dim3(n_cu), dim3(576), 0, s, (const __bf16*)Xs, n_rows, dim, qsplit, nq, scores, fa.ld_s,     \
+    else hipLaunchKernelGGL((k_filter_fused<QQ, (QQ == 8 ? 2 : 4), 1, RS>), dim3(n_cu), dim3(576), 0, s, (const __bf16*)Xs, n_rows, dim, qsplit, nq, scores, fa.ld_s,     \
                             gmax, fa.nblk_s, fa.nblk_ld_s, fa.nsamp, fa.nmain, fa.ss, fa.k, qf32, fa.bounds, fa.thr, fa.eps, fa.cand, fa.cnt, fa.cap, fa.ctl, fa.phases);      \
     break;
   switch (qt) { LRX_FU(1) LRX_FU(2) LRX_FU(3) LRX_FU(4) LRX_FU(5) LRX_FU(6) LRX_FU(7) LRX_FU(8)
@@ -460,25 +470,30 @@ extern "C" int32_t lrx_flat_ip_bounded_chunk_queries(int64_t n_rows, int32_t dim
   return chunk_queries(n_rows, dim, n_queries > 0 ? n_queries : 1, k, has_shadow && dim % 64 == 0, flags & 3);
 }
 
+// the largest chunk plan of a call (its full chunks and its last one, either chain: flags, LRX_SEARCH_FUSED)
+static size_t chunk_plans_bytes(int64_t n_rows, int32_t dim, int32_t nq, int32_t k, int mode, bool shadow) {
+  size_t need = 0;
+  const int chunk = chunk_queries(n_rows, dim, nq, k, shadow, mode);
+  const int sizes[2] = {nq < chunk ? nq : chunk, nq > chunk ? nq % chunk : 0};
+  for (int i = 0; i < 2; ++i)
+    if (sizes[i] > 0) {
+      size_t t = plan_chunk(n_rows, dim, sizes[i], k, shadow, mode, 0).total;
+      const size_t tf = plan_chunk(n_rows, dim, sizes[i], k, shadow, mode, 1).total;
+      t = tf > t ? tf : t;
+      need = t > need ? t : need;
+    }
+  return need;
+}
+
 extern "C" size_t lrx_flat_ip_bounded_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags) {
   // the search walks the queries in chunks (chunk_queries: 256 over a shadow, up to LRX_EMIT_MAX_QUERIES where the GEMM main pass applies; 128
   // over fp32 rows), each chunk with its own plan over the same buffer; sized for the filter `flags` selects (the score-matrix filter of
   // LRX_SEARCH_FILTER_MATRIX needs [min(Q, 256), rows] floats), with or without a shadow
   const int32_t nq = n_queries > 0 ? n_queries : 1;
-  const int mode = flags & 3;
-  size_t need = lrx_flat_ip_workspace_bytes(n_rows, dim, nq < 128 ? nq : 128, k);   // tiny shards / few queries without shadow: plain path in chunks of 128
-  for (int sh = 0; sh < 2; ++sh) {
-    const int chunk = chunk_queries(n_rows, dim, nq, k, sh != 0, mode);
-    const int sizes[2] = {nq < chunk ? nq : chunk, nq > chunk ? nq % chunk : 0};
-    for (int i = 0; i < 2; ++i)
-      if (sizes[i] > 0) {
-        size_t t = plan_chunk(n_rows, dim, sizes[i], k, sh != 0, mode, 0).total;
-        const size_t tf = plan_chunk(n_rows, dim, sizes[i], k, sh != 0, mode, 1).total;   // (either chain may run: flags, LRX_SEARCH_FUSED)
-        t = tf > t ? tf : t;
-        need = t > need ? t : need;
-      }
-  }
-  return need + 512;
+  const size_t need = lrx_flat_ip_workspace_bytes(n_rows, dim, nq < 128 ? nq : 128, k);   // tiny shards / few queries without shadow: plain path in chunks of 128
+  const size_t a = chunk_plans_bytes(n_rows, dim, nq, k, flags & 3, false), b = chunk_plans_bytes(n_rows, dim, nq, k, flags & 3, true);
+  const size_t m = a > b ? a : b;
+  return (m > need ? m : need) + 512;
 }
 
 extern "C" int lrx_flat_ip_search_bounded(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
@@ -488,24 +503,20 @@ extern "C" int lrx_flat_ip_search_bounded(const float* X, int64_t n_rows, int64_
                                          workspace, workspace_bytes, flags, stream);
 }
 
-extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
-                                               const float* q, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
-                                               const int64_t* row_map, uint64_t* out_wire, void* workspace, size_t workspace_bytes, int32_t flags,
-                                               void* stream) {
-  LRX_CHECK_ARG(row_bounds != nullptr, "flat_ip_search_bounded: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
-  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "flat_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "flat_ip_search: shard rows=%lld out of range", (long long)n_rows);
-  LRX_CHECK_ARG((flags & ~63) == 0 && (flags & 12) != 12 && (flags & 48) != 48, "flat_ip_search_bounded: unknown flags 0x%x", flags);
-  if (n_queries <= 0) return LRX_OK;
-  if (workspace_bytes < lrx_flat_ip_bounded_workspace_bytes(n_rows, dim, n_queries, k, flags)) {
-    lrx_set_error("flat_ip_search_bounded: workspace %zu B < required %zu B", workspace_bytes, lrx_flat_ip_bounded_workspace_bytes(n_rows, dim, n_queries, k, flags));
-    return LRX_ERR_WORKSPACE;
-  }
+// The bounded search over either row source (lrx_search_select.h, row_dot): RS = ROWS_F32 -- X = fp32 rows (stride ldx), X_shadow = their
+// optional tiled fp16 shadow (lrx_flat_ip_search_bounded_wire); RS = ROWS_F16T -- X = X_shadow = the tiled fp16 codes of a scalar-quantised
+// index, nothing else resident (lrx_sq_fp16_ip_search): the filter is the same pass over the same layout, the exact rescoring reads the
+// codes, and the gated fallback is the one-product score-matrix filter over the codes + k_topk_select_rescore<ROWS_F16T> instead of the
+// six-product pass over fp32 rows.  Arguments checked by the callers.
+template <int RS>
+static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
+                          const float* q, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
+                          const int64_t* row_map, uint64_t* out_wire, void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
   const int mode = flags & 3;
   const bool shadow = X_shadow != nullptr && dim % 64 == 0;
   const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;
   // tiny shards and odd widths take the plain path; so do small query batches without a shadow (HBM-bound on the exact-fp32 kernel already)
-  if ((qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0) {
+  if (RS == ROWS_F32 && ((qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0)) {
     for (int q0 = 0; q0 < n_queries; q0 += 128) {
       const int nq = n_queries - q0 < 128 ? n_queries - q0 : 128;
       const int rc = lrx_flat_ip_search(X, n_rows, ldx, dim, row_bounds, q + (int64_t)q0 * dim, nq, k, id_base, out_scores + (int64_t)q0 * k,
@@ -551,7 +562,7 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
     // (per 256-query sub-chunk j of the chunk: the plane sets of its two 128-query groups, qs3 + (2 j + g) * stride)
     auto presplit_of = [&](int j) {
       PreSplit ps;
-      if (!shadow) return ps;
+      if (!shadow || RS == ROWS_F16T) return ps;              // (no six-product fallback over codes)
       const int n0 = j * 256, nj = nq - n0 < 256 ? nq - n0 : 256;
       ps.qs3 = qs3 + (int64_t)(2 * j) * qs3_stride;
       ps.stride = qs3_stride;
@@ -583,6 +594,7 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
         // (sample + selection + main pass, always; LRX_FUSED_PHASES bit 7 in a dev build adds the per-workgroup phase stamps of lrx_probe_fused_timestamps)
         static const int fused_stamps = lrx_dev_knob("LRX_FUSED_PHASES", 0) & 128;
         fa.phases = 7 | fused_stamps;
+        fa.rs = RS;
         fs.fused = &fa;
       }
       __bf16* q16 = (__bf16*)(ws + p.off_q16);
@@ -606,7 +618,7 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
       }
       if (rc != LRX_OK) return rc;
       if (fs.fused == nullptr)
-      hipLaunchKernelGGL(k_sample_threshold, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld_s, p.nsamp_wg * p.rb, k, (const float*)blkmax,
+      hipLaunchKernelGGL(k_sample_threshold<RS>, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld_s, p.nsamp_wg * p.rb, k, (const float*)blkmax,
                          (int)p.nblk_s, (int)p.nblk_ld_s, qc, dim, row_bounds, p.rb, p.ss, n_rows, thr, eps, cand, cnt, fs.group_max ? 16 : 128, p.cap);
       LRX_LAUNCH_CHECK();
       if (fs.fused != nullptr) {
@@ -651,7 +663,7 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
           rp.total = grp_off + ngroups + 1;
           rp.grp_shift = gshift;
           LRX_HIP(hipMemsetAsync(rp.grp_cnt, 0, (size_t)((char*)(rp.total + 1) - (char*)rp.grp_cnt), s));
-          hipLaunchKernelGGL(k_refine_band, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
+          hipLaunchKernelGGL(k_refine_band<RS>, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
                              (const unsigned int*)cnt, (const float*)eps, k, parts, part_cnt, nsplit, p.cap, rp);
           LRX_LAUNCH_CHECK();
           hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, (const unsigned int*)rp.grp_cnt, grp_off, (int)ngroups);
@@ -659,13 +671,13 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
           hipLaunchKernelGGL(k_pairs_scatter, dim3((unsigned)(4 * lrx_cu_count())), dim3(256), 0, s, (const unsigned long long*)rp.pairs, (const unsigned int*)rp.total,
                              rp.grp_cnt, (const unsigned int*)grp_off, gshift, sorted);
           LRX_LAUNCH_CHECK();
-          hipLaunchKernelGGL(k_rescore_row_groups, dim3((unsigned)ngroups), dim3(ROWGRP_THREADS), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)sorted,
+          hipLaunchKernelGGL(k_rescore_row_groups<RS>, dim3((unsigned)ngroups), dim3(ROWGRP_THREADS), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)sorted,
                              (const unsigned int*)grp_off, gshift, parts);
           LRX_LAUNCH_CHECK();
         }
       }
       if (rp.pairs == nullptr) {
-        hipLaunchKernelGGL(k_refine_band, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
+        hipLaunchKernelGGL(k_refine_band<RS>, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
                            (const unsigned int*)cnt, (const float*)eps, k, parts, part_cnt, nsplit, p.cap, rp);
         LRX_LAUNCH_CHECK();
       }
@@ -679,7 +691,7 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
       hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld, n_rows, k, id_base, (const float*)blkmax, (int)p.nblk,
                          (int)p.nblk_ld, osc, oic, (const int*)nullptr, (const int*)nullptr);
       LRX_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_refine_topk, dim3(nq, REF_SPLIT), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const float*)scores, p.ld, (const float*)blkmax,
+      hipLaunchKernelGGL(k_refine_topk<RS>, dim3(nq, REF_SPLIT), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const float*)scores, p.ld, (const float*)blkmax,
                          (int)p.nblk, (int)p.nblk_ld, row_bounds, k, id_base, (const float*)osc, parts, part_cnt);
       LRX_LAUNCH_CHECK();
     }
@@ -696,16 +708,96 @@ extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, i
       const PreSplit psf = presplit_of(f0 / 256);
       ff.planes_ready = psf.ngroups > 0;                      // written by the packing kernel(s) at the head of the chain
       const int* gate = any_flag + f0 / 128;                  // this group's flag: raised by k_refine_merge when one of its queries overflowed
-      rc = launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, ff.planes_ready ? qs3 + (f0 / 128) * qs3_stride : qsplit, stream, 3,
-                         gate, nullptr, 0, ff);
+      if (RS == ROWS_F16T)   // (the one-product score matrix over the codes: query_eps_block<ROWS_F16T> bounds its error)
+        rc = launch_scores(nullptr, n_rows, dim, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, qsplit, stream, 1, gate, X_shadow, 0, FilterMode());
+      else
+        rc = launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, ff.planes_ready ? qs3 + (f0 / 128) * qs3_stride : qsplit, stream, 3,
+                           gate, nullptr, 0, ff);
       if (rc != LRX_OK) return rc;
-      hipLaunchKernelGGL(k_topk_select_rescore, dim3(nf), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld, n_rows, k, id_base, (const float*)blkmax,
+      hipLaunchKernelGGL(k_topk_select_rescore<RS>, dim3(nf), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld, n_rows, k, id_base, (const float*)blkmax,
                          (int)p.nblk, (int)p.nblk_ld, X, ldx, dim, qc + (int64_t)f0 * dim, osc + (int64_t)f0 * k, oic + (int64_t)f0 * k,
                          gate, (const int*)(flg + f0), row_bounds,
                          out_wire != nullptr ? (unsigned long long*)out_wire + ((int64_t)q0 + f0) * k : (unsigned long long*)nullptr, row_map);
       LRX_LAUNCH_CHECK();
     }
   }
+  return LRX_OK;
+}
+
+extern "C" int lrx_flat_ip_search_bounded_wire(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
+                                               const float* q, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
+                                               const int64_t* row_map, uint64_t* out_wire, void* workspace, size_t workspace_bytes, int32_t flags,
+                                               void* stream) {
+  LRX_CHECK_ARG(row_bounds != nullptr, "flat_ip_search_bounded: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
+  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "flat_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "flat_ip_search: shard rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG((flags & ~63) == 0 && (flags & 12) != 12 && (flags & 48) != 48, "flat_ip_search_bounded: unknown flags 0x%x", flags);
+  if (n_queries <= 0) return LRX_OK;
+  if (workspace_bytes < lrx_flat_ip_bounded_workspace_bytes(n_rows, dim, n_queries, k, flags)) {
+    lrx_set_error("flat_ip_search_bounded: workspace %zu B < required %zu B", workspace_bytes, lrx_flat_ip_bounded_workspace_bytes(n_rows, dim, n_queries, k, flags));
+    return LRX_ERR_WORKSPACE;
+  }
+  return bounded_search<ROWS_F32>(X, n_rows, ldx, dim, X_shadow, row_bounds, q, n_queries, k, id_base, out_scores, out_ids, row_map, out_wire,
+                                  workspace, workspace_bytes, flags, stream);
+}
+
+// ---- fp16 scalar-quantised inner-product index (faiss IndexScalarQuantizer(QT_fp16, METRIC_INNER_PRODUCT)): the tiled fp16 codes are the
+// only resident copy of the rows; the search is bounded_search<ROWS_F16T> (see there and query_eps_block in lrx_search_bounded.h).
+extern "C" size_t lrx_sq_fp16_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags) {
+  return chunk_plans_bytes(n_rows, dim, n_queries > 0 ? n_queries : 1, k, flags & 3, true) + 512;
+}
+
+extern "C" int32_t lrx_sq_fp16_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags) {
+  return chunk_queries(n_rows, dim, n_queries > 0 ? n_queries : 1, k, true, flags & 3);
+}
+
+extern "C" int lrx_sq_fp16_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* row_bounds, const float* q, int32_t n_queries,
+                                     int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, uint64_t* out_wire,
+                                     void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
+  LRX_CHECK_ARG(dim > 0 && dim % 64 == 0, "sq_fp16_ip_search: dim=%d must be a positive multiple of 64", dim);
+  LRX_CHECK_ARG(row_bounds != nullptr, "sq_fp16_ip_search: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
+  LRX_CHECK_ARG(codes != nullptr || n_rows == 0, "sq_fp16_ip_search: null codes");
+  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "sq_fp16_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "sq_fp16_ip_search: rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG((flags & ~63) == 0 && (flags & 12) != 12 && (flags & 48) != 48, "sq_fp16_ip_search: unknown flags 0x%x", flags);
+  if (n_queries <= 0) return LRX_OK;
+  if (workspace_bytes < lrx_sq_fp16_ip_workspace_bytes(n_rows, dim, n_queries, k, flags)) {
+    lrx_set_error("sq_fp16_ip_search: workspace %zu B < required %zu B", workspace_bytes, lrx_sq_fp16_ip_workspace_bytes(n_rows, dim, n_queries, k, flags));
+    return LRX_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (n_rows == 0) {   // (nothing to filter: every output is padding)
+    hipLaunchKernelGGL(k_topk_select, dim3(n_queries), dim3(SEL_THREADS), 0, s, (const float*)nullptr, (int64_t)0, (int64_t)0, k, id_base,
+                       (const float*)nullptr, 0, 0, out_scores, out_ids, (const int*)nullptr, (const int*)nullptr);
+    LRX_LAUNCH_CHECK();
+    return out_wire != nullptr ? lrx_pack_topk(out_scores, out_ids, row_map, id_base, (int64_t)n_queries * k, out_wire, stream) : LRX_OK;
+  }
+  return bounded_search<ROWS_F16T>((const float*)codes, n_rows, dim, dim, codes, row_bounds, q, n_queries, k, id_base, out_scores, out_ids, row_map,
+                                   out_wire, workspace, workspace_bytes, flags, stream);
+}
+
+// exact decode of rows [row0, row0 + n_rows) of the tiled codes to fp32 rows out[i * ldo + c]: one 16-byte piece (8 elements) per thread
+__global__ void k_sq_fp16_decode(const _Float16* __restrict__ C, int64_t row0, int64_t n_rows, int D, float* __restrict__ out, int64_t ldo) {
+  const int64_t per_row = D / 8;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_rows * per_row; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / per_row;
+    const int c = (int)(t - i * per_row) * 8;
+    const f16x8 h = *(const f16x8*)(C + lrx_shadow_off(row0 + i, c, D));
+    float* o = out + i * ldo + c;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (float)h[j];
+  }
+}
+extern "C" int lrx_sq_fp16_decode_rows(const void* codes, int64_t row0, int64_t n_rows, int32_t dim, float* out, int64_t ldo, void* stream) {
+  LRX_CHECK_ARG(dim > 0 && dim % 64 == 0, "sq_fp16_decode_rows: dim=%d must be a positive multiple of 64", dim);
+  LRX_CHECK_ARG(row0 >= 0 && n_rows >= 0 && ldo >= dim, "sq_fp16_decode_rows: row0=%lld n_rows=%lld ldo=%lld", (long long)row0, (long long)n_rows, (long long)ldo);
+  if (n_rows == 0) return LRX_OK;
+  LRX_CHECK_ARG(codes != nullptr && out != nullptr, "sq_fp16_decode_rows: null pointer");
+  const int64_t threads = n_rows * (dim / 8);
+  const int64_t blocks = (threads + 255) / 256;
+  hipLaunchKernelGGL(k_sq_fp16_decode, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, (const _Float16*)codes, row0,
+                     n_rows, (int)dim, out, ldo);
+  LRX_LAUNCH_CHECK();
   return LRX_OK;
 }
 

@@ -40,7 +40,16 @@ struct RadixShared {
 };
 
 // eps(q) of the header comment; all threads of the (<= 1024-thread) block take part, fixed summation order.  Optionally stages the
-// query row in LDS (s_q).  bounds = {R, E}; E <= 0 means "not measured": bounded from R below.
+// query row in LDS (s_q).  bounds = {R, E}; E <= 0 means "not measured": bounded from R below.  RS = the row source the exact scores come
+// from (ROWS_F32: the fp32 rows of a flat index; ROWS_F16T: the fp16 codes of the scalar-quantised index, below) -- every caller passes it.
+//
+// ROWS_F16T.  The codes ARE the rows: c = fp16(x) is stored, the exact score is s = q . c, and the filter computes s~ = fp16(q) . c with the
+// same fp32 accumulation.  So s - s~ = (q - q~) . c + (accumulation error), and by Cauchy-Schwarz
+//     |s - s~| <= eps16(q) = |q - q~| R16 + (D + 32) 2^-23 |q~| R16,        R16 = max |c_row|
+// -- no |q~| E term: nothing is rounded on the row side.  R16 comes from the bounds pair the writers of the codes already maintain
+// (lrx_shard_commit_rows, the encoder's last kernel): |c| = |x - (x - c)| <= |x| + |x - c| <= R + E by the triangle inequality, with the
+// same conservative E as below when E was not measured.
+template <int RS>
 __device__ float query_eps_block(const float* __restrict__ qglob, int D, const float* __restrict__ bounds, float* s_q, float* s_red /* 32 */) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   float a = 0.f, b = 0.f;
@@ -65,6 +74,10 @@ __device__ float query_eps_block(const float* __restrict__ qglob, int D, const f
   const float R = bounds[0];
   const float E = bounds[1] > 0.f ? bounds[1] : (R <= 65504.f ? R * 0.00048828125f + sqrtf((float)D) * 2.9802322e-8f : R);
   const float accum = (float)(D + 32) * 1.1920929e-7f;   // 2^-23 per accumulated term
+  if constexpr (RS == ROWS_F16T) {
+    const float R16 = (R + E) * 1.0001f;                  // (the sum rounded up: R16 >= R + E)
+    return (sqrtf(B) * R16 + sqrtf(A) * accum * R16 * 1.01f) * 1.0001f + 1e-30f;
+  }
   return (sqrtf(B) * R + sqrtf(A) * (E + accum * R * 1.01f)) * 1.0001f + 1e-30f;
 }
 
@@ -82,7 +95,7 @@ struct ThrShared {
   float s_red[32];
   unsigned int s_fill;
 };
-template <bool SORTED, bool COH = false>
+template <bool SORTED, bool COH = false, int RS = ROWS_F32>
 __device__ __forceinline__ void sample_threshold_query(ThrShared& ts, int qi, const float* __restrict__ scores, int64_t ld_s, int64_t Ns, int k,
                    const float* __restrict__ blkmax, int nblk, int nblk_ld,
                    const float* __restrict__ q, int D, const float* __restrict__ bounds, int rb, int ss, int64_t N, float* __restrict__ thr_out,
@@ -120,7 +133,7 @@ __device__ __forceinline__ void sample_threshold_query(ThrShared& ts, int qi, co
     kth = -FLT_MAX;                                              // (not reachable: plan_chunk admits the fused launch only with >= k sample groups)
   }
   __syncthreads();
-  const float eps = query_eps_block(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
+  const float eps = query_eps_block<RS>(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
   const float thr = kth - 2.0f * eps;
   // this workgroup is the only writer of the query's list until the main pass starts: slots come from an LDS counter (a global
   // atomic per hit cost ~2 us of round trip per qualifying block and wave: 49 -> 3x us for the kernel), the count is stored once
@@ -190,12 +203,13 @@ __device__ __forceinline__ void sample_threshold_query(ThrShared& ts, int qi, co
   }
 }
 
+template <int RS>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_sample_threshold(const float* __restrict__ scores, int64_t ld_s, int64_t Ns, int k, const float* __restrict__ blkmax, int nblk, int nblk_ld,
                    const float* __restrict__ q, int D, const float* __restrict__ bounds, int rb, int ss, int64_t N, float* __restrict__ thr_out,
                    float* __restrict__ eps_out, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, int gsz, unsigned int cap) {
   __shared__ ThrShared ts;
-  sample_threshold_query<true>(ts, blockIdx.x, scores, ld_s, Ns, k, blkmax, nblk, nblk_ld, q, D, bounds, rb, ss, N, thr_out, eps_out, cand, cnt, gsz, cap);
+  sample_threshold_query<true, false, RS>(ts, blockIdx.x, scores, ld_s, Ns, k, blkmax, nblk, nblk_ld, q, D, bounds, rb, ss, N, thr_out, eps_out, cand, cnt, gsz, cap);
 }
 
 // ---- the fused filter kernel (see filter_sample_block above for the design): selection + the two passes in one persistent launch
@@ -216,7 +230,7 @@ struct FusedLds {
   static constexpr int BYTES = A > (int)sizeof(ThrShared) + 64 ? A : (int)sizeof(ThrShared) + 64;
 };
 
-template <int QT, int PF, int RT>
+template <int QT, int PF, int RT, int RS>
 __global__ void __launch_bounds__(576, 3)
 k_filter_fused(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, float* __restrict__ scores, int64_t ld_s,
                float* __restrict__ gmax, int nblk_s, int nblk_ld_s, int nsamp, int nmain, int ss, int k, const float* __restrict__ qf32,
@@ -261,7 +275,7 @@ k_filter_fused(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __
         while (__hip_atomic_load(&ctl->done_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned int)nsamp) __builtin_amdgcn_s_sleep(8);
       __syncthreads();
       if (ts != nullptr && tid == 0 && ts[2] == 0) ts[2] = __builtin_amdgcn_s_memrealtime();
-      sample_threshold_query<false, true>(*(ThrShared*)smem, (int)qi, scores, ld_s, (int64_t)nsamp * 128, k, gmax, nblk_s, nblk_ld_s, qf32, D, bounds, 128, ss, N,
+      sample_threshold_query<false, true, RS>(*(ThrShared*)smem, (int)qi, scores, ld_s, (int64_t)nsamp * 128, k, gmax, nblk_s, nblk_ld_s, qf32, D, bounds, 128, ss, N,
                                     thr, eps, cand, cnt, 16, cap);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (thread 0's device-scope stores of thr / eps / list count have landed)
       __syncthreads();

@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(256) k_range_threshold(const float* __restrict
                                                          float* __restrict__ thr) {
   __shared__ float s_red[32];
   const int qi = blockIdx.x;
-  const float eps = query_eps_block(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
+  const float eps = query_eps_block<ROWS_F32>(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
   if (threadIdx.x == 0) {
     const double r = (double)radius;
     thr[qi] = radius == INFINITY ? INFINITY : range_round_down(r - fabs(r) * 1.1920928955078125e-7 - (double)eps * (1.0 + 9.5367431640625e-7) - 1e-30);

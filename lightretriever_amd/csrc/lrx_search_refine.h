@@ -7,13 +7,15 @@
 // rounding to fp32); the packed (score, row) pairs go to `mine`.  (A version that streams the rows as 1024-float chunks through two
 // register buffers, the next chunk requested before the current one is accumulated, changed nothing: the step is bound by the chip's
 // random 8-KiB gather rate, 0.30 GB in ~58 us = 5.2 TB/s at Q = 100, 5.8 TB/s at Q = 256.)
+// RS: the row source (ROWS_F32 / ROWS_F16T, row_dot in lrx_search_select.h).
+template <int RS>
 __device__ __forceinline__ void refine_rescore(const float* __restrict__ X, int64_t ldx, int D, const float* qrow, const unsigned long long* s_cand,
                                                int nc, unsigned long long* __restrict__ mine) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int c0 = wave * 2; c0 < nc; c0 += 32) {
     const int c = min(c0 + (lane >> 5), nc - 1);
     const int64_t n = (int64_t)s_cand[c];
-    const float sc = exact_dot(X + n * ldx, qrow, D, lane);
+    const float sc = row_dot<RS>(X, ldx, n, qrow, D, lane);
     if ((lane & 31) == 0 && c0 + (lane >> 5) < nc) mine[c] = sel_pack(f2key(sc), n);
   }
 }
@@ -27,6 +29,7 @@ struct RowPairs {                         // row-grouped rescoring (below): NULL
   unsigned int* grp_cnt;                  // [groups] pairs per group of (1 << grp_shift) rows
   int grp_shift;
 };
+template <int RS>
 __global__ void __launch_bounds__(1024)
 k_refine_band(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const float* __restrict__ q, const unsigned long long* __restrict__ cand,
               const unsigned int* __restrict__ cnt, const float* __restrict__ eps, int k, unsigned long long* __restrict__ parts,
@@ -78,7 +81,7 @@ k_refine_band(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const 
       atomicAdd(&rp.grp_cnt[row >> rp.grp_shift], 1u);
     }
   } else {
-    refine_rescore(X, ldx, D, qrow, s_cand, nc, parts + ((int64_t)qi * nsplit + part) * pcand);
+    refine_rescore<RS>(X, ldx, D, qrow, s_cand, nc, parts + ((int64_t)qi * nsplit + part) * pcand);
   }
   if (tid == 0) part_cnt[qi * nsplit + part] = overflow ? -1 : nc;
 }
@@ -149,6 +152,9 @@ __device__ __forceinline__ float exact_dot_lds_row(const float* x_lds, const flo
 }
 #define ROWGRP_LDS_FLOATS 16384          // 64 KiB of rows per workgroup (two workgroups per CU: one stages while the other multiplies): 8 rows at D = 2048, 4 at 4096
 #define ROWGRP_THREADS 512
+// RS = ROWS_F16T: the group's codes are decoded to fp32 on the way into LDS (16-byte pieces of the tiled layout, 8 elements each), so the
+// products and their order are those of exact_dot_codes.
+template <int RS>
 __global__ void __launch_bounds__(ROWGRP_THREADS)
 k_rescore_row_groups(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const float* __restrict__ q, const unsigned long long* __restrict__ sorted,
                      const unsigned int* __restrict__ grp_off, int grp_shift, unsigned long long* __restrict__ parts) {
@@ -159,9 +165,19 @@ k_rescore_row_groups(const float* __restrict__ X, int64_t N, int64_t ldx, int D,
   if (p0 == p1) return;
   const int64_t r0 = (int64_t)g << grp_shift;
   const int nrows = (int)min((int64_t)1 << grp_shift, N - r0);
-  for (int i = tid * 4; i < nrows * D; i += ROWGRP_THREADS * 4) {
-    const int rr = i / D, cc = i - rr * D;
-    *(f32x4*)(s_x + i) = REF_ROW_LOAD((const f32x4*)(X + (r0 + rr) * ldx + cc));
+  if constexpr (RS == ROWS_F32) {
+    for (int i = tid * 4; i < nrows * D; i += ROWGRP_THREADS * 4) {
+      const int rr = i / D, cc = i - rr * D;
+      *(f32x4*)(s_x + i) = REF_ROW_LOAD((const f32x4*)(X + (r0 + rr) * ldx + cc));
+    }
+  } else {
+    const _Float16* Cb = (const _Float16*)X;
+    for (int i = tid * 8; i < nrows * D; i += ROWGRP_THREADS * 8) {
+      const int rr = i / D, cc = i - rr * D;
+      const f16x8 h = REF_ROW_LOAD((const f16x8*)(Cb + lrx_shadow_off(r0 + rr, cc, D)));
+      *(f32x4*)(s_x + i) = f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+      *(f32x4*)(s_x + i + 4) = f32x4{(float)h[4], (float)h[5], (float)h[6], (float)h[7]};
+    }
   }
   __syncthreads();
   for (unsigned int pi = p0 + hw; pi < p1; pi += ROWGRP_THREADS / 32) {
@@ -176,6 +192,7 @@ k_rescore_row_groups(const float* __restrict__ X, int64_t N, int64_t ldx, int D,
 // Refine step of the score-matrix filter, grid (n_queries, REF_SPLIT): part s of query q owns the 128-row blocks b with b % REF_SPLIT == s:
 // it gathers their rows inside the band from the score matrix, rescores them exactly and publishes the packed (score, row) list
 // (count -1 = the part's lists overflowed); k_refine_merge finishes.
+template <int RS>
 __global__ void __launch_bounds__(1024)
 k_refine_topk(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const float* __restrict__ q, const float* __restrict__ scores, int64_t ld,
               const float* __restrict__ blkmax, int nblk, int nblk_ld, const float* __restrict__ bounds, int k, int64_t id_base,
@@ -193,7 +210,7 @@ k_refine_topk(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const 
   if (keff == 0) return;                      // (outputs already padded by k_topk_select)
   const float* qglob = q + (int64_t)qi * D;
   const float* qrow = D <= REF_QLDS ? s_q : qglob;
-  const float band = 2.0f * query_eps_block(qglob, D, bounds, D <= REF_QLDS ? s_q : nullptr, s_red);
+  const float band = 2.0f * query_eps_block<RS>(qglob, D, bounds, D <= REF_QLDS ? s_q : nullptr, s_red);
   const float kth = os[keff - 1];             // k-th largest filter score (written by k_topk_select; nobody writes os before the merge)
   const float thr = kth - band;
   // this part's qualifying 128-row blocks
@@ -229,7 +246,7 @@ k_refine_topk(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const 
     overflow = s_ncand > REF_PCAND;
   }
   const int nc = overflow ? 0 : (int)s_ncand;
-  refine_rescore(X, ldx, D, qrow, s_cand, nc, parts + ((int64_t)qi * REF_SPLIT + part) * REF_PCAND);
+  refine_rescore<RS>(X, ldx, D, qrow, s_cand, nc, parts + ((int64_t)qi * REF_SPLIT + part) * REF_PCAND);
   if (tid == 0) part_cnt[qi * REF_SPLIT + part] = overflow ? -1 : nc;
 }
 

@@ -164,9 +164,9 @@ __device__ uint32_t radix_select_kth(const float* __restrict__ row, int64_t n, u
 
 // the same for a SHORT row (n <= 4 * blockDim.x, n % 4 == 0, 16-byte aligned): every thread keeps its four keys in registers, so the four
 // digit passes read nothing but their LDS histograms (the group maxima of a per-rank shard's sample: 3.9 k values -- k_sample_threshold
-// 14.6 -> ~12 us)
+// 14.6 -> ~12 us).  (Forced inline: with the ROWS_F16T instantiations of its callers the inliner stopped inlining it into k_filter_fused.)
 template <class SH, bool COH = false>
-__device__ uint32_t radix_select_kth_small(const float* __restrict__ row, int n, unsigned int kk, SH& sh) {
+__device__ __forceinline__ uint32_t radix_select_kth_small(const float* __restrict__ row, int n, unsigned int kk, SH& sh) {
   const int tid = threadIdx.x, wave = tid >> 6, NT = blockDim.x;   // (any block of >= 256 threads, at most 16 waves)
   uint32_t key[4];
   const bool have = 4 * tid < n;
@@ -355,6 +355,44 @@ __device__ __forceinline__ float exact_dot(const float* __restrict__ x, const fl
   return (float)acc;
 }
 
+// Row source of every exact rescoring (ROWS_F32 / ROWS_F16T, lrx_search.hip): row_dot below.
+typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+// exact_dot over row r of the tiled fp16 codes: the SAME partial products in the same order (lane sub of a half-wave: elements i0 + 128 u +
+// (0..3), i0 = 4 sub), each code decoded exactly to fp32, fp64 accumulation, the same xor tree -- for codes equal to fp32 rows, bit-identical
+// to exact_dot.  Elements i0 + 128 u .. + 3 are half of one 16-byte piece of the layout (D % 64 == 0): one 8-byte load, 16 KiB apart per u
+// (two 64-column tiles).  A row is D / 8 pieces of 16 bytes, each in a 256-byte run it shares with the other 15 rows of its 16-row group.
+__device__ __forceinline__ float exact_dot_codes(const _Float16* __restrict__ C, int64_t r, const float* __restrict__ qrow, int D, int lane) {
+  const int sub = lane & 31;
+  double acc = 0.0;
+  for (int i0 = sub * 4; i0 < D; i0 += 2048) {
+    const _Float16* p = C + lrx_shadow_off(r, i0, D);
+    f16x4 xv[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = i0 + u * 128;
+      xv[u] = i < D ? __builtin_nontemporal_load((const f16x4*)(p + (int64_t)u * 16384)) : f16x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = i0 + u * 128;
+      if (i < D) {
+        const f32x4 qv = *(const f32x4*)(qrow + i);
+        acc += (double)(float)xv[u][0] * (double)qv[0] + (double)(float)xv[u][1] * (double)qv[1] + (double)(float)xv[u][2] * (double)qv[2] +
+               (double)(float)xv[u][3] * (double)qv[3];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  return (float)acc;
+}
+template <int RS>
+__device__ __forceinline__ float row_dot(const float* __restrict__ X, int64_t ldx, int64_t r, const float* __restrict__ qrow, int D, int lane) {
+  if constexpr (RS == ROWS_F32) return exact_dot(X + r * ldx, qrow, D, lane);
+  else return exact_dot_codes((const _Float16*)X, r, qrow, D, lane);
+}
+
 // Select + final step of the plain path (and of the gated fallback of the bounded search) in one launch, RIGOROUS since round 3: the
 // matrix scores s6 (six bf16 products, or the fp32 fma chain for <= 32 queries) differ from the exact inner product s by at most
 //     eps6(q) = (6 D + 8) 2^-23 |q| R            R >= max |x_row|  (bounds[0])
@@ -364,6 +402,8 @@ __device__ __forceinline__ float exact_dot(const float* __restrict__ x, const fl
 // and the best k of them returned.  Usually that is k + a few rows; a near-duplicate cluster with more than SEL_CAND rows inside the band
 // takes the streaming form (the score row walked in 2048-row windows, a running exact top-k in LDS): slow (~ms per such query) but exact
 // for any cluster size.  (Round 2 selected k + 64 rows by score: a heuristic that a stress run had already caught once.)
+// RS = ROWS_F16T (the gated fallback of the fp16 scalar-quantised index): the matrix holds the one-product fp16 filter scores over the codes,
+// so the band is 2 eps(q) of query_eps_block<true> (lrx_search_bounded.h), and the rows are rescored from the codes.
 __device__ __forceinline__ float block_sum_1024(float v, float* red /* 16 */) {
   v = wave_sum(v);
   __syncthreads();
@@ -375,6 +415,9 @@ __device__ __forceinline__ float block_sum_1024(float v, float* red /* 16 */) {
   return t;
 }
 
+template <int RS>   // (lrx_search_bounded.h)
+__device__ float query_eps_block(const float* __restrict__ qglob, int D, const float* __restrict__ bounds, float* s_q, float* s_red);
+template <int RS>
 __device__ __forceinline__ void select_rescore_query(const float* __restrict__ scores, int64_t ld, int64_t N, int k, int64_t id_base,
                                                      const float* __restrict__ blkmax, int nblk, int nblk_ld, const float* __restrict__ X, int64_t ldx,
                                                      int D, const float* __restrict__ q, float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
@@ -388,10 +431,15 @@ __device__ __forceinline__ void select_rescore_query(const float* __restrict__ s
   if (keff == 0) return;
   const float* qrow = q + (int64_t)blockIdx.x * D;
   const float* bm = blkmax ? blkmax + (int64_t)blockIdx.x * nblk_ld : nullptr;
-  float q2 = 0.f;
-  for (int i = tid; i < D; i += SEL_THREADS) { const float v = qrow[i]; q2 += v * v; }
-  q2 = block_sum_1024(q2, s_red);
-  const float eps6 = (float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f;
+  float eps6;
+  if constexpr (RS == ROWS_F32) {
+    float q2 = 0.f;
+    for (int i = tid; i < D; i += SEL_THREADS) { const float v = qrow[i]; q2 += v * v; }
+    q2 = block_sum_1024(q2, s_red);
+    eps6 = (float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f;
+  } else {
+    eps6 = query_eps_block<RS>(qrow, D, bounds, nullptr, s_red);
+  }
   select_topk_sorted(row, N, keff, bm, nblk, sh);            // sh.cand[0..keff): the top-keff by matrix score, sorted
   const float kth6 = key2f((uint32_t)(sh.cand[keff - 1] >> 32));
   const float thr = kth6 - 2.0f * eps6;                      // (a non-finite query gives a NaN threshold: nothing qualifies below, the selection above stands)
@@ -402,7 +450,7 @@ __device__ __forceinline__ void select_rescore_query(const float* __restrict__ s
       const int c = min(c0 + (lane >> 5), n - 1);
       int64_t r = sel_row(list[c]);
       r = r < 0 ? 0 : (r >= N ? N - 1 : r);
-      const float sc = exact_dot(X + r * ldx, qrow, D, lane);
+      const float sc = row_dot<RS>(X, ldx, r, qrow, D, lane);
       if ((lane & 31) == 0 && c0 + (lane >> 5) < n) list[c] = sel_pack(f2key(sc), r);
     }
   };
@@ -492,16 +540,17 @@ __device__ __forceinline__ void select_rescore_query(const float* __restrict__ s
 // a chunk in which something overflowed.  wire (round 4, optional): the query's k results -- whoever wrote them, this workgroup or
 // k_refine_merge one launch earlier -- also leave as the 64-bit words of the multi-GPU exchange (lrx_pack_topk's format; row_map as
 // there), so a sharded search needs no packing launch between the local search and the all-gather.
+template <int RS>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_topk_select_rescore(const float* __restrict__ scores, int64_t ld, int64_t N, int k, int64_t id_base, const float* __restrict__ blkmax, int nblk,
                       int nblk_ld, const float* __restrict__ X, int64_t ldx, int D, const float* __restrict__ q, float* __restrict__ out_scores,
                       int64_t* __restrict__ out_ids, const int* __restrict__ gate, const int* __restrict__ qflags, const float* __restrict__ bounds,
                       unsigned long long* __restrict__ wire, const int64_t* __restrict__ row_map) {
   __shared__ SelShared sh;
-  __shared__ float s_red[16];
+  __shared__ float s_red[RS == ROWS_F32 ? 16 : 32];             // (query_eps_block: 32)
   const bool idle = (gate != nullptr && *gate == 0) ||                  // fallback launch of the bounded search: nothing overflowed
                     (qflags != nullptr && qflags[blockIdx.x] == 0);     // ... or not this query
-  if (!idle) select_rescore_query(scores, ld, N, k, id_base, blkmax, nblk, nblk_ld, X, ldx, D, q, out_scores, out_ids, bounds, sh, s_red);
+  if (!idle) select_rescore_query<RS>(scores, ld, N, k, id_base, blkmax, nblk, nblk_ld, X, ldx, D, q, out_scores, out_ids, bounds, sh, s_red);
   if (wire == nullptr) return;
   __syncthreads();                                            // (this workgroup's own stores of the rows it is about to read)
   const float* os = out_scores + (int64_t)blockIdx.x * k;

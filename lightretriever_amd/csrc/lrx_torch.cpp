@@ -254,6 +254,32 @@ std::tuple<at::Tensor, at::Tensor> merge_topk(const at::Tensor& d_parts, const a
   return {d, i};
 }
 
+// fp16 scalar-quantised index (lrx_sq_fp16_ip_search): codes = the 1-D tiled fp16 codes (include/lrx.h, whole 128-row blocks) holding n_rows
+// rows of q.size(1) columns; row_bounds [2] as maintained by shard_commit_rows.  Returns (D, I, wire words) like flat_ip_topk_bounded_wire.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& row_bounds,
+                                                               int64_t k, int64_t id_base, const c10::optional<at::Tensor>& row_map, int64_t flags) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(row_bounds, "row_bounds", at::kFloat, 1);
+  const int64_t dim = q.size(1);
+  TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && dim % 64 == 0 && n_rows >= 0, "sq_fp16_ip_topk: q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kHalf && codes.dim() == 1 && codes.is_contiguous() && codes.numel() >= ((n_rows + 127) / 128) * 128 * dim,
+              "sq_fp16_ip_topk: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
+  if (row_map.has_value()) {
+    need(*row_map, "row_map", at::kLong, 1);
+    TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= n_rows, "sq_fp16_ip_topk: row_map int64 [>= n_rows] contiguous");
+  }
+  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  at::Tensor w = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  const size_t wsb = lrx_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  lrx_check(lrx_sq_fp16_ip_search(codes.data_ptr(), n_rows, (int32_t)dim, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k,
+                                  id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), row_map.has_value() ? row_map->data_ptr<int64_t>() : nullptr,
+                                  (uint64_t*)w.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags, cur_stream()),
+            "sq_fp16_ip_topk");
+  return {d, i, w};
+}
+
 // Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
 // with the exact capacity, when the first guess of 1024 hits per query was short).
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
@@ -306,6 +332,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("shard_commit_rows(Tensor x, Tensor(a!)? x_shadow, Tensor(b!) row_bounds, int row0=0) -> ()");
   m.def("merge_topk(Tensor d_parts, Tensor i_parts) -> (Tensor, Tensor)");
   m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
+  m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HIP tensors under the CUDA key)
@@ -322,4 +349,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("shard_commit_rows", &shard_commit_rows);
   m.impl("merge_topk", &merge_topk);
   m.impl("flat_ip_range_search", &flat_ip_range_search);
+  m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
 }

@@ -264,18 +264,15 @@ class FlatIPIndex:
         # [queries, rows] fp32 score matrix.  Either way the queries go through in chunks that keep it under max_workspace_bytes
         # (results do not depend on the chunking).
         flags = int(self.search_flags)
-        ws_bytes = (lambda n, d, nq, kk: self.lib.lrx_flat_ip_bounded_workspace_bytes(n, d, nq, kk, flags)) if self.two_pass else self.lib.lrx_flat_ip_workspace_bytes
+        ws_bytes = self._search_ws_bytes(flags)
         chunk = Q
         while chunk > 1 and int(ws_bytes(self.ntotal, self.d, chunk, k)) > int(self.max_workspace_bytes):
             chunk = 256 if chunk > 256 else (128 if chunk > 128 else chunk // 2)
-        ldx = self._x.stride(0) if self._x.shape[0] else self.d
-        if self.two_pass and self.shadow_f16:
-            self._ensure_shadow()                       # (no-op unless rows were committed while the shadow was switched off)
-        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
+        ldx, xb = self._search_rows()
         # the library walks a call's queries in chunks of this size: 256 over the shadow (128 without) or, where its main pass runs on the GEMM
         # kernel (D >= 1024), ONE pass over the shadow per up to 1024 queries (lrx_flat_ip_bounded_chunk_queries, round 6)
         has_xb = xb is not None and self.d % 64 == 0
-        lib_chunk_of = lambda n: int(self.lib.lrx_flat_ip_bounded_chunk_queries(self.ntotal, self.d, n, k, flags, int(has_xb))) if self.two_pass else 128
+        lib_chunk_of = lambda n: self._lib_chunk_queries(n, k, flags, has_xb)
         lib_chunk = lib_chunk_of(min(Q, chunk))
         # More queries than one library chunk: the chunks are independent searches over the same rows, so they alternate between two
         # internal HIP streams (own workspaces), forked from and joined back into the caller's stream inside this call -- the short
@@ -312,6 +309,23 @@ class FlatIPIndex:
         self._last_search = ((n_last_call - 1) % lib_chunk_of(n_last_call) + 1, k, flags, xb is not None, last_ws, self.ntotal, bool(self.two_pass))   # ... and of its last chunk
         return D, I
 
+    # (search() over this index's rows: the hooks SQFp16Index replaces)
+    def _search_ws_bytes(self, flags: int):
+        if self.two_pass:
+            return lambda n, d, nq, kk: self.lib.lrx_flat_ip_bounded_workspace_bytes(n, d, nq, kk, flags)
+        return self.lib.lrx_flat_ip_workspace_bytes
+
+    def _search_rows(self):
+        """(row stride of the fp32 rows, the tiled fp16 shadow the search streams or None)."""
+        ldx = self._x.stride(0) if self._x.shape[0] else self.d
+        if self.two_pass and self.shadow_f16:
+            self._ensure_shadow()                       # (no-op unless rows were committed while the shadow was switched off)
+        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
+        return ldx, xb
+
+    def _lib_chunk_queries(self, n: int, k: int, flags: int, has_xb: bool) -> int:
+        return int(self.lib.lrx_flat_ip_bounded_chunk_queries(self.ntotal, self.d, n, k, flags, int(has_xb))) if self.two_pass else 128
+
     def _run_chunks(self, q, D, I, k, chunk, fork, lane_ws, ws, start, xb, ldx, flags, row_map, wire_out):
         Q = q.shape[0]
         for j, s in enumerate(range(0, Q, chunk)):
@@ -324,14 +338,17 @@ class FlatIPIndex:
                 stream = C.c_void_p(st.cuda_stream)
             else:
                 stream = _lib.current_stream()
-            if self.two_pass:
-                _lib.check(self.lib.lrx_flat_ip_search_bounded_wire(
-                    _lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(xb), _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k, self.id_base,
-                    _lib.ptr(Dc), _lib.ptr(Ic), _lib.ptr(row_map), _lib.ptr(wire_out[s:s + chunk]) if wire_out is not None else None,
-                    _lib.ptr(ws), ws.numel(), flags, stream))
-            else:
-                _lib.check(self.lib.lrx_flat_ip_search(_lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k,
-                                                       self.id_base, _lib.ptr(Dc), _lib.ptr(Ic), _lib.ptr(ws), ws.numel(), stream))
+            self._search_chunk(qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire_out[s:s + chunk] if wire_out is not None else None)
+
+    def _search_chunk(self, qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire):
+        if self.two_pass:
+            _lib.check(self.lib.lrx_flat_ip_search_bounded_wire(
+                _lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(xb), _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k, self.id_base,
+                _lib.ptr(Dc), _lib.ptr(Ic), _lib.ptr(row_map), _lib.ptr(wire) if wire is not None else None,
+                _lib.ptr(ws), ws.numel(), flags, stream))
+        else:
+            _lib.check(self.lib.lrx_flat_ip_search(_lib.ptr(self._x), self.ntotal, ldx, self.d, _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k,
+                                                   self.id_base, _lib.ptr(Dc), _lib.ptr(Ic), _lib.ptr(ws), ws.numel(), stream))
 
     def range_search(self, q, radius: float):
         """faiss range_search for inner product -> (lims i64[Q+1], D f32[lims[Q]], I i64[lims[Q]]) device tensors: query i's hits are
@@ -402,6 +419,178 @@ class FlatIPIndex:
             _lib.check(self.lib.lrx_flat_ip_bounded_list_counts(_lib.ptr(ws), ntotal, self.d, nq, k, flags, int(has_shadow), _lib.ptr(out),
                                                                 _lib.current_stream()))
         return out.to(torch.int64)
+
+
+
+class SQFp16Index(FlatIPIndex):
+    """fp16 scalar-quantised inner-product shard: the faiss IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT) surface (add / search /
+    reset / ntotal / reconstruct_n / save / load), backed by lrx_sq_fp16_ip_search.  The only resident copy of the rows is their codes
+    c = fp16(x) (round-to-nearest-even, saturating at +-65504 where faiss gives inf) in the tiled layout of FlatIPIndex's shadow: 2 B/element
+    instead of 6.  Scores are (float) of the fp64 sum of q_i * c_i, exact top-k under that score, ties to the lower row, (-FLT_MAX, -1)
+    padding -- for rows that are exactly fp16-representable, bit-identical to FlatIPIndex.  d % 64 == 0.
+    Search chunking, lanes, workspaces and wire_out / row_map are FlatIPIndex's (lrx_sq_fp16_ip_workspace_bytes sizes the workspace).
+    Rows enter through add() (lrx_shard_commit_rows straight from the caller's rows) or through append_slot(n) / commit(n): the slot is a
+    transient fp32 staging view that LrxEncoder.encode_packed recognises (shard_of), so the encoder's last kernel writes the codes and the
+    bounds itself; commit() converts whatever it did not write and releases the staging.  Staging scales with the chunk being added."""
+
+    def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        _lib.require_gpu()
+        if d % 64 != 0:
+            raise ValueError(f"SQFp16Index: d={d} must be a multiple of 64")
+        self.lib = _lib.lib()
+        self.d = d
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.ntotal = 0
+        self.id_base = id_base
+        self._ws = None
+        self._lane_ws: dict = {}
+        self.chunk_lanes = 2
+        self._chunk_streams = None
+        self._last_search = None
+        self._bounds = torch.zeros(2, dtype=torch.float32, device=self.device)   # {max |x|, max |x - fp16(x)|}: R16 <= R + E (include/lrx.h)
+        self.two_pass = True
+        self.shadow_f16 = True
+        self.max_workspace_bytes = 12 << 30
+        self._xb = torch.empty(0, dtype=torch.float16, device=self.device)         # the codes, whole 128-row blocks
+        self._shadow_rows = 0
+        self._fused: list = []
+        self._x = torch.empty(0, d, dtype=torch.float32, device=self.device)       # staging of the open append_slot (rows ntotal ...)
+        self.reserve(capacity)
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        return self._xb.numel() // self.d
+
+    def reserve(self, n_rows: int):
+        need = -(-max(n_rows, 0) // 128) * 128 * self.d
+        if need > self._xb.numel():
+            xb = torch.empty(need, dtype=torch.float16, device=self.device)
+            n_old = min(self._xb.numel(), -(-self.ntotal // 128) * 128 * self.d)
+            if n_old:
+                xb[:n_old].copy_(self._xb[:n_old])
+            self._xb = xb
+
+    def _ensure_shadow(self):
+        pass                                           # (the codes are the rows: always complete)
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """A transient fp32 staging view for rows [ntotal, ntotal + n): write them (the encoder writes codes and bounds itself through
+        shard_of), then commit(n)."""
+        if self.ntotal + n_rows > self.capacity:
+            self.reserve(max(self.ntotal + n_rows, int(self.capacity * 1.5) + 1))
+        if self._x.shape[0] < n_rows:
+            self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))
+            self._set_storage(torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device))
+        self._fused = []
+        return self._x[:n_rows]
+
+    def shard_sink(self, row0: int, n_rows: int):
+        """(codes, first code row, bounds) for staging rows [row0, row0 + n) and a note that their producer maintains them."""
+        self._fused.append((row0, row0 + n_rows))
+        return self._xb, self.ntotal + row0, self._bounds
+
+    def _commit_from(self, x: torch.Tensor, row0: int):
+        if x.shape[0]:
+            _lib.check(self.lib.lrx_shard_commit_rows(_lib.ptr(x), x.stride(0), x.shape[0], self.d, _lib.ptr(self._xb), row0, _lib.ptr(self._bounds),
+                                                      _lib.current_stream()))
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            if n_rows > self._x.shape[0]:
+                raise ValueError(f"commit({n_rows}): only {self._x.shape[0]} staged rows")
+            pos = 0
+            for s, e in sorted(self._fused):
+                s, e = max(s, 0), min(e, n_rows)
+                if e <= pos:
+                    continue
+                if s > pos:
+                    self._commit_from(self._x[pos:s], self.ntotal + pos)
+                pos = max(pos, e)
+            if pos < n_rows:
+                self._commit_from(self._x[pos:n_rows], self.ntotal + pos)
+        self._fused = []
+        self.ntotal += n_rows
+        self._shadow_rows = self.ntotal
+        self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))   # staging released (stream-ordered by the allocator)
+
+    def add(self, x):
+        """faiss add(x f32[n,d]): the codes are written straight from the rows (one device copy when x is not already fp32 on this device)."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(x)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"add: expected [n,{self.d}], got {tuple(x.shape)}")
+        n = x.shape[0]
+        if self.ntotal + n > self.capacity:
+            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        x = x.to(device=self.device, dtype=torch.float32)
+        if x.stride(1) != 1 or (n > 1 and x.stride(0) % 4):
+            x = x.contiguous()
+        self._commit_from(x, self.ntotal)
+        self.ntotal += n
+        self._shadow_rows = self.ntotal
+
+    def refresh_norm_bound(self):
+        pass                                           # (rows are written through commit / add only: the bounds are always current)
+
+    def reset(self):
+        self.ntotal = 0
+        self._shadow_rows = 0
+        self._bounds.zero_()
+        self._fused = []
+        self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))
+
+    def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
+        """Rows [i0, i0 + n) decoded exactly to fp32 (device tensor [n, d])."""
+        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
+            raise ValueError(f"reconstruct_n({i0}, {n}) outside [0, {self.ntotal})")
+        out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
+        if n:
+            _lib.check(self.lib.lrx_sq_fp16_decode_rows(_lib.ptr(self._xb), i0, n, self.d, _lib.ptr(out), self.d, _lib.current_stream()))
+        return out
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
+    def codes(self) -> torch.Tensor:
+        """The codes as a row-major [ntotal, d] fp16 tensor (a copy: the stored layout is tiled)."""
+        return self.shadow_rows()
+
+    # -- persistence (faiss.write_index / read_index of an IndexScalarQuantizer(QT_fp16), see index_io.py) -----------
+    def save(self, fname: str, chunk_rows: int = 262144):
+        from .index_io import write_sq_fp16
+        write_sq_fp16(fname, (self.reconstruct_n(s, min(chunk_rows, self.ntotal - s)).half().cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
+                      self.d, self.ntotal)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144) -> "SQFp16Index":
+        from .index_io import read_sq_fp16
+        import numpy as np
+        mm = read_sq_fp16(fname)
+        idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
+        for s in range(0, mm.shape[0], chunk_rows):
+            e = min(s + chunk_rows, mm.shape[0])
+            idx.add(torch.from_numpy(np.array(mm[s:e], copy=True)).to(idx.device).float())   # fp16 -> fp32 -> fp16: exact
+        return idx
+
+    # -- search (FlatIPIndex.search: chunking, lanes, workspaces; these hooks point it at the codes) ----------------
+    def _search_ws_bytes(self, flags: int):
+        return lambda n, d, nq, kk: self.lib.lrx_sq_fp16_ip_workspace_bytes(n, d, nq, kk, flags)
+
+    def _search_rows(self):
+        return self.d, self._xb
+
+    def _lib_chunk_queries(self, n: int, k: int, flags: int, has_xb: bool) -> int:
+        return int(self.lib.lrx_sq_fp16_ip_chunk_queries(self.ntotal, self.d, n, k, flags))
+
+    def _search_chunk(self, qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire):
+        _lib.check(self.lib.lrx_sq_fp16_ip_search(
+            _lib.ptr(self._xb), self.ntotal, self.d, _lib.ptr(self._bounds), _lib.ptr(qc), qc.shape[0], k, self.id_base, _lib.ptr(Dc), _lib.ptr(Ic),
+            _lib.ptr(row_map), _lib.ptr(wire) if wire is not None else None, _lib.ptr(ws), ws.numel(), flags, stream))
+
+    def range_search(self, q, radius: float):
+        raise NotImplementedError("SQFp16Index.range_search is not served yet (a follow-up: the range search's list path over the codes)")
 
 
 def merge_topk(D_parts: torch.Tensor, I_parts: torch.Tensor):

@@ -16,7 +16,20 @@ own serialisation of IndexFlat as published in faiss/impl/index_write.cpp (v1.7.
 so a shard written here is a regular Faiss flat index file and a `{prefix}.flat.faiss` written by the reference loads here.
 Faiss itself is not installed in this image: the layout is **unverified against a Faiss build** (round trip and header bytes
 are tested).  Multi-rank: every rank writes `{prefix}.rank{r}-of-{R}.{ext}.faiss/.tsv` holding its own rows, so a 10 M-document
-index reloads per rank without re-encoding and without one rank ever holding the whole matrix."""
+index reloads per rank without re-encoding and without one rank ever holding the whole matrix.
+
+An fp16 scalar-quantised shard (SQFp16Index) is written as Faiss's serialisation of IndexScalarQuantizer, same source:
+
+    u32   fourcc 'IxSQ'
+          the index header of 'IxFI' above (d, ntotal, two dummies, is_trained, metric_type = 0)
+    i32   qtype = 4                           (ScalarQuantizer::QT_fp16)
+    i32   rangestat = 0,  f32 rangestat_arg = 0
+    u64   d,  u64 code_size = 2 d
+    u64   0                                   (`trained`: an empty float vector -- QT_fp16 trains nothing)
+    u64   n_bytes = ntotal * 2 d              (WRITEVECTOR of the codes)
+    f16   codes[ntotal * d]                   row-major, little-endian
+
+Like the flat layout it is **unverified against a Faiss build**.  Files with any other qtype are rejected."""
 from __future__ import annotations
 
 import csv
@@ -67,6 +80,58 @@ def read_flat_ip(fname: str) -> np.memmap:
     if metric != 0 or d <= 0 or ntotal < 0 or n_floats != ntotal * d or size != HEADER_BYTES + 4 * n_floats:
         raise ValueError(f"{fname}: inconsistent flat index header (d={d}, ntotal={ntotal}, floats={n_floats}, metric={metric}, bytes={size})")
     return np.memmap(fname, dtype="<f4", mode="r", offset=HEADER_BYTES, shape=(ntotal, d))
+
+
+FOURCC_SQ = b"IxSQ"
+QT_FP16 = 4
+_SQ = struct.Struct("<iifQQ")            # qtype, rangestat, rangestat_arg, d, code_size  (28 bytes, packed)
+SQ_HEADER_BYTES = _HEADER.size + _SQ.size + 8 + 8   # + empty `trained` vector + u64 code bytes
+
+
+def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
+    """blocks: fp16 [n_i, d] arrays (the codes) in row order, sum n_i == ntotal."""
+    tmp = fname + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(_HEADER.pack(FOURCC_SQ, d, ntotal, 1 << 20, 1 << 20, 1, 0))
+        f.write(_SQ.pack(QT_FP16, 0, 0.0, d, 2 * d))
+        f.write(struct.pack("<Q", 0))
+        f.write(struct.pack("<Q", ntotal * 2 * d))
+        rows = 0
+        for b in blocks:
+            b = np.ascontiguousarray(b, dtype="<f2")
+            if b.ndim != 2 or b.shape[1] != d:
+                raise ValueError(f"write_sq_fp16: block {b.shape} does not match d={d}")
+            f.write(b.tobytes())
+            rows += b.shape[0]
+        if rows != ntotal:
+            raise ValueError(f"write_sq_fp16: wrote {rows} rows, header says {ntotal}")
+    os.replace(tmp, fname)
+
+
+def read_sq_fp16(fname: str) -> np.memmap:
+    """-> read-only memmap fp16 [ntotal, d] of the codes (no copy)."""
+    size = os.path.getsize(fname)
+    if size < _HEADER.size + _SQ.size + 8:
+        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
+    with open(fname, "rb") as f:
+        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
+        if fourcc != FOURCC_SQ:
+            raise ValueError(f"{fname}: fourcc {fourcc!r} is not a scalar-quantiser index ('IxSQ')")
+        qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
+        if qtype != QT_FP16:
+            raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served (only QT_fp16 = {QT_FP16})")
+        (n_trained,) = struct.unpack("<Q", f.read(8))
+        off = _HEADER.size + _SQ.size + 8 + 4 * n_trained
+        f.seek(off)
+        tail = f.read(8)
+    if len(tail) < 8:
+        raise ValueError(f"{fname}: truncated scalar-quantiser index header")
+    (n_bytes,) = struct.unpack("<Q", tail)
+    off += 8
+    if metric != 0 or d <= 0 or ntotal < 0 or sq_d != d or code_size != 2 * d or n_bytes != ntotal * 2 * d or size != off + n_bytes:
+        raise ValueError(f"{fname}: inconsistent QT_fp16 index (d={d}, ntotal={ntotal}, sq.d={sq_d}, code_size={code_size}, "
+                         f"code bytes={n_bytes}, metric={metric}, file bytes={size})")
+    return np.memmap(fname, dtype="<f2", mode="r", offset=off, shape=(ntotal, d))
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

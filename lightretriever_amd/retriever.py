@@ -2,6 +2,7 @@
 
     FaissIndex          <- retriever/faiss_index.py:20-73      (build / search / reset over the HBM-resident FlatIPIndex)
     FlatIPFaissSearch   <- retriever/faiss_search.py:46-293, :477-510   (BEIR-style dense searcher)
+    SQFaissSearch       <- retriever/faiss_search.py:567-611             (QT_fp16 inner product only, over SQFp16Index)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; sparse + fusion out of scope)
 
 Design differences, results preserved: corpus embeddings are encoded straight into the index shard (no CPU round trip, no
@@ -23,7 +24,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .index import FlatIPIndex, merge_topk
+from .index import FlatIPIndex, SQFp16Index, merge_topk
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -199,18 +200,21 @@ class DenseRetrievalFaissSearch:
 
 
 class FlatIPFaissSearch(DenseRetrievalFaissSearch):
+    index_cls = FlatIPIndex          # the shard type every index / load builds
+    serves_rpc_shards = True         # _chunked_dense_search may place the shards on the reference's RPC workers (rpc_shards: FlatIPIndex)
+
     def index(self, corpus_emb, corpus_ids):
         """Index already-encoded embeddings (Tensor on any device / ndarray) -- faiss_search.py:490-504."""
         self._create_mapping_ids(corpus_ids)
         self.dim_size = corpus_emb.shape[1]
         rows = [self.mapping.get(c, c) for c in corpus_ids]
-        self.faiss_index = FaissIndex.build(rows, corpus_emb)
+        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=self.index_cls(corpus_emb.shape[1], capacity=len(rows)))
 
     def _index_in_place(self, docs: list, corpus_ids: list, dim: int):
         """Encode a corpus chunk straight into a fresh shard (embeddings never leave HBM)."""
         self._create_mapping_ids(corpus_ids)
         self.dim_size = dim
-        idx = FlatIPIndex(dim, capacity=len(docs))
+        idx = self.index_cls(dim, capacity=len(docs))
         if not docs:                                  # a rank without a batch in this chunk: empty shard, searches return padding
             self.faiss_index = FaissIndex(idx, None)
             return None
@@ -228,7 +232,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
     def load(self, input_dir: str, prefix: str = "my-index", ext: str = "flat"):
         """faiss_search.py:478-488: id map + index file -> HBM shard of this rank."""
         path, passage_ids = self._load(input_dir, prefix, ext)
-        idx = FlatIPIndex.load(path)
+        idx = self.index_cls.load(path)
         if passage_ids and len(passage_ids) != idx.ntotal:
             raise ValueError(f"{path}: {idx.ntotal} rows but {len(passage_ids)} ids in the map")
         self.dim_size = idx.d
@@ -239,6 +243,33 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
 
     def get_index_name(self):
         return "flat_faiss_index"
+
+
+class SQFaissSearch(FlatIPFaissSearch):
+    """faiss_search.py:567-611 with its default quantizer: IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT), served by SQFp16Index --
+    2 B/element resident, exact inner products of the fp32 query with the decoded codes.  index / _index_in_place / load / save behave like
+    FlatIPFaissSearch's with that shard.  Other quantizer types and metrics are not served; neither are shards on RPC workers."""
+    index_cls = SQFp16Index
+    serves_rpc_shards = False
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, similarity_metric=0, quantizer_type: str = "QT_fp16",
+                 **kwargs):
+        if quantizer_type != "QT_fp16":
+            raise NotImplementedError(f"SQFaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_fp16')")
+        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
+            raise NotImplementedError(f"SQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.similarity_metric = 0
+        self.qname = quantizer_type
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: str = "sq"):
+        super().load(input_dir, prefix, ext)
+
+    def save(self, output_dir: str, prefix: str = "my-index", ext: str = "sq"):
+        super().save(output_dir, prefix, ext)
+
+    def get_index_name(self):
+        return "sq_faiss_index"
 
 
 class HybridSearch:
@@ -259,7 +290,12 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        self.dense_search = FlatIPFaissSearch(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu)
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default) and "sq" (QT_fp16) are served; anything else is served flat
+        faiss_search_map = kwargs.get("faiss_search_map", "flat")
+        den_cls = SQFaissSearch if faiss_search_map == "sq" else FlatIPFaissSearch
+        if faiss_search_map not in ("flat", "sq"):
+            logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
+        self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu)
         self.return_all_results = return_all_results
         self.mteb_model_meta = None
 
@@ -434,6 +470,9 @@ def _chunked_dense_search(searcher: FlatIPFaissSearch, query_embs, query_ids: li
         rpc_names = rpc_shards.rpc_workers()
         if len(rpc_names) <= 1 or "model" not in rpc_shards._WORKER or on_chunk is not None:
             rpc_names = []                            # (with a sparse engine the calling rank encodes everything itself)
+        elif not getattr(searcher, "serves_rpc_shards", True):
+            raise NotImplementedError(f"{type(searcher).__name__}: shards on RPC workers are not served (rpc_shards builds flat shards); "
+                                      "use a single-process or one-process-per-GPU launch")
     for s in range(0, n, searcher.corpus_chunk_size):
         e = min(s + searcher.corpus_chunk_size, n)
         logger.info("Encoding Batch %d/%d...", s // searcher.corpus_chunk_size + 1, -(-n // searcher.corpus_chunk_size))
