@@ -523,6 +523,38 @@ int lrx_shard_commit_rows(const float* X, int64_t ldx, int64_t n_rows, int32_t d
  * coalesced 1-KiB request straight into registers (no LDS staging of the corpus side).  (Round 2 also accepted a row-major bf16
  * shadow; it is gone: the tiled layout was faster at every shape and fp16 gives the narrower band.)                               */
 
+/* (added in ABI 8, additively) PRODUCT-QUANTISED inner-product index (faiss IndexPQ(d, M, nbits = 8, METRIC_INNER_PRODUCT)), DESIGN §5.4.3.
+ * ksub = 256 centroids per sub-space, dsub = dim / M (dim % M == 0).  centroids: fp32 C[M][256][dsub], faiss's layout
+ * centroids[(m * 256 + j) * dsub + i].  The contract, which fixes (D, I) given the centroids and the codes:
+ *   code[m]       = argmin_j sum_i (x[m dsub + i] - C[m][j][i])^2, each term an fp64 subtract and square, summed in order over i with
+ *                   separate fp64 adds (no contraction); ties to the lower j.
+ *   LUT[q][m][j]  = (float) sum_i (double) q[m dsub + i] * (double) C[m][j][i], in order over i (the products are exact in fp64, so a
+ *                   contracted fma rounds the same).
+ *   s(q, r)       = ((0.f + LUT[q][0][c0]) + LUT[q][1][c1]) + ... + LUT[q][M-1][c_{M-1}]: fp32 adds in ascending m.
+ *   top-k         = the flat index's rules: score descending, ties to the lower row, (-FLT_MAX, -1) padding when k > n_rows, 1 <= k <= 2048.
+ * faiss's own arithmetic (its LUT and accumulation order depend on the ISA) is not reproduced and cannot be pinned here.
+ * THE CODE LAYOUT: Mp = M rounded up to 16; the codes are an array of 128-row blocks of 128 Mp bytes, each block sub-space-group major
+ *   [Mp / 16][128 rows][16 bytes]: code m of row r sits at byte  (r / 128) 128 Mp + (m / 16) 2048 + (r % 128) 16 + m % 16
+ * -- a lane of the scan loads the 16 codes of one group of its row with one 16-byte load and a wave's 64 loads are 1 KiB contiguous.  The
+ * bytes of sub-spaces m >= M are padding (never read as codes).  Allocated for whole 128-row blocks.
+ * lrx_pq_ip_search: LUT (lrx_pq_lut) -> k_pq_scan (the query's table in LDS, per-row lookups, [Q, rows] fp32 score matrix of a row chunk of
+ * up to 4 Mi rows + 128-row block maxima) -> the flat index's exact top-k selection; row chunks are merged with lrx_merge_topk's kernel.
+ * out_ids: id_base + row, or row_map[row] when row_map != NULL (a shard-local row -> its global row, as lrx_pack_topk).  Queries are walked
+ * in chunks of lrx_pq_ip_chunk_queries (score matrices of <= 1 GiB); the workspace (lrx_pq_ip_workspace_bytes) holds one chunk.  flags: 0. */
+size_t lrx_pq_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k);
+int32_t lrx_pq_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k);
+int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
+                     int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
+                     size_t workspace_bytes, int32_t flags, void* stream);
+/* Encode n_rows fp32 rows (row stride ldx >= dim) into rows row0 .. of the blocked codes (dim / M <= 64). */
+int lrx_pq_encode(const float* x, int64_t n_rows, int64_t ldx, const float* centroids, int32_t dim, int32_t M, void* codes, int64_t row0,
+                  void* stream);
+/* Rows [row0, row0 + n_rows) decoded to fp32: out[i * ldo + m * dsub + e] = C[m][code_m][e] (ldo >= dim). */
+int lrx_pq_decode_rows(const void* codes, int64_t row0, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, float* out,
+                       int64_t ldo, void* stream);
+/* The lookup tables alone: lut[n_queries][M][256] fp32 (tests). */
+int lrx_pq_lut(const float* q, int32_t n_queries, const float* centroids, int32_t dim, int32_t M, float* lut, void* stream);
+
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);
 int lrx_flat_ip_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries,

@@ -4,6 +4,7 @@
 //     lrx_search_filter.h   A. score / filter kernels          lrx_search_select.h   B. selection
 //     lrx_search_bounded.h  C. error bound, threshold, fused   lrx_search_refine.h   C. band refine, row-grouped rescoring, part merge
 //     lrx_search_range.h    F. range search: threshold from a given radius, exact rescoring, row-ordered output (host driver: lrx_flat_ip_range_search)
+//     lrx_search_pq.h       G. product-quantised index: encode, lookup tables, ADC scan -> k_topk_select / merge, decode (with its host driver)
 // Map of the unit:
 //
 //  A. Score kernels (what a search streams the shard through)
@@ -1205,3 +1206,5 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
   LRX_LAUNCH_CHECK();
   return LRX_OK;
 }
+
+#include "lrx_search_pq.h"       // product-quantised index: encode, lookup tables, ADC scan (-> k_topk_select, merge_launch), decode

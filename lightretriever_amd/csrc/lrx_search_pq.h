@@ -1,0 +1,302 @@
+// liblrx search, part 6 -- PRODUCT-QUANTISED inner-product index (faiss IndexPQ(d, M, 8, METRIC_INNER_PRODUCT)), map: section G.
+// Part of the ONE translation unit lrx_search.hip (included at its end: it reuses k_topk_select, merge_launch and lrx_cu_count).  Not a
+// stand-alone header.  Contract and code layout: include/lrx.h (lrx_pq_ip_search), DESIGN.md §5.4.3.
+//
+//     k_pq_encode    code[m] = argmin_j sum_i (x_i - C[m][j][i])^2, fp64 terms summed in order, ties to the lower j (add() and k-means)
+//     k_pq_lut       LUT[q][m][j] = (float) sum_i (double) q_i (double) C[m][j][i]
+//     k_pq_scan      THE HOT PATH: s(q, r) = fp32 sum of LUT[q][m][code_m(r)] in ascending m, the query's table in LDS; writes the
+//                    [Q, ld] score matrix of a row chunk and its 128-row block maxima -> k_topk_select (-> merge_launch across row chunks)
+//     k_pq_decode    rows from their codes (reconstruct_n)
+//     k_pq_map_ids   local rows -> id_base + row or row_map[row]
+#pragma once
+
+#define PQ_KSUB 256
+#define PQ_BLK 128            // rows per code block
+#define PQ_GRP 16             // sub-spaces per 16-byte piece of a row
+#define PQ_SCAN_THREADS 1024  // one row per lane, 1024-row tiles (8 code blocks)
+#define PQ_SCAN_MC 128        // sub-spaces whose tables sit in LDS at once (128 KiB); more are scanned in passes over the tile
+#define PQ_ENC_ROWS 256
+#define PQ_ENC_MAX_DSUB 64
+#define PQ_ROW_CHUNK (1ll << 22)       // rows per score matrix (16 MiB per query)
+#define PQ_MATRIX_BYTES (1ll << 30)    // score matrix budget of one query chunk
+
+static __host__ __device__ __forceinline__ int pq_mp(int M) { return (M + PQ_GRP - 1) / PQ_GRP * PQ_GRP; }
+// byte offset of code m of row r in the blocked layout (include/lrx.h): block r / 128, 16-sub-space group m / 16, row r % 128, byte m % 16
+static __host__ __device__ __forceinline__ int64_t pq_code_off(int64_t r, int m, int Mp) {
+  return (r / PQ_BLK) * PQ_BLK * Mp + (int64_t)(m / PQ_GRP) * (PQ_BLK * PQ_GRP) + (r % PQ_BLK) * PQ_GRP + (m % PQ_GRP);
+}
+
+// One thread per (row, sub-space): the sub-space's 256 x dsub centroids and the workgroup's 256 row pieces are staged in LDS (row pieces
+// padded by one float: lane t reads row t's piece, stride dsub + 1 keeps the banks apart; centroid reads are broadcasts).  The distance is
+// formed exactly as the contract writes it: fp64 subtract, square, add, in order over i -- no contraction (a fused multiply-add would round
+// differently from numpy's separate operations), so the codes equal the numpy yardstick's bit for bit.
+__global__ void __launch_bounds__(PQ_ENC_ROWS)
+k_pq_encode(const float* __restrict__ X, int64_t n_rows, int64_t ldx, const float* __restrict__ C, int dsub, int Mp,
+            uint8_t* __restrict__ codes, int64_t row0) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) float pq_enc_smem[];
+  float* Cs = pq_enc_smem;                          // [256][dsub]
+  float* Xs = pq_enc_smem + PQ_KSUB * dsub;         // [256][dsub + 1]
+  const int m = blockIdx.y, tid = threadIdx.x;
+  const int64_t r_base = (int64_t)blockIdx.x * PQ_ENC_ROWS;
+  const float* Cm = C + (int64_t)m * PQ_KSUB * dsub;
+  for (int e = tid; e < PQ_KSUB * dsub; e += PQ_ENC_ROWS) Cs[e] = Cm[e];
+  for (int e = tid; e < PQ_ENC_ROWS * dsub; e += PQ_ENC_ROWS) {
+    const int rr = e / dsub, i = e - rr * dsub;
+    const int64_t r = r_base + rr;
+    Xs[rr * (dsub + 1) + i] = r < n_rows ? X[r * ldx + (int64_t)m * dsub + i] : 0.f;
+  }
+  __syncthreads();
+  const int64_t r = r_base + tid;
+  if (r >= n_rows) return;
+  const float* xr = Xs + tid * (dsub + 1);
+  double best = 0.0;
+  int bj = 0;
+  for (int j = 0; j < PQ_KSUB; ++j) {
+    const float* cj = Cs + j * dsub;
+    double acc = 0.0;
+    for (int i = 0; i < dsub; ++i) {
+      const double t = (double)xr[i] - (double)cj[i];
+      acc = acc + t * t;
+    }
+    if (j == 0 || acc < best) { best = acc; bj = j; }   // strict: ties keep the lower j
+  }
+  codes[pq_code_off(row0 + r, m, Mp)] = (uint8_t)bj;
+}
+
+// One thread per (query, sub-space, centroid).  The fp32 x fp32 products are exact in fp64, so a contracted fma(q, c, acc) rounds exactly
+// like acc + q * c: contraction cannot change the table.  The sum runs in order over i, one final rounding to fp32.
+__global__ void __launch_bounds__(256)
+k_pq_lut(const float* __restrict__ q, int nq, const float* __restrict__ C, int dim, int M, int dsub, float* __restrict__ lut) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)nq * M * PQ_KSUB) return;
+  const int j = (int)(t % PQ_KSUB);
+  const int m = (int)((t / PQ_KSUB) % M);
+  const int qi = (int)(t / ((int64_t)PQ_KSUB * M));
+  const float* qm = q + (int64_t)qi * dim + (int64_t)m * dsub;
+  const float* cj = C + ((int64_t)m * PQ_KSUB + j) * dsub;
+  double acc = 0.0;
+  for (int i = 0; i < dsub; ++i) acc += (double)qm[i] * (double)cj[i];
+  lut[t] = (float)acc;
+}
+
+// The ADC scan.  Grid (gx, queries): workgroup (x, q) keeps query q's table -- up to PQ_SCAN_MC sub-spaces of it, 1 KiB each -- in LDS and
+// walks the 1024-row tiles x, x + gx, ...; lane t scores row 1024 tile + t.  Its codes are one 16-byte load per 16 sub-spaces (64 lanes:
+// 1 KiB contiguous, the next group prefetched while the current one is looked up); the score is ((0 + LUT[0][c0]) + LUT[1][c1]) + ... in
+// ascending m, fp32.  More than PQ_SCAN_MC sub-spaces: the table is loaded in passes per tile and the partial sum stays in a register, so
+// the order of the adds is the same.  Writes scores[q][r] for r < n_rows and the maximum of every 128-row block over its valid rows.
+__global__ void __launch_bounds__(PQ_SCAN_THREADS)
+k_pq_scan(const uint8_t* __restrict__ codes, int64_t n_rows, int M, int Mp, const float* __restrict__ lut, float* __restrict__ scores, int64_t ld,
+          float* __restrict__ blkmax, int nblk_ld) {
+  extern __shared__ __attribute__((aligned(16))) float pq_lut_s[];
+  __shared__ float wmax[PQ_SCAN_THREADS / 64];
+  const int tid = threadIdx.x, qi = blockIdx.y;
+  const float* lq = lut + (int64_t)qi * M * PQ_KSUB;
+  const int mc = M < PQ_SCAN_MC ? M : PQ_SCAN_MC;
+  const bool one_pass = mc == M;
+  const int64_t ntiles = (n_rows + PQ_SCAN_THREADS - 1) / PQ_SCAN_THREADS;
+  if (one_pass) {
+    for (int e = tid * 4; e < M * PQ_KSUB; e += PQ_SCAN_THREADS * 4) *(float4*)(pq_lut_s + e) = *(const float4*)(lq + e);
+    __syncthreads();
+  }
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t r = tile * PQ_SCAN_THREADS + tid;
+    const bool valid = r < n_rows;
+    const uint8_t* rc = codes + (r / PQ_BLK) * PQ_BLK * Mp + (r % PQ_BLK) * PQ_GRP;
+    float acc = 0.f;
+    for (int m0 = 0; m0 < M; m0 += mc) {
+      const int m1 = m0 + mc < M ? m0 + mc : M;
+      if (!one_pass) {
+        __syncthreads();
+        for (int e = tid * 4; e < (m1 - m0) * PQ_KSUB; e += PQ_SCAN_THREADS * 4)
+          *(float4*)(pq_lut_s + e) = *(const float4*)(lq + (int64_t)m0 * PQ_KSUB + e);
+        __syncthreads();
+      }
+      if (valid) {
+        uint4 cur = *(const uint4*)(rc + (int64_t)(m0 / PQ_GRP) * (PQ_BLK * PQ_GRP));
+        for (int g = m0; g < m1; g += PQ_GRP) {
+          uint4 nxt = cur;
+          if (g + PQ_GRP < m1) nxt = *(const uint4*)(rc + (int64_t)((g + PQ_GRP) / PQ_GRP) * (PQ_BLK * PQ_GRP));
+          const float* tg = pq_lut_s + (g - m0) * PQ_KSUB;
+          const uint32_t w[4] = {cur.x, cur.y, cur.z, cur.w};
+          if (g + PQ_GRP <= m1) {
+#pragma unroll
+            for (int u = 0; u < PQ_GRP; ++u) acc += tg[u * PQ_KSUB + ((w[u >> 2] >> (8 * (u & 3))) & 255u)];
+          } else {                                     // (M % 16 != 0: the last group's padding bytes are not sub-spaces)
+#pragma unroll
+            for (int u = 0; u < PQ_GRP; ++u)
+              if (g + u < m1) acc += tg[u * PQ_KSUB + ((w[u >> 2] >> (8 * (u & 3))) & 255u)];
+          }
+          cur = nxt;
+        }
+      }
+    }
+    if (valid) scores[(int64_t)qi * ld + r] = acc;
+    const float wm = wave_max(valid ? acc : -INFINITY);
+    if ((tid & 63) == 0) wmax[tid >> 6] = wm;
+    __syncthreads();
+    if (tid < PQ_SCAN_THREADS / PQ_BLK) {
+      const int64_t b = tile * (PQ_SCAN_THREADS / PQ_BLK) + tid;
+      if (b * PQ_BLK < n_rows) blkmax[(int64_t)qi * nblk_ld + b] = fmaxf(wmax[2 * tid], wmax[2 * tid + 1]);
+    }
+    __syncthreads();
+  }
+}
+
+// out[i * ldo + m * dsub + e] = C[m][code_m(row0 + i)][e]: one thread per output element.
+__global__ void __launch_bounds__(256)
+k_pq_decode(const uint8_t* __restrict__ codes, int64_t row0, int64_t n_rows, const float* __restrict__ C, int dim, int dsub, int Mp,
+            float* __restrict__ out, int64_t ldo) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_rows * dim) return;
+  const int64_t i = t / dim;
+  const int col = (int)(t - i * dim), m = col / dsub;
+  const int c = codes[pq_code_off(row0 + i, m, Mp)];
+  out[i * ldo + col] = C[((int64_t)m * PQ_KSUB + c) * dsub + (col - m * dsub)];
+}
+
+__global__ void k_pq_map_ids(int64_t* __restrict__ ids, int64_t n, int64_t id_base, const int64_t* __restrict__ row_map) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const int64_t r = ids[t];
+  if (r >= 0) ids[t] = row_map != nullptr ? row_map[r] : id_base + r;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+struct PQPlan {
+  int64_t rc, ld;         // rows per score matrix, its row stride
+  int nblk_ld, qc;        // block maxima stride, queries per chunk
+  bool merge;             // more than one row chunk: running top-k merged with each chunk's
+  size_t lut_off, sc_off, bm_off, part_s_off, part_i_off, total;
+};
+
+static PQPlan pq_plan(int64_t n_rows, int32_t M, int32_t n_queries, int32_t k) {
+  PQPlan p;
+  p.rc = n_rows < PQ_ROW_CHUNK ? (n_rows > 0 ? n_rows : 1) : PQ_ROW_CHUNK;
+  p.ld = (p.rc + 63) & ~(int64_t)63;
+  p.nblk_ld = ((int)lrx_cdiv(p.rc, PQ_BLK) + 3) & ~3;
+  p.merge = n_rows > PQ_ROW_CHUNK;
+  const int64_t per_q = p.ld * 4 + (int64_t)p.nblk_ld * 4;
+  int64_t qc = PQ_MATRIX_BYTES / per_q;
+  const int64_t nq = n_queries > 0 ? n_queries : 1;
+  p.qc = (int)(qc < 1 ? 1 : (qc > nq ? nq : qc));
+  const size_t q = (size_t)p.qc;
+  p.lut_off = 0;
+  p.sc_off = align256(q * M * PQ_KSUB * 4);
+  p.bm_off = p.sc_off + align256(q * (size_t)p.ld * 4);
+  p.part_s_off = p.bm_off + align256(q * (size_t)p.nblk_ld * 4);
+  p.part_i_off = p.part_s_off + (p.merge ? align256(2 * q * k * 4) : 0);
+  p.total = p.part_i_off + (p.merge ? align256(2 * q * k * 8) : 0);
+  return p;
+}
+
+extern "C" size_t lrx_pq_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k) {
+  (void)dim;
+  return pq_plan(n_rows, M > 0 ? M : 1, n_queries, k).total;
+}
+
+extern "C" int32_t lrx_pq_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k) {
+  (void)dim;
+  return pq_plan(n_rows, M > 0 ? M : 1, n_queries, k).qc;
+}
+
+extern "C" int lrx_pq_lut(const float* q, int32_t n_queries, const float* centroids, int32_t dim, int32_t M, float* lut, void* stream) {
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "pq_lut: dim=%d is not a multiple of M=%d", dim, M);
+  if (n_queries <= 0) return LRX_OK;
+  const int64_t n = (int64_t)n_queries * M * PQ_KSUB;
+  hipLaunchKernelGGL(k_pq_lut, dim3((unsigned)lrx_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, q, n_queries, centroids, dim, M, dim / M, lut);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
+extern "C" int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
+                                int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
+                                size_t workspace_bytes, int32_t flags, void* stream) {
+  (void)flags;
+  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "pq_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32) - 1, "pq_ip_search: shard rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "pq_ip_search: dim=%d is not a multiple of M=%d", dim, M);
+  if (n_queries <= 0) return LRX_OK;
+  const PQPlan p = pq_plan(n_rows, M, n_queries, k);
+  if (workspace_bytes < p.total) {
+    lrx_set_error("pq_ip_search: workspace %zu B < required %zu B", workspace_bytes, p.total);
+    return LRX_ERR_WORKSPACE;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* lut = (float*)(ws + p.lut_off);
+  float* sc = (float*)(ws + p.sc_off);
+  float* bm = (float*)(ws + p.bm_off);
+  float* part_s = (float*)(ws + p.part_s_off);
+  int64_t* part_i = (int64_t*)(ws + p.part_i_off);
+  const int Mp = pq_mp(M);
+  const int mc = M < PQ_SCAN_MC ? M : PQ_SCAN_MC;
+  const size_t smem = (size_t)mc * PQ_KSUB * 4;
+  LRX_HIP(hipFuncSetAttribute((const void*)k_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  const int ncu = lrx_cu_count();
+  for (int32_t q0 = 0; q0 < n_queries; q0 += p.qc) {
+    const int nq = n_queries - q0 < p.qc ? n_queries - q0 : p.qc;
+    float* os = out_scores + (int64_t)q0 * k;
+    int64_t* oi = out_ids + (int64_t)q0 * k;
+    int rc = lrx_pq_lut(q + (int64_t)q0 * dim, nq, centroids, dim, M, lut, stream);
+    if (rc != LRX_OK) return rc;
+    int64_t r0 = 0;
+    do {
+      const int64_t nr = n_rows - r0 < p.rc ? n_rows - r0 : p.rc;
+      const int64_t ntiles = lrx_cdiv(nr, PQ_SCAN_THREADS);
+      const int nblk = (int)lrx_cdiv(nr, PQ_BLK);
+      if (nr > 0) {
+        int64_t gx = lrx_cdiv(2 * (int64_t)ncu, nq);
+        gx = gx > ntiles ? ntiles : gx;
+        hipLaunchKernelGGL(k_pq_scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, s,
+                           (const uint8_t*)codes + (r0 / PQ_BLK) * PQ_BLK * Mp, nr, M, Mp, (const float*)lut, sc, p.ld, bm, p.nblk_ld);
+        LRX_LAUNCH_CHECK();
+      }
+      // first chunk: straight into the output; later chunks: into part 1, merged with the running result (copied to part 0)
+      const bool into_part = r0 > 0;
+      hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)sc, p.ld, nr, k, r0, (const float*)bm, nblk, p.nblk_ld,
+                         into_part ? part_s + (int64_t)nq * k : os, into_part ? part_i + (int64_t)nq * k : oi, (const int*)nullptr, (const int*)nullptr);
+      LRX_LAUNCH_CHECK();
+      if (into_part) {
+        LRX_HIP(hipMemcpyAsync(part_s, os, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, s));
+        LRX_HIP(hipMemcpyAsync(part_i, oi, (size_t)nq * k * 8, hipMemcpyDeviceToDevice, s));
+        rc = merge_launch(part_s, part_i, nullptr, 2, nq, k, os, oi, stream);
+        if (rc != LRX_OK) return rc;
+      }
+      r0 += nr;
+    } while (r0 < n_rows);
+    const int64_t n_out = (int64_t)nq * k;
+    hipLaunchKernelGGL(k_pq_map_ids, dim3((unsigned)lrx_cdiv(n_out, 256)), dim3(256), 0, s, oi, n_out, id_base, row_map);
+    LRX_LAUNCH_CHECK();
+  }
+  return LRX_OK;
+}
+
+extern "C" int lrx_pq_encode(const float* x, int64_t n_rows, int64_t ldx, const float* centroids, int32_t dim, int32_t M, void* codes, int64_t row0,
+                             void* stream) {
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "pq_encode: dim=%d is not a multiple of M=%d", dim, M);
+  LRX_CHECK_ARG(dim / M <= PQ_ENC_MAX_DSUB, "pq_encode: dsub=%d > %d is not served", dim / M, PQ_ENC_MAX_DSUB);
+  LRX_CHECK_ARG(n_rows >= 0 && row0 >= 0 && ldx >= dim, "pq_encode: bad rows (n_rows=%lld, row0=%lld, ldx=%lld)", (long long)n_rows,
+                (long long)row0, (long long)ldx);
+  if (n_rows == 0) return LRX_OK;
+  const int dsub = dim / M;
+  const size_t smem = ((size_t)PQ_KSUB * dsub + (size_t)PQ_ENC_ROWS * (dsub + 1)) * 4;
+  LRX_HIP(hipFuncSetAttribute((const void*)k_pq_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL(k_pq_encode, dim3((unsigned)lrx_cdiv(n_rows, PQ_ENC_ROWS), (unsigned)M), dim3(PQ_ENC_ROWS), smem, (hipStream_t)stream, x, n_rows,
+                     ldx, centroids, dsub, pq_mp(M), (uint8_t*)codes, row0);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
+extern "C" int lrx_pq_decode_rows(const void* codes, int64_t row0, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, float* out,
+                                  int64_t ldo, void* stream) {
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0 && ldo >= dim, "pq_decode_rows: dim=%d, M=%d, ldo=%lld", dim, M, (long long)ldo);
+  if (n_rows <= 0) return LRX_OK;
+  const int64_t n = n_rows * dim;
+  hipLaunchKernelGGL(k_pq_decode, dim3((unsigned)lrx_cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)codes, row0, n_rows, centroids,
+                     dim, dim / M, pq_mp(M), out, ldo);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}

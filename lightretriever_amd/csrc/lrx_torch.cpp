@@ -280,6 +280,33 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_topk(const at::Tensor&
   return {d, i, w};
 }
 
+// Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
+// centroids [M, 256, D / M] fp32.  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
+                                              int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(centroids, "centroids", at::kFloat, 3);
+  const int64_t dim = q.size(1), M = centroids.size(0);
+  TORCH_CHECK(q.is_contiguous() && centroids.is_contiguous() && centroids.size(1) == 256 && M > 0 && dim % M == 0 && centroids.size(2) == dim / M && n_rows >= 0,
+              "pq_ip_topk: q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
+  const int64_t mp = (M + 15) / 16 * 16;
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1 && codes.is_contiguous() && codes.numel() >= ((n_rows + 127) / 128) * 128 * mp,
+              "pq_ip_topk: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
+  if (row_map.has_value()) {
+    need(*row_map, "row_map", at::kLong, 1);
+    TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= n_rows, "pq_ip_topk: row_map int64 [>= n_rows] contiguous");
+  }
+  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  const size_t wsb = lrx_pq_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)k);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  lrx_check(lrx_pq_ip_search(codes.data_ptr(), n_rows, centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, q.data_ptr<float>(), (int32_t)q.size(0),
+                             (int32_t)k, id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), row_map.has_value() ? row_map->data_ptr<int64_t>() : nullptr,
+                             ws.data_ptr(), wsb, 0, cur_stream()),
+            "pq_ip_topk");
+  return {d, i};
+}
+
 // Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
 // with the exact capacity, when the first guess of 1024 hits per query was short).
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
@@ -333,6 +360,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("merge_topk(Tensor d_parts, Tensor i_parts) -> (Tensor, Tensor)");
   m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
+  m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HIP tensors under the CUDA key)
@@ -350,4 +378,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("merge_topk", &merge_topk);
   m.impl("flat_ip_range_search", &flat_ip_range_search);
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
+  m.impl("pq_ip_topk", &pq_ip_topk);
 }

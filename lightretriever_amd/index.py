@@ -6,6 +6,7 @@ import ctypes as C
 import weakref
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -591,6 +592,273 @@ class SQFp16Index(FlatIPIndex):
 
     def range_search(self, q, radius: float):
         raise NotImplementedError("SQFp16Index.range_search is not served yet (a follow-up: the range search's list path over the codes)")
+
+
+class PQIndex:
+    """Product-quantised inner-product shard: the faiss IndexPQ(d, M, nbits=8, METRIC_INNER_PRODUCT) surface (train / is_trained / add /
+    search / reset / ntotal / reconstruct_n / save / load), backed by lrx_pq_ip_search.  Resident: M bytes per row (the codes, in the
+    blocked layout of include/lrx.h) + the centroids [M, 256, d / M] fp32.  Scores are the fp32 sums of the query's lookup table over the
+    row's codes in ascending m; exact top-k under that score with the flat index's tie and padding rules.
+    Training: Lloyd k-means per sub-space (256 centroids, 25 iterations, at most 256 x 256 sampled rows, fixed seed), assignments by the
+    encoding kernel, deterministic fp64 centroid sums (sorted by code, segmented sums), faiss's split of empty clusters.  The same input
+    and seed give the same centroids; they are not faiss's (its RNG differs).
+    Rows enter through add() or through append_slot(n) / commit(n): the slot is a transient fp32 staging view; commit() trains the index
+    if it is untrained, encodes the rows and releases the staging.  Search: one library call (it walks the queries in chunks that keep
+    the score matrix under 1 GiB), workspace kept by the index.  NOT thread-safe."""
+
+    KSUB = 256
+    NITER = 25
+    MAX_POINTS_PER_CENTROID = 256
+    SEED = 1234
+
+    def __init__(self, d: int, M: int = 96, nbits: int = 8, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        if nbits != 8:
+            raise NotImplementedError(f"PQIndex: nbits={nbits} is not served (only 8)")
+        if M <= 0 or d % M != 0:
+            raise ValueError(f"PQIndex: d={d} is not a multiple of M={M}")
+        if d // M > 64:
+            raise NotImplementedError(f"PQIndex: sub-space dimension d / M = {d // M} > 64 is not served")
+        _lib.require_gpu()
+        self.lib = _lib.lib()
+        self.d, self.M, self.nbits, self.dsub = d, M, nbits, d // M
+        self.Mp = -(-M // 16) * 16
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.id_base = id_base
+        self.ntotal = 0
+        self.is_trained = False
+        self.centroids = torch.zeros(M, self.KSUB, self.dsub, dtype=torch.float32, device=self.device)
+        self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._stage = None
+        self._ws = None
+        self.reserve(capacity)
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        return self._codes.numel() // self.Mp
+
+    def reserve(self, n_rows: int):
+        need = -(-max(n_rows, 0) // 128) * 128 * self.Mp
+        if need > self._codes.numel():
+            c = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            n_old = min(self._codes.numel(), -(-self.ntotal // 128) * 128 * self.Mp)
+            if n_old:
+                c[:n_old].copy_(self._codes[:n_old])
+            self._codes = c
+
+    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, centroids: torch.Tensor):
+        for s in range(0, x.shape[0], 262144):
+            xs = x[s:s + 262144]
+            _lib.check(self.lib.lrx_pq_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(centroids), self.d, self.M, _lib.ptr(codes),
+                                              row0 + s, _lib.current_stream()))
+
+    def _rows(self, x) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(x)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n,{self.d}], got {tuple(x.shape)}")
+        x = x.to(device=self.device, dtype=torch.float32)
+        return x.contiguous() if x.stride(1) != 1 else x
+
+    def blocked_to_rows(self, blocked: torch.Tensor, n: int) -> torch.Tensor:
+        """Blocked codes (include/lrx.h) -> row-major uint8 [n, M]."""
+        nb = -(-n // 128)
+        return blocked[:nb * 128 * self.Mp].view(nb, self.Mp // 16, 128, 16).permute(0, 2, 1, 3).reshape(nb * 128, self.Mp)[:n, :self.M]
+
+    def rows_to_blocked(self, codes: torch.Tensor) -> torch.Tensor:
+        n = codes.shape[0]
+        nb = -(-n // 128)
+        buf = torch.zeros(nb * 128, self.Mp, dtype=torch.uint8, device=self.device)
+        buf[:n, :self.M] = codes.to(self.device)
+        return buf.view(nb, 128, self.Mp // 16, 16).permute(0, 2, 1, 3).contiguous().view(-1)
+
+    def encode(self, x, centroids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """faiss sa_encode: row-major uint8 [n, M] codes of x under `centroids` (default: this index's)."""
+        x = self._rows(x)
+        c = (self.centroids if centroids is None else centroids).to(self.device, torch.float32).contiguous()
+        blocked = torch.zeros(-(-x.shape[0] // 128) * 128 * self.Mp, dtype=torch.uint8, device=self.device)
+        if x.shape[0]:
+            self._encode_into(x, blocked, 0, c)
+        return self.blocked_to_rows(blocked, x.shape[0])
+
+    # -- training ------------------------------------------------------------------------------------------------
+    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
+        """Lloyd k-means per sub-space (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
+        x = self._rows(x)
+        n = x.shape[0]
+        if n < self.KSUB:
+            raise ValueError(f"PQIndex.train: {n} training rows < {self.KSUB} centroids")
+        niter = self.NITER if niter is None else niter
+        rng = np.random.default_rng(self.SEED if seed is None else seed)
+        max_pts = self.KSUB * self.MAX_POINTS_PER_CENTROID
+        if n > max_pts:
+            x = x[torch.from_numpy(np.sort(rng.permutation(n)[:max_pts])).to(self.device)]
+            n = max_pts
+        M, K, ds = self.M, self.KSUB, self.dsub
+        xs = x.view(n, M, ds)
+        init = np.stack([rng.permutation(n)[:K] for _ in range(M)])                       # [M, K] distinct rows per sub-space
+        cent = xs[torch.from_numpy(init).to(self.device), torch.arange(M, device=self.device)[:, None]].contiguous()   # [M, K, ds]
+        x_t = xs.permute(1, 0, 2).double()                                                 # [M, n, ds]
+        blocked = torch.zeros(-(-n // 128) * 128 * self.Mp, dtype=torch.uint8, device=self.device)
+        for _ in range(niter):
+            self._encode_into(x, blocked, 0, cent)
+            codes = self.blocked_to_rows(blocked, n).t().long()                            # [M, n]
+            cent = _pq_update(x_t, codes, K, cent, rng)
+        self.centroids = cent.float().contiguous()
+        self.is_trained = True
+
+    # -- rows ------------------------------------------------------------------------------------------------------
+    def add(self, x):
+        """faiss add(x f32[n, d]): encode into the codes (raises before train(), as faiss does)."""
+        if not self.is_trained:
+            raise RuntimeError("PQIndex.add: the index is not trained (call train() first)")
+        x = self._rows(x)
+        n = x.shape[0]
+        if self.ntotal + n > self.capacity:
+            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        if n:
+            self._encode_into(x, self._codes, self.ntotal, self.centroids)
+        self.ntotal += n
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
+        if self._stage is None or self._stage.shape[0] < n_rows:
+            self._stage = None
+            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+        return self._stage[:n_rows]
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            if self._stage is None or n_rows > self._stage.shape[0]:
+                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
+            rows = self._stage[:n_rows]
+            if not self.is_trained:
+                self.train(rows)
+            self.add(rows)
+        self._stage = None                             # staging released (stream-ordered by the allocator)
+
+    def reset(self):
+        """faiss reset(): drops the rows, keeps the training."""
+        self.ntotal = 0
+        self._stage = None
+
+    def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
+        """Rows [i0, i0 + n) decoded (centroid of each code) to fp32, device tensor [n, d]."""
+        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
+            raise ValueError(f"reconstruct_n({i0}, {n}) outside [0, {self.ntotal})")
+        out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
+        if n:
+            _lib.check(self.lib.lrx_pq_decode_rows(_lib.ptr(self._codes), i0, n, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(out), self.d,
+                                                   _lib.current_stream()))
+        return out
+
+    def codes(self) -> torch.Tensor:
+        """The codes as a row-major uint8 [ntotal, M] tensor (a copy: the stored layout is blocked)."""
+        return self.blocked_to_rows(self._codes, self.ntotal).contiguous()
+
+    def set_contents(self, centroids, codes):
+        """Replace the centroids ([M, 256, d / M]) and the rows (row-major uint8 [n, M] codes): load() and tests."""
+        c = torch.as_tensor(centroids).to(self.device, torch.float32).reshape(self.M, self.KSUB, self.dsub).contiguous()
+        codes = torch.as_tensor(codes)
+        if codes.ndim != 2 or codes.shape[1] != self.M or codes.dtype != torch.uint8:
+            raise ValueError(f"set_contents: codes must be uint8 [n, {self.M}]")
+        self.centroids = c
+        self.is_trained = True
+        self._codes = self.rows_to_blocked(codes)
+        self.ntotal = codes.shape[0]
+
+    # -- persistence (faiss.write_index / read_index of an IndexPQ, see index_io.py) ----------------------------------------
+    def save(self, fname: str, chunk_rows: int = 1 << 20):
+        from .index_io import write_pq
+        write_pq(fname, self.centroids.cpu().numpy(), (self.blocked_to_rows(self._codes[s // 128 * 128 * self.Mp:], min(chunk_rows, self.ntotal - s)).cpu().numpy()
+                                                       for s in range(0, self.ntotal, chunk_rows)), self.d, self.M, self.ntotal, self.is_trained)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "PQIndex":
+        from .index_io import read_pq
+        cent, codes, trained = read_pq(fname)
+        M, _, dsub = cent.shape
+        idx = cls(M * dsub, M, device=device, id_base=id_base)
+        idx.set_contents(torch.from_numpy(cent), torch.from_numpy(np.array(codes, copy=True)))
+        idx.is_trained = trained
+        return idx
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
+    # -- search --------------------------------------------------------------------------------------------------
+    def search(self, q, k: int, row_map: Optional[torch.Tensor] = None):
+        """faiss search -> (D f32[Q,k], I i64[Q,k]) device tensors: score descending, ties to the lower row, (-FLT_MAX, -1) padding when
+        k > ntotal.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries) when given."""
+        if not isinstance(q, torch.Tensor):
+            q = torch.from_numpy(q)
+        q = q.to(device=self.device, dtype=torch.float32).contiguous()
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        if not 1 <= k <= 2048:
+            raise ValueError(f"search: k={k} out of range (1..2048)")
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        Q = q.shape[0]
+        D = torch.empty(Q, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
+        if Q == 0:
+            return D, I
+        need = int(self.lib.lrx_pq_ip_workspace_bytes(self.ntotal, self.d, self.M, Q, k))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.lrx_pq_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(q), Q, k,
+                                             int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(self._ws), self._ws.numel(), 0,
+                                             _lib.current_stream()))
+        return D, I
+
+
+_PQ_EPS = np.float32(1.0 / 1024.0)
+
+
+def _pq_update(x_t: torch.Tensor, codes: torch.Tensor, K: int, cent: torch.Tensor, rng) -> torch.Tensor:
+    """One k-means update of every sub-space: x_t fp64 [M, n, ds], codes int64 [M, n] -> centroids fp32 [M, K, ds].  The sums are fp64
+    segmented sums over the rows sorted (stably) by code -- a fixed order, no float atomics -- so the update is deterministic.  Empty
+    clusters are re-seeded as faiss does: split a cluster drawn with probability ~ (size - 1), the two copies perturbed by +-1/1024."""
+    M, n, ds = x_t.shape
+    order = torch.argsort(codes, dim=1, stable=True)
+    xs = torch.gather(x_t, 1, order[:, :, None].expand(M, n, ds))
+    cs = torch.cumsum(xs, dim=1)
+    counts = torch.zeros(M, K, dtype=torch.int64, device=codes.device).scatter_add_(1, codes, torch.ones_like(codes))
+    ends = torch.cumsum(counts, dim=1)
+    cs0 = torch.cat([torch.zeros(M, 1, ds, dtype=cs.dtype, device=cs.device), cs], dim=1)          # cs0[:, e] = sum of the first e rows
+    sums = torch.gather(cs0, 1, ends[:, :, None].expand(M, K, ds)) - torch.gather(cs0, 1, (ends - counts)[:, :, None].expand(M, K, ds))
+    new = torch.where(counts[:, :, None] > 0, sums / counts.clamp(min=1)[:, :, None].double(), cent.double()).float()
+    cnt = counts.cpu().numpy()
+    if (cnt == 0).any():
+        c = new.cpu().numpy()
+        for m in range(M):
+            _split_empty(c[m], cnt[m], n, rng)
+        new = torch.from_numpy(c).to(new.device)
+    return new
+
+
+def _split_empty(c: np.ndarray, hassign: np.ndarray, n: int, rng):
+    """faiss Clustering's handling of empty clusters (in place, fp32): copy a cluster drawn with probability (size - 1) / (n - K) and
+    perturb the two copies symmetrically by +-1/1024 per coordinate (even coordinates: up for the new one, odd: down)."""
+    K = c.shape[0]
+    for ci in range(K):
+        if hassign[ci] != 0:
+            continue
+        cj = 0
+        while True:
+            p = (float(hassign[cj]) - 1.0) / float(max(n - K, 1))
+            if rng.random() < p:
+                break
+            cj = (cj + 1) % K
+        c[ci] = c[cj]
+        sign = np.where(np.arange(c.shape[1]) % 2 == 0, np.float32(1), np.float32(-1))
+        c[ci] = c[ci] * (np.float32(1) + sign * _PQ_EPS)
+        c[cj] = c[cj] * (np.float32(1) - sign * _PQ_EPS)
+        hassign[ci] = hassign[cj] // 2
+        hassign[cj] -= hassign[ci]
 
 
 def merge_topk(D_parts: torch.Tensor, I_parts: torch.Tensor):

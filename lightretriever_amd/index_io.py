@@ -29,7 +29,19 @@ An fp16 scalar-quantised shard (SQFp16Index) is written as Faiss's serialisation
     u64   n_bytes = ntotal * 2 d              (WRITEVECTOR of the codes)
     f16   codes[ntotal * d]                   row-major, little-endian
 
-Like the flat layout it is **unverified against a Faiss build**.  Files with any other qtype are rejected."""
+Like the flat layout it is **unverified against a Faiss build**.  Files with any other qtype are rejected.
+
+A product-quantised shard (PQIndex, faiss IndexPQ(d, M, 8, METRIC_INNER_PRODUCT)) is written as Faiss's serialisation of IndexPQ, same
+source:
+
+    u32   fourcc 'IxPq'
+          the index header of 'IxFI' above (d, ntotal, two dummies, is_trained, metric_type = 0)
+    u64   d,  u64 M,  u64 nbits = 8           (write_ProductQuantizer)
+    u64   d * 256,  f32 centroids[M][256][d / M]
+    u64   ntotal * M,  u8 codes[ntotal][M]    row-major
+    i32   search_type = 0 (ST_PQ),  u8 encode_signs = 0,  i32 polysemous_ht = M * nbits + 1
+
+It too is **unverified against a Faiss build**.  Files with nbits != 8 or any other inconsistency are rejected."""
 from __future__ import annotations
 
 import csv
@@ -132,6 +144,67 @@ def read_sq_fp16(fname: str) -> np.memmap:
         raise ValueError(f"{fname}: inconsistent QT_fp16 index (d={d}, ntotal={ntotal}, sq.d={sq_d}, code_size={code_size}, "
                          f"code bytes={n_bytes}, metric={metric}, file bytes={size})")
     return np.memmap(fname, dtype="<f2", mode="r", offset=off, shape=(ntotal, d))
+
+
+FOURCC_PQ = b"IxPq"
+_PQ = struct.Struct("<QQQ")              # d, M, nbits (write_ProductQuantizer)
+_PQ_TAIL = struct.Struct("<iBi")         # search_type, encode_signs, polysemous_ht (9 bytes, packed)
+
+
+def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d: int, M: int, ntotal: int, is_trained: bool = True) -> None:
+    """centroids: fp32 [M, 256, d / M]; blocks: uint8 [n_i, M] code arrays in row order, sum n_i == ntotal."""
+    c = np.ascontiguousarray(centroids, dtype="<f4")
+    if c.size != d * 256:
+        raise ValueError(f"write_pq: {c.size} centroid floats, expected d * 256 = {d * 256}")
+    tmp = fname + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(_HEADER.pack(FOURCC_PQ, d, ntotal, 1 << 20, 1 << 20, int(bool(is_trained)), 0))
+        f.write(_PQ.pack(d, M, 8))
+        f.write(struct.pack("<Q", d * 256))
+        f.write(c.tobytes())
+        f.write(struct.pack("<Q", ntotal * M))
+        rows = 0
+        for b in blocks:
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+            if b.ndim != 2 or b.shape[1] != M:
+                raise ValueError(f"write_pq: block {b.shape} does not match M={M}")
+            f.write(b.tobytes())
+            rows += b.shape[0]
+        if rows != ntotal:
+            raise ValueError(f"write_pq: wrote {rows} rows, header says {ntotal}")
+        f.write(_PQ_TAIL.pack(0, 0, M * 8 + 1))
+    os.replace(tmp, fname)
+
+
+def read_pq(fname: str):
+    """-> (centroids fp32 [M, 256, d / M], codes: read-only memmap uint8 [ntotal, M], is_trained)."""
+    size = os.path.getsize(fname)
+    fixed = _HEADER.size + _PQ.size + 8
+    if size < fixed:
+        raise ValueError(f"{fname}: too short for a product-quantiser index header")
+    with open(fname, "rb") as f:
+        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
+        if fourcc != FOURCC_PQ:
+            raise ValueError(f"{fname}: fourcc {fourcc!r} is not a product-quantiser index ('IxPq')")
+        pq_d, M, nbits = _PQ.unpack(f.read(_PQ.size))
+        if nbits != 8:
+            raise ValueError(f"{fname}: ProductQuantizer nbits={nbits} is not served (only 8)")
+        if metric != 0 or d <= 0 or ntotal < 0 or pq_d != d or M <= 0 or d % M:
+            raise ValueError(f"{fname}: inconsistent IndexPQ header (d={d}, ntotal={ntotal}, pq.d={pq_d}, M={M}, metric={metric})")
+        (n_c,) = struct.unpack("<Q", f.read(8))
+        if n_c != d * 256 or size < fixed + 4 * n_c + 8:
+            raise ValueError(f"{fname}: truncated or inconsistent centroids ({n_c} floats, expected {d * 256})")
+        cent = np.frombuffer(f.read(4 * n_c), dtype="<f4").reshape(M, 256, d // M).copy()
+        (n_b,) = struct.unpack("<Q", f.read(8))
+        off = fixed + 4 * n_c + 8
+        if n_b != ntotal * M or size != off + n_b + _PQ_TAIL.size:
+            raise ValueError(f"{fname}: inconsistent IndexPQ codes (code bytes={n_b}, ntotal * M={ntotal * M}, file bytes={size})")
+        f.seek(off + n_b)
+        search_type, _, _ = _PQ_TAIL.unpack(f.read(_PQ_TAIL.size))
+    if search_type != 0:
+        raise ValueError(f"{fname}: IndexPQ search_type {search_type} is not served (only ST_PQ = 0)")
+    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=off, shape=(ntotal, M)) if ntotal else np.zeros((0, M), np.uint8)
+    return cent, codes, bool(trained)
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

@@ -3,6 +3,7 @@
     FaissIndex          <- retriever/faiss_index.py:20-73      (build / search / reset over the HBM-resident FlatIPIndex)
     FlatIPFaissSearch   <- retriever/faiss_search.py:46-293, :477-510   (BEIR-style dense searcher)
     SQFaissSearch       <- retriever/faiss_search.py:567-611             (QT_fp16 inner product only, over SQFp16Index)
+    PQFaissSearch       <- retriever/faiss_search.py:326-383             (IndexPQ, 8-bit codes, inner product only, over PQIndex)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; sparse + fusion out of scope)
 
 Design differences, results preserved: corpus embeddings are encoded straight into the index shard (no CPU round trip, no
@@ -24,7 +25,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .index import FlatIPIndex, SQFp16Index, merge_topk
+from .index import FlatIPIndex, PQIndex, SQFp16Index, merge_topk
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -203,6 +204,9 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
     index_cls = FlatIPIndex          # the shard type every index / load builds
     serves_rpc_shards = True         # _chunked_dense_search may place the shards on the reference's RPC workers (rpc_shards: FlatIPIndex)
 
+    def _new_index(self, dim: int, capacity: int):
+        return self.index_cls(dim, capacity=capacity)
+
     def index(self, corpus_emb, corpus_ids):
         """Index already-encoded embeddings (Tensor on any device / ndarray) -- faiss_search.py:490-504."""
         self._create_mapping_ids(corpus_ids)
@@ -214,7 +218,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         """Encode a corpus chunk straight into a fresh shard (embeddings never leave HBM)."""
         self._create_mapping_ids(corpus_ids)
         self.dim_size = dim
-        idx = self.index_cls(dim, capacity=len(docs))
+        idx = self._new_index(dim, len(docs))
         if not docs:                                  # a rank without a batch in this chunk: empty shard, searches return padding
             self.faiss_index = FaissIndex(idx, None)
             return None
@@ -272,6 +276,52 @@ class SQFaissSearch(FlatIPFaissSearch):
         return "sq_faiss_index"
 
 
+class PQFaissSearch(FlatIPFaissSearch):
+    """faiss_search.py:326-383: IndexPQ(d, num_of_centroids, code_size, METRIC_INNER_PRODUCT), served by PQIndex -- num_of_centroids is
+    faiss's M (sub-quantisers, M bytes per row), code_size its nbits.  index() trains on the chunk and then adds it (FaissTrainIndex.build);
+    _index_in_place trains on the encoded chunk when its staging slot is committed.  Not served: OPQ (use_rotation), the L2 metric,
+    code_size != 8, shards on RPC workers."""
+    index_cls = PQIndex
+    serves_rpc_shards = False
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, num_of_centroids: int = 96, code_size: int = 8,
+                 similarity_metric=0, use_rotation: bool = False, **kwargs):
+        if use_rotation:
+            raise NotImplementedError("PQFaissSearch: use_rotation (OPQ) is not served")
+        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
+            raise NotImplementedError(f"PQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        if code_size != 8:
+            raise NotImplementedError(f"PQFaissSearch: code_size (nbits) {code_size} is not served (only 8)")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.num_of_centroids = num_of_centroids
+        self.code_size = code_size
+        self.use_rotation = False
+        self.similarity_metric = 0
+
+    def _new_index(self, dim: int, capacity: int) -> PQIndex:
+        if dim % self.num_of_centroids:
+            raise ValueError(f"PQFaissSearch: dimension {dim} is not a multiple of num_of_centroids={self.num_of_centroids}")
+        return PQIndex(dim, self.num_of_centroids, self.code_size, capacity=capacity)
+
+    def index(self, corpus_emb, corpus_ids):
+        """Train on the chunk, then add it (faiss_search.py:370-383 via FaissTrainIndex.build)."""
+        self._create_mapping_ids(corpus_ids)
+        self.dim_size = corpus_emb.shape[1]
+        rows = [self.mapping.get(c, c) for c in corpus_ids]
+        idx = self._new_index(corpus_emb.shape[1], len(rows))
+        idx.train(corpus_emb)
+        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=idx)
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: str = "pq"):
+        super().load(input_dir, prefix, ext)
+
+    def save(self, output_dir: str, prefix: str = "my-index", ext: str = "pq"):
+        super().save(output_dir, prefix, ext)
+
+    def get_index_name(self):
+        return "pq_faiss_index"
+
+
 class HybridSearch:
     """Dense half of the reference's HybridSearch: routes `dense_reps` -> results["den"], `emb_reps` -> results["emb"]
     (hybrid_search.py:121-180); `search()` returns the last enabled type unless return_all_results."""
@@ -292,10 +342,13 @@ class HybridSearch:
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
         # faiss_search_map (hybrid_search.py:32-70): "flat" (default) and "sq" (QT_fp16) are served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
-        den_cls = SQFaissSearch if faiss_search_map == "sq" else FlatIPFaissSearch
-        if faiss_search_map not in ("flat", "sq"):
+        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
-        self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu)
+        den_kwargs = {}
+        if faiss_search_map == "pq":                  # (the reference passes its **kwargs through to the searcher)
+            den_kwargs = {a: kwargs[a] for a in ("num_of_centroids", "code_size", "use_rotation", "similarity_metric") if a in kwargs}
+        self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
         self.return_all_results = return_all_results
         self.mteb_model_meta = None
 
