@@ -8,6 +8,11 @@ separately) = lrx_flat_ip_search of Q=100 queries over the 1M-row index (row-sha
 of per-shard top-100 + on-device merge.  Inputs are resident in HBM before the timed regions start.
 
 Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job docs/s.
+
+A plain run does only what that line's headline needs: set-up, the warm-up and timed steps of the encode and search legs, --dump-outputs
+when given (the sparse vectors it writes are computed for it, untimed), the line.  Everything else the benchmark measures -- the per-class
+kernel table (two extra profiled steps), the search leg's two-in-flight / graph-replay / Q = 1 and 1000 figures, the sparse leg, BASELINE's
+other configurations (`configs`, and over a communicator `sharded`), the CPU baseline -- runs with --full only.
 """
 import argparse
 import json
@@ -24,6 +29,9 @@ sys.path.insert(0, ROOT)
 PEAK_BF16_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
 PEAK_HBM_GBS = 8000.0      # HBM3E spec (same table); ~6300 achievable
 PEAK_F32_MFMA_TFLOPS = 157.3
+
+ALL_LEGS = ("encode", "search", "sparse", "sharded", "configs", "cpu")
+HEADLINE_LEGS = ("encode", "search")       # the two halves of the metric: all a plain run (no --full) times
 
 
 def parse():
@@ -42,8 +50,12 @@ def parse():
     ap.add_argument("--no-search", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the extra single-GPU legs (BASELINE configs 2-4, 8-way shard, top_k = 1000)")
     ap.add_argument("--no-sparse", action="store_true", help="skip the dense+sparse document-vector leg (SURVEY 8f N2)")
-    ap.add_argument("--legs", default="all", help="comma list of encode,search,sparse,sharded,configs,cpu (default all): one leg per run gives one "
-                    "rocprofv3 kernel-stats file per leg (tools/final_profile.sh); a partial run is marked `partial_run` and is not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-class kernel table, search extras, sparse leg, `configs`, "
+                         "`sharded`, CPU baseline (a plain run times the headline legs only)")
+    ap.add_argument("--legs", default="all", help="comma list of %s (default all; any but %s needs --full): one leg per run gives one "
+                    "rocprofv3 kernel-stats file per leg (tools/final_profile.sh); a partial run is marked `partial_run` and is not the headline"
+                    % (",".join(ALL_LEGS), ",".join(HEADLINE_LEGS)))
     ap.add_argument("--config-legs", default="all", help="comma list of the `configs` entries to run (default all)")
     ap.add_argument("--sharded-rows", type=int, default=10_000_000,
                     help="rows of the row-sharded indexes of BASELINE configs[3] / configs[4] (the `sharded` leg: runs over the communicator when "
@@ -58,6 +70,12 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.legs != "all":
+        named = set(args.legs.split(","))
+        if named - set(ALL_LEGS):
+            ap.error("unknown --legs %s" % sorted(named - set(ALL_LEGS)))
+        if not args.full and named - set(HEADLINE_LEGS):
+            ap.error("--full is needed for --legs %s" % ",".join(sorted(named - set(HEADLINE_LEGS))))
     return args
 
 
@@ -931,12 +949,9 @@ def main():
            "qwen2.5-1.5b": EncoderConfig.qwen25_1_5b, "qwen2.5-3b": EncoderConfig.qwen25_3b, "qwen2.5-7b": EncoderConfig.qwen25_7b}[args.model](args.seq_len)
     if os.environ.get("LRX_FOLD_NORM") is not None:          # dev A/B switch; the default is the library's (folded)
         cfg.fold_norm = os.environ["LRX_FOLD_NORM"] != "0"
-    all_legs = ("encode", "search", "sparse", "sharded", "configs", "cpu")
-    legs = set(all_legs) if args.legs == "all" else set(args.legs.split(","))
-    if legs - set(all_legs):
-        sys.stderr.write("bench.py: unknown --legs %s\n" % sorted(legs - set(all_legs)))
-        sys.exit(2)
-    partial = legs != set(all_legs)
+    # (without --full the legs beyond HEADLINE_LEGS only compute what --dump-outputs writes of them: parse() refuses them by name)
+    legs = set(ALL_LEGS) if args.legs == "all" else set(args.legs.split(","))
+    partial = legs != set(ALL_LEGS)
     if args.no_search:
         legs.discard("search")
     if args.no_sparse:
@@ -997,7 +1012,7 @@ def main():
     if "search" in legs:
         gq = torch.Generator(device=dev).manual_seed(99)      # same queries on every rank (replicated query side)
         table = torch.randn(cfg.vocab_size, D, generator=gq, device=dev)
-        for Qx in (args.queries, 1, 1000):
+        for Qx in (args.queries, 1, 1000) if args.full else (args.queries,):
             lens_x = torch.randint(8, 33, (Qx,), generator=gq, device=dev)
             offs_x = (torch.cumsum(lens_x, 0) - lens_x).to(torch.int64)
             ids_x = torch.randint(1000, 127000, (int(lens_x.sum().item()),), generator=gq, device=dev)
@@ -1017,7 +1032,7 @@ def main():
 
     # ---- encode leg: W warmup steps, then EXACTLY K timed steps between barrier + synchronize.  Inside the timed region only the
     #      dominant kernel (gate-up GEMM, class 2) is bracketed by HIP events on the launch stream -- read after the region, no
-    #      host sync inside it; the per-class table comes from two extra fully profiled steps afterwards.
+    #      host sync inside it; the per-class table comes from two extra fully profiled steps afterwards (--full).
     # k_trace_marker<0> ... <1> bracket the HEADLINE legs in a rocprofv3 kernel trace (tools/check_trace_clean.py counts every kernel between
     # them that is not liblrx's)
     _lib.check(lrx.lrx_trace_marker(0, _lib.current_stream()))
@@ -1039,11 +1054,12 @@ def main():
         gu_timed = enc.get_profile()["gemm_swiglu"]
         enc_s = reduce_max(enc_s, dev, distributed)
         docs_per_s = world * B * args.steps / enc_s
-        enc.set_profiling(True)
-        n_prof = min(2, args.steps)
-        for i in range(n_prof):
-            encode_step(args.warmup + i)
-        prof = enc.get_profile()
+        if args.full:
+            enc.set_profiling(True)
+            n_prof = min(2, args.steps)
+            for i in range(n_prof):
+                encode_step(args.warmup + i)
+            prof = enc.get_profile()
         enc.set_profiling(False)
 
     # ---- search leg (queries: 8-32 random token ids -> EmbeddingBag(mean) over a synthetic [V,H] table -> normalise)
@@ -1082,29 +1098,30 @@ def main():
         #      per pass, same bits; between the same barrier + synchronize brackets: the throughput a serving loop with the next batch at hand
         #      gets.  Reported next to `value`, not as it.
         pipe = None
-        try:
-            # (more than one rank: every rank submits the same searches in the same order, so the lanes' all-gathers reach the communicator in the
-            # same order everywhere; tests/test_gpu_00_multi_gpu.py runs exactly this over R = 2, 4, 8 RCCL ranks where the GPUs exist)
-            from lightretriever_amd.pipeline import SearchLanes
-            lanes = SearchLanes(sharded, lanes=2)
-            mk = lambda: ops.embedding_bag_mean(table, q_ids, offs, normalize=True)
-            for _ in range(4):
-                lanes.submit(mk, args.topk)
-            lanes.drain()
-            # (at least 100 passes: the fixed cost of the two barriers and of filling / draining the lanes is ~1 ms, +7 % on 20 passes of 0.7 ms)
-            n_lp = max(n_pass, 100)
-            barrier_sync(distributed)
-            t0 = time.perf_counter()
-            pend = [lanes.submit(mk, args.topk) for _ in range(n_lp)]
-            lanes.drain()
-            barrier_sync(distributed)
-            pipe_s = time.perf_counter() - t0
-            Dp_, Ip_ = pend[-1].result()
-            pipe_s = reduce_max(pipe_s, dev, distributed)
-            pipe = {"lanes": 2, "passes": n_lp, "queries_per_s": round(args.queries * n_lp / pipe_s, 2), "ms_per_pass": round(1e3 * pipe_s / n_lp, 4),
-                    "identical_to_one_at_a_time": bool(torch.equal(Dp_, Dk) and torch.equal(Ip_, Ik))}
-        except Exception as e:  # noqa: BLE001  (the one-at-a-time figure then stands as the value)
-            pipe = {"failed": "%r" % (e,)}
+        if args.full:
+            try:
+                # (more than one rank: every rank submits the same searches in the same order, so the lanes' all-gathers reach the communicator in the
+                # same order everywhere; tests/test_gpu_00_multi_gpu.py runs exactly this over R = 2, 4, 8 RCCL ranks where the GPUs exist)
+                from lightretriever_amd.pipeline import SearchLanes
+                lanes = SearchLanes(sharded, lanes=2)
+                mk = lambda: ops.embedding_bag_mean(table, q_ids, offs, normalize=True)
+                for _ in range(4):
+                    lanes.submit(mk, args.topk)
+                lanes.drain()
+                # (at least 100 passes: the fixed cost of the two barriers and of filling / draining the lanes is ~1 ms, +7 % on 20 passes of 0.7 ms)
+                n_lp = max(n_pass, 100)
+                barrier_sync(distributed)
+                t0 = time.perf_counter()
+                pend = [lanes.submit(mk, args.topk) for _ in range(n_lp)]
+                lanes.drain()
+                barrier_sync(distributed)
+                pipe_s = time.perf_counter() - t0
+                Dp_, Ip_ = pend[-1].result()
+                pipe_s = reduce_max(pipe_s, dev, distributed)
+                pipe = {"lanes": 2, "passes": n_lp, "queries_per_s": round(args.queries * n_lp / pipe_s, 2), "ms_per_pass": round(1e3 * pipe_s / n_lp, 4),
+                        "identical_to_one_at_a_time": bool(torch.equal(Dp_, Dk) and torch.equal(Ip_, Ik))}
+            except Exception as e:  # noqa: BLE001  (the one-at-a-time figure then stands as the value)
+                pipe = {"failed": "%r" % (e,)}
         # (`value` stays the one-search-at-a-time figure of rounds 1-3; at 1M rows the chain is 90 % streaming passes and a second search in
         # flight buys 0-4 %, on the 125 k-row per-rank shard 14 % -- `configs.search_per_shard_8way.two_in_flight`)
         best_s = srch_s
@@ -1125,68 +1142,69 @@ def main():
                          "fp32_mfma_peak_for_reference": PEAK_F32_MFMA_TFLOPS},
         }
 
-        # the same local search captured in a HIP graph and replayed (the library neither allocates nor synchronises, so a serving loop can
-        # replay it; tests/test_gpu_search_emit.py::test_search_captured_in_a_hip_graph_replays_bit_identically): launch gaps of the chain gone
-        try:
-            qg = q.clone()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                index.search(qg, args.topk)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                Dgr, Igr = index.search(qg, args.topk)
-            def back_to_back(fn, n):                 # one event pair around n calls queued without a gap: what a serving loop sees
-                for _ in range(3):
-                    fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(n):
-                    fn()
-                e1.record()
+        if args.full:                            # the search leg's other figures
+            # the same local search captured in a HIP graph and replayed (the library neither allocates nor synchronises, so a serving loop can
+            # replay it; tests/test_gpu_search_emit.py::test_search_captured_in_a_hip_graph_replays_bit_identically): launch gaps of the chain gone
+            try:
+                qg = q.clone()
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    index.search(qg, args.topk)
+                torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
-                return e0.elapsed_time(e1) / n
-            g_ms = back_to_back(graph.replay, 2 * n_pass)
-            e_ms = back_to_back(lambda: index.search(qg, args.topk), 2 * n_pass)
-            De_, Ie_ = index.search(qg, args.topk)
-            search["graph_replay"] = {"ms_back_to_back": round(g_ms, 4), "eager_ms_back_to_back": round(e_ms, 4), "calls": 2 * n_pass,
-                                      "bit_identical_to_eager": bool(torch.equal(Dgr, De_) and torch.equal(Igr, Ie_)),
-                                      "roofline_frac": round(alg_bytes / (g_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
-            del graph
-        except Exception as e:  # noqa: BLE001
-            search["graph_replay"] = {"failed": "%r" % (e,)}
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    Dgr, Igr = index.search(qg, args.topk)
+                def back_to_back(fn, n):                 # one event pair around n calls queued without a gap: what a serving loop sees
+                    for _ in range(3):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(n):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    return e0.elapsed_time(e1) / n
+                g_ms = back_to_back(graph.replay, 2 * n_pass)
+                e_ms = back_to_back(lambda: index.search(qg, args.topk), 2 * n_pass)
+                De_, Ie_ = index.search(qg, args.topk)
+                search["graph_replay"] = {"ms_back_to_back": round(g_ms, 4), "eager_ms_back_to_back": round(e_ms, 4), "calls": 2 * n_pass,
+                                          "bit_identical_to_eager": bool(torch.equal(Dgr, De_) and torch.equal(Igr, Ie_)),
+                                          "roofline_frac": round(alg_bytes / (g_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
+                del graph
+            except Exception as e:  # noqa: BLE001
+                search["graph_replay"] = {"failed": "%r" % (e,)}
 
-        # the other query counts of SURVEY 8d (Q = 1 and Q = 1000), same flow (EmbeddingBag -> local search -> exchange + merge)
-        other = {}
-        for Qx in (1, 1000):
-            ids_x, offs_x = qsets[Qx]
-            sharded.search(ops.embedding_bag_mean(table, ids_x, offs_x, normalize=True), args.topk)
-            barrier_sync(distributed)
-            t0 = time.perf_counter()
-            n_px = n_pass if Qx == 1 else args.steps
-            for _ in range(n_px):
+            # the other query counts of SURVEY 8d (Q = 1 and Q = 1000), same flow (EmbeddingBag -> local search -> exchange + merge)
+            other = {}
+            for Qx in (1, 1000):
+                ids_x, offs_x = qsets[Qx]
                 sharded.search(ops.embedding_bag_mean(table, ids_x, offs_x, normalize=True), args.topk)
-            barrier_sync(distributed)
-            sx = reduce_max(time.perf_counter() - t0, dev, distributed)
-            ms_x = 1e3 * sx / n_px
-            # which bound applies: one query streams the shard's fp16 shadow once (HBM); 1000 queries are one pass of the f16 MFMA
-            # GEMM over it (wide chunks: the shadow is read once per <= 1024 queries) -- both fractions, the applicable one named
-            hb = hbm_roofline(shard_rows, D, Qx, args.topk, ms_x)
-            tf = 2.0 * Qx * D * shard_rows / (ms_x * 1e-3) / 1e12
-            other[str(Qx)] = {"queries_per_s": round(Qx * n_px / sx, 1), "ms_per_pass": round(ms_x, 4), "passes": n_px,
-                              "roofline": {"bound": "hbm" if Qx <= 128 else "mfma", "frac": hb["frac"] if Qx <= 128 else round(tf / PEAK_BF16_TFLOPS, 4),
-                                           "hbm_frac": hb["frac"], "hbm_achieved_gbs": hb["achieved"], "mfma_f16_tflops": round(tf, 1),
-                                           "mfma_frac": round(tf / PEAK_BF16_TFLOPS, 4), "mfma_peak_tflops": PEAK_BF16_TFLOPS,
-                                           "note": "whole pass incl. EmbeddingBag + exchange; f16 dense MFMA peak = the bf16 figure"}}
-        search["other_query_counts"] = other
+                barrier_sync(distributed)
+                t0 = time.perf_counter()
+                n_px = n_pass if Qx == 1 else args.steps
+                for _ in range(n_px):
+                    sharded.search(ops.embedding_bag_mean(table, ids_x, offs_x, normalize=True), args.topk)
+                barrier_sync(distributed)
+                sx = reduce_max(time.perf_counter() - t0, dev, distributed)
+                ms_x = 1e3 * sx / n_px
+                # which bound applies: one query streams the shard's fp16 shadow once (HBM); 1000 queries are one pass of the f16 MFMA
+                # GEMM over it (wide chunks: the shadow is read once per <= 1024 queries) -- both fractions, the applicable one named
+                hb = hbm_roofline(shard_rows, D, Qx, args.topk, ms_x)
+                tf = 2.0 * Qx * D * shard_rows / (ms_x * 1e-3) / 1e12
+                other[str(Qx)] = {"queries_per_s": round(Qx * n_px / sx, 1), "ms_per_pass": round(ms_x, 4), "passes": n_px,
+                                  "roofline": {"bound": "hbm" if Qx <= 128 else "mfma", "frac": hb["frac"] if Qx <= 128 else round(tf / PEAK_BF16_TFLOPS, 4),
+                                               "hbm_frac": hb["frac"], "hbm_achieved_gbs": hb["achieved"], "mfma_f16_tflops": round(tf, 1),
+                                               "mfma_frac": round(tf / PEAK_BF16_TFLOPS, 4), "mfma_peak_tflops": PEAK_BF16_TFLOPS,
+                                               "note": "whole pass incl. EmbeddingBag + exchange; f16 dense MFMA peak = the bf16 figure"}}
+            search["other_query_counts"] = other
 
     # ---- dense + sparse document vectors (row N2): same batches through lrx_encode_packed_sparse; not part of `value`
     if "search" not in legs:
         _lib.check(lrx.lrx_trace_marker(1, _lib.current_stream()))
     sparse = None
-    if "sparse" in legs and batches is None:
+    if args.full and "sparse" in legs and batches is None:
         n_sp = min(2, args.steps)
         enc.encode_packed_sparse(ids_all[0].reshape(-1), cu, S)
         enc.lib.lrx_set_profiling(1 << 8)                    # events around the max-aggregation GEMM (class 7) only
@@ -1208,10 +1226,15 @@ def main():
                                "achieved": round(mx_fl / (mx_ms / n_sp * 1e-3) / 1e12, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                                "frac": round(mx_fl / (mx_ms / n_sp * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4), "avg_launch_ms": round(mx_ms / n_sp, 3),
                                "traffic": pmc_traffic("k_gemm_bf16_nt<4>") if (args.model == "llama3.2-1b" and B == 256 and S == 512) else None}}
+    elif "sparse" in legs and batches is None and args.dump_outputs:
+        # (a plain run: only the vectors --dump-outputs writes of this leg, those of its last step, untimed)
+        last = args.warmup + min(2, args.steps) - 1
+        sp_dense, sp_vectors = enc.encode_packed_sparse(ids_all[last].reshape(-1), cu, S)
+        dumps.update(sparse_dense=sp_dense, sparse_vectors=sp_vectors)
 
     # ---- BASELINE configs[3] / configs[4] + the 8B encoder over the communicator (every rank takes part; N > 1, or one forced RCCL rank)
     sharded_legs = None
-    if distributed and "sharded" in legs and batches is None:
+    if args.full and distributed and "sharded" in legs and batches is None:
         if world > 1:                              # (N = 1 keeps the headline index for the single-GPU `configs` legs below)
             del sharded, index, slot
             enc = None
@@ -1234,7 +1257,7 @@ def main():
     if "encode" not in legs:
         line = {"partial_run": sorted(legs), "metric": "partial run (profiling aid): not the headline line", "value": None, "unit": "docs/s", "n_gpus": world,
                 "search": search, "sparse": sparse}
-        if world == 1 and "configs" in legs and batches is None:
+        if args.full and world == 1 and "configs" in legs and batches is None:
             line["configs"] = extra_legs(args, dev, index if (D == 2048 and args.index_rows == 1_000_000) else None)
         if sharded_legs is not None:
             line.setdefault("configs", {}).update(sharded_legs)
@@ -1249,8 +1272,9 @@ def main():
     # FLOPs per document of the timed batches: F(S) for the fixed-length headline, the mean of F(len) over the ragged batches
     fl_doc = cfg.flops_per_doc(S) if batches is None else sum(batches[i][4] for i in timed) / args.steps
     m_rows = "%d" % (B * S) if batches is None else "%d..%d" % (min(batches[i][3] for i in timed), max(batches[i][3] for i in timed))
-    gemm_all_ms = sum(prof[k_]["ms"] for k_ in ("gemm_store", "gemm_resid", "gemm_swiglu"))
-    gemm_all_fl = sum(prof[k_]["flops"] for k_ in ("gemm_store", "gemm_resid", "gemm_swiglu"))
+    gemm_prof = [prof[k_] for k_ in ("gemm_store", "gemm_resid", "gemm_swiglu") if k_ in prof]     # (the profiled steps: --full only)
+    gemm_all_ms = sum(v["ms"] for v in gemm_prof)
+    gemm_all_fl = sum(v["flops"] for v in gemm_prof)
     achieved = gu["flops"] / (gu["ms"] * 1e-3) / 1e12 if gu["ms"] > 0 else 0.0
     roofline = {
         "bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
@@ -1258,7 +1282,7 @@ def main():
         "kernel": "k_gemm_bf16_nt<EPI_SWIGLU> M=%s N=%d K=%d" % (m_rows, 2 * cfg.intermediate_size, H),
         "avg_launch_ms": round(gu["ms"] / max(gu["launches"], 1), 4), "launches": gu["launches"],
         "all_gemms_tflops": round(gemm_all_fl / (gemm_all_ms * 1e-3) / 1e12, 2) if gemm_all_ms > 0 else None,
-        "per_class_ms_per_step": {k_: round(v["ms"] / n_prof, 3) for k_, v in prof.items()},
+        "per_class_ms_per_step": {k_: round(v["ms"] / n_prof, 3) for k_, v in prof.items()} if prof else None,
         # NOT measured by this run (PMC counters cannot be read from inside the timed process): numbers of committed rocprofv3 --pmc passes,
         # each with the git blob id of the file it was read from; `traffic` above comes from pmc_summary
         "offline_profile": {"pmc_summary": {"file": PMC_SUMMARY, "git_blob": git_blob_sha(PMC_SUMMARY)},
@@ -1276,7 +1300,7 @@ def main():
     # (end_to_end_tflops counts the algorithmic F(S) per document; the final layer's O-projection / MLP run on the B pooled rows only, so the
     # FLOPs actually executed are lower: `executed_tflops` = the sum over the profiled kernel classes / the profiled steps' time share)
     ex_fl = sum(v["flops"] for v in prof.values()) / max(n_prof, 1)
-    roofline["executed_tflops"] = round(ex_fl / (enc_s / args.steps) / 1e12, 2)
+    roofline["executed_tflops"] = round(ex_fl / (enc_s / args.steps) / 1e12, 2) if prof else None
     line = {
         "metric": "docs embedded/sec (%s dims, seq_len=%d, bf16) [+ queries/sec@top-%d over %d-doc index in `search`]" % (args.model, S, args.topk, args.index_rows),
         "value": round(docs_per_s, 2), "unit": "docs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1305,7 +1329,7 @@ def main():
                          "search_peak_gbs": PEAK_HBM_GBS, "search_alg_bytes": sk["search_alg_bytes"], "search_local_ms": sk["search_local_ms"]})
     if partial:
         line["partial_run"] = sorted(legs)
-    if world == 1 and "configs" in legs and batches is None:
+    if args.full and world == 1 and "configs" in legs and batches is None:
         try:
             line["configs"] = extra_legs(args, dev, index if (D == 2048 and args.index_rows == 1_000_000) else None)
             mc = line["configs"].get("measured_ceilings")
@@ -1320,7 +1344,7 @@ def main():
             line["configs"] = {"failed": "%r" % (e,)}
     if sharded_legs is not None:
         line.setdefault("configs", {}).update(sharded_legs)
-    if world == 1 and "cpu" in legs:
+    if args.full and world == 1 and "cpu" in legs:
         try:
             cb = cpu_baseline(cfg, S, args.topk, D)
             if cb.get("search"):

@@ -84,7 +84,7 @@ def test_sharded_search_lanes_and_hybrid_search_over_rccl_ranks(n_ranks):
 def test_bench_line_reports_the_rccl_ranks_and_the_shard_sizes():
     n_ranks = max(_ranks_available())
     rows = 1_000_003                                 # no R divides it: the remainder rows go one each to the first ranks
-    rc, out, err = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--legs", "encode,search,sharded",
+    rc, out, err = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n_ranks), "--steps", "2", "--warmup", "1", "--full", "--legs", "encode,search,sharded",
                          "--index-rows", str(rows), "--sharded-rows", "2000003"], 900)
     assert rc == 0, err[-6000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
@@ -110,7 +110,7 @@ def test_bench_with_two_ranks_on_one_gpu_over_gloo_runs_every_branch_of_the_n_gt
     and the 8B encoder over a two-rank communicator, lanes over it) run to a well-formed line.  Replaces retriever/faiss_index.py:60-70."""
     rows, srows = 200_003, 300_001
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--legs", "encode,search,sharded", "--index-rows", str(rows),
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--legs", "encode,search,sharded", "--index-rows", str(rows),
            "--sharded-rows", str(srows)]
     rc, out, err = _run(cmd, 1100, {"LRX_BENCH_BACKEND": "gloo", "LRX_BENCH_ONE_GPU": "1"})
     assert rc == 0, err[-6000:]

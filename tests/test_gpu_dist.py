@@ -187,7 +187,7 @@ def test_bench_with_a_forced_one_rank_rccl_group_matches_the_plain_run():
     agree with the plain run within 3 % (docs/s; the search pays one extra collective + merge per pass: within 15 %)."""
     plain = _bench_line({})
     forced = _bench_line({"LRX_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(29800 + os.getpid() % 1000), "RANK": "0",
-                          "WORLD_SIZE": "1", "LOCAL_RANK": "0"}, "--legs", "encode,search,sharded", "--sharded-rows", "1000000")
+                          "WORLD_SIZE": "1", "LOCAL_RANK": "0"}, "--full", "--legs", "encode,search,sharded", "--sharded-rows", "1000000")
     for line in (plain, forced):
         assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["scaling"] == "weak" and line["steps"] == 4 and line["warmup"] == 1
         s = line["search"]
@@ -203,6 +203,9 @@ def test_bench_with_a_forced_one_rank_rccl_group_matches_the_plain_run():
     # round 6: over a communicator the line also carries BASELINE configs[3] / configs[4] (row-sharded 4096- and 256-wide indexes; here
     # --sharded-rows 1 000 000 on the one rank) and the 8B encoder under weak scaling -- local / exchange / merge split by HIP events
     assert "configs" not in plain
+    # (a plain run measures the headline only: the search leg's extras and the per-class table come with --full)
+    assert "other_query_counts" not in plain["search"] and plain["search"]["two_in_flight"] is None and plain["roofline"]["per_class_ms_per_step"] is None
+    assert "other_query_counts" in forced["search"] and forced["roofline"]["per_class_ms_per_step"]["gemm_swiglu"] > 0
     fc = forced["configs"]
     for key, dim in (("config3_10Mx4096", 4096), ("config4_10Mx256_mrl", 256)):
         c = fc[key]

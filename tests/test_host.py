@@ -598,6 +598,19 @@ def test_bench_gpus_flag_is_checked_before_any_gpu_work():
     assert r.returncode == 2 and "--gpus 64 but only" in r.stderr
 
 
+def test_bench_legs_beyond_the_headline_need_full_before_any_gpu_work():
+    """A plain bench.py run times the headline legs (encode, search) only; naming another leg without --full, or a leg that does not
+    exist, is refused while the arguments are parsed."""
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    for legs in ("sparse", "encode,configs", "cpu", "sharded"):
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--legs", legs], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "--full is needed for --legs" in r.stderr, (legs, r.stderr[-500:])
+    r = subprocess.run([sys.executable, bench, "--gpus", "1", "--full", "--legs", "encode,bogus"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "unknown --legs ['bogus']" in r.stderr
+
+
 def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
     """bench.py --dump-outputs: float arrays as float32, integer ids as exact float64; an array over its share of the 64 MB budget becomes the
     same seeded sample of its rows on every run, with the row indices next to it."""

@@ -13,7 +13,7 @@ SETS=("SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_MFMA SQ_WAVE_CYCLES S
 i=0
 for S in "${SETS[@]}"; do
   QS=1000 timeout 300 rocprofv3 --kernel-trace --pmc $S --output-format csv -d $OUT/s$i -o a -- python3 $R/tools/bench_search.py > $OUT/s$i.log 2>&1 || echo "search pass $i failed"
-  timeout 300 rocprofv3 --kernel-trace --pmc $S --output-format csv -d $OUT/e$i -o a -- python3 $R/bench.py --steps 2 --warmup 1 --legs encode > $OUT/e$i.log 2>&1 || echo "encode pass $i failed"
+  timeout 300 rocprofv3 --kernel-trace --pmc $S --output-format csv -d $OUT/e$i -o a -- python3 $R/bench.py --full --steps 2 --warmup 1 --legs encode > $OUT/e$i.log 2>&1 || echo "encode pass $i failed"
   i=$((i+1))
 done
 python3 - <<PY

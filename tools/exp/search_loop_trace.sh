@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/loop_trace; rm -rf $OUT; mkdir -p $OUT; cd /tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-sparse > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-sparse > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/**/*kernel_trace.csv", recursive=True)[0]

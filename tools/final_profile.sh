@@ -1,8 +1,8 @@
 #!/bin/bash
-# Round-end evidence: the default bench line, then ONE rocprofv3 --kernel-trace --stats run PER BENCH LEG (program directly after `--`), so
+# Round-end evidence: the full bench line (--full), then ONE rocprofv3 --kernel-trace --stats run PER BENCH LEG (program directly after `--`), so
 # that every `frac` of the line can be recomputed from a kernel-stats file that holds that leg's launches only (one
 # file for the whole bench mixed the 1B and 8B shapes of k_gemm_bf16_nt<2> under one average).  Output: gpurun_out/final/
-#   bench.json                      the default `python bench.py` line
+#   bench.json                      the `python bench.py --full` line
 #   leg_<name>_kernel_stats.csv     per leg: encode, search, sparse, and each entry of `configs`
 #   trace_clean.txt                 tools/check_trace_clean.py on a run of the two headline legs
 set -e
@@ -11,12 +11,12 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/final
 mkdir -p $OUT
 cd /tmp
-timeout 900 python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
+timeout 900 python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || echo "bench failed"
 tail -c 1500 $OUT/bench.json
 prof() {   # name, bench arguments ...
   local name=$1; shift
   rm -rf $OUT/prof_$name
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o t -- python3 $R/bench.py --steps 4 --warmup 2 "$@" > $OUT/prof_$name.log 2>&1 || echo "profile of $name failed"
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$name -o t -- python3 $R/bench.py --full --steps 4 --warmup 2 "$@" > $OUT/prof_$name.log 2>&1 || echo "profile of $name failed"
   cp $(find $OUT/prof_$name -name "*kernel_stats.csv" | head -1) $OUT/leg_${name}_kernel_stats.csv 2>/dev/null || true
   echo "leg $name: $(wc -l < $OUT/leg_${name}_kernel_stats.csv 2>/dev/null) kernels"
 }

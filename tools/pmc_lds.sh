@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/pmc_lds
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-timeout 500 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES --output-format csv -d $OUT/a -o a -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-sparse > $OUT/a.log 2>&1 || echo "pass failed"
+timeout 500 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE SQ_BUSY_CU_CYCLES --output-format csv -d $OUT/a -o a -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-sparse > $OUT/a.log 2>&1 || echo "pass failed"
 python3 - <<PY
 import csv, glob, collections
 cnt = collections.defaultdict(lambda: collections.defaultdict(list))

@@ -1,11 +1,11 @@
 #!/bin/bash
-# rocprofv3 kernel stats of a short default-config bench run (program directly after `--`)
+# rocprofv3 kernel stats of a short default-config bench run (--full: with the per-class table and the `configs` legs) (program directly after `--`)
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_bench
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-search --no-sparse > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o t -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-search --no-sparse > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv
 rows=list(csv.DictReader(open("$OUT/t_kernel_trace.csv")))
