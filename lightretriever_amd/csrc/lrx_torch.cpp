@@ -27,6 +27,32 @@ void need(const at::Tensor& t, const char* name, at::ScalarType dt, int64_t dim 
 
 at::Tensor bytes(int64_t n, const at::Tensor& like) { return at::empty({n}, like.options().dtype(at::kByte)); }
 
+// ---- index ops: shared argument checks and outputs --------------------------------------------------------------------------------
+// an optional 1-D tiled buffer of `dt` elements (include/lrx.h: whole 128-row blocks) that must hold rows [0, n_rows) of `width` columns
+// -> its address, or null when absent; `msg` names the op
+void* tiled_rows(const c10::optional<at::Tensor>& t, at::ScalarType dt, int64_t n_rows, int64_t width, const char* msg) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == dt && t->dim() == 1 && t->is_contiguous() && t->numel() >= ((n_rows + 127) / 128) * 128 * width, msg);
+  return t->data_ptr();
+}
+
+// an optional int64 map of >= n_rows local rows -> its address, or null when absent; `msg` names the op
+const int64_t* row_map_ptr(const c10::optional<at::Tensor>& row_map, int64_t n_rows, const char* msg) {
+  if (!row_map.has_value()) return nullptr;
+  need(*row_map, "row_map", at::kLong, 1);
+  TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= n_rows, msg);
+  return row_map->data_ptr<int64_t>();
+}
+
+// the [Q, k] outputs of a top-k search over queries q: fp32 scores d, int64 ids i and, for the wire ops, the int64 exchange words w
+struct TopK {
+  at::Tensor d, i, w;
+};
+TopK topk_out(const at::Tensor& q, int64_t k, bool wire = false) {
+  const auto ids = q.options().dtype(at::kLong);
+  return {at::empty({q.size(0), k}, q.options()), at::empty({q.size(0), k}, ids), wire ? at::empty({q.size(0), k}, ids) : at::Tensor()};
+}
+
 // ---- encoder ---------------------------------------------------------------------------------------------------------------------
 // weights: the address of an lrx_encoder_handle {cfg*, weights*} kept alive by its owner (LrxEncoder.handle)
 // shadow / row_bounds (optional): `out` = rows [shadow_row0, ...) of an index shard -- the last kernel also writes their tiled shadow rows and
@@ -142,7 +168,7 @@ std::tuple<at::Tensor, at::Tensor> flat_ip_topk(const at::Tensor& q, const at::T
   need(q, "q", at::kFloat, 2);
   need(x, "x", at::kFloat, 2);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1), "flat_ip_topk: q [Q,D] contiguous, x [N,D]");
-  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  TopK o = topk_out(q, k);
   const size_t wsb = lrx_flat_ip_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)q.size(0), (int32_t)k);
   at::Tensor ws = bytes((int64_t)wsb, q);
   const float* rb = nullptr;
@@ -152,9 +178,9 @@ std::tuple<at::Tensor, at::Tensor> flat_ip_topk(const at::Tensor& q, const at::T
     rb = row_bounds->data_ptr<float>();
   }
   lrx_check(lrx_flat_ip_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), rb, q.data_ptr<float>(),
-                               (int32_t)q.size(0), (int32_t)k, id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), ws.data_ptr(), wsb, cur_stream()),
+                               (int32_t)q.size(0), (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), ws.data_ptr(), wsb, cur_stream()),
             "flat_ip_topk");
-  return {d, i};
+  return {o.d, o.i};
 }
 
 // x_shadow: the shard's 1-D tiled fp16 shadow (include/lrx.h), block 0 row 0 = x row 0; flags: LRX_SEARCH_FILTER_*
@@ -165,20 +191,16 @@ std::tuple<at::Tensor, at::Tensor> flat_ip_topk_bounded(const at::Tensor& q, con
   need(x, "x", at::kFloat, 2);
   need(row_bounds, "row_bounds", at::kFloat, 1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_topk_bounded: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  if (x_shadow.has_value()) {
-    TORCH_CHECK(x_shadow->is_cuda() && x_shadow->scalar_type() == at::kHalf && x_shadow->dim() == 1 && x_shadow->is_contiguous() &&
-                    x_shadow->numel() >= ((x.size(0) + 127) / 128) * 128 * x.size(1),
-                "flat_ip_topk_bounded: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
-  }
-  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
+                        "flat_ip_topk_bounded: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  TopK o = topk_out(q, k);
   const size_t wsb = lrx_flat_ip_bounded_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
   at::Tensor ws = bytes((int64_t)wsb, q);
-  lrx_check(lrx_flat_ip_search_bounded(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1),
-                                       x_shadow.has_value() ? x_shadow->data_ptr() : nullptr, row_bounds.data_ptr<float>(), q.data_ptr<float>(),
-                                       (int32_t)q.size(0), (int32_t)k, id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags,
-                                       cur_stream()),
+  lrx_check(lrx_flat_ip_search_bounded(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), xb,
+                                       row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                       o.i.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags, cur_stream()),
             "flat_ip_topk_bounded");
-  return {d, i};
+  return {o.d, o.i};
 }
 
 // The same search for one rank of a row-sharded index: also returns the [Q, k] int64 wire words of the exchange (lrx_pack_topk's format,
@@ -191,26 +213,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_topk_bounded_wire(const a
   need(x, "x", at::kFloat, 2);
   need(row_bounds, "row_bounds", at::kFloat, 1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_topk_bounded_wire: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  if (x_shadow.has_value()) {
-    TORCH_CHECK(x_shadow->is_cuda() && x_shadow->scalar_type() == at::kHalf && x_shadow->dim() == 1 && x_shadow->is_contiguous() &&
-                    x_shadow->numel() >= ((x.size(0) + 127) / 128) * 128 * x.size(1),
-                "flat_ip_topk_bounded_wire: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
-  }
-  if (row_map.has_value()) {
-    need(*row_map, "row_map", at::kLong, 1);
-    TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= x.size(0), "flat_ip_topk_bounded_wire: row_map int64 [>= N] contiguous");
-  }
-  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
-  at::Tensor w = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
+                        "flat_ip_topk_bounded_wire: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  const int64_t* rm = row_map_ptr(row_map, x.size(0), "flat_ip_topk_bounded_wire: row_map int64 [>= N] contiguous");
+  TopK o = topk_out(q, k, true);
   const size_t wsb = lrx_flat_ip_bounded_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
   at::Tensor ws = bytes((int64_t)wsb, q);
-  lrx_check(lrx_flat_ip_search_bounded_wire(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1),
-                                            x_shadow.has_value() ? x_shadow->data_ptr() : nullptr, row_bounds.data_ptr<float>(), q.data_ptr<float>(),
-                                            (int32_t)q.size(0), (int32_t)k, id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(),
-                                            row_map.has_value() ? row_map->data_ptr<int64_t>() : nullptr, (uint64_t*)w.data_ptr<int64_t>(), ws.data_ptr(), wsb,
-                                            (int32_t)flags, cur_stream()),
+  lrx_check(lrx_flat_ip_search_bounded_wire(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), xb,
+                                            row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                            o.i.data_ptr<int64_t>(), rm, (uint64_t*)o.w.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags, cur_stream()),
             "flat_ip_topk_bounded_wire");
-  return {d, i, w};
+  return {o.d, o.i, o.w};
 }
 
 // [R, Q, k] gathered wire words -> the global top-k (lrx_merge_topk_packed)
@@ -231,13 +244,9 @@ void shard_commit_rows(const at::Tensor& x, const c10::optional<at::Tensor>& x_s
   DevGuard guard(x.device());
   need(x, "x", at::kFloat, 2);
   need(row_bounds, "row_bounds", at::kFloat, 1);
-  if (x_shadow.has_value()) {
-    TORCH_CHECK(x_shadow->is_cuda() && x_shadow->scalar_type() == at::kHalf && x_shadow->is_contiguous() && x_shadow->dim() == 1 &&
-                    x_shadow->numel() >= ((row0 + x.size(0) + 127) / 128) * 128 * x.size(1),
-                "shard_commit_rows: x_shadow must be the 1-D tiled fp16 shadow, large enough for rows row0 .. row0 + n");
-  }
-  lrx_check(lrx_shard_commit_rows(x.data_ptr<float>(), x.stride(0), x.size(0), (int32_t)x.size(1), x_shadow.has_value() ? x_shadow->data_ptr() : nullptr, row0,
-                                  row_bounds.data_ptr<float>(), cur_stream()),
+  void* xb = tiled_rows(x_shadow, at::kHalf, row0 + x.size(0), x.size(1),
+                        "shard_commit_rows: x_shadow must be the 1-D tiled fp16 shadow, large enough for rows row0 .. row0 + n");
+  lrx_check(lrx_shard_commit_rows(x.data_ptr<float>(), x.stride(0), x.size(0), (int32_t)x.size(1), xb, row0, row_bounds.data_ptr<float>(), cur_stream()),
             "shard_commit_rows");
 }
 
@@ -263,21 +272,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_topk(const at::Tensor&
   need(row_bounds, "row_bounds", at::kFloat, 1);
   const int64_t dim = q.size(1);
   TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && dim % 64 == 0 && n_rows >= 0, "sq_fp16_ip_topk: q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kHalf && codes.dim() == 1 && codes.is_contiguous() && codes.numel() >= ((n_rows + 127) / 128) * 128 * dim,
-              "sq_fp16_ip_topk: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
-  if (row_map.has_value()) {
-    need(*row_map, "row_map", at::kLong, 1);
-    TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= n_rows, "sq_fp16_ip_topk: row_map int64 [>= n_rows] contiguous");
-  }
-  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
-  at::Tensor w = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  void* cb = tiled_rows(codes, at::kHalf, n_rows, dim, "sq_fp16_ip_topk: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "sq_fp16_ip_topk: row_map int64 [>= n_rows] contiguous");
+  TopK o = topk_out(q, k, true);
   const size_t wsb = lrx_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
   at::Tensor ws = bytes((int64_t)wsb, q);
-  lrx_check(lrx_sq_fp16_ip_search(codes.data_ptr(), n_rows, (int32_t)dim, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k,
-                                  id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), row_map.has_value() ? row_map->data_ptr<int64_t>() : nullptr,
-                                  (uint64_t*)w.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags, cur_stream()),
+  lrx_check(lrx_sq_fp16_ip_search(cb, n_rows, (int32_t)dim, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k, id_base,
+                                  o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, (uint64_t*)o.w.data_ptr<int64_t>(), ws.data_ptr(), wsb, (int32_t)flags,
+                                  cur_stream()),
             "sq_fp16_ip_topk");
-  return {d, i, w};
+  return {o.d, o.i, o.w};
 }
 
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
@@ -291,20 +295,15 @@ std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Ten
   TORCH_CHECK(q.is_contiguous() && centroids.is_contiguous() && centroids.size(1) == 256 && M > 0 && dim % M == 0 && centroids.size(2) == dim / M && n_rows >= 0,
               "pq_ip_topk: q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
   const int64_t mp = (M + 15) / 16 * 16;
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1 && codes.is_contiguous() && codes.numel() >= ((n_rows + 127) / 128) * 128 * mp,
-              "pq_ip_topk: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
-  if (row_map.has_value()) {
-    need(*row_map, "row_map", at::kLong, 1);
-    TORCH_CHECK(row_map->is_contiguous() && row_map->numel() >= n_rows, "pq_ip_topk: row_map int64 [>= n_rows] contiguous");
-  }
-  at::Tensor d = at::empty({q.size(0), k}, q.options()), i = at::empty({q.size(0), k}, q.options().dtype(at::kLong));
+  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, "pq_ip_topk: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "pq_ip_topk: row_map int64 [>= n_rows] contiguous");
+  TopK o = topk_out(q, k);
   const size_t wsb = lrx_pq_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)k);
   at::Tensor ws = bytes((int64_t)wsb, q);
-  lrx_check(lrx_pq_ip_search(codes.data_ptr(), n_rows, centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, q.data_ptr<float>(), (int32_t)q.size(0),
-                             (int32_t)k, id_base, d.data_ptr<float>(), i.data_ptr<int64_t>(), row_map.has_value() ? row_map->data_ptr<int64_t>() : nullptr,
-                             ws.data_ptr(), wsb, 0, cur_stream()),
+  lrx_check(lrx_pq_ip_search(cb, n_rows, centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k, id_base,
+                             o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, 0, cur_stream()),
             "pq_ip_topk");
-  return {d, i};
+  return {o.d, o.i};
 }
 
 // Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
@@ -316,11 +315,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Te
   need(x, "x", at::kFloat, 2);
   need(row_bounds, "row_bounds", at::kFloat, 1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_range_search: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  if (x_shadow.has_value()) {
-    TORCH_CHECK(x_shadow->is_cuda() && x_shadow->scalar_type() == at::kHalf && x_shadow->dim() == 1 && x_shadow->is_contiguous() &&
-                    x_shadow->numel() >= ((x.size(0) + 127) / 128) * 128 * x.size(1),
-                "flat_ip_range_search: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
-  }
+  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
+                        "flat_ip_range_search: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
   const int64_t Q = q.size(0);
   at::Tensor lims = at::zeros({Q + 1}, q.options().dtype(at::kLong));
   const size_t wsb = lrx_flat_ip_range_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)Q, x_shadow.has_value() ? 1 : 0);
@@ -330,9 +326,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Te
   for (int attempt = 0; attempt < 2; ++attempt) {
     d = at::empty({cap}, q.options());
     i = at::empty({cap}, q.options().dtype(at::kLong));
-    lrx_check(lrx_flat_ip_range_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1),
-                                       x_shadow.has_value() ? x_shadow->data_ptr() : nullptr, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)Q,
-                                       (float)radius, id_base, lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap, ws.data_ptr(), wsb,
+    lrx_check(lrx_flat_ip_range_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), xb,
+                                       row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)Q, (float)radius, id_base, lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap, ws.data_ptr(), wsb,
                                        cur_stream()),
               "flat_ip_range_search");
     const int64_t n = lims[Q].item<int64_t>();

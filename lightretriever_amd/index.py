@@ -1,5 +1,5 @@
-"""HBM-resident flat inner-product index shard: the faiss.IndexFlatIP surface the reference uses
-(retriever/faiss_index.py:20-73: add / search / reset / ntotal), backed by lrx_flat_ip_search."""
+"""HBM-resident inner-product index shards: the faiss.IndexFlatIP surface the reference uses (retriever/faiss_index.py:20-73: add / search /
+reset / ntotal), backed by lrx_flat_ip_search, and its fp16 scalar-quantised and product-quantised siblings."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,12 +12,13 @@ import torch
 from . import _lib
 
 
-_SHARDS = weakref.WeakValueDictionary()   # fp32 storage pointer -> FlatIPIndex (lets the encoder recognise a shard slot it writes into)
+_SHARDS = weakref.WeakValueDictionary()   # fp32 storage pointer -> FlatIPIndex / SQFp16Index (lets the encoder recognise a shard slot it writes into)
 
 
 def shard_of(out: torch.Tensor):
-    """(index, first_row) when `out` is a view of whole rows of a live FlatIPIndex's fp32 storage, else None.  LrxEncoder.encode_packed
-    uses it to hand the shard's fp16 shadow rows and bounds to the encoder's last kernel (lrx_encode_packed_shard)."""
+    """(index, first_row) when `out` is a view of whole rows of a live shard's fp32 storage (FlatIPIndex rows, SQFp16Index staging), else
+    None.  LrxEncoder.encode_packed uses it to hand the shard's fp16 shadow rows (or codes) and bounds to the encoder's last kernel
+    (lrx_encode_packed_shard)."""
     if not _SHARDS or out.dtype != torch.float32 or out.ndim != 2:
         return None
     idx = _SHARDS.get(out.untyped_storage().data_ptr())
@@ -30,25 +31,85 @@ def shard_of(out: torch.Tensor):
     return idx, off // row_bytes
 
 
-class FlatIPIndex:
-    """One HBM-resident shard.  Memory: 4 B/element fp32 rows + 2 B/element tiled fp16 shadow + the search workspace -- per lane in use,
-    for a chunk of up to 256 queries (up to 1024 where the main pass runs on the GEMM kernel: shadow, d >= 1024, more than 256 queries in the
-    call): candidate lists of max(64 Ki, 64 k rounded up to a power of two) 8-byte entries per query (512 KiB per
-    query up to k = 1024: 134 MB per 256-query chunk, 0.5 GB per 1024), the compact sample scores and the [128, ntotal] fp32 region of the gated fallback;
-    `lrx_flat_ip_bounded_workspace_bytes` is the exact figure.  A search of MORE queries than one library chunk forks its chunks over
-    `chunk_lanes` (2) internal HIP streams with one workspace each (so up to 2 x the figure above) unless that would exceed
-    `max_workspace_bytes`, in which case it runs the chunks one after the other on the caller's stream.  Lanes != 0 (pipeline.SearchLanes)
-    add one workspace each.  NOT thread-safe: an index keeps search state (workspaces, internal streams, the statistics of the last search);
-    two host threads must not call search() on the same index at the same time (concurrent searches from ONE thread go through
-    SearchLanes, one lane per search in flight)."""
+def _as_rows(x, d: int, where: str = "", rows: str = "n") -> torch.Tensor:
+    """x (torch tensor on any device, or numpy) as a tensor, checked to be [rows, d] (ValueError "{where}expected [{rows},{d}], got ...")."""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(x)
+    if x.ndim != 2 or x.shape[1] != d:
+        raise ValueError(f"{where}expected [{rows},{d}], got {tuple(x.shape)}")
+    return x
+
+
+def _grow_blocks(buf: torch.Tensor, n_rows: int, width: int, keep_rows: int, zero: bool = False) -> torch.Tensor:
+    """`buf` (flat, whole 128-row blocks of `width` elements per row), or a larger copy of it (zero- or empty-filled) when it holds fewer than
+    `n_rows` rows; the copy keeps the blocks that hold rows [0, keep_rows)."""
+    need = -(-max(n_rows, 0) // 128) * 128 * width
+    if need <= buf.numel():
+        return buf
+    new = (torch.zeros if zero else torch.empty)(need, dtype=buf.dtype, device=buf.device)
+    n_old = min(buf.numel(), -(-keep_rows // 128) * 128 * width)
+    if n_old:
+        new[:n_old].copy_(buf[:n_old])
+    return new
+
+
+def _workspace(slots: dict, key, need: int, device, capture_error: Optional[str] = None) -> torch.Tensor:
+    """slots[key] (a uint8 workspace), regrown to `need` bytes when smaller.  The old block is dropped before the new one is allocated, so
+    the caching allocator can reuse its memory.  capture_error: raise it instead of allocating under HIP-graph capture."""
+    ws = slots.get(key)
+    if ws is None or ws.numel() < need:
+        if capture_error is not None and torch.cuda.is_current_stream_capturing():
+            raise _lib.LrxError(capture_error)
+        ws = slots[key] = None
+        ws = slots[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _check_range(i0: int, n: int, ntotal: int):
+    if i0 < 0 or n < 0 or i0 + n > ntotal:
+        raise ValueError(f"reconstruct_n({i0}, {n}) outside [0, {ntotal})")
+
+
+def _uncovered(intervals: list, a: int, b: int):
+    """The maximal sub-ranges of [a, b) that no (start, end) interval covers, in ascending order."""
+    pos = a
+    for s, e in sorted(intervals):
+        s, e = max(s, a), min(e, b)
+        if e <= pos:
+            continue
+        if s > pos:
+            yield pos, min(s, b)
+        pos = max(pos, e)
+    if pos < b:
+        yield pos, b
+
+
+_CAPTURE_WS_ERROR = ("FlatIPIndex.search under graph capture: the search workspace must exist before the capture starts -- "
+                     "run one eager search with the same number of queries and k first")
+
+
+class _TiledIPIndex:
+    """What FlatIPIndex and SQFp16Index share: rows streamed by the bounded inner-product search from a tiled fp16 layout (include/lrx.h:
+    [128-row block][64-wide k-slice] tiles of 16 KiB, fragment-major inside), the {max |row|, max |row - fp16(row)|} bounds pair, the
+    fp32 storage or staging view the encoder recognises (shard_of), and the search driver: query chunking under max_workspace_bytes, the
+    fork of a call's library chunks over `chunk_lanes` internal streams, per-lane workspaces, wire_out / row_map, last_list_counts.
+    A subclass keeps its own storage (reserve / append_slot / shard_sink / commit / add / save / load) and points the driver at its rows
+    with four hooks:
+      _search_ws_bytes(flags)                     -> f(ntotal, d, nq, k): workspace bytes of one library call of nq queries
+      _search_rows()                              -> (row stride of the fp32 rows, the tiled fp16 rows the search streams or None)
+      _lib_chunk_queries(n, k, flags, has_xb)     -> queries per library chunk of a call of n queries
+      _search_chunk(qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire)   one library call over queries qc on `stream`"""
     # lrx_flat_ip_search_bounded flags (_lib.SEARCH_FILTER_*): which filter the bounded search runs.  A class-level default that tests and A/B
     # tools override (per index or for all); the hits do not depend on it.  (Round 2 had a process-global switch inside the library.)
     search_flags = _lib.SEARCH_FILTER_AUTO
+    # the bounded search (filter pass + exact rescoring); FlatIPIndex.two_pass = False forces the six-product path for every search
+    two_pass = True
+    _D_ALIGN = 32
 
-    def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+    def __init__(self, d: int, device: Optional[torch.device], id_base: int):
         _lib.require_gpu()
-        if d % 32 != 0:
-            raise ValueError(f"FlatIPIndex: d={d} must be a multiple of 32")
+        if d % self._D_ALIGN != 0:
+            raise ValueError(f"{type(self).__name__}: d={d} must be a multiple of {self._D_ALIGN}")
         self.lib = _lib.lib()
         self.d = d
         self.device = device or torch.device("cuda", torch.cuda.current_device())
@@ -60,28 +121,13 @@ class FlatIPIndex:
         self._chunk_streams = None
         self._last_search = None             # what last_list_counts() needs to find the statistics of the last two-pass search
         # {max |row|, max |row - fp16(row)|} over the committed rows, kept on the device (no host sync): the error bound of the fp16
-        # filter pass of lrx_flat_ip_search_bounded is built from them.  two_pass = False forces the six-product path for every search.
+        # filter pass is built from them
         self._bounds = torch.zeros(2, dtype=torch.float32, device=self.device)
-        self.two_pass = True
-        # fp16 shadow of the rows (round-to-nearest-even, saturating): the filter pass of the two-pass search streams it instead of the fp32
-        # rows (half the bytes; the exact rescoring still reads fp32).  +50 % index memory; False = no shadow.  Shadow rows and bounds are
-        # written by the kernel that produces the fp32 rows (the encoder's last kernel for slots, lrx_shard_commit_rows for add()).
-        # Layout: [128-row block][64-wide k-slice] tiles of 16 KiB, fragment-major inside (include/lrx.h): a wave of the filter pass loads
-        # its MFMA operand with one coalesced 1-KiB request, straight into registers.
-        self.shadow_f16 = True
         self.max_workspace_bytes = 12 << 30  # search(): cap of the search workspace; larger query batches are chunked
-        self._xb: Optional[torch.Tensor] = None
-        self._shadow_rows = 0                # committed rows [0, _shadow_rows) have valid shadow rows (== ntotal while shadow_f16 stays on)
-        self._fused: list = []               # row intervals whose shadow + bounds the encoder has already written
+        self._xb: Optional[torch.Tensor] = None   # the tiled fp16 rows (FlatIPIndex: shadow, SQFp16Index: codes), whole 128-row blocks
+        self._shadow_rows = 0                # committed rows [0, _shadow_rows) have valid tiled rows
+        self._fused: list = []               # row intervals whose tiled rows + bounds the encoder has already written
         self._x = torch.empty(0, d, dtype=torch.float32, device=self.device)
-        self._set_storage(torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device))
-
-    @property
-    def _norm_bound(self) -> torch.Tensor:
-        return self._bounds[:1]
-
-    def _wants_shadow(self) -> bool:
-        return self.shadow_f16 and self.d % 64 == 0
 
     def _set_storage(self, x: torch.Tensor):
         if self._x.numel():
@@ -90,36 +136,14 @@ class FlatIPIndex:
         if x.numel():
             _SHARDS[x.untyped_storage().data_ptr()] = self
 
-    # -- storage -------------------------------------------------------------------------------------------------
-    def reserve(self, n_rows: int):
-        if n_rows > self._x.shape[0]:
-            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
-            if self.ntotal:
-                new[:self.ntotal].copy_(self._x[:self.ntotal])
-            self._set_storage(new)
-        self._ensure_shadow()
-
-    def _ensure_shadow(self):
-        if not self._wants_shadow():
-            return
-        cap = self._x.shape[0]
-        need = -(-cap // 128) * 128 * self.d                           # whole 128-row blocks, flat
-        if self._xb is None or self._xb.numel() < need:
-            xb = torch.empty(need, dtype=torch.float16, device=self.device)   # (padding rows of the last block are masked by the kernels)
-            if self._xb is not None and self._shadow_rows:
-                n_old = min(self._xb.numel(), -(-self._shadow_rows // 128) * 128 * self.d)   # the blocks that hold shadowed rows
-                xb[:n_old].copy_(self._xb[:n_old])
-            else:
-                self._shadow_rows = 0
-            self._xb = xb
-        if self._shadow_rows < self.ntotal:
-            # committed rows without a shadow (shadow_f16 switched on after rows were added, or switched off for a while and on again:
-            # commits made meanwhile maintained the bounds only): build their shadow from the fp32 rows before anything streams it
-            a, self._shadow_rows = self._shadow_rows, self.ntotal
-            self._maintain(a, self.ntotal)
+    def reset(self):
+        self.ntotal = 0
+        self._shadow_rows = 0
+        self._bounds.zero_()
+        self._fused = []
 
     def shadow_rows(self, n: Optional[int] = None) -> torch.Tensor:
-        """The shadow as a row-major [n, d] fp16 tensor (a copy: the stored layout is tiled): tests and tools."""
+        """The tiled fp16 rows as a row-major [n, d] fp16 tensor (a copy: the stored layout is tiled): tests and tools."""
         n = self.ntotal if n is None else n
         if self._xb is None:
             raise ValueError("this index keeps no fp16 shadow")
@@ -128,132 +152,31 @@ class FlatIPIndex:
         t = self._xb[:nb * 128 * self.d].view(nb, self.d // 64, 8, 2, 4, 16, 8)          # b, s, w, ks, fq, fi, j
         return t.permute(0, 2, 5, 1, 3, 4, 6).reshape(nb * 128, self.d)[:n]
 
-    def append_slot(self, n_rows: int) -> torch.Tensor:
-        """Rows [ntotal, ntotal+n) of the shard as a writable view (the encoder writes embeddings straight into it, together with
-        their shadow rows and the bounds); call commit(n) afterwards."""
-        if self.ntotal + n_rows > self._x.shape[0]:
-            self.reserve(max(self.ntotal + n_rows, int(self._x.shape[0] * 1.5) + 1))
-        self._ensure_shadow()
-        # whoever receives these rows may write them with anything: an earlier encoder write into them no longer vouches for
-        # their shadow / bounds (commit() maintains whatever is not re-recorded by shard_sink() after this point)
-        a, b = self.ntotal, self.ntotal + n_rows
-        self._fused = [iv for s, e in self._fused for iv in ((s, min(e, a)), (max(s, b), e)) if iv[1] > iv[0]]
-        return self._x[a:b]
-
-    def shard_sink(self, row0: int, n_rows: int):
-        """(tiled shadow tensor or None, first shadow row, bounds) for rows [row0, row0 + n) and a note that their producer maintains them."""
-        self._ensure_shadow()
-        if row0 + n_rows > self.ntotal:               # (rows already committed need no bookkeeping: their producer keeps them valid)
-            self._fused.append((row0, row0 + n_rows))
-        if not (self._wants_shadow() and self._xb is not None):
-            return None, 0, self._bounds
-        return self._xb, row0, self._bounds
-
-    def _maintain(self, a: int, b: int):
-        """Shadow + bounds of rows [a, b) by lrx_shard_commit_rows (one read of the fp32 rows)."""
-        if b <= a:
-            return
-        self._ensure_shadow()
-        xb = self._xb if self._wants_shadow() else None
-        _lib.check(self.lib.lrx_shard_commit_rows(_lib.ptr(self._x[a:]), self._x.stride(0), b - a, self.d, _lib.ptr(xb), a, _lib.ptr(self._bounds),
-                                                  _lib.current_stream()))
-
-    def commit(self, n_rows: int):
-        if n_rows > 0:
-            a, b = self.ntotal, self.ntotal + n_rows
-            # rows the encoder wrote through shard_sink() are done; anything else in [a, b) gets its shadow + bounds now
-            pos = a
-            for s, e in sorted(self._fused):
-                s, e = max(s, a), min(e, b)
-                if e <= pos:
-                    continue
-                self._maintain(pos, min(s, b))
-                pos = max(pos, e)
-            self._maintain(pos, b)
-        # an interval vouches for ONE commit: rows beyond b that are handed out again (append_slot) or written by something else are
-        # maintained by the commit that covers them
-        self._fused = []
-        self.ntotal += n_rows
-        if self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal - n_rows:
-            self._shadow_rows = self.ntotal
-
-    def add(self, x):
-        """faiss add(x f32[n,d]); accepts torch (any device) or numpy."""
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(x)
-        if x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add: expected [n,{self.d}], got {tuple(x.shape)}")
-        slot = self.append_slot(x.shape[0])
-        slot.copy_(x.to(dtype=torch.float32))
-        self.commit(x.shape[0])
-
-    def refresh_norm_bound(self):
-        """Recompute the bounds and the fp16 shadow over all committed rows: needed only after writing into committed rows in place
-        with something other than the encoder (which maintains both itself)."""
-        self._bounds.zero_()
-        self._maintain(0, self.ntotal)
-
-    def reset(self):
-        self.ntotal = 0
-        self._shadow_rows = 0
-        self._bounds.zero_()
-        self._fused = []
-
-    # -- persistence (faiss.write_index / read_index of an IndexFlatIP, see index_io.py) --------------------------
-    def save(self, fname: str, chunk_rows: int = 262144):
-        from .index_io import write_flat_ip
-        write_flat_ip(fname, (self._x[s:min(s + chunk_rows, self.ntotal)].cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
-                      self.d, self.ntotal)
-
-    @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144) -> "FlatIPIndex":
-        from .index_io import read_flat_ip
-        import numpy as np
-        mm = read_flat_ip(fname)
-        idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
-        for s in range(0, mm.shape[0], chunk_rows):
-            e = min(s + chunk_rows, mm.shape[0])
-            idx._x[s:e].copy_(torch.from_numpy(np.array(mm[s:e], copy=True)), non_blocking=False)
-        idx.commit(mm.shape[0])
-        return idx
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self._x[:self.ntotal]
-
     # -- search --------------------------------------------------------------------------------------------------
     def _lane_workspace(self, lane: int, need: int, user_stream: Optional["torch.cuda.Stream"] = None) -> torch.Tensor:
         """The workspace of `lane`, grown to `need` bytes.  user_stream: the stream its kernels will run on when that is not the stream
         current now (the internal chunk streams): the caching allocator is told, so that a later regrow / free cannot hand the block to the
         caller's stream while kernels of that stream still use it."""
-        ws = self._ws if lane == 0 else self._lane_ws.get(lane)
-        if ws is None or ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                # an allocation made under HIP-graph capture lives in the graph's private pool: the index would keep pointing at memory that
-                # goes back to the allocator with the graph (the memory-access fault of round 2's capture probe)
-                raise _lib.LrxError("FlatIPIndex.search under graph capture: the search workspace must exist before the capture starts -- "
-                                    "run one eager search with the same number of queries and k first")
-            ws = None
-            if lane == 0:
-                self._ws = None
-                ws = self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            else:
-                self._lane_ws.pop(lane, None)
-                ws = self._lane_ws[lane] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        # (an allocation made under HIP-graph capture lives in the graph's private pool: the index would keep pointing at memory that goes
+        # back to the allocator with the graph -- the memory-access fault of round 2's capture probe)
+        ws = _workspace(vars(self) if lane == 0 else self._lane_ws, "_ws" if lane == 0 else lane, need, self.device, _CAPTURE_WS_ERROR)
         if user_stream is not None and user_stream != torch.cuda.current_stream():
             ws.record_stream(user_stream)
         return ws
+
+    def _fit_chunk(self, Q: int, ws_bytes) -> int:
+        """Queries per host chunk: Q, or the largest of 256, 128, 64, ... whose workspace ws_bytes(chunk) stays under max_workspace_bytes."""
+        chunk = Q
+        while chunk > 1 and int(ws_bytes(chunk)) > int(self.max_workspace_bytes):
+            chunk = 256 if chunk > 256 else (128 if chunk > 128 else chunk // 2)
+        return chunk
 
     def search(self, q, k: int, wire_out: Optional[torch.Tensor] = None, row_map: Optional[torch.Tensor] = None, lane: int = 0):
         """-> (D f32[Q,k], I i64[Q,k]) device tensors, descending scores, ids = id_base + row, ties -> lower id,
         (-FLT_MAX, -1) padding when k > ntotal.  wire_out (int64 [Q,k], optional): also filled with the exchange words of a row-sharded
         search (lrx_pack_topk's format, `row_map` applied) by the last kernel of the search itself.  lane: which of the index's search
         workspaces to use -- searches that may be in flight at the same time (different HIP streams: pipeline.SearchLanes) take different lanes."""
-        if not isinstance(q, torch.Tensor):
-            q = torch.from_numpy(q)
-        q = q.to(device=self.device, dtype=torch.float32).contiguous()
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
         Q = q.shape[0]
         D = torch.empty(Q, k, dtype=torch.float32, device=self.device)
         I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
@@ -266,9 +189,7 @@ class FlatIPIndex:
         # (results do not depend on the chunking).
         flags = int(self.search_flags)
         ws_bytes = self._search_ws_bytes(flags)
-        chunk = Q
-        while chunk > 1 and int(ws_bytes(self.ntotal, self.d, chunk, k)) > int(self.max_workspace_bytes):
-            chunk = 256 if chunk > 256 else (128 if chunk > 128 else chunk // 2)
+        chunk = self._fit_chunk(Q, lambda n: ws_bytes(self.ntotal, self.d, n, k))
         ldx, xb = self._search_rows()
         # the library walks a call's queries in chunks of this size: 256 over the shadow (128 without) or, where its main pass runs on the GEMM
         # kernel (D >= 1024), ONE pass over the shadow per up to 1024 queries (lrx_flat_ip_bounded_chunk_queries, round 6)
@@ -310,23 +231,6 @@ class FlatIPIndex:
         self._last_search = ((n_last_call - 1) % lib_chunk_of(n_last_call) + 1, k, flags, xb is not None, last_ws, self.ntotal, bool(self.two_pass))   # ... and of its last chunk
         return D, I
 
-    # (search() over this index's rows: the hooks SQFp16Index replaces)
-    def _search_ws_bytes(self, flags: int):
-        if self.two_pass:
-            return lambda n, d, nq, kk: self.lib.lrx_flat_ip_bounded_workspace_bytes(n, d, nq, kk, flags)
-        return self.lib.lrx_flat_ip_workspace_bytes
-
-    def _search_rows(self):
-        """(row stride of the fp32 rows, the tiled fp16 shadow the search streams or None)."""
-        ldx = self._x.stride(0) if self._x.shape[0] else self.d
-        if self.two_pass and self.shadow_f16:
-            self._ensure_shadow()                       # (no-op unless rows were committed while the shadow was switched off)
-        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
-        return ldx, xb
-
-    def _lib_chunk_queries(self, n: int, k: int, flags: int, has_xb: bool) -> int:
-        return int(self.lib.lrx_flat_ip_bounded_chunk_queries(self.ntotal, self.d, n, k, flags, int(has_xb))) if self.two_pass else 128
-
     def _run_chunks(self, q, D, I, k, chunk, fork, lane_ws, ws, start, xb, ldx, flags, row_map, wire_out):
         Q = q.shape[0]
         for j, s in enumerate(range(0, Q, chunk)):
@@ -340,6 +244,163 @@ class FlatIPIndex:
             else:
                 stream = _lib.current_stream()
             self._search_chunk(qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire_out[s:s + chunk] if wire_out is not None else None)
+
+    def last_list_counts(self) -> torch.Tensor:
+        """uint32-valued int64 tensor [q]: candidate-list entries per query of the last chunk of the last two-pass search (the rows that
+        passed the filter threshold and reached the refine step) -- statistics for tools and bench legs.  Zeros when the last search was
+        not a two-pass search (no candidate lists exist); raises before the first search."""
+        if self._last_search is None:
+            raise _lib.LrxError("last_list_counts(): no search has run on this index yet")
+        nq, k, flags, has_shadow, ws, ntotal, two_pass = self._last_search
+        out = torch.zeros(nq, dtype=torch.int32, device=self.device)
+        if two_pass:                    # the workspace layout is the one planned for the ntotal of THAT search (add() / reset() since do not matter)
+            _lib.check(self.lib.lrx_flat_ip_bounded_list_counts(_lib.ptr(ws), ntotal, self.d, nq, k, flags, int(has_shadow), _lib.ptr(out),
+                                                                _lib.current_stream()))
+        return out.to(torch.int64)
+
+
+class FlatIPIndex(_TiledIPIndex):
+    """One HBM-resident shard.  Memory: 4 B/element fp32 rows + 2 B/element tiled fp16 shadow + the search workspace -- per lane in use,
+    for a chunk of up to 256 queries (up to 1024 where the main pass runs on the GEMM kernel: shadow, d >= 1024, more than 256 queries in the
+    call): candidate lists of max(64 Ki, 64 k rounded up to a power of two) 8-byte entries per query (512 KiB per
+    query up to k = 1024: 134 MB per 256-query chunk, 0.5 GB per 1024), the compact sample scores and the [128, ntotal] fp32 region of the gated fallback;
+    `lrx_flat_ip_bounded_workspace_bytes` is the exact figure.  A search of MORE queries than one library chunk forks its chunks over
+    `chunk_lanes` (2) internal HIP streams with one workspace each (so up to 2 x the figure above) unless that would exceed
+    `max_workspace_bytes`, in which case it runs the chunks one after the other on the caller's stream.  Lanes != 0 (pipeline.SearchLanes)
+    add one workspace each.  NOT thread-safe: an index keeps search state (workspaces, internal streams, the statistics of the last search);
+    two host threads must not call search() on the same index at the same time (concurrent searches from ONE thread go through
+    SearchLanes, one lane per search in flight)."""
+
+    def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        super().__init__(d, device, id_base)
+        # fp16 shadow of the rows (round-to-nearest-even, saturating): the filter pass of the two-pass search streams it instead of the fp32
+        # rows (half the bytes; the exact rescoring still reads fp32).  +50 % index memory; False = no shadow.  Shadow rows and bounds are
+        # written by the kernel that produces the fp32 rows (the encoder's last kernel for slots, lrx_shard_commit_rows for add()).
+        # Layout: [128-row block][64-wide k-slice] tiles of 16 KiB, fragment-major inside (include/lrx.h): a wave of the filter pass loads
+        # its MFMA operand with one coalesced 1-KiB request, straight into registers.  (_shadow_rows == ntotal while shadow_f16 stays on.)
+        self.shadow_f16 = True
+        self._set_storage(torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device))
+
+    @property
+    def _norm_bound(self) -> torch.Tensor:
+        return self._bounds[:1]
+
+    def _wants_shadow(self) -> bool:
+        return self.shadow_f16 and self.d % 64 == 0
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    def reserve(self, n_rows: int):
+        if n_rows > self._x.shape[0]:
+            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+            if self.ntotal:
+                new[:self.ntotal].copy_(self._x[:self.ntotal])
+            self._set_storage(new)
+        self._ensure_shadow()
+
+    def _ensure_shadow(self):
+        if not self._wants_shadow():
+            return
+        if self._xb is None:
+            self._xb = torch.empty(0, dtype=torch.float16, device=self.device)
+        # (padding rows of the last block are masked by the kernels; the copy keeps the blocks that hold shadowed rows)
+        self._xb = _grow_blocks(self._xb, self._x.shape[0], self.d, self._shadow_rows)
+        if self._shadow_rows < self.ntotal:
+            # committed rows without a shadow (shadow_f16 switched on after rows were added, or switched off for a while and on again:
+            # commits made meanwhile maintained the bounds only): build their shadow from the fp32 rows before anything streams it
+            a, self._shadow_rows = self._shadow_rows, self.ntotal
+            self._maintain(a, self.ntotal)
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """Rows [ntotal, ntotal+n) of the shard as a writable view (the encoder writes embeddings straight into it, together with
+        their shadow rows and the bounds); call commit(n) afterwards."""
+        if self.ntotal + n_rows > self._x.shape[0]:
+            self.reserve(max(self.ntotal + n_rows, int(self._x.shape[0] * 1.5) + 1))
+        self._ensure_shadow()
+        # whoever receives these rows may write them with anything: an earlier encoder write into them no longer vouches for
+        # their shadow / bounds (commit() maintains whatever is not re-recorded by shard_sink() after this point)
+        a, b = self.ntotal, self.ntotal + n_rows
+        self._fused = [iv for s, e in self._fused for iv in ((s, min(e, a)), (max(s, b), e)) if iv[1] > iv[0]]
+        return self._x[a:b]
+
+    def shard_sink(self, row0: int, n_rows: int):
+        """(tiled shadow tensor or None, first shadow row, bounds) for rows [row0, row0 + n) and a note that their producer maintains them."""
+        self._ensure_shadow()
+        if row0 + n_rows > self.ntotal:               # (rows already committed need no bookkeeping: their producer keeps them valid)
+            self._fused.append((row0, row0 + n_rows))
+        if not (self._wants_shadow() and self._xb is not None):
+            return None, 0, self._bounds
+        return self._xb, row0, self._bounds
+
+    def _maintain(self, a: int, b: int):
+        """Shadow + bounds of rows [a, b) by lrx_shard_commit_rows (one read of the fp32 rows)."""
+        if b <= a:
+            return
+        self._ensure_shadow()
+        xb = self._xb if self._wants_shadow() else None
+        _lib.check(self.lib.lrx_shard_commit_rows(_lib.ptr(self._x[a:]), self._x.stride(0), b - a, self.d, _lib.ptr(xb), a, _lib.ptr(self._bounds),
+                                                  _lib.current_stream()))
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            # rows the encoder wrote through shard_sink() are done; anything else in [a, b) gets its shadow + bounds now
+            for a, b in _uncovered(self._fused, self.ntotal, self.ntotal + n_rows):
+                self._maintain(a, b)
+        # an interval vouches for ONE commit: rows beyond b that are handed out again (append_slot) or written by something else are
+        # maintained by the commit that covers them
+        self._fused = []
+        self.ntotal += n_rows
+        if self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal - n_rows:
+            self._shadow_rows = self.ntotal
+
+    def add(self, x):
+        """faiss add(x f32[n,d]); accepts torch (any device) or numpy."""
+        x = _as_rows(x, self.d, "add: ")
+        slot = self.append_slot(x.shape[0])
+        slot.copy_(x.to(dtype=torch.float32))
+        self.commit(x.shape[0])
+
+    def refresh_norm_bound(self):
+        """Recompute the bounds and the fp16 shadow over all committed rows: needed only after writing into committed rows in place
+        with something other than the encoder (which maintains both itself)."""
+        self._bounds.zero_()
+        self._maintain(0, self.ntotal)
+
+    # -- persistence (faiss.write_index / read_index of an IndexFlatIP, see index_io.py) --------------------------
+    def save(self, fname: str, chunk_rows: int = 262144):
+        from .index_io import write_flat_ip
+        write_flat_ip(fname, (self._x[s:min(s + chunk_rows, self.ntotal)].cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
+                      self.d, self.ntotal)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144) -> "FlatIPIndex":
+        from .index_io import read_flat_ip
+        mm = read_flat_ip(fname)
+        idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
+        for s in range(0, mm.shape[0], chunk_rows):
+            e = min(s + chunk_rows, mm.shape[0])
+            idx._x[s:e].copy_(torch.from_numpy(np.array(mm[s:e], copy=True)), non_blocking=False)
+        idx.commit(mm.shape[0])
+        return idx
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self._x[:self.ntotal]
+
+    # -- search hooks (see _TiledIPIndex) ---------------------------------------------------------------------------
+    def _search_ws_bytes(self, flags: int):
+        if self.two_pass:
+            return lambda n, d, nq, kk: self.lib.lrx_flat_ip_bounded_workspace_bytes(n, d, nq, kk, flags)
+        return self.lib.lrx_flat_ip_workspace_bytes
+
+    def _search_rows(self):
+        ldx = self._x.stride(0) if self._x.shape[0] else self.d
+        if self.two_pass and self.shadow_f16:
+            self._ensure_shadow()                       # (no-op unless rows were committed while the shadow was switched off)
+        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
+        return ldx, xb
+
+    def _lib_chunk_queries(self, n: int, k: int, flags: int, has_xb: bool) -> int:
+        return int(self.lib.lrx_flat_ip_bounded_chunk_queries(self.ntotal, self.d, n, k, flags, int(has_xb))) if self.two_pass else 128
 
     def _search_chunk(self, qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire):
         if self.two_pass:
@@ -361,11 +422,7 @@ class FlatIPIndex:
         library call when the workspace cap splits the queries); not under graph capture."""
         if torch.cuda.is_current_stream_capturing():
             raise _lib.LrxError("FlatIPIndex.range_search under graph capture: the result length is read back to the host")
-        if not isinstance(q, torch.Tensor):
-            q = torch.from_numpy(q)
-        q = q.to(device=self.device, dtype=torch.float32).contiguous()
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"range_search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        q = _as_rows(q, self.d, "range_search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
         radius = float(radius)
         if radius != radius:
             raise ValueError("range_search: radius is NaN")
@@ -373,14 +430,9 @@ class FlatIPIndex:
         lims = torch.zeros(Q + 1, dtype=torch.int64, device=self.device)
         if Q == 0 or self.ntotal == 0:
             return lims, torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)
-        ldx = self._x.stride(0) if self._x.shape[0] else self.d
-        if self.two_pass and self.shadow_f16:
-            self._ensure_shadow()
-        xb = self._xb if (self.two_pass and self._wants_shadow() and self._xb is not None and self._shadow_rows >= self.ntotal) else None
+        ldx, xb = self._search_rows()
         ws_bytes = lambda n: int(self.lib.lrx_flat_ip_range_workspace_bytes(self.ntotal, self.d, n, int(xb is not None)))
-        chunk = Q
-        while chunk > 1 and ws_bytes(chunk) > int(self.max_workspace_bytes):
-            chunk = 256 if chunk > 256 else (128 if chunk > 128 else chunk // 2)
+        chunk = self._fit_chunk(Q, ws_bytes)
         ws = self._lane_workspace(0, ws_bytes(chunk))
         stream = _lib.current_stream()
         parts = []
@@ -408,54 +460,23 @@ class FlatIPIndex:
             off += n
         return lims, torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts])
 
-    def last_list_counts(self) -> torch.Tensor:
-        """uint32-valued int64 tensor [q]: candidate-list entries per query of the last chunk of the last two-pass search (the rows that
-        passed the filter threshold and reached the refine step) -- statistics for tools and bench legs.  Zeros when the last search was
-        not a two-pass search (no candidate lists exist); raises before the first search."""
-        if self._last_search is None:
-            raise _lib.LrxError("last_list_counts(): no search has run on this index yet")
-        nq, k, flags, has_shadow, ws, ntotal, two_pass = self._last_search
-        out = torch.zeros(nq, dtype=torch.int32, device=self.device)
-        if two_pass:                    # the workspace layout is the one planned for the ntotal of THAT search (add() / reset() since do not matter)
-            _lib.check(self.lib.lrx_flat_ip_bounded_list_counts(_lib.ptr(ws), ntotal, self.d, nq, k, flags, int(has_shadow), _lib.ptr(out),
-                                                                _lib.current_stream()))
-        return out.to(torch.int64)
 
-
-
-class SQFp16Index(FlatIPIndex):
+class SQFp16Index(_TiledIPIndex):
     """fp16 scalar-quantised inner-product shard: the faiss IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT) surface (add / search /
     reset / ntotal / reconstruct_n / save / load), backed by lrx_sq_fp16_ip_search.  The only resident copy of the rows is their codes
     c = fp16(x) (round-to-nearest-even, saturating at +-65504 where faiss gives inf) in the tiled layout of FlatIPIndex's shadow: 2 B/element
     instead of 6.  Scores are (float) of the fp64 sum of q_i * c_i, exact top-k under that score, ties to the lower row, (-FLT_MAX, -1)
     padding -- for rows that are exactly fp16-representable, bit-identical to FlatIPIndex.  d % 64 == 0.
-    Search chunking, lanes, workspaces and wire_out / row_map are FlatIPIndex's (lrx_sq_fp16_ip_workspace_bytes sizes the workspace).
-    Rows enter through add() (lrx_shard_commit_rows straight from the caller's rows) or through append_slot(n) / commit(n): the slot is a
-    transient fp32 staging view that LrxEncoder.encode_packed recognises (shard_of), so the encoder's last kernel writes the codes and the
-    bounds itself; commit() converts whatever it did not write and releases the staging.  Staging scales with the chunk being added."""
+    Search chunking, lanes, workspaces and wire_out / row_map are the shared driver's (_TiledIPIndex; lrx_sq_fp16_ip_workspace_bytes sizes
+    the workspace).  Rows enter through add() (lrx_shard_commit_rows straight from the caller's rows) or through append_slot(n) / commit(n):
+    the slot is a transient fp32 staging view that LrxEncoder.encode_packed recognises (shard_of), so the encoder's last kernel writes the
+    codes and the bounds itself; commit() converts whatever it did not write and releases the staging.  Staging scales with the chunk being
+    added."""
+    _D_ALIGN = 64
 
     def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
-        _lib.require_gpu()
-        if d % 64 != 0:
-            raise ValueError(f"SQFp16Index: d={d} must be a multiple of 64")
-        self.lib = _lib.lib()
-        self.d = d
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.ntotal = 0
-        self.id_base = id_base
-        self._ws = None
-        self._lane_ws: dict = {}
-        self.chunk_lanes = 2
-        self._chunk_streams = None
-        self._last_search = None
-        self._bounds = torch.zeros(2, dtype=torch.float32, device=self.device)   # {max |x|, max |x - fp16(x)|}: R16 <= R + E (include/lrx.h)
-        self.two_pass = True
-        self.shadow_f16 = True
-        self.max_workspace_bytes = 12 << 30
-        self._xb = torch.empty(0, dtype=torch.float16, device=self.device)         # the codes, whole 128-row blocks
-        self._shadow_rows = 0
-        self._fused: list = []
-        self._x = torch.empty(0, d, dtype=torch.float32, device=self.device)       # staging of the open append_slot (rows ntotal ...)
+        super().__init__(d, device, id_base)   # (_x: the staging of the open append_slot, rows ntotal ...)
+        self._xb = torch.empty(0, dtype=torch.float16, device=self.device)     # the codes; R16 <= R + E from the bounds pair (include/lrx.h)
         self.reserve(capacity)
 
     # -- storage -------------------------------------------------------------------------------------------------
@@ -464,16 +485,10 @@ class SQFp16Index(FlatIPIndex):
         return self._xb.numel() // self.d
 
     def reserve(self, n_rows: int):
-        need = -(-max(n_rows, 0) // 128) * 128 * self.d
-        if need > self._xb.numel():
-            xb = torch.empty(need, dtype=torch.float16, device=self.device)
-            n_old = min(self._xb.numel(), -(-self.ntotal // 128) * 128 * self.d)
-            if n_old:
-                xb[:n_old].copy_(self._xb[:n_old])
-            self._xb = xb
+        self._xb = _grow_blocks(self._xb, n_rows, self.d, self.ntotal)
 
-    def _ensure_shadow(self):
-        pass                                           # (the codes are the rows: always complete)
+    def _set_staging(self, n_rows: int):
+        self._set_storage(torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device))
 
     def append_slot(self, n_rows: int) -> torch.Tensor:
         """A transient fp32 staging view for rows [ntotal, ntotal + n): write them (the encoder writes codes and bounds itself through
@@ -481,8 +496,8 @@ class SQFp16Index(FlatIPIndex):
         if self.ntotal + n_rows > self.capacity:
             self.reserve(max(self.ntotal + n_rows, int(self.capacity * 1.5) + 1))
         if self._x.shape[0] < n_rows:
-            self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))
-            self._set_storage(torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device))
+            self._set_staging(0)
+            self._set_staging(n_rows)
         self._fused = []
         return self._x[:n_rows]
 
@@ -500,27 +515,16 @@ class SQFp16Index(FlatIPIndex):
         if n_rows > 0:
             if n_rows > self._x.shape[0]:
                 raise ValueError(f"commit({n_rows}): only {self._x.shape[0]} staged rows")
-            pos = 0
-            for s, e in sorted(self._fused):
-                s, e = max(s, 0), min(e, n_rows)
-                if e <= pos:
-                    continue
-                if s > pos:
-                    self._commit_from(self._x[pos:s], self.ntotal + pos)
-                pos = max(pos, e)
-            if pos < n_rows:
-                self._commit_from(self._x[pos:n_rows], self.ntotal + pos)
+            for a, b in _uncovered(self._fused, 0, n_rows):
+                self._commit_from(self._x[a:b], self.ntotal + a)
         self._fused = []
         self.ntotal += n_rows
         self._shadow_rows = self.ntotal
-        self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))   # staging released (stream-ordered by the allocator)
+        self._set_staging(0)                           # staging released (stream-ordered by the allocator)
 
     def add(self, x):
         """faiss add(x f32[n,d]): the codes are written straight from the rows (one device copy when x is not already fp32 on this device)."""
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(x)
-        if x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add: expected [n,{self.d}], got {tuple(x.shape)}")
+        x = _as_rows(x, self.d, "add: ")
         n = x.shape[0]
         if self.ntotal + n > self.capacity:
             self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
@@ -531,20 +535,13 @@ class SQFp16Index(FlatIPIndex):
         self.ntotal += n
         self._shadow_rows = self.ntotal
 
-    def refresh_norm_bound(self):
-        pass                                           # (rows are written through commit / add only: the bounds are always current)
-
     def reset(self):
-        self.ntotal = 0
-        self._shadow_rows = 0
-        self._bounds.zero_()
-        self._fused = []
-        self._set_storage(torch.empty(0, self.d, dtype=torch.float32, device=self.device))
+        super().reset()
+        self._set_staging(0)
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """Rows [i0, i0 + n) decoded exactly to fp32 (device tensor [n, d])."""
-        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
-            raise ValueError(f"reconstruct_n({i0}, {n}) outside [0, {self.ntotal})")
+        _check_range(i0, n, self.ntotal)
         out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
         if n:
             _lib.check(self.lib.lrx_sq_fp16_decode_rows(_lib.ptr(self._xb), i0, n, self.d, _lib.ptr(out), self.d, _lib.current_stream()))
@@ -567,7 +564,6 @@ class SQFp16Index(FlatIPIndex):
     @classmethod
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144) -> "SQFp16Index":
         from .index_io import read_sq_fp16
-        import numpy as np
         mm = read_sq_fp16(fname)
         idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
         for s in range(0, mm.shape[0], chunk_rows):
@@ -575,7 +571,7 @@ class SQFp16Index(FlatIPIndex):
             idx.add(torch.from_numpy(np.array(mm[s:e], copy=True)).to(idx.device).float())   # fp16 -> fp32 -> fp16: exact
         return idx
 
-    # -- search (FlatIPIndex.search: chunking, lanes, workspaces; these hooks point it at the codes) ----------------
+    # -- search hooks (see _TiledIPIndex): the codes are the rows -----------------------------------------------------
     def _search_ws_bytes(self, flags: int):
         return lambda n, d, nq, kk: self.lib.lrx_sq_fp16_ip_workspace_bytes(n, d, nq, kk, flags)
 
@@ -638,13 +634,7 @@ class PQIndex:
         return self._codes.numel() // self.Mp
 
     def reserve(self, n_rows: int):
-        need = -(-max(n_rows, 0) // 128) * 128 * self.Mp
-        if need > self._codes.numel():
-            c = torch.zeros(need, dtype=torch.uint8, device=self.device)
-            n_old = min(self._codes.numel(), -(-self.ntotal // 128) * 128 * self.Mp)
-            if n_old:
-                c[:n_old].copy_(self._codes[:n_old])
-            self._codes = c
+        self._codes = _grow_blocks(self._codes, n_rows, self.Mp, self.ntotal, zero=True)
 
     def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, centroids: torch.Tensor):
         for s in range(0, x.shape[0], 262144):
@@ -653,11 +643,7 @@ class PQIndex:
                                               row0 + s, _lib.current_stream()))
 
     def _rows(self, x) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor):
-            x = torch.from_numpy(x)
-        if x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"expected [n,{self.d}], got {tuple(x.shape)}")
-        x = x.to(device=self.device, dtype=torch.float32)
+        x = _as_rows(x, self.d).to(device=self.device, dtype=torch.float32)
         return x.contiguous() if x.stride(1) != 1 else x
 
     def blocked_to_rows(self, blocked: torch.Tensor, n: int) -> torch.Tensor:
@@ -744,8 +730,7 @@ class PQIndex:
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """Rows [i0, i0 + n) decoded (centroid of each code) to fp32, device tensor [n, d]."""
-        if i0 < 0 or n < 0 or i0 + n > self.ntotal:
-            raise ValueError(f"reconstruct_n({i0}, {n}) outside [0, {self.ntotal})")
+        _check_range(i0, n, self.ntotal)
         out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
         if n:
             _lib.check(self.lib.lrx_pq_decode_rows(_lib.ptr(self._codes), i0, n, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(out), self.d,
@@ -791,11 +776,7 @@ class PQIndex:
     def search(self, q, k: int, row_map: Optional[torch.Tensor] = None):
         """faiss search -> (D f32[Q,k], I i64[Q,k]) device tensors: score descending, ties to the lower row, (-FLT_MAX, -1) padding when
         k > ntotal.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries) when given."""
-        if not isinstance(q, torch.Tensor):
-            q = torch.from_numpy(q)
-        q = q.to(device=self.device, dtype=torch.float32).contiguous()
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
         if not 1 <= k <= 2048:
             raise ValueError(f"search: k={k} out of range (1..2048)")
         if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
@@ -805,12 +786,9 @@ class PQIndex:
         I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
         if Q == 0:
             return D, I
-        need = int(self.lib.lrx_pq_ip_workspace_bytes(self.ntotal, self.d, self.M, Q, k))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_pq_ip_workspace_bytes(self.ntotal, self.d, self.M, Q, k)), self.device)
         _lib.check(self.lib.lrx_pq_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(q), Q, k,
-                                             int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(self._ws), self._ws.numel(), 0,
+                                             int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
                                              _lib.current_stream()))
         return D, I
 

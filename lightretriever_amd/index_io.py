@@ -61,22 +61,38 @@ def shard_prefix(prefix: str, rank: int = 0, world: int = 1) -> str:
     return prefix if world == 1 else f"{prefix}.rank{rank}-of-{world}"
 
 
-def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
-    """blocks: fp32 [n_i, d] arrays in row order (streamed: the shard comes off the GPU in chunks), sum n_i == ntotal."""
+def _write_index(fname: str, who: str, fourcc: bytes, d: int, ntotal: int, is_trained: bool, head: bytes, blocks: Iterable[np.ndarray],
+                 dtype: str, width: int, width_name: str = "d", tail: bytes = b"") -> None:
+    """The common index header, `head` (the format's fields up to and including the size word of the rows), the rows streamed from
+    `blocks` (arrays [n_i, width] in row order, sum n_i == ntotal, written as `dtype`), then `tail` -- to a .tmp file renamed over fname."""
     tmp = fname + ".tmp"
     with open(tmp, "wb") as f:
-        f.write(_HEADER.pack(FOURCC_FLAT_IP, d, ntotal, 1 << 20, 1 << 20, 1, 0))
-        f.write(struct.pack("<Q", ntotal * d))
+        f.write(_HEADER.pack(fourcc, d, ntotal, 1 << 20, 1 << 20, int(bool(is_trained)), 0))
+        f.write(head)
         rows = 0
         for b in blocks:
-            b = np.ascontiguousarray(b, dtype="<f4")
-            if b.ndim != 2 or b.shape[1] != d:
-                raise ValueError(f"write_flat_ip: block {b.shape} does not match d={d}")
+            b = np.ascontiguousarray(b, dtype=dtype)
+            if b.ndim != 2 or b.shape[1] != width:
+                raise ValueError(f"{who}: block {b.shape} does not match {width_name}={width}")
             f.write(b.tobytes())
             rows += b.shape[0]
         if rows != ntotal:
-            raise ValueError(f"write_flat_ip: wrote {rows} rows, header says {ntotal}")
+            raise ValueError(f"{who}: wrote {rows} rows, header says {ntotal}")
+        f.write(tail)
     os.replace(tmp, fname)
+
+
+def _read_header(f, fname: str, fourcc: bytes, what: str):
+    """-> (d, ntotal, is_trained, metric_type) of the common index header at f's position; ValueError unless its fourcc is `fourcc`."""
+    got, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
+    if got != fourcc:
+        raise ValueError(f"{fname}: fourcc {got!r} is not {what} ({fourcc.decode()!r})")
+    return d, ntotal, trained, metric
+
+
+def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
+    """blocks: fp32 [n_i, d] arrays in row order (streamed: the shard comes off the GPU in chunks), sum n_i == ntotal."""
+    _write_index(fname, "write_flat_ip", FOURCC_FLAT_IP, d, ntotal, True, struct.pack("<Q", ntotal * d), blocks, "<f4", d)
 
 
 def read_flat_ip(fname: str) -> np.memmap:
@@ -85,10 +101,8 @@ def read_flat_ip(fname: str) -> np.memmap:
     if size < HEADER_BYTES:
         raise ValueError(f"{fname}: too short for a flat index header")
     with open(fname, "rb") as f:
-        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
+        d, ntotal, _, metric = _read_header(f, fname, FOURCC_FLAT_IP, "an inner-product flat index")
         (n_floats,) = struct.unpack("<Q", f.read(8))
-    if fourcc != FOURCC_FLAT_IP:
-        raise ValueError(f"{fname}: fourcc {fourcc!r} is not an inner-product flat index ('IxFI')")
     if metric != 0 or d <= 0 or ntotal < 0 or n_floats != ntotal * d or size != HEADER_BYTES + 4 * n_floats:
         raise ValueError(f"{fname}: inconsistent flat index header (d={d}, ntotal={ntotal}, floats={n_floats}, metric={metric}, bytes={size})")
     return np.memmap(fname, dtype="<f4", mode="r", offset=HEADER_BYTES, shape=(ntotal, d))
@@ -102,22 +116,8 @@ SQ_HEADER_BYTES = _HEADER.size + _SQ.size + 8 + 8   # + empty `trained` vector +
 
 def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
     """blocks: fp16 [n_i, d] arrays (the codes) in row order, sum n_i == ntotal."""
-    tmp = fname + ".tmp"
-    with open(tmp, "wb") as f:
-        f.write(_HEADER.pack(FOURCC_SQ, d, ntotal, 1 << 20, 1 << 20, 1, 0))
-        f.write(_SQ.pack(QT_FP16, 0, 0.0, d, 2 * d))
-        f.write(struct.pack("<Q", 0))
-        f.write(struct.pack("<Q", ntotal * 2 * d))
-        rows = 0
-        for b in blocks:
-            b = np.ascontiguousarray(b, dtype="<f2")
-            if b.ndim != 2 or b.shape[1] != d:
-                raise ValueError(f"write_sq_fp16: block {b.shape} does not match d={d}")
-            f.write(b.tobytes())
-            rows += b.shape[0]
-        if rows != ntotal:
-            raise ValueError(f"write_sq_fp16: wrote {rows} rows, header says {ntotal}")
-    os.replace(tmp, fname)
+    head = _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<QQ", 0, ntotal * 2 * d)   # (empty `trained` vector, code bytes)
+    _write_index(fname, "write_sq_fp16", FOURCC_SQ, d, ntotal, True, head, blocks, "<f2", d)
 
 
 def read_sq_fp16(fname: str) -> np.memmap:
@@ -126,9 +126,7 @@ def read_sq_fp16(fname: str) -> np.memmap:
     if size < _HEADER.size + _SQ.size + 8:
         raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
     with open(fname, "rb") as f:
-        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
-        if fourcc != FOURCC_SQ:
-            raise ValueError(f"{fname}: fourcc {fourcc!r} is not a scalar-quantiser index ('IxSQ')")
+        d, ntotal, _, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
         qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
         if qtype != QT_FP16:
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served (only QT_fp16 = {QT_FP16})")
@@ -156,24 +154,8 @@ def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d:
     c = np.ascontiguousarray(centroids, dtype="<f4")
     if c.size != d * 256:
         raise ValueError(f"write_pq: {c.size} centroid floats, expected d * 256 = {d * 256}")
-    tmp = fname + ".tmp"
-    with open(tmp, "wb") as f:
-        f.write(_HEADER.pack(FOURCC_PQ, d, ntotal, 1 << 20, 1 << 20, int(bool(is_trained)), 0))
-        f.write(_PQ.pack(d, M, 8))
-        f.write(struct.pack("<Q", d * 256))
-        f.write(c.tobytes())
-        f.write(struct.pack("<Q", ntotal * M))
-        rows = 0
-        for b in blocks:
-            b = np.ascontiguousarray(b, dtype=np.uint8)
-            if b.ndim != 2 or b.shape[1] != M:
-                raise ValueError(f"write_pq: block {b.shape} does not match M={M}")
-            f.write(b.tobytes())
-            rows += b.shape[0]
-        if rows != ntotal:
-            raise ValueError(f"write_pq: wrote {rows} rows, header says {ntotal}")
-        f.write(_PQ_TAIL.pack(0, 0, M * 8 + 1))
-    os.replace(tmp, fname)
+    head = _PQ.pack(d, M, 8) + struct.pack("<Q", d * 256) + c.tobytes() + struct.pack("<Q", ntotal * M)
+    _write_index(fname, "write_pq", FOURCC_PQ, d, ntotal, is_trained, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1))
 
 
 def read_pq(fname: str):
@@ -183,9 +165,7 @@ def read_pq(fname: str):
     if size < fixed:
         raise ValueError(f"{fname}: too short for a product-quantiser index header")
     with open(fname, "rb") as f:
-        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
-        if fourcc != FOURCC_PQ:
-            raise ValueError(f"{fname}: fourcc {fourcc!r} is not a product-quantiser index ('IxPq')")
+        d, ntotal, trained, metric = _read_header(f, fname, FOURCC_PQ, "a product-quantiser index")
         pq_d, M, nbits = _PQ.unpack(f.read(_PQ.size))
         if nbits != 8:
             raise ValueError(f"{fname}: ProductQuantizer nbits={nbits} is not served (only 8)")

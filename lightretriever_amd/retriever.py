@@ -202,17 +202,23 @@ class DenseRetrievalFaissSearch:
 
 class FlatIPFaissSearch(DenseRetrievalFaissSearch):
     index_cls = FlatIPIndex          # the shard type every index / load builds
+    index_ext = "flat"               # the default `ext` of load / save: files {prefix}.{ext}.faiss / .tsv
     serves_rpc_shards = True         # _chunked_dense_search may place the shards on the reference's RPC workers (rpc_shards: FlatIPIndex)
 
     def _new_index(self, dim: int, capacity: int):
         return self.index_cls(dim, capacity=capacity)
+
+    def _train(self, idx, corpus_emb):
+        """index(): fit a fresh shard that needs training to the chunk before its rows are added (nothing to fit for a flat shard)."""
 
     def index(self, corpus_emb, corpus_ids):
         """Index already-encoded embeddings (Tensor on any device / ndarray) -- faiss_search.py:490-504."""
         self._create_mapping_ids(corpus_ids)
         self.dim_size = corpus_emb.shape[1]
         rows = [self.mapping.get(c, c) for c in corpus_ids]
-        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=self.index_cls(corpus_emb.shape[1], capacity=len(rows)))
+        idx = self._new_index(corpus_emb.shape[1], len(rows))
+        self._train(idx, corpus_emb)
+        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=idx)
 
     def _index_in_place(self, docs: list, corpus_ids: list, dim: int):
         """Encode a corpus chunk straight into a fresh shard (embeddings never leave HBM)."""
@@ -233,17 +239,17 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         self.faiss_index = FaissIndex(idx, [self.mapping.get(c, c) for c in corpus_ids])
         return enc if isinstance(enc, dict) else {"dense_reps": enc}   # what encode_corpus returned (sparse_reps ride along)
 
-    def load(self, input_dir: str, prefix: str = "my-index", ext: str = "flat"):
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
         """faiss_search.py:478-488: id map + index file -> HBM shard of this rank."""
-        path, passage_ids = self._load(input_dir, prefix, ext)
+        path, passage_ids = self._load(input_dir, prefix, self.index_ext if ext is None else ext)
         idx = self.index_cls.load(path)
         if passage_ids and len(passage_ids) != idx.ntotal:
             raise ValueError(f"{path}: {idx.ntotal} rows but {len(passage_ids)} ids in the map")
         self.dim_size = idx.d
         self.faiss_index = FaissIndex(idx, passage_ids or None)
 
-    def save(self, output_dir: str, prefix: str = "my-index", ext: str = "flat"):
-        super().save(output_dir, prefix, ext)
+    def save(self, output_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().save(output_dir, prefix, self.index_ext if ext is None else ext)
 
     def get_index_name(self):
         return "flat_faiss_index"
@@ -254,6 +260,7 @@ class SQFaissSearch(FlatIPFaissSearch):
     2 B/element resident, exact inner products of the fp32 query with the decoded codes.  index / _index_in_place / load / save behave like
     FlatIPFaissSearch's with that shard.  Other quantizer types and metrics are not served; neither are shards on RPC workers."""
     index_cls = SQFp16Index
+    index_ext = "sq"
     serves_rpc_shards = False
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, similarity_metric=0, quantizer_type: str = "QT_fp16",
@@ -266,12 +273,6 @@ class SQFaissSearch(FlatIPFaissSearch):
         self.similarity_metric = 0
         self.qname = quantizer_type
 
-    def load(self, input_dir: str, prefix: str = "my-index", ext: str = "sq"):
-        super().load(input_dir, prefix, ext)
-
-    def save(self, output_dir: str, prefix: str = "my-index", ext: str = "sq"):
-        super().save(output_dir, prefix, ext)
-
     def get_index_name(self):
         return "sq_faiss_index"
 
@@ -282,6 +283,7 @@ class PQFaissSearch(FlatIPFaissSearch):
     _index_in_place trains on the encoded chunk when its staging slot is committed.  Not served: OPQ (use_rotation), the L2 metric,
     code_size != 8, shards on RPC workers."""
     index_cls = PQIndex
+    index_ext = "pq"
     serves_rpc_shards = False
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, num_of_centroids: int = 96, code_size: int = 8,
@@ -303,20 +305,8 @@ class PQFaissSearch(FlatIPFaissSearch):
             raise ValueError(f"PQFaissSearch: dimension {dim} is not a multiple of num_of_centroids={self.num_of_centroids}")
         return PQIndex(dim, self.num_of_centroids, self.code_size, capacity=capacity)
 
-    def index(self, corpus_emb, corpus_ids):
-        """Train on the chunk, then add it (faiss_search.py:370-383 via FaissTrainIndex.build)."""
-        self._create_mapping_ids(corpus_ids)
-        self.dim_size = corpus_emb.shape[1]
-        rows = [self.mapping.get(c, c) for c in corpus_ids]
-        idx = self._new_index(corpus_emb.shape[1], len(rows))
-        idx.train(corpus_emb)
-        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=idx)
-
-    def load(self, input_dir: str, prefix: str = "my-index", ext: str = "pq"):
-        super().load(input_dir, prefix, ext)
-
-    def save(self, output_dir: str, prefix: str = "my-index", ext: str = "pq"):
-        super().save(output_dir, prefix, ext)
+    def _train(self, idx: PQIndex, corpus_emb):
+        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it (faiss_search.py:370-383 via FaissTrainIndex.build)
 
     def get_index_name(self):
         return "pq_faiss_index"
@@ -340,7 +330,7 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        # faiss_search_map (hybrid_search.py:32-70): "flat" (default) and "sq" (QT_fp16) are served; anything else is served flat
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16) and "pq" (IndexPQ) are served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
         den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
         if faiss_search_map not in ("flat", "sq", "pq"):
