@@ -555,6 +555,43 @@ int lrx_pq_decode_rows(const void* codes, int64_t row0, int64_t n_rows, const fl
 /* The lookup tables alone: lut[n_queries][M][256] fp32 (tests). */
 int lrx_pq_lut(const float* q, int32_t n_queries, const float* centroids, int32_t dim, int32_t M, float* lut, void* stream);
 
+/* (added in ABI 8, additively) BINARY flat index (faiss IndexBinaryFlat(d)) with the reference's float rerank (retriever/faiss_index.py
+ * FaissBinaryIndex), DESIGN §5.4.4.  One bit per dimension: dim / 8 bytes per row.  The contract, which fixes every output:
+ *   bits          bit j of a row or a query = 1 iff x[j] > threshold[j] -- strict, NaN gives 0; threshold: one float, or threshold_vec[dim]
+ *                 when that is not NULL (np.where(x > threshold, 1, 0)).
+ *   bytes         np.packbits order: dimension 8 i + b is bit 7 - b of byte i.  dim % 8 == 0, dim <= 16384.
+ *   h(q, r)       = popcount(bits(q) XOR bits(r)), an integer in [0, dim].
+ *   Hamming top-k   ascending h, ties to the lower row; D int32, I int64; positions beyond n_rows hold (2^31 - 1, -1).  (This tie rule is this
+ *                 library's: faiss's depends on which of its kernels runs.)
+ *   rerank        candidates = the Hamming top-min(binary_k, n_rows) under that rule; s(q, r) = (float) sum_j (double) q[j] * (bits(r)[j] ? +1 : -1),
+ *                 fp64 accumulation, one rounding; result = the top-k candidates by s descending, ties to the lower row, (-FLT_MAX, -1) padding.
+ *   limits        1 <= k <= binary_k <= 2048.
+ * THE CODE LAYOUT: the product-quantised index's, with M = dim / 8 bytes per row: G = ceil(dim / 128) 16-byte groups per row; the codes are an
+ *   array of 128-row blocks of 2048 G bytes, each block group major [G][128 rows][16 bytes]: byte i of row r sits at
+ *   (r / 128) 2048 G + (i / 16) 2048 + (r % 128) 16 + i % 16.  Bytes i >= dim / 8 of a row are ZERO (the writers below write them; the scan
+ *   reads whole groups).  Allocated for whole 128-row blocks.
+ * The search: queries packed -> scan 1 (per-query histogram of h, integer atomics) -> cutoff t_q and need_eq = kk - count(h < t_q) -> scan 2
+ *   (rows with h < t_q appended to the query's list, ties h == t_q counted per 1024-row tile) -> prefix sum of the tie counts in row order ->
+ *   scan 3 (the need_eq lowest ties, only over tiles that hold one) -> LDS sort of the <= 2048 (h, row) keys, or the rerank and its sort.
+ *   h is recomputed by every scan, never stored.  No float atomics, no host synchronisation: deterministic.
+ * out_ids: id_base + row, or row_map[row] when row_map != NULL.  Workspace: lrx_binary_workspace_bytes (the same for both searches).
+ * flags: 0, or LRX_BINARY_SELECT_ONLY (tools: stop once the candidates are selected; the outputs are not written and may be NULL). */
+enum { LRX_BINARY_SELECT_ONLY = 1 };
+size_t lrx_binary_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t binary_k);
+int lrx_binary_hamming_search(const void* codes, int64_t n_rows, int32_t dim, const float* q, int32_t n_queries, float threshold,
+                              const float* threshold_vec, int32_t k, int64_t id_base, int32_t* out_dist, int64_t* out_ids, const int64_t* row_map,
+                              void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
+int lrx_binary_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* q, int32_t n_queries, float threshold,
+                         const float* threshold_vec, int32_t k, int32_t binary_k, int64_t id_base, float* out_scores, int64_t* out_ids,
+                         const int64_t* row_map, void* workspace, size_t workspace_bytes, int32_t flags, void* stream);
+/* Binarise n_rows fp32 rows (row stride ldx >= dim) into rows row0 .. of the blocked codes. */
+int lrx_binary_pack_rows(const float* x, int64_t n_rows, int64_t ldx, int32_t dim, float threshold, const float* threshold_vec, void* codes,
+                         int64_t row0, void* stream);
+/* Rows that are already packed (uint8, dim / 8 bytes each, row stride ld_bytes) into rows row0 .. of the blocked codes. */
+int lrx_binary_store_rows(const void* bytes, int64_t n_rows, int64_t ld_bytes, int32_t dim, void* codes, int64_t row0, void* stream);
+/* Rows [row0, row0 + n_rows) as row-major packed bytes: out_bytes[i * ldo + b] (ldo >= dim / 8). */
+int lrx_binary_decode_rows(const void* codes, int64_t row0, int64_t n_rows, int32_t dim, void* out_bytes, int64_t ldo, void* stream);
+
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);
 int lrx_flat_ip_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries,

@@ -11,6 +11,7 @@ ABI_VERSION = 8   # LRX_ABI_VERSION of include/lrx.h
 SEARCH_FILTER_AUTO, SEARCH_FILTER_MATRIX, SEARCH_FILTER_SCORE_FREE, SEARCH_FILTER_SCORE_FREE_NO_GEMM = 0, 1, 2, 3
 SEARCH_FUSED_ALWAYS, SEARCH_FUSED_NEVER = 4, 8
 SEARCH_REFINE_ROWS_ALWAYS, SEARCH_REFINE_ROWS_NEVER = 16, 32   # exact rescoring grouped by row / per query (include/lrx.h)       # OR-ed on: the fused filter launch wherever eligible / never (default: a measured rule)
+BINARY_SELECT_ONLY = 1   # lrx_binary_*_search flags (LRX_BINARY_SELECT_ONLY): tools
 PROF_CLASS_NAMES = ["gemm_store", "gemm_resid", "gemm_swiglu", "attention", "rmsnorm", "rope", "other", "gemm_maxagg"]
 
 
@@ -80,6 +81,12 @@ SIGNATURES = {
     "lrx_pq_encode": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _P, _I64, _P]),
     "lrx_pq_decode_rows": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _P, _I64, _P]),
     "lrx_pq_lut": (_I32, [_P, _I32, _P, _I32, _I32, _P, _P]),
+    "lrx_binary_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "lrx_binary_hamming_search": (_I32, [_P, _I64, _I32, _P, _I32, _F, _P, _I32, _I64, _P, _P, _P, _P, _SZ, _I32, _P]),
+    "lrx_binary_ip_search": (_I32, [_P, _I64, _I32, _P, _I32, _F, _P, _I32, _I32, _I64, _P, _P, _P, _P, _SZ, _I32, _P]),
+    "lrx_binary_pack_rows": (_I32, [_P, _I64, _I64, _I32, _F, _P, _P, _I64, _P]),
+    "lrx_binary_store_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P]),
+    "lrx_binary_decode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P]),
     "lrx_shard_commit_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P, _P]),
     "lrx_pool_norm_shard": (_I32, [_P, _P, _P, _I32, _I32, _F, _P, _I64, _I32, _I32, _P, _I64, _P, _I32, _P]),
     "lrx_gemm_bf16_nt_resid32": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),

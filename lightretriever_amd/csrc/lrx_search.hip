@@ -5,6 +5,7 @@
 //     lrx_search_bounded.h  C. error bound, threshold, fused   lrx_search_refine.h   C. band refine, row-grouped rescoring, part merge
 //     lrx_search_range.h    F. range search: threshold from a given radius, exact rescoring, row-ordered output (host driver: lrx_flat_ip_range_search)
 //     lrx_search_pq.h       G. product-quantised index: encode, lookup tables, ADC scan -> k_topk_select / merge, decode (with its host driver)
+//     lrx_search_binary.h   H. binary flat index: pack, Hamming scan, selection by counting, fp64 rerank, decode (with its host driver)
 // Map of the unit:
 //
 //  A. Score kernels (what a search streams the shard through)
@@ -1208,3 +1209,4 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
 }
 
 #include "lrx_search_pq.h"       // product-quantised index: encode, lookup tables, ADC scan (-> k_topk_select, merge_launch), decode
+#include "lrx_search_binary.h"   // binary flat index: pack, Hamming scan, selection by counting, rerank, decode

@@ -306,6 +306,45 @@ std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Ten
   return {o.d, o.i};
 }
 
+// Binary flat index (lrx_binary_ip_search / lrx_binary_hamming_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of
+// n_rows rows of q.size(1) bits; threshold: None (0), one element, or [D].  rerank: (D fp32, I) of the float rerank of the Hamming top-binary_k;
+// else (D int32, I) of the Hamming top-k.
+std::tuple<at::Tensor, at::Tensor> binary_topk(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, int64_t k, int64_t binary_k, bool rerank,
+                                               const c10::optional<at::Tensor>& threshold, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  const int64_t dim = q.size(1);
+  TORCH_CHECK(q.is_contiguous() && dim > 0 && dim % 8 == 0 && n_rows >= 0, "binary_topk: q [Q,D] contiguous with D % 8 == 0, n_rows >= 0");
+  void* cb = tiled_rows(codes, at::kByte, n_rows, (dim + 127) / 128 * 16, "binary_topk: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "binary_topk: row_map int64 [>= n_rows] contiguous");
+  float thr = 0.f;
+  const float* thr_vec = nullptr;
+  at::Tensor tv;
+  if (threshold.has_value()) {
+    TORCH_CHECK(threshold->numel() == 1 || threshold->numel() == dim, "binary_topk: threshold must hold 1 or D values");
+    if (threshold->numel() == 1) {
+      thr = threshold->item<float>();
+    } else {
+      tv = threshold->to(q.options()).contiguous();
+      thr_vec = tv.data_ptr<float>();
+    }
+  }
+  TopK o = topk_out(q, k);
+  const size_t wsb = lrx_binary_workspace_bytes(n_rows, (int32_t)dim, (int32_t)q.size(0), (int32_t)binary_k);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  if (rerank) {
+    lrx_check(lrx_binary_ip_search(cb, n_rows, (int32_t)dim, q.data_ptr<float>(), (int32_t)q.size(0), thr, thr_vec, (int32_t)k, (int32_t)binary_k, id_base,
+                                   o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, 0, cur_stream()),
+              "binary_topk");
+    return {o.d, o.i};
+  }
+  at::Tensor dist = at::empty({q.size(0), k}, q.options().dtype(at::kInt));
+  lrx_check(lrx_binary_hamming_search(cb, n_rows, (int32_t)dim, q.data_ptr<float>(), (int32_t)q.size(0), thr, thr_vec, (int32_t)k, id_base,
+                                      dist.data_ptr<int32_t>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, 0, cur_stream()),
+            "binary_topk");
+  return {dist, o.i};
+}
+
 // Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
 // with the exact capacity, when the first guess of 1024 hits per query was short).
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
@@ -356,6 +395,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HIP tensors under the CUDA key)
@@ -374,4 +414,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("flat_ip_range_search", &flat_ip_range_search);
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("pq_ip_topk", &pq_ip_topk);
+  m.impl("binary_topk", &binary_topk);
 }

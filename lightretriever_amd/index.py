@@ -1,5 +1,5 @@
 """HBM-resident inner-product index shards: the faiss.IndexFlatIP surface the reference uses (retriever/faiss_index.py:20-73: add / search /
-reset / ntotal), backed by lrx_flat_ip_search, and its fp16 scalar-quantised and product-quantised siblings."""
+reset / ntotal), backed by lrx_flat_ip_search, its fp16 scalar-quantised and product-quantised siblings, and the binary flat index (IndexBinaryFlat)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -790,6 +790,163 @@ class PQIndex:
         _lib.check(self.lib.lrx_pq_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(q), Q, k,
                                              int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
                                              _lib.current_stream()))
+        return D, I
+
+
+class BinaryFlatIndex:
+    """Binary flat shard: the faiss IndexBinaryFlat(d) surface (add / search / reset / ntotal / reconstruct_n / save / load) plus the reference's
+    float rerank (FaissBinaryIndex.search), backed by lrx_binary_ip_search / lrx_binary_hamming_search.  Resident: d / 8 bytes per row (d = the
+    number of bits, d % 8 == 0), in the blocked layout of include/lrx.h (rows padded to whole 16-byte groups).  Bit j of a row is
+    x[j] > threshold[j] (strict, NaN -> 0), bytes in np.packbits order.  search(): the Hamming top-binary_k (ascending distance, ties to the lower
+    row) rescored with the float query against the +-1 rows -- (float) of the fp64 sum -- and the top-k of those by score descending, ties to the
+    lower row, (-FLT_MAX, -1) padding; rerank=False returns the int32 Hamming lists, padded with (2^31 - 1, -1).
+    Rows enter through add() -- floating rows, binarised with the index's threshold, or uint8 [n, d / 8] rows that are already packed -- or
+    through append_slot(n) / commit(n): the slot is a transient fp32 staging view, commit() binarises it and releases it.  Search: one library
+    call, workspace kept by the index.  NOT thread-safe."""
+
+    MAX_K = 2048
+
+    def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0, threshold=0):
+        if d <= 0 or d % 8 != 0:
+            raise ValueError(f"BinaryFlatIndex: d={d} (bits) must be a positive multiple of 8")
+        if d > 16384:
+            raise NotImplementedError(f"BinaryFlatIndex: d={d} > 16384 bits is not served")
+        _lib.require_gpu()
+        self.lib = _lib.lib()
+        self.d = d
+        self.code_size = d // 8
+        self.Mp = -(-d // 128) * 16            # bytes per row in the blocked layout
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.id_base = id_base
+        self.ntotal = 0
+        self.threshold = threshold
+        self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._stage = None
+        self._ws = None
+        self.reserve(capacity)
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        return self._codes.numel() // self.Mp
+
+    def reserve(self, n_rows: int):
+        self._codes = _grow_blocks(self._codes, n_rows, self.Mp, self.ntotal, zero=True)
+
+    def _threshold_args(self, threshold):
+        """threshold (a number, or d values) -> (the scalar, the [d] fp32 device vector or None)."""
+        if isinstance(threshold, (int, float)):
+            return float(threshold), None
+        t = torch.as_tensor(threshold)
+        if t.numel() == 1:
+            return float(t.reshape(()).item()), None
+        if t.numel() != self.d:
+            raise ValueError(f"threshold must be a scalar or hold d={self.d} values, got {tuple(t.shape)}")
+        return 0.0, t.reshape(self.d).to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _pack_into(self, x: torch.Tensor, row0: int):
+        thr, tv = self._threshold_args(self.threshold)
+        _lib.check(self.lib.lrx_binary_pack_rows(_lib.ptr(x), x.shape[0], x.stride(0), self.d, thr, _lib.ptr(tv), _lib.ptr(self._codes), row0,
+                                                 _lib.current_stream()))
+
+    def add(self, x):
+        """faiss add: floating rows [n, d] (binarised with the index's threshold) or uint8 [n, d / 8] rows already packed (np.packbits order)."""
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        packed = x.dtype == torch.uint8
+        x = _as_rows(x, self.code_size if packed else self.d, "add: ")
+        n = x.shape[0]
+        if self.ntotal + n > self.capacity:
+            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        if n:
+            if packed:
+                x = x.to(self.device).contiguous()
+                _lib.check(self.lib.lrx_binary_store_rows(_lib.ptr(x), n, x.stride(0), self.d, _lib.ptr(self._codes), self.ntotal, _lib.current_stream()))
+            else:
+                x = x.to(device=self.device, dtype=torch.float32)
+                self._pack_into(x if x.stride(1) == 1 else x.contiguous(), self.ntotal)
+        self.ntotal += n
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
+        if self._stage is None or self._stage.shape[0] < n_rows:
+            self._stage = None
+            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+        return self._stage[:n_rows]
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            if self._stage is None or n_rows > self._stage.shape[0]:
+                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
+            self.add(self._stage[:n_rows])
+        self._stage = None                             # staging released (stream-ordered by the allocator)
+
+    def reset(self):
+        self.ntotal = 0
+        self._stage = None
+
+    def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
+        """Rows [i0, i0 + n) as packed bytes: uint8 device tensor [n, d / 8] (faiss reconstruct of a binary index)."""
+        _check_range(i0, n, self.ntotal)
+        out = torch.empty(n, self.code_size, dtype=torch.uint8, device=self.device)
+        if n:
+            _lib.check(self.lib.lrx_binary_decode_rows(_lib.ptr(self._codes), i0, n, self.d, _lib.ptr(out), self.code_size, _lib.current_stream()))
+        return out
+
+    def codes(self) -> torch.Tensor:
+        """The rows as a row-major uint8 [ntotal, d / 8] tensor (a copy: the stored layout is blocked)."""
+        return self.reconstruct_n(0, self.ntotal)
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.codes()
+
+    # -- persistence (faiss.write_index_binary / read_index_binary of an IndexBinaryFlat, see index_io.py) ---------------------
+    def save(self, fname: str, chunk_rows: int = 1 << 20):
+        from .index_io import write_binary_flat
+        write_binary_flat(fname, (self.reconstruct_n(s, min(chunk_rows, self.ntotal - s)).cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
+                          self.d, self.ntotal)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 1 << 20) -> "BinaryFlatIndex":
+        from .index_io import read_binary_flat
+        mm = read_binary_flat(fname)
+        idx = cls(mm.shape[1] * 8, capacity=mm.shape[0], device=device, id_base=id_base)
+        for s in range(0, mm.shape[0], chunk_rows):
+            idx.add(torch.from_numpy(np.array(mm[s:s + chunk_rows], copy=True)))
+        return idx
+
+    # -- search --------------------------------------------------------------------------------------------------
+    def search(self, q, k: int, binary_k: int = 1000, rerank: bool = True, score_function: str = "dot", threshold=None,
+               row_map: Optional[torch.Tensor] = None, flags: int = 0):
+        """-> (D, I) device tensors [Q, k].  rerank=True: D fp32 scores of the float query against the +-1 rows over the Hamming top-binary_k
+        candidates, descending, ties to the lower row, (-FLT_MAX, -1) padding.  rerank=False: D int32 Hamming distances, ascending, ties to the
+        lower row, (2^31 - 1, -1) padding (binary_k is not used).  threshold: binarises the queries (default: the index's).  I = id_base + row, or
+        row_map[row] (int64 CUDA tensor of >= ntotal entries) when given.  1 <= k <= binary_k <= 2048."""
+        if score_function != "dot":
+            raise NotImplementedError(f"BinaryFlatIndex.search: score_function {score_function!r} is not served (only 'dot')")
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        if rerank and not 1 <= k <= binary_k <= self.MAX_K:
+            raise ValueError(f"search: need 1 <= k <= binary_k <= {self.MAX_K}, got k={k}, binary_k={binary_k}")
+        if not rerank and not 1 <= k <= self.MAX_K:
+            raise ValueError(f"search: k={k} out of range (1..{self.MAX_K})")
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        thr, tv = self._threshold_args(self.threshold if threshold is None else threshold)
+        Q = q.shape[0]
+        D = torch.empty(Q, k, dtype=torch.float32 if rerank else torch.int32, device=self.device)
+        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
+        if Q == 0:
+            return D, I
+        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_binary_workspace_bytes(self.ntotal, self.d, Q, binary_k)), self.device)
+        if rerank:
+            _lib.check(self.lib.lrx_binary_ip_search(_lib.ptr(self._codes), self.ntotal, self.d, _lib.ptr(q), Q, thr, _lib.ptr(tv), k, binary_k,
+                                                     int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), flags,
+                                                     _lib.current_stream()))
+        else:
+            _lib.check(self.lib.lrx_binary_hamming_search(_lib.ptr(self._codes), self.ntotal, self.d, _lib.ptr(q), Q, thr, _lib.ptr(tv), k,
+                                                          int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), flags,
+                                                          _lib.current_stream()))
         return D, I
 
 

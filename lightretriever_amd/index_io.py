@@ -41,7 +41,22 @@ source:
     u64   ntotal * M,  u8 codes[ntotal][M]    row-major
     i32   search_type = 0 (ST_PQ),  u8 encode_signs = 0,  i32 polysemous_ht = M * nbits + 1
 
-It too is **unverified against a Faiss build**.  Files with nbits != 8 or any other inconsistency are rejected."""
+It too is **unverified against a Faiss build**.  Files with nbits != 8 or any other inconsistency are rejected.
+
+A binary flat shard (BinaryFlatIndex, faiss IndexBinaryFlat(d)) is written as Faiss's `write_index_binary` of an IndexBinaryFlat, same source
+(write_index_binary_header: no dummies, and the code size in the header):
+
+    u32   fourcc 'IBxF'
+    i32   d                                   (bits)
+    i32   code_size = d / 8
+    i64   ntotal
+    u8    is_trained = 1
+    i32   metric_type = 1                     (METRIC_L2: what IndexBinary's constructor sets; the search is by Hamming distance)
+    u64   n_bytes = ntotal * code_size        (WRITEVECTOR of xb)
+    u8    xb[ntotal][code_size]               row-major, np.packbits bit order
+
+Like the others it is **unverified against a Faiss build**.  Files with code_size != d / 8, a size word or a length that does not match are
+rejected."""
 from __future__ import annotations
 
 import csv
@@ -185,6 +200,50 @@ def read_pq(fname: str):
         raise ValueError(f"{fname}: IndexPQ search_type {search_type} is not served (only ST_PQ = 0)")
     codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=off, shape=(ntotal, M)) if ntotal else np.zeros((0, M), np.uint8)
     return cent, codes, bool(trained)
+
+
+FOURCC_BINARY_FLAT = b"IBxF"
+_BIN_HEADER = struct.Struct("<4siiqBi")  # fourcc, d (bits), code_size, ntotal, is_trained, metric_type  (25 bytes, packed)
+BIN_HEADER_BYTES = _BIN_HEADER.size + 8  # + u64 vector size
+
+
+def write_binary_flat(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
+    """blocks: uint8 [n_i, d / 8] arrays of packed rows in row order, sum n_i == ntotal.  (A sibling of _write_index: the binary header has no
+    dummies and carries code_size.)"""
+    if d <= 0 or d % 8:
+        raise ValueError(f"write_binary_flat: d={d} (bits) must be a positive multiple of 8")
+    cs = d // 8
+    tmp = fname + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(_BIN_HEADER.pack(FOURCC_BINARY_FLAT, d, cs, ntotal, 1, 1))
+        f.write(struct.pack("<Q", ntotal * cs))
+        rows = 0
+        for b in blocks:
+            b = np.ascontiguousarray(b, dtype=np.uint8)
+            if b.ndim != 2 or b.shape[1] != cs:
+                raise ValueError(f"write_binary_flat: block {b.shape} does not match code_size={cs}")
+            f.write(b.tobytes())
+            rows += b.shape[0]
+        if rows != ntotal:
+            raise ValueError(f"write_binary_flat: wrote {rows} rows, header says {ntotal}")
+    os.replace(tmp, fname)
+
+
+def read_binary_flat(fname: str) -> np.ndarray:
+    """-> read-only memmap uint8 [ntotal, d / 8] of the packed rows (no copy)."""
+    size = os.path.getsize(fname)
+    if size < BIN_HEADER_BYTES:
+        raise ValueError(f"{fname}: too short for a binary flat index header")
+    with open(fname, "rb") as f:
+        got, d, cs, ntotal, _, _ = _BIN_HEADER.unpack(f.read(_BIN_HEADER.size))
+        (n_bytes,) = struct.unpack("<Q", f.read(8))
+    if got != FOURCC_BINARY_FLAT:
+        raise ValueError(f"{fname}: fourcc {got!r} is not a binary flat index ({FOURCC_BINARY_FLAT.decode()!r})")
+    if d <= 0 or d % 8 or cs * 8 != d or ntotal < 0 or n_bytes != ntotal * cs or size != BIN_HEADER_BYTES + n_bytes:
+        raise ValueError(f"{fname}: inconsistent binary flat index (d={d}, code_size={cs}, ntotal={ntotal}, code bytes={n_bytes}, file bytes={size})")
+    if ntotal == 0:
+        return np.zeros((0, cs), np.uint8)
+    return np.memmap(fname, dtype=np.uint8, mode="r", offset=BIN_HEADER_BYTES, shape=(ntotal, cs))
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

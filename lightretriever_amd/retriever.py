@@ -4,6 +4,8 @@
     FlatIPFaissSearch   <- retriever/faiss_search.py:46-293, :477-510   (BEIR-style dense searcher)
     SQFaissSearch       <- retriever/faiss_search.py:567-611             (QT_fp16 inner product only, over SQFp16Index)
     PQFaissSearch       <- retriever/faiss_search.py:326-383             (IndexPQ, 8-bit codes, inner product only, over PQIndex)
+    FaissBinaryIndex    <- retriever/faiss_index.py:116-192              (Hamming candidates + float rerank over BinaryFlatIndex)
+    BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; sparse + fusion out of scope)
 
 Design differences, results preserved: corpus embeddings are encoded straight into the index shard (no CPU round trip, no
@@ -25,7 +27,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .index import FlatIPIndex, PQIndex, SQFp16Index, merge_topk
+from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQFp16Index, merge_topk
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -72,6 +74,35 @@ class FaissIndex:
 
     def reset(self):
         self.index.reset()
+
+
+class FaissBinaryIndex(FaissIndex):
+    """`FaissBinaryIndex(index, passage_ids)` of the reference over a BinaryFlatIndex: search() binarises the queries with `threshold`, takes the
+    Hamming top-`binary_k` and -- unless rerank=False, which returns the int32 Hamming lists -- rescores them with the float queries against
+    the +-1 rows (BinaryFlatIndex.search); ids go through `_passage_ids`, QPS is logged.  The packed rows live in the index only (the
+    reference keeps a second host copy for the rerank)."""
+
+    def search(self, query_embeddings, k: int, binary_k: int = 1000, rerank: bool = True, score_function: str = "dot", threshold=0, **kwargs):
+        n = query_embeddings.shape[0]
+        t0 = time.time()
+        scores, ids = self.index.search(query_embeddings, k, binary_k=binary_k, rerank=rerank, score_function=score_function, threshold=threshold)
+        if self._passage_ids is not None:
+            ids = torch.where(ids >= 0, self._passage_ids[ids.clamp(min=0)], ids)
+        torch.cuda.synchronize(self.index.device)
+        dt = max(time.time() - t0, 1e-9)
+        logger.info("Num of queries: %d\tSearch time (s): %.3f\tQPS: %.3f", n, dt, n / dt)
+        return scores, ids
+
+    def range_search(self, query_embeddings, radius: float):
+        raise NotImplementedError("FaissBinaryIndex.range_search is not served")
+
+    @classmethod
+    def build(cls, passage_ids: list, passage_embeddings, index: Optional[BinaryFlatIndex] = None, buffer_size: int = 50000):
+        """passage_embeddings: floating [n, d] rows (binarised by the index) or uint8 [n, d / 8] packed rows, as the reference hands faiss."""
+        if index is None:
+            packed = str(passage_embeddings.dtype).endswith("uint8")
+            index = BinaryFlatIndex(passage_embeddings.shape[1] * (8 if packed else 1), capacity=len(passage_ids))
+        return super().build(passage_ids, passage_embeddings, index=index, buffer_size=buffer_size)
 
 
 def _ids_and_list(queries):
@@ -204,6 +235,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
     index_cls = FlatIPIndex          # the shard type every index / load builds
     index_ext = "flat"               # the default `ext` of load / save: files {prefix}.{ext}.faiss / .tsv
     serves_rpc_shards = True         # _chunked_dense_search may place the shards on the reference's RPC workers (rpc_shards: FlatIPIndex)
+    faiss_index_cls = FaissIndex     # the (index, passage_ids) wrapper that search() goes through
 
     def _new_index(self, dim: int, capacity: int):
         return self.index_cls(dim, capacity=capacity)
@@ -218,7 +250,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         rows = [self.mapping.get(c, c) for c in corpus_ids]
         idx = self._new_index(corpus_emb.shape[1], len(rows))
         self._train(idx, corpus_emb)
-        self.faiss_index = FaissIndex.build(rows, corpus_emb, index=idx)
+        self.faiss_index = self.faiss_index_cls.build(rows, corpus_emb, index=idx)
 
     def _index_in_place(self, docs: list, corpus_ids: list, dim: int):
         """Encode a corpus chunk straight into a fresh shard (embeddings never leave HBM)."""
@@ -226,7 +258,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         self.dim_size = dim
         idx = self._new_index(dim, len(docs))
         if not docs:                                  # a rank without a batch in this chunk: empty shard, searches return padding
-            self.faiss_index = FaissIndex(idx, None)
+            self.faiss_index = self.faiss_index_cls(idx, None)
             return None
         slot = idx.append_slot(len(docs))
         enc = emb = self.model.encode_corpus(docs, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
@@ -236,7 +268,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         if emb.data_ptr() != slot.data_ptr():       # a model that does not support `out=`: one device copy
             slot.copy_(emb.to(slot.device))
         idx.commit(len(docs))
-        self.faiss_index = FaissIndex(idx, [self.mapping.get(c, c) for c in corpus_ids])
+        self.faiss_index = self.faiss_index_cls(idx, [self.mapping.get(c, c) for c in corpus_ids])
         return enc if isinstance(enc, dict) else {"dense_reps": enc}   # what encode_corpus returned (sparse_reps ride along)
 
     def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
@@ -246,7 +278,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         if passage_ids and len(passage_ids) != idx.ntotal:
             raise ValueError(f"{path}: {idx.ntotal} rows but {len(passage_ids)} ids in the map")
         self.dim_size = idx.d
-        self.faiss_index = FaissIndex(idx, passage_ids or None)
+        self.faiss_index = self.faiss_index_cls(idx, passage_ids or None)
 
     def save(self, output_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
         super().save(output_dir, prefix, self.index_ext if ext is None else ext)
@@ -312,6 +344,49 @@ class PQFaissSearch(FlatIPFaissSearch):
         return "pq_faiss_index"
 
 
+class BinaryFaissSearch(FlatIPFaissSearch):
+    """faiss_search.py:296-323: IndexBinaryFlat(d) over the binarised embeddings (bit j = x[j] > threshold[j]), searched through FaissBinaryIndex --
+    the Hamming top-`binary_k` rescored with the float queries against the +-1 rows.  d / 8 bytes per row resident.  index / _index_in_place /
+    load / save behave like FlatIPFaissSearch's with a BinaryFlatIndex shard.  Every retrieval of the chunk loop is the rerank search, so per-chunk
+    scores are fp32 and merge like any other searcher's.  Not served: score_function "cos_sim" (a per-query rescale of the same ranking), shards
+    on RPC workers."""
+    index_cls = BinaryFlatIndex
+    index_ext = "bin"
+    serves_rpc_shards = False
+    faiss_index_cls = FaissBinaryIndex
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, binary_k: int = 1000, threshold=0,
+                 score_function: str = "dot", **kwargs):
+        if score_function != "dot":
+            raise NotImplementedError(f"BinaryFaissSearch: score_function {score_function!r} is not served (only 'dot')")
+        if not 1 <= int(binary_k) <= BinaryFlatIndex.MAX_K:
+            raise ValueError(f"BinaryFaissSearch: binary_k={binary_k} out of range (1..{BinaryFlatIndex.MAX_K})")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.binary_k = int(binary_k)
+        self.threshold = threshold
+        self.score_function = score_function
+
+    def _new_index(self, dim: int, capacity: int) -> BinaryFlatIndex:
+        return BinaryFlatIndex(dim, capacity=capacity, threshold=self.threshold)
+
+    def _retrieve_device(self, query_emb, top_k: int):
+        if top_k > self.binary_k:
+            raise ValueError(f"BinaryFaissSearch: top_k={top_k} > binary_k={self.binary_k} (the rerank sees binary_k candidates; raise binary_k, at most "
+                             f"{BinaryFlatIndex.MAX_K})")
+        return self.faiss_index.search(_as_device(query_emb, self.faiss_index.index.device), top_k, binary_k=self.binary_k, rerank=True,
+                                       score_function=self.score_function, threshold=self.threshold)
+
+    def search(self, corpus, queries, top_k: int = 1000, score_function: str = None, **kwargs) -> dict:
+        if top_k > self.binary_k:
+            raise ValueError(f"BinaryFaissSearch: top_k={top_k} > binary_k={self.binary_k}")
+        if score_function not in (None, "dot"):
+            raise NotImplementedError(f"BinaryFaissSearch: score_function {score_function!r} is not served (only 'dot')")
+        return super().search(corpus, queries, top_k=top_k, score_function=score_function, **kwargs)
+
+    def get_index_name(self):
+        return "binary_faiss_index"
+
+
 class HybridSearch:
     """Dense half of the reference's HybridSearch: routes `dense_reps` -> results["den"], `emb_reps` -> results["emb"]
     (hybrid_search.py:121-180); `search()` returns the last enabled type unless return_all_results."""
@@ -330,14 +405,17 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16) and "pq" (IndexPQ) are served; anything else is served flat
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16), "pq" (IndexPQ) and "binary" (IndexBinaryFlat + rerank) are
+        # served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
-        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq"):
+        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
         den_kwargs = {}
         if faiss_search_map == "pq":                  # (the reference passes its **kwargs through to the searcher)
             den_kwargs = {a: kwargs[a] for a in ("num_of_centroids", "code_size", "use_rotation", "similarity_metric") if a in kwargs}
+        if faiss_search_map == "binary":
+            den_kwargs = {a: kwargs[a] for a in ("binary_k", "threshold") if a in kwargs}
         self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
         self.return_all_results = return_all_results
         self.mteb_model_meta = None
