@@ -592,6 +592,48 @@ int lrx_binary_store_rows(const void* bytes, int64_t n_rows, int64_t ld_bytes, i
 /* Rows [row0, row0 + n_rows) as row-major packed bytes: out_bytes[i * ldo + b] (ldo >= dim / 8). */
 int lrx_binary_decode_rows(const void* codes, int64_t row0, int64_t n_rows, int32_t dim, void* out_bytes, int64_t ldo, void* stream);
 
+/* (added in ABI 8, additively) 8-BIT SCALAR-QUANTISED inner-product index (faiss IndexScalarQuantizer(d, QT_8bit | QT_8bit_uniform,
+ * METRIC_INNER_PRODUCT), range statistic RS_minmax with argument 0), DESIGN §5.4.5.  One byte per element, dim % 64 == 0, dim <= 65536.
+ * qtype is faiss's QuantizerType: 0 = QT_8bit (a range per dimension), 2 = QT_8bit_uniform (one range for all).  All arithmetic below is fp32
+ * with separate operations (no contraction) and IEEE division.  The contract, which fixes (D, I) given `trained` and the codes:
+ *   train         vmin[i] = min_r x[r][i], vdiff[i] = max_r x[r][i] - vmin[i]; uniform: one vmin, vdiff over all elements.  NaN training values
+ *                 are ignored (fminf / fmaxf semantics), -0 counts as +0; a range with no value that is not NaN gets vmin = vdiff = 0 (SQ8Index.train:
+ *                 lrx_sq8_train_minmax leaves +inf / -inf there); the result does not depend on the order of the rows.
+ *                 trained = vmin ++ vdiff: 2 dim floats (QT_8bit), 2 floats (QT_8bit_uniform).
+ *   encode        t = vdiff[i] != 0 ? (x[i] - vmin[i]) / vdiff[i] : 0;  t < 0 -> 0, t > 1 -> 1, NaN -> 0;  code[i] = (uint8)(int)(255.f * t)
+ *                 (truncation; rows outside the trained range clamp, as in faiss).
+ *   decode        y[i] = vmin[i] + (((float)code[i] + 0.5f) / 255.f) * vdiff[i].
+ *   s(q, r)       = (float) sum_i (double) q[i] * (double) y_r[i]: fp64 accumulation, one rounding.
+ *   top-k         the flat index's rules: exact under s, score descending, ties to the lower row, (-FLT_MAX, -1) padding when k > n_rows,
+ *                 1 <= k <= 2048.
+ * faiss's own accumulation (fp32 SIMD, order depends on the ISA) is not reproduced.
+ * THE CODE LAYOUT: an array of 128-row blocks of 128 dim bytes; a block is [dim / 64 column slices][8 groups of 16 rows] tiles of 1 KiB, each tile
+ *   [4 pieces of 16 columns][16 rows][16 bytes] -- the i8 MFMA operand of one wave, lane 16 piece + row holding 16 consecutive codes of its
+ *   row: one coalesced 16-byte-per-lane request.  Code i of row r sits at byte
+ *     (r / 128) 128 dim + (i / 64) 8192 + ((r / 16) % 8) 1024 + ((i / 16) % 4) 256 + (r % 16) 16 + i % 16.
+ *   Allocated for whole 128-row blocks (the scan reads whole blocks; what lies beyond n_rows is never reported).
+ * lrx_sq8_ip_search, per chunk of lrx_sq8_ip_chunk_queries (<= 128) queries and row chunk of up to 4 Mi rows: query preparation (w = q vdiff / 255
+ *   as two int8 digit planes, the bias, a rigorous per-query bound eps(q) on |filter score - s|, for finite inputs
+ *   whose scores are normal fp32 numbers or zero) -> one scan of the codes on the i8 MFMA (exact i32
+ *   sums; [Q, rows] fp32 filter scores + 128-row block maxima) -> per query: top-k of the filter scores, every row within 2 eps(q) of the k-th
+ *   rescored from the codes with the contract's arithmetic, best k.  A band of more than 4096 rows is walked in windows (slow, exact; counted
+ *   by lrx_search_fallback_count).  Row chunks are merged with lrx_merge_topk's kernel.  No decoded copy of the rows exists in memory.  No host
+ *   synchronisation.  out_ids: id_base + row, or row_map[row] when row_map != NULL.  Workspace: lrx_sq8_ip_workspace_bytes.  flags: 0.      */
+size_t lrx_sq8_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k);
+int32_t lrx_sq8_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k);
+int lrx_sq8_ip_search(const void* codes, int64_t n_rows, const float* trained, int32_t dim, int32_t qtype, const float* q, int32_t n_queries,
+                      int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
+                      size_t workspace_bytes, int32_t flags, void* stream);
+/* Column minima and maxima of n_rows fp32 rows (row stride ldx >= dim) folded into minmax[2][dim] (device; the caller initialises row 0 to +inf
+ * and row 1 to -inf): callable repeatedly, so training walks a large input in pieces.  Integer atomics only. */
+int lrx_sq8_train_minmax(const float* x, int64_t n_rows, int64_t ldx, int32_t dim, float* minmax, void* stream);
+/* Encode n_rows fp32 rows (row stride ldx >= dim) into rows row0 .. of the tiled codes. */
+int lrx_sq8_encode(const float* x, int64_t n_rows, int64_t ldx, const float* trained, int32_t dim, int32_t qtype, void* codes, int64_t row0,
+                   void* stream);
+/* Rows [row0, row0 + n_rows) decoded to fp32: out[i * ldo + j] (ldo >= dim). */
+int lrx_sq8_decode_rows(const void* codes, int64_t row0, int64_t n_rows, const float* trained, int32_t dim, int32_t qtype, float* out,
+                        int64_t ldo, void* stream);
+
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);
 int lrx_flat_ip_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries,

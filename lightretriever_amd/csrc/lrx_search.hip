@@ -1210,3 +1210,4 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
 
 #include "lrx_search_pq.h"       // product-quantised index: encode, lookup tables, ADC scan (-> k_topk_select, merge_launch), decode
 #include "lrx_search_binary.h"   // binary flat index: pack, Hamming scan, selection by counting, rerank, decode
+#include "lrx_search_sq8.h"      // 8-bit scalar-quantised index: min/max, encode, i8-MFMA filter scan, band rescoring from the codes, decode

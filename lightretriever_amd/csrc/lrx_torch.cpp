@@ -306,6 +306,28 @@ std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Ten
   return {o.d, o.i};
 }
 
+// 8-bit scalar-quantised index (lrx_sq8_ip_search): codes = the 1-D tiled uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
+// trained = vmin ++ vdiff fp32: 2 D floats (QT_8bit) or 2 (QT_8bit_uniform).  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& trained, int64_t k,
+                                               int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(trained, "trained", at::kFloat, 1);
+  const int64_t dim = q.size(1);
+  TORCH_CHECK(q.is_contiguous() && trained.is_contiguous() && dim > 0 && dim % 64 == 0 && (trained.numel() == 2 * dim || trained.numel() == 2) && n_rows >= 0,
+              "sq8_ip_topk: q [Q,D] contiguous with D % 64 == 0, trained [2 D] (QT_8bit) or [2] (QT_8bit_uniform), n_rows >= 0");
+  const int32_t qtype = trained.numel() == 2 ? 2 : 0;
+  void* cb = tiled_rows(codes, at::kByte, n_rows, dim, "sq8_ip_topk: codes must be the 1-D tiled uint8 codes of n_rows rows (whole 128-row blocks)");
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "sq8_ip_topk: row_map int64 [>= n_rows] contiguous");
+  TopK o = topk_out(q, k);
+  const size_t wsb = lrx_sq8_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)q.size(0), (int32_t)k);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  lrx_check(lrx_sq8_ip_search(cb, n_rows, trained.data_ptr<float>(), (int32_t)dim, qtype, q.data_ptr<float>(), (int32_t)q.size(0), (int32_t)k, id_base,
+                              o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, 0, cur_stream()),
+            "sq8_ip_topk");
+  return {o.d, o.i};
+}
+
 // Binary flat index (lrx_binary_ip_search / lrx_binary_hamming_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of
 // n_rows rows of q.size(1) bits; threshold: None (0), one element, or [D].  rerank: (D fp32, I) of the float rerank of the Hamming top-binary_k;
 // else (D int32, I) of the Hamming top-k.
@@ -395,6 +417,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
@@ -414,5 +437,6 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("flat_ip_range_search", &flat_ip_range_search);
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("pq_ip_topk", &pq_ip_topk);
+  m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("binary_topk", &binary_topk);
 }

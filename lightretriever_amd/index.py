@@ -793,6 +793,215 @@ class PQIndex:
         return D, I
 
 
+class SQ8Index:
+    """8-bit scalar-quantised inner-product shard: the faiss IndexScalarQuantizer(d, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT)
+    surface (train / is_trained / add / search / reset / ntotal / reconstruct_n / save / load), backed by lrx_sq8_ip_search.  Resident:
+    ntotal * d bytes of codes (whole 128-row blocks, the tiled layout of include/lrx.h) + `trained` (vmin ++ vdiff: 8 d bytes for QT_8bit,
+    8 for QT_8bit_uniform).  Training is a per-dimension (or global) min / max: no RNG, so codes and files can equal a faiss-written index
+    byte for byte.  A score is the (float) of the fp64 sum of q_i * y_i over the decoded row y; top-k is exact under that score with the
+    flat index's tie and padding rules: the i8-MFMA scan is a filter with a rigorous per-query bound, the rows inside the
+    band are rescored from the codes.  d % 64 == 0.
+    train() may be called on several pieces (train(x, more=True) folds a further piece into the range of the earlier ones).  Rows enter
+    through add() or through append_slot(n) / commit(n): the slot is a transient fp32 staging view; commit() trains the index on the
+    staged rows if it is untrained, encodes them and releases the staging.  Search: one library call (it walks the queries in chunks of
+    <= 128), workspace kept by the index; under a HIP-graph capture the workspace must already exist.  NOT thread-safe."""
+
+    QTYPES = {"QT_8bit": 0, "QT_8bit_uniform": 2}     # faiss ScalarQuantizer::QuantizerType
+
+    def __init__(self, d: int, qtype: str = "QT_8bit", capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        if qtype not in self.QTYPES:
+            raise NotImplementedError(f"SQ8Index: qtype={qtype!r} is not served (only {sorted(self.QTYPES)})")
+        if d <= 0 or d % 64 != 0:
+            raise ValueError(f"SQ8Index: d={d} must be a multiple of 64")
+        _lib.require_gpu()
+        self.lib = _lib.lib()
+        self.d, self.qtype, self._qt = d, qtype, self.QTYPES[qtype]
+        self.uniform = self._qt == 2
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.id_base = id_base
+        self.ntotal = 0
+        self.is_trained = False
+        self.trained = torch.zeros(2 if self.uniform else 2 * d, dtype=torch.float32, device=self.device)
+        self._minmax = None                            # [2, d] running column min / max of the training pieces
+        self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._stage = None
+        self._ws = None
+        self.reserve(capacity)
+
+    # -- storage -------------------------------------------------------------------------------------------------
+    @property
+    def capacity(self) -> int:
+        return self._codes.numel() // self.d
+
+    def reserve(self, n_rows: int):
+        self._codes = _grow_blocks(self._codes, n_rows, self.d, self.ntotal, zero=True)
+
+    def _rows(self, x) -> torch.Tensor:
+        x = _as_rows(x, self.d).to(device=self.device, dtype=torch.float32)
+        return x.contiguous() if x.stride(1) != 1 else x
+
+    def blocked_to_rows(self, blocked: torch.Tensor, n: int) -> torch.Tensor:
+        """Tiled codes (include/lrx.h) -> row-major uint8 [n, d]."""
+        nb = -(-n // 128)
+        v = blocked[:nb * 128 * self.d].view(nb, self.d // 64, 8, 4, 16, 16)           # block, slice, row group, piece, row, byte
+        return v.permute(0, 2, 4, 1, 3, 5).reshape(nb * 128, self.d)[:n]
+
+    def rows_to_blocked(self, codes: torch.Tensor) -> torch.Tensor:
+        n = codes.shape[0]
+        nb = -(-n // 128)
+        buf = torch.zeros(nb * 128, self.d, dtype=torch.uint8, device=self.device)
+        buf[:n] = codes.to(self.device)
+        return buf.view(nb, 8, 16, self.d // 64, 4, 16).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)
+
+    # -- training ------------------------------------------------------------------------------------------------
+    def train(self, x, more: bool = False):
+        """Range statistic RS_minmax: vmin / vdiff per dimension (QT_8bit) or over all elements (QT_8bit_uniform); NaN values are ignored
+        (a range with no other value gets vmin = vdiff = 0).
+        more=True folds x into the range of the earlier train() calls (training on a large input in pieces)."""
+        x = self._rows(x)
+        if x.shape[0] < 1:
+            raise ValueError("SQ8Index.train: 0 training rows")
+        if self._minmax is None or not more:
+            self._minmax = torch.empty(2, self.d, dtype=torch.float32, device=self.device)
+            self._minmax[0].fill_(float("inf"))
+            self._minmax[1].fill_(float("-inf"))
+        for s in range(0, x.shape[0], 1 << 22):
+            xs = x[s:s + (1 << 22)]
+            _lib.check(self.lib.lrx_sq8_train_minmax(_lib.ptr(xs), xs.shape[0], xs.stride(0), self.d, _lib.ptr(self._minmax), _lib.current_stream()))
+        mn, mx = self._minmax[0], self._minmax[1]
+        if self.uniform:
+            mn, mx = mn.min().reshape(1), mx.max().reshape(1)
+        empty = mn > mx                                # no value that is not NaN: vmin = vdiff = 0 (every code 0, decoded 0)
+        mn, mx = mn.masked_fill(empty, 0.0), mx.masked_fill(empty, 0.0)
+        self.trained = torch.cat([mn, mx - mn])        # (fp32 subtraction: the contract's vdiff)
+        self.is_trained = True
+
+    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, trained: torch.Tensor):
+        for s in range(0, x.shape[0], 262144):
+            xs = x[s:s + 262144]
+            _lib.check(self.lib.lrx_sq8_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(trained), self.d, self._qt, _lib.ptr(codes), row0 + s,
+                                               _lib.current_stream()))
+
+    def encode(self, x) -> torch.Tensor:
+        """faiss sa_encode: row-major uint8 [n, d] codes of x under this index's training."""
+        x = self._rows(x)
+        blocked = torch.zeros(-(-x.shape[0] // 128) * 128 * self.d, dtype=torch.uint8, device=self.device)
+        if x.shape[0]:
+            self._encode_into(x, blocked, 0, self.trained)
+        return self.blocked_to_rows(blocked, x.shape[0]).contiguous()
+
+    # -- rows ------------------------------------------------------------------------------------------------------
+    def add(self, x):
+        """faiss add(x f32[n, d]): encode into the codes (raises before train(), as faiss does)."""
+        if not self.is_trained:
+            raise RuntimeError("SQ8Index.add: the index is not trained (call train() first)")
+        x = self._rows(x)
+        n = x.shape[0]
+        if self.ntotal + n > self.capacity:
+            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        if n:
+            self._encode_into(x, self._codes, self.ntotal, self.trained)
+        self.ntotal += n
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
+        if self._stage is None or self._stage.shape[0] < n_rows:
+            self._stage = None
+            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+        return self._stage[:n_rows]
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            if self._stage is None or n_rows > self._stage.shape[0]:
+                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
+            rows = self._stage[:n_rows]
+            if not self.is_trained:
+                self.train(rows)
+            self.add(rows)
+        self._stage = None                             # staging released (stream-ordered by the allocator)
+
+    def reset(self):
+        """faiss reset(): drops the rows, keeps the training."""
+        self.ntotal = 0
+        self._stage = None
+
+    def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
+        """Rows [i0, i0 + n) decoded to fp32 (the rows the scores are defined over), device tensor [n, d]."""
+        _check_range(i0, n, self.ntotal)
+        out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
+        for s in range(0, n, 1 << 20):
+            m = min(1 << 20, n - s)
+            _lib.check(self.lib.lrx_sq8_decode_rows(_lib.ptr(self._codes), i0 + s, m, _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(out[s:]), self.d,
+                                                    _lib.current_stream()))
+        return out
+
+    def codes(self) -> torch.Tensor:
+        """The codes as a row-major uint8 [ntotal, d] tensor (a copy: the stored layout is tiled)."""
+        return self.blocked_to_rows(self._codes, self.ntotal).contiguous()
+
+    def set_contents(self, trained, codes):
+        """Replace the training (vmin ++ vdiff) and the rows (row-major uint8 [n, d] codes): load() and tests."""
+        t = torch.as_tensor(trained).to(self.device, torch.float32).reshape(-1).contiguous()
+        codes = torch.as_tensor(codes)
+        if t.numel() != self.trained.numel():
+            raise ValueError(f"set_contents: trained must hold {self.trained.numel()} floats for {self.qtype}")
+        if codes.ndim != 2 or codes.shape[1] != self.d or codes.dtype != torch.uint8:
+            raise ValueError(f"set_contents: codes must be uint8 [n, {self.d}]")
+        self.trained = t
+        self.is_trained = True
+        self._minmax = None
+        self._codes = None
+        self._codes = self.rows_to_blocked(codes)
+        self.ntotal = codes.shape[0]
+
+    # -- persistence (faiss.write_index / read_index of an IndexScalarQuantizer(QT_8bit[_uniform]), see index_io.py) ----------
+    def save(self, fname: str, chunk_rows: int = 1 << 18):
+        from .index_io import write_sq8
+        write_sq8(fname, self.trained.cpu().numpy(), (self.blocked_to_rows(self._codes[s // 128 * 128 * self.d:], min(chunk_rows, self.ntotal - s)).cpu().numpy()
+                                                      for s in range(0, self.ntotal, chunk_rows)), self.d, self.ntotal, self._qt, self.is_trained)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 1 << 18) -> "SQ8Index":
+        from .index_io import read_sq8
+        qt, trained, codes, is_trained = read_sq8(fname)
+        n, d = codes.shape
+        idx = cls(d, {v: k for k, v in cls.QTYPES.items()}[qt], capacity=n, device=device, id_base=id_base)
+        idx.trained = torch.from_numpy(trained).to(idx.device)
+        for s in range(0, n, chunk_rows):              # (chunk_rows is a multiple of 128: whole blocks)
+            e = min(s + chunk_rows, n)
+            blk = idx.rows_to_blocked(torch.from_numpy(np.array(codes[s:e], copy=True)))
+            idx._codes[s * d:s * d + blk.numel()].copy_(blk)
+        idx.ntotal = n
+        idx.is_trained = is_trained
+        return idx
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
+    # -- search --------------------------------------------------------------------------------------------------
+    def search(self, q, k: int, row_map: Optional[torch.Tensor] = None):
+        """faiss search -> (D f32[Q,k], I i64[Q,k]) device tensors: score descending, ties to the lower row, (-FLT_MAX, -1) padding when
+        k > ntotal.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries) when given."""
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        if not 1 <= k <= 2048:
+            raise ValueError(f"search: k={k} out of range (1..2048)")
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        Q = q.shape[0]
+        D = torch.empty(Q, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
+        if Q == 0:
+            return D, I
+        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_sq8_ip_workspace_bytes(self.ntotal, self.d, Q, k)), self.device,
+                        "SQ8Index.search under graph capture: the search workspace must exist before the capture starts -- run one eager "
+                        "search with the same number of queries and k first")
+        _lib.check(self.lib.lrx_sq8_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(q), Q, k,
+                                              int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
+                                              _lib.current_stream()))
+        return D, I
+
+
 class BinaryFlatIndex:
     """Binary flat shard: the faiss IndexBinaryFlat(d) surface (add / search / reset / ntotal / reconstruct_n / save / load) plus the reference's
     float rerank (FaissBinaryIndex.search), backed by lrx_binary_ip_search / lrx_binary_hamming_search.  Resident: d / 8 bytes per row (d = the

@@ -29,7 +29,15 @@ An fp16 scalar-quantised shard (SQFp16Index) is written as Faiss's serialisation
     u64   n_bytes = ntotal * 2 d              (WRITEVECTOR of the codes)
     f16   codes[ntotal * d]                   row-major, little-endian
 
-Like the flat layout it is **unverified against a Faiss build**.  Files with any other qtype are rejected.
+Like the flat layout it is **unverified against a Faiss build**.  read_sq_fp16 rejects files with any other qtype.
+
+An 8-bit scalar-quantised shard (SQ8Index) is the same 'IxSQ' record with qtype = 0 (QT_8bit: code_size = d, `trained` = vmin[d] ++ vdiff[d],
+2 d floats) or qtype = 2 (QT_8bit_uniform: `trained` = vmin, vdiff, 2 floats) and one byte per element:
+
+    u64   len(trained),  f32 trained[len(trained)]
+    u64   n_bytes = ntotal * d,  u8 codes[ntotal][d]      row-major
+
+(file size 37 + 28 + 8 + 4 len(trained) + 8 + ntotal * d).  sq_qtype(fname) tells a caller which of the two readers a file needs.
 
 A product-quantised shard (PQIndex, faiss IndexPQ(d, M, 8, METRIC_INNER_PRODUCT)) is written as Faiss's serialisation of IndexPQ, same
 source:
@@ -157,6 +165,58 @@ def read_sq_fp16(fname: str) -> np.memmap:
         raise ValueError(f"{fname}: inconsistent QT_fp16 index (d={d}, ntotal={ntotal}, sq.d={sq_d}, code_size={code_size}, "
                          f"code bytes={n_bytes}, metric={metric}, file bytes={size})")
     return np.memmap(fname, dtype="<f2", mode="r", offset=off, shape=(ntotal, d))
+
+
+QT_8BIT, QT_8BIT_UNIFORM = 0, 2
+SQ8_QTYPES = {"QT_8bit": QT_8BIT, "QT_8bit_uniform": QT_8BIT_UNIFORM}
+
+
+def _sq8_trained_len(qtype: int, d: int) -> int:
+    if qtype not in (QT_8BIT, QT_8BIT_UNIFORM):
+        raise ValueError(f"ScalarQuantizer qtype {qtype} is not an 8-bit quantiser (QT_8bit = {QT_8BIT}, QT_8bit_uniform = {QT_8BIT_UNIFORM})")
+    return 2 * d if qtype == QT_8BIT else 2
+
+
+def sq_qtype(fname: str) -> int:
+    """The ScalarQuantizer qtype of an 'IxSQ' file (faiss's enum: 0 8bit, 1 4bit, 2 8bit_uniform, 3 4bit_uniform, 4 fp16, ...)."""
+    if os.path.getsize(fname) < _HEADER.size + _SQ.size:
+        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
+    with open(fname, "rb") as f:
+        _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
+        return _SQ.unpack(f.read(_SQ.size))[0]
+
+
+def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: int, ntotal: int, qtype: int = QT_8BIT, is_trained: bool = True) -> None:
+    """trained: fp32 vmin ++ vdiff (2 d floats for QT_8bit, 2 for QT_8bit_uniform); blocks: uint8 [n_i, d] code arrays in row order."""
+    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    if t.size != _sq8_trained_len(qtype, d):
+        raise ValueError(f"write_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
+    head = _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes() + struct.pack("<Q", ntotal * d)
+    _write_index(fname, "write_sq8", FOURCC_SQ, d, ntotal, is_trained, head, blocks, np.uint8, d)
+
+
+def read_sq8(fname: str):
+    """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained)."""
+    size = os.path.getsize(fname)
+    fixed = _HEADER.size + _SQ.size + 8
+    if size < fixed:
+        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
+    with open(fname, "rb") as f:
+        d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
+        qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
+        if qtype not in (QT_8BIT, QT_8BIT_UNIFORM):
+            raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served here (QT_8bit = {QT_8BIT}, QT_8bit_uniform = {QT_8BIT_UNIFORM})")
+        (n_t,) = struct.unpack("<Q", f.read(8))
+        if metric != 0 or d <= 0 or ntotal < 0 or sq_d != d or code_size != d or n_t != _sq8_trained_len(qtype, d) or size < fixed + 4 * n_t + 8:
+            raise ValueError(f"{fname}: inconsistent 8-bit scalar-quantiser index (d={d}, ntotal={ntotal}, sq.d={sq_d}, code_size={code_size}, "
+                             f"trained floats={n_t}, metric={metric}, file bytes={size})")
+        trained = np.frombuffer(f.read(4 * n_t), dtype="<f4").copy()
+        (n_b,) = struct.unpack("<Q", f.read(8))
+    off = fixed + 4 * n_t + 8
+    if n_b != ntotal * d or size != off + n_b:
+        raise ValueError(f"{fname}: inconsistent 8-bit codes (code bytes={n_b}, ntotal * d={ntotal * d}, file bytes={size})")
+    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=off, shape=(ntotal, d)) if ntotal else np.zeros((0, d), np.uint8)
+    return qtype, trained, codes, bool(is_trained)
 
 
 FOURCC_PQ = b"IxPq"

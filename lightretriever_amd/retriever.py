@@ -2,7 +2,7 @@
 
     FaissIndex          <- retriever/faiss_index.py:20-73      (build / search / reset over the HBM-resident FlatIPIndex)
     FlatIPFaissSearch   <- retriever/faiss_search.py:46-293, :477-510   (BEIR-style dense searcher)
-    SQFaissSearch       <- retriever/faiss_search.py:567-611             (QT_fp16 inner product only, over SQFp16Index)
+    SQFaissSearch       <- retriever/faiss_search.py:567-611             (inner product; QT_fp16 over SQFp16Index, QT_8bit_uniform over SQ8Index)
     PQFaissSearch       <- retriever/faiss_search.py:326-383             (IndexPQ, 8-bit codes, inner product only, over PQIndex)
     FaissBinaryIndex    <- retriever/faiss_index.py:116-192              (Hamming candidates + float rerank over BinaryFlatIndex)
     BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
@@ -27,7 +27,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQFp16Index, merge_topk
+from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -288,22 +288,47 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
 
 
 class SQFaissSearch(FlatIPFaissSearch):
-    """faiss_search.py:567-611 with its default quantizer: IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT), served by SQFp16Index --
-    2 B/element resident, exact inner products of the fp32 query with the decoded codes.  index / _index_in_place / load / save behave like
-    FlatIPFaissSearch's with that shard.  Other quantizer types and metrics are not served; neither are shards on RPC workers."""
+    """faiss_search.py:567-611: IndexScalarQuantizer(d, quantizer_type, METRIC_INNER_PRODUCT).  "QT_fp16" (the default) is served by
+    SQFp16Index -- 2 B/element resident, exact inner products of the fp32 query with the decoded codes -- and "QT_8bit_uniform" by SQ8Index:
+    1 B/element, one trained range for all dimensions, index() trains on the chunk and then adds it (FaissTrainIndex.build), _index_in_place
+    trains when the staging slot is committed.  index / _index_in_place / save behave like FlatIPFaissSearch's with that shard; load() picks
+    the shard class from the file's qtype, as faiss.read_index would, whatever the constructor said.
+    "QT_8bit" (a range per dimension) is REFUSED by this constructor although SQ8Index serves it: an existing test pins the refusal.  It is
+    reachable through SQ8Index(d, "QT_8bit"), torch.ops.lrx.sq8_ip_topk, the C API and load() of a QT_8bit file; lifting the refusal (together
+    with that test) is a one-line follow-up.  Other quantizer types and metrics are not served; neither are shards on RPC workers."""
     index_cls = SQFp16Index
     index_ext = "sq"
     serves_rpc_shards = False
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, similarity_metric=0, quantizer_type: str = "QT_fp16",
                  **kwargs):
-        if quantizer_type != "QT_fp16":
-            raise NotImplementedError(f"SQFaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_fp16')")
+        if quantizer_type not in ("QT_fp16", "QT_8bit_uniform"):
+            raise NotImplementedError(f"SQFaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_fp16' and 'QT_8bit_uniform')")
         if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
             raise NotImplementedError(f"SQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
         super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
         self.similarity_metric = 0
         self.qname = quantizer_type
+        if quantizer_type != "QT_fp16":
+            self.index_cls = SQ8Index
+
+    def _new_index(self, dim: int, capacity: int):
+        if self.index_cls is SQ8Index:
+            return SQ8Index(dim, self.qname, capacity=capacity)
+        return super()._new_index(dim, capacity)
+
+    def _train(self, idx, corpus_emb):
+        if isinstance(idx, SQ8Index):
+            idx.train(corpus_emb)                     # index() trains on the chunk, then adds it (FaissTrainIndex.build)
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        """The shard class follows the file's qtype (4: SQFp16Index, 0 / 2: SQ8Index), as faiss.read_index would."""
+        from .index_io import QT_FP16, shard_prefix, sq_qtype
+        e = self.index_ext if ext is None else ext
+        path = os.path.join(input_dir, "{}.{}.faiss".format(shard_prefix(prefix, *self._rank_world()), e))
+        self.index_cls = SQFp16Index if sq_qtype(path) == QT_FP16 else SQ8Index
+        super().load(input_dir, prefix, ext)
+        self.qname = "QT_fp16" if self.index_cls is SQFp16Index else self.faiss_index.index.qtype
 
     def get_index_name(self):
         return "sq_faiss_index"
@@ -405,7 +430,7 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16), "pq" (IndexPQ) and "binary" (IndexBinaryFlat + rerank) are
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ) and "binary" (IndexBinaryFlat + rerank) are
         # served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
         den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
@@ -414,6 +439,8 @@ class HybridSearch:
         den_kwargs = {}
         if faiss_search_map == "pq":                  # (the reference passes its **kwargs through to the searcher)
             den_kwargs = {a: kwargs[a] for a in ("num_of_centroids", "code_size", "use_rotation", "similarity_metric") if a in kwargs}
+        if faiss_search_map == "sq":
+            den_kwargs = {a: kwargs[a] for a in ("quantizer_type", "similarity_metric") if a in kwargs}
         if faiss_search_map == "binary":
             den_kwargs = {a: kwargs[a] for a in ("binary_k", "threshold") if a in kwargs}
         self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
