@@ -1,7 +1,7 @@
 """The attention launch on a prebuilt work list (include/lrx.h, ABI 7: lrx_attn_items_bytes / lrx_attn_build_items /
 lrx_attn_varlen_causal_items) against the launch without one: the same bits, whatever the head layout, the batch size (grouped lists once the
-items outnumber the workgroup slots) and the mode.  Oracle parity of the list kernel itself: tests/test_gpu_kernels.py (ops.attn_varlen_causal
-builds a list by default).  Replaces the FA2 varlen call of utils/nested_input.py:137-146."""
+items outnumber the workgroup slots) and the mode.  Parity of the list kernel itself with a float64 reference, at every entry of CASES below:
+tests/test_gpu_attn_reference.py (it imports the list).  Replaces the FA2 varlen call of utils/nested_input.py:137-146."""
 import numpy as np
 import pytest
 import torch

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_reference as AR
 from oracle import lrx_oracle as O
 from helpers import GOLDEN
 
@@ -151,7 +152,14 @@ def attn_oracle(qkv, cu, nq, nkv, d):
     return out.reshape(T, nq * d)
 
 
-@pytest.mark.parametrize("d,nq,nkv,lens", [
+def attn_within_bound(got: torch.Tensor, O64: torch.Tensor, A64: torch.Tensor):
+    """the derived bound of tests/attn_reference.py against the float64 reference (beside, not instead of, the numpy oracle's tolerance)"""
+    ratio = AR.worst_ratio(got, O64, A64)
+    print(f"worst |err| / bound = {ratio:.3f}")
+    assert ratio <= 1.0, f"worst |err| / bound = {ratio:.3f}"
+
+
+VARLEN_CASES = [
     (64, 4, 2, [1, 2, 31, 32, 33, 63, 64, 65, 100, 128, 129, 200]),
     (64, 8, 2, [512, 7, 300]),
     (64, 2, 2, [96, 5]),
@@ -174,7 +182,10 @@ def attn_oracle(qkv, cu, nq, nkv, d):
     (64, 3, 1, [530, 33]),           # ... with an odd group
     (64, 16, 1, [513, 70]),          # ... group 16: two workgroups of 8 heads
     (128, 4, 1, [700, 64]),
-])
+]
+
+
+@pytest.mark.parametrize("d,nq,nkv,lens", VARLEN_CASES)
 def test_attention_varlen_causal(d, nq, nkv, lens):
     from lightretriever_amd import ops
     rng = np.random.default_rng(sum(lens) + d)
@@ -187,6 +198,7 @@ def test_attention_varlen_causal(d, nq, nkv, lens):
     np.testing.assert_allclose(f32(got), want, atol=2e-2, rtol=2e-2)
     # rows are convex combinations of v: a tighter relative check on the row norms catches scale errors
     assert abs(np.linalg.norm(f32(got)) / np.linalg.norm(want) - 1) < 3e-3
+    attn_within_bound(got, *AR.causal_gqa_fp64(f16_t(qkv), cu, nq, nkv, d))
 
 
 def test_attention_forced_max_jump():
@@ -199,6 +211,7 @@ def test_attention_forced_max_jump():
     cu = np.array([0, L], np.int32)
     got = ops.attn_varlen_causal(f16_t(qkv), torch.from_numpy(cu).to(dev()), L, nq, nkv, d)
     np.testing.assert_allclose(f32(got), attn_oracle(qkv, cu, nq, nkv, d), atol=2e-2, rtol=2e-2)
+    attn_within_bound(got, *AR.causal_gqa_fp64(f16_t(qkv), cu, nq, nkv, d))
 
 
 @pytest.mark.parametrize("H,out_dim,normalize", [(256, 256, True), (256, 64, True), (2048, 2048, True), (2048, 256, False)])
@@ -356,11 +369,14 @@ def test_gemm_qkv_rope_fused_equals_fp32_projection_then_rope(d, nq, nkv, bias, 
     assert torch.equal(perm[(nq + nkv) * d:], torch.arange((nq + nkv) * d, N, device=perm.device))    # v columns stay in place
 
 
-@pytest.mark.parametrize("d,nq,nkv,P1,S2,n", [(64, 4, 2, 9, 2, 37), (64, 32, 8, 22, 2, 5), (128, 8, 1, 3, 3, 11), (64, 2, 2, 0, 2, 4), (128, 4, 4, 40, 1, 3),
+PREFIX_SUFFIX_CASES = [(64, 4, 2, 9, 2, 37), (64, 32, 8, 22, 2, 5), (128, 8, 1, 3, 3, 11), (64, 2, 2, 0, 2, 4), (128, 4, 4, 40, 1, 3),
                                               # round 2: the matrix-core kernel (P1 <= 64): 32-sequence blocks with a ragged tail, two prefix tiles,
                                               # GQA groups of 6 (Qwen2.5-1.5B) and 4 suffix tokens; and shapes that keep the VALU kernel
                                               (64, 32, 8, 21, 2, 100), (64, 8, 8, 33, 2, 65), (128, 12, 2, 21, 2, 70), (128, 32, 8, 64, 2, 33), (64, 4, 1, 1, 4, 64),
-                                              (64, 8, 2, 70, 2, 9), (128, 28, 4, 21, 2, 40)])
+                                              (64, 8, 2, 70, 2, 9), (128, 28, 4, 21, 2, 40)]
+
+
+@pytest.mark.parametrize("d,nq,nkv,P1,S2,n", PREFIX_SUFFIX_CASES)
 def test_attention_prefix_suffix_equals_full_causal(d, nq, nkv, P1, S2, n):
     """Suffix queries over a shared prefix == the suffix rows of full causal attention on [prefix + suffix] per sequence."""
     from lightretriever_amd import ops
@@ -370,13 +386,15 @@ def test_attention_prefix_suffix_equals_full_causal(d, nq, nkv, P1, S2, n):
     suf = rnd(rng, n * S2, W)
     suf[:, :nq * d] *= 2.0
     prefix_kv = np.ascontiguousarray(pre[:, nq * d:])
-    got = f32(ops.attn_prefix_suffix(f16_t(suf), f16_t(prefix_kv).reshape(P1, 2 * nkv * d), n, S2, nq, nkv, d))
+    got_t = ops.attn_prefix_suffix(f16_t(suf), f16_t(prefix_kv).reshape(P1, 2 * nkv * d), n, S2, nq, nkv, d)
+    got = f32(got_t)
     L = P1 + S2
     full = np.concatenate([np.concatenate([pre, suf[i * S2:(i + 1) * S2]]) for i in range(n)])
     cu = (np.arange(n + 1) * L).astype(np.int32)
     want = attn_oracle(full, cu, nq, nkv, d).reshape(n, L, nq * d)[:, P1:].reshape(n * S2, nq * d)
     np.testing.assert_allclose(got, want, atol=2e-2, rtol=2e-2)
     assert abs(np.linalg.norm(got) / np.linalg.norm(want) - 1) < 3e-3
+    attn_within_bound(got_t, *AR.prefix_suffix_fp64(f16_t(suf), f16_t(prefix_kv).reshape(P1, 2 * nkv * d), n, S2, nq, nkv, d))
 
 
 def test_uniform_layout():
