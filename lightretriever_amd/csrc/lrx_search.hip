@@ -4,6 +4,7 @@
 //     lrx_search_filter.h   A. score / filter kernels          lrx_search_select.h   B. selection
 //     lrx_search_bounded.h  C. error bound, threshold, fused   lrx_search_refine.h   C. band refine, row-grouped rescoring, part merge
 //     lrx_search_range.h    F. range search: threshold from a given radius, exact rescoring, row-ordered output (host driver: lrx_flat_ip_range_search)
+//     lrx_search_codes.h    G-I. the code-based indexes' shared host side: argument checks, workspace plan, row-chunked scan driver, k_map_ids
 //     lrx_search_pq.h       G. product-quantised index: encode, lookup tables, ADC scan -> k_topk_select / merge, decode (with its host driver)
 //     lrx_search_binary.h   H. binary flat index: pack, Hamming scan, selection by counting, fp64 rerank, decode (with its host driver)
 // Map of the unit:
@@ -1208,6 +1209,7 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
   return LRX_OK;
 }
 
-#include "lrx_search_pq.h"       // product-quantised index: encode, lookup tables, ADC scan (-> k_topk_select, merge_launch), decode
+#include "lrx_search_codes.h"    // what the three code-based indexes share: argument checks, ScanPlan, scan_search (row-chunked scan driver), k_map_ids
+#include "lrx_search_pq.h"       // product-quantised index: encode, lookup tables, ADC scan (-> k_topk_select), decode
 #include "lrx_search_binary.h"   // binary flat index: pack, Hamming scan, selection by counting, rerank, decode
 #include "lrx_search_sq8.h"      // 8-bit scalar-quantised index: min/max, encode, i8-MFMA filter scan, band rescoring from the codes, decode

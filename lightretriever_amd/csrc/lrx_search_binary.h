@@ -462,17 +462,12 @@ static int bin_check_search(const char* who, const void* codes, int64_t n_rows, 
                             const void* out_d, const void* out_i, const void* ws, size_t ws_bytes, int32_t flags) {
   LRX_CHECK_ARG(dim > 0 && dim % 8 == 0 && dim <= BIN_MAX_BITS, "%s: dim=%d must be a positive multiple of 8, at most %d", who, dim, BIN_MAX_BITS);
   LRX_CHECK_ARG(k >= 1 && k <= binary_k && binary_k <= BIN_MAXK, "%s: need 1 <= k <= binary_k <= %d (k=%d, binary_k=%d)", who, BIN_MAXK, k, binary_k);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32) - 1, "%s: shard rows=%lld out of range", who, (long long)n_rows);
+  if (codes_check_rows(who, n_rows) != LRX_OK) return LRX_ERR_INVALID;
   LRX_CHECK_ARG((flags & ~LRX_BINARY_SELECT_ONLY) == 0, "%s: unknown flags 0x%x", who, flags);
   if (n_queries <= 0) return LRX_OK;
   LRX_CHECK_ARG((codes != nullptr || n_rows == 0) && q != nullptr && ((out_d != nullptr && out_i != nullptr) || (flags & LRX_BINARY_SELECT_ONLY)) && ws != nullptr,
                 "%s: null pointer", who);
-  const size_t need = bin_plan(n_rows, dim, n_queries).total;
-  if (ws_bytes < need) {
-    lrx_set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
-    return LRX_ERR_WORKSPACE;
-  }
-  return LRX_OK;
+  return codes_check_workspace(who, ws_bytes, bin_plan(n_rows, dim, n_queries).total);
 }
 
 extern "C" int lrx_binary_hamming_search(const void* codes, int64_t n_rows, int32_t dim, const float* q, int32_t n_queries, float threshold,

@@ -1,13 +1,12 @@
 // liblrx search, part 6 -- PRODUCT-QUANTISED inner-product index (faiss IndexPQ(d, M, 8, METRIC_INNER_PRODUCT)), map: section G.
-// Part of the ONE translation unit lrx_search.hip (included at its end: it reuses k_topk_select, merge_launch and lrx_cu_count).  Not a
-// stand-alone header.  Contract and code layout: include/lrx.h (lrx_pq_ip_search), DESIGN.md §5.4.3.
+// Part of the ONE translation unit lrx_search.hip (included at its end, after lrx_search_codes.h: it reuses k_topk_select, lrx_cu_count and the
+// shared plan, checks and scan driver).  Not a stand-alone header.  Contract and code layout: include/lrx.h (lrx_pq_ip_search), DESIGN.md §5.4.3.
 //
 //     k_pq_encode    code[m] = argmin_j sum_i (x_i - C[m][j][i])^2, fp64 terms summed in order, ties to the lower j (add() and k-means)
 //     k_pq_lut       LUT[q][m][j] = (float) sum_i (double) q_i (double) C[m][j][i]
 //     k_pq_scan      THE HOT PATH: s(q, r) = fp32 sum of LUT[q][m][code_m(r)] in ascending m, the query's table in LDS; writes the
-//                    [Q, ld] score matrix of a row chunk and its 128-row block maxima -> k_topk_select (-> merge_launch across row chunks)
+//                    [Q, ld] score matrix of a row chunk and its 128-row block maxima -> k_topk_select (scan_search, lrx_search_codes.h)
 //     k_pq_decode    rows from their codes (reconstruct_n)
-//     k_pq_map_ids   local rows -> id_base + row or row_map[row]
 #pragma once
 
 #define PQ_KSUB 256
@@ -155,41 +154,12 @@ k_pq_decode(const uint8_t* __restrict__ codes, int64_t row0, int64_t n_rows, con
   out[i * ldo + col] = C[((int64_t)m * PQ_KSUB + c) * dsub + (col - m * dsub)];
 }
 
-__global__ void k_pq_map_ids(int64_t* __restrict__ ids, int64_t n, int64_t id_base, const int64_t* __restrict__ row_map) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  const int64_t r = ids[t];
-  if (r >= 0) ids[t] = row_map != nullptr ? row_map[r] : id_base + r;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct PQPlan {
-  int64_t rc, ld;         // rows per score matrix, its row stride
-  int nblk_ld, qc;        // block maxima stride, queries per chunk
-  bool merge;             // more than one row chunk: running top-k merged with each chunk's
-  size_t lut_off, sc_off, bm_off, part_s_off, part_i_off, total;
-};
-
-static PQPlan pq_plan(int64_t n_rows, int32_t M, int32_t n_queries, int32_t k) {
-  PQPlan p;
-  p.rc = n_rows < PQ_ROW_CHUNK ? (n_rows > 0 ? n_rows : 1) : PQ_ROW_CHUNK;
-  p.ld = (p.rc + 63) & ~(int64_t)63;
-  p.nblk_ld = ((int)lrx_cdiv(p.rc, PQ_BLK) + 3) & ~3;
-  p.merge = n_rows > PQ_ROW_CHUNK;
-  const int64_t per_q = p.ld * 4 + (int64_t)p.nblk_ld * 4;
-  int64_t qc = PQ_MATRIX_BYTES / per_q;
-  const int64_t nq = n_queries > 0 ? n_queries : 1;
-  p.qc = (int)(qc < 1 ? 1 : (qc > nq ? nq : qc));
-  const size_t q = (size_t)p.qc;
-  p.lut_off = 0;
-  p.sc_off = align256(q * M * PQ_KSUB * 4);
-  p.bm_off = p.sc_off + align256(q * (size_t)p.ld * 4);
-  p.part_s_off = p.bm_off + align256(q * (size_t)p.nblk_ld * 4);
-  p.part_i_off = p.part_s_off + (p.merge ? align256(2 * q * k * 4) : 0);
-  p.total = p.part_i_off + (p.merge ? align256(2 * q * k * 8) : 0);
-  return p;
+// the leading region of the workspace is the chunk's lookup tables [qc, M, 256] fp32
+static ScanPlan pq_plan(int64_t n_rows, int32_t M, int32_t n_queries, int32_t k) {
+  return scan_plan(n_rows, n_queries, k, PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, INT32_MAX, [&](int qc) { return align256((size_t)qc * M * PQ_KSUB * 4); });
 }
 
 extern "C" size_t lrx_pq_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k) {
@@ -215,63 +185,37 @@ extern "C" int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* 
                                 int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                 size_t workspace_bytes, int32_t flags, void* stream) {
   (void)flags;
-  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "pq_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32) - 1, "pq_ip_search: shard rows=%lld out of range", (long long)n_rows);
+  int rc = codes_check_topk("pq_ip_search", k, n_rows);
+  if (rc != LRX_OK) return rc;
   LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "pq_ip_search: dim=%d is not a multiple of M=%d", dim, M);
   if (n_queries <= 0) return LRX_OK;
-  const PQPlan p = pq_plan(n_rows, M, n_queries, k);
-  if (workspace_bytes < p.total) {
-    lrx_set_error("pq_ip_search: workspace %zu B < required %zu B", workspace_bytes, p.total);
-    return LRX_ERR_WORKSPACE;
-  }
+  const ScanPlan p = pq_plan(n_rows, M, n_queries, k);
+  if ((rc = codes_check_workspace("pq_ip_search", workspace_bytes, p.total)) != LRX_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float* lut = (float*)(ws + p.lut_off);
-  float* sc = (float*)(ws + p.sc_off);
-  float* bm = (float*)(ws + p.bm_off);
-  float* part_s = (float*)(ws + p.part_s_off);
-  int64_t* part_i = (int64_t*)(ws + p.part_i_off);
+  float* lut = (float*)workspace;
   const int Mp = pq_mp(M);
   const int mc = M < PQ_SCAN_MC ? M : PQ_SCAN_MC;
   const size_t smem = (size_t)mc * PQ_KSUB * 4;
   LRX_HIP(hipFuncSetAttribute((const void*)k_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   const int ncu = lrx_cu_count();
-  for (int32_t q0 = 0; q0 < n_queries; q0 += p.qc) {
-    const int nq = n_queries - q0 < p.qc ? n_queries - q0 : p.qc;
-    float* os = out_scores + (int64_t)q0 * k;
-    int64_t* oi = out_ids + (int64_t)q0 * k;
-    int rc = lrx_pq_lut(q + (int64_t)q0 * dim, nq, centroids, dim, M, lut, stream);
-    if (rc != LRX_OK) return rc;
-    int64_t r0 = 0;
-    do {
-      const int64_t nr = n_rows - r0 < p.rc ? n_rows - r0 : p.rc;
-      const int64_t ntiles = lrx_cdiv(nr, PQ_SCAN_THREADS);
-      const int nblk = (int)lrx_cdiv(nr, PQ_BLK);
-      if (nr > 0) {
+  return scan_search(
+      p, workspace, n_rows, n_queries, k, id_base, out_scores, out_ids, row_map, stream,
+      [&](int32_t q0, int nq) { return lrx_pq_lut(q + (int64_t)q0 * dim, nq, centroids, dim, M, lut, stream); },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) {
+        const int64_t ntiles = lrx_cdiv(nr, PQ_SCAN_THREADS);
         int64_t gx = lrx_cdiv(2 * (int64_t)ncu, nq);
         gx = gx > ntiles ? ntiles : gx;
         hipLaunchKernelGGL(k_pq_scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, s,
                            (const uint8_t*)codes + (r0 / PQ_BLK) * PQ_BLK * Mp, nr, M, Mp, (const float*)lut, sc, p.ld, bm, p.nblk_ld);
         LRX_LAUNCH_CHECK();
-      }
-      // first chunk: straight into the output; later chunks: into part 1, merged with the running result (copied to part 0)
-      const bool into_part = r0 > 0;
-      hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)sc, p.ld, nr, k, r0, (const float*)bm, nblk, p.nblk_ld,
-                         into_part ? part_s + (int64_t)nq * k : os, into_part ? part_i + (int64_t)nq * k : oi, (const int*)nullptr, (const int*)nullptr);
-      LRX_LAUNCH_CHECK();
-      if (into_part) {
-        LRX_HIP(hipMemcpyAsync(part_s, os, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, s));
-        LRX_HIP(hipMemcpyAsync(part_i, oi, (size_t)nq * k * 8, hipMemcpyDeviceToDevice, s));
-        rc = merge_launch(part_s, part_i, nullptr, 2, nq, k, os, oi, stream);
-        if (rc != LRX_OK) return rc;
-      }
-      r0 += nr;
-    } while (r0 < n_rows);
-    const int64_t n_out = (int64_t)nq * k;
-    hipLaunchKernelGGL(k_pq_map_ids, dim3((unsigned)lrx_cdiv(n_out, 256)), dim3(256), 0, s, oi, n_out, id_base, row_map);
-    LRX_LAUNCH_CHECK();
-  }
-  return LRX_OK;
+        return LRX_OK;
+      },
+      [&](int32_t, int64_t r0, int64_t nr, int nq, const float* sc, const float* bm, float* os, int64_t* oi) {
+        hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, sc, p.ld, nr, k, r0, bm, (int)lrx_cdiv(nr, PQ_BLK), p.nblk_ld, os, oi,
+                           (const int*)nullptr, (const int*)nullptr);
+        LRX_LAUNCH_CHECK();
+        return LRX_OK;
+      });
 }
 
 extern "C" int lrx_pq_encode(const float* x, int64_t n_rows, int64_t ldx, const float* centroids, int32_t dim, int32_t M, void* codes, int64_t row0,

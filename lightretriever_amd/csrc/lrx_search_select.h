@@ -393,56 +393,17 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ X, int64_t ld
   else return exact_dot_codes((const _Float16*)X, r, qrow, D, lane);
 }
 
-// Select + final step of the plain path (and of the gated fallback of the bounded search) in one launch, RIGOROUS since round 3: the
-// matrix scores s6 (six bf16 products, or the fp32 fma chain for <= 32 queries) differ from the exact inner product s by at most
-//     eps6(q) = (6 D + 8) 2^-23 |q| R            R >= max |x_row|  (bounds[0])
-// (dropped product terms mid*lo, lo*mid, lo*lo <= 2^-23 sum |q_i x_i|; at most 6 D fp32 accumulation steps, each within 2^-23 of a
-// partial sum that is itself <= (1 + 2^-7) |q| |x|; Cauchy-Schwarz).  Every row of the exact top-k has s >= S_k >= kth6 - eps6 (k rows
-// have s6 >= kth6), hence s6 >= kth6 - 2 eps6: ALL rows at or above that threshold are rescored exactly (fp64 accumulation, one rounding)
-// and the best k of them returned.  Usually that is k + a few rows; a near-duplicate cluster with more than SEL_CAND rows inside the band
-// takes the streaming form (the score row walked in 2048-row windows, a running exact top-k in LDS): slow (~ms per such query) but exact
-// for any cluster size.  (Round 2 selected k + 64 rows by score: a heuristic that a stress run had already caught once.)
-// RS = ROWS_F16T (the gated fallback of the fp16 scalar-quantised index): the matrix holds the one-product fp16 filter scores over the codes,
-// so the band is 2 eps(q) of query_eps_block<true> (lrx_search_bounded.h), and the rows are rescored from the codes.
-__device__ __forceinline__ float block_sum_1024(float v, float* red /* 16 */) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) t += red[w];
-  return t;
-}
-
-template <int RS>   // (lrx_search_bounded.h)
-__device__ float query_eps_block(const float* __restrict__ qglob, int D, const float* __restrict__ bounds, float* s_q, float* s_red);
-template <int RS>
-__device__ __forceinline__ void select_rescore_query(const float* __restrict__ scores, int64_t ld, int64_t N, int k, int64_t id_base,
-                                                     const float* __restrict__ blkmax, int nblk, int nblk_ld, const float* __restrict__ X, int64_t ldx,
-                                                     int D, const float* __restrict__ q, float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
-                                                     const float* __restrict__ bounds, SelShared& sh, float* s_red) {
-  const float* row = scores + (int64_t)blockIdx.x * ld;
-  float* os = out_scores + (int64_t)blockIdx.x * k;
-  int64_t* oi = out_ids + (int64_t)blockIdx.x * k;
+// What every rigorous select does once its threshold is known (one workgroup per query; select_rescore_query below and k_sq8_select_rescore,
+// lrx_search_sq8.h): ALL rows of the score row with a matrix score >= thr -- found through the 128-row block maxima `bm` when the row is
+// longer than SEL_CAND (bm == nullptr: straight to the streaming form) -- are rescored in place by row_score(r) (every lane of a half-wave
+// calls it with the same row and gets the exact score) and sorted; os / oi receive the best keff, ids = id_base + row.  sh.cand[0..keff) holds
+// the caller's selection by matrix score: it stands when thr is NaN (non-finite query or bound).  More than SEL_CAND band rows (duplicate
+// clusters): the streaming form -- the score row walked in 2048-row windows, a running exact top in LDS -- slow (~ms per such query) but
+// exact for any band; returns whether it was taken.
+template <class RowScore>
+__device__ __forceinline__ bool rescore_band(const float* __restrict__ row, int64_t N, int keff, float thr, const float* __restrict__ bm, int nblk,
+                                             int64_t id_base, float* __restrict__ os, int64_t* __restrict__ oi, SelShared& sh, RowScore row_score) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int keff = (int)(N < (int64_t)k ? N : (int64_t)k);
-  for (int i = keff + tid; i < k; i += SEL_THREADS) { os[i] = -FLT_MAX; oi[i] = -1; }
-  if (keff == 0) return;
-  const float* qrow = q + (int64_t)blockIdx.x * D;
-  const float* bm = blkmax ? blkmax + (int64_t)blockIdx.x * nblk_ld : nullptr;
-  float eps6;
-  if constexpr (RS == ROWS_F32) {
-    float q2 = 0.f;
-    for (int i = tid; i < D; i += SEL_THREADS) { const float v = qrow[i]; q2 += v * v; }
-    q2 = block_sum_1024(q2, s_red);
-    eps6 = (float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f;
-  } else {
-    eps6 = query_eps_block<RS>(qrow, D, bounds, nullptr, s_red);
-  }
-  select_topk_sorted(row, N, keff, bm, nblk, sh);            // sh.cand[0..keff): the top-keff by matrix score, sorted
-  const float kth6 = key2f((uint32_t)(sh.cand[keff - 1] >> 32));
-  const float thr = kth6 - 2.0f * eps6;                      // (a non-finite query gives a NaN threshold: nothing qualifies below, the selection above stands)
   __syncthreads();
   unsigned long long* s_c = sh.cand;
   auto rescore = [&](unsigned long long* list, int n) {      // exact scores of list[0..n) in place: entry c is read and written by the same half-wave
@@ -450,11 +411,11 @@ __device__ __forceinline__ void select_rescore_query(const float* __restrict__ s
       const int c = min(c0 + (lane >> 5), n - 1);
       int64_t r = sel_row(list[c]);
       r = r < 0 ? 0 : (r >= N ? N - 1 : r);
-      const float sc = row_dot<RS>(X, ldx, r, qrow, D, lane);
+      const float sc = row_score(r);
       if ((lane & 31) == 0 && c0 + (lane >> 5) < n) list[c] = sel_pack(f2key(sc), r);
     }
   };
-  // ---- every row with s6 >= thr: the qualifying 128-row blocks first (block maxima), then their rows
+  // ---- every row with a matrix score >= thr: the qualifying 128-row blocks first (block maxima), then their rows
   unsigned int* blist = (unsigned int*)sh.eqs;               // 2 * SEL_EQCAP entries
   bool overflow = false;
   if (!(thr == thr)) {                                       // NaN band (non-finite query or bound): keep the score selection
@@ -534,6 +495,58 @@ __device__ __forceinline__ void select_rescore_query(const float* __restrict__ s
     os[i] = key2f((uint32_t)(c >> 32));
     oi[i] = id_base + sel_row(c);
   }
+  return overflow;
+}
+
+// Select + final step of the plain path (and of the gated fallback of the bounded search) in one launch, RIGOROUS since round 3: the
+// matrix scores s6 (six bf16 products, or the fp32 fma chain for <= 32 queries) differ from the exact inner product s by at most
+//     eps6(q) = (6 D + 8) 2^-23 |q| R            R >= max |x_row|  (bounds[0])
+// (dropped product terms mid*lo, lo*mid, lo*lo <= 2^-23 sum |q_i x_i|; at most 6 D fp32 accumulation steps, each within 2^-23 of a
+// partial sum that is itself <= (1 + 2^-7) |q| |x|; Cauchy-Schwarz).  Every row of the exact top-k has s >= S_k >= kth6 - eps6 (k rows
+// have s6 >= kth6), hence s6 >= kth6 - 2 eps6: ALL rows at or above that threshold are rescored exactly (fp64 accumulation, one rounding)
+// and the best k of them returned (rescore_band above).  (Round 2 selected k + 64 rows by score: a heuristic that a stress run had already caught once.)
+// RS = ROWS_F16T (the gated fallback of the fp16 scalar-quantised index): the matrix holds the one-product fp16 filter scores over the codes,
+// so the band is 2 eps(q) of query_eps_block<true> (lrx_search_bounded.h), and the rows are rescored from the codes.
+__device__ __forceinline__ float block_sum_1024(float v, float* red /* 16 */) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = 0.f;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) t += red[w];
+  return t;
+}
+
+template <int RS>   // (lrx_search_bounded.h)
+__device__ float query_eps_block(const float* __restrict__ qglob, int D, const float* __restrict__ bounds, float* s_q, float* s_red);
+template <int RS>
+__device__ __forceinline__ void select_rescore_query(const float* __restrict__ scores, int64_t ld, int64_t N, int k, int64_t id_base,
+                                                     const float* __restrict__ blkmax, int nblk, int nblk_ld, const float* __restrict__ X, int64_t ldx,
+                                                     int D, const float* __restrict__ q, float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+                                                     const float* __restrict__ bounds, SelShared& sh, float* s_red) {
+  const float* row = scores + (int64_t)blockIdx.x * ld;
+  float* os = out_scores + (int64_t)blockIdx.x * k;
+  int64_t* oi = out_ids + (int64_t)blockIdx.x * k;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int keff = (int)(N < (int64_t)k ? N : (int64_t)k);
+  for (int i = keff + tid; i < k; i += SEL_THREADS) { os[i] = -FLT_MAX; oi[i] = -1; }
+  if (keff == 0) return;
+  const float* qrow = q + (int64_t)blockIdx.x * D;
+  const float* bm = blkmax ? blkmax + (int64_t)blockIdx.x * nblk_ld : nullptr;
+  float eps6;
+  if constexpr (RS == ROWS_F32) {
+    float q2 = 0.f;
+    for (int i = tid; i < D; i += SEL_THREADS) { const float v = qrow[i]; q2 += v * v; }
+    q2 = block_sum_1024(q2, s_red);
+    eps6 = (float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f;
+  } else {
+    eps6 = query_eps_block<RS>(qrow, D, bounds, nullptr, s_red);
+  }
+  select_topk_sorted(row, N, keff, bm, nblk, sh);            // sh.cand[0..keff): the top-keff by matrix score, sorted
+  const float kth6 = key2f((uint32_t)(sh.cand[keff - 1] >> 32));
+  const float thr = kth6 - 2.0f * eps6;                      // (a non-finite query gives a NaN threshold: nothing qualifies below, the selection above stands)
+  rescore_band(row, N, keff, thr, bm, nblk, id_base, os, oi, sh, [&](int64_t r) { return row_dot<RS>(X, ldx, r, qrow, D, lane); });
 }
 
 // The last kernel of every bounded search (one workgroup per query).  gate / qflags: the exact fallback runs only for a flagged query of

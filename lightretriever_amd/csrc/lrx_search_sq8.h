@@ -1,8 +1,8 @@
 // liblrx search, part 8 -- 8-BIT SCALAR-QUANTISED inner-product index (faiss IndexScalarQuantizer(d, QT_8bit | QT_8bit_uniform,
 // METRIC_INNER_PRODUCT), range statistic RS_minmax), map: section I.
-// Part of the ONE translation unit lrx_search.hip (included at its end: it reuses SelShared, select_topk_sorted, bitonic_sort_desc,
-// merge_launch, k_pq_map_ids, align256 and lrx_cu_count).  Not a stand-alone header.  Contract and code layout: include/lrx.h
-// (lrx_sq8_ip_search), DESIGN.md §5.4.5.
+// Part of the ONE translation unit lrx_search.hip (included at its end, after lrx_search_codes.h: it reuses SelShared, select_topk_sorted and
+// rescore_band of the selection, lrx_cu_count, and the shared plan, checks and scan driver).  Needs no other index header.  Contract and
+// code layout: include/lrx.h (lrx_sq8_ip_search), DESIGN.md §5.4.5.
 //
 //     k_sq8_minmax          column min / max of a row range folded into a device [2, d] (integer atomics on the float's bits, NaN skipped)
 //     k_sq8_encode          fp32 rows -> tiled codes: t = (x - vmin) / vdiff clamped to [0, 1], code = (int)(255 t)
@@ -12,7 +12,7 @@
 //     k_sq8_scan            THE HOT PATH: one pass over the codes on the i8 MFMA (codes xor 0x80 = code - 128 as int8, exact i32 sums),
 //                           writes the [Q, ld] filter scores of a row chunk and their 128-row block maxima
 //     k_sq8_select_rescore  per query: top-k of the filter scores, every row within 2 eps of the k-th rescored from the codes in fp64,
-//                           the best k returned; a band larger than the list takes the streaming form (exact, counted as a fallback)
+//                           the best k returned (rescore_band; a band larger than the list takes its streaming form, counted as a fallback)
 #pragma once
 
 #define SQ8_BLK 128                     // rows per code block
@@ -294,12 +294,11 @@ __device__ __forceinline__ float sq8_row_dot(const uint8_t* __restrict__ codes, 
   return (float)acc;
 }
 
-// Selection + exact rescoring of one query over one row chunk (the structure of select_rescore_query, lrx_search_select.h, with the
-// query's own eps and the rows rescored from the 8-bit codes).  k rows have filter score >= kth, each of them has an exact score
-// >= kth - eps, so the exact k-th score is >= kth - eps and every row of the exact top-k has filter score >= kth - 2 eps: all rows at or
-// above that threshold (lowered by one more ulp for the rounding of the subtraction) are rescored and the best k of them returned.  More
-// than SEL_CAND band rows (duplicate clusters): the streaming form -- the score row walked in 2048-row windows, a running exact top in
-// LDS -- slow but exact for any band; counted in g_search_fallback_queries.  Row ids are chunk-local + id_base.
+// Selection + exact rescoring of one query over one row chunk: select_rescore_query (lrx_search_select.h) with the query's own eps and the
+// rows rescored from the 8-bit codes.  k rows have filter score >= kth, each of them has an exact score >= kth - eps, so the exact k-th score
+// is >= kth - eps and every row of the exact top-k has filter score >= kth - 2 eps: all rows at or above that threshold (lowered by one
+// more ulp for the rounding of the subtraction) are rescored and the best k of them returned (rescore_band; its streaming form is counted
+// in g_search_fallback_queries).  Row ids are chunk-local + id_base.
 __global__ void __launch_bounds__(SEL_THREADS)
 k_sq8_select_rescore(const float* __restrict__ scores, int64_t ld, int64_t N, int k, int64_t id_base, const float* __restrict__ blkmax, int nblk,
                      int nblk_ld, const uint8_t* __restrict__ codes, const float* __restrict__ trained, int D, int uniform,
@@ -308,7 +307,7 @@ k_sq8_select_rescore(const float* __restrict__ scores, int64_t ld, int64_t N, in
   const float* row = scores + (int64_t)blockIdx.x * ld;
   float* os = out_scores + (int64_t)blockIdx.x * k;
   int64_t* oi = out_ids + (int64_t)blockIdx.x * k;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int keff = (int)(N < (int64_t)k ? N : (int64_t)k);
   for (int i = keff + tid; i < k; i += SEL_THREADS) { os[i] = -FLT_MAX; oi[i] = -1; }
   if (keff == 0) return;
@@ -318,130 +317,30 @@ k_sq8_select_rescore(const float* __restrict__ scores, int64_t ld, int64_t N, in
   const float kth = key2f((uint32_t)(sh.cand[keff - 1] >> 32));
   float thr = kth - 2.0f * qeps[blockIdx.x];
   thr -= fabsf(thr) * 1.1920929e-7f;                         // (a non-finite query gives a NaN threshold: the filter selection stands)
-  __syncthreads();
-  unsigned long long* s_c = sh.cand;
-  auto rescore = [&](unsigned long long* list, int n) {      // exact scores of list[0..n) in place: entry c is read and written by the same half-wave
-    for (int c0 = wave * 2; c0 < n; c0 += 32) {
-      const int c = min(c0 + (lane >> 5), n - 1);
-      int64_t r = sel_row(list[c]);
-      r = r < 0 ? 0 : (r >= N ? N - 1 : r);
-      const float sc = sq8_row_dot(codes, r, qrow, trained, D, uniform, lane);
-      if ((lane & 31) == 0 && c0 + (lane >> 5) < n) list[c] = sel_pack(f2key(sc), r);
-    }
-  };
-  unsigned int* blist = (unsigned int*)sh.eqs;               // 2 * SEL_EQCAP entries
-  bool overflow = false;
-  if (!(thr == thr)) {
-    if (tid == 0) sh.ngt = (unsigned int)keff;
-  } else if (N <= SEL_CAND) {
-    if (tid == 0) sh.ngt = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < N; i += SEL_THREADS) {
-      const float v = row[i];
-      if (v >= thr) s_c[atomicAdd(&sh.ngt, 1u)] = sel_pack(f2key(v), i);
-    }
-  } else {
-    if (tid == 0) { sh.ngt = 0; sh.neq = 0; }
-    __syncthreads();
-    for (int b = tid; b < nblk; b += SEL_THREADS)
-      if (bm[b] >= thr) {
-        const unsigned int p = atomicAdd(&sh.neq, 1u);
-        if (p < 2 * SEL_EQCAP) blist[p] = (unsigned int)b;
-      }
-    __syncthreads();
-    const unsigned int nb = sh.neq;
-    overflow = nb > 2 * SEL_EQCAP;
-    if (!overflow) {
-      for (unsigned int idx = tid; idx < nb * SQ8_BLK; idx += SEL_THREADS) {
-        const int64_t i = (int64_t)blist[idx >> 7] * SQ8_BLK + (idx & (SQ8_BLK - 1));
-        if (i < N) {
-          const float v = row[i];
-          if (v >= thr) {
-            const unsigned int p = atomicAdd(&sh.ngt, 1u);
-            if (p < SEL_CAND) s_c[p] = sel_pack(f2key(v), i);
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  overflow = overflow || sh.ngt > SEL_CAND;
-  __syncthreads();
-  if (!overflow) {
-    const int n = (int)sh.ngt;                               // >= keff: the keff selected rows are among them
-    rescore(s_c, n);
-    __syncthreads();
-    int P = 1;
-    while (P < n) P <<= 1;
-    for (int i = n + tid; i < P; i += SEL_THREADS) s_c[i] = 0ull;
-    bitonic_sort_desc(s_c, P);
-  } else {
-    if (tid == 0) atomicAdd(&g_search_fallback_queries, 1u);
-    unsigned long long* best = s_c;
-    unsigned long long* chunk = s_c + SEL_MAXK;
-    for (int i = tid; i < SEL_MAXK; i += SEL_THREADS) best[i] = 0ull;
-    for (int64_t w0 = 0; w0 < N; w0 += SEL_MAXK) {
-      if (tid == 0) sh.ngt = 0;
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < SEL_MAXK / SEL_THREADS; ++j) {
-        const int64_t i = w0 + tid + j * SEL_THREADS;
-        if (i < N) {
-          const float v = row[i];
-          if (v >= thr) chunk[atomicAdd(&sh.ngt, 1u)] = sel_pack(f2key(v), i);
-        }
-      }
-      __syncthreads();
-      const int n = (int)sh.ngt;
-      if (n == 0) continue;
-      rescore(chunk, n);
-      __syncthreads();
-      for (int i = n + tid; i < SEL_MAXK; i += SEL_THREADS) chunk[i] = 0ull;
-      bitonic_sort_desc(best, 2 * SEL_MAXK);                 // merge: the best SEL_MAXK (>= keff) of best + chunk stay in front
-      __syncthreads();
-    }
-  }
-  for (int i = tid; i < keff; i += SEL_THREADS) {
-    const unsigned long long c = s_c[i];
-    os[i] = key2f((uint32_t)(c >> 32));
-    oi[i] = id_base + sel_row(c);
-  }
+  const bool streamed = rescore_band(row, N, keff, thr, bm, nblk, id_base, os, oi, sh,
+                                     [&](int64_t r) { return sq8_row_dot(codes, r, qrow, trained, D, uniform, lane); });
+  if (streamed && tid == 0) atomicAdd(&g_search_fallback_queries, 1u);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct SQ8Plan {
-  int64_t rc, ld;         // rows per score matrix, its row stride (whole 128-row blocks)
-  int nblk_ld, qc;        // block maxima stride, queries per chunk
-  bool merge;
-  size_t dig_off, scale_off, bias_off, eps_off, sc_off, bm_off, part_s_off, part_i_off, total;
-};
-
 static int sq8_scan_tiles(int nq) { const int t = (int)lrx_cdiv(nq, 16); return t <= 1 ? 1 : (t <= 2 ? 2 : (t <= 4 ? 4 : 8)); }   // k_sq8_scan<QT>
 
-static SQ8Plan sq8_plan(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k) {
-  SQ8Plan p;
-  p.rc = n_rows < SQ8_ROW_CHUNK ? (n_rows > 0 ? n_rows : 1) : SQ8_ROW_CHUNK;
-  p.ld = lrx_cdiv(p.rc, SQ8_BLK) * SQ8_BLK;
-  p.nblk_ld = ((int)(p.ld / SQ8_BLK) + 3) & ~3;
-  p.merge = n_rows > SQ8_ROW_CHUNK;
-  const int64_t per_q = p.ld * 4 + (int64_t)p.nblk_ld * 4;
-  int64_t qc = SQ8_MATRIX_BYTES / per_q;
-  const int64_t nq = n_queries > 0 ? n_queries : 1;
-  qc = qc > SQ8_QCHUNK ? SQ8_QCHUNK : qc;
-  p.qc = (int)(qc < 1 ? 1 : (qc > nq ? nq : qc));
-  const size_t q = (size_t)p.qc, qpad = (size_t)sq8_scan_tiles(p.qc) * 16;   // digit tiles of every query tile the scan template reads
-  p.dig_off = 0;
-  p.scale_off = align256(qpad * (size_t)dim * 2);
-  p.bias_off = p.scale_off + align256(q * 8);
-  p.eps_off = p.bias_off + align256(q * 8);
-  p.sc_off = p.eps_off + align256(q * 4);
-  p.bm_off = p.sc_off + align256(q * (size_t)p.ld * 4);
-  p.part_s_off = p.bm_off + align256(q * (size_t)p.nblk_ld * 4);
-  p.part_i_off = p.part_s_off + (p.merge ? align256(2 * q * k * 4) : 0);
-  p.total = p.part_i_off + (p.merge ? align256(2 * q * k * 8) : 0);
-  return p;
+// the leading regions of the workspace: what k_sq8_prep writes for a chunk of qc queries
+struct SQ8Lead { size_t scale_off, bias_off, eps_off, total; };   // (the digit tiles are at 0)
+static SQ8Lead sq8_lead(int qc, int32_t dim) {
+  const size_t q = (size_t)qc, qpad = (size_t)sq8_scan_tiles(qc) * 16;   // digit tiles of every query tile the scan template reads
+  SQ8Lead l;
+  l.scale_off = align256(qpad * (size_t)dim * 2);
+  l.bias_off = l.scale_off + align256(q * 8);
+  l.eps_off = l.bias_off + align256(q * 8);
+  l.total = l.eps_off + align256(q * 4);
+  return l;
+}
+
+static ScanPlan sq8_plan(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k) {
+  return scan_plan(n_rows, n_queries, k, SQ8_ROW_CHUNK, SQ8_BLK, SQ8_MATRIX_BYTES, SQ8_QCHUNK, [&](int qc) { return sq8_lead(qc, dim).total; });
 }
 
 static bool sq8_qtype_ok(int32_t qtype) { return qtype == SQ8_QT_8BIT || qtype == SQ8_QT_8BIT_UNIFORM; }
@@ -496,73 +395,53 @@ extern "C" int lrx_sq8_decode_rows(const void* codes, int64_t row0, int64_t n_ro
 }
 
 #define SQ8_SCAN(QT_)                                                                                                                           \
-  hipLaunchKernelGGL(k_sq8_scan<QT_>, dim3((unsigned)gx), dim3(256), 0, s, cchunk, nr, (int)dim, (const int8_t*)dig, (const double*)qscale, \
+  hipLaunchKernelGGL(k_sq8_scan<QT_>, dim3((unsigned)gx), dim3(256), 0, s, cchunk(r0), nr, (int)dim, (const int8_t*)dig, (const double*)qscale, \
                      (const double*)qbias, nq, sc, p.ld, bm, p.nblk_ld)
 
 extern "C" int lrx_sq8_ip_search(const void* codes, int64_t n_rows, const float* trained, int32_t dim, int32_t qtype, const float* q, int32_t n_queries,
                                  int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                  size_t workspace_bytes, int32_t flags, void* stream) {
   (void)flags;
-  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK, "sq8_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32) - 1, "sq8_ip_search: shard rows=%lld out of range", (long long)n_rows);
+  int rc = codes_check_topk("sq8_ip_search", k, n_rows);
+  if (rc != LRX_OK) return rc;
   SQ8_CHECK_DIM("sq8_ip_search", dim, qtype);
   if (n_queries <= 0) return LRX_OK;
-  const SQ8Plan p = sq8_plan(n_rows, dim, n_queries, k);
-  if (workspace_bytes < p.total) {
-    lrx_set_error("sq8_ip_search: workspace %zu B < required %zu B", workspace_bytes, p.total);
-    return LRX_ERR_WORKSPACE;
-  }
+  const ScanPlan p = sq8_plan(n_rows, dim, n_queries, k);
+  if ((rc = codes_check_workspace("sq8_ip_search", workspace_bytes, p.total)) != LRX_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  int8_t* dig = (int8_t*)(ws + p.dig_off);
-  double* qscale = (double*)(ws + p.scale_off);
-  double* qbias = (double*)(ws + p.bias_off);
-  float* qeps = (float*)(ws + p.eps_off);
-  float* sc = (float*)(ws + p.sc_off);
-  float* bm = (float*)(ws + p.bm_off);
-  float* part_s = (float*)(ws + p.part_s_off);
-  int64_t* part_i = (int64_t*)(ws + p.part_i_off);
+  const SQ8Lead l = sq8_lead(p.qc, dim);
+  int8_t* dig = (int8_t*)ws;
+  double* qscale = (double*)(ws + l.scale_off);
+  double* qbias = (double*)(ws + l.bias_off);
+  float* qeps = (float*)(ws + l.eps_off);
   const int uniform = qtype == SQ8_QT_8BIT_UNIFORM ? 1 : 0;
   const int ncu = lrx_cu_count();
-  for (int32_t q0 = 0; q0 < n_queries; q0 += p.qc) {
-    const int nq = n_queries - q0 < p.qc ? n_queries - q0 : p.qc;
-    const int qtiles = sq8_scan_tiles(nq);
-    const float* qc = q + (int64_t)q0 * dim;
-    float* os = out_scores + (int64_t)q0 * k;
-    int64_t* oi = out_ids + (int64_t)q0 * k;
-    hipLaunchKernelGGL(k_sq8_prep, dim3(qtiles * 16), dim3(256), 0, s, qc, nq, trained, (int)dim, uniform, dig, qscale, qbias, qeps);
-    LRX_LAUNCH_CHECK();
-    int64_t r0 = 0;
-    do {
-      const int64_t nr = n_rows - r0 < p.rc ? n_rows - r0 : p.rc;
-      const int nblk = (int)lrx_cdiv(nr, SQ8_BLK);
-      const uint8_t* cchunk = (const uint8_t*)codes + r0 * (int64_t)dim;     // (r0 is a multiple of 128)
-      if (nr > 0) {
+  auto cchunk = [&](int64_t r0) { return (const uint8_t*)codes + r0 * (int64_t)dim; };   // (r0 is a multiple of 128)
+  return scan_search(
+      p, workspace, n_rows, n_queries, k, id_base, out_scores, out_ids, row_map, stream,
+      [&](int32_t q0, int nq) {
+        hipLaunchKernelGGL(k_sq8_prep, dim3(sq8_scan_tiles(nq) * 16), dim3(256), 0, s, q + (int64_t)q0 * dim, nq, trained, (int)dim, uniform, dig, qscale,
+                           qbias, qeps);
+        LRX_LAUNCH_CHECK();
+        return LRX_OK;
+      },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) {
+        const int64_t nblk = lrx_cdiv(nr, SQ8_BLK);
         const int64_t gx = nblk < 8 * (int64_t)ncu ? nblk : 8 * (int64_t)ncu;
-        switch (qtiles) {
+        switch (sq8_scan_tiles(nq)) {
           case 1: SQ8_SCAN(1); break;
           case 2: SQ8_SCAN(2); break;
           case 4: SQ8_SCAN(4); break;
           default: SQ8_SCAN(8); break;
         }
         LRX_LAUNCH_CHECK();
-      }
-      const bool into_part = r0 > 0;
-      hipLaunchKernelGGL(k_sq8_select_rescore, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)sc, p.ld, nr, k, r0, (const float*)bm, nblk, p.nblk_ld,
-                         cchunk, trained, (int)dim, uniform, qc, (const float*)qeps, into_part ? part_s + (int64_t)nq * k : os,
-                         into_part ? part_i + (int64_t)nq * k : oi);
-      LRX_LAUNCH_CHECK();
-      if (into_part) {
-        LRX_HIP(hipMemcpyAsync(part_s, os, (size_t)nq * k * 4, hipMemcpyDeviceToDevice, s));
-        LRX_HIP(hipMemcpyAsync(part_i, oi, (size_t)nq * k * 8, hipMemcpyDeviceToDevice, s));
-        const int rc = merge_launch(part_s, part_i, nullptr, 2, nq, k, os, oi, stream);
-        if (rc != LRX_OK) return rc;
-      }
-      r0 += nr;
-    } while (r0 < n_rows);
-    const int64_t n_out = (int64_t)nq * k;
-    hipLaunchKernelGGL(k_pq_map_ids, dim3((unsigned)lrx_cdiv(n_out, 256)), dim3(256), 0, s, oi, n_out, id_base, row_map);
-    LRX_LAUNCH_CHECK();
-  }
-  return LRX_OK;
+        return LRX_OK;
+      },
+      [&](int32_t q0, int64_t r0, int64_t nr, int nq, const float* sc, const float* bm, float* os, int64_t* oi) {
+        hipLaunchKernelGGL(k_sq8_select_rescore, dim3(nq), dim3(SEL_THREADS), 0, s, sc, p.ld, nr, k, r0, bm, (int)lrx_cdiv(nr, SQ8_BLK), p.nblk_ld,
+                           cchunk(r0), trained, (int)dim, uniform, q + (int64_t)q0 * dim, (const float*)qeps, os, oi);
+        LRX_LAUNCH_CHECK();
+        return LRX_OK;
+      });
 }

@@ -53,6 +53,11 @@ def _grow_blocks(buf: torch.Tensor, n_rows: int, width: int, keep_rows: int, zer
     return new
 
 
+def _grown(have: int, need: int) -> int:
+    """Rows to reserve when `need` rows no longer fit `have`: at least half as many again, so that repeated appends copy O(n) rows in all."""
+    return max(need, int(have * 1.5) + 1)
+
+
 def _workspace(slots: dict, key, need: int, device, capture_error: Optional[str] = None) -> torch.Tensor:
     """slots[key] (a uint8 workspace), regrown to `need` bytes when smaller.  The old block is dropped before the new one is allocated, so
     the caching allocator can reuse its memory.  capture_error: raise it instead of allocating under HIP-graph capture."""
@@ -314,7 +319,7 @@ class FlatIPIndex(_TiledIPIndex):
         """Rows [ntotal, ntotal+n) of the shard as a writable view (the encoder writes embeddings straight into it, together with
         their shadow rows and the bounds); call commit(n) afterwards."""
         if self.ntotal + n_rows > self._x.shape[0]:
-            self.reserve(max(self.ntotal + n_rows, int(self._x.shape[0] * 1.5) + 1))
+            self.reserve(_grown(self._x.shape[0], self.ntotal + n_rows))
         self._ensure_shadow()
         # whoever receives these rows may write them with anything: an earlier encoder write into them no longer vouches for
         # their shadow / bounds (commit() maintains whatever is not re-recorded by shard_sink() after this point)
@@ -494,7 +499,7 @@ class SQFp16Index(_TiledIPIndex):
         """A transient fp32 staging view for rows [ntotal, ntotal + n): write them (the encoder writes codes and bounds itself through
         shard_of), then commit(n)."""
         if self.ntotal + n_rows > self.capacity:
-            self.reserve(max(self.ntotal + n_rows, int(self.capacity * 1.5) + 1))
+            self.reserve(_grown(self.capacity, self.ntotal + n_rows))
         if self._x.shape[0] < n_rows:
             self._set_staging(0)
             self._set_staging(n_rows)
@@ -527,7 +532,7 @@ class SQFp16Index(_TiledIPIndex):
         x = _as_rows(x, self.d, "add: ")
         n = x.shape[0]
         if self.ntotal + n > self.capacity:
-            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+            self.reserve(_grown(self.capacity, self.ntotal + n))
         x = x.to(device=self.device, dtype=torch.float32)
         if x.stride(1) != 1 or (n > 1 and x.stride(0) % 4):
             x = x.contiguous()
@@ -590,39 +595,24 @@ class SQFp16Index(_TiledIPIndex):
         raise NotImplementedError("SQFp16Index.range_search is not served yet (a follow-up: the range search's list path over the codes)")
 
 
-class PQIndex:
-    """Product-quantised inner-product shard: the faiss IndexPQ(d, M, nbits=8, METRIC_INNER_PRODUCT) surface (train / is_trained / add /
-    search / reset / ntotal / reconstruct_n / save / load), backed by lrx_pq_ip_search.  Resident: M bytes per row (the codes, in the
-    blocked layout of include/lrx.h) + the centroids [M, 256, d / M] fp32.  Scores are the fp32 sums of the query's lookup table over the
-    row's codes in ascending m; exact top-k under that score with the flat index's tie and padding rules (DESIGN §5.4.3).
-    Training: Lloyd k-means per sub-space (256 centroids, 25 iterations, at most 256 x 256 sampled rows, fixed seed), assignments by the
-    encoding kernel, deterministic fp64 centroid sums (sorted by code, segmented sums), faiss's split of empty clusters.  The same input
-    and seed give the same centroids; they are not faiss's (its RNG differs).
-    Rows enter through add() or through append_slot(n) / commit(n): the slot is a transient fp32 staging view; commit() trains the index
-    if it is untrained, encodes the rows and releases the staging.  Search: one library call (it walks the queries in chunks that keep
-    the score matrix under 1 GiB), workspace kept by the index.  NOT thread-safe."""
+class _CodeIndex:
+    """What PQIndex, SQ8Index and BinaryFlatIndex share: `code_size` bytes of codes per row (faiss's name), stored as whole 128-row blocks of
+    `_width` bytes per row in `_codes` (the layouts of include/lrx.h); reserve / capacity and the grow policy; the transient fp32 staging view
+    of append_slot(n) / commit(n) -- commit() trains an untrained index on the staged rows, add()s them and releases the staging; reset()
+    (drops the rows, keeps the training); the search prologue and the search workspace `_ws`.  A subclass checks its arguments BEFORE it
+    calls this constructor (no GPU is needed to refuse them) and keeps what is its own: training, _encode_into (or add), the decode call of
+    reconstruct_n, the layout permutation (_layout), persistence and the library calls of search."""
+    MAX_K = 2048
+    is_trained = True          # (faiss: an index that needs no training is trained; PQIndex / SQ8Index start untrained)
+    _capture_ws_error = None   # SQ8Index: the message that refuses to allocate the search workspace under HIP-graph capture
 
-    KSUB = 256
-    NITER = 25
-    MAX_POINTS_PER_CENTROID = 256
-    SEED = 1234
-
-    def __init__(self, d: int, M: int = 96, nbits: int = 8, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
-        if nbits != 8:
-            raise NotImplementedError(f"PQIndex: nbits={nbits} is not served (only 8)")
-        if M <= 0 or d % M != 0:
-            raise ValueError(f"PQIndex: d={d} is not a multiple of M={M}")
-        if d // M > 64:
-            raise NotImplementedError(f"PQIndex: sub-space dimension d / M = {d // M} > 64 is not served")
+    def __init__(self, d: int, code_size: int, width: int, capacity: int, device: Optional[torch.device], id_base: int):
         _lib.require_gpu()
         self.lib = _lib.lib()
-        self.d, self.M, self.nbits, self.dsub = d, M, nbits, d // M
-        self.Mp = -(-M // 16) * 16
+        self.d, self.code_size, self._width = d, code_size, width
         self.device = device or torch.device("cuda", torch.cuda.current_device())
         self.id_base = id_base
         self.ntotal = 0
-        self.is_trained = False
-        self.centroids = torch.zeros(M, self.KSUB, self.dsub, dtype=torch.float32, device=self.device)
         self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
         self._stage = None
         self._ws = None
@@ -631,79 +621,47 @@ class PQIndex:
     # -- storage -------------------------------------------------------------------------------------------------
     @property
     def capacity(self) -> int:
-        return self._codes.numel() // self.Mp
+        return self._codes.numel() // self._width
 
     def reserve(self, n_rows: int):
-        self._codes = _grow_blocks(self._codes, n_rows, self.Mp, self.ntotal, zero=True)
+        self._codes = _grow_blocks(self._codes, n_rows, self._width, self.ntotal, zero=True)
 
-    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, centroids: torch.Tensor):
-        for s in range(0, x.shape[0], 262144):
-            xs = x[s:s + 262144]
-            _lib.check(self.lib.lrx_pq_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(centroids), self.d, self.M, _lib.ptr(codes),
-                                              row0 + s, _lib.current_stream()))
+    def _make_room(self, n: int):
+        if self.ntotal + n > self.capacity:
+            self.reserve(_grown(self.capacity, self.ntotal + n))
 
     def _rows(self, x) -> torch.Tensor:
         x = _as_rows(x, self.d).to(device=self.device, dtype=torch.float32)
         return x.contiguous() if x.stride(1) != 1 else x
 
+    def _scratch_blocks(self, n: int) -> torch.Tensor:
+        return torch.zeros(-(-n // 128) * 128 * self._width, dtype=torch.uint8, device=self.device)
+
     def blocked_to_rows(self, blocked: torch.Tensor, n: int) -> torch.Tensor:
-        """Blocked codes (include/lrx.h) -> row-major uint8 [n, M]."""
+        """Codes in the stored layout (include/lrx.h) -> row-major uint8 [n, code_size]."""
+        shape, perm = self._layout()
         nb = -(-n // 128)
-        return blocked[:nb * 128 * self.Mp].view(nb, self.Mp // 16, 128, 16).permute(0, 2, 1, 3).reshape(nb * 128, self.Mp)[:n, :self.M]
+        return blocked[:nb * 128 * self._width].view(nb, *shape).permute(0, *perm).reshape(nb * 128, self._width)[:n, :self.code_size]
 
     def rows_to_blocked(self, codes: torch.Tensor) -> torch.Tensor:
+        shape, perm = self._layout()
         n = codes.shape[0]
         nb = -(-n // 128)
-        buf = torch.zeros(nb * 128, self.Mp, dtype=torch.uint8, device=self.device)
-        buf[:n, :self.M] = codes.to(self.device)
-        return buf.view(nb, 128, self.Mp // 16, 16).permute(0, 2, 1, 3).contiguous().view(-1)
-
-    def encode(self, x, centroids: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """faiss sa_encode: row-major uint8 [n, M] codes of x under `centroids` (default: this index's)."""
-        x = self._rows(x)
-        c = (self.centroids if centroids is None else centroids).to(self.device, torch.float32).contiguous()
-        blocked = torch.zeros(-(-x.shape[0] // 128) * 128 * self.Mp, dtype=torch.uint8, device=self.device)
-        if x.shape[0]:
-            self._encode_into(x, blocked, 0, c)
-        return self.blocked_to_rows(blocked, x.shape[0])
-
-    # -- training ------------------------------------------------------------------------------------------------
-    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
-        """Lloyd k-means per sub-space (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
-        x = self._rows(x)
-        n = x.shape[0]
-        if n < self.KSUB:
-            raise ValueError(f"PQIndex.train: {n} training rows < {self.KSUB} centroids")
-        niter = self.NITER if niter is None else niter
-        rng = np.random.default_rng(self.SEED if seed is None else seed)
-        max_pts = self.KSUB * self.MAX_POINTS_PER_CENTROID
-        if n > max_pts:
-            x = x[torch.from_numpy(np.sort(rng.permutation(n)[:max_pts])).to(self.device)]
-            n = max_pts
-        M, K, ds = self.M, self.KSUB, self.dsub
-        xs = x.view(n, M, ds)
-        init = np.stack([rng.permutation(n)[:K] for _ in range(M)])                       # [M, K] distinct rows per sub-space
-        cent = xs[torch.from_numpy(init).to(self.device), torch.arange(M, device=self.device)[:, None]].contiguous()   # [M, K, ds]
-        x_t = xs.permute(1, 0, 2).double()                                                 # [M, n, ds]
-        blocked = torch.zeros(-(-n // 128) * 128 * self.Mp, dtype=torch.uint8, device=self.device)
-        for _ in range(niter):
-            self._encode_into(x, blocked, 0, cent)
-            codes = self.blocked_to_rows(blocked, n).t().long()                            # [M, n]
-            cent = _pq_update(x_t, codes, K, cent, rng)
-        self.centroids = cent.float().contiguous()
-        self.is_trained = True
+        buf = torch.zeros(nb * 128, self._width, dtype=torch.uint8, device=self.device)
+        buf[:n, :self.code_size] = codes.to(self.device)
+        back = [perm.index(a) + 1 for a in range(1, len(perm) + 1)]                       # the inverse permutation
+        return buf.view(nb, *(shape[p - 1] for p in perm)).permute(0, *back).contiguous().view(-1)
 
     # -- rows ------------------------------------------------------------------------------------------------------
     def add(self, x):
         """faiss add(x f32[n, d]): encode into the codes (raises before train(), as faiss does)."""
         if not self.is_trained:
-            raise RuntimeError("PQIndex.add: the index is not trained (call train() first)")
+            raise RuntimeError(f"{type(self).__name__}.add: the index is not trained (call train() first)")
         x = self._rows(x)
         n = x.shape[0]
-        if self.ntotal + n > self.capacity:
-            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        self._make_room(n)
         if n:
-            self._encode_into(x, self._codes, self.ntotal, self.centroids)
+            self._encode_into(x, self._codes, self.ntotal)
         self.ntotal += n
 
     def append_slot(self, n_rows: int) -> torch.Tensor:
@@ -728,6 +686,109 @@ class PQIndex:
         self.ntotal = 0
         self._stage = None
 
+    def codes(self) -> torch.Tensor:
+        """The codes as a row-major uint8 [ntotal, code_size] tensor (a copy: the stored layout is blocked)."""
+        return self.blocked_to_rows(self._codes, self.ntotal).contiguous()
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
+    # -- search --------------------------------------------------------------------------------------------------
+    def _begin_search(self, q, k: int, row_map: Optional[torch.Tensor], d_dtype=torch.float32, k_error: Optional[str] = None):
+        """The checks every search starts with (k_error: the subclass's own complaint about k; otherwise 1 <= k <= MAX_K) -> (q fp32 [Q, d] on
+        the device, D [Q, k] of d_dtype, I int64 [Q, k]); with no queries the caller returns (D, I) as they are."""
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        if k_error is None and not 1 <= k <= self.MAX_K:
+            k_error = f"search: k={k} out of range (1..{self.MAX_K})"
+        if k_error is not None:
+            raise ValueError(k_error)
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        D = torch.empty(q.shape[0], k, dtype=d_dtype, device=self.device)
+        I = torch.empty(q.shape[0], k, dtype=torch.int64, device=self.device)
+        return q, D, I
+
+    def _search_workspace(self, need: int) -> torch.Tensor:
+        return _workspace(vars(self), "_ws", int(need), self.device, self._capture_ws_error)
+
+
+class PQIndex(_CodeIndex):
+    """Product-quantised inner-product shard: the faiss IndexPQ(d, M, nbits=8, METRIC_INNER_PRODUCT) surface (train / is_trained / add /
+    search / reset / ntotal / reconstruct_n / save / load), backed by lrx_pq_ip_search.  Resident: M bytes per row (the codes, in the
+    blocked layout of include/lrx.h) + the centroids [M, 256, d / M] fp32.  Scores are the fp32 sums of the query's lookup table over the
+    row's codes in ascending m; exact top-k under that score with the flat index's tie and padding rules (DESIGN §5.4.3).
+    Training: Lloyd k-means per sub-space (256 centroids, 25 iterations, at most 256 x 256 sampled rows, fixed seed), assignments by the
+    encoding kernel, deterministic fp64 centroid sums (sorted by code, segmented sums), faiss's split of empty clusters.  The same input
+    and seed give the same centroids; they are not faiss's (its RNG differs).
+    Rows enter through add() or through append_slot(n) / commit(n): the slot is a transient fp32 staging view; commit() trains the index
+    if it is untrained, encodes the rows and releases the staging.  Search: one library call (it walks the queries in chunks that keep
+    the score matrix under 1 GiB), workspace kept by the index.  NOT thread-safe."""
+
+    KSUB = 256
+    NITER = 25
+    MAX_POINTS_PER_CENTROID = 256
+    SEED = 1234
+
+    def __init__(self, d: int, M: int = 96, nbits: int = 8, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        if nbits != 8:
+            raise NotImplementedError(f"PQIndex: nbits={nbits} is not served (only 8)")
+        if M <= 0 or d % M != 0:
+            raise ValueError(f"PQIndex: d={d} is not a multiple of M={M}")
+        if d // M > 64:
+            raise NotImplementedError(f"PQIndex: sub-space dimension d / M = {d // M} > 64 is not served")
+        self.M, self.nbits, self.dsub = M, nbits, d // M
+        self.Mp = -(-M // 16) * 16
+        super().__init__(d, M, self.Mp, capacity, device, id_base)
+        self.is_trained = False
+        self.centroids = torch.zeros(M, self.KSUB, self.dsub, dtype=torch.float32, device=self.device)
+
+    def _layout(self):
+        return (self.Mp // 16, 128, 16), (2, 1, 3)       # a block: [16-sub-space group][row][byte] -> [row][group][byte]
+
+    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, centroids: Optional[torch.Tensor] = None):
+        centroids = self.centroids if centroids is None else centroids
+        for s in range(0, x.shape[0], 262144):
+            xs = x[s:s + 262144]
+            _lib.check(self.lib.lrx_pq_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(centroids), self.d, self.M, _lib.ptr(codes),
+                                              row0 + s, _lib.current_stream()))
+
+    def encode(self, x, centroids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """faiss sa_encode: row-major uint8 [n, M] codes of x under `centroids` (default: this index's)."""
+        x = self._rows(x)
+        c = (self.centroids if centroids is None else centroids).to(self.device, torch.float32).contiguous()
+        blocked = self._scratch_blocks(x.shape[0])
+        if x.shape[0]:
+            self._encode_into(x, blocked, 0, c)
+        return self.blocked_to_rows(blocked, x.shape[0])
+
+    # -- training ------------------------------------------------------------------------------------------------
+    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
+        """Lloyd k-means per sub-space (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
+        x = self._rows(x)
+        n = x.shape[0]
+        if n < self.KSUB:
+            raise ValueError(f"PQIndex.train: {n} training rows < {self.KSUB} centroids")
+        niter = self.NITER if niter is None else niter
+        rng = np.random.default_rng(self.SEED if seed is None else seed)
+        max_pts = self.KSUB * self.MAX_POINTS_PER_CENTROID
+        if n > max_pts:
+            x = x[torch.from_numpy(np.sort(rng.permutation(n)[:max_pts])).to(self.device)]
+            n = max_pts
+        M, K, ds = self.M, self.KSUB, self.dsub
+        xs = x.view(n, M, ds)
+        init = np.stack([rng.permutation(n)[:K] for _ in range(M)])                       # [M, K] distinct rows per sub-space
+        cent = xs[torch.from_numpy(init).to(self.device), torch.arange(M, device=self.device)[:, None]].contiguous()   # [M, K, ds]
+        x_t = xs.permute(1, 0, 2).double()                                                 # [M, n, ds]
+        blocked = self._scratch_blocks(n)
+        for _ in range(niter):
+            self._encode_into(x, blocked, 0, cent)
+            codes = self.blocked_to_rows(blocked, n).t().long()                            # [M, n]
+            cent = _pq_update(x_t, codes, K, cent, rng)
+        self.centroids = cent.float().contiguous()
+        self.is_trained = True
+
+    # -- rows ------------------------------------------------------------------------------------------------------
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """Rows [i0, i0 + n) decoded (centroid of each code) to fp32, device tensor [n, d]."""
         _check_range(i0, n, self.ntotal)
@@ -736,10 +797,6 @@ class PQIndex:
             _lib.check(self.lib.lrx_pq_decode_rows(_lib.ptr(self._codes), i0, n, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(out), self.d,
                                                    _lib.current_stream()))
         return out
-
-    def codes(self) -> torch.Tensor:
-        """The codes as a row-major uint8 [ntotal, M] tensor (a copy: the stored layout is blocked)."""
-        return self.blocked_to_rows(self._codes, self.ntotal).contiguous()
 
     def set_contents(self, centroids, codes):
         """Replace the centroids ([M, 256, d / M]) and the rows (row-major uint8 [n, M] codes): load() and tests."""
@@ -768,32 +825,22 @@ class PQIndex:
         idx.is_trained = trained
         return idx
 
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
-
     # -- search --------------------------------------------------------------------------------------------------
     def search(self, q, k: int, row_map: Optional[torch.Tensor] = None):
         """faiss search -> (D f32[Q,k], I i64[Q,k]) device tensors: score descending, ties to the lower row, (-FLT_MAX, -1) padding when
         k > ntotal.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries) when given."""
-        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
-        if not 1 <= k <= 2048:
-            raise ValueError(f"search: k={k} out of range (1..2048)")
-        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
-            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        q, D, I = self._begin_search(q, k, row_map)
         Q = q.shape[0]
-        D = torch.empty(Q, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
         if Q == 0:
             return D, I
-        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_pq_ip_workspace_bytes(self.ntotal, self.d, self.M, Q, k)), self.device)
+        ws = self._search_workspace(self.lib.lrx_pq_ip_workspace_bytes(self.ntotal, self.d, self.M, Q, k))
         _lib.check(self.lib.lrx_pq_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.centroids), self.d, self.M, _lib.ptr(q), Q, k,
                                              int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
                                              _lib.current_stream()))
         return D, I
 
 
-class SQ8Index:
+class SQ8Index(_CodeIndex):
     """8-bit scalar-quantised inner-product shard: the faiss IndexScalarQuantizer(d, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT)
     surface (train / is_trained / add / search / reset / ntotal / reconstruct_n / save / load), backed by lrx_sq8_ip_search.  Resident:
     ntotal * d bytes of codes (whole 128-row blocks, the tiled layout of include/lrx.h) + `trained` (vmin ++ vdiff: 8 d bytes for QT_8bit,
@@ -807,51 +854,24 @@ class SQ8Index:
     <= 128), workspace kept by the index; under a HIP-graph capture the workspace must already exist.  NOT thread-safe."""
 
     QTYPES = {"QT_8bit": 0, "QT_8bit_uniform": 2}     # faiss ScalarQuantizer::QuantizerType
+    _capture_ws_error = ("SQ8Index.search under graph capture: the search workspace must exist before the capture starts -- run one eager "
+                         "search with the same number of queries and k first")
 
     def __init__(self, d: int, qtype: str = "QT_8bit", capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
         if qtype not in self.QTYPES:
             raise NotImplementedError(f"SQ8Index: qtype={qtype!r} is not served (only {sorted(self.QTYPES)})")
         if d <= 0 or d % 64 != 0:
             raise ValueError(f"SQ8Index: d={d} must be a multiple of 64")
-        _lib.require_gpu()
-        self.lib = _lib.lib()
-        self.d, self.qtype, self._qt = d, qtype, self.QTYPES[qtype]
+        super().__init__(d, d, d, capacity, device, id_base)
+        self.qtype, self._qt = qtype, self.QTYPES[qtype]
         self.uniform = self._qt == 2
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.id_base = id_base
-        self.ntotal = 0
         self.is_trained = False
         self.trained = torch.zeros(2 if self.uniform else 2 * d, dtype=torch.float32, device=self.device)
         self._minmax = None                            # [2, d] running column min / max of the training pieces
-        self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self._stage = None
-        self._ws = None
-        self.reserve(capacity)
 
-    # -- storage -------------------------------------------------------------------------------------------------
-    @property
-    def capacity(self) -> int:
-        return self._codes.numel() // self.d
-
-    def reserve(self, n_rows: int):
-        self._codes = _grow_blocks(self._codes, n_rows, self.d, self.ntotal, zero=True)
-
-    def _rows(self, x) -> torch.Tensor:
-        x = _as_rows(x, self.d).to(device=self.device, dtype=torch.float32)
-        return x.contiguous() if x.stride(1) != 1 else x
-
-    def blocked_to_rows(self, blocked: torch.Tensor, n: int) -> torch.Tensor:
-        """Tiled codes (include/lrx.h) -> row-major uint8 [n, d]."""
-        nb = -(-n // 128)
-        v = blocked[:nb * 128 * self.d].view(nb, self.d // 64, 8, 4, 16, 16)           # block, slice, row group, piece, row, byte
-        return v.permute(0, 2, 4, 1, 3, 5).reshape(nb * 128, self.d)[:n]
-
-    def rows_to_blocked(self, codes: torch.Tensor) -> torch.Tensor:
-        n = codes.shape[0]
-        nb = -(-n // 128)
-        buf = torch.zeros(nb * 128, self.d, dtype=torch.uint8, device=self.device)
-        buf[:n] = codes.to(self.device)
-        return buf.view(nb, 8, 16, self.d // 64, 4, 16).permute(0, 3, 1, 4, 2, 5).contiguous().view(-1)
+    def _layout(self):
+        # a block: [64-column slice][16-row group][16-column piece][row][byte] -> [row group][row][slice][piece][byte]
+        return (self.d // 64, 8, 4, 16, 16), (2, 4, 1, 3, 5)
 
     # -- training ------------------------------------------------------------------------------------------------
     def train(self, x, more: bool = False):
@@ -876,55 +896,21 @@ class SQ8Index:
         self.trained = torch.cat([mn, mx - mn])        # (fp32 subtraction: the contract's vdiff)
         self.is_trained = True
 
-    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int, trained: torch.Tensor):
+    def _encode_into(self, x: torch.Tensor, codes: torch.Tensor, row0: int):
         for s in range(0, x.shape[0], 262144):
             xs = x[s:s + 262144]
-            _lib.check(self.lib.lrx_sq8_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(trained), self.d, self._qt, _lib.ptr(codes), row0 + s,
+            _lib.check(self.lib.lrx_sq8_encode(_lib.ptr(xs), xs.shape[0], xs.stride(0), _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(codes), row0 + s,
                                                _lib.current_stream()))
 
     def encode(self, x) -> torch.Tensor:
         """faiss sa_encode: row-major uint8 [n, d] codes of x under this index's training."""
         x = self._rows(x)
-        blocked = torch.zeros(-(-x.shape[0] // 128) * 128 * self.d, dtype=torch.uint8, device=self.device)
+        blocked = self._scratch_blocks(x.shape[0])
         if x.shape[0]:
-            self._encode_into(x, blocked, 0, self.trained)
+            self._encode_into(x, blocked, 0)
         return self.blocked_to_rows(blocked, x.shape[0]).contiguous()
 
     # -- rows ------------------------------------------------------------------------------------------------------
-    def add(self, x):
-        """faiss add(x f32[n, d]): encode into the codes (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("SQ8Index.add: the index is not trained (call train() first)")
-        x = self._rows(x)
-        n = x.shape[0]
-        if self.ntotal + n > self.capacity:
-            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
-        if n:
-            self._encode_into(x, self._codes, self.ntotal, self.trained)
-        self.ntotal += n
-
-    def append_slot(self, n_rows: int) -> torch.Tensor:
-        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
-        if self._stage is None or self._stage.shape[0] < n_rows:
-            self._stage = None
-            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
-        return self._stage[:n_rows]
-
-    def commit(self, n_rows: int):
-        if n_rows > 0:
-            if self._stage is None or n_rows > self._stage.shape[0]:
-                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
-            rows = self._stage[:n_rows]
-            if not self.is_trained:
-                self.train(rows)
-            self.add(rows)
-        self._stage = None                             # staging released (stream-ordered by the allocator)
-
-    def reset(self):
-        """faiss reset(): drops the rows, keeps the training."""
-        self.ntotal = 0
-        self._stage = None
-
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """Rows [i0, i0 + n) decoded to fp32 (the rows the scores are defined over), device tensor [n, d]."""
         _check_range(i0, n, self.ntotal)
@@ -934,10 +920,6 @@ class SQ8Index:
             _lib.check(self.lib.lrx_sq8_decode_rows(_lib.ptr(self._codes), i0 + s, m, _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(out[s:]), self.d,
                                                     _lib.current_stream()))
         return out
-
-    def codes(self) -> torch.Tensor:
-        """The codes as a row-major uint8 [ntotal, d] tensor (a copy: the stored layout is tiled)."""
-        return self.blocked_to_rows(self._codes, self.ntotal).contiguous()
 
     def set_contents(self, trained, codes):
         """Replace the training (vmin ++ vdiff) and the rows (row-major uint8 [n, d] codes): load() and tests."""
@@ -975,34 +957,22 @@ class SQ8Index:
         idx.is_trained = is_trained
         return idx
 
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
-
     # -- search --------------------------------------------------------------------------------------------------
     def search(self, q, k: int, row_map: Optional[torch.Tensor] = None):
         """faiss search -> (D f32[Q,k], I i64[Q,k]) device tensors: score descending, ties to the lower row, (-FLT_MAX, -1) padding when
         k > ntotal.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries) when given."""
-        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
-        if not 1 <= k <= 2048:
-            raise ValueError(f"search: k={k} out of range (1..2048)")
-        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
-            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        q, D, I = self._begin_search(q, k, row_map)
         Q = q.shape[0]
-        D = torch.empty(Q, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
         if Q == 0:
             return D, I
-        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_sq8_ip_workspace_bytes(self.ntotal, self.d, Q, k)), self.device,
-                        "SQ8Index.search under graph capture: the search workspace must exist before the capture starts -- run one eager "
-                        "search with the same number of queries and k first")
+        ws = self._search_workspace(self.lib.lrx_sq8_ip_workspace_bytes(self.ntotal, self.d, Q, k))
         _lib.check(self.lib.lrx_sq8_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(q), Q, k,
                                               int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
                                               _lib.current_stream()))
         return D, I
 
 
-class BinaryFlatIndex:
+class BinaryFlatIndex(_CodeIndex):
     """Binary flat shard: the faiss IndexBinaryFlat(d) surface (add / search / reset / ntotal / reconstruct_n / save / load) plus the reference's
     float rerank (FaissBinaryIndex.search), backed by lrx_binary_ip_search / lrx_binary_hamming_search.  Resident: d / 8 bytes per row (d = the
     number of bits, d % 8 == 0), in the blocked layout of include/lrx.h (rows padded to whole 16-byte groups).  Bit j of a row is
@@ -1013,34 +983,14 @@ class BinaryFlatIndex:
     through append_slot(n) / commit(n): the slot is a transient fp32 staging view, commit() binarises it and releases it.  Search: one library
     call, workspace kept by the index.  NOT thread-safe."""
 
-    MAX_K = 2048
-
     def __init__(self, d: int, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0, threshold=0):
         if d <= 0 or d % 8 != 0:
             raise ValueError(f"BinaryFlatIndex: d={d} (bits) must be a positive multiple of 8")
         if d > 16384:
             raise NotImplementedError(f"BinaryFlatIndex: d={d} > 16384 bits is not served")
-        _lib.require_gpu()
-        self.lib = _lib.lib()
-        self.d = d
-        self.code_size = d // 8
         self.Mp = -(-d // 128) * 16            # bytes per row in the blocked layout
-        self.device = device or torch.device("cuda", torch.cuda.current_device())
-        self.id_base = id_base
-        self.ntotal = 0
+        super().__init__(d, d // 8, self.Mp, capacity, device, id_base)
         self.threshold = threshold
-        self._codes = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self._stage = None
-        self._ws = None
-        self.reserve(capacity)
-
-    # -- storage -------------------------------------------------------------------------------------------------
-    @property
-    def capacity(self) -> int:
-        return self._codes.numel() // self.Mp
-
-    def reserve(self, n_rows: int):
-        self._codes = _grow_blocks(self._codes, n_rows, self.Mp, self.ntotal, zero=True)
 
     def _threshold_args(self, threshold):
         """threshold (a number, or d values) -> (the scalar, the [d] fp32 device vector or None)."""
@@ -1065,8 +1015,7 @@ class BinaryFlatIndex:
         packed = x.dtype == torch.uint8
         x = _as_rows(x, self.code_size if packed else self.d, "add: ")
         n = x.shape[0]
-        if self.ntotal + n > self.capacity:
-            self.reserve(max(self.ntotal + n, int(self.capacity * 1.5) + 1))
+        self._make_room(n)
         if n:
             if packed:
                 x = x.to(self.device).contiguous()
@@ -1075,24 +1024,6 @@ class BinaryFlatIndex:
                 x = x.to(device=self.device, dtype=torch.float32)
                 self._pack_into(x if x.stride(1) == 1 else x.contiguous(), self.ntotal)
         self.ntotal += n
-
-    def append_slot(self, n_rows: int) -> torch.Tensor:
-        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
-        if self._stage is None or self._stage.shape[0] < n_rows:
-            self._stage = None
-            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
-        return self._stage[:n_rows]
-
-    def commit(self, n_rows: int):
-        if n_rows > 0:
-            if self._stage is None or n_rows > self._stage.shape[0]:
-                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
-            self.add(self._stage[:n_rows])
-        self._stage = None                             # staging released (stream-ordered by the allocator)
-
-    def reset(self):
-        self.ntotal = 0
-        self._stage = None
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """Rows [i0, i0 + n) as packed bytes: uint8 device tensor [n, d / 8] (faiss reconstruct of a binary index)."""
@@ -1105,10 +1036,6 @@ class BinaryFlatIndex:
     def codes(self) -> torch.Tensor:
         """The rows as a row-major uint8 [ntotal, d / 8] tensor (a copy: the stored layout is blocked)."""
         return self.reconstruct_n(0, self.ntotal)
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.codes()
 
     # -- persistence (faiss.write_index_binary / read_index_binary of an IndexBinaryFlat, see index_io.py) ---------------------
     def save(self, fname: str, chunk_rows: int = 1 << 20):
@@ -1134,20 +1061,15 @@ class BinaryFlatIndex:
         row_map[row] (int64 CUDA tensor of >= ntotal entries) when given.  1 <= k <= binary_k <= 2048."""
         if score_function != "dot":
             raise NotImplementedError(f"BinaryFlatIndex.search: score_function {score_function!r} is not served (only 'dot')")
-        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        k_error = None
         if rerank and not 1 <= k <= binary_k <= self.MAX_K:
-            raise ValueError(f"search: need 1 <= k <= binary_k <= {self.MAX_K}, got k={k}, binary_k={binary_k}")
-        if not rerank and not 1 <= k <= self.MAX_K:
-            raise ValueError(f"search: k={k} out of range (1..{self.MAX_K})")
-        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
-            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+            k_error = f"search: need 1 <= k <= binary_k <= {self.MAX_K}, got k={k}, binary_k={binary_k}"
+        q, D, I = self._begin_search(q, k, row_map, torch.float32 if rerank else torch.int32, k_error)
         thr, tv = self._threshold_args(self.threshold if threshold is None else threshold)
         Q = q.shape[0]
-        D = torch.empty(Q, k, dtype=torch.float32 if rerank else torch.int32, device=self.device)
-        I = torch.empty(Q, k, dtype=torch.int64, device=self.device)
         if Q == 0:
             return D, I
-        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_binary_workspace_bytes(self.ntotal, self.d, Q, binary_k)), self.device)
+        ws = self._search_workspace(self.lib.lrx_binary_workspace_bytes(self.ntotal, self.d, Q, binary_k))
         if rerank:
             _lib.check(self.lib.lrx_binary_ip_search(_lib.ptr(self._codes), self.ntotal, self.d, _lib.ptr(q), Q, thr, _lib.ptr(tv), k, binary_k,
                                                      int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), flags,

@@ -84,13 +84,16 @@ def shard_prefix(prefix: str, rank: int = 0, world: int = 1) -> str:
     return prefix if world == 1 else f"{prefix}.rank{rank}-of-{world}"
 
 
-def _write_index(fname: str, who: str, fourcc: bytes, d: int, ntotal: int, is_trained: bool, head: bytes, blocks: Iterable[np.ndarray],
-                 dtype: str, width: int, width_name: str = "d", tail: bytes = b"") -> None:
-    """The common index header, `head` (the format's fields up to and including the size word of the rows), the rows streamed from
+def _index_header(fourcc: bytes, d: int, ntotal: int, is_trained: bool = True) -> bytes:
+    return _HEADER.pack(fourcc, d, ntotal, 1 << 20, 1 << 20, int(bool(is_trained)), 0)
+
+
+def _write_index(fname: str, who: str, ntotal: int, head: bytes, blocks: Iterable[np.ndarray], dtype: str, width: int, width_name: str = "d",
+                 tail: bytes = b"") -> None:
+    """`head` (the packed index header and the format's fields up to and including the size word of the rows), the rows streamed from
     `blocks` (arrays [n_i, width] in row order, sum n_i == ntotal, written as `dtype`), then `tail` -- to a .tmp file renamed over fname."""
     tmp = fname + ".tmp"
     with open(tmp, "wb") as f:
-        f.write(_HEADER.pack(fourcc, d, ntotal, 1 << 20, 1 << 20, int(bool(is_trained)), 0))
         f.write(head)
         rows = 0
         for b in blocks:
@@ -115,7 +118,7 @@ def _read_header(f, fname: str, fourcc: bytes, what: str):
 
 def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
     """blocks: fp32 [n_i, d] arrays in row order (streamed: the shard comes off the GPU in chunks), sum n_i == ntotal."""
-    _write_index(fname, "write_flat_ip", FOURCC_FLAT_IP, d, ntotal, True, struct.pack("<Q", ntotal * d), blocks, "<f4", d)
+    _write_index(fname, "write_flat_ip", ntotal, _index_header(FOURCC_FLAT_IP, d, ntotal) + struct.pack("<Q", ntotal * d), blocks, "<f4", d)
 
 
 def read_flat_ip(fname: str) -> np.memmap:
@@ -139,18 +142,25 @@ SQ_HEADER_BYTES = _HEADER.size + _SQ.size + 8 + 8   # + empty `trained` vector +
 
 def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
     """blocks: fp16 [n_i, d] arrays (the codes) in row order, sum n_i == ntotal."""
-    head = _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<QQ", 0, ntotal * 2 * d)   # (empty `trained` vector, code bytes)
-    _write_index(fname, "write_sq_fp16", FOURCC_SQ, d, ntotal, True, head, blocks, "<f2", d)
+    head = _index_header(FOURCC_SQ, d, ntotal) + _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<QQ", 0, ntotal * 2 * d)   # (empty `trained`, code bytes)
+    _write_index(fname, "write_sq_fp16", ntotal, head, blocks, "<f2", d)
+
+
+def _read_sq_prefix(f, fname: str, more: int = 8):
+    """The 'IxSQ' prefix (index header + _SQ) at the start of the open file f -> (file size, d, ntotal, is_trained, metric_type, qtype,
+    sq.d, code_size); ValueError when the file is shorter than the prefix and `more` bytes, or is no 'IxSQ' file."""
+    size = os.path.getsize(fname)
+    if size < _HEADER.size + _SQ.size + more:
+        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
+    d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
+    qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
+    return size, d, ntotal, is_trained, metric, qtype, sq_d, code_size
 
 
 def read_sq_fp16(fname: str) -> np.memmap:
     """-> read-only memmap fp16 [ntotal, d] of the codes (no copy)."""
-    size = os.path.getsize(fname)
-    if size < _HEADER.size + _SQ.size + 8:
-        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
     with open(fname, "rb") as f:
-        d, ntotal, _, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
-        qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
+        size, d, ntotal, _, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname)
         if qtype != QT_FP16:
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served (only QT_fp16 = {QT_FP16})")
         (n_trained,) = struct.unpack("<Q", f.read(8))
@@ -179,11 +189,8 @@ def _sq8_trained_len(qtype: int, d: int) -> int:
 
 def sq_qtype(fname: str) -> int:
     """The ScalarQuantizer qtype of an 'IxSQ' file (faiss's enum: 0 8bit, 1 4bit, 2 8bit_uniform, 3 4bit_uniform, 4 fp16, ...)."""
-    if os.path.getsize(fname) < _HEADER.size + _SQ.size:
-        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
     with open(fname, "rb") as f:
-        _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
-        return _SQ.unpack(f.read(_SQ.size))[0]
+        return _read_sq_prefix(f, fname, more=0)[5]
 
 
 def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: int, ntotal: int, qtype: int = QT_8BIT, is_trained: bool = True) -> None:
@@ -191,19 +198,15 @@ def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: 
     t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
     if t.size != _sq8_trained_len(qtype, d):
         raise ValueError(f"write_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
-    head = _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes() + struct.pack("<Q", ntotal * d)
-    _write_index(fname, "write_sq8", FOURCC_SQ, d, ntotal, is_trained, head, blocks, np.uint8, d)
+    head = _index_header(FOURCC_SQ, d, ntotal, is_trained) + _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes() + struct.pack("<Q", ntotal * d)
+    _write_index(fname, "write_sq8", ntotal, head, blocks, np.uint8, d)
 
 
 def read_sq8(fname: str):
     """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained)."""
-    size = os.path.getsize(fname)
     fixed = _HEADER.size + _SQ.size + 8
-    if size < fixed:
-        raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
     with open(fname, "rb") as f:
-        d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
-        qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
+        size, d, ntotal, is_trained, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname)
         if qtype not in (QT_8BIT, QT_8BIT_UNIFORM):
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served here (QT_8bit = {QT_8BIT}, QT_8bit_uniform = {QT_8BIT_UNIFORM})")
         (n_t,) = struct.unpack("<Q", f.read(8))
@@ -229,8 +232,8 @@ def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d:
     c = np.ascontiguousarray(centroids, dtype="<f4")
     if c.size != d * 256:
         raise ValueError(f"write_pq: {c.size} centroid floats, expected d * 256 = {d * 256}")
-    head = _PQ.pack(d, M, 8) + struct.pack("<Q", d * 256) + c.tobytes() + struct.pack("<Q", ntotal * M)
-    _write_index(fname, "write_pq", FOURCC_PQ, d, ntotal, is_trained, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1))
+    head = _index_header(FOURCC_PQ, d, ntotal, is_trained) + _PQ.pack(d, M, 8) + struct.pack("<Q", d * 256) + c.tobytes() + struct.pack("<Q", ntotal * M)
+    _write_index(fname, "write_pq", ntotal, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1))
 
 
 def read_pq(fname: str):
@@ -268,25 +271,12 @@ BIN_HEADER_BYTES = _BIN_HEADER.size + 8  # + u64 vector size
 
 
 def write_binary_flat(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
-    """blocks: uint8 [n_i, d / 8] arrays of packed rows in row order, sum n_i == ntotal.  (A sibling of _write_index: the binary header has no
-    dummies and carries code_size.)"""
+    """blocks: uint8 [n_i, d / 8] arrays of packed rows in row order, sum n_i == ntotal.  (The binary header has no dummies and carries
+    code_size.)"""
     if d <= 0 or d % 8:
         raise ValueError(f"write_binary_flat: d={d} (bits) must be a positive multiple of 8")
-    cs = d // 8
-    tmp = fname + ".tmp"
-    with open(tmp, "wb") as f:
-        f.write(_BIN_HEADER.pack(FOURCC_BINARY_FLAT, d, cs, ntotal, 1, 1))
-        f.write(struct.pack("<Q", ntotal * cs))
-        rows = 0
-        for b in blocks:
-            b = np.ascontiguousarray(b, dtype=np.uint8)
-            if b.ndim != 2 or b.shape[1] != cs:
-                raise ValueError(f"write_binary_flat: block {b.shape} does not match code_size={cs}")
-            f.write(b.tobytes())
-            rows += b.shape[0]
-        if rows != ntotal:
-            raise ValueError(f"write_binary_flat: wrote {rows} rows, header says {ntotal}")
-    os.replace(tmp, fname)
+    head = _BIN_HEADER.pack(FOURCC_BINARY_FLAT, d, d // 8, ntotal, 1, 1) + struct.pack("<Q", ntotal * (d // 8))
+    _write_index(fname, "write_binary_flat", ntotal, head, blocks, np.uint8, d // 8, "code_size")
 
 
 def read_binary_flat(fname: str) -> np.ndarray:
