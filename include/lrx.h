@@ -634,6 +634,40 @@ int lrx_sq8_encode(const float* x, int64_t n_rows, int64_t ldx, const float* tra
 int lrx_sq8_decode_rows(const void* codes, int64_t row0, int64_t n_rows, const float* trained, int32_t dim, int32_t qtype, float* out,
                         int64_t ldo, void* stream);
 
+/* (added in ABI 8, additively) IMPACT index: the sparse half of the hybrid retriever -- what Lucene serves for `-impact -pretokenized` over a
+ * JsonVectorCollection, an integer dot product -- DESIGN §5.4.6.  The contract, which fixes (D, I) given the documents and the queries:
+ *   documents     a document is a set of (term, weight) pairs, 1 <= weight < 2^31, a term at most once; its row is its insertion number.
+ *   queries       a query is a set of (term, count) pairs, count >= 1; terms the index has never seen contribute nothing.
+ *   terms         int32 ids here; the strings (token ids as strings, tokens, the empty-vector marker "-1", an ordinary term) and their
+ *                 str -> int32 dictionary in first-seen order are the caller's (ImpactSearch).
+ *   S(q, r)       = sum_t count_q[t] * weight_r[t], an exact integer.
+ *   hits          row r is a hit iff S(q, r) >= 1, i.e. iff it shares a term with the query; a row that is no hit is never returned.
+ *   score         (float) S: ONE round-to-nearest-even conversion -- exact below 2^24; from 2^24 on distinct integers may give one float.
+ *   ranking       by the RETURNED float, descending, ties to the lower row (the flat index's rule, Lucene's docid rule); a list of fewer than k
+ *                 hits is padded like the flat index pads past n_rows: score -FLT_MAX, id -1.  1 <= k <= 2048; k > n_rows is legal.
+ *   overflow      the device accumulates in int32.  The CALLER refuses, before anything is launched, every query with
+ *                 B_q = sum_t count_q[t] * maxw[t] >= 2^31 (maxw[t]: the largest weight of term t over all documents, int64 arithmetic):
+ *                 S <= B_q, so no accumulator wraps.  ImpactIndex.search raises ValueError; this entry point cannot check it (it does not see
+ *                 maxw) and its results are unspecified for such a query.
+ * STORAGE, inverted: `postings` = nnz pairs {int32 row, int32 weight} (8 bytes, interleaved: the scan fetches a posting -- or two, 16 bytes --
+ *   with one load from the cache lines its range search has just touched), grouped by term, ascending row inside a term;
+ *   term_off int64 [n_terms + 1] (device): term t's postings are [term_off[t], term_off[t + 1]).  n_rows < 2^31.
+ * QUERIES, CSR on the device: q_off int32 [n_queries + 1] ascending from 0, q_term / q_cnt int32 [q_off[n_queries]]; a term outside
+ *   [0, n_terms) has no postings.
+ * lrx_impact_search, per chunk of lrx_impact_chunk_queries queries and row chunk of up to 4 Mi rows: one workgroup per (query, window of W
+ *   consecutive rows) walks the query's terms, finds the window's piece of each posting list by a lower-bound search on the rows and adds
+ *   count * weight into int32 accumulators in LDS (integer adds: deterministic whatever the order), then writes its slice of the [Q, rows] fp32
+ *   scores -- zeros included, nothing is cleared beforehand -- and their 128-row block maxima -> the flat index's selection (k_topk_select) ->
+ *   results that are not hits become padding -> row chunks merged with lrx_merge_topk's kernel.  No host synchronisation.
+ *   window_rows: 0 = the library's rule (32768, 8192 or 2048 rows: the largest that gives every CU two workgroups), else a multiple of 128 up
+ *   to 32768 (tests, tools); the results do not depend on it.  out_ids: id_base + row, or row_map[row] when row_map != NULL.
+ *   Workspace: lrx_impact_workspace_bytes.                                                                                                */
+size_t lrx_impact_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t k);
+int32_t lrx_impact_chunk_queries(int64_t n_rows, int32_t n_queries, int32_t k);
+int lrx_impact_search(const void* postings, const int64_t* term_off, int32_t n_terms, int64_t n_rows, const int32_t* q_off,
+                      const int32_t* q_term, const int32_t* q_cnt, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores,
+                      int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, int32_t window_rows, void* stream);
+
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);
 int lrx_flat_ip_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries,

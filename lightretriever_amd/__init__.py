@@ -1,3 +1,4 @@
 """lightretriever_amd: MI355X-native corpus-embedding + flat-IP search path of LightRetriever."""
 from .encoder import EncoderConfig, LrxEncoder, interleave_gate_up, lora_merge, rope_tables  # noqa: F401
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk  # noqa: F401
+from .impact_index import ImpactIndex  # noqa: F401

@@ -328,6 +328,35 @@ std::tuple<at::Tensor, at::Tensor> sq8_ip_topk(const at::Tensor& q, const at::Te
   return {o.d, o.i};
 }
 
+// Impact index (lrx_impact_search): postings int32 [nnz, 2] = {row, weight} grouped by term, ascending row inside a term; term_off int64
+// [n_terms + 1]; the queries in CSR form, q_off int32 [Q + 1], q_term / q_cnt int32 [q_off[Q]] (include/lrx.h).  Reads q_off[Q] back to the
+// host once (the CSR is checked against its arrays).  The overflow refusal of the contract is the caller's (ImpactIndex.search makes it).
+// Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> impact_topk(const at::Tensor& postings, const at::Tensor& term_off, int64_t n_rows, const at::Tensor& q_off,
+                                               const at::Tensor& q_term, const at::Tensor& q_cnt, int64_t k, int64_t id_base,
+                                               const c10::optional<at::Tensor>& row_map, int64_t window_rows) {
+  DevGuard guard(postings.device());
+  need(postings, "postings", at::kInt, 2);
+  need(term_off, "term_off", at::kLong, 1);
+  need(q_off, "q_off", at::kInt, 1);
+  need(q_term, "q_term", at::kInt, 1);
+  need(q_cnt, "q_cnt", at::kInt, 1);
+  TORCH_CHECK(postings.is_contiguous() && postings.size(1) == 2 && term_off.numel() >= 1 && q_off.numel() >= 1 && q_term.numel() == q_cnt.numel() && n_rows >= 0,
+              "impact_topk: postings int32 [nnz,2] contiguous, term_off int64 [T+1], q_off int32 [Q+1], q_term / q_cnt int32 of one length, n_rows >= 0");
+  const int64_t Q = q_off.numel() - 1;
+  TORCH_CHECK(q_off[Q].item<int32_t>() == q_term.numel(), "impact_topk: q_off[Q] must equal the length of q_term");
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "impact_topk: row_map int64 [>= n_rows] contiguous");
+  const auto f32 = postings.options().dtype(at::kFloat);
+  at::Tensor d = at::empty({Q, k}, f32), i = at::empty({Q, k}, f32.dtype(at::kLong));
+  const size_t wsb = lrx_impact_workspace_bytes(n_rows, (int32_t)Q, (int32_t)k);
+  at::Tensor ws = bytes((int64_t)wsb, postings);
+  lrx_check(lrx_impact_search(postings.data_ptr(), term_off.data_ptr<int64_t>(), (int32_t)(term_off.numel() - 1), n_rows, q_off.data_ptr<int32_t>(),
+                              q_term.data_ptr<int32_t>(), q_cnt.data_ptr<int32_t>(), (int32_t)Q, (int32_t)k, id_base, d.data_ptr<float>(),
+                              i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, (int32_t)window_rows, cur_stream()),
+            "impact_topk");
+  return {d, i};
+}
+
 // Binary flat index (lrx_binary_ip_search / lrx_binary_hamming_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of
 // n_rows rows of q.size(1) bits; threshold: None (0), one element, or [D].  rerank: (D fp32, I) of the float rerank of the Hamming top-binary_k;
 // else (D int32, I) of the Hamming top-k.
@@ -418,6 +447,8 @@ TORCH_LIBRARY(lrx, m) {
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
+        "int window_rows=0) -> (Tensor, Tensor)");
   m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
@@ -438,5 +469,6 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
+  m.impl("impact_topk", &impact_topk);
   m.impl("binary_topk", &binary_topk);
 }

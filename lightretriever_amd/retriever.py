@@ -6,7 +6,8 @@
     PQFaissSearch       <- retriever/faiss_search.py:326-383             (IndexPQ, 8-bit codes, inner product only, over PQIndex)
     FaissBinaryIndex    <- retriever/faiss_index.py:116-192              (Hamming candidates + float rerank over BinaryFlatIndex)
     BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
-    HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; sparse + fusion out of scope)
+    HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
+    ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
 Design differences, results preserved: corpus embeddings are encoded straight into the index shard (no CPU round trip, no
 `index.add` copy); the per-chunk (score, pid) heaps of hybrid_search.py:182-205 are a running [Q, top_k] list kept on the
@@ -27,6 +28,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .impact_index import ImpactIndex, query_csr
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 
 logger = logging.getLogger(__name__)
@@ -412,6 +414,71 @@ class BinaryFaissSearch(FlatIPFaissSearch):
         return "binary_faiss_index"
 
 
+class ImpactSearch:
+    """The sparse engine HybridSearch calls, with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
+    `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`), over an HBM-resident ImpactIndex instead of Lucene behind a JVM: impact
+    search (`-impact -pretokenized`) of a JsonVectorCollection -- the contract of include/lrx.h (lrx_impact_search), DESIGN §5.4.6.
+    Documents are {term: integer weight} dicts, queries {term: count} dicts or pseudo text ("tok tok tok ...": split on whitespace and
+    counted).  Terms are strings -- token ids as strings, tokens, the empty-vector marker "-1" (an ordinary term) -- numbered in first-seen
+    order by `vocab`; query terms no document has brought are dropped.  A document is a row in insertion order (an id indexed twice is two
+    rows); equal scores rank the earlier row first.  BM25 (`anserini_impact_search=False`) and other collections are not served."""
+
+    def __init__(self, model=None, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, **kwargs):
+        if not kwargs.get("anserini_impact_search", True):
+            raise NotImplementedError("ImpactSearch: anserini_impact_search=False (BM25) is not served, only impact search")
+        vector_type = kwargs.get("anserini_vector_type", "JsonVectorCollection")
+        if vector_type != "JsonVectorCollection":
+            raise NotImplementedError(f"ImpactSearch: anserini_vector_type={vector_type!r} is not served (only 'JsonVectorCollection')")
+        self.model = model
+        self.batch_size = batch_size
+        self.corpus_chunk_size = corpus_chunk_size
+        self.vocab: dict = {}              # term -> int32 id, first-seen order; survives _clear() like a tokenizer would
+        self.impact_index = ImpactIndex()
+        self.rev_mapping: list = []        # row -> pid
+
+    @classmethod
+    def name(cls):
+        return "impact_search"
+
+    def _clear(self):
+        self.impact_index.reset()
+        self.rev_mapping = []
+
+    def index(self, corpus_emb, corpus_ids):
+        """corpus_emb: a list of {term: weight} dicts (the JsonVectorCollection `vector` field); appended to the index, the GPU is not touched
+        before the first retrieval."""
+        assert len(corpus_emb) == len(corpus_ids)
+        vocab = self.vocab
+        off = np.zeros(len(corpus_emb) + 1, dtype=np.int64)
+        terms, weights = [], []
+        for i, doc in enumerate(corpus_emb):
+            for t, w in doc.items():
+                if int(w) != w:
+                    raise ValueError(f"ImpactSearch.index: weight {w!r} of term {t!r} is not an integer (impact search scores quantised weights)")
+                terms.append(vocab.setdefault(t, len(vocab)))
+                weights.append(int(w))
+            off[i + 1] = len(terms)
+        self.impact_index.add(np.asarray(terms, dtype=np.int64), np.asarray(weights, dtype=np.int64), off)
+        self.rev_mapping += list(corpus_ids)
+
+    def _query_terms(self, query):
+        """One query -> (term ids, counts): pseudo text is split and counted, unknown terms are dropped."""
+        if isinstance(query, str):
+            from collections import Counter
+            query = Counter(query.split())
+        pairs = [(self.vocab[t], c) for t, c in query.items() if t in self.vocab]
+        for _, c in pairs:
+            if int(c) != c:
+                raise ValueError(f"ImpactSearch: query count {c!r} is not an integer")
+        return [t for t, _ in pairs], [int(c) for _, c in pairs]
+
+    def retrieve_with_emb(self, query_emb, query_ids, top_k: int, **kwargs):
+        """query_emb: per query a {term: count} dict or pseudo text -> {qid: {pid: score}} of the top_k hits (documents sharing a term)."""
+        assert len(query_emb) == len(query_ids)
+        D, I = self.impact_index.search(*query_csr([self._query_terms(q) for q in query_emb]), top_k)
+        return _to_result_dict(D, I, query_ids, self.rev_mapping)
+
+
 class HybridSearch:
     """Dense half of the reference's HybridSearch: routes `dense_reps` -> results["den"], `emb_reps` -> results["emb"]
     (hybrid_search.py:121-180); `search()` returns the last enabled type unless return_all_results."""
@@ -421,10 +488,16 @@ class HybridSearch:
         """sparse_search: an engine with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
         `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`); the Lucene engine itself is outside this package.  When
         one is given, `tok` / `emb_tok` (query token counts x sparse document vectors, and their fusion with the dense hits,
-        hybrid_search.py:160-180) are produced like the reference does; the fusion runs on the GPU (score_fuse_utils)."""
+        hybrid_search.py:160-180) are produced like the reference does; the fusion runs on the GPU (score_fuse_utils).
+        sparse_search="gpu": this package's own engine, an ImpactSearch (it gets the anserini_* arguments among **kwargs)."""
         self.model = model
         self.score_fuse_method = score_fuse_method
         self.fuse_weights = list(fuse_weights)
+        if isinstance(sparse_search, str):
+            if sparse_search != "gpu":
+                raise ValueError(f"HybridSearch: sparse_search={sparse_search!r} (an engine object, None or 'gpu')")
+            sparse_search = ImpactSearch(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size,
+                                         **{a: kwargs[a] for a in ("anserini_impact_search", "anserini_vector_type") if a in kwargs})
         self.sparse_search = sparse_search
         self.batch_size = batch_size
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
