@@ -306,6 +306,20 @@ int lrx_sparsify(float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_st
 int lrx_sparse_compact(const float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_stride, int32_t quantization_factor,
                        int32_t capacity, int32_t* ids_out, int32_t* weights_out, int32_t* counts_out, void* stream);
 
+/* (added in ABI 8, additively) The same quantise + compact as ragged CSR, without a capacity: two launches around an exclusive scan of
+ * the counts, which is the caller's (row_off[0] = 0, row_off[b + 1] = row_off[b] + counts_out[b]).
+ *   lrx_sparse_csr_count: counts_out int32 [n_rows] = number of v with round-half-even(max(x[b, v], 0) * q) != 0 (fp32 arithmetic, the
+ *                         arithmetic of lrx_sparse_compact); a row without any counts 1 when empty_marker != 0.
+ *   lrx_sparse_csr_fill:  terms_out / weights_out int32 [row_off[n_rows]]: row b's (token id, weight) pairs at [row_off[b], row_off[b + 1])
+ *                         in ascending id order; a row without any holds the single pair (vocab_size, 1) when empty_marker != 0 -- the
+ *                         device form of the reference's {"-1": 1} (sparse_converter_mixin.py), an ordinary term.  Nothing is written
+ *                         outside a row's range; the outputs need no clearing.
+ * Each launch streams the [n_rows, vocab_size] fp32 rows once (16-byte loads when reps and row_stride * 4 are 16-byte aligned).            */
+int lrx_sparse_csr_count(const float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_stride, int32_t quantization_factor,
+                         int32_t empty_marker, int32_t* counts_out, void* stream);
+int lrx_sparse_csr_fill(const float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_stride, int32_t quantization_factor,
+                        int32_t empty_marker, const int64_t* row_off, int32_t* terms_out, int32_t* weights_out, void* stream);
+
 /* Hit-list fusion (retriever/score_fuse_utils.py:3-91 on arrays; IEEE double like the reference's numpy float64).
  * Stage 1, one retrieval system: scores f64 / ids i64 [n_queries, k] (id < 0 = empty slot) -> contribution per entry:
  *   method 0 (fuse_scores_rrf):    1 / (param0 + rank), rank 1 = highest score of the row;

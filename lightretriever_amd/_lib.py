@@ -61,6 +61,8 @@ SIGNATURES = {
     "lrx_sparse_max_aggregate": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _I64, _P, _P]),
     "lrx_sparsify": (_I32, [_P, _I32, _I32, _I64, _I32, _I32, _I32, _I32, _I32, _P]),
     "lrx_sparse_compact": (_I32, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "lrx_sparse_csr_count": (_I32, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P]),
+    "lrx_sparse_csr_fill": (_I32, [_P, _I32, _I32, _I64, _I32, _I32, _P, _P, _P, _P]),
     "lrx_hit_contributions": (_I32, [_P, _P, _I32, _I32, _I64, _I32, C.c_double, C.c_double, _P, _I64, _P]),
     "lrx_hit_union": (_I32, [_P, _P, _I32, _I32, _I64, _P, _P, _P, _P]),
     "lrx_flat_ip_bounded_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),

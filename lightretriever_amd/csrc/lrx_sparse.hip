@@ -170,3 +170,145 @@ extern "C" int lrx_sparse_compact(const float* reps, int32_t n_rows, int32_t voc
   LRX_LAUNCH_CHECK();
   return LRX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// ragged compaction (CSR, no capacity): the arithmetic of k_sparse_compact in two launches around an exclusive scan of the
+// counts (the caller's).  One workgroup of 1024 lanes per row; a sweep covers CSR_SWEEP = 2 x 4096 columns, every lane reads
+// two 16-byte vectors (both issued before either is used) when the rows are 16-byte aligned, else the same columns one by one.
+// Lane l of sub-sweep u holds columns c0 + u * 4096 + 4 l .. + 3: ascending lane order is ascending column order.
+// ---------------------------------------------------------------------------------------------------------------
+#define CSR_LANES 1024
+#define CSR_SUB 2
+#define CSR_SWEEP (CSR_LANES * 4 * CSR_SUB)
+
+template <bool VEC>
+__device__ __forceinline__ void csr_load_sweep(const float* __restrict__ row, int c0, int cols, int tid, float (&x)[CSR_SUB][4]) {
+#pragma unroll
+  for (int u = 0; u < CSR_SUB; ++u) {
+    const int i = c0 + u * (CSR_LANES * 4) + tid * 4;
+    if (VEC && i + 3 < cols) {
+      const float4 v = *reinterpret_cast<const float4*>(row + i);
+      x[u][0] = v.x; x[u][1] = v.y; x[u][2] = v.z; x[u][3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[u][j] = (i + j < cols) ? row[i + j] : 0.0f;
+    }
+  }
+}
+
+__device__ __forceinline__ int csr_quant(float v, float quant) { return (int)rintf(fmaxf(v, 0.0f) * quant); }
+
+template <bool VEC>
+__global__ void __launch_bounds__(CSR_LANES) k_sparse_csr_count(const float* __restrict__ x, int cols, int64_t ld, float quant, int empty_marker,
+                                                                int32_t* __restrict__ counts) {
+  __shared__ int wave_cnt[CSR_LANES / 64];
+  const float* row = x + (int64_t)blockIdx.x * ld;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int n = 0;
+  for (int c0 = 0; c0 < cols; c0 += CSR_SWEEP) {
+    float v[CSR_SUB][4];
+    csr_load_sweep<VEC>(row, c0, cols, tid, v);
+#pragma unroll
+    for (int u = 0; u < CSR_SUB; ++u)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) n += csr_quant(v[u][j], quant) != 0;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) n += __shfl_xor(n, d, 64);
+  if (lane == 0) wave_cnt[wave] = n;
+  __syncthreads();
+  if (tid == 0) {
+    int t = 0;
+    for (int w = 0; w < CSR_LANES / 64; ++w) t += wave_cnt[w];
+    counts[blockIdx.x] = (t == 0 && empty_marker) ? 1 : t;
+  }
+}
+
+// Row b's pairs go to [row_off[b], row_off[b + 1]) in ascending column order; nothing is written outside that range even when row_off does
+// not match the counts.  The running base lives in a register of every lane (all of them add the same wave totals); the wave totals are
+// double-buffered in LDS, so a sweep costs one barrier.
+template <bool VEC>
+__global__ void __launch_bounds__(CSR_LANES) k_sparse_csr_fill(const float* __restrict__ x, int cols, int64_t ld, float quant, int empty_marker,
+                                                               const int64_t* __restrict__ row_off, int32_t* __restrict__ terms,
+                                                               int32_t* __restrict__ weights) {
+  __shared__ int wave_cnt[2][CSR_SUB][CSR_LANES / 64];
+  const float* row = x + (int64_t)blockIdx.x * ld;
+  const int64_t begin = row_off[blockIdx.x], end = row_off[blockIdx.x + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int64_t base = begin;
+  int buf = 0;
+  for (int c0 = 0; c0 < cols; c0 += CSR_SWEEP, buf ^= 1) {
+    float v[CSR_SUB][4];
+    csr_load_sweep<VEC>(row, c0, cols, tid, v);
+    int q[CSR_SUB][4], before[CSR_SUB];
+#pragma unroll
+    for (int u = 0; u < CSR_SUB; ++u) {
+      int b = 0, tot = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        q[u][j] = csr_quant(v[u][j], quant);
+        const unsigned long long bal = __ballot(q[u][j] != 0);
+        b += __popcll(bal & below);
+        tot += __popcll(bal);
+      }
+      before[u] = b;
+      if (lane == 0) wave_cnt[buf][u][wave] = tot;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < CSR_SUB; ++u) {
+      int pre = 0, tot = 0;
+#pragma unroll
+      for (int w = 0; w < CSR_LANES / 64; ++w) {
+        const int c = wave_cnt[buf][u][w];
+        pre += w < wave ? c : 0;
+        tot += c;
+      }
+      int64_t pos = base + pre + before[u];
+      const int i = c0 + u * (CSR_LANES * 4) + tid * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (q[u][j] != 0) {
+          if (pos < end) { terms[pos] = i + j; weights[pos] = q[u][j]; }
+          ++pos;
+        }
+      base += tot;
+    }
+  }
+  if (tid == 0 && base == begin && empty_marker && begin < end) { terms[begin] = cols; weights[begin] = 1; }
+}
+
+static bool csr_rows_aligned(const float* reps, int64_t row_stride) { return ((uintptr_t)reps & 15u) == 0 && (row_stride & 3) == 0; }
+
+extern "C" int lrx_sparse_csr_count(const float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_stride, int32_t quantization_factor,
+                                    int32_t empty_marker, int32_t* counts_out, void* stream) {
+  LRX_CHECK_ARG(n_rows >= 0 && vocab_size > 0 && vocab_size <= INT32_MAX - CSR_SWEEP && row_stride >= vocab_size && quantization_factor > 0,
+                "sparse_csr_count: bad sizes");
+  if (n_rows == 0) return LRX_OK;
+  LRX_CHECK_ARG(reps && counts_out, "sparse_csr_count: null operand");
+  if (csr_rows_aligned(reps, row_stride))
+    hipLaunchKernelGGL(k_sparse_csr_count<true>, dim3(n_rows), dim3(CSR_LANES), 0, (hipStream_t)stream, reps, vocab_size, row_stride,
+                       (float)quantization_factor, empty_marker, counts_out);
+  else
+    hipLaunchKernelGGL(k_sparse_csr_count<false>, dim3(n_rows), dim3(CSR_LANES), 0, (hipStream_t)stream, reps, vocab_size, row_stride,
+                       (float)quantization_factor, empty_marker, counts_out);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
+extern "C" int lrx_sparse_csr_fill(const float* reps, int32_t n_rows, int32_t vocab_size, int64_t row_stride, int32_t quantization_factor,
+                                   int32_t empty_marker, const int64_t* row_off, int32_t* terms_out, int32_t* weights_out, void* stream) {
+  LRX_CHECK_ARG(n_rows >= 0 && vocab_size > 0 && vocab_size <= INT32_MAX - CSR_SWEEP && row_stride >= vocab_size && quantization_factor > 0,
+                "sparse_csr_fill: bad sizes");
+  if (n_rows == 0) return LRX_OK;
+  LRX_CHECK_ARG(reps && row_off, "sparse_csr_fill: null operand");
+  if (csr_rows_aligned(reps, row_stride))
+    hipLaunchKernelGGL(k_sparse_csr_fill<true>, dim3(n_rows), dim3(CSR_LANES), 0, (hipStream_t)stream, reps, vocab_size, row_stride,
+                       (float)quantization_factor, empty_marker, row_off, terms_out, weights_out);
+  else
+    hipLaunchKernelGGL(k_sparse_csr_fill<false>, dim3(n_rows), dim3(CSR_LANES), 0, (hipStream_t)stream, reps, vocab_size, row_stride,
+                       (float)quantization_factor, empty_marker, row_off, terms_out, weights_out);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}

@@ -4,6 +4,7 @@
 // Built by lightretriever_amd/build.py into lightretriever_amd/liblrx_torch.so (next to liblrx.so, rpath $ORIGIN).
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
+#include <c10/hip/HIPGraphsC10Utils.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
@@ -427,6 +428,32 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Te
   TORCH_CHECK(false, "flat_ip_range_search: the result grew between two identical calls");
 }
 
+// Quantise + compact to ragged CSR (lrx_sparse_csr_count / lrx_sparse_csr_fill): reps fp32 [B, V] (rows may be strided) -> (row_off int64 [B + 1],
+// terms int32 [row_off[B]], weights int32 [row_off[B]]).  The exclusive scan between the two launches is at::cumsum; row_off[B] is read back to
+// the host once to size the outputs, so the op is refused under graph capture before anything is launched.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sparse_compact_csr(const at::Tensor& reps, int64_t quantization_factor, bool empty_marker) {
+  DevGuard guard(reps.device());
+  need(reps, "reps", at::kFloat, 2);
+  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None,
+              "sparse_compact_csr under graph capture: the result length is read back to the host");
+  const int64_t B = reps.size(0), V = reps.size(1);
+  TORCH_CHECK(V > 0 && B < (int64_t(1) << 31) && quantization_factor > 0 && quantization_factor < (int64_t(1) << 31),
+              "sparse_compact_csr: reps [B, V > 0], 0 < quantization_factor < 2^31");
+  const int64_t ld = B ? reps.stride(0) : V;
+  at::Tensor counts = at::empty({B}, reps.options().dtype(at::kInt));
+  lrx_check(lrx_sparse_csr_count(reps.data_ptr<float>(), (int32_t)B, (int32_t)V, ld, (int32_t)quantization_factor, empty_marker ? 1 : 0,
+                                 counts.data_ptr<int32_t>(), cur_stream()),
+            "sparse_compact_csr");
+  at::Tensor row_off = at::zeros({B + 1}, reps.options().dtype(at::kLong));
+  if (B) row_off.narrow(0, 1, B).copy_(at::cumsum(counts, 0, at::kLong));
+  const int64_t nnz = B ? row_off[B].item<int64_t>() : 0;
+  at::Tensor terms = at::empty({nnz}, counts.options()), weights = at::empty({nnz}, counts.options());
+  lrx_check(lrx_sparse_csr_fill(reps.data_ptr<float>(), (int32_t)B, (int32_t)V, ld, (int32_t)quantization_factor, empty_marker ? 1 : 0,
+                                row_off.data_ptr<int64_t>(), terms.data_ptr<int32_t>(), weights.data_ptr<int32_t>(), cur_stream()),
+            "sparse_compact_csr");
+  return {row_off, terms, weights};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(lrx, m) {
@@ -449,6 +476,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
         "int window_rows=0) -> (Tensor, Tensor)");
+  m.def("sparse_compact_csr(Tensor reps, int quantization_factor=100, bool empty_marker=True) -> (Tensor, Tensor, Tensor)");
   m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
@@ -471,4 +499,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);
   m.impl("binary_topk", &binary_topk);
+  m.impl("sparse_compact_csr", &sparse_compact_csr);
 }

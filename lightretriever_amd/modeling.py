@@ -18,6 +18,7 @@ import torch
 
 from . import ops
 from .encoder import LrxEncoder
+from .sparse_rows import SparseRows
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -300,6 +301,16 @@ class LrxHybridModel:
                 out.append({str(int(i)): int(v) for i, v in zip(ids[b, :n], w[b, :n])})
         return out
 
+    def convert_sparse_reps_to_csr(self, reps: torch.Tensor, quantization_factor: int = 100):
+        """The vectors of convert_sparse_reps_to_json as a SparseRows that stays on the GPU (ops.sparse_compact_csr): same weights, ascending
+        token ids, an empty vector is the marker pair (vocab size, 1).  Only the total number of non-zeros comes to the host."""
+        if reps.dim() == 1:
+            reps = reps.unsqueeze(0)
+        reps = reps.to(self.device, dtype=torch.float32)
+        if reps.stride(1) != 1:
+            reps = reps.contiguous()
+        return ops.sparse_compact_csr(reps, quantization_factor, empty_marker=True)
+
     def convert_sparse_reps_to_pseudo_text(self, reps: torch.Tensor, quantization_factor: int = 100, convert_id_to_token: bool = False,
                                            vocab_dict: Optional[dict] = None) -> list[str]:
         """Each token repeated its quantised weight times, space-joined (finetune/sparse_converter_mixin.py:63-101, :162-189): the form
@@ -433,6 +444,11 @@ class LrxHybridModel:
 # ------------------------------------------------------------------------------------------------------------------
 # encode_queries / encode_corpus (B2)
 # ------------------------------------------------------------------------------------------------------------------
+def _check_sparse_format(sparse_format: str):
+    if sparse_format not in ("json", "csr"):
+        raise ValueError(f"sparse_format={sparse_format!r}: 'json' or 'csr'")
+
+
 def _as_items(texts) -> list[dict]:
     try:
         import datasets
@@ -607,10 +623,13 @@ class LrxExactSearchModel:
             items = [dict(it, prompt=prompt) for it in items]
         return items
 
-    def encode_queries(self, queries, batch_size: int, show_progress_bar: bool = True, convert_to_tensor: bool = True, **kwargs):
+    def encode_queries(self, queries, batch_size: int, show_progress_bar: bool = True, convert_to_tensor: bool = True,
+                       sparse_format: str = "json", **kwargs):
         """-> {"emb_reps"?, "dense_reps"?, "sparse_reps"?, "token_id_reps"?} by the model's flags (exact_search_base.py:94-122 +
         exact_search_torchrpc.py:139-170).  `sparse_reps` (`--hybrid_use_sparse_vector`): the LM-head query vectors as the quantised pseudo text
-        call_batch_encode makes of them (inference/exact_search_base.py:231-236)."""
+        call_batch_encode makes of them (inference/exact_search_base.py:231-236); with sparse_format="csr" the same quantised vectors as one
+        SparseRows on the GPU (weights are the counts; no pseudo text).  `token_id_reps` are host dicts either way (the tokenizer makes them)."""
+        _check_sparse_format(sparse_format)
         items = self.parse_texts(queries, prompt=self.query_prompt)        # the `prompt` column the LM-encoded query vectors prepend
         hm = self.model
         use_dense = bool(getattr(hm, "hybrid_use_dense_vector", False))
@@ -632,9 +651,12 @@ class LrxExactSearchModel:
                               sep_token_id=getattr(hm, "sep_token_id", None), add_sep_token=bool(getattr(hm, "add_sep_token", False)))
         outs: dict = {}
         spr_text: list[str] = []
+        spr_csr: list = []
         for s in (range(0, len(items), batch_size) if (need_lm or (use_emb and nonctx)) else ()):     # (token-id-only models tokenise in token_id_reps)
             for k, v in hm.encode_query(coll(items[s:s + batch_size])).items():
-                if k == "sparse_reps":    # [batch, vocab] fp32 on the GPU -> quantised pseudo text per query (only the non-zeros come to the host)
+                if k == "sparse_reps" and sparse_format == "csr":
+                    spr_csr.append(hm.convert_sparse_reps_to_csr(v, quantization_factor=100))
+                elif k == "sparse_reps":    # [batch, vocab] fp32 on the GPU -> quantised pseudo text per query (only the non-zeros come to the host)
                     spr_text.extend(hm.convert_sparse_reps_to_pseudo_text(v, quantization_factor=100))
                 else:
                     outs.setdefault(k, []).append(v)
@@ -645,7 +667,7 @@ class LrxExactSearchModel:
             reps = torch.cat(parts, 0)
             res[k] = reps if convert_to_tensor else reps.cpu().numpy()
         if use_spr:
-            res["sparse_reps"] = spr_text
+            res["sparse_reps"] = SparseRows.cat(spr_csr) if sparse_format == "csr" else spr_text
         if getattr(hm, "hybrid_use_token_id_vector", hm.encode_sparse):
             res["token_id_reps"] = self.token_id_reps(items)
         return self._unwrap(res)
@@ -657,13 +679,17 @@ class LrxExactSearchModel:
         return res
 
     def encode_corpus(self, corpus, batch_size: int, show_progress_bar: bool = True, convert_to_tensor: bool = True,
-                      out: Optional[torch.Tensor] = None, **kwargs):
-        return self.encode(corpus, batch_size, show_progress_bar, convert_to_tensor, out=out, **kwargs)
+                      out: Optional[torch.Tensor] = None, sparse_format: str = "json", **kwargs):
+        """sparse_format="csr": `sparse_reps` is one SparseRows on the GPU (the per-batch parts appended on the device) instead of a list of
+        {token id: weight} dicts."""
+        return self.encode(corpus, batch_size, show_progress_bar, convert_to_tensor, out=out, sparse_format=sparse_format, **kwargs)
 
     def encode(self, sentences, batch_size: int, show_progress_bar: bool = True, convert_to_tensor: bool = True,
-               out: Optional[torch.Tensor] = None, **kwargs):
+               out: Optional[torch.Tensor] = None, sparse_format: str = "json", **kwargs):
+        _check_sparse_format(sparse_format)
         items = self.parse_texts(sentences, prompt=self.corpus_prompt)
         sparse = self.model.encode_sparse
+        csr = sparse and sparse_format == "csr"
         # the reference's own launch (torch RPC, this rank drives, a model registered on every worker): a direct encode call fans the
         # documents out in contiguous spans and assembles the rows in input order, as PytorchRPCExactSearchModel._encode does
         # (exact_search_torchrpc.py:185-295).  Search keeps its shards on the workers instead (rpc_shards.index_chunk) and passes
@@ -672,6 +698,8 @@ class LrxExactSearchModel:
             from . import rpc_shards
             names = rpc_shards.rpc_workers()
             if len(names) > 1 and rpc_shards._WORKER.get("model") is self:
+                if csr:
+                    raise NotImplementedError("encode(sparse_format='csr'): sparse rows of other ranks are not served (the RPC fan-out returns dicts)")
                 return self._unwrap(rpc_shards.encode_fanout(names, items, batch_size, convert_to_tensor, self.model.device))
         coll = EncodeCollator(self.tokenizer, encode_is_query=False, q_max_len=self.q_max_len, p_max_len=self.p_max_len, sparse_mask=sparse,
                               sep_token_id=self.model.sep_token_id, add_sep_token=self.model.add_sep_token)
@@ -679,13 +707,16 @@ class LrxExactSearchModel:
         if out is None:
             out = torch.empty(len(items), D, dtype=torch.float32, device=self.model.device)
         sparse_json: list[dict] = []
+        sparse_csr: list = []
         for s, e, batch in _token_budget_batches(_prefetch_batches(coll, items, batch_size), self.max_batch_tokens, self.max_batch_docs):
             r = self.model.encode_passage(batch, out=out[s:e])
-            if sparse:   # quantised {token id: weight} per document, what call_batch_encode hands to the sparse engine
+            if csr:      # the same quantised vectors as device CSR: no posting leaves the GPU
+                sparse_csr.append(self.model.convert_sparse_reps_to_csr(r["sparse_reps"], quantization_factor=100))
+            elif sparse:   # quantised {token id: weight} per document, what call_batch_encode hands to the sparse engine
                 sparse_json.extend(self.model.convert_sparse_reps_to_json(r["sparse_reps"], quantization_factor=100))
         self._check_device_counters("encode")
         reps = out[:len(items)]
         res = {"dense_reps": reps if convert_to_tensor else reps.cpu().numpy()}
         if sparse:
-            res["sparse_reps"] = sparse_json
+            res["sparse_reps"] = SparseRows.cat(sparse_csr) if csr else sparse_json
         return self._unwrap(res)

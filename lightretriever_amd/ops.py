@@ -241,3 +241,27 @@ def sparse_compact(reps: torch.Tensor, quantization_factor: int = 100, capacity:
     _lib.check(_lib.lib().lrx_sparse_compact(_lib.ptr(reps), B, V, reps.stride(0), int(quantization_factor), cap, _lib.ptr(ids), _lib.ptr(w),
                                              _lib.ptr(cnt), _s()))
     return ids, w, cnt
+
+
+def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty_marker: bool = True):
+    """Quantise + compact fp32 [B, V] (unit inner stride) to ragged CSR -> SparseRows: per row the (token id, rint(max(x, 0) * q)) pairs
+    with a non-zero weight in ascending id order; a row without any holds the marker pair (V, 1) when empty_marker.  Two launches
+    (lrx_sparse_csr_count / lrx_sparse_csr_fill) around a device cumsum; the total length is read back to the host once, so the call
+    is refused under graph capture."""
+    from .sparse_rows import SparseRows
+    if reps.dtype != torch.float32 or reps.dim() != 2 or reps.stride(1) != 1 or not reps.is_cuda:
+        raise ValueError("sparse_compact_csr: fp32 device [B, V] with unit inner stride")
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.LrxError("sparse_compact_csr under graph capture: the result length is read back to the host")
+    B, V = reps.shape
+    lib, q, mark = _lib.lib(), int(quantization_factor), int(bool(empty_marker))
+    ld = reps.stride(0) if B else V
+    counts = torch.empty(B, dtype=torch.int32, device=reps.device)
+    _lib.check(lib.lrx_sparse_csr_count(_lib.ptr(reps), B, V, ld, q, mark, _lib.ptr(counts), _s()))
+    row_off = torch.zeros(B + 1, dtype=torch.int64, device=reps.device)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=row_off[1:])
+    nnz = int(row_off[-1])
+    terms = torch.empty(nnz, dtype=torch.int32, device=reps.device)
+    weights = torch.empty(nnz, dtype=torch.int32, device=reps.device)
+    _lib.check(lib.lrx_sparse_csr_fill(_lib.ptr(reps), B, V, ld, q, mark, _lib.ptr(row_off), _lib.ptr(terms), _lib.ptr(weights), _s()))
+    return SparseRows(row_off, terms, weights, V)

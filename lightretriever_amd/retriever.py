@@ -30,6 +30,7 @@ import torch
 
 from .impact_index import ImpactIndex, query_csr
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
+from .sparse_rows import SparseRows, identity_term
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -148,6 +149,8 @@ def _sorted_corpus(corpus):
 
 
 class DenseRetrievalFaissSearch:
+    encode_kwargs: dict = {}           # extra arguments of the model's encode_corpus; HybridSearch(sparse_format="csr") sets them on its instance
+
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, use_single_gpu: bool = False,
                  use_multiple_gpu: bool = False, **kwargs):
         self.model = model       # provides encode_corpus() and encode_queries()
@@ -264,7 +267,7 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
             return None
         slot = idx.append_slot(len(docs))
         enc = emb = self.model.encode_corpus(docs, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
-                                             convert_to_tensor=True, out=slot)
+                                             convert_to_tensor=True, out=slot, **self.encode_kwargs)
         if isinstance(emb, dict):
             emb = emb["dense_reps"]
         if emb.data_ptr() != slot.data_ptr():       # a model that does not support `out=`: one device copy
@@ -421,7 +424,13 @@ class ImpactSearch:
     Documents are {term: integer weight} dicts, queries {term: count} dicts or pseudo text ("tok tok tok ...": split on whitespace and
     counted).  Terms are strings -- token ids as strings, tokens, the empty-vector marker "-1" (an ordinary term) -- numbered in first-seen
     order by `vocab`; query terms no document has brought are dropped.  A document is a row in insertion order (an id indexed twice is two
-    rows); equal scores rank the earlier row first.  BM25 (`anserini_impact_search=False`) and other collections are not served."""
+    rows); equal scores rank the earlier row first.  BM25 (`anserini_impact_search=False`) and other collections are not served.
+
+    Documents and queries may also be a SparseRows (device CSR of token ids, sparse_rows.py): the three arrays go to the ImpactIndex as they
+    are, no Python object per posting.  The first index() call of a kind fixes the numbering of the engine -- dicts: `vocab`; SparseRows: the
+    identity rule, token id i is term i and the empty-vector marker is term vocab_size (`identity_term` maps host queries the same way) --
+    until _clear() followed by a call of the other kind.  Mixing the kinds on a non-empty engine raises ValueError.  Every query form is
+    served under either numbering and gives the same hits."""
 
     def __init__(self, model=None, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, **kwargs):
         if not kwargs.get("anserini_impact_search", True):
@@ -435,6 +444,7 @@ class ImpactSearch:
         self.vocab: dict = {}              # term -> int32 id, first-seen order; survives _clear() like a tokenizer would
         self.impact_index = ImpactIndex()
         self.rev_mapping: list = []        # row -> pid
+        self.identity_vocab_size: Optional[int] = None   # None: terms are numbered by `vocab`; V: the identity rule over V token ids
 
     @classmethod
     def name(cls):
@@ -448,6 +458,11 @@ class ImpactSearch:
         """corpus_emb: a list of {term: weight} dicts (the JsonVectorCollection `vector` field); appended to the index, the GPU is not touched
         before the first retrieval."""
         assert len(corpus_emb) == len(corpus_ids)
+        if isinstance(corpus_emb, SparseRows):
+            return self._index_rows(corpus_emb, corpus_ids)
+        if self.rev_mapping and self.identity_vocab_size is not None:
+            raise ValueError("ImpactSearch.index: dicts after SparseRows on a non-empty engine (one numbering per engine: _clear() first)")
+        self.identity_vocab_size = None
         vocab = self.vocab
         off = np.zeros(len(corpus_emb) + 1, dtype=np.int64)
         terms, weights = [], []
@@ -461,21 +476,60 @@ class ImpactSearch:
         self.impact_index.add(np.asarray(terms, dtype=np.int64), np.asarray(weights, dtype=np.int64), off)
         self.rev_mapping += list(corpus_ids)
 
+    def _index_rows(self, rows: SparseRows, corpus_ids):
+        """A SparseRows of documents: the identity numbering, the arrays handed to the index where they are."""
+        if self.rev_mapping and self.identity_vocab_size is None:
+            raise ValueError("ImpactSearch.index: SparseRows after dicts on a non-empty engine (one numbering per engine: _clear() first)")
+        if self.rev_mapping and self.identity_vocab_size != rows.vocab_size:
+            raise ValueError(f"ImpactSearch.index: SparseRows over {rows.vocab_size} token ids, the engine holds rows over {self.identity_vocab_size}")
+        self.impact_index.add(rows.terms, rows.weights, rows.row_off)
+        self.identity_vocab_size = rows.vocab_size
+        self.rev_mapping += list(corpus_ids)
+
+    def _term_id(self, term: str) -> Optional[int]:
+        if self.identity_vocab_size is not None:
+            return identity_term(term, self.identity_vocab_size)
+        return self.vocab.get(term)
+
+    def _query_rows(self, rows: SparseRows) -> tuple:
+        """A SparseRows of queries (weights are counts) -> (q_off, q_term, q_cnt) for ImpactIndex.search.  Under the identity numbering of the
+        same vocabulary the arrays are the answer; else the token ids are renumbered on the host like the string terms they stand for."""
+        if self.identity_vocab_size == rows.vocab_size:
+            return rows.row_off, rows.terms, rows.weights
+        off, term, cnt = rows.row_off.cpu().numpy(), rows.terms.cpu().numpy().astype(np.int64), rows.weights.cpu().numpy()
+        lut = np.full(rows.vocab_size + 1, -1, dtype=np.int64)
+        if self.identity_vocab_size is not None:     # identity over another vocabulary size: shared token ids keep their number
+            n = min(rows.vocab_size, self.identity_vocab_size)
+            lut[:n] = np.arange(n)
+            lut[rows.vocab_size] = self.identity_vocab_size
+        else:
+            for t, i in self.vocab.items():
+                j = identity_term(t, rows.vocab_size)
+                if j is not None:
+                    lut[j] = i
+        mapped = lut[term]
+        keep = mapped >= 0
+        new_off = np.zeros(off.size, dtype=np.int64)
+        np.add.at(new_off, np.repeat(np.arange(off.size - 1), np.diff(off))[keep] + 1, 1)
+        return np.cumsum(new_off), mapped[keep], cnt[keep]
+
     def _query_terms(self, query):
         """One query -> (term ids, counts): pseudo text is split and counted, unknown terms are dropped."""
         if isinstance(query, str):
             from collections import Counter
             query = Counter(query.split())
-        pairs = [(self.vocab[t], c) for t, c in query.items() if t in self.vocab]
+        pairs = [(i, c) for i, c in ((self._term_id(t), c) for t, c in query.items()) if i is not None]
         for _, c in pairs:
             if int(c) != c:
                 raise ValueError(f"ImpactSearch: query count {c!r} is not an integer")
         return [t for t, _ in pairs], [int(c) for _, c in pairs]
 
     def retrieve_with_emb(self, query_emb, query_ids, top_k: int, **kwargs):
-        """query_emb: per query a {term: count} dict or pseudo text -> {qid: {pid: score}} of the top_k hits (documents sharing a term)."""
+        """query_emb: per query a {term: count} dict or pseudo text, or one SparseRows of queries (weights are counts) -> {qid: {pid: score}}
+        of the top_k hits (documents sharing a term)."""
         assert len(query_emb) == len(query_ids)
-        D, I = self.impact_index.search(*query_csr([self._query_terms(q) for q in query_emb]), top_k)
+        csr = self._query_rows(query_emb) if isinstance(query_emb, SparseRows) else query_csr([self._query_terms(q) for q in query_emb])
+        D, I = self.impact_index.search(*csr, top_k)
         return _to_result_dict(D, I, query_ids, self.rev_mapping)
 
 
@@ -484,12 +538,15 @@ class HybridSearch:
     (hybrid_search.py:121-180); `search()` returns the last enabled type unless return_all_results."""
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, use_multiple_gpu: bool = False,
-                 score_fuse_method: str = "linear", fuse_weights=(0.7, 0.3), return_all_results: bool = False, sparse_search=None, **kwargs):
+                 score_fuse_method: str = "linear", fuse_weights=(0.7, 0.3), return_all_results: bool = False, sparse_search=None,
+                 sparse_format: str = "json", **kwargs):
         """sparse_search: an engine with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
         `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`); the Lucene engine itself is outside this package.  When
         one is given, `tok` / `emb_tok` (query token counts x sparse document vectors, and their fusion with the dense hits,
         hybrid_search.py:160-180) are produced like the reference does; the fusion runs on the GPU (score_fuse_utils).
-        sparse_search="gpu": this package's own engine, an ImpactSearch (it gets the anserini_* arguments among **kwargs)."""
+        sparse_search="gpu": this package's own engine, an ImpactSearch (it gets the anserini_* arguments among **kwargs).
+        sparse_format="csr" (with this package's engine only): the model's encode_corpus / encode_queries are called with sparse_format="csr"
+        and hand their `sparse_reps` over as SparseRows on the GPU; "json" (default) passes nothing new to the model."""
         self.model = model
         self.score_fuse_method = score_fuse_method
         self.fuse_weights = list(fuse_weights)
@@ -499,6 +556,13 @@ class HybridSearch:
             sparse_search = ImpactSearch(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size,
                                          **{a: kwargs[a] for a in ("anserini_impact_search", "anserini_vector_type") if a in kwargs})
         self.sparse_search = sparse_search
+        if sparse_format not in ("json", "csr"):
+            raise ValueError(f"HybridSearch: sparse_format={sparse_format!r} ('json' or 'csr')")
+        if sparse_format == "csr" and not isinstance(sparse_search, ImpactSearch):
+            raise ValueError("HybridSearch: sparse_format='csr' needs this package's sparse engine (sparse_search='gpu' or an ImpactSearch); "
+                             f"got {type(sparse_search).__name__}")
+        self.sparse_format = sparse_format
+        self._encode_kwargs = {"sparse_format": "csr"} if sparse_format == "csr" else {}
         self.batch_size = batch_size
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
@@ -517,6 +581,7 @@ class HybridSearch:
         if faiss_search_map == "binary":
             den_kwargs = {a: kwargs[a] for a in ("binary_k", "threshold") if a in kwargs}
         self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
+        self.dense_search.encode_kwargs = dict(self._encode_kwargs)
         self.return_all_results = return_all_results
         self.mteb_model_meta = None
 
@@ -528,10 +593,10 @@ class HybridSearch:
         return self.model.encode(sentences=sentences, batch_size=batch_size, **kw)
 
     def encode_queries(self, queries, batch_size, **kw):
-        return self.model.encode_queries(queries=queries, batch_size=batch_size, **kw)
+        return self.model.encode_queries(queries=queries, batch_size=batch_size, **{**self._encode_kwargs, **kw})
 
     def encode_corpus(self, corpus, batch_size, **kw):
-        return self.model.encode_corpus(corpus=corpus, batch_size=batch_size, **kw)
+        return self.model.encode_corpus(corpus=corpus, batch_size=batch_size, **{**self._encode_kwargs, **kw})
 
     def _clear(self, dense: bool = True, sparse: bool = True):
         if dense:
@@ -582,7 +647,7 @@ class HybridSearch:
                ignore_identical_ids: bool = False, **kwargs):
         query_ids, queries_list = _ids_and_list(queries)
         qe = self.model.encode_queries(queries_list, batch_size=self.batch_size, show_progress_bar=self.show_progress_bar,
-                                       convert_to_tensor=self.convert_to_tensor)
+                                       convert_to_tensor=self.convert_to_tensor, **self._encode_kwargs)
         assert isinstance(qe, dict) and any(k in qe for k in ("dense_reps", "emb_reps", "sparse_reps", "token_id_reps"))
         results, default = {}, None
         # one corpus pass serves every enabled query representation (they share the document `dense_reps`)
