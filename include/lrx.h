@@ -158,7 +158,9 @@ int lrx_encode_prefixed(const lrx_encoder_config* cfg, const lrx_encoder_weights
 #define LRX_POOL_AVG_TOP2 6        /* ... of (hidden_states[-2] + hidden_states[-1]) / 2: the stream before the final layer and the final-norm rows (:43-46) */
 /* LASTTOKEN runs the final layer's O-projection / MLP on the pooled rows only; every other strategy runs all layers over all tokens and pools
  * from the residual stream (final norm inside the pooling kernel, fp32 when the stream is).  A sequence shorter than its strategy needs (the
- * reference asserts there) gets a zero row and raises lrx_device_error_count.  The two-layer strategies add one column-sum pass over the other
+ * reference asserts there) gets a zero row and raises lrx_device_error_count; an empty sequence (cu_seqlens[b + 1] <= cu_seqlens[b]) is too
+ * short for every strategy, LASTTOKEN included, here and in lrx_pool_norm_mode, and lrx_gather_last_rows / lrx_scatter_last_rows answer it
+ * with a zero row / with no write and the same counter (cu_seqlens lives on the device: only the kernels can see it).  The two-layer strategies add one column-sum pass over the other
  * hidden state (the embedding rows; the stream as it enters the final layer) -- served here only: lrx_pool_norm_mode sees one hidden state. */
 int lrx_encode_packed_pooled(const lrx_encoder_config* cfg, const lrx_encoder_weights* w, const int32_t* ids,
                              const int32_t* cu_seqlens, int32_t n_seqs, int32_t total_tokens, int32_t max_seqlen, int32_t pooling,
@@ -206,7 +208,8 @@ int lrx_get_profile(float* ms, double* flops, int32_t* launches);
 int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens, int32_t hidden, int32_t vocab, void* out,
                          void* stream);
 /* Number of out-of-range token ids any embedding gather (stand-alone or inside lrx_encode_*) has met since the last reset, plus the
- * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing); -1 if the read
+ * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
+ * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);

@@ -361,8 +361,8 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
 // bf16 LlamaRMSNorm (the reference for the 1e-3 bound is the fp32 model).
 // mode (LRX_POOL_*, include/lrx.h; finetune/dense_pooling.py:12-82): which row(s) of the sequence are pooled -- its last token (the
 // released models), its first ('cls'), its second / third to last, or the MEAN of the final-norm rows of all its tokens (one token at a
-// time through the same norm, fp32 accumulation in token order).  A sequence too short for its strategy (the reference asserts) gets a
-// zero row and raises the input-error counter (lrx_device_error_count).
+// time through the same norm, fp32 accumulation in token order).  A sequence too short for its strategy (the reference asserts; an EMPTY
+// one is too short for every strategy, the last token included) gets a zero row and raises the input-error counter (lrx_device_error_count).
 template <bool F32>
 __global__ void __launch_bounds__(256) k_pool_norm(const void* __restrict__ hidden_v, const __bf16* __restrict__ w,
                                                    const int32_t* __restrict__ cu, int H, float eps, float* __restrict__ out,
@@ -375,9 +375,10 @@ __global__ void __launch_bounds__(256) k_pool_norm(const void* __restrict__ hidd
   int b = blockIdx.x;
   int64_t t0 = cu ? (int64_t)cu[b + 1] - 1 : (int64_t)b, t1 = t0 + 1;      // rows [t0, t1) are pooled
   bool bad = false;
-  if (cu && mode != LRX_POOL_LASTTOKEN) {
+  if (cu) {
     const int64_t s0 = cu[b], s1 = cu[b + 1];
-    if (mode == LRX_POOL_MEAN || mode >= LRX_POOL_AVG_FIRST_LAST) { t0 = s0; t1 = s1; bad = s1 <= s0; }
+    if (mode == LRX_POOL_LASTTOKEN) bad = s1 <= s0;                     // (an empty sequence has no last token: row s1 - 1 is its neighbour's, or row -1)
+    else if (mode == LRX_POOL_MEAN || mode >= LRX_POOL_AVG_FIRST_LAST) { t0 = s0; t1 = s1; bad = s1 <= s0; }
     else {
       t0 = mode == LRX_POOL_CLS ? s0 : s1 - (mode == LRX_POOL_SECOND_TO_LAST ? 2 : 3);
       t1 = t0 + 1;
@@ -522,14 +523,25 @@ extern "C" int lrx_pool_norm(const void* hidden, const void* final_norm_w, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// gather of the last-token rows (compaction for the pooled tail of the final layer): one wave per sequence
+// gather of the last-token rows (compaction for the pooled tail of the final layer): one wave per sequence.  An empty sequence
+// (cu[b + 1] <= cu[b]) has no last token -- row cu[b + 1] - 1 is the previous sequence's, or row -1: like k_pool_norm, the gathers write a
+// zero row for it, the scatter writes nothing, and each raises the input-error counter (lrx_device_error_count).
 // ---------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_gather_last_rows(const bf16x8* __restrict__ src, const int32_t* __restrict__ cu, int n_seqs, int chunks,
                                                           bf16x8* __restrict__ dst) {
   int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= n_seqs) return;
   int lane = threadIdx.x & 63;
-  int64_t s = ((int64_t)cu[b + 1] - 1) * chunks, d = (int64_t)b * chunks;
+  const int32_t s1 = cu[b + 1];
+  int64_t s = ((int64_t)s1 - 1) * chunks, d = (int64_t)b * chunks;
+  if (s1 <= cu[b]) {
+    if (lane == 0) atomicAdd(&g_bad_token_ids, 1u);
+    bf16x8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.f;
+    for (int c = lane; c < chunks; c += 64) dst[d + c] = z;
+    return;
+  }
   for (int c = lane; c < chunks; c += 64) dst[d + c] = src[s + c];
 }
 
@@ -544,7 +556,10 @@ extern "C" int lrx_gather_last_rows(const void* src, const int32_t* cu_seqlens, 
 
 __global__ void __launch_bounds__(256) k_gather_rows_u32(const uint32_t* __restrict__ src, const int32_t* __restrict__ cu, int n_seqs, uint32_t* __restrict__ dst) {
   const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b < n_seqs) dst[b] = src[cu[b + 1] - 1];
+  if (b >= n_seqs) return;
+  const int32_t s1 = cu[b + 1];
+  if (s1 <= cu[b]) { atomicAdd(&g_bad_token_ids, 1u); dst[b] = 0u; return; }
+  dst[b] = src[s1 - 1];
 }
 int lrx_gather_rows_u32(const void* src, const int32_t* cu_seqlens, int32_t n_seqs, void* dst, hipStream_t stream) {
   if (n_seqs == 0) return LRX_OK;
@@ -559,7 +574,12 @@ __global__ void __launch_bounds__(256) k_scatter_last_rows(const bf16x8* __restr
   int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= n_seqs) return;
   int lane = threadIdx.x & 63;
-  int64_t d = ((int64_t)cu[b + 1] - 1) * dst_chunks, s = (int64_t)b * chunks;
+  const int32_t s1 = cu[b + 1];
+  if (s1 <= cu[b]) {                                                    // (no row of dst belongs to an empty sequence: nothing is written)
+    if (lane == 0) atomicAdd(&g_bad_token_ids, 1u);
+    return;
+  }
+  int64_t d = ((int64_t)s1 - 1) * dst_chunks, s = (int64_t)b * chunks;
   for (int c = lane; c < chunks; c += 64) dst[d + c] = src[s + c];
 }
 

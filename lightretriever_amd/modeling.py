@@ -593,8 +593,9 @@ class LrxExactSearchModel:
         if bad < 0 or sat < 0:
             raise _lib.LrxError(f"{what}: reading the device counters failed")
         if bad:
-            raise _lib.LrxError(f"{what}: {bad} device-side input error(s) (token ids outside the embedding table or an attention work list that "
-                                "did not fit): the rows of this call are not the model's")
+            raise _lib.LrxError(f"{what}: {bad} device-side input error(s) (token ids outside the embedding table, an attention work list that "
+                                "did not fit, or a sequence that is empty or shorter than its pooling strategy needs -- such a sequence gets a "
+                                "zero row): the rows of this call are not the model's")
         if sat:
             msg = (f"{what}: {sat} wave instruction(s) met q|k|v / projection-operand / embedding elements that were NaN or beyond fp16's +-65504 and "
                    "stored them as +-65504: the embeddings of this call are not the model's (broken checkpoint, or activations outside the range the "

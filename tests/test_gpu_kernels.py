@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import attn_reference as AR
+import elementwise_reference as ER
 from oracle import lrx_oracle as O
 from helpers import GOLDEN
 
@@ -214,18 +215,31 @@ def test_attention_forced_max_jump():
     attn_within_bound(got, *AR.causal_gqa_fp64(f16_t(qkv), cu, nq, nkv, d))
 
 
+def pool_norm_bf16_by_the_rounding_rule(got, x, w, cu, pooling, out_dim, normalize, eps=1e-5):
+    """The comparison rule of tests/elementwise_reference.py for k_pool_norm on a bf16 stream: every pooled token's final-norm row is HF's
+    bf16(w * bf16(x * rstd)) BIT FOR BIT, except where the float64 x * rstd lies within the kernel's derived fp32 error budget of a bf16
+    rounding boundary (either neighbour there; at most 2 % of the elements, proven on the host for these inputs); the mean adds the tokens
+    in fp32.  A normalised result is held against the float64 normalisation of the kernel's own un-normalised rows, which are checked first."""
+    from lightretriever_amd import ops
+    H = x.shape[1]
+    _, info = ER.pool_norm(x, w, cu, eps, pooling, out_dim, False, f32=False)
+    un = got if not normalize else ops.pool_norm(bf16_t(x), bf16_t(w), torch.from_numpy(np.asarray(cu, np.int32)).to(dev()), eps, out_dim, False, pooling=pooling)
+    un = f32(un).astype(np.float64)
+    lo, hi, share = ER.pool_allowed(info, w, H, out_dim, f32=False)
+    assert share <= ER.NEAR_CAP
+    single = np.array([t is not None and len(t) == 1 for t in info["tokens"]])[:, None]
+    ok = np.where(single, (un == lo) | (un == hi), (un >= lo) & (un <= hi))
+    assert ok.all(), f"{int((~ok).sum())} / {ok.size} elements outside what the rounding rule allows, first at {np.argwhere(~ok)[0].tolist()}"
+    if normalize:
+        ER.assert_rel(f32(got), ER.l2_normalize(un), ER.normalize_budget(out_dim), "normalised")
+
+
 @pytest.mark.parametrize("H,out_dim,normalize", [(256, 256, True), (256, 64, True), (2048, 2048, True), (2048, 256, False)])
 def test_pool_norm(H, out_dim, normalize):
     from lightretriever_amd import ops
-    rng = np.random.default_rng(H + out_dim)
-    lens = [3, 1, 40, 17]
-    T = sum(lens)
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    x, w = rnd(rng, T, H, scale=2.0), O.round_bf16(1 + 0.1 * rng.standard_normal(H).astype(np.float32))
+    x, w, cu = ER.legacy_pool_inputs(H, out_dim, [3, 1, 40, 17])                        # (the seeds this test always had)
     got = ops.pool_norm(bf16_t(x), bf16_t(w), torch.from_numpy(cu).to(dev()), 1e-5, out_dim, normalize)
-    pooled = O.lasttoken_pool_packed(O.rmsnorm(x, w, 1e-5, bf16=True), cu)[:, :out_dim]
-    want = O.l2_normalize(pooled) if normalize else pooled
-    np.testing.assert_allclose(f32(got), want, atol=3e-3 if not normalize else 3e-4, rtol=1e-2)
+    pool_norm_bf16_by_the_rounding_rule(got, x, w, cu, "lasttoken", out_dim, normalize)
     if normalize:
         np.testing.assert_allclose(np.linalg.norm(f32(got), axis=1), 1.0, atol=1e-5)
 
@@ -250,17 +264,13 @@ def test_pool_norm_strategies_against_the_reference_pooling(pooling):
         want = O.pool_padded(hn, m, pooling)
         np.testing.assert_allclose(f32(got)[:, :H] / np.float32(np.sqrt(64 / H)), want, atol=2e-6, err_msg=name)
         np.testing.assert_allclose(O.pool_padded(g[f"fn_{name}_hidden"], m, pooling), g[f"fn_{name}_{pooling}"], atol=1e-6)   # (the restatement is the reference's)
-    rng = np.random.default_rng(5)
-    lens = [3, 40, 17, 129, 5]
-    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    x, w = rnd(rng, sum(lens), 256, scale=2.0), O.round_bf16(1 + 0.1 * rng.standard_normal(256).astype(np.float32))
+    x, w, cu = ER.legacy_strategy_inputs([3, 40, 17, 129, 5])                            # (the seed this test always had)
     for out_dim, normalize in ((256, True), (64, True), (256, False)):
         got32 = ops.pool_norm(torch.from_numpy(x).to(dev()), bf16_t(w), torch.from_numpy(cu).to(dev()), 1e-5, out_dim, normalize, pooling=pooling)
         pooled = O.pool_packed(O.rmsnorm(x, w, 1e-5, bf16=False), cu, pooling)[:, :out_dim]
         np.testing.assert_allclose(f32(got32), O.l2_normalize(pooled) if normalize else pooled, atol=2e-5, rtol=1e-5)
         got16 = ops.pool_norm(bf16_t(x), bf16_t(w), torch.from_numpy(cu).to(dev()), 1e-5, out_dim, normalize, pooling=pooling)
-        pooled16 = O.pool_packed(O.rmsnorm(O.round_bf16(x), w, 1e-5, bf16=True), cu, pooling)[:, :out_dim]
-        np.testing.assert_allclose(f32(got16), O.l2_normalize(pooled16) if normalize else pooled16, atol=3e-3 if not normalize else 3e-4, rtol=1e-2)
+        pool_norm_bf16_by_the_rounding_rule(got16, x, w, cu, pooling, out_dim, normalize)
     # the two-layer strategies need a second hidden state: not this entry point's (lrx_encode_packed_pooled serves them) -- refused, not guessed
     if pooling == "mean":
         for st in ("avg_first_last", "avg_top2"):
