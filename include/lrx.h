@@ -219,7 +219,7 @@ int64_t lrx_device_error_count(int32_t reset);
  * selection start, selection done, first main K loop done, thresholds seen, ..., end); this copies the first n_words of them to the host.     */
 int lrx_probe_fused_timestamps(uint64_t* out, int32_t n_words);
 /* (ABI 5) fp16 range events since the last reset: q|k|v elements of the fused QKV + RoPE epilogue and fp16-shadow elements of pooled rows
- * that were NaN or beyond +-65504 and were stored as a finite +-65504 (counted once per wave instruction that saw any, so "0 or not" is
+ * that were beyond +-65504 and were stored as +-65504, or NaN and were stored as -65504 (counted once per wave instruction that saw any, so "0 or not" is
  * the meaningful reading).  0 on every checkpoint whose q|k|v stay inside fp16's range -- the precondition of the fp16 attention path;
  * a non-zero count means the embeddings of that call are not the model's.  -1 if the read failed.  SYNCHRONISES like the call above. */
 int64_t lrx_device_saturation_count(int32_t reset);

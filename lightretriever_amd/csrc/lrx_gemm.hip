@@ -50,10 +50,10 @@ struct RopeArgs {
 };
 
 __device__ __forceinline__ __bf16 f2h_bits(float v) {   // fp16 (saturating) in the kernel's 16-bit container type
-  return __builtin_bit_cast(__bf16, (_Float16)fminf(fmaxf(v, -65504.f), 65504.f));
+  return __builtin_bit_cast(__bf16, (_Float16)fminf(fmaxf(v, -65504.f), 65504.f));   // NaN -> -65504: fmaxf(NaN, -65504) is -65504
 }
-// q|k|v elements of the fused QKV epilogue that left fp16's range (|v| > 65504) or were NaN -- both become a finite 65504 in the store
-// above, which is a silent change of the model's arithmetic: counted here, read by lrx_device_saturation_count (one atomic per wave
+// q|k|v elements of the fused QKV epilogue that left fp16's range (|v| > 65504) or were NaN -- the former are stored as +-65504 by sign,
+// a NaN as -65504 (tests/test_gpu_gemm_reference.py pins it) -- which is a silent change of the model's arithmetic: counted here, read by lrx_device_saturation_count (one atomic per wave
 // that saw any, i.e. none on a healthy checkpoint).
 __device__ unsigned int g_qkv_fp16_saturations = 0;
 unsigned int lrx_gemm_saturations(int* ok) {                 // read only: lrx_device_saturation_count resets after BOTH counters were read

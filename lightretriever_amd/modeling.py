@@ -568,7 +568,7 @@ class LrxExactSearchModel:
     # What encode() / encode_queries() do when the device counters of the calls they made are non-zero (read ONCE per call, after the last
     # batch was enqueued: one blocking 8-byte copy per corpus chunk).  lrx_device_error_count (token ids outside the embedding table, an
     # attention work list that did not fit) always raises: those rows are not the model's.  lrx_device_saturation_count (q|k|v or shadow
-    # elements that were NaN or beyond fp16's +-65504 and were stored as +-65504 -- the precondition of the fp16 attention operands,
+    # elements that were beyond fp16's +-65504 and were stored as +-65504, or NaN and were stored as -65504 -- the precondition of the fp16 attention operands,
     # csrc/lrx_gemm.hip:f2h_bits): "raise" (default), "warn" (log at WARNING with the count) or "ignore" (do not read either counter).
     on_fp16_saturation: str = "raise"
 
@@ -597,8 +597,8 @@ class LrxExactSearchModel:
                                 "did not fit, or a sequence that is empty or shorter than its pooling strategy needs -- such a sequence gets a "
                                 "zero row): the rows of this call are not the model's")
         if sat:
-            msg = (f"{what}: {sat} wave instruction(s) met q|k|v / projection-operand / embedding elements that were NaN or beyond fp16's +-65504 and "
-                   "stored them as +-65504: the embeddings of this call are not the model's (broken checkpoint, or activations outside the range the "
+            msg = (f"{what}: {sat} wave instruction(s) met q|k|v / projection-operand / embedding elements that were beyond fp16's +-65504 or NaN and "
+                   "stored them as +-65504 (a NaN as -65504): the embeddings of this call are not the model's (broken checkpoint, or activations outside the range the "
                    "fp16 operands assume -- EncoderConfig(operand_dtype='bf16') keeps the projection operands in bf16; q|k|v stay fp16)")
             if self.on_fp16_saturation == "raise":
                 raise _lib.LrxError(msg)

@@ -80,6 +80,19 @@ def gemm_qkv_rope(A: torch.Tensor, Wqkv: torch.Tensor, positions: torch.Tensor, 
     return out
 
 
+def gemm_qkv_rope_slice(A: torch.Tensor, Wqkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, nq: int, nkv: int,
+                        d: int, head0: int, n_heads: int, out: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                        rscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """lrx_gemm_qkv_rope_slice: heads [head0, head0 + n_heads) of the projection (Wqkv / bias are the FULL matrices) into their columns of
+    `out`, fp16 [M, (nq+2nkv)d]; every other column of `out` is left alone."""
+    M, K = A.shape
+    if out.dtype != torch.float16 or out.shape != (M, (nq + 2 * nkv) * d) or not out.is_contiguous():
+        raise ValueError("gemm_qkv_rope_slice: out must be contiguous fp16 [M, (nq+2nkv)d]")
+    _lib.check(_lib.lib().lrx_gemm_qkv_rope_slice(_lib.ptr(A), _lib.ptr(Wqkv), _lib.ptr(out), _lib.ptr(bias), _lib.ptr(positions), _lib.ptr(cos),
+                                                  _lib.ptr(sin), M, K, nq, nkv, d, _lib.ptr(rscale), head0, n_heads, _s()))
+    return out
+
+
 def gemm_resid32(A: torch.Tensor, B: torch.Tensor, x32: torch.Tensor, gamma: Optional[torch.Tensor] = None, want_a16: bool = True, want_ss: bool = False):
     """lrx_gemm_bf16_nt_resid32: x32 (fp32 [M,N], in place) += A . B^T -> (a16 bf16 [M,N] = bf16(x32 * gamma) or None, ss_part or None)."""
     M, K = A.shape
@@ -207,15 +220,19 @@ def flat_ip_scores(X: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
 
 # -- sparse document vectors (N2) ------------------------------------------------------------------------------------------
 def sparse_max_aggregate(hidden: torch.Tensor, lm_head: torch.Tensor, cu_seqlens: torch.Tensor, tok_mask: Optional[torch.Tensor] = None,
-                         bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """hidden bf16 [T,H], lm_head bf16 [V,H], tok_mask uint8 [T] (None = drop first/last token) -> fp32 [B,V] running maxima."""
+                         bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hidden bf16 [T,H], lm_head bf16 [V,H], tok_mask uint8 [T] (None = drop first/last token) -> fp32 [B,V] running maxima
+    (out: fp32 [B, >= V] with unit inner stride to write them into; its columns from V on are left alone)."""
     T, H = hidden.shape
     V, B = lm_head.shape[0], cu_seqlens.numel() - 1
     if lm_head.shape[1] != H or hidden.dtype != torch.bfloat16 or lm_head.dtype != torch.bfloat16:
         raise ValueError("sparse_max_aggregate: hidden [T,H] / lm_head [V,H] must be bf16 with matching H")
     if tok_mask is not None and (tok_mask.dtype != torch.uint8 or tok_mask.numel() != T):
         raise ValueError("sparse_max_aggregate: tok_mask must be uint8 [T]")
-    out = torch.empty(B, V, dtype=torch.float32, device=hidden.device)
+    if out is None:
+        out = torch.empty(B, V, dtype=torch.float32, device=hidden.device)
+    elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < V or out.stride(1) != 1:
+        raise ValueError("sparse_max_aggregate: out must be fp32 [B, >= V] with unit inner stride")
     seg = torch.empty(T, dtype=torch.int32, device=hidden.device)
     _lib.check(_lib.lib().lrx_sparse_max_aggregate(_lib.ptr(hidden), _lib.ptr(lm_head), _lib.ptr(bias) if bias is not None else None,
                                                    _lib.ptr(cu_seqlens), _lib.ptr(tok_mask) if tok_mask is not None else None, B, T, H, V,
