@@ -23,6 +23,10 @@
 //                                     per-query candidate lists (per-wave LDS lists, one reservation per (wave, query) per flush).
 //                                     (More than 128 queries over a shadow of D >= 1024: BOTH passes run on the GEMM kernel, lrx_gemm.hip
 //                                     EPI_SAMPLE / EPI_EMIT, in WIDE chunks of up to 1024 queries -- chunk_queries, round 6.)
+//     shared by these kernels:        filter_block_of (launch index -> corpus block), XregLds (LDS geometry per QT and q ring depth), QProducer
+//                                     (the producer wave's q ring), xreg_block_kloop (K loop of one block step of k_filter_xreg; the fused
+//                                     kernel's sample block keeps a copy), WalkPlan / XregWalk (the persistent walk of _emit and _store),
+//                                     wave_row_max, stage_store_rows + StorePlain / StoreNontemporal (scores through LDS as whole row segments).
 //     launch_scores(), k_pack_queries_xb, k_round_queries: query planes / fragment order + the chain's zero-fills; kernel dispatch.
 //  B. Selection
 //     radix_select_kth*, select_topk_sorted, bitonic_sort_desc: exact k-th / top-k of a score row or a candidate list (one workgroup).

@@ -225,8 +225,7 @@ k_sample_threshold(const float* __restrict__ scores, int64_t ld_s, int64_t Ns, i
 #endif
 template <int QT>
 struct FusedLds {
-  static constexpr int SAMPLE = ((QT > 8 ? 2 : 4) * 2 * QT * 1024) > 16 * (128 * 4 + 16) ? ((QT > 8 ? 2 : 4) * 2 * QT * 1024) : 16 * (128 * 4 + 16);
-  static constexpr int A = EmitLds<QT>::BYTES > SAMPLE ? EmitLds<QT>::BYTES : SAMPLE;
+  static constexpr int A = EmitLds<QT>::EMIT_BYTES > BlockLds<QT>::BLOCK_BYTES ? EmitLds<QT>::EMIT_BYTES : BlockLds<QT>::BLOCK_BYTES;   // phases M, S
   static constexpr int BYTES = A > (int)sizeof(ThrShared) + 64 ? A : (int)sizeof(ThrShared) + 64;
 };
 

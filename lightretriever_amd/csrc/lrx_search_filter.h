@@ -20,6 +20,88 @@ __device__ __forceinline__ __bf16 f2h_bits(float v) { return __builtin_bit_cast(
 #define S_XTILE (S_ROWS * S_BK * 4)
 #define SP_ROWS 128      // corpus rows per workgroup of the split-bf16 kernel
 
+// ---------------------------------------------------------------------------------------------------------------
+// Pieces the score / filter kernels of this file share: the launch index -> corpus block mapping and the epilogues.
+// ---------------------------------------------------------------------------------------------------------------
+// bmode selects the blocks a filter launch covers: 0 = all, 1 = the sample, 2 = all blocks that are not in the sample.  Sample units of
+// `unit` consecutive blocks, every ss-th unit is in the sample.  I = the type the arithmetic runs in: unsigned in the register-streaming
+// kernels (all < 2^25), int64_t in k_flat_ip_scores_split.
+template <typename I>
+__device__ __forceinline__ I filter_block_of(int bmode, int ss, int unit, I i) {
+  if (bmode == 1) { const I u = i / (I)unit; return u * (I)ss * (I)unit + (i - u * (I)unit); }
+  if (bmode != 2) return i;
+  const I u = i / (I)unit, g = u / (I)(ss - 1);
+  return (g * (I)ss + 1 + (u - g * (I)(ss - 1))) * (I)unit + (i - u * (I)unit);
+}
+
+// D[i = corpus row][j = query]: a lane holds one query and rows n + 16 a + {0..3} of the NT accumulator tiles v[a * stride].  Rows past N
+// are masked to -FLT_MAX in place; returns the query's maximum over the 16 NT rows of the wave.
+template <int NT>
+__device__ __forceinline__ float wave_row_max(f32x4* v, int stride, int64_t n, int64_t N) {
+  float mx = -FLT_MAX;
+#pragma unroll
+  for (int a = 0; a < NT; ++a)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (n + a * 16 + e >= N) v[a * stride][e] = -FLT_MAX;
+      mx = fmaxf(mx, v[a * stride][e]);
+    }
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  return fmaxf(mx, __shfl_xor(mx, 32, 64));
+}
+
+// Scores: the accumulator layout would store 64-B pieces into 16 different query rows per instruction (measured: 0.18 ms of
+// the 1.8 ms filter pass at Q = 100).  Staged through LDS instead -- [query][RB rows] with a 16-B pad per query, conflict-free
+// ds_write_b128 -- and written as whole RB*4-byte row segments, 1 KiB contiguous per wave instruction.
+// The final store of a staged piece: plain or nontemporal.
+struct StorePlain {
+  static constexpr int BYTES = 16;
+  __device__ __forceinline__ void operator()(float* dst, const char* src) const { *(f32x4*)dst = *(const f32x4*)src; }
+};
+struct StoreNontemporal {
+  static constexpr int BYTES = 16;
+  __device__ __forceinline__ void operator()(float* dst, const char* src) const { __builtin_nontemporal_store(*(const f32x4*)src, (f32x4*)dst); }
+};
+// pass ps of the staging: q-tiles ps * QPT .. of the wave's NT tiles v[a * QT + b] (WV waves, RB = 16 NT WV rows) -> stg[query][RB rows + pad]
+template <int QT, int NT, int WV, int QPT>
+__device__ __forceinline__ void stage_rows(char* stg, const f32x4* v, int ps, int wave, int fi, int fq) {
+  constexpr int SEG = 16 * NT * WV * 4 + 16;
+#pragma unroll
+  for (int b = 0; b < QT; ++b) {
+    if (b / QPT == ps) {
+#pragma unroll
+      for (int a = 0; a < NT; ++a) *(f32x4*)(stg + ((b - ps * QPT) * 16 + fi) * SEG + (wave * 16 * NT + a * 16 + fq * 4) * 4) = v[a * QT + b];
+    }
+  }
+}
+// the staged rows of queries q0 .. q0 + nrows - 1 -> dst[query * ld + 0 .. RB), by NTHR threads
+template <int RB, int NTHR, class ST>
+__device__ __forceinline__ void store_staged_rows(const char* stg, int tid, int nrows, int q0, int nq, float* __restrict__ dst, int64_t ld, ST st) {
+  constexpr int SEG = RB * 4 + 16, CH = RB * 4 / ST::BYTES;
+  for (int idx = tid; idx < nrows * CH; idx += NTHR) {
+    const int ql = idx / CH, c = idx % CH;
+    const int qi = q0 + ql;
+    if (qi < nq) st(dst + (int64_t)qi * ld + c * (ST::BYTES / 4), stg + ql * SEG + c * ST::BYTES);
+  }
+}
+// the whole epilogue: NPASS passes of QPT q-tiles through the LDS_BYTES at smem (dead by now); every thread of the workgroup calls it, waves
+// >= WV (a producer) only take part in the barriers
+template <int QT, int NT, int WV, int LDS_BYTES, int NTHR, class ST>
+__device__ __forceinline__ void stage_store_rows(char* smem, const f32x4* v, int tid, int wave, int fi, int fq, int nq, float* __restrict__ dst, int64_t ld, ST st) {
+  constexpr int RB = 16 * NT * WV, SEG = RB * 4 + 16;
+  constexpr int QPT = (LDS_BYTES / SEG / 16) < QT ? (LDS_BYTES / SEG / 16) : QT;   // q-tiles staged per pass
+  static_assert(QPT >= 1, "epilogue staging does not fit");
+  constexpr int NPASS = (QT + QPT - 1) / QPT;
+#pragma unroll
+  for (int ps = 0; ps < NPASS; ++ps) {
+    __syncthreads();
+    if (NTHR == 64 * WV || wave < WV) stage_rows<QT, NT, WV, QPT>(smem, v, ps, wave, fi, fq);
+    __syncthreads();
+    const int nqt = (QT - ps * QPT) < QPT ? (QT - ps * QPT) : QPT;
+    store_staged_rows<RB, NTHR>(smem, tid, nqt * 16, ps * QPT * 16, nq, dst, ld, st);
+  }
+}
+
 template <int QT>
 __global__ void __launch_bounds__(256, 1)
 k_flat_ip_scores(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const float* __restrict__ Q, int nq,
@@ -266,13 +348,7 @@ k_flat_ip_scores_split(const float* __restrict__ X, int64_t N, int64_t ldx, int 
   // workgroups return at once when nothing overflowed, and 78 k of them over a 10M-row shard still cost 19 us)
   for (int64_t bx = blockIdx.x; bx < nbx; bx += gridDim.x) {
   if (bx != (int64_t)blockIdx.x) __syncthreads();   // the previous block's LDS is dead
-  int64_t blk = bx;                                // sample units of `unit` consecutive blocks, every ss-th unit is in the sample
-  if (bmode == 1) { const int u = (int)(bx / unit); blk = (int64_t)u * ss * unit + (bx - (int64_t)u * unit); }
-  else if (bmode == 2) {
-    const int u = (int)(bx / unit), g = u / (ss - 1);
-    blk = ((int64_t)g * ss + 1 + (u - g * (ss - 1))) * unit + (bx - (int64_t)u * unit);
-  }
-  const int64_t n0 = blk * RB;                     // corpus rows of this workgroup
+  const int64_t n0 = filter_block_of<int64_t>(bmode, ss, unit, bx) * RB;   // corpus rows of this workgroup
   const int64_t n0s = bx * RB;    // where its scores go (compact in sample mode)
 
   const float* px[2 * RT];
@@ -415,18 +491,7 @@ k_flat_ip_scores_split(const float* __restrict__ X, int64_t N, int64_t ldx, int 
 #pragma unroll
   for (int b = 0; b < QT; ++b) {
     int qi = b * 16 + fi;
-    float mx = -FLT_MAX;
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-      int64_t n = n0 + wave * 16 * RT + a * 16 + fq * 4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (n + e >= N) acc[a][b][e] = -FLT_MAX;
-        mx = fmaxf(mx, acc[a][b][e]);
-      }
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mx = wave_row_max<RT>(&acc[0][b], QT, n0 + wave * 16 * RT + fq * 4, N);
     if (fq == 0) wmax[wave * (QT * 16) + qi] = mx;
   }
   __syncthreads();
@@ -441,33 +506,7 @@ k_flat_ip_scores_split(const float* __restrict__ X, int64_t N, int64_t ldx, int 
       }
     }
   }
-  // Scores: the accumulator layout would store 64-B pieces into 16 different query rows per instruction (measured: 0.18 ms of
-  // the 1.8 ms filter pass at Q = 100).  Staged through LDS instead -- [query][RB rows] with a 16-B pad per query, conflict-free
-  // ds_write_b128 -- and written as whole RB*4-byte row segments, 1 KiB contiguous per wave instruction.
-  constexpr int SEG = RB * 4 + 16;
-  constexpr int QPT = (LDS_BYTES / SEG / 16) < QT ? (LDS_BYTES / SEG / 16) : QT;   // q-tiles staged per pass
-  static_assert(QPT >= 1, "epilogue staging does not fit");
-  constexpr int NPASS = (QT + QPT - 1) / QPT;
-#pragma unroll
-  for (int ps = 0; ps < NPASS; ++ps) {
-    __syncthreads();
-#pragma unroll
-    for (int b = 0; b < QT; ++b) {
-      if (b / QPT == ps) {
-#pragma unroll
-        for (int a = 0; a < RT; ++a)
-          *(f32x4*)(smem + ((b - ps * QPT) * 16 + fi) * SEG + (wave * 16 * RT + a * 16 + fq * 4) * 4) = acc[a][b];
-      }
-    }
-    __syncthreads();
-    const int nqt = (QT - ps * QPT) < QPT ? (QT - ps * QPT) : QPT;
-    for (int idx = tid; idx < nqt * 16 * (RB / 4); idx += 64 * WV) {
-      const int ql = idx / (RB / 4), c = idx % (RB / 4);
-      const int qi = ps * QPT * 16 + ql;
-      if (qi < nq)
-        *(f32x4*)(scores + (int64_t)qi * ld + n0s + c * 4) = *(const f32x4*)(smem + ql * SEG + c * 16);
-    }
-  }
+  stage_store_rows<QT, RT, WV, LDS_BYTES, 64 * WV>(smem, &acc[0][0], tid, wave, fi, fq, nq, scores + n0s, ld, StorePlain());
   if constexpr (NP != 3) break;   // only the six-product (fallback) instantiations are ever launched with fewer workgroups than blocks;
                                   // as a real loop the single-product kernels went from 60 to 107 VGPRs (two workgroups per CU instead of three)
   }   // blocks of this workgroup
@@ -483,68 +522,83 @@ k_flat_ip_scores_split(const float* __restrict__ X, int64_t N, int64_t ldx, int 
 // Only the q k-slice, which all eight waves share, goes through LDS: a ninth PRODUCER wave requests it one slice ahead by LDS-DMA
 // (its own in-order vmcnt, so the consumers' counted waits see nothing but their X loads); one barrier per k-slice.
 // ---------------------------------------------------------------------------------------------------------------
-template <int QT, int PF, bool EMIT, int RT = 1>
-__global__ void __launch_bounds__(576, QT > 8 ? 1 : 2)
-k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, float* __restrict__ scores, int64_t ld,
-              float* __restrict__ blkmax, int nblk_ld, const int* __restrict__ gate, int bmode, int ss, int unit,
-              const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, int nlaunch, int gmax,
-              unsigned int cap) {
-  // RT = blocks per workgroup (launch indices RT * blockIdx.x + a < nlaunch): with two, the q slice is fetched once per 256 rows -- the
-  // sample pass of a 100-query search had 391 workgroups on 256 CUs, one or two per CU (56 -> 52 us; Q = 128: 61 -> 50 us)
-  static_assert(RT == 1 || !EMIT, "the emitting epilogue works on one block");
-  constexpr int WV = 8, RB = 128;
-  constexpr int QINST = 2 * QT;                    // 1-KiB LDS-DMA instructions per q slice
-  constexpr int QBYTES = QINST * 1024;
-  constexpr int SEG = RB * 4 + 16;                 // epilogue staging: one query's 128 scores + pad
-  constexpr int QB = QT > 8 ? 2 : 4;               // q ring: the producer runs QB-1 slices ahead
+// LDS geometry of the register-streaming kernels, per QT and depth of the q ring (the producer runs QB-1 slices ahead)
+// One struct for all of them; a kernel reads the total of its own form only (static members are instantiated on use): BLOCK_BYTES
+// k_filter_xreg and filter_sample_block (BlockLds), STORE_BYTES k_filter_xreg_store (QB = 4, QT <= 8), EMIT_BYTES / WCAP / WL_BYTES
+// filter_emit_body (EmitLds); FusedLds takes the larger of the sample block's and the emit body's.
+template <int QT, int QB_>
+struct XregLds {
+  static constexpr int WV = 8, RB = 128;           // consumer waves, corpus rows per block
+  static constexpr int QB = QB_;
+  static constexpr int QINST = 2 * QT;             // 1-KiB LDS-DMA instructions per q slice
+  static constexpr int QBYTES = QINST * 1024;
   static_assert((QB - 2) * QINST <= 63, "vmcnt immediate");
-  constexpr int LDS_BYTES = QB * QBYTES > 16 * SEG ? QB * QBYTES : 16 * SEG;
-  __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
-  if (gate != nullptr && *gate == 0) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int64_t blks[RT], lis[RT];                       // corpus block and launch index (= where the scores go: compact in sample mode) per slot
+  static constexpr int SEG = RB * 4 + 16;          // epilogue staging: one query's 128 scores + pad
+  static constexpr int BLOCK_BYTES = QB * QBYTES > 16 * SEG ? QB * QBYTES : 16 * SEG;   // one-block kernels: the epilogue stages through the dead q ring
+  static constexpr int STORE_BYTES = QB * QBYTES + QT * 16 * SEG;                       // persistent store: q ring + a staging region of its own
+  // persistent emit: q ring + per-wave hit lists + thresholds.
+  // hits a wave parks in LDS: as many as the 160 KiB of the CU allow next to the q ring (one workgroup per CU).  A pass emits ~5 000 hits per
+  // query, i.e. 2.4 x queries per wave: with 320 entries most waves of a 100-query pass had to flush once in mid-pass (one memory-side atomic
+  // per hit, the wave waits, the workgroup waits for it at the next barrier): 630 us against 580 us for the same pass with hardly any hits
+  static constexpr int WQC_BYTES = QT * 16 * 4;    // per wave: hits per query of a mid-pass flush, then the first global slot (see flush)
+  static constexpr int WCAP_FIT = ((160 * 1024 - QB * QBYTES - QT * 64 - 1024 - WV * (WQC_BYTES + 16)) / (WV * 12)) / 64 * 64;
+  static constexpr int WCAP = WCAP_FIT > 1024 ? 1024 : WCAP_FIT;
+  static constexpr int WL_BYTES = WCAP * 12 + 16 + WQC_BYTES;
+  static constexpr int EMIT_BYTES = QB * QBYTES + WV * WL_BYTES + QT * 16 * 4;
+};
+template <int QT> using BlockLds = XregLds<QT, (QT > 8 ? 2 : 4)>;   // k_filter_xreg, filter_sample_block
+template <int QT> using EmitLds = XregLds<QT, (QT > 8 ? 3 : 4)>;    // filter_emit_body (k_filter_xreg_emit, k_filter_fused)
+
+// The producer wave's side of the q ring: the q slices by LDS-DMA, cyclically (slice hs into ring buffer hb), QB-1 steps ahead of the consumers.
+template <int QT, int QB>
+struct QProducer {
+  using L = XregLds<QT, QB>;
+  char* smem;
+  const __bf16* pq;
+  int nk, hs = 0, hb = 0;                          // head: slice and ring buffer
+  __device__ __forceinline__ QProducer(char* smem, const __bf16* qs, int lane, int nk) : smem(smem), pq(qs + (int64_t)lane * 8), nk(nk) {}
+  __device__ __forceinline__ void stage_next() {
+    char* sQ = smem + hb * L::QBYTES;
 #pragma unroll
-  for (int a = 0; a < RT; ++a) {
-    const int li = min((int)blockIdx.x * RT + a, nlaunch - 1);   // (an odd one out: the last block again, nothing stored)
-    int64_t blk = li;
-    if (bmode == 1) { const int u = li / unit; blk = (int64_t)u * ss * unit + (li - u * unit); }
-    else if (bmode == 2) {
-      const int u = li / unit, g = u / (ss - 1);
-      blk = ((int64_t)g * ss + 1 + (u - g * (ss - 1))) * unit + (li - u * unit);
-    }
-    blks[a] = blk;
-    lis[a] = li;
+    for (int j = 0; j < L::QINST; ++j)
+      __builtin_amdgcn_global_load_lds((gptr_t)(pq + ((int64_t)hs * L::QINST + j) * 512), (lptr_t)(sQ + j * 1024), 16, 0, 0);
+    hs = hs + 1 == nk ? 0 : hs + 1;
+    hb = hb + 1 == QB ? 0 : hb + 1;
   }
-  const int nk = D / 64;
-  const int fi = lane & 15, fq = lane >> 4;
-
-  f32x4 acc[RT][QT];
+  // qres: the whole q fits the ring and is staged once, with one barrier; otherwise `total` steps follow
+  template <typename T>
+  __device__ __forceinline__ void start(bool qres, T total) {
+    if (qres) {
+      for (int p = 0; p < nk; ++p) stage_next();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+    } else {
 #pragma unroll
-  for (int a = 0; a < RT; ++a)
-#pragma unroll
-    for (int b = 0; b < QT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (wave == WV) {
-    // ---- producer: q slice kt+1 requested while the consumers work on kt
-    const __bf16* pq = qs + (int64_t)lane * 8;
-    auto stage_q = [&](int kt) {
-      char* sQ = smem + (kt % QB) * QBYTES;
-#pragma unroll
-      for (int j = 0; j < QINST; ++j)
-        __builtin_amdgcn_global_load_lds((gptr_t)(pq + ((int64_t)kt * QINST + j) * 512), (lptr_t)(sQ + j * 1024), 16, 0, 0);
-    };
-#pragma unroll
-    for (int p = 0; p < QB - 1; ++p)
-      if (p < nk) stage_q(p);
-    for (int kt = 0; kt < nk; ++kt) {
-      if (kt + QB - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((QB - 2) * QINST) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();                // q(kt) is in LDS; every consumer has finished slice kt-1 -> its buffer is free
-      if (kt + QB - 1 < nk) stage_q(kt + QB - 1);
+      for (int p = 0; p < QB - 1; ++p)
+        if (p < total) stage_next();
     }
+  }
+  template <typename T>
+  __device__ __forceinline__ void step(T g, T total) {
+    if (g + QB - 2 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((QB - 2) * L::QINST) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                  // q(g) is in LDS; the consumers are done with step g-1 -> its buffer is free
+    if (g + QB - 1 < total) stage_next();
+  }
+};
+
+// The K loop of ONE step of RT blocks (blks: their corpus blocks), called by all nine waves: the producer requests q slice kt+1.. while the
+// consumers work on kt; consumer wave w owns rows 16w .. 16w+15 of each block.  One barrier per k-slice on either side.
+template <int QT, int PF, int RT, int QB>
+__device__ __forceinline__ void xreg_block_kloop(char* smem, const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs,
+                                                 const int64_t (&blks)[RT], f32x4 (&acc)[RT][QT], int wave, int lane) {
+  using L = XregLds<QT, QB>;
+  const int nk = D / 64;
+  if (wave == L::WV) {
+    QProducer<QT, QB> p(smem, qs, lane, nk);
+    p.start(false, nk);
+    for (int kt = 0; kt < nk; ++kt) p.step(kt, nk);
   } else {
-    // ---- consumers: wave w owns rows 16w .. 16w+15 of each block
     const bf16x8* px[RT];                          // + kt*1024 (+64: k-step 1)
 #pragma unroll
     for (int a = 0; a < RT; ++a) px[a] = (const bf16x8*)(Xb + (min(blks[a], (N - 1) >> 7) * (int64_t)(D / 64)) * 8192 + wave * 1024) + lane;
@@ -561,7 +615,7 @@ k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __r
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      const char* sQ = smem + (kt % QB) * QBYTES + lane * 16;
+      const char* sQ = smem + (kt % QB) * L::QBYTES + lane * 16;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -595,6 +649,39 @@ k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __r
         if (kt0 + u < nk) step(u, kt0 + u, kt0 + u + PF - 1 < nk);
     }
   }
+}
+
+template <int QT, int PF, bool EMIT, int RT = 1>
+__global__ void __launch_bounds__(576, QT > 8 ? 1 : 2)
+k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, float* __restrict__ scores, int64_t ld,
+              float* __restrict__ blkmax, int nblk_ld, const int* __restrict__ gate, int bmode, int ss, int unit,
+              const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, int nlaunch, int gmax,
+              unsigned int cap) {
+  // RT = blocks per workgroup (launch indices RT * blockIdx.x + a < nlaunch): with two, the q slice is fetched once per 256 rows -- the
+  // sample pass of a 100-query search had 391 workgroups on 256 CUs, one or two per CU (56 -> 52 us; Q = 128: 61 -> 50 us)
+  static_assert(RT == 1 || !EMIT, "the emitting epilogue works on one block");
+  using L = BlockLds<QT>;
+  constexpr int WV = L::WV, RB = L::RB;
+  __shared__ __attribute__((aligned(1024))) char smem[L::BLOCK_BYTES];
+  if (gate != nullptr && *gate == 0) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int64_t blks[RT], lis[RT];                       // corpus block and launch index (= where the scores go: compact in sample mode) per slot
+#pragma unroll
+  for (int a = 0; a < RT; ++a) {
+    const int li = min((int)blockIdx.x * RT + a, nlaunch - 1);   // (an odd one out: the last block again, nothing stored)
+    blks[a] = filter_block_of<unsigned int>(bmode, ss, unit, (unsigned int)li);
+    lis[a] = li;
+  }
+  const int fi = lane & 15, fq = lane >> 4;
+
+  f32x4 acc[RT][QT];
+#pragma unroll
+  for (int a = 0; a < RT; ++a)
+#pragma unroll
+    for (int b = 0; b < QT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  xreg_block_kloop<QT, PF, RT, L::QB>(smem, Xb, N, D, qs, blks, acc, wave, lane);
   if constexpr (EMIT) {
     if (wave == WV) return;
     float t[QT];
@@ -630,9 +717,6 @@ k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __r
     return;
   }
   float* wmax = (float*)smem;  // [8 waves][QT*16]
-  constexpr int QPT = (LDS_BYTES / SEG / 16) < QT ? (LDS_BYTES / SEG / 16) : QT;   // q-tiles staged per pass
-  static_assert(QPT >= 1, "epilogue staging does not fit");
-  constexpr int NPASS = (QT + QPT - 1) / QPT;
 #pragma unroll
   for (int a = 0; a < RT; ++a) {
     if (a > 0 && (int)blockIdx.x * RT + a >= nlaunch) break;     // (uniform)
@@ -669,22 +753,7 @@ k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __r
           blkmax[(int64_t)t * nblk_ld + lis[a]] = mx;
         }
     }
-#pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {
-      __syncthreads();
-      if (wave < WV) {
-#pragma unroll
-        for (int b = 0; b < QT; ++b)
-          if (b / QPT == ps) *(f32x4*)(smem + ((b - ps * QPT) * 16 + fi) * SEG + (wave * 16 + fq * 4) * 4) = acc[a][b];
-      }
-      __syncthreads();
-      const int nqt = (QT - ps * QPT) < QPT ? (QT - ps * QPT) : QPT;
-      for (int idx = tid; idx < nqt * 16 * (RB / 4); idx += 576) {
-        const int ql = idx / (RB / 4), c = idx % (RB / 4);
-        const int qi = ps * QPT * 16 + ql;
-        if (qi < nq) *(f32x4*)(scores + (int64_t)qi * ld + n0s + c * 4) = *(const f32x4*)(smem + ql * SEG + c * 16);
-      }
-    }
+    stage_store_rows<QT, 1, WV, L::BLOCK_BYTES, 576>(smem, &acc[a][0], tid, wave, fi, fq, nq, scores + n0s, ld, StorePlain());
   }
 }
 
@@ -698,17 +767,91 @@ k_filter_xreg(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __r
 // CU with half the LDS each, one block at a time, so that one's epilogue runs under the other's loads -- 96 VGPRs, 78 KiB LDS, correct, and
 // 1.25M x 256 / Q = 100 went from 0.201-0.206 to 0.276-0.284 ms, 10M x 256 from 0.99 to 1.26: with one block in work the q fragments are read
 // from LDS once per block instead of once per two, and that, not the epilogue, is what the narrow-row pass is short of.  Q = 1, 32: no change.)
-// LDS bytes of the persistent emitting pass (q ring + per-wave hit lists + thresholds)
-template <int QT>
-struct EmitLds {
-  static constexpr int WV = 8;
-  static constexpr int QBYTES = 2 * QT * 1024;
-  static constexpr int QB = QT > 8 ? 3 : 4;
-  static constexpr int WQC_BYTES = QT * 16 * 4;
-  static constexpr int WCAP_FIT = ((160 * 1024 - QB * QBYTES - QT * 64 - 1024 - WV * (WQC_BYTES + 16)) / (WV * 12)) / 64 * 64;
-  static constexpr int WCAP = WCAP_FIT > 1024 ? 1024 : WCAP_FIT;
-  static constexpr int WL_BYTES = WCAP * 12 + 16 + WQC_BYTES;
-  static constexpr int BYTES = QB * QBYTES + WV * WL_BYTES + QT * 16 * 4;
+// A persistent workgroup's blocks: launch indices blockIdx.x + i * gridDim.x, i < nbw (the counts differ by at most one block over the grid),
+// walked RT at a time; an odd one out at the end is worked on with its own block in the second slot (cache hits, result dropped)
+template <int RT, int QB>
+struct WalkPlan {
+  int nbw, nmine, nk;                              // blocks, steps of RT blocks (>= 1), k-steps per block
+  int64_t total;                                   // k-steps of this workgroup
+  bool qres;                                       // the whole q fits the ring (D <= 256): staged once, no barrier per k-step
+  __device__ __forceinline__ WalkPlan(int nblocks, int D)
+      : nbw((nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x), nmine((nbw + RT - 1) / RT), nk(D / 64), total((int64_t)nmine * nk), qres(nk <= QB) {}
+};
+
+// The consumers' side of the persistent walk: wave w owns rows 16w .. 16w+15 of each of the RT blocks in work; the X ring (PF k-slices in
+// registers) runs straight across block boundaries.
+template <int QT, int PF, int RT, int QB>
+struct XregWalk {
+  using L = XregLds<QT, QB>;
+  const WalkPlan<RT, QB>& pl;
+  const __bf16* Xb;
+  const int D, bmode, ss, unit, last_blk, wave, lane;
+  int pf_j = 0, pf_kt = 0, qb = 0;                 // prefetch head: step and k-slice; ring buffer of the next k-step
+  const bf16x8* pfp[RT];
+  bf16x8 xf[PF][RT][2];
+  __device__ __forceinline__ XregWalk(const WalkPlan<RT, QB>& pl, const __bf16* Xb, int64_t N, int D, int bmode, int ss, int unit, int wave, int lane)
+      : pl(pl), Xb(Xb), D(D), bmode(bmode), ss(ss), unit(unit), last_blk((int)((N - 1) >> 7)), wave(wave), lane(lane) {}
+  __device__ __forceinline__ int blk_of(int i) const { return (int)filter_block_of<unsigned int>(bmode, ss, unit, (unsigned int)i); }   // launch index -> 128-row block
+  __device__ __forceinline__ int li_of(int j, int a) const { return (int)blockIdx.x + min(j * RT + a, pl.nbw - 1) * (int)gridDim.x; }   // launch index of slot a in step j
+  __device__ __forceinline__ const bf16x8* base_of(int i) const {
+    const int b = min(blk_of(i), last_blk);
+    return (const bf16x8*)(Xb + ((int64_t)b * (D / 64)) * 8192 + wave * 1024) + lane;
+  }
+  __device__ __forceinline__ void fetch(int slot) {
+#pragma unroll
+    for (int a = 0; a < RT; ++a) {
+      xf[slot][a][0] = __builtin_nontemporal_load(pfp[a]);
+      xf[slot][a][1] = __builtin_nontemporal_load(pfp[a] + 64);
+    }
+    if (++pf_kt == pl.nk) {                       // next group of blocks (past the end: the last group again -- loaded, never used)
+      pf_kt = 0;
+      pf_j = min(pf_j + 1, pl.nmine - 1);
+#pragma unroll
+      for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(pf_j, a));
+    } else {
+#pragma unroll
+      for (int a = 0; a < RT; ++a) pfp[a] += 1024;
+    }
+  }
+  // prefetch head; with a resident q, the barrier behind which it has landed
+  __device__ __forceinline__ void start() {
+#pragma unroll
+    for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(0, a));
+#pragma unroll
+    for (int p = 0; p < PF - 1; ++p) {
+      fetch(p);
+      __builtin_amdgcn_sched_barrier(0);             // issue order = ring order: the counted waits of the loop rely on it
+    }
+    if (pl.qres) {
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();                  // the whole q has landed
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // the nk k-steps of one step of RT blocks (nk is a multiple of PF); the slice of step g sits in ring buffer g % qper
+  __device__ __forceinline__ void block_step(const char* smem, f32x4 (&acc)[RT][QT]) {
+    const int qper = pl.qres ? pl.nk : QB;
+    for (int kt0 = 0; kt0 < pl.nk; kt0 += PF) {
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        fetch((u + PF - 1) % PF);
+        __builtin_amdgcn_sched_barrier(0);
+        if (!pl.qres) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        const char* sQ = smem + qb * L::QBYTES + lane * 16;
+        qb = qb + 1 == qper ? 0 : qb + 1;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+          for (int b = 0; b < QT; ++b) {
+            const bf16x8 qf = *(const bf16x8*)(sQ + (ks * QT + b) * 1024);
+#pragma unroll
+            for (int a = 0; a < RT; ++a) acc[a][b] = mfma_f16(xf[u][a][ks], qf, acc[a][b]);
+          }
+        }
+      }
+    }
+  }
 };
 
 // thr_ready / thr_target (fused kernel): the thresholds are published by other workgroups of the SAME launch -- the first block step's K loop
@@ -720,82 +863,32 @@ template <int QT, int PF, int RT, bool SAT = false>
 __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, int nblocks, int bmode, int ss,
                    int unit, const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, unsigned int cap,
                    const unsigned int* thr_ready, unsigned int thr_target, unsigned long long* ts = nullptr) {
-  constexpr int WV = 8;
-  constexpr int QINST = 2 * QT;
-  constexpr int QBYTES = QINST * 1024;
-  constexpr int QB = QT > 8 ? 3 : 4;               // q ring: the producer runs QB-1 slices ahead
-  static_assert((QB - 2) * QINST <= 63, "vmcnt immediate");
-  // hits a wave parks in LDS: as many as the 160 KiB of the CU allow next to the q ring (one workgroup per CU).  A pass emits ~5 000 hits per
-  // query, i.e. 2.4 x queries per wave: with 320 entries most waves of a 100-query pass had to flush once in mid-pass (one memory-side atomic
-  // per hit, the wave waits, the workgroup waits for it at the next barrier): 630 us against 580 us for the same pass with hardly any hits
-  constexpr int WQC_BYTES = QT * 16 * 4;          // per wave: hits per query of a mid-pass flush, then the first global slot (see flush)
-  constexpr int WCAP_FIT = ((160 * 1024 - QB * QBYTES - QT * 64 - 1024 - WV * (WQC_BYTES + 16)) / (WV * 12)) / 64 * 64;
-  constexpr int WCAP = WCAP_FIT > 1024 ? 1024 : WCAP_FIT;
+  using L = EmitLds<QT>;
+  constexpr int WV = L::WV, QB = L::QB, WCAP = L::WCAP;
   static_assert(WCAP >= 256, "hit lists do not fit next to the q ring");
-  constexpr int WL_BYTES = WCAP * 12 + 16 + WQC_BYTES;
-  static_assert(EmitLds<QT>::BYTES == QB * QBYTES + WV * WL_BYTES + QT * 16 * 4, "EmitLds out of sync");
-  float* sthr = (float*)(smem + QB * QBYTES + WV * WL_BYTES);   // the thresholds (LDS: they are needed once per block, not per k-step)
+  float* sthr = (float*)(smem + QB * L::QBYTES + WV * L::WL_BYTES);   // the thresholds (LDS: they are needed once per block, not per k-step)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (thr_ready == nullptr) {
     for (int i = tid; i < QT * 16; i += 576) sthr[i] = i < nq ? thr[i] : FLT_MAX;
   }
   __syncthreads();
-  // this workgroup's blocks: launch indices blockIdx.x + i * gridDim.x, i < nbw (the counts differ by at most one block over the grid),
-  // walked RT at a time; an odd one out at the end is worked on with its own block in the second slot (cache hits, result dropped)
-  const int nbw = (nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int nmine = (nbw + RT - 1) / RT;                                         // steps of RT blocks (>= 1)
-  const int nk = D / 64;
-  const int64_t total = (int64_t)nmine * nk;                                     // k-steps of this workgroup
-  const bool qres = nk <= QB;                      // the whole q fits the ring (D <= 256): staged once, no barrier per k-step
+  const WalkPlan<RT, QB> pl(nblocks, D);
 
   if (wave == WV) {
-    // ---- producer: the q slices, cyclically, QB-1 steps ahead
-    const __bf16* pq = qs + (int64_t)lane * 8;
-    int hs = 0, hb = 0;                            // head: slice and ring buffer
-    auto stage_next = [&]() {
-      char* sQ = smem + hb * QBYTES;
-#pragma unroll
-      for (int j = 0; j < QINST; ++j)
-        __builtin_amdgcn_global_load_lds((gptr_t)(pq + ((int64_t)hs * QINST + j) * 512), (lptr_t)(sQ + j * 1024), 16, 0, 0);
-      hs = hs + 1 == nk ? 0 : hs + 1;
-      hb = hb + 1 == QB ? 0 : hb + 1;
-    };
-    if (qres) {
-      for (int p = 0; p < nk; ++p) stage_next();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    } else {
-#pragma unroll
-      for (int p = 0; p < QB - 1; ++p)
-        if (p < total) stage_next();
-      for (int64_t g = 0; g < total; ++g) {
-        if (g + QB - 2 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((QB - 2) * QINST) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();              // q(g) is in LDS; the consumers are done with step g-1 -> its buffer is free
-        if (g + QB - 1 < total) stage_next();
-      }
-    }
+    QProducer<QT, QB> p(smem, qs, lane, pl.nk);
+    p.start(pl.qres, pl.total);
+    if (!pl.qres)
+      for (int64_t g = 0; g < pl.total; ++g) p.step(g, pl.total);
 #pragma unroll
     for (int i = 0; i < 4; ++i) __builtin_amdgcn_s_barrier();   // the four barriers of the consumers' final flush
     return;
   }
 
-  // ---- consumers: wave w owns rows 16w .. 16w+15 of each of the RT blocks in work
   const int fi = lane & 15, fq = lane >> 4;
-  unsigned long long* wl = (unsigned long long*)(smem + QB * QBYTES + wave * WL_BYTES);
+  unsigned long long* wl = (unsigned long long*)(smem + QB * L::QBYTES + wave * L::WL_BYTES);
   unsigned int* wq = (unsigned int*)(wl + WCAP);
-  auto blk_of = [&](int i) -> int {                // launch index -> 128-row block (see k_flat_ip_scores_split); all < 2^25
-    if (bmode != 2) return i;
-    const unsigned int u = (unsigned int)i / (unsigned int)unit, g = u / (unsigned int)(ss - 1);
-    return (int)((g * ss + 1 + (u - g * (ss - 1))) * unit + ((unsigned int)i - u * unit));
-  };
-  const int last_blk = (int)((N - 1) >> 7);
-  auto li_of = [&](int j, int a) -> int { return (int)blockIdx.x + min(j * RT + a, nbw - 1) * (int)gridDim.x; };   // launch index of slot a in step j
-  auto base_of = [&](int i) -> const bf16x8* {
-    const int b = min(blk_of(i), last_blk);
-    return (const bf16x8*)(Xb + ((int64_t)b * (D / 64)) * 8192 + wave * 1024) + lane;
-  };
+  XregWalk<QT, PF, RT, QB> w(pl, Xb, N, D, bmode, ss, unit, wave, lane);
   unsigned int wcnt = 0;                           // entries in this wave's list (wave-uniform)
   unsigned int* wqc = (unsigned int*)((char*)wl + WCAP * 12 + 16);
   // mid-pass flush, by the wave alone, ONE global reservation per (wave, query with hits) -- round 2 reserved per hit (memory-side atomics
@@ -827,62 +920,10 @@ __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __res
 #pragma unroll
     for (int b = 0; b < QT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // prefetch head
-  int pf_j = 0, pf_kt = 0;
-  const bf16x8* pfp[RT];
-#pragma unroll
-  for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(0, a));
-  bf16x8 xf[PF][RT][2];
-  auto fetch = [&](int slot) {
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-      xf[slot][a][0] = __builtin_nontemporal_load(pfp[a]);
-      xf[slot][a][1] = __builtin_nontemporal_load(pfp[a] + 64);
-    }
-    if (++pf_kt == nk) {                          // next group of blocks (past the end: the last group again -- loaded, never used)
-      pf_kt = 0;
-      pf_j = min(pf_j + 1, nmine - 1);
-#pragma unroll
-      for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(pf_j, a));
-    } else {
-#pragma unroll
-      for (int a = 0; a < RT; ++a) pfp[a] += 1024;
-    }
-  };
-#pragma unroll
-  for (int p = 0; p < PF - 1; ++p) {
-    fetch(p);
-    __builtin_amdgcn_sched_barrier(0);             // issue order = ring order: the counted waits of the loop rely on it
-  }
-  int qb = 0;
-  const int qper = qres ? nk : QB;                 // slice of step g sits in ring buffer g % qper
   unsigned int ovf = 0;
-  if (qres) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();                  // the whole q has landed
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  for (int j = 0; j < nmine; ++j) {
-    for (int kt0 = 0; kt0 < nk; kt0 += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        fetch((u + PF - 1) % PF);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!qres) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const char* sQ = smem + qb * QBYTES + lane * 16;
-        qb = qb + 1 == qper ? 0 : qb + 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int b = 0; b < QT; ++b) {
-            const bf16x8 qf = *(const bf16x8*)(sQ + (ks * QT + b) * 1024);
-#pragma unroll
-            for (int a = 0; a < RT; ++a) acc[a][b] = mfma_f16(xf[u][a][ks], qf, acc[a][b]);
-          }
-        }
-      }
-    }
+  w.start();
+  for (int j = 0; j < pl.nmine; ++j) {
+    w.block_step(smem, acc);
     if (thr_ready != nullptr && j == 0) {
       // thresholds published by the selection step of this launch: every consumer wave waits for itself and fills the (shared) table with the
       // same values -- a wave reads the table only after its own complete write, so no barrier is needed
@@ -899,9 +940,9 @@ __device__ __forceinline__ void filter_emit_body(char* smem, const __bf16* __res
     //      more hits than the list holds (near-duplicate rows) pushes the query's counter past the list capacity instead -> flagged, redone by the fallback
 #pragma unroll
     for (int a = 0; a < RT; ++a) {
-      const int64_t n64 = (int64_t)blk_of(li_of(j, a)) * 128 + wave * 16 + fq * 4;
+      const int64_t n64 = (int64_t)w.blk_of(w.li_of(j, a)) * 128 + wave * 16 + fq * 4;
       const unsigned int n = (unsigned int)n64;
-      const int valid = j * RT + a < nbw ? (int)max((int64_t)0, min((int64_t)4, N - n64)) : 0;
+      const int valid = j * RT + a < pl.nbw ? (int)max((int64_t)0, min((int64_t)4, N - n64)) : 0;
 #pragma unroll
       for (int b = 0; b < QT; ++b) {
         const f32x4 v = acc[a][b];
@@ -972,7 +1013,7 @@ template <int QT, int PF, int RT, bool SAT = false>
 __global__ void __launch_bounds__(576, (QT > 8 || RT > 1) ? 3 : 5)   // (second argument: waves per SIMD -> two workgroups of nine waves per CU need five)
 k_filter_xreg_emit(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, int nblocks, int bmode, int ss,
                    int unit, const float* __restrict__ thr, unsigned long long* __restrict__ cand, unsigned int* __restrict__ cnt, unsigned int cap) {
-  __shared__ __attribute__((aligned(1024))) char smem[EmitLds<QT>::BYTES];
+  __shared__ __attribute__((aligned(1024))) char smem[EmitLds<QT>::EMIT_BYTES];
   filter_emit_body<QT, PF, RT, SAT>(smem, Xb, N, D, qs, nq, nblocks, bmode, ss, unit, thr, cand, cnt, cap, nullptr, 0u);
 }
 
@@ -1022,15 +1063,13 @@ struct FusedCtl {              // five counters in the zero-initialised ints of 
 
 // one 128-row sample block (RT = 1): the body of k_filter_xreg<QT, PF, false, 1> with group maxima; all nine waves call it together.
 // li = index of the block inside the sample (where its scores go), blk = corpus block.
+// (Kept as a copy of its own, not a caller of xreg_block_kloop / stage_store_rows: k_filter_fused spills registers, and with the shared
+// pieces its spill and scratch counts moved in every instantiation from three query tiles on -- compile-time resource table, not measured.)
 template <int QT, int PF>
 __device__ __forceinline__ void filter_sample_block(char* smem, const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq,
                                                     float* __restrict__ scores, int64_t ld, float* __restrict__ gmax, int nblk_ld, int64_t blk, int64_t li) {
-  constexpr int WV = 8, RB = 128;
-  constexpr int QINST = 2 * QT;
-  constexpr int QBYTES = QINST * 1024;
-  constexpr int SEG = RB * 4 + 16;                 // epilogue staging: one query's 128 scores + pad
-  constexpr int QB = QT > 8 ? 2 : 4;
-  static_assert((QB - 2) * QINST <= 63, "vmcnt immediate");
+  using L = BlockLds<QT>;
+  constexpr int WV = L::WV, RB = L::RB, QINST = L::QINST, QBYTES = L::QBYTES, SEG = L::SEG, QB = L::QB;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nk = D / 64;
@@ -1100,7 +1139,7 @@ __device__ __forceinline__ void filter_sample_block(char* smem, const __bf16* __
   }
   // ---- epilogue: group maxima from registers, scores through the (dead) q ring
   float* wmax = (float*)smem;                      // [8 waves][QT*16]
-  constexpr int LDS_Q = QB * QBYTES > 16 * SEG ? QB * QBYTES : 16 * SEG;
+  constexpr int LDS_Q = L::BLOCK_BYTES;
   constexpr int QPT = (LDS_Q / SEG / 16) < QT ? (LDS_Q / SEG / 16) : QT;   // q-tiles staged per pass
   static_assert(QPT >= 1, "epilogue staging does not fit");
   constexpr int NPASS = (QT + QPT - 1) / QPT;
@@ -1158,163 +1197,59 @@ __global__ void __launch_bounds__(576, 3)
 k_filter_xreg_store(const __bf16* __restrict__ Xb, int64_t N, int D, const __bf16* __restrict__ qs, int nq, float* __restrict__ scores, int64_t ld,
                     float* __restrict__ gmax, int nblk_ld, int nblocks, int bmode, int ss, int unit) {
   static_assert(QT <= 8, "staging sized for eight query tiles");
-  constexpr int WV = 8, RB = 128;
-  constexpr int QINST = 2 * QT;
-  constexpr int QBYTES = QINST * 1024;
-  constexpr int QB = 4;
-  static_assert((QB - 2) * QINST <= 63, "vmcnt immediate");
-  constexpr int SEG = RB * 4 + 16;                 // staging: one query's 128 scores + pad
-  __shared__ __attribute__((aligned(1024))) char smem[QB * QBYTES + QT * 16 * SEG];
-  char* stg = smem + QB * QBYTES;
+  using L = XregLds<QT, 4>;
+  constexpr int WV = L::WV, RB = L::RB, QB = L::QB;
+  __shared__ __attribute__((aligned(1024))) char smem[L::STORE_BYTES];
+  char* stg = smem + QB * L::QBYTES;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nbw = (nblocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;   // this workgroup's blocks: blockIdx.x + i * gridDim.x
-  const int nmine = (nbw + RT - 1) / RT;                                               // steps of RT blocks
-  const int nk = D / 64;
-  const int64_t total = (int64_t)nmine * nk;
-  const bool qres = nk <= QB;
+  const WalkPlan<RT, QB> pl(nblocks, D);
 
   if (wave == WV) {
-    // ---- producer: the q slices, cyclically, QB-1 steps ahead; joins the barriers of the block epilogues
-    const __bf16* pq = qs + (int64_t)lane * 8;
-    int hs = 0, hb = 0;
-    auto stage_next = [&]() {
-      char* sQ = smem + hb * QBYTES;
-#pragma unroll
-      for (int j = 0; j < QINST; ++j)
-        __builtin_amdgcn_global_load_lds((gptr_t)(pq + ((int64_t)hs * QINST + j) * 512), (lptr_t)(sQ + j * 1024), 16, 0, 0);
-      hs = hs + 1 == nk ? 0 : hs + 1;
-      hb = hb + 1 == QB ? 0 : hb + 1;
-    };
-    if (qres) {
-      for (int p = 0; p < nk; ++p) stage_next();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    } else {
-#pragma unroll
-      for (int p = 0; p < QB - 1; ++p)
-        if (p < total) stage_next();
-    }
+    // ---- producer: joins the barriers of the block epilogues
+    QProducer<QT, QB> p(smem, qs, lane, pl.nk);
+    p.start(pl.qres, pl.total);
     int64_t g = 0;
-    for (int j = 0; j < nmine; ++j) {
-      if (!qres)
-        for (int kt = 0; kt < nk; ++kt, ++g) {
-          if (g + QB - 2 < total) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((QB - 2) * QINST) : "memory");
-          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          if (g + QB - 1 < total) stage_next();
-        }
+    for (int j = 0; j < pl.nmine; ++j) {
+      if (!pl.qres)
+        for (int kt = 0; kt < pl.nk; ++kt, ++g) p.step(g, pl.total);
 #pragma unroll
       for (int a = 0; a < RT; ++a)
-        if (j * RT + a < nbw) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }
+        if (j * RT + a < pl.nbw) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }
     }
     return;
   }
 
   // ---- consumers
   const int fi = lane & 15, fq = lane >> 4;
-  auto blk_of = [&](int i) -> int {                // launch index -> 128-row block
-    if (bmode == 1) { const unsigned int u = (unsigned int)i / (unsigned int)unit; return (int)(u * ss * unit + ((unsigned int)i - u * unit)); }
-    if (bmode != 2) return i;
-    const unsigned int u = (unsigned int)i / (unsigned int)unit, g = u / (unsigned int)(ss - 1);
-    return (int)((g * ss + 1 + (u - g * (ss - 1))) * unit + ((unsigned int)i - u * unit));
-  };
-  const int last_blk = (int)((N - 1) >> 7);
-  auto li_of = [&](int j, int a) -> int { return (int)blockIdx.x + min(j * RT + a, nbw - 1) * (int)gridDim.x; };
-  auto base_of = [&](int i) -> const bf16x8* {
-    const int b = min(blk_of(i), last_blk);
-    return (const bf16x8*)(Xb + ((int64_t)b * (D / 64)) * 8192 + wave * 1024) + lane;
-  };
+  XregWalk<QT, PF, RT, QB> w(pl, Xb, N, D, bmode, ss, unit, wave, lane);
   f32x4 acc[RT][QT];
 #pragma unroll
   for (int a = 0; a < RT; ++a)
 #pragma unroll
     for (int b = 0; b < QT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int pf_j = 0, pf_kt = 0;
-  const bf16x8* pfp[RT];
-#pragma unroll
-  for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(0, a));
-  bf16x8 xf[PF][RT][2];
-  auto fetch = [&](int slot) {
-#pragma unroll
-    for (int a = 0; a < RT; ++a) {
-      xf[slot][a][0] = __builtin_nontemporal_load(pfp[a]);
-      xf[slot][a][1] = __builtin_nontemporal_load(pfp[a] + 64);
-    }
-    if (++pf_kt == nk) {
-      pf_kt = 0;
-      pf_j = min(pf_j + 1, nmine - 1);
-#pragma unroll
-      for (int a = 0; a < RT; ++a) pfp[a] = base_of(li_of(pf_j, a));
-    } else {
-#pragma unroll
-      for (int a = 0; a < RT; ++a) pfp[a] += 1024;
-    }
-  };
-#pragma unroll
-  for (int p = 0; p < PF - 1; ++p) {
-    fetch(p);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  int qb = 0;
-  const int qper = qres ? nk : QB;
-  if (qres) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();                  // the whole q has landed
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  for (int j = 0; j < nmine; ++j) {
-    for (int kt0 = 0; kt0 < nk; kt0 += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; ++u) {
-        fetch((u + PF - 1) % PF);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!qres) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const char* sQ = smem + qb * QBYTES + lane * 16;
-        qb = qb + 1 == qper ? 0 : qb + 1;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int b = 0; b < QT; ++b) {
-            const bf16x8 qf = *(const bf16x8*)(sQ + (ks * QT + b) * 1024);
-#pragma unroll
-            for (int a = 0; a < RT; ++a) acc[a][b] = mfma_f16(xf[u][a][ks], qf, acc[a][b]);
-          }
-      }
-    }
+  w.start();
+  for (int j = 0; j < pl.nmine; ++j) {
+    w.block_step(smem, acc);
     // ---- block epilogue: the wave groups' maxima straight from registers, the scores through the staging region
 #pragma unroll
     for (int a = 0; a < RT; ++a) {
-      if (j * RT + a >= nbw) break;                // (uniform over the workgroup, producer included)
-      const int li = li_of(j, a);
-      const int64_t n0 = (int64_t)blk_of(li) * RB, n = n0 + wave * 16 + fq * 4;
+      if (j * RT + a >= pl.nbw) break;             // (uniform over the workgroup, producer included)
+      const int li = w.li_of(j, a);
+      const int64_t n = (int64_t)w.blk_of(li) * RB + wave * 16 + fq * 4;
 #pragma unroll
       for (int b = 0; b < QT; ++b) {
-        float mx = -FLT_MAX;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (n + e >= N) acc[a][b][e] = -FLT_MAX;
-          mx = fmaxf(mx, acc[a][b][e]);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float mx = wave_row_max<1>(&acc[a][b], 1, n, N);
         const int qi = b * 16 + fi;
         if (fq == 0 && qi < nq) gmax[(int64_t)qi * (8 * (int64_t)nblk_ld) + (int64_t)li * 8 + wave] = mx;
       }
       __builtin_amdgcn_s_barrier();                // the previous block's scores have left the staging region
+      stage_rows<QT, 1, WV, QT>(stg, &acc[a][0], 0, wave, fi, fq);
 #pragma unroll
-      for (int b = 0; b < QT; ++b) {
-        *(f32x4*)(stg + (b * 16 + fi) * SEG + (wave * 16 + fq * 4) * 4) = acc[a][b];
-        acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      for (int b = 0; b < QT; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                // staged
-      for (int idx = tid; idx < QT * 16 * (RB / 4); idx += 512) {
-        const int ql = idx / (RB / 4), c = idx % (RB / 4);
-        if (ql < nq) __builtin_nontemporal_store(*(const f32x4*)(stg + ql * SEG + c * 16), (f32x4*)(scores + (int64_t)ql * ld + (int64_t)li * RB + c * 4));
-      }
+      store_staged_rows<RB, 512>(stg, tid, QT * 16, 0, nq, scores + (int64_t)li * RB, ld, StoreNontemporal());
     }
   }
 }
-

@@ -58,6 +58,9 @@ def _index(X, shadow=True, id_base=0, pieces=2):
     # resident in LDS (D = 256) and with a cycling q ring (D = 512), two blocks at a time and one (seven query tiles)
     (300000, 256, 20, 1000, "unit", True), (300001, 512, 100, 1000, "mixed", True),
     (120000, 256, 30, 1, "unit", True), (200000, 128, 9, 3, "mixed", True),      # samples of >= 8 k blocks: threshold from the block maxima
+    # an odd number of sample blocks (2345 blocks at stride 4 = 587), two per workgroup (k_filter_xreg<.., 2>): the last workgroup works on
+    # its block twice and stores it once
+    (300100, 256, 100, 100, "unit", True),
 ])
 def test_score_free_filter_equals_score_matrix_filter_bitwise(N, D, Q, k, scale, shadow, search_mode):
     """Both filters end in the same exact rescoring of a superset of the exact top-k: same ids, same score bits."""
