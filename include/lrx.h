@@ -501,6 +501,41 @@ int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_
                              const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
                              int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (added in ABI 8, additively) RANGE search over the quantised and sparse indexes: the contract of lrx_flat_ip_range_search above -- lims /
+ * out_scores / out_ids in faiss's layout, a row is in the result iff the score the index's own top-k search reports for it, bit for bit,
+ * is strictly greater than `radius`; ids = id_base + row, ascending rows inside a query; exact, never truncated, deterministic (independent
+ * of the query batch and of the path inside the library); lims always written; the outputs written only when lims[n_queries] <= capacity
+ * (checked on the device; call again with at least lims[n_queries]).  radius must not be NaN; +inf gives an empty result; capacity >= 0;
+ * out_scores / out_ids may be NULL only with capacity == 0.  n_rows == 0 or n_queries == 0: lims cleared, nothing launched.  Asynchronous
+ * on `stream`, no host synchronisation.
+ *
+ * lrx_sq_fp16_ip_range_search  fp16 scalar-quantised index (codes / row_bounds / dim % 64 == 0 as for lrx_sq_fp16_ip_search below): the
+ *     score is (float) of the fp64 sum of q_i * (float) c_i.  The chain is the flat one with the tiled codes in both roles -- ONE filter
+ *     pass over the codes with the threshold radius - eps16(q), exact rescoring of the candidate lists from the codes; shards of <= 4096
+ *     rows (the flat range search's rule, not the 16 Ki of the fp16-SQ top-k) and queries whose list overflowed (counted by lrx_search_fallback_count) take a one-product score matrix over the codes and
+ *     the exact rescoring of every row within eps16(q) of the radius.  Capacity is checked per chunk of 256 queries, as in the flat call.
+ * lrx_pq_ip_range_search       product-quantised index (arguments as for lrx_pq_ip_search): the score is the fp32 sum of the lookup table
+ *     in ascending m, which the scan writes -- the predicate is applied to the scan's score matrix.
+ * lrx_range_impact_search      impact index (arguments as for lrx_impact_search, the caller's overflow refusal included): a row is in the
+ *     result iff it is a hit (S >= 1) and (float) S > radius; a negative radius returns every hit.
+ *     (Named lrx_range_impact_*: the lrx_impact_* prefix is the top-k family's, and its tests pin that family to its three entry points.)
+ * The last two run the scan driver twice (count per 4096-row segment, lims, scan again and fill in row order) and check `capacity` once for
+ * the whole call.  row_chunk (trailing): rows per score matrix, 0 = the library's 4 Mi, otherwise a positive multiple of 128 -- for tests,
+ * the result does not depend on it; pass the same value to the workspace function.                                                  */
+size_t lrx_sq_fp16_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries);
+int lrx_sq_fp16_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, const float* row_bounds, const float* q, int32_t n_queries,
+                                float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                void* workspace, size_t workspace_bytes, void* stream);
+size_t lrx_pq_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int64_t row_chunk);
+int lrx_pq_ip_range_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
+                           float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, void* workspace,
+                           size_t workspace_bytes, void* stream, int64_t row_chunk);
+size_t lrx_range_impact_workspace_bytes(int64_t n_rows, int32_t n_queries, int64_t row_chunk);
+int lrx_range_impact_search(const void* postings, const int64_t* term_off, int32_t n_terms, int64_t n_rows, const int32_t* q_off,
+                            const int32_t* q_term, const int32_t* q_cnt, int32_t n_queries, float radius, int64_t id_base, int64_t* lims,
+                            float* out_scores, int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, int32_t window_rows,
+                            void* stream, int64_t row_chunk);
+
 /* (added in ABI 8, additively) fp16 SCALAR-QUANTISED inner-product index (faiss IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT)):
  * the only resident copy of the rows is their codes c = fp16(x) -- round-to-nearest-even per element, saturating at +-65504 (faiss maps
  * an overflow to inf; counted by lrx_device_saturation_count) -- in the TILED layout of the shadow below (lrx_shard_commit_rows with X_shadow

@@ -73,6 +73,12 @@ SIGNATURES = {
     "lrx_flat_ip_bounded_list_counts": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "lrx_flat_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "lrx_flat_ip_range_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "lrx_sq_fp16_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
+    "lrx_sq_fp16_ip_range_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
+    "lrx_pq_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I64]),
+    "lrx_pq_ip_range_search": (_I32, [_P, _I64, _P, _I32, _I32, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _P, _I64]),
+    "lrx_range_impact_workspace_bytes": (_SZ, [_I64, _I32, _I64]),
+    "lrx_range_impact_search": (_I32, [_P, _P, _I32, _I64, _P, _P, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _I32, _P, _I64]),
     "lrx_sq_fp16_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
     "lrx_sq_fp16_ip_chunk_queries": (_I32, [_I64, _I32, _I32, _I32, _I32]),
     "lrx_sq_fp16_ip_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _I32, _I64, _P, _P, _P, _P, _P, _SZ, _I32, _P]),

@@ -872,25 +872,15 @@ extern "C" size_t lrx_flat_ip_range_workspace_bytes(int64_t n_rows, int32_t dim,
   return range_plan(n_rows, dim > 0 ? dim : 1, nq, list).total + 512;
 }
 
-extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
-                                        const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
-                                        int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream) {
-  LRX_CHECK_ARG(row_bounds != nullptr, "flat_ip_range_search: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
-  LRX_CHECK_ARG(dim > 0 && dim % 4 == 0, "flat_ip_range_search: dim=%d must be a positive multiple of 4", dim);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "flat_ip_range_search: shard rows=%lld out of range", (long long)n_rows);
-  LRX_CHECK_ARG(n_queries >= 0 && capacity >= 0, "flat_ip_range_search: n_queries=%d / capacity=%lld must be >= 0", n_queries, (long long)capacity);
-  LRX_CHECK_ARG(radius == radius, "flat_ip_range_search: radius is NaN");
-  LRX_CHECK_ARG(lims != nullptr, "flat_ip_range_search: null lims");
+// The chain over either row source (row_dot): RS = ROWS_F32 -- X = fp32 rows (stride ldx), X_shadow = their optional tiled fp16 shadow;
+// RS = ROWS_F16T -- X = X_shadow = the tiled fp16 codes of the scalar-quantised index (ldx unused): the codes are the filter operand and the
+// rows the rescoring reads, the threshold is k_range_threshold<ROWS_F16T>, and the score matrix of the fallbacks (tiny shards, overflowed lists) is
+// the one-product filter matrix over the codes, whose band k_range_scan<.., ROWS_F16T> takes from the same eps16.  Arguments checked by the callers.
+template <int RS>
+static int range_search_chain(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds, const float* q,
+                              int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                              void* workspace, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (n_queries == 0 || n_rows == 0) {
-    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), s));
-    return LRX_OK;
-  }
-  if (workspace_bytes < lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr)) {
-    lrx_set_error("flat_ip_range_search: workspace %zu B < required %zu B", workspace_bytes,
-                  lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr));
-    return LRX_ERR_WORKSPACE;
-  }
   const bool list = range_list_path(n_rows, dim, X_shadow != nullptr);
   const int chunk = list ? 256 : 128;
   const int n_cu = lrx_cu_count();
@@ -917,13 +907,13 @@ extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t 
     int rc;
     if (list) {
       LRX_HIP(hipMemsetAsync(bits, 0, (size_t)nq * p.nw * 8, s));
-      hipLaunchKernelGGL(k_range_threshold, dim3(nq), dim3(256), 0, s, qc, dim, row_bounds, radius, thr);
+      hipLaunchKernelGGL(k_range_threshold<RS>, dim3(nq), dim3(256), 0, s, qc, dim, row_bounds, radius, thr);
       LRX_LAUNCH_CHECK();
       FilterMode fm;                                                    // every block, no sample: the given radius is the threshold
       fm.bmode = 0; fm.thr = thr; fm.cand = cand; fm.cnt = cnt; fm.cap = RANGE_CAP; fm.range = true;
       rc = launch_scores(X, n_rows, ldx, dim, qc, nq, nullptr, nullptr, qsplit, stream, 1, nullptr, X_shadow, p.ld, fm);
       if (rc != LRX_OK) return rc;
-      hipLaunchKernelGGL(k_range_rescore, dim3(nq, parts), dim3(256), 0, s, X, n_rows, ldx, dim, qc, cand, (const unsigned int*)cnt, (unsigned int)RANGE_CAP,
+      hipLaunchKernelGGL(k_range_rescore<RS>, dim3(nq, parts), dim3(256), 0, s, X, n_rows, ldx, dim, qc, cand, (const unsigned int*)cnt, (unsigned int)RANGE_CAP,
                          radius, bits, p.nw, surv, flg, any_flag);
       LRX_LAUNCH_CHECK();
       hipLaunchKernelGGL(k_range_bitmap_prefix, dim3(nq), dim3(256), 0, s, (const unsigned long long*)bits, p.nw, (const unsigned int*)cnt,
@@ -933,17 +923,19 @@ extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t 
     // score-matrix path, <= 128 queries at a time: the overflowed queries of a list chunk (launches gated on the group's flag), or all queries
     auto matrix = [&](int f0, int nf) -> int {
       const int* gate = list ? any_flag + f0 / 128 : nullptr;
+      if (RS == ROWS_F16T)   // (the one-product score matrix over the codes: query_eps_block<ROWS_F16T> bounds its error)
+        return launch_scores(nullptr, n_rows, dim, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, qsplit, stream, 1, gate, X_shadow, 0, FilterMode());
       return launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, qsplit, stream, 3, gate, nullptr, 0, FilterMode());
     };
     auto scan = [&](int f0, int nf, bool fill) {
       const int* gate = list ? any_flag + f0 / 128 : nullptr;
       const int* qf = list ? flg + f0 : nullptr;
       if (fill)
-        hipLaunchKernelGGL(k_range_scan<true>, dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
+        hipLaunchKernelGGL((k_range_scan<true, RS>), dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
                            X, ldx, dim, qc + (int64_t)f0 * dim, row_bounds, radius, gate, qf, surv + f0, (const int64_t*)lc + f0, lend, capacity, id_base,
                            out_scores, out_ids);
       else
-        hipLaunchKernelGGL(k_range_scan<false>, dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
+        hipLaunchKernelGGL((k_range_scan<false, RS>), dim3(nf), dim3(1024), 0, s, (const float*)scores, p.ld, n_rows, (const float*)blkmax, (int)p.nblk, (int)p.nblk_ld,
                            X, ldx, dim, qc + (int64_t)f0 * dim, row_bounds, radius, gate, qf, surv + f0, (const int64_t*)lc + f0, lend, capacity, id_base,
                            out_scores, out_ids);
     };
@@ -970,6 +962,57 @@ extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t 
     }
   }
   return LRX_OK;
+}
+
+extern "C" int lrx_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const void* X_shadow, const float* row_bounds,
+                                        const float* q, int32_t n_queries, float radius, int64_t id_base, int64_t* lims, float* out_scores,
+                                        int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(row_bounds != nullptr, "flat_ip_range_search: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
+  LRX_CHECK_ARG(dim > 0 && dim % 4 == 0, "flat_ip_range_search: dim=%d must be a positive multiple of 4", dim);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "flat_ip_range_search: shard rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG(n_queries >= 0 && capacity >= 0, "flat_ip_range_search: n_queries=%d / capacity=%lld must be >= 0", n_queries, (long long)capacity);
+  LRX_CHECK_ARG(radius == radius, "flat_ip_range_search: radius is NaN");
+  LRX_CHECK_ARG(lims != nullptr, "flat_ip_range_search: null lims");
+  if (n_queries == 0 || n_rows == 0) {
+    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), (hipStream_t)stream));
+    return LRX_OK;
+  }
+  if (workspace_bytes < lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr)) {
+    lrx_set_error("flat_ip_range_search: workspace %zu B < required %zu B", workspace_bytes,
+                  lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, X_shadow != nullptr));
+    return LRX_ERR_WORKSPACE;
+  }
+  return range_search_chain<ROWS_F32>(X, n_rows, ldx, dim, X_shadow, row_bounds, q, n_queries, radius, id_base, lims, out_scores, out_ids, capacity, workspace,
+                                      stream);
+}
+
+// fp16 scalar-quantised index: the argument list of lrx_flat_ip_range_search minus the fp32 rows (include/lrx.h)
+extern "C" size_t lrx_sq_fp16_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries) {
+  return lrx_flat_ip_range_workspace_bytes(n_rows, dim, n_queries, 1);
+}
+
+extern "C" int lrx_sq_fp16_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, const float* row_bounds, const float* q, int32_t n_queries,
+                                           float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(dim > 0 && dim % 64 == 0, "sq_fp16_ip_range_search: dim=%d must be a positive multiple of 64", dim);
+  LRX_CHECK_ARG(row_bounds != nullptr, "sq_fp16_ip_range_search: null row_bounds (device pointer to {max |x_row|, max |x_row - fp16(x_row)|})");
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "sq_fp16_ip_range_search: rows=%lld out of range", (long long)n_rows);
+  LRX_CHECK_ARG(codes != nullptr || n_rows == 0, "sq_fp16_ip_range_search: null codes");
+  LRX_CHECK_ARG(n_queries >= 0 && capacity >= 0, "sq_fp16_ip_range_search: n_queries=%d / capacity=%lld must be >= 0", n_queries, (long long)capacity);
+  LRX_CHECK_ARG(radius == radius, "sq_fp16_ip_range_search: radius is NaN");
+  LRX_CHECK_ARG(lims != nullptr, "sq_fp16_ip_range_search: null lims");
+  LRX_CHECK_ARG(capacity == 0 || (out_scores != nullptr && out_ids != nullptr), "sq_fp16_ip_range_search: null outputs with capacity=%lld", (long long)capacity);
+  if (n_queries == 0 || n_rows == 0) {
+    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), (hipStream_t)stream));
+    return LRX_OK;
+  }
+  LRX_CHECK_ARG(q != nullptr, "sq_fp16_ip_range_search: null queries");
+  if (workspace_bytes < lrx_sq_fp16_ip_range_workspace_bytes(n_rows, dim, n_queries)) {
+    lrx_set_error("sq_fp16_ip_range_search: workspace %zu B < required %zu B", workspace_bytes, lrx_sq_fp16_ip_range_workspace_bytes(n_rows, dim, n_queries));
+    return LRX_ERR_WORKSPACE;
+  }
+  return range_search_chain<ROWS_F16T>((const float*)codes, n_rows, dim, dim, codes, row_bounds, q, n_queries, radius, id_base, lims, out_scores, out_ids,
+                                       capacity, workspace, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@
 //                     posting list (lower-bound search on the rows) streamed into int32 accumulators in LDS with non-returning adds;
 //                     writes its slice of the [Q, ld] fp32 score matrix (zeros included) and the 128-row block maxima -> k_topk_select
 //     k_impact_hits   entries of the [Q, k] result whose score is not positive (rows that share no term with the query) become padding
+// Range search (lrx_range_impact_search): the same k_impact_scan under scan_range (lrx_search_codes.h) -- every HIT whose score is > radius,
+// never cut at k: the predicate is s > 0 && s > radius on the matrix score (float) S.
 #pragma once
 
 #define IMP_MAX_W 32768                 // rows per window at most: 128 KiB of int32 accumulators next to 6 KiB of term ranges
@@ -134,6 +136,39 @@ static int impact_window_rows(int64_t nr, int nq, int ncu) {
   return cand[2];
 }
 
+// The two steps the impact index hands to the scan drivers (scan_search and scan_range, lrx_search_codes.h): prep notes the chunk's first
+// query (the queries are on the device already), scan is k_impact_scan over a row chunk.  One place for the window rule and the launch
+// geometry of both the top-k and the range search.
+struct ImpactSteps {
+  const void* postings;
+  const int64_t* term_off;
+  int32_t n_terms;
+  const int32_t *q_off, *q_term, *q_cnt;
+  int32_t window_rows;
+  int64_t ld;
+  int nblk_ld;
+  void* stream;
+  int ncu;
+  int32_t q0_cur;
+  int init(const void* postings_, const int64_t* term_off_, int32_t n_terms_, const int32_t* q_off_, const int32_t* q_term_, const int32_t* q_cnt_,
+           int32_t window_rows_, const ScanPlan& p, void* stream_) {
+    postings = postings_; term_off = term_off_; n_terms = n_terms_; q_off = q_off_; q_term = q_term_; q_cnt = q_cnt_; window_rows = window_rows_;
+    ld = p.ld; nblk_ld = p.nblk_ld; stream = stream_; q0_cur = 0;
+    LRX_HIP(hipFuncSetAttribute((const void*)k_impact_scan, hipFuncAttributeMaxDynamicSharedMemorySize, IMP_MAX_W * 4));
+    ncu = lrx_cu_count();
+    return LRX_OK;
+  }
+  int prep(int32_t q0, int) { q0_cur = q0; return LRX_OK; }
+  int scan(int64_t r0, int64_t nr, int nq, float* sc, float* bm) const {
+    const int W = window_rows ? window_rows : impact_window_rows(nr, nq, ncu);
+    const int threads = W >= IMP_MAX_W ? 1024 : (W >= 8192 ? 512 : 256);
+    hipLaunchKernelGGL(k_impact_scan, dim3((unsigned)lrx_cdiv(nr, W), (unsigned)nq), dim3(threads), (size_t)W * 4, (hipStream_t)stream,
+                       (const imp_i32x2*)postings, term_off, (int)n_terms, r0, nr, W, q_off + q0_cur, q_term, q_cnt, sc, ld, bm, nblk_ld);
+    LRX_LAUNCH_CHECK();
+    return LRX_OK;
+  }
+};
+
 extern "C" size_t lrx_impact_workspace_bytes(int64_t n_rows, int32_t n_queries, int32_t k) { return impact_plan(n_rows, n_queries, k).total; }
 
 extern "C" int32_t lrx_impact_chunk_queries(int64_t n_rows, int32_t n_queries, int32_t k) { return impact_plan(n_rows, n_queries, k).qc; }
@@ -154,20 +189,12 @@ extern "C" int lrx_impact_search(const void* postings, const int64_t* term_off, 
   const ScanPlan p = impact_plan(n_rows, n_queries, k);
   if ((rc = codes_check_workspace("impact_search", workspace_bytes, p.total)) != LRX_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  LRX_HIP(hipFuncSetAttribute((const void*)k_impact_scan, hipFuncAttributeMaxDynamicSharedMemorySize, IMP_MAX_W * 4));
-  const int ncu = lrx_cu_count();
-  int32_t q0_cur = 0;
+  ImpactSteps st;
+  if ((rc = st.init(postings, term_off, n_terms, q_off, q_term, q_cnt, window_rows, p, stream)) != LRX_OK) return rc;
   return scan_search(
       p, workspace, n_rows, n_queries, k, id_base, out_scores, out_ids, row_map, stream,
-      [&](int32_t q0, int) { q0_cur = q0; return LRX_OK; },
-      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) {
-        const int W = window_rows ? window_rows : impact_window_rows(nr, nq, ncu);
-        const int threads = W >= IMP_MAX_W ? 1024 : (W >= 8192 ? 512 : 256);
-        hipLaunchKernelGGL(k_impact_scan, dim3((unsigned)lrx_cdiv(nr, W), (unsigned)nq), dim3(threads), (size_t)W * 4, s, (const imp_i32x2*)postings,
-                           term_off, (int)n_terms, r0, nr, W, q_off + q0_cur, q_term, q_cnt, sc, p.ld, bm, p.nblk_ld);
-        LRX_LAUNCH_CHECK();
-        return LRX_OK;
-      },
+      [&](int32_t q0, int nq) { return st.prep(q0, nq); },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) { return st.scan(r0, nr, nq, sc, bm); },
       [&](int32_t, int64_t r0, int64_t nr, int nq, const float* sc, const float* bm, float* os, int64_t* oi) {
         hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, sc, p.ld, nr, k, r0, bm, (int)lrx_cdiv(nr, SP_ROWS), p.nblk_ld, os, oi,
                            (const int*)nullptr, (const int*)nullptr);
@@ -177,4 +204,41 @@ extern "C" int lrx_impact_search(const void* postings, const int64_t* term_off, 
         LRX_LAUNCH_CHECK();
         return LRX_OK;
       });
+}
+
+// ---- range search: every hit (S >= 1) with (float) S > radius, in row order (the contract of lrx_flat_ip_range_search; include/lrx.h) ----
+static ScanRangePlan impact_range_plan(int64_t n_rows, int32_t n_queries, int64_t row_chunk) {
+  return scan_range_plan(n_rows, n_queries, row_chunk > 0 ? row_chunk : IMP_ROW_CHUNK, SP_ROWS, IMP_MATRIX_BYTES, IMP_QC_MAX, [](int) { return (size_t)0; });
+}
+
+extern "C" size_t lrx_range_impact_workspace_bytes(int64_t n_rows, int32_t n_queries, int64_t row_chunk) {
+  return impact_range_plan(n_rows, n_queries, row_chunk > 0 && row_chunk % SP_ROWS == 0 ? row_chunk : 0).p.total;
+}
+
+extern "C" int lrx_range_impact_search(const void* postings, const int64_t* term_off, int32_t n_terms, int64_t n_rows, const int32_t* q_off,
+                                       const int32_t* q_term, const int32_t* q_cnt, int32_t n_queries, float radius, int64_t id_base, int64_t* lims,
+                                       float* out_scores, int64_t* out_ids, int64_t capacity, void* workspace, size_t workspace_bytes, int32_t window_rows,
+                                       void* stream, int64_t row_chunk) {
+  int rc = codes_check_range("impact_range_search", n_rows, n_queries, radius, lims, out_scores, out_ids, capacity, row_chunk);
+  if (rc != LRX_OK) return rc;
+  LRX_CHECK_ARG(n_rows < (1ll << 31), "impact_range_search: rows=%lld do not fit the postings' int32 row", (long long)n_rows);
+  LRX_CHECK_ARG(n_terms >= 0 && (n_rows == 0 || n_terms == 0 || (postings != nullptr && term_off != nullptr)), "impact_range_search: null postings (terms=%d)",
+                n_terms);
+  LRX_CHECK_ARG(window_rows == 0 || (window_rows > 0 && window_rows <= IMP_MAX_W && window_rows % SP_ROWS == 0),
+                "impact_range_search: window_rows=%d must be 0 (the library's rule) or a multiple of %d up to %d", window_rows, SP_ROWS, IMP_MAX_W);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_queries == 0 || n_rows == 0) {
+    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), s));
+    return LRX_OK;
+  }
+  LRX_CHECK_ARG(q_off != nullptr, "impact_range_search: null q_off (queries=%d)", n_queries);
+  const ScanRangePlan rp = impact_range_plan(n_rows, n_queries, row_chunk);
+  if ((rc = codes_check_workspace("impact_range_search", workspace_bytes, rp.p.total)) != LRX_OK) return rc;
+  ImpactSteps st;
+  if ((rc = st.init(postings, term_off, n_terms, q_off, q_term, q_cnt, window_rows, rp.p, stream)) != LRX_OK) return rc;
+  return scan_range(
+      rp, workspace, n_rows, n_queries, id_base, lims, out_scores, out_ids, capacity, stream,
+      [&](int32_t q0, int nq) { return st.prep(q0, nq); },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) { return st.scan(r0, nr, nq, sc, bm); },
+      KeepHitAbove{radius});
 }

@@ -7,6 +7,8 @@
 //     k_pq_scan      THE HOT PATH: s(q, r) = fp32 sum of LUT[q][m][code_m(r)] in ascending m, the query's table in LDS; writes the
 //                    [Q, ld] score matrix of a row chunk and its 128-row block maxima -> k_topk_select (scan_search, lrx_search_codes.h)
 //     k_pq_decode    rows from their codes (reconstruct_n)
+// Range search (lrx_pq_ip_range_search): the same lookup tables and the same k_pq_scan under scan_range (lrx_search_codes.h) -- the matrix
+// score is the reported score, the predicate is s > radius.
 #pragma once
 
 #define PQ_KSUB 256
@@ -181,6 +183,39 @@ extern "C" int lrx_pq_lut(const float* q, int32_t n_queries, const float* centro
   return LRX_OK;
 }
 
+// The two steps PQ hands to the scan drivers (scan_search and scan_range, lrx_search_codes.h): the chunk's lookup tables into the head of the
+// workspace, and k_pq_scan over a row chunk.  One place for the launch geometry of both the top-k and the range search.
+struct PqSteps {
+  const void* codes;
+  const float* centroids;
+  const float* q;
+  int32_t dim, M;
+  float* lut;
+  int64_t ld;
+  int nblk_ld;
+  void* stream;
+  int Mp, ncu;
+  size_t smem;
+  int init(const void* codes_, const float* centroids_, const float* q_, int32_t dim_, int32_t M_, void* workspace, const ScanPlan& p, void* stream_) {
+    codes = codes_; centroids = centroids_; q = q_; dim = dim_; M = M_; lut = (float*)workspace; ld = p.ld; nblk_ld = p.nblk_ld; stream = stream_;
+    Mp = pq_mp(M);
+    smem = (size_t)(M < PQ_SCAN_MC ? M : PQ_SCAN_MC) * PQ_KSUB * 4;
+    LRX_HIP(hipFuncSetAttribute((const void*)k_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    ncu = lrx_cu_count();
+    return LRX_OK;
+  }
+  int prep(int32_t q0, int nq) const { return lrx_pq_lut(q + (int64_t)q0 * dim, nq, centroids, dim, M, lut, stream); }
+  int scan(int64_t r0, int64_t nr, int nq, float* sc, float* bm) const {
+    const int64_t ntiles = lrx_cdiv(nr, PQ_SCAN_THREADS);
+    int64_t gx = lrx_cdiv(2 * (int64_t)ncu, nq);
+    gx = gx > ntiles ? ntiles : gx;
+    hipLaunchKernelGGL(k_pq_scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, (hipStream_t)stream,
+                       (const uint8_t*)codes + (r0 / PQ_BLK) * PQ_BLK * Mp, nr, M, Mp, (const float*)lut, sc, ld, bm, nblk_ld);
+    LRX_LAUNCH_CHECK();
+    return LRX_OK;
+  }
+};
+
 extern "C" int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
                                 int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                 size_t workspace_bytes, int32_t flags, void* stream) {
@@ -192,30 +227,52 @@ extern "C" int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* 
   const ScanPlan p = pq_plan(n_rows, M, n_queries, k);
   if ((rc = codes_check_workspace("pq_ip_search", workspace_bytes, p.total)) != LRX_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
-  float* lut = (float*)workspace;
-  const int Mp = pq_mp(M);
-  const int mc = M < PQ_SCAN_MC ? M : PQ_SCAN_MC;
-  const size_t smem = (size_t)mc * PQ_KSUB * 4;
-  LRX_HIP(hipFuncSetAttribute((const void*)k_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  const int ncu = lrx_cu_count();
+  PqSteps st;
+  if ((rc = st.init(codes, centroids, q, dim, M, workspace, p, stream)) != LRX_OK) return rc;
   return scan_search(
       p, workspace, n_rows, n_queries, k, id_base, out_scores, out_ids, row_map, stream,
-      [&](int32_t q0, int nq) { return lrx_pq_lut(q + (int64_t)q0 * dim, nq, centroids, dim, M, lut, stream); },
-      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) {
-        const int64_t ntiles = lrx_cdiv(nr, PQ_SCAN_THREADS);
-        int64_t gx = lrx_cdiv(2 * (int64_t)ncu, nq);
-        gx = gx > ntiles ? ntiles : gx;
-        hipLaunchKernelGGL(k_pq_scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, s,
-                           (const uint8_t*)codes + (r0 / PQ_BLK) * PQ_BLK * Mp, nr, M, Mp, (const float*)lut, sc, p.ld, bm, p.nblk_ld);
-        LRX_LAUNCH_CHECK();
-        return LRX_OK;
-      },
+      [&](int32_t q0, int nq) { return st.prep(q0, nq); },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) { return st.scan(r0, nr, nq, sc, bm); },
       [&](int32_t, int64_t r0, int64_t nr, int nq, const float* sc, const float* bm, float* os, int64_t* oi) {
         hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, sc, p.ld, nr, k, r0, bm, (int)lrx_cdiv(nr, PQ_BLK), p.nblk_ld, os, oi,
                            (const int*)nullptr, (const int*)nullptr);
         LRX_LAUNCH_CHECK();
         return LRX_OK;
       });
+}
+
+// ---- range search: every row with s(q, r) > radius (the contract of lrx_flat_ip_range_search; include/lrx.h) ----
+static ScanRangePlan pq_range_plan(int64_t n_rows, int32_t M, int32_t n_queries, int64_t row_chunk) {
+  return scan_range_plan(n_rows, n_queries, row_chunk > 0 ? row_chunk : PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, 65535,
+                         [&](int qc) { return align256((size_t)qc * M * PQ_KSUB * 4); });
+}
+
+extern "C" size_t lrx_pq_ip_range_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int64_t row_chunk) {
+  (void)dim;
+  return pq_range_plan(n_rows, M > 0 ? M : 1, n_queries, row_chunk > 0 && row_chunk % SP_ROWS == 0 ? row_chunk : 0).p.total;
+}
+
+extern "C" int lrx_pq_ip_range_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
+                                      float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, void* workspace,
+                                      size_t workspace_bytes, void* stream, int64_t row_chunk) {
+  int rc = codes_check_range("pq_ip_range_search", n_rows, n_queries, radius, lims, out_scores, out_ids, capacity, row_chunk);
+  if (rc != LRX_OK) return rc;
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "pq_ip_range_search: dim=%d is not a multiple of M=%d", dim, M);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_queries == 0 || n_rows == 0) {
+    LRX_HIP(hipMemsetAsync(lims, 0, sizeof(int64_t) * ((size_t)n_queries + 1), s));
+    return LRX_OK;
+  }
+  LRX_CHECK_ARG(codes != nullptr && centroids != nullptr && q != nullptr, "pq_ip_range_search: null codes / centroids / queries");
+  const ScanRangePlan rp = pq_range_plan(n_rows, M, n_queries, row_chunk);
+  if ((rc = codes_check_workspace("pq_ip_range_search", workspace_bytes, rp.p.total)) != LRX_OK) return rc;
+  PqSteps st;
+  if ((rc = st.init(codes, centroids, q, dim, M, workspace, rp.p, stream)) != LRX_OK) return rc;
+  return scan_range(
+      rp, workspace, n_rows, n_queries, id_base, lims, out_scores, out_ids, capacity, stream,
+      [&](int32_t q0, int nq) { return st.prep(q0, nq); },
+      [&](int64_t r0, int64_t nr, int nq, float* sc, float* bm) { return st.scan(r0, nr, nq, sc, bm); },
+      KeepAbove{radius});
 }
 
 extern "C" int lrx_pq_encode(const float* x, int64_t n_rows, int64_t ldx, const float* centroids, int32_t dim, int32_t M, void* codes, int64_t row0,

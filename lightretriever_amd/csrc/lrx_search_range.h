@@ -15,6 +15,9 @@
 //   score-matrix path   queries whose list overflowed (counter > cap) and every state without a list path (no shadow, dim % 64 != 0,
 //                       tiny shards): six-product / exact-fp32 score matrix of <= 128 queries, then k_range_scan walks each score row
 //                       in row order (count pass, then fill pass) -- ordered by construction.
+// RS (ROWS_F32 / ROWS_F16T, lrx_search.hip) is the row source of the exact rescoring in k_range_rescore and k_range_scan, the way
+// k_refine_band has it: ROWS_F16T is the fp16 scalar-quantised index (host driver lrx_sq_fp16_ip_range_search), whose tiled codes are the
+// filter operand AND the rows the rescoring reads; its threshold is k_range_threshold<ROWS_F16T>, its score matrix the one-product filter scores.
 #pragma once
 
 #define RANGE_CAP CAND_CAP_MIN   // candidate-list entries per query (64 Ki); a query with more filter hits takes the score-matrix path
@@ -38,11 +41,23 @@ __device__ __forceinline__ float range_round_down(double t) {
 //   t = radius - 2^-23 |radius| - (1 + 2^-20) eps - 1e-30
 // is formed in fp64 (its own rounding error, < 2^-52 |t|, is far inside the 2^-24 |radius| and 1e-30 of slack) and rounded DOWN to fp32,
 // so thr <= t < s~ for every such row, and the filter keeps s~ >= thr.  radius = +inf: thr = +inf, nothing passes (nothing is > +inf).
+// RS = ROWS_F16T: the same threshold over the fp16 CODES of the scalar-quantised index.  The codes are the rows:
+//   s      = the exact inner product (real arithmetic) of the fp32 query and the decoded code row c;
+//   s64    = the fp64-accumulated sum of the products q_i * (float) c_i; |s64 - s| <= D 2^-52 |q| R16  (e64), R16 >= max |c_row|;
+//   s_rep  = (float) s64, the score SQFp16Index.search reports; s64 >= s_rep - 2^-23 |s_rep| as above;
+//   s~     = the fp32 result of the fp16 filter MFMA over fp16(q) and c, |s~ - s| <= eps16(q) = |q - q~| R16 + (D + 32) 2^-23 |q~| R16
+//            (query_eps_block<ROWS_F16T>, the bound the fp16-SQ top-k filters with).  Nothing is rounded on the row side, so the flat
+//            bound's row-rounding term |q~| E is absent; the query-rounding term and the accumulation term stay.
+// A row in the result has s_rep > radius, so s~ >= s - eps16 >= s64 - e64 - eps16 > radius - 2^-23 |radius| - e64 - eps16.  And
+// e64 <= 2^-29 eps16: |q| <= |q~| + |q - q~| and (D + 32) 2^-23 <= 1 give (D + 32) 2^-23 |q| R16 <= eps16, and D 2^-52 <= 2^-29 (D + 32) 2^-23.
+// Hence the same expression with eps16 in the place of eps:
+//   t = radius - 2^-23 |radius| - (1 + 2^-20) eps16 - 1e-30,   thr = t rounded DOWN to fp32 (+inf for radius = +inf).
+template <int RS>
 __global__ void __launch_bounds__(256) k_range_threshold(const float* __restrict__ q, int D, const float* __restrict__ bounds, float radius,
                                                          float* __restrict__ thr) {
   __shared__ float s_red[32];
   const int qi = blockIdx.x;
-  const float eps = query_eps_block<ROWS_F32>(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
+  const float eps = query_eps_block<RS>(q + (int64_t)qi * D, D, bounds, nullptr, s_red);
   if (threadIdx.x == 0) {
     const double r = (double)radius;
     thr[qi] = radius == INFINITY ? INFINITY : range_round_down(r - fabs(r) * 1.1920928955078125e-7 - (double)eps * (1.0 + 9.5367431640625e-7) - 1e-30);
@@ -52,6 +67,8 @@ __global__ void __launch_bounds__(256) k_range_threshold(const float* __restrict
 // Exact rescoring of the candidate lists, grid (query, part), 256 threads: a half-wave per entry.  A list whose counter exceeds the capacity
 // (entries were dropped) flags its query for the score-matrix path (statistics: lrx_search_fallback_count).  An entry becomes
 // (score bits << 32 | row) when its exact score is > radius, ~0 otherwise; survivors set their bit in the query's bitmap.
+// RS: the row source (row_dot, lrx_search_select.h).
+template <int RS>
 __global__ void __launch_bounds__(256)
 k_range_rescore(const float* __restrict__ X, int64_t N, int64_t ldx, int D, const float* __restrict__ q, unsigned long long* __restrict__ cand,
                 const unsigned int* __restrict__ cnt, unsigned int cap, float radius, unsigned long long* __restrict__ bits, int64_t nw,
@@ -74,7 +91,7 @@ k_range_rescore(const float* __restrict__ X, int64_t N, int64_t ldx, int D, cons
     const int e = min(c0 + (lane >> 5), n - 1);
     int64_t r = sel_row(list[e]);
     r = r < 0 ? 0 : (r >= N ? N - 1 : r);                                  // (a list entry is always a shard row; clamped all the same)
-    const float sc = exact_dot(X + r * ldx, qrow, D, lane);
+    const float sc = row_dot<RS>(X, ldx, r, qrow, D, lane);
     if ((lane & 31) == 0 && c0 + (lane >> 5) < n) {
       const bool keep = sc > radius;
       list[e] = keep ? (((unsigned long long)__float_as_uint(sc) << 32) | (unsigned long long)(uint32_t)r) : ~0ull;
@@ -163,7 +180,9 @@ k_range_fill_list(const unsigned long long* __restrict__ cand, const unsigned in
 // s6 >= thr6 = round_down(radius - 2^-23 |radius| - 2 eps6) is rescored exactly and kept when its score is > radius.  Windows whose 128-row
 // block maxima are all below thr6 are skipped.  FILL = false: the query's count goes to surv[qi]; FILL = true: the survivors go to
 // out[lims[qi] ..] in row order (a per-window bitmap gives each its slot), unless *lims_end > capacity.  gate / qflags: only flagged queries.
-template <bool FILL>
+// RS = ROWS_F16T: the matrix holds the one-product fp16 filter scores over the codes, within eps16(q) of s (k_range_threshold<ROWS_F16T>), so the
+// rows with a matrix score >= that kernel's thr are rescored from the codes.
+template <bool FILL, int RS>
 __global__ void __launch_bounds__(1024)
 k_range_scan(const float* __restrict__ scores, int64_t ld, int64_t N, const float* __restrict__ blkmax, int nblk, int nblk_ld,
              const float* __restrict__ X, int64_t ldx, int D, const float* __restrict__ q, const float* __restrict__ bounds, float radius,
@@ -171,23 +190,30 @@ k_range_scan(const float* __restrict__ scores, int64_t ld, int64_t N, const floa
              const int64_t* __restrict__ lims_end, int64_t capacity, int64_t id_base, float* __restrict__ out_scores, int64_t* __restrict__ out_ids) {
   __shared__ unsigned long long s_c[1024];
   __shared__ unsigned int s_words[32], s_pre[33], s_n;
-  __shared__ float s_red[16];
+  __shared__ float s_red[RS == ROWS_F32 ? 16 : 32];             // (query_eps_block: 32)
   const int qi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if ((gate != nullptr && *gate == 0) || (qflags != nullptr && qflags[qi] == 0)) return;
   if (FILL && *lims_end > capacity) return;
   const float* row = scores + (int64_t)qi * ld;
   const float* bm = blkmax + (int64_t)qi * nblk_ld;
   const float* qrow = q + (int64_t)qi * D;
-  float q2 = 0.f;
-  for (int i = tid; i < D; i += 1024) { const float v = qrow[i]; q2 += v * v; }
-  q2 = wave_sum(q2);
-  if (lane == 0) s_red[wave] = q2;
-  __syncthreads();
-  q2 = 0.f;
-  for (int w = 0; w < 16; ++w) q2 += s_red[w];
-  const double eps6 = (double)((float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f);
-  const double r = (double)radius;
-  const float thr6 = radius == INFINITY ? INFINITY : range_round_down(r - fabs(r) * 1.1920928955078125e-7 - 2.0 * eps6 - 1e-30);
+  float thr6;
+  if constexpr (RS == ROWS_F32) {
+    float q2 = 0.f;
+    for (int i = tid; i < D; i += 1024) { const float v = qrow[i]; q2 += v * v; }
+    q2 = wave_sum(q2);
+    if (lane == 0) s_red[wave] = q2;
+    __syncthreads();
+    q2 = 0.f;
+    for (int w = 0; w < 16; ++w) q2 += s_red[w];
+    const double eps6 = (double)((float)(6 * D + 8) * 1.1920929e-7f * sqrtf(q2) * bounds[0] * 1.01f);
+    const double r = (double)radius;
+    thr6 = radius == INFINITY ? INFINITY : range_round_down(r - fabs(r) * 1.1920928955078125e-7 - 2.0 * eps6 - 1e-30);
+  } else {
+    const double eps16 = (double)query_eps_block<RS>(qrow, D, bounds, nullptr, s_red);
+    const double r = (double)radius;
+    thr6 = radius == INFINITY ? INFINITY : range_round_down(r - fabs(r) * 1.1920928955078125e-7 - eps16 * (1.0 + 9.5367431640625e-7) - 1e-30);
+  }
   const int64_t base = FILL ? lims[qi] : 0;
   unsigned int run = 0;                                                    // survivors in the windows before (uniform)
   for (int64_t w0 = 0; w0 < N; w0 += 1024) {
@@ -203,7 +229,7 @@ k_range_scan(const float* __restrict__ scores, int64_t ld, int64_t N, const floa
     for (int c0 = wave * 2; c0 < n; c0 += 32) {
       const int e = min(c0 + (lane >> 5), n - 1);
       const int loc = (int)(uint32_t)s_c[e];
-      const float sc = exact_dot(X + (w0 + loc) * ldx, qrow, D, lane);
+      const float sc = row_dot<RS>(X, ldx, w0 + loc, qrow, D, lane);
       if ((lane & 31) == 0 && c0 + (lane >> 5) < n) {
         const bool keep = sc > radius;
         s_c[e] = keep ? (((unsigned long long)__float_as_uint(sc) << 32) | (unsigned long long)loc) : ~0ull;

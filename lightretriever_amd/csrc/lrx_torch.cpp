@@ -397,8 +397,27 @@ std::tuple<at::Tensor, at::Tensor> binary_topk(const at::Tensor& q, const at::Te
   return {dist, o.i};
 }
 
-// Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).  Reads lims[Q] back to the host once (and calls again once,
-// with the exact capacity, when the first guess of 1024 hits per query was short).
+// The result protocol of every range-search op (lrx_flat_ip_range_search / lrx_sq_fp16_ip_range_search / lrx_pq_ip_range_search /
+// lrx_range_impact_search): `call(lims, d, i, cap)` runs the library call, lims[Q] is read back to the host once, and the call is repeated
+// once with the exact capacity when the first guess of 1024 hits per query was short.  Refused under graph capture before anything is launched.
+template <class Call>
+std::tuple<at::Tensor, at::Tensor, at::Tensor> range_result(const at::Tensor& like, int64_t Q, const char* who, Call call) {
+  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None, who,
+              " under graph capture: the result length is read back to the host");
+  const auto f32 = like.options().dtype(at::kFloat);
+  at::Tensor lims = at::zeros({Q + 1}, f32.dtype(at::kLong));
+  int64_t cap = Q * 1024;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    at::Tensor d = at::empty({cap}, f32), i = at::empty({cap}, f32.dtype(at::kLong));
+    lrx_check(call(lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap), who);
+    const int64_t n = lims[Q].item<int64_t>();
+    if (n <= cap) return {lims, d.narrow(0, 0, n), i.narrow(0, 0, n)};
+    cap = n;
+  }
+  TORCH_CHECK(false, who, ": the result grew between two identical calls");
+}
+
+// Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
                                                                     const at::Tensor& row_bounds, double radius, int64_t id_base) {
   DevGuard guard(q.device());
@@ -409,23 +428,73 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Te
   void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
                         "flat_ip_range_search: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
   const int64_t Q = q.size(0);
-  at::Tensor lims = at::zeros({Q + 1}, q.options().dtype(at::kLong));
   const size_t wsb = lrx_flat_ip_range_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)Q, x_shadow.has_value() ? 1 : 0);
   at::Tensor ws = bytes((int64_t)wsb, q);
-  int64_t cap = Q * 1024;
-  at::Tensor d, i;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    d = at::empty({cap}, q.options());
-    i = at::empty({cap}, q.options().dtype(at::kLong));
-    lrx_check(lrx_flat_ip_range_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), xb,
-                                       row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)Q, (float)radius, id_base, lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap, ws.data_ptr(), wsb,
-                                       cur_stream()),
-              "flat_ip_range_search");
-    const int64_t n = lims[Q].item<int64_t>();
-    if (n <= cap) return {lims, d.narrow(0, 0, n), i.narrow(0, 0, n)};
-    cap = n;
-  }
-  TORCH_CHECK(false, "flat_ip_range_search: the result grew between two identical calls");
+  return range_result(q, Q, "flat_ip_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_flat_ip_range_search(x.data_ptr<float>(), x.size(0), x.size(0) ? x.stride(0) : x.size(1), (int32_t)x.size(1), xb, row_bounds.data_ptr<float>(),
+                                    q.data_ptr<float>(), (int32_t)Q, (float)radius, id_base, lims, d, i, cap, ws.data_ptr(), wsb, cur_stream());
+  });
+}
+
+// Range search over the quantised and sparse indexes: the result protocol is range_result's (above flat_ip_range_search).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& row_bounds,
+                                                                       double radius, int64_t id_base) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(row_bounds, "row_bounds", at::kFloat, 1);
+  const int64_t dim = q.size(1), Q = q.size(0);
+  TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && dim % 64 == 0 && n_rows >= 0,
+              "sq_fp16_ip_range_search: q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
+  void* cb = tiled_rows(codes, at::kHalf, n_rows, dim, "sq_fp16_ip_range_search: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
+  const size_t wsb = lrx_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)dim, (int32_t)Q);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, Q, "sq_fp16_ip_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_sq_fp16_ip_range_search(cb, n_rows, (int32_t)dim, row_bounds.data_ptr<float>(), q.data_ptr<float>(), (int32_t)Q, (float)radius, id_base, lims, d, i,
+                                       cap, ws.data_ptr(), wsb, cur_stream());
+  });
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows,
+                                                                  double radius, int64_t id_base, int64_t row_chunk) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(centroids, "centroids", at::kFloat, 3);
+  const int64_t dim = q.size(1), M = centroids.size(0), Q = q.size(0);
+  TORCH_CHECK(q.is_contiguous() && centroids.is_contiguous() && centroids.size(1) == 256 && M > 0 && dim % M == 0 && centroids.size(2) == dim / M && n_rows >= 0,
+              "pq_ip_range_search: q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
+  const int64_t mp = (M + 15) / 16 * 16;
+  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, "pq_ip_range_search: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
+  const size_t wsb = lrx_pq_ip_range_workspace_bytes(n_rows, (int32_t)dim, (int32_t)M, (int32_t)Q, row_chunk);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, Q, "pq_ip_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_pq_ip_range_search(cb, n_rows, centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, q.data_ptr<float>(), (int32_t)Q, (float)radius, id_base, lims,
+                                  d, i, cap, ws.data_ptr(), wsb, cur_stream(), row_chunk);
+  });
+}
+
+// (the overflow refusal of the contract is the caller's, as for impact_topk: ImpactIndex.range_search makes it)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> impact_range_search(const at::Tensor& postings, const at::Tensor& term_off, int64_t n_rows, const at::Tensor& q_off,
+                                                                   const at::Tensor& q_term, const at::Tensor& q_cnt, double radius, int64_t id_base,
+                                                                   int64_t window_rows, int64_t row_chunk) {
+  DevGuard guard(postings.device());
+  need(postings, "postings", at::kInt, 2);
+  need(term_off, "term_off", at::kLong, 1);
+  need(q_off, "q_off", at::kInt, 1);
+  need(q_term, "q_term", at::kInt, 1);
+  need(q_cnt, "q_cnt", at::kInt, 1);
+  TORCH_CHECK(postings.is_contiguous() && postings.size(1) == 2 && term_off.numel() >= 1 && q_off.numel() >= 1 && q_term.numel() == q_cnt.numel() && n_rows >= 0,
+              "impact_range_search: postings int32 [nnz,2] contiguous, term_off int64 [T+1], q_off int32 [Q+1], q_term / q_cnt int32 of one length, n_rows >= 0");
+  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None,
+              "impact_range_search under graph capture: the result length is read back to the host");
+  const int64_t Q = q_off.numel() - 1;
+  TORCH_CHECK(q_off[Q].item<int32_t>() == q_term.numel(), "impact_range_search: q_off[Q] must equal the length of q_term");
+  const size_t wsb = lrx_range_impact_workspace_bytes(n_rows, (int32_t)Q, row_chunk);
+  at::Tensor ws = bytes((int64_t)wsb, postings);
+  return range_result(postings, Q, "impact_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_range_impact_search(postings.data_ptr(), term_off.data_ptr<int64_t>(), (int32_t)(term_off.numel() - 1), n_rows, q_off.data_ptr<int32_t>(),
+                                   q_term.data_ptr<int32_t>(), q_cnt.data_ptr<int32_t>(), (int32_t)Q, (float)radius, id_base, lims, d, i, cap, ws.data_ptr(), wsb,
+                                   (int32_t)window_rows, cur_stream(), row_chunk);
+  });
 }
 
 // Quantise + compact to ragged CSR (lrx_sparse_csr_count / lrx_sparse_csr_fill): reps fp32 [B, V] (rows may be strided) -> (row_off int64 [B + 1],
@@ -477,6 +546,10 @@ TORCH_LIBRARY(lrx, m) {
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
         "int window_rows=0) -> (Tensor, Tensor)");
   m.def("sparse_compact_csr(Tensor reps, int quantization_factor=100, bool empty_marker=True) -> (Tensor, Tensor, Tensor)");
+  m.def("sq_fp16_ip_range_search(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
+  m.def("pq_ip_range_search(Tensor q, Tensor codes, Tensor centroids, int n_rows, float radius, int id_base=0, int row_chunk=0) -> (Tensor, Tensor, Tensor)");
+  m.def("impact_range_search(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, float radius, int id_base=0, "
+        "int window_rows=0, int row_chunk=0) -> (Tensor, Tensor, Tensor)");
   m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
@@ -500,4 +573,7 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("impact_topk", &impact_topk);
   m.impl("binary_topk", &binary_topk);
   m.impl("sparse_compact_csr", &sparse_compact_csr);
+  m.impl("sq_fp16_ip_range_search", &sq_fp16_ip_range_search);
+  m.impl("pq_ip_range_search", &pq_ip_range_search);
+  m.impl("impact_range_search", &impact_range_search);
 }

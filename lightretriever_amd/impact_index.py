@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .index import _workspace
+from .index import _range_args, _range_call, _range_empty, _workspace
 
 SCORE_LIMIT = 1 << 31   # the device accumulates in int32: a query whose bound B_q reaches this is refused
 
@@ -40,6 +40,7 @@ class ImpactIndex:
     Nothing touches the GPU before finalize() (the first search after an add runs it), so documents can be collected and a query be refused
     without one.  Not persisted: the reference's Lucene index lives in a temporary directory too.  NOT thread-safe."""
     MAX_K = 2048
+    range_row_chunk = 0   # lrx_range_impact_search's row_chunk: 0 = the library's 4 Mi; tests set a multiple of 128 (the hits do not depend on it)
     window_rows = 0   # lrx_impact_search's window_rows: 0 = the library's rule; tests and tools set a multiple of 128 (the hits do not depend on it)
 
     def __init__(self, device: Optional[torch.device] = None, id_base: int = 0):
@@ -175,3 +176,29 @@ class ImpactIndex:
                                               _lib.ptr(d_term), _lib.ptr(d_cnt), Q, k, int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map),
                                               _lib.ptr(ws), ws.numel(), int(self.window_rows), _lib.current_stream()))
         return D, I
+
+    def range_search(self, q_off, q_term, q_cnt, radius: float):
+        """Every hit above a score, never cut at k -> (lims i64[Q+1], D f32[lims[Q]], I i64[lims[Q]]) device tensors in the layout of
+        FlatIPIndex.range_search: query i owns [lims[i], lims[i+1]); a row is in it iff it is a hit (S >= 1) and (float) S, the score search()
+        reports, is strictly greater than `radius` -- a negative radius returns every hit; I = id_base + row in ascending row order.  Exact,
+        deterministic, independent of window_rows and the row chunking.  The queries and the overflow refusal are search()'s
+        (check_queries).  Synchronises with the host once per call; not under graph capture."""
+        radius = _range_args("ImpactIndex", radius)
+        off, term, cnt = self.check_queries(q_off, q_term, q_cnt)
+        Q = off.size - 1
+        if Q == 0 or self.ntotal == 0:
+            _lib.require_gpu()
+            return _range_empty(self.device or torch.device("cuda", torch.cuda.current_device()), Q)
+        self._dirty = self._dirty or self._postings is None
+        self.finalize()
+        csr = torch.from_numpy(np.concatenate([off, term, cnt])).to(self.device)       # one upload
+        d_off, d_term, d_cnt = csr[:Q + 1], csr[Q + 1:Q + 1 + term.size], csr[Q + 1 + term.size:]
+        rc = int(self.range_row_chunk)
+        ws = _workspace(vars(self), "_ws", int(self.lib.lrx_range_impact_workspace_bytes(self.ntotal, Q, rc)), self.device)
+        stream = _lib.current_stream()
+
+        def call(s, n, lc, Dc, Ic, cap):
+            _lib.check(self.lib.lrx_range_impact_search(_lib.ptr(self._postings), _lib.ptr(self._term_off), self.n_terms, self.ntotal, _lib.ptr(d_off),
+                                                        _lib.ptr(d_term), _lib.ptr(d_cnt), n, radius, int(self.id_base), _lib.ptr(lc), _lib.ptr(Dc),
+                                                        _lib.ptr(Ic), cap, _lib.ptr(ws), ws.numel(), int(self.window_rows), stream, rc))
+        return _range_call(self.device, Q, Q, call)

@@ -55,7 +55,8 @@ class FaissIndex:
         return scores, ids
 
     def range_search(self, query_embeddings, radius: float):
-        """-> (lims, D, I) of FlatIPIndex.range_search, with I mapped through the passage ids as in search()."""
+        """-> (lims, D, I) of FlatIPIndex.range_search, with I mapped through the passage ids as in search().  The wrapped index may be a
+        FlatIPIndex, an SQFp16Index or a PQIndex: each serves range_search under its own score."""
         lims, scores, ids = self.index.range_search(query_embeddings, radius)
         if self._passage_ids is not None:
             ids = self._passage_ids[ids]
@@ -531,6 +532,17 @@ class ImpactSearch:
         csr = self._query_rows(query_emb) if isinstance(query_emb, SparseRows) else query_csr([self._query_terms(q) for q in query_emb])
         D, I = self.impact_index.search(*csr, top_k)
         return _to_result_dict(D, I, query_ids, self.rev_mapping)
+
+    def retrieve_all_with_emb(self, query_emb, query_ids, min_score=0):
+        """Every hit, not the top_k: the query forms of retrieve_with_emb -> {qid: {pid: score}} of ALL documents that share a term with the
+        query and score above `min_score` (ImpactIndex.range_search; scores are >= 1, so the default keeps every hit).  A pid indexed twice
+        keeps the score of its later row, as in retrieve_with_emb."""
+        assert len(query_emb) == len(query_ids)
+        csr = self._query_rows(query_emb) if isinstance(query_emb, SparseRows) else query_csr([self._query_terms(q) for q in query_emb])
+        lims, D, I = self.impact_index.range_search(*csr, float(min_score))
+        lims, D, I = lims.cpu().tolist(), D.cpu().tolist(), I.cpu().tolist()
+        rev = self.rev_mapping
+        return {qid: {rev[I[j]]: D[j] for j in range(lims[i], lims[i + 1])} for i, qid in enumerate(query_ids)}
 
 
 class HybridSearch:
