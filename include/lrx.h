@@ -720,6 +720,17 @@ int lrx_impact_search(const void* postings, const int64_t* term_off, int32_t n_t
                       const int32_t* q_term, const int32_t* q_cnt, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores,
                       int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, int32_t window_rows, void* stream);
 
+/* (added in ABI 8, additively) Exact fp32 linear map, the hot path of a PCA pre-transform (PCAMatrix / PreTransformIndex):
+ *   out[r * ldo + o] = b[o] + sum_k A[o * d_in + k] * x[r * ldx + k]      r < n_rows, o < d_out; A row-major [d_out, d_in]; b may be NULL (+0).
+ * fp32 operands on the f32-input MFMA.  Every output has ONE accumulator chain: it starts at b[o] and takes the products in ascending k, one
+ * rounding per product.  No split-K, no atomics: a row's result depends on that row, A and b alone -- not on n_rows, on the row's position in
+ * the call or on the tile it lands in.  Columns [d_out, ldo) of `out` are left untouched.
+ * d_in % 8 == 0, 8 <= d_in <= 8192; any d_out >= 1 and n_rows >= 0 (0 rows: nothing is launched); ldx >= d_in, ldo >= d_out; anything else is
+ * LRX_ERR_INVALID before any device work.  x and A are read 16 bytes at a time where their addresses allow it, 4 otherwise.  `out` must not
+ * overlap x or A. */
+int lrx_linear_transform(const float* x, int64_t n_rows, int64_t ldx, const float* A, const float* b, int32_t d_in, int32_t d_out, float* out,
+                         int64_t ldo, void* stream);
+
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);
 int lrx_flat_ip_scores(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries,

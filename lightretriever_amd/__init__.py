@@ -3,3 +3,4 @@ from .encoder import EncoderConfig, LrxEncoder, interleave_gate_up, lora_merge, 
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk  # noqa: F401
 from .impact_index import ImpactIndex  # noqa: F401
 from .sparse_rows import SparseRows  # noqa: F401
+from .transform import PCAMatrix, PreTransformIndex  # noqa: F401

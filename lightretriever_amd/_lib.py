@@ -101,6 +101,7 @@ SIGNATURES = {
     "lrx_sq8_train_minmax": (_I32, [_P, _I64, _I64, _I32, _P, _P]),
     "lrx_sq8_encode": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _P, _I64, _P]),
     "lrx_sq8_decode_rows": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _P, _I64, _P]),
+    "lrx_linear_transform": (_I32, [_P, _I64, _I64, _P, _P, _I32, _I32, _P, _I64, _P]),
     "lrx_impact_workspace_bytes": (_SZ, [_I64, _I32, _I32]),
     "lrx_impact_chunk_queries": (_I32, [_I64, _I32, _I32]),
     "lrx_impact_search": (_I32, [_P, _P, _I32, _I64, _P, _P, _P, _I32, _I32, _I64, _P, _P, _P, _P, _SZ, _I32, _P]),

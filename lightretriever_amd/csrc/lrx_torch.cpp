@@ -523,6 +523,25 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sparse_compact_csr(const at::Tens
   return {row_off, terms, weights};
 }
 
+// Exact fp32 linear map (lrx_linear_transform): x [n, d_in] (rows may be strided), A [d_out, d_in] contiguous, b [d_out] or None -> [n, d_out].
+at::Tensor linear_transform(const at::Tensor& x, const at::Tensor& A, const c10::optional<at::Tensor>& b) {
+  DevGuard guard(x.device());
+  need(x, "x", at::kFloat, 2);
+  need(A, "A", at::kFloat, 2);
+  TORCH_CHECK(A.is_contiguous() && A.size(1) == x.size(1), "linear_transform: x [n, d_in], A [d_out, d_in] contiguous");
+  const float* bp = nullptr;
+  if (b.has_value()) {
+    need(*b, "b", at::kFloat, 1);
+    TORCH_CHECK(b->is_contiguous() && b->numel() == A.size(0), "linear_transform: b [d_out] contiguous");
+    bp = b->data_ptr<float>();
+  }
+  at::Tensor out = at::empty({x.size(0), A.size(0)}, x.options());
+  lrx_check(lrx_linear_transform(x.data_ptr<float>(), x.size(0), x.size(0) > 1 ? x.stride(0) : x.size(1), A.data_ptr<float>(), bp, (int32_t)x.size(1),
+                                 (int32_t)A.size(0), out.data_ptr<float>(), A.size(0), cur_stream()),
+            "linear_transform");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(lrx, m) {
@@ -550,6 +569,7 @@ TORCH_LIBRARY(lrx, m) {
   m.def("pq_ip_range_search(Tensor q, Tensor codes, Tensor centroids, int n_rows, float radius, int id_base=0, int row_chunk=0) -> (Tensor, Tensor, Tensor)");
   m.def("impact_range_search(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, float radius, int id_base=0, "
         "int window_rows=0, int row_chunk=0) -> (Tensor, Tensor, Tensor)");
+  m.def("linear_transform(Tensor x, Tensor A, Tensor? b=None) -> Tensor");
   m.def("binary_topk(Tensor q, Tensor codes, int n_rows, int k, int binary_k=1000, bool rerank=True, Tensor? threshold=None, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
 }
 
@@ -576,4 +596,5 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq_fp16_ip_range_search", &sq_fp16_ip_range_search);
   m.impl("pq_ip_range_search", &pq_ip_range_search);
   m.impl("impact_range_search", &impact_range_search);
+  m.impl("linear_transform", &linear_transform);
 }

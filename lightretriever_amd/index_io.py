@@ -64,7 +64,23 @@ A binary flat shard (BinaryFlatIndex, faiss IndexBinaryFlat(d)) is written as Fa
     u8    xb[ntotal][code_size]               row-major, np.packbits bit order
 
 Like the others it is **unverified against a Faiss build**.  Files with code_size != d / 8, a size word or a length that does not match are
-rejected."""
+rejected.
+
+A PCA pre-transform index (PreTransformIndex over a PCAMatrix, faiss IndexPreTransform(PCAMatrix, base)) is written as Faiss's serialisation of
+IndexPreTransform with a chain of one PCAMatrix (write_VectorTransform), same source:
+
+    u32   fourcc 'IxPT'
+          the index header of 'IxFI' above (d = d_in, ntotal, two dummies, is_trained, metric_type = 0)
+    i32   nchain = 1
+    u32   fourcc 'PcAm'                       (PCAMatrix with epsilon; the legacy 'PCAm' record has none and is rejected)
+    f32   eigen_power,  f32 epsilon = 0,  u8 random_rotation,  i32 balanced_bins = 0
+    u64 n, f32 mean[n]    u64 n, f32 eigenvalues[n]    u64 n, f32 PCAMat[n]        (n = d_in, d_in, d_in * d_in; all 0 when untrained)
+    u8    have_bias = 1                       (the LinearTransform part)
+    u64 n, f32 A[n]       u64 n, f32 b[n]                                          (n = d_out * d_in, d_out; 0 when untrained)
+    i32   d_in,  i32 d_out,  u8 is_trained    (the VectorTransform part)
+          the base index: a complete 'IxFI', 'IxSQ' or 'IxPq' record as above, to the end of the file
+
+It too is **unverified against a Faiss build**.  Truncated files, other chain lengths, other transforms and inconsistent sizes are rejected."""
 from __future__ import annotations
 
 import csv
@@ -89,11 +105,13 @@ def _index_header(fourcc: bytes, d: int, ntotal: int, is_trained: bool = True) -
 
 
 def _write_index(fname: str, who: str, ntotal: int, head: bytes, blocks: Iterable[np.ndarray], dtype: str, width: int, width_name: str = "d",
-                 tail: bytes = b"") -> None:
+                 tail: bytes = b"", prefix: bytes = b"") -> None:
     """`head` (the packed index header and the format's fields up to and including the size word of the rows), the rows streamed from
-    `blocks` (arrays [n_i, width] in row order, sum n_i == ntotal, written as `dtype`), then `tail` -- to a .tmp file renamed over fname."""
+    `blocks` (arrays [n_i, width] in row order, sum n_i == ntotal, written as `dtype`), then `tail` -- to a .tmp file renamed over fname.
+    `prefix`: bytes that precede the record (the enclosing record of write_pre_transform); every reader takes the matching `offset`."""
     tmp = fname + ".tmp"
     with open(tmp, "wb") as f:
+        f.write(prefix)
         f.write(head)
         rows = 0
         for b in blocks:
@@ -116,22 +134,25 @@ def _read_header(f, fname: str, fourcc: bytes, what: str):
     return d, ntotal, trained, metric
 
 
-def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
+def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"") -> None:
     """blocks: fp32 [n_i, d] arrays in row order (streamed: the shard comes off the GPU in chunks), sum n_i == ntotal."""
-    _write_index(fname, "write_flat_ip", ntotal, _index_header(FOURCC_FLAT_IP, d, ntotal) + struct.pack("<Q", ntotal * d), blocks, "<f4", d)
+    _write_index(fname, "write_flat_ip", ntotal, _index_header(FOURCC_FLAT_IP, d, ntotal) + struct.pack("<Q", ntotal * d), blocks, "<f4", d,
+                 prefix=prefix)
 
 
-def read_flat_ip(fname: str) -> np.memmap:
-    """-> read-only memmap fp32 [ntotal, d] over the file (no copy; the caller streams it to the GPU)."""
-    size = os.path.getsize(fname)
+def read_flat_ip(fname: str, offset: int = 0) -> np.memmap:
+    """-> read-only memmap fp32 [ntotal, d] over the file (no copy; the caller streams it to the GPU).  offset: where the record starts (it
+    runs to the end of the file)."""
+    size = os.path.getsize(fname) - offset
     if size < HEADER_BYTES:
         raise ValueError(f"{fname}: too short for a flat index header")
     with open(fname, "rb") as f:
+        f.seek(offset)
         d, ntotal, _, metric = _read_header(f, fname, FOURCC_FLAT_IP, "an inner-product flat index")
         (n_floats,) = struct.unpack("<Q", f.read(8))
     if metric != 0 or d <= 0 or ntotal < 0 or n_floats != ntotal * d or size != HEADER_BYTES + 4 * n_floats:
         raise ValueError(f"{fname}: inconsistent flat index header (d={d}, ntotal={ntotal}, floats={n_floats}, metric={metric}, bytes={size})")
-    return np.memmap(fname, dtype="<f4", mode="r", offset=HEADER_BYTES, shape=(ntotal, d))
+    return np.memmap(fname, dtype="<f4", mode="r", offset=offset + HEADER_BYTES, shape=(ntotal, d))
 
 
 FOURCC_SQ = b"IxSQ"
@@ -140,32 +161,33 @@ _SQ = struct.Struct("<iifQQ")            # qtype, rangestat, rangestat_arg, d, c
 SQ_HEADER_BYTES = _HEADER.size + _SQ.size + 8 + 8   # + empty `trained` vector + u64 code bytes
 
 
-def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int) -> None:
+def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"") -> None:
     """blocks: fp16 [n_i, d] arrays (the codes) in row order, sum n_i == ntotal."""
     head = _index_header(FOURCC_SQ, d, ntotal) + _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<QQ", 0, ntotal * 2 * d)   # (empty `trained`, code bytes)
-    _write_index(fname, "write_sq_fp16", ntotal, head, blocks, "<f2", d)
+    _write_index(fname, "write_sq_fp16", ntotal, head, blocks, "<f2", d, prefix=prefix)
 
 
-def _read_sq_prefix(f, fname: str, more: int = 8):
-    """The 'IxSQ' prefix (index header + _SQ) at the start of the open file f -> (file size, d, ntotal, is_trained, metric_type, qtype,
-    sq.d, code_size); ValueError when the file is shorter than the prefix and `more` bytes, or is no 'IxSQ' file."""
-    size = os.path.getsize(fname)
+def _read_sq_prefix(f, fname: str, more: int = 8, offset: int = 0):
+    """The 'IxSQ' prefix (index header + _SQ) at `offset` of the open file f -> (record size, d, ntotal, is_trained, metric_type, qtype,
+    sq.d, code_size); ValueError when the record is shorter than the prefix and `more` bytes, or is no 'IxSQ' record."""
+    size = os.path.getsize(fname) - offset
     if size < _HEADER.size + _SQ.size + more:
         raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
+    f.seek(offset)
     d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_SQ, "a scalar-quantiser index")
     qtype, _, _, sq_d, code_size = _SQ.unpack(f.read(_SQ.size))
     return size, d, ntotal, is_trained, metric, qtype, sq_d, code_size
 
 
-def read_sq_fp16(fname: str) -> np.memmap:
-    """-> read-only memmap fp16 [ntotal, d] of the codes (no copy)."""
+def read_sq_fp16(fname: str, offset: int = 0) -> np.memmap:
+    """-> read-only memmap fp16 [ntotal, d] of the codes (no copy).  offset: where the record starts (it runs to the end of the file)."""
     with open(fname, "rb") as f:
-        size, d, ntotal, _, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname)
+        size, d, ntotal, _, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset)
         if qtype != QT_FP16:
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served (only QT_fp16 = {QT_FP16})")
         (n_trained,) = struct.unpack("<Q", f.read(8))
         off = _HEADER.size + _SQ.size + 8 + 4 * n_trained
-        f.seek(off)
+        f.seek(offset + off)
         tail = f.read(8)
     if len(tail) < 8:
         raise ValueError(f"{fname}: truncated scalar-quantiser index header")
@@ -174,7 +196,7 @@ def read_sq_fp16(fname: str) -> np.memmap:
     if metric != 0 or d <= 0 or ntotal < 0 or sq_d != d or code_size != 2 * d or n_bytes != ntotal * 2 * d or size != off + n_bytes:
         raise ValueError(f"{fname}: inconsistent QT_fp16 index (d={d}, ntotal={ntotal}, sq.d={sq_d}, code_size={code_size}, "
                          f"code bytes={n_bytes}, metric={metric}, file bytes={size})")
-    return np.memmap(fname, dtype="<f2", mode="r", offset=off, shape=(ntotal, d))
+    return np.memmap(fname, dtype="<f2", mode="r", offset=offset + off, shape=(ntotal, d))
 
 
 QT_8BIT, QT_8BIT_UNIFORM = 0, 2
@@ -187,26 +209,28 @@ def _sq8_trained_len(qtype: int, d: int) -> int:
     return 2 * d if qtype == QT_8BIT else 2
 
 
-def sq_qtype(fname: str) -> int:
+def sq_qtype(fname: str, offset: int = 0) -> int:
     """The ScalarQuantizer qtype of an 'IxSQ' file (faiss's enum: 0 8bit, 1 4bit, 2 8bit_uniform, 3 4bit_uniform, 4 fp16, ...)."""
     with open(fname, "rb") as f:
-        return _read_sq_prefix(f, fname, more=0)[5]
+        return _read_sq_prefix(f, fname, more=0, offset=offset)[5]
 
 
-def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: int, ntotal: int, qtype: int = QT_8BIT, is_trained: bool = True) -> None:
+def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: int, ntotal: int, qtype: int = QT_8BIT, is_trained: bool = True,
+              prefix: bytes = b"") -> None:
     """trained: fp32 vmin ++ vdiff (2 d floats for QT_8bit, 2 for QT_8bit_uniform); blocks: uint8 [n_i, d] code arrays in row order."""
     t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
     if t.size != _sq8_trained_len(qtype, d):
         raise ValueError(f"write_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
     head = _index_header(FOURCC_SQ, d, ntotal, is_trained) + _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes() + struct.pack("<Q", ntotal * d)
-    _write_index(fname, "write_sq8", ntotal, head, blocks, np.uint8, d)
+    _write_index(fname, "write_sq8", ntotal, head, blocks, np.uint8, d, prefix=prefix)
 
 
-def read_sq8(fname: str):
-    """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained)."""
+def read_sq8(fname: str, offset: int = 0):
+    """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained).  offset: where the record starts (it runs
+    to the end of the file)."""
     fixed = _HEADER.size + _SQ.size + 8
     with open(fname, "rb") as f:
-        size, d, ntotal, is_trained, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname)
+        size, d, ntotal, is_trained, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset)
         if qtype not in (QT_8BIT, QT_8BIT_UNIFORM):
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served here (QT_8bit = {QT_8BIT}, QT_8bit_uniform = {QT_8BIT_UNIFORM})")
         (n_t,) = struct.unpack("<Q", f.read(8))
@@ -218,7 +242,7 @@ def read_sq8(fname: str):
     off = fixed + 4 * n_t + 8
     if n_b != ntotal * d or size != off + n_b:
         raise ValueError(f"{fname}: inconsistent 8-bit codes (code bytes={n_b}, ntotal * d={ntotal * d}, file bytes={size})")
-    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=off, shape=(ntotal, d)) if ntotal else np.zeros((0, d), np.uint8)
+    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=offset + off, shape=(ntotal, d)) if ntotal else np.zeros((0, d), np.uint8)
     return qtype, trained, codes, bool(is_trained)
 
 
@@ -227,22 +251,25 @@ _PQ = struct.Struct("<QQQ")              # d, M, nbits (write_ProductQuantizer)
 _PQ_TAIL = struct.Struct("<iBi")         # search_type, encode_signs, polysemous_ht (9 bytes, packed)
 
 
-def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d: int, M: int, ntotal: int, is_trained: bool = True) -> None:
+def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d: int, M: int, ntotal: int, is_trained: bool = True,
+             prefix: bytes = b"") -> None:
     """centroids: fp32 [M, 256, d / M]; blocks: uint8 [n_i, M] code arrays in row order, sum n_i == ntotal."""
     c = np.ascontiguousarray(centroids, dtype="<f4")
     if c.size != d * 256:
         raise ValueError(f"write_pq: {c.size} centroid floats, expected d * 256 = {d * 256}")
     head = _index_header(FOURCC_PQ, d, ntotal, is_trained) + _PQ.pack(d, M, 8) + struct.pack("<Q", d * 256) + c.tobytes() + struct.pack("<Q", ntotal * M)
-    _write_index(fname, "write_pq", ntotal, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1))
+    _write_index(fname, "write_pq", ntotal, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1), prefix=prefix)
 
 
-def read_pq(fname: str):
-    """-> (centroids fp32 [M, 256, d / M], codes: read-only memmap uint8 [ntotal, M], is_trained)."""
-    size = os.path.getsize(fname)
+def read_pq(fname: str, offset: int = 0):
+    """-> (centroids fp32 [M, 256, d / M], codes: read-only memmap uint8 [ntotal, M], is_trained).  offset: where the record starts (it runs to
+    the end of the file)."""
+    size = os.path.getsize(fname) - offset
     fixed = _HEADER.size + _PQ.size + 8
     if size < fixed:
         raise ValueError(f"{fname}: too short for a product-quantiser index header")
     with open(fname, "rb") as f:
+        f.seek(offset)
         d, ntotal, trained, metric = _read_header(f, fname, FOURCC_PQ, "a product-quantiser index")
         pq_d, M, nbits = _PQ.unpack(f.read(_PQ.size))
         if nbits != 8:
@@ -257,11 +284,11 @@ def read_pq(fname: str):
         off = fixed + 4 * n_c + 8
         if n_b != ntotal * M or size != off + n_b + _PQ_TAIL.size:
             raise ValueError(f"{fname}: inconsistent IndexPQ codes (code bytes={n_b}, ntotal * M={ntotal * M}, file bytes={size})")
-        f.seek(off + n_b)
+        f.seek(offset + off + n_b)
         search_type, _, _ = _PQ_TAIL.unpack(f.read(_PQ_TAIL.size))
     if search_type != 0:
         raise ValueError(f"{fname}: IndexPQ search_type {search_type} is not served (only ST_PQ = 0)")
-    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=off, shape=(ntotal, M)) if ntotal else np.zeros((0, M), np.uint8)
+    codes = np.memmap(fname, dtype=np.uint8, mode="r", offset=offset + off, shape=(ntotal, M)) if ntotal else np.zeros((0, M), np.uint8)
     return cent, codes, bool(trained)
 
 
@@ -294,6 +321,84 @@ def read_binary_flat(fname: str) -> np.ndarray:
     if ntotal == 0:
         return np.zeros((0, cs), np.uint8)
     return np.memmap(fname, dtype=np.uint8, mode="r", offset=BIN_HEADER_BYTES, shape=(ntotal, cs))
+
+
+FOURCC_PRE_TRANSFORM = b"IxPT"
+FOURCC_PCA = b"PcAm"
+_PCA = struct.Struct("<4sffBi")          # fourcc, eigen_power, epsilon, random_rotation, balanced_bins  (17 bytes, packed)
+_VT_TAIL = struct.Struct("<iiB")         # d_in, d_out, is_trained (9 bytes, packed)
+_PCA_VECTORS = ("mean", "eigenvalues", "PCAMat", "A", "b")
+
+
+def pre_transform_prefix(pca: dict, ntotal: int, is_trained: bool = True) -> bytes:
+    """The bytes of an 'IxPT' record up to its base index.  pca: d_in, d_out, eigen_power, random_rotation, is_trained and the fp32 arrays
+    mean [d_in], eigenvalues [d_in], PCAMat [d_in, d_in], A [d_out, d_in], b [d_out] (all empty for an untrained transform)."""
+    d_in, d_out = int(pca["d_in"]), int(pca["d_out"])
+    want = dict(mean=d_in, eigenvalues=d_in, PCAMat=d_in * d_in, A=d_out * d_in, b=d_out)
+    vec = {}
+    for name in _PCA_VECTORS:
+        v = np.ascontiguousarray(pca[name], dtype="<f4").reshape(-1)
+        if v.size != (want[name] if pca["is_trained"] else 0):
+            raise ValueError(f"write_pre_transform: {name} holds {v.size} floats, expected {want[name] if pca['is_trained'] else 0}")
+        vec[name] = struct.pack("<Q", v.size) + v.tobytes()
+    return (_index_header(FOURCC_PRE_TRANSFORM, d_in, ntotal, is_trained) + struct.pack("<i", 1)
+            + _PCA.pack(FOURCC_PCA, float(pca["eigen_power"]), 0.0, int(bool(pca["random_rotation"])), 0)
+            + vec["mean"] + vec["eigenvalues"] + vec["PCAMat"] + struct.pack("<B", 1) + vec["A"] + vec["b"]
+            + _VT_TAIL.pack(d_in, d_out, int(bool(pca["is_trained"]))))
+
+
+def write_pre_transform(fname: str, pca: dict, ntotal: int, is_trained: bool, write_base) -> None:
+    """An 'IxPT' file: the transform (see pre_transform_prefix), then the base index, written by `write_base(fname, prefix)` -- the writer of
+    the base's class (write_flat_ip, write_sq_fp16, write_sq8, write_pq) with the bytes that precede its record."""
+    write_base(fname, pre_transform_prefix(pca, ntotal, is_trained))
+
+
+def read_pre_transform(fname: str):
+    """-> (pca, base): pca as pre_transform_prefix takes it; base = dict(offset, fourcc, qtype, d, ntotal, is_trained): where the base index
+    record starts, its fourcc ('IxFI', 'IxSQ' or 'IxPq'; qtype: the ScalarQuantizer type of an 'IxSQ' record, else None) and the header of the
+    'IxPT' record.  The caller reads the base with the reader of its class at `offset`."""
+    size = os.path.getsize(fname)
+    with open(fname, "rb") as f:
+        def take(n: int, what: str) -> bytes:
+            b = f.read(n)
+            if len(b) != n:
+                raise ValueError(f"{fname}: truncated pre-transform index ({what})")
+            return b
+
+        fourcc, d, ntotal, _, _, is_trained, metric = _HEADER.unpack(take(_HEADER.size, "index header"))
+        if fourcc != FOURCC_PRE_TRANSFORM:
+            raise ValueError(f"{fname}: fourcc {fourcc!r} is not a pre-transform index ({FOURCC_PRE_TRANSFORM.decode()!r})")
+        (nchain,) = struct.unpack("<i", take(4, "chain length"))
+        if nchain != 1:
+            raise ValueError(f"{fname}: a chain of {nchain} transforms is not served (only one PCAMatrix)")
+        tcc, eigen_power, epsilon, rr, bins = _PCA.unpack(take(_PCA.size, "transform header"))
+        if tcc != FOURCC_PCA:
+            raise ValueError(f"{fname}: transform {tcc!r} is not served (only PCAMatrix {FOURCC_PCA.decode()!r}; the legacy 'PCAm' record has no epsilon)")
+        if epsilon != 0 or bins != 0:
+            raise ValueError(f"{fname}: PCAMatrix epsilon={epsilon} / balanced_bins={bins} are not served (only 0)")
+        pca = dict(eigen_power=eigen_power, random_rotation=bool(rr))
+        for name in _PCA_VECTORS:
+            if name == "A" and take(1, "have_bias") != b"\x01":
+                raise ValueError(f"{fname}: a PCAMatrix without bias is not served")
+            (n,) = struct.unpack("<Q", take(8, name))
+            if f.tell() + 4 * n > size:
+                raise ValueError(f"{fname}: truncated pre-transform index ({name}: {n} floats)")
+            pca[name] = np.frombuffer(take(4 * n, name), dtype="<f4").copy()
+        d_in, d_out, t_trained = _VT_TAIL.unpack(take(_VT_TAIL.size, "transform dimensions"))
+        offset = f.tell()
+        sub = take(4, "base index")
+    want = dict(mean=d_in, eigenvalues=d_in, PCAMat=d_in * d_in, A=d_out * d_in, b=d_out)
+    sizes = {name: pca[name].size for name in _PCA_VECTORS}
+    if metric != 0 or d != d_in or not 0 < d_out <= d_in or ntotal < 0 or sizes != (want if t_trained else dict.fromkeys(want, 0)):
+        raise ValueError(f"{fname}: inconsistent pre-transform index (d={d}, d_in={d_in}, d_out={d_out}, ntotal={ntotal}, metric={metric}, "
+                         f"trained={t_trained}, floats={sizes})")
+    if t_trained:
+        pca["PCAMat"], pca["A"] = pca["PCAMat"].reshape(d_in, d_in), pca["A"].reshape(d_out, d_in)
+    pca.update(d_in=d_in, d_out=d_out, is_trained=bool(t_trained))
+    if sub not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
+        raise ValueError(f"{fname}: base index {sub!r} is not served ('IxFI', 'IxSQ', 'IxPq')")
+    qtype = sq_qtype(fname, offset) if sub == FOURCC_SQ else None
+    return pca, dict(offset=offset, fourcc=sub, qtype=qtype, d=d, ntotal=ntotal, is_trained=bool(is_trained))
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

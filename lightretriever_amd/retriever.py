@@ -6,6 +6,7 @@
     PQFaissSearch       <- retriever/faiss_search.py:326-383             (IndexPQ, 8-bit codes, inner product only, over PQIndex)
     FaissBinaryIndex    <- retriever/faiss_index.py:116-192              (Hamming candidates + float rerank over BinaryFlatIndex)
     BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
+    PCAFaissSearch      <- retriever/faiss_search.py:512-565             (IndexPreTransform(PCAMatrix, base) over PreTransformIndex)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
     ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
@@ -31,6 +32,7 @@ import torch
 from .impact_index import ImpactIndex, query_csr
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 from .sparse_rows import SparseRows, identity_term
+from .transform import BASES as _PCA_BASES, PCAMatrix, PreTransformIndex
 
 logger = logging.getLogger(__name__)
 FLT_MAX = float(np.finfo(np.float32).max)
@@ -418,6 +420,62 @@ class BinaryFaissSearch(FlatIPFaissSearch):
         return "binary_faiss_index"
 
 
+class PCAFaissSearch(FlatIPFaissSearch):
+    """faiss_search.py:512-565: IndexPreTransform(PCAMatrix(d, output_dimension, eigen_power, random_rotation), base_index), served by
+    PreTransformIndex -- the dense rows are reduced to output_dimension by an exact fp32 linear map on their way into the base index, the
+    queries on their way into its search.  base_index: a FlatIPIndex, SQFp16Index, SQ8Index or PQIndex of dimension output_dimension, used
+    (and emptied first) for every chunk, or None: a fresh FlatIPIndex(output_dimension) per chunk.  As in the reference the matrix trained
+    on the first chunk is kept in `pca_matrix` and copied (PCAMatrix.copy_from) into the index of every later chunk, so the chunk loop
+    trains once and the scores of different chunks are comparable; pass pca_matrix= to start from a trained one.  index() trains on the chunk
+    and then adds it, _index_in_place trains when the staging slot is committed.  Not served: random_rotation, shards on RPC workers."""
+    index_cls = PreTransformIndex
+    index_ext = "pca"
+    serves_rpc_shards = False
+
+    def __init__(self, model, base_index=None, output_dimension: Optional[int] = None, batch_size: int = 128, corpus_chunk_size: Optional[int] = None,
+                 pca_matrix: Optional[PCAMatrix] = None, random_rotation: bool = False, eigen_power: float = 0.0, **kwargs):
+        if output_dimension is None or int(output_dimension) < 1:
+            raise ValueError(f"PCAFaissSearch: output_dimension={output_dimension!r} must be a positive integer (the dimension after the PCA)")
+        if random_rotation:
+            raise NotImplementedError("PCAFaissSearch: random_rotation is not served (faiss's random rotation cannot be reproduced)")
+        if base_index is not None and not isinstance(base_index, _PCA_BASES):
+            raise TypeError(f"PCAFaissSearch: base index {type(base_index).__name__} is not served (only "
+                            f"{', '.join(c.__name__ for c in _PCA_BASES)})")
+        if base_index is not None and base_index.d != int(output_dimension):
+            raise ValueError(f"PCAFaissSearch: the base index's d={base_index.d} is not output_dimension={output_dimension}")
+        if pca_matrix is not None and not isinstance(pca_matrix, PCAMatrix):
+            raise TypeError(f"PCAFaissSearch: pca_matrix must be a PCAMatrix, got {type(pca_matrix).__name__}")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.base_index = base_index
+        self.output_dim = int(output_dimension)
+        self.pca_matrix = pca_matrix
+        self.random_rotation = False
+        self.eigen_power = float(eigen_power)
+
+    def _new_index(self, dim: int, capacity: int) -> PreTransformIndex:
+        pca = PCAMatrix(dim, self.output_dim, self.eigen_power, self.random_rotation)
+        if self.pca_matrix is not None:
+            pca.copy_from(self.pca_matrix)
+        self.pca_matrix = pca                         # (trained with the index it belongs to: index() / the commit of _index_in_place)
+        base = self.base_index
+        if base is None:
+            base = FlatIPIndex(self.output_dim, capacity=capacity)
+        else:
+            base.reset()
+        return PreTransformIndex(pca, base)
+
+    def _train(self, idx: PreTransformIndex, corpus_emb):
+        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it (FaissTrainIndex.build)
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        self.pca_matrix = self.faiss_index.index.transform
+        self.output_dim, self.eigen_power = self.pca_matrix.d_out, self.pca_matrix.eigen_power
+
+    def get_index_name(self):
+        return "pca_faiss_index"
+
+
 class ImpactSearch:
     """The sparse engine HybridSearch calls, with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
     `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`), over an HBM-resident ImpactIndex instead of Lucene behind a JVM: impact
@@ -579,11 +637,11 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ) and "binary" (IndexBinaryFlat + rerank) are
-        # served; anything else is served flat
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank) and
+        # "pca" (IndexPreTransform(PCAMatrix, base)) are served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
-        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq", "binary"):
+        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
         den_kwargs = {}
         if faiss_search_map == "pq":                  # (the reference passes its **kwargs through to the searcher)
@@ -592,6 +650,10 @@ class HybridSearch:
             den_kwargs = {a: kwargs[a] for a in ("quantizer_type", "similarity_metric") if a in kwargs}
         if faiss_search_map == "binary":
             den_kwargs = {a: kwargs[a] for a in ("binary_k", "threshold") if a in kwargs}
+        if faiss_search_map == "pca":
+            if kwargs.get("output_dimension") is None:
+                raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
+            den_kwargs = {a: kwargs[a] for a in ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation") if a in kwargs}
         self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
         self.dense_search.encode_kwargs = dict(self._encode_kwargs)
         self.return_all_results = return_all_results
