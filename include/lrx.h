@@ -209,7 +209,8 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
                          void* stream);
 /* Number of out-of-range token ids any embedding gather (stand-alone or inside lrx_encode_*) has met since the last reset, plus the
  * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
- * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter); -1 if the read
+ * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
+ * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped; -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -730,6 +731,31 @@ int lrx_impact_search(const void* postings, const int64_t* term_off, int32_t n_t
  * overlap x or A. */
 int lrx_linear_transform(const float* x, int64_t n_rows, int64_t ldx, const float* A, const float* b, int32_t d_in, int32_t d_out, float* out,
                          int64_t ldo, void* stream);
+
+/* (added in ABI 8, additively) RERANK: the exact scores of a CALLER's candidate rows and their top k -- the second stage of faiss
+ * IndexRefineFlat / IndexRefine over a full-precision copy of the rows (RefineFlatIndex).
+ *   candidates  cand_rows[i * ld_cand + j], j < n_cand: ROW numbers of query i's candidates (what a base search with id_base = 0 returns).
+ *               An entry < 0 (the base's -1 padding) is skipped.  An entry >= n_rows is NEVER dereferenced: it is skipped and counted once in
+ *               lrx_device_error_count.  A row that occurs twice is scored and reported twice, as faiss does.
+ *   score       lrx_flat_ip_rerank: the flat index's score over the fp32 rows X[row * ldx + c], (float) of the fp64 sum of the fp32 products;
+ *               lrx_sq_fp16_ip_rerank: the same over the tiled fp16 codes (lrx_sq_fp16_ip_search's layout and score).  Bit for bit what
+ *               lrx_flat_ip_search_bounded / lrx_sq_fp16_ip_search report for that (query, row): the same device function computes it.
+ *   order       score descending, ties to the lower row; (-FLT_MAX, -1) where fewer than k valid candidates exist.  out_ids = id_base + row,
+ *               or row_map[row] when row_map != NULL (int64 [>= n_rows], device).  out_scores / out_ids: [n_queries, k], contiguous.
+ *   a query's result depends on its own row of q and of cand_rows alone: not on n_queries, its position in the call or the split below.
+ *   limits      1 <= k <= n_cand <= 2048; ld_cand >= n_cand; 0 <= n_rows < 2^32; q 16-byte aligned ([n_queries, dim] contiguous);
+ *               fp32 rows: dim % 4 == 0, ldx >= dim, ldx % 4 == 0, X 16-byte aligned; codes: dim % 64 == 0.  n_queries == 0 launches nothing.
+ *               Anything else is LRX_ERR_INVALID before any device work; a workspace under lrx_ip_rerank_workspace_bytes: LRX_ERR_WORKSPACE.
+ * Two launches on `stream`, no host synchronisation, capturable in a HIP graph: grid (query, part) -- a part takes every part-count-th
+ * candidate, one half-wave per row (a random gather of whole rows, non-temporal loads), and publishes packed (score, row) words -- then one
+ * workgroup per query sorts at most 2048 words in LDS and writes the top k. */
+size_t lrx_ip_rerank_workspace_bytes(int32_t n_queries, int32_t n_cand, int32_t k);
+int lrx_flat_ip_rerank(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const float* q, int32_t n_queries, const int64_t* cand_rows,
+                       int32_t n_cand, int64_t ld_cand, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int lrx_sq_fp16_ip_rerank(const void* codes, int64_t n_rows, int32_t dim, const float* q, int32_t n_queries, const int64_t* cand_rows,
+                          int32_t n_cand, int64_t ld_cand, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

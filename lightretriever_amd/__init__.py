@@ -4,3 +4,4 @@ from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index,
 from .impact_index import ImpactIndex  # noqa: F401
 from .sparse_rows import SparseRows  # noqa: F401
 from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
+from .refine import RefineFlatIndex  # noqa: F401

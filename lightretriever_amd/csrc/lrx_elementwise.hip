@@ -166,11 +166,14 @@ extern "C" int64_t lrx_device_saturation_count(int32_t reset) {
 }
 
 unsigned int lrx_attn_list_overflows(int* ok, int reset);   // lrx_attn.hip: attention work lists the builder could not fit (their launches compute nothing)
+unsigned int lrx_rerank_bad_rows(int* ok, int reset);       // lrx_search_rerank.h: candidate entries >= n_rows the rerank skipped
 extern "C" int64_t lrx_device_error_count(int32_t reset) {
   unsigned int v = 0;
   if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_bad_token_ids), sizeof(v)) != hipSuccess) return -1;
   int ok = 0;
-  const unsigned int a = lrx_attn_list_overflows(&ok, reset);
+  unsigned int a = lrx_attn_list_overflows(&ok, reset);
+  if (!ok) return -1;
+  a += lrx_rerank_bad_rows(&ok, reset);
   if (!ok) return -1;
   if (reset && v) {
     const unsigned int z = 0;

@@ -285,6 +285,59 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_topk(const at::Tensor&
   return {o.d, o.i, o.w};
 }
 
+// Rerank (lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank): the exact scores of the caller's candidate rows cand [Q, n_cand] (int64 row numbers, rows
+// may be strided; < 0 skipped, >= n_rows skipped and counted) and their top k.  Returns (D, I).
+struct RerankArgs {
+  int64_t n_cand, ld_cand;
+  const int64_t* rm;
+  at::Tensor ws;
+  size_t wsb;
+};
+RerankArgs rerank_args(const char* op, const at::Tensor& q, int64_t dim, const at::Tensor& cand, int64_t k, int64_t n_rows,
+                       const c10::optional<at::Tensor>& row_map) {
+  need(q, "q", at::kFloat, 2);
+  need(cand, "cand", at::kLong, 2);
+  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && cand.size(0) == q.size(0), op, ": q [Q,D] contiguous, cand int64 [Q, n_cand]");
+  const int64_t n_cand = cand.size(1);
+  TORCH_CHECK(1 <= k && k <= n_cand && n_cand <= 2048 && n_rows >= 0, op, ": need 1 <= k <= n_cand <= 2048, got k=", k, ", n_cand=", n_cand);
+  RerankArgs a;
+  a.n_cand = n_cand;
+  a.ld_cand = cand.size(0) > 1 ? cand.stride(0) : n_cand;
+  a.rm = row_map_ptr(row_map, n_rows, "rerank: row_map int64 [>= n_rows] contiguous");
+  a.wsb = lrx_ip_rerank_workspace_bytes((int32_t)q.size(0), (int32_t)n_cand, (int32_t)k);
+  a.ws = bytes((int64_t)a.wsb, q);
+  return a;
+}
+
+std::tuple<at::Tensor, at::Tensor> flat_ip_rerank(const at::Tensor& q, const at::Tensor& x, const at::Tensor& cand, int64_t k, int64_t id_base,
+                                                  const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(x, "x", at::kFloat, 2);
+  const int64_t n_rows = x.size(0), dim = x.size(1);
+  TORCH_CHECK(dim % 4 == 0 && dim > 0, "flat_ip_rerank: x [n_rows, D] with D % 4 == 0");
+  RerankArgs a = rerank_args("flat_ip_rerank", q, dim, cand, k, n_rows, row_map);
+  TopK o = topk_out(q, k);
+  lrx_check(lrx_flat_ip_rerank(x.data_ptr<float>(), n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, q.data_ptr<float>(), (int32_t)q.size(0),
+                               cand.data_ptr<int64_t>(), (int32_t)a.n_cand, a.ld_cand, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(),
+                               a.rm, a.ws.data_ptr(), a.wsb, cur_stream()),
+            "flat_ip_rerank");
+  return {o.d, o.i};
+}
+
+std::tuple<at::Tensor, at::Tensor> sq_fp16_ip_rerank(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& cand, int64_t k,
+                                                     int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  TORCH_CHECK(q.dim() == 2 && q.size(1) % 64 == 0 && q.size(1) > 0 && n_rows >= 0, "sq_fp16_ip_rerank: q [Q,D] with D % 64 == 0, n_rows >= 0");
+  const int64_t dim = q.size(1);
+  RerankArgs a = rerank_args("sq_fp16_ip_rerank", q, dim, cand, k, n_rows, row_map);
+  void* cb = tiled_rows(codes, at::kHalf, n_rows, dim, "sq_fp16_ip_rerank: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
+  TopK o = topk_out(q, k);
+  lrx_check(lrx_sq_fp16_ip_rerank(cb, n_rows, (int32_t)dim, q.data_ptr<float>(), (int32_t)q.size(0), cand.data_ptr<int64_t>(), (int32_t)a.n_cand, a.ld_cand,
+                                  (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), a.rm, a.ws.data_ptr(), a.wsb, cur_stream()),
+            "sq_fp16_ip_rerank");
+  return {o.d, o.i};
+}
+
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
 // centroids [M, 256, D / M] fp32.  Returns (D, I).
 std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
@@ -560,6 +613,8 @@ TORCH_LIBRARY(lrx, m) {
   m.def("merge_topk(Tensor d_parts, Tensor i_parts) -> (Tensor, Tensor)");
   m.def("flat_ip_range_search(Tensor q, Tensor x, Tensor? x_shadow, Tensor row_bounds, float radius, int id_base=0) -> (Tensor, Tensor, Tensor)");
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
+  m.def("flat_ip_rerank(Tensor q, Tensor x, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("sq_fp16_ip_rerank(Tensor q, Tensor codes, int n_rows, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
@@ -588,6 +643,8 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("merge_topk", &merge_topk);
   m.impl("flat_ip_range_search", &flat_ip_range_search);
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
+  m.impl("flat_ip_rerank", &flat_ip_rerank);
+  m.impl("sq_fp16_ip_rerank", &sq_fp16_ip_rerank);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);

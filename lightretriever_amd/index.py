@@ -416,17 +416,21 @@ class FlatIPIndex(_TiledIPIndex):
         self._maintain(0, self.ntotal)
 
     # -- persistence (faiss.write_index / read_index of an IndexFlatIP, see index_io.py) --------------------------
-    def save(self, fname: str, chunk_rows: int = 262144, prefix: bytes = b""):
-        """prefix / load's offset: the record inside an enclosing one (PreTransformIndex.save)."""
+    def save(self, fname: str, chunk_rows: int = 262144, prefix: bytes = b"", append: bool = False):
+        """prefix / load's offset: the record inside an enclosing one (PreTransformIndex.save); append / load's end: the record continues a
+        file and is followed by more (RefineFlatIndex.save).  The same holds for every index class's save / load."""
         from .index_io import write_flat_ip
         write_flat_ip(fname, (self._x[s:min(s + chunk_rows, self.ntotal)].cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
-                      self.d, self.ntotal, prefix=prefix)
+                      self.d, self.ntotal, prefix=prefix, append=append)
 
     @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144, offset: int = 0) -> "FlatIPIndex":
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144, offset: int = 0,
+             end: Optional[int] = None, shadow_f16: bool = True) -> "FlatIPIndex":
+        """shadow_f16=False: the shard is built without its fp16 shadow (a row store that is never streamed: RefineFlatIndex.load)."""
         from .index_io import read_flat_ip
-        mm = read_flat_ip(fname, offset)
+        mm = read_flat_ip(fname, offset, end)
         idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
+        idx.shadow_f16 = shadow_f16
         for s in range(0, mm.shape[0], chunk_rows):
             e = min(s + chunk_rows, mm.shape[0])
             idx._x[s:e].copy_(torch.from_numpy(np.array(mm[s:e], copy=True)), non_blocking=False)
@@ -584,15 +588,16 @@ class SQFp16Index(_TiledIPIndex):
         return self.shadow_rows()
 
     # -- persistence (faiss.write_index / read_index of an IndexScalarQuantizer(QT_fp16), see index_io.py) -----------
-    def save(self, fname: str, chunk_rows: int = 262144, prefix: bytes = b""):
+    def save(self, fname: str, chunk_rows: int = 262144, prefix: bytes = b"", append: bool = False):
         from .index_io import write_sq_fp16
         write_sq_fp16(fname, (self.reconstruct_n(s, min(chunk_rows, self.ntotal - s)).half().cpu().numpy() for s in range(0, self.ntotal, chunk_rows)),
-                      self.d, self.ntotal, prefix=prefix)
+                      self.d, self.ntotal, prefix=prefix, append=append)
 
     @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144, offset: int = 0) -> "SQFp16Index":
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 262144, offset: int = 0,
+             end: Optional[int] = None) -> "SQFp16Index":
         from .index_io import read_sq_fp16
-        mm = read_sq_fp16(fname, offset)
+        mm = read_sq_fp16(fname, offset, end)
         idx = cls(mm.shape[1], capacity=mm.shape[0], device=device, id_base=id_base)
         for s in range(0, mm.shape[0], chunk_rows):
             e = min(s + chunk_rows, mm.shape[0])
@@ -852,15 +857,16 @@ class PQIndex(_CodeIndex):
         self.ntotal = codes.shape[0]
 
     # -- persistence (faiss.write_index / read_index of an IndexPQ, see index_io.py) ----------------------------------------
-    def save(self, fname: str, chunk_rows: int = 1 << 20, prefix: bytes = b""):
+    def save(self, fname: str, chunk_rows: int = 1 << 20, prefix: bytes = b"", append: bool = False):
         from .index_io import write_pq
         write_pq(fname, self.centroids.cpu().numpy(), (self.blocked_to_rows(self._codes[s // 128 * 128 * self.Mp:], min(chunk_rows, self.ntotal - s)).cpu().numpy()
-                                                       for s in range(0, self.ntotal, chunk_rows)), self.d, self.M, self.ntotal, self.is_trained, prefix=prefix)
+                                                       for s in range(0, self.ntotal, chunk_rows)), self.d, self.M, self.ntotal, self.is_trained, prefix=prefix,
+                 append=append)
 
     @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, offset: int = 0) -> "PQIndex":
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, offset: int = 0, end: Optional[int] = None) -> "PQIndex":
         from .index_io import read_pq
-        cent, codes, trained = read_pq(fname, offset)
+        cent, codes, trained = read_pq(fname, offset, end)
         M, _, dsub = cent.shape
         idx = cls(M * dsub, M, device=device, id_base=id_base)
         idx.set_contents(torch.from_numpy(cent), torch.from_numpy(np.array(codes, copy=True)))
@@ -1003,15 +1009,17 @@ class SQ8Index(_CodeIndex):
         self.ntotal = codes.shape[0]
 
     # -- persistence (faiss.write_index / read_index of an IndexScalarQuantizer(QT_8bit[_uniform]), see index_io.py) ----------
-    def save(self, fname: str, chunk_rows: int = 1 << 18, prefix: bytes = b""):
+    def save(self, fname: str, chunk_rows: int = 1 << 18, prefix: bytes = b"", append: bool = False):
         from .index_io import write_sq8
         write_sq8(fname, self.trained.cpu().numpy(), (self.blocked_to_rows(self._codes[s // 128 * 128 * self.d:], min(chunk_rows, self.ntotal - s)).cpu().numpy()
-                                                      for s in range(0, self.ntotal, chunk_rows)), self.d, self.ntotal, self._qt, self.is_trained, prefix=prefix)
+                                                      for s in range(0, self.ntotal, chunk_rows)), self.d, self.ntotal, self._qt, self.is_trained, prefix=prefix,
+                  append=append)
 
     @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 1 << 18, offset: int = 0) -> "SQ8Index":
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, chunk_rows: int = 1 << 18, offset: int = 0,
+             end: Optional[int] = None) -> "SQ8Index":
         from .index_io import read_sq8
-        qt, trained, codes, is_trained = read_sq8(fname, offset)
+        qt, trained, codes, is_trained = read_sq8(fname, offset, end)
         n, d = codes.shape
         idx = cls(d, {v: k for k, v in cls.QTYPES.items()}[qt], capacity=n, device=device, id_base=id_base)
         idx.trained = torch.from_numpy(trained).to(idx.device)

@@ -80,7 +80,21 @@ IndexPreTransform with a chain of one PCAMatrix (write_VectorTransform), same so
     i32   d_in,  i32 d_out,  u8 is_trained    (the VectorTransform part)
           the base index: a complete 'IxFI', 'IxSQ' or 'IxPq' record as above, to the end of the file
 
-It too is **unverified against a Faiss build**.  Truncated files, other chain lengths, other transforms and inconsistent sizes are rejected."""
+It too is **unverified against a Faiss build**.  Truncated files, other chain lengths, other transforms and inconsistent sizes are rejected.
+
+A refine index (RefineFlatIndex, faiss IndexRefineFlat(base) / IndexRefine(base, refine_index)) is written as Faiss's serialisation of
+IndexRefine, same source:
+
+    u32   fourcc 'IxRF'
+          the index header of 'IxFI' above (d, ntotal, two dummies, is_trained, metric_type = 0)
+          the base index: a complete 'IxPq', 'IxSQ' or 'IxPT' record as above
+          the refine index: a complete 'IxFI' record, or an 'IxSQ' record with qtype = 4 (QT_fp16)
+    f32   k_factor
+
+It too is **unverified against a Faiss build**.  Here a record is followed by more: every reader takes, next to `offset`, an optional `end`
+(default: the end of the file) that its record must fill exactly, index_record_end finds where a record stops, and every writer can continue
+a file (`append=True`).  Truncated files, a base or refine index whose d / ntotal disagree with the header and other record types are
+rejected."""
 from __future__ import annotations
 
 import csv
@@ -105,12 +119,13 @@ def _index_header(fourcc: bytes, d: int, ntotal: int, is_trained: bool = True) -
 
 
 def _write_index(fname: str, who: str, ntotal: int, head: bytes, blocks: Iterable[np.ndarray], dtype: str, width: int, width_name: str = "d",
-                 tail: bytes = b"", prefix: bytes = b"") -> None:
+                 tail: bytes = b"", prefix: bytes = b"", append: bool = False) -> None:
     """`head` (the packed index header and the format's fields up to and including the size word of the rows), the rows streamed from
     `blocks` (arrays [n_i, width] in row order, sum n_i == ntotal, written as `dtype`), then `tail` -- to a .tmp file renamed over fname.
-    `prefix`: bytes that precede the record (the enclosing record of write_pre_transform); every reader takes the matching `offset`."""
-    tmp = fname + ".tmp"
-    with open(tmp, "wb") as f:
+    `prefix`: bytes that precede the record (the enclosing record of write_pre_transform); every reader takes the matching `offset`.
+    append: continue the existing file fname instead (the second record of write_refine, which does the renaming itself)."""
+    tmp = fname if append else fname + ".tmp"
+    with open(tmp, "ab" if append else "wb") as f:
         f.write(prefix)
         f.write(head)
         rows = 0
@@ -123,7 +138,16 @@ def _write_index(fname: str, who: str, ntotal: int, head: bytes, blocks: Iterabl
         if rows != ntotal:
             raise ValueError(f"{who}: wrote {rows} rows, header says {ntotal}")
         f.write(tail)
-    os.replace(tmp, fname)
+    if not append:
+        os.replace(tmp, fname)
+
+
+def _end(fname: str, end: Optional[int]) -> int:
+    """Where a record that starts somewhere in fname must stop: `end`, or the end of the file."""
+    size = os.path.getsize(fname)
+    if end is not None and not 0 <= end <= size:
+        raise ValueError(f"{fname}: a record is said to end at byte {end} of {size}")
+    return size if end is None else end
 
 
 def _read_header(f, fname: str, fourcc: bytes, what: str):
@@ -134,16 +158,16 @@ def _read_header(f, fname: str, fourcc: bytes, what: str):
     return d, ntotal, trained, metric
 
 
-def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"") -> None:
+def write_flat_ip(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"", append: bool = False) -> None:
     """blocks: fp32 [n_i, d] arrays in row order (streamed: the shard comes off the GPU in chunks), sum n_i == ntotal."""
     _write_index(fname, "write_flat_ip", ntotal, _index_header(FOURCC_FLAT_IP, d, ntotal) + struct.pack("<Q", ntotal * d), blocks, "<f4", d,
-                 prefix=prefix)
+                 prefix=prefix, append=append)
 
 
-def read_flat_ip(fname: str, offset: int = 0) -> np.memmap:
-    """-> read-only memmap fp32 [ntotal, d] over the file (no copy; the caller streams it to the GPU).  offset: where the record starts (it
-    runs to the end of the file)."""
-    size = os.path.getsize(fname) - offset
+def read_flat_ip(fname: str, offset: int = 0, end: Optional[int] = None) -> np.memmap:
+    """-> read-only memmap fp32 [ntotal, d] over the file (no copy; the caller streams it to the GPU).  offset: where the record starts; it
+    runs to `end` (default: the end of the file)."""
+    size = _end(fname, end) - offset
     if size < HEADER_BYTES:
         raise ValueError(f"{fname}: too short for a flat index header")
     with open(fname, "rb") as f:
@@ -161,16 +185,16 @@ _SQ = struct.Struct("<iifQQ")            # qtype, rangestat, rangestat_arg, d, c
 SQ_HEADER_BYTES = _HEADER.size + _SQ.size + 8 + 8   # + empty `trained` vector + u64 code bytes
 
 
-def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"") -> None:
+def write_sq_fp16(fname: str, blocks: Iterable[np.ndarray], d: int, ntotal: int, prefix: bytes = b"", append: bool = False) -> None:
     """blocks: fp16 [n_i, d] arrays (the codes) in row order, sum n_i == ntotal."""
     head = _index_header(FOURCC_SQ, d, ntotal) + _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<QQ", 0, ntotal * 2 * d)   # (empty `trained`, code bytes)
-    _write_index(fname, "write_sq_fp16", ntotal, head, blocks, "<f2", d, prefix=prefix)
+    _write_index(fname, "write_sq_fp16", ntotal, head, blocks, "<f2", d, prefix=prefix, append=append)
 
 
-def _read_sq_prefix(f, fname: str, more: int = 8, offset: int = 0):
+def _read_sq_prefix(f, fname: str, more: int = 8, offset: int = 0, end: Optional[int] = None):
     """The 'IxSQ' prefix (index header + _SQ) at `offset` of the open file f -> (record size, d, ntotal, is_trained, metric_type, qtype,
     sq.d, code_size); ValueError when the record is shorter than the prefix and `more` bytes, or is no 'IxSQ' record."""
-    size = os.path.getsize(fname) - offset
+    size = _end(fname, end) - offset
     if size < _HEADER.size + _SQ.size + more:
         raise ValueError(f"{fname}: too short for a scalar-quantiser index header")
     f.seek(offset)
@@ -179,16 +203,17 @@ def _read_sq_prefix(f, fname: str, more: int = 8, offset: int = 0):
     return size, d, ntotal, is_trained, metric, qtype, sq_d, code_size
 
 
-def read_sq_fp16(fname: str, offset: int = 0) -> np.memmap:
-    """-> read-only memmap fp16 [ntotal, d] of the codes (no copy).  offset: where the record starts (it runs to the end of the file)."""
+def read_sq_fp16(fname: str, offset: int = 0, end: Optional[int] = None) -> np.memmap:
+    """-> read-only memmap fp16 [ntotal, d] of the codes (no copy).  offset: where the record starts; it runs to `end` (default: the end of
+    the file)."""
     with open(fname, "rb") as f:
-        size, d, ntotal, _, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset)
+        size, d, ntotal, _, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset, end=end)
         if qtype != QT_FP16:
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served (only QT_fp16 = {QT_FP16})")
         (n_trained,) = struct.unpack("<Q", f.read(8))
         off = _HEADER.size + _SQ.size + 8 + 4 * n_trained
         f.seek(offset + off)
-        tail = f.read(8)
+        tail = f.read(8) if off + 8 <= size else b""
     if len(tail) < 8:
         raise ValueError(f"{fname}: truncated scalar-quantiser index header")
     (n_bytes,) = struct.unpack("<Q", tail)
@@ -209,28 +234,28 @@ def _sq8_trained_len(qtype: int, d: int) -> int:
     return 2 * d if qtype == QT_8BIT else 2
 
 
-def sq_qtype(fname: str, offset: int = 0) -> int:
+def sq_qtype(fname: str, offset: int = 0, end: Optional[int] = None) -> int:
     """The ScalarQuantizer qtype of an 'IxSQ' file (faiss's enum: 0 8bit, 1 4bit, 2 8bit_uniform, 3 4bit_uniform, 4 fp16, ...)."""
     with open(fname, "rb") as f:
-        return _read_sq_prefix(f, fname, more=0, offset=offset)[5]
+        return _read_sq_prefix(f, fname, more=0, offset=offset, end=end)[5]
 
 
 def write_sq8(fname: str, trained: np.ndarray, blocks: Iterable[np.ndarray], d: int, ntotal: int, qtype: int = QT_8BIT, is_trained: bool = True,
-              prefix: bytes = b"") -> None:
+              prefix: bytes = b"", append: bool = False) -> None:
     """trained: fp32 vmin ++ vdiff (2 d floats for QT_8bit, 2 for QT_8bit_uniform); blocks: uint8 [n_i, d] code arrays in row order."""
     t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
     if t.size != _sq8_trained_len(qtype, d):
         raise ValueError(f"write_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
     head = _index_header(FOURCC_SQ, d, ntotal, is_trained) + _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes() + struct.pack("<Q", ntotal * d)
-    _write_index(fname, "write_sq8", ntotal, head, blocks, np.uint8, d, prefix=prefix)
+    _write_index(fname, "write_sq8", ntotal, head, blocks, np.uint8, d, prefix=prefix, append=append)
 
 
-def read_sq8(fname: str, offset: int = 0):
-    """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained).  offset: where the record starts (it runs
-    to the end of the file)."""
+def read_sq8(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> (qtype, trained fp32 [2 d] or [2], codes: read-only memmap uint8 [ntotal, d], is_trained).  offset: where the record starts; it runs
+    to `end` (default: the end of the file)."""
     fixed = _HEADER.size + _SQ.size + 8
     with open(fname, "rb") as f:
-        size, d, ntotal, is_trained, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset)
+        size, d, ntotal, is_trained, metric, qtype, sq_d, code_size = _read_sq_prefix(f, fname, offset=offset, end=end)
         if qtype not in (QT_8BIT, QT_8BIT_UNIFORM):
             raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served here (QT_8bit = {QT_8BIT}, QT_8bit_uniform = {QT_8BIT_UNIFORM})")
         (n_t,) = struct.unpack("<Q", f.read(8))
@@ -252,19 +277,19 @@ _PQ_TAIL = struct.Struct("<iBi")         # search_type, encode_signs, polysemous
 
 
 def write_pq(fname: str, centroids: np.ndarray, blocks: Iterable[np.ndarray], d: int, M: int, ntotal: int, is_trained: bool = True,
-             prefix: bytes = b"") -> None:
+             prefix: bytes = b"", append: bool = False) -> None:
     """centroids: fp32 [M, 256, d / M]; blocks: uint8 [n_i, M] code arrays in row order, sum n_i == ntotal."""
     c = np.ascontiguousarray(centroids, dtype="<f4")
     if c.size != d * 256:
         raise ValueError(f"write_pq: {c.size} centroid floats, expected d * 256 = {d * 256}")
     head = _index_header(FOURCC_PQ, d, ntotal, is_trained) + _PQ.pack(d, M, 8) + struct.pack("<Q", d * 256) + c.tobytes() + struct.pack("<Q", ntotal * M)
-    _write_index(fname, "write_pq", ntotal, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1), prefix=prefix)
+    _write_index(fname, "write_pq", ntotal, head, blocks, np.uint8, M, "M", _PQ_TAIL.pack(0, 0, M * 8 + 1), prefix=prefix, append=append)
 
 
-def read_pq(fname: str, offset: int = 0):
-    """-> (centroids fp32 [M, 256, d / M], codes: read-only memmap uint8 [ntotal, M], is_trained).  offset: where the record starts (it runs to
-    the end of the file)."""
-    size = os.path.getsize(fname) - offset
+def read_pq(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> (centroids fp32 [M, 256, d / M], codes: read-only memmap uint8 [ntotal, M], is_trained).  offset: where the record starts; it runs to
+    `end` (default: the end of the file)."""
+    size = _end(fname, end) - offset
     fixed = _HEADER.size + _PQ.size + 8
     if size < fixed:
         raise ValueError(f"{fname}: too short for a product-quantiser index header")
@@ -347,20 +372,24 @@ def pre_transform_prefix(pca: dict, ntotal: int, is_trained: bool = True) -> byt
             + _VT_TAIL.pack(d_in, d_out, int(bool(pca["is_trained"]))))
 
 
-def write_pre_transform(fname: str, pca: dict, ntotal: int, is_trained: bool, write_base) -> None:
+def write_pre_transform(fname: str, pca: dict, ntotal: int, is_trained: bool, write_base, prefix: bytes = b"") -> None:
     """An 'IxPT' file: the transform (see pre_transform_prefix), then the base index, written by `write_base(fname, prefix)` -- the writer of
-    the base's class (write_flat_ip, write_sq_fp16, write_sq8, write_pq) with the bytes that precede its record."""
-    write_base(fname, pre_transform_prefix(pca, ntotal, is_trained))
+    the base's class (write_flat_ip, write_sq_fp16, write_sq8, write_pq) with the bytes that precede its record.  prefix: bytes that precede
+    the 'IxPT' record itself."""
+    write_base(fname, prefix + pre_transform_prefix(pca, ntotal, is_trained))
 
 
-def read_pre_transform(fname: str):
+def read_pre_transform(fname: str, offset: int = 0, end: Optional[int] = None):
     """-> (pca, base): pca as pre_transform_prefix takes it; base = dict(offset, fourcc, qtype, d, ntotal, is_trained): where the base index
     record starts, its fourcc ('IxFI', 'IxSQ' or 'IxPq'; qtype: the ScalarQuantizer type of an 'IxSQ' record, else None) and the header of the
-    'IxPT' record.  The caller reads the base with the reader of its class at `offset`."""
-    size = os.path.getsize(fname)
+    'IxPT' record.  The caller reads the base with the reader of its class at `offset` (and the same `end`).  offset / end: where the 'IxPT'
+    record starts and stops (default: the whole file)."""
+    size = _end(fname, end)
     with open(fname, "rb") as f:
+        f.seek(offset)
+
         def take(n: int, what: str) -> bytes:
-            b = f.read(n)
+            b = f.read(n) if f.tell() + n <= size else b""
             if len(b) != n:
                 raise ValueError(f"{fname}: truncated pre-transform index ({what})")
             return b
@@ -397,8 +426,97 @@ def read_pre_transform(fname: str):
     pca.update(d_in=d_in, d_out=d_out, is_trained=bool(t_trained))
     if sub not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
         raise ValueError(f"{fname}: base index {sub!r} is not served ('IxFI', 'IxSQ', 'IxPq')")
-    qtype = sq_qtype(fname, offset) if sub == FOURCC_SQ else None
+    qtype = sq_qtype(fname, offset, end) if sub == FOURCC_SQ else None
     return pca, dict(offset=offset, fourcc=sub, qtype=qtype, d=d, ntotal=ntotal, is_trained=bool(is_trained))
+
+
+FOURCC_REFINE = b"IxRF"
+_REFINE_BASES = (FOURCC_PQ, FOURCC_SQ, FOURCC_PRE_TRANSFORM)
+
+
+def refine_prefix(d: int, ntotal: int, is_trained: bool = True) -> bytes:
+    """The bytes of an 'IxRF' record up to its base index."""
+    return _index_header(FOURCC_REFINE, d, ntotal, is_trained)
+
+
+def peek_index_header(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> (fourcc, d, ntotal, is_trained, metric_type) of the index record that starts at `offset`; ValueError when fewer bytes are left."""
+    if _end(fname, end) - offset < _HEADER.size:
+        raise ValueError(f"{fname}: truncated index record at byte {offset}")
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        fourcc, d, ntotal, _, _, trained, metric = _HEADER.unpack(f.read(_HEADER.size))
+    return fourcc, d, ntotal, bool(trained), metric
+
+
+def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> int:
+    """Where the 'IxFI', 'IxSQ', 'IxPq' or 'IxPT' record that starts at `offset` stops, from its own size words; ValueError when that is past
+    `end` (default: the end of the file) or the record is of another type.  The reader of the record's class then validates it against
+    [offset, the returned end)."""
+    size = _end(fname, end)
+    fourcc = peek_index_header(fname, offset, end)[0]
+    if fourcc == FOURCC_PRE_TRANSFORM:
+        return index_record_end(fname, read_pre_transform(fname, offset, end)[1]["offset"], end)
+    if fourcc not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
+        raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT')")
+    with open(fname, "rb") as f:
+        pos = offset + _HEADER.size + {FOURCC_FLAT_IP: 0, FOURCC_SQ: _SQ.size, FOURCC_PQ: _PQ.size}[fourcc]
+        # the vectors that follow: (bytes per element, ...) -- each a u64 count and its elements
+        for width in {FOURCC_FLAT_IP: (4,), FOURCC_SQ: (4, 1), FOURCC_PQ: (4, 1)}[fourcc]:
+            f.seek(pos)
+            word = f.read(8) if pos + 8 <= size else b""
+            if len(word) != 8:
+                raise ValueError(f"{fname}: truncated index record {fourcc!r} at byte {offset}")
+            pos += 8 + width * struct.unpack("<Q", word)[0]
+    pos += _PQ_TAIL.size if fourcc == FOURCC_PQ else 0
+    if pos > size:
+        raise ValueError(f"{fname}: truncated index record {fourcc!r} at byte {offset} (it needs {pos - offset} bytes, {size - offset} are left)")
+    return pos
+
+
+def write_refine(fname: str, d: int, ntotal: int, is_trained: bool, k_factor: float, write_base, write_store) -> None:
+    """An 'IxRF' file: the header, the base index written by `write_base(fname, prefix)`, the refine index appended by `write_store(fname)` --
+    the savers of the two indexes, the second one continuing the file -- and k_factor; built as fname.tmp and renamed over fname."""
+    tmp = fname + ".tmp"
+    write_base(tmp, refine_prefix(d, ntotal, is_trained))
+    write_store(tmp)
+    with open(tmp, "ab") as f:
+        f.write(struct.pack("<f", float(k_factor)))
+    os.replace(tmp, fname)
+
+
+def read_refine(fname: str):
+    """-> dict(d, ntotal, is_trained, k_factor, base, store); base / store = dict(offset, end, fourcc, qtype): where each record lies, its
+    fourcc (base: 'IxPq', 'IxSQ' or 'IxPT'; store: 'IxFI', or 'IxSQ' with qtype QT_fp16) and the ScalarQuantizer type of an 'IxSQ' record
+    (else None).  The caller reads each with the reader of its class at (offset, end)."""
+    size = os.path.getsize(fname)
+    if size < _HEADER.size + 4:
+        raise ValueError(f"{fname}: too short for a refine index")
+    fourcc, d, ntotal, is_trained, metric = peek_index_header(fname)
+    if fourcc != FOURCC_REFINE:
+        raise ValueError(f"{fname}: fourcc {fourcc!r} is not a refine index ({FOURCC_REFINE.decode()!r})")
+    if metric != 0 or d <= 0 or ntotal < 0:
+        raise ValueError(f"{fname}: inconsistent refine index header (d={d}, ntotal={ntotal}, metric={metric})")
+    body_end = size - 4
+    parts, pos = [], _HEADER.size
+    for what, served in (("base", _REFINE_BASES), ("refine", (FOURCC_FLAT_IP, FOURCC_SQ))):
+        cc, sub_d, sub_n, _, _ = peek_index_header(fname, pos, body_end)
+        if cc not in served:
+            raise ValueError(f"{fname}: {what} index {cc!r} is not served ({', '.join(repr(c.decode()) for c in served)})")
+        if sub_d != d or sub_n != ntotal:
+            raise ValueError(f"{fname}: the refine header says d={d}, ntotal={ntotal}; its {what} index d={sub_d}, ntotal={sub_n}")
+        stop = index_record_end(fname, pos, body_end)
+        qtype = sq_qtype(fname, pos, stop) if cc == FOURCC_SQ else None
+        parts.append(dict(offset=pos, end=stop, fourcc=cc, qtype=qtype))
+        pos = stop
+    if parts[1]["fourcc"] == FOURCC_SQ and parts[1]["qtype"] != QT_FP16:
+        raise ValueError(f"{fname}: refine index with ScalarQuantizer qtype {parts[1]['qtype']} is not served (only QT_fp16 = {QT_FP16})")
+    if pos != body_end:
+        raise ValueError(f"{fname}: {body_end - pos} bytes between the refine index and k_factor")
+    with open(fname, "rb") as f:
+        f.seek(body_end)
+        (k_factor,) = struct.unpack("<f", f.read(4))
+    return dict(d=d, ntotal=ntotal, is_trained=is_trained, k_factor=k_factor, base=parts[0], store=parts[1])
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

@@ -7,6 +7,7 @@
     FaissBinaryIndex    <- retriever/faiss_index.py:116-192              (Hamming candidates + float rerank over BinaryFlatIndex)
     BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
     PCAFaissSearch      <- retriever/faiss_search.py:512-565             (IndexPreTransform(PCAMatrix, base) over PreTransformIndex)
+    RefineFaissSearch   (no counterpart in the reference)                (faiss IndexRefineFlat over a PQ / SQ / PCA base: RefineFlatIndex)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
     ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
@@ -32,6 +33,7 @@ import torch
 from .impact_index import ImpactIndex, query_csr
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 from .sparse_rows import SparseRows, identity_term
+from .refine import RefineFlatIndex, check_k_factor, check_k_base
 from .transform import BASES as _PCA_BASES, PCAMatrix, PreTransformIndex
 
 logger = logging.getLogger(__name__)
@@ -476,6 +478,63 @@ class PCAFaissSearch(FlatIPFaissSearch):
         return "pca_faiss_index"
 
 
+class RefineFaissSearch(FlatIPFaissSearch):
+    """faiss IndexRefineFlat(base) / IndexRefine(base, IndexScalarQuantizer(QT_fp16)) as a searcher, served by RefineFlatIndex: every chunk is
+    indexed twice -- into a lossy base shard and into a full-precision row store -- and searched in two stages: the base's top
+    int(top_k * k_factor) rows, rescored exactly from the store, best top_k.  refine_base: "pq", "sq" or "pca" -- the searcher (PQFaissSearch,
+    SQFaissSearch, PCAFaissSearch) whose shard is the base; its own arguments go through **kwargs unchanged, so its refusals (use_rotation,
+    QT_8bit, random_rotation, ...) apply unchanged, and so does PCAFaissSearch's reuse of the first chunk's matrix.  refine_type: "flat" (fp32
+    rows without a shadow, 4 B/element) or "fp16" (SQFp16Index codes, 2 B/element).  index / _index_in_place / load / save behave like
+    FlatIPFaissSearch's with that shard; load() takes k_factor and the shard classes from the file.  Not served: shards on RPC workers."""
+    index_cls = RefineFlatIndex
+    index_ext = "refine"
+    serves_rpc_shards = False
+    BASE_SEARCHERS = {"pq": PQFaissSearch, "sq": SQFaissSearch, "pca": PCAFaissSearch}
+
+    def __init__(self, model, refine_base: Optional[str] = None, k_factor: float = 1.0, refine_type: str = "flat", batch_size: int = 128,
+                 corpus_chunk_size: Optional[int] = None, **kwargs):
+        if refine_base not in self.BASE_SEARCHERS:
+            raise ValueError(f"RefineFaissSearch: refine_base={refine_base!r} must be one of {sorted(self.BASE_SEARCHERS)}")
+        if refine_type not in ("flat", "fp16"):
+            raise ValueError(f"RefineFaissSearch: refine_type={refine_type!r} must be 'flat' or 'fp16'")
+        self.k_factor = check_k_factor(k_factor)
+        # held only to build and train base shards (_new_index / _train); it never indexes or searches itself
+        self.base_search = self.BASE_SEARCHERS[refine_base](model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, **kwargs)
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.refine_base, self.refine_type = refine_base, refine_type
+
+    def _new_index(self, dim: int, capacity: int) -> RefineFlatIndex:
+        base = self.base_search._new_index(dim, capacity)
+        if self.refine_type == "fp16":
+            store = SQFp16Index(dim, capacity=capacity)
+        else:
+            store = FlatIPIndex(dim, capacity=capacity)
+            store.shadow_f16 = False                  # gathered, never streamed: 4 B/element instead of 6
+        return RefineFlatIndex(base, store, k_factor=self.k_factor)
+
+    def _train(self, idx: RefineFlatIndex, corpus_emb):
+        self.base_search._train(idx.base_index, corpus_emb)
+
+    def _retrieve_device(self, query_emb, top_k: int):
+        check_k_base(top_k, self.k_factor, "RefineFaissSearch")
+        return super()._retrieve_device(query_emb, top_k)
+
+    def search(self, corpus, queries, top_k: int = 1000, score_function: str = None, **kwargs) -> dict:
+        check_k_base(top_k, self.k_factor, "RefineFaissSearch")
+        return super().search(corpus, queries, top_k=top_k, score_function=score_function, **kwargs)
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        idx = self.faiss_index.index
+        self.k_factor = idx.k_factor
+        self.refine_type = "fp16" if isinstance(idx.refine_index, SQFp16Index) else "flat"
+        if isinstance(idx.base_index, PreTransformIndex) and isinstance(self.base_search, PCAFaissSearch):
+            self.base_search.pca_matrix = idx.base_index.transform
+
+    def get_index_name(self):
+        return "refine_faiss_index"
+
+
 class ImpactSearch:
     """The sparse engine HybridSearch calls, with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
     `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`), over an HBM-resident ImpactIndex instead of Lucene behind a JVM: impact
@@ -637,23 +696,22 @@ class HybridSearch:
         self.corpus_chunk_size = batch_size * 800 if corpus_chunk_size is None else corpus_chunk_size
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
-        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank) and
-        # "pca" (IndexPreTransform(PCAMatrix, base)) are served; anything else is served flat
+        # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank),
+        # "pca" (IndexPreTransform(PCAMatrix, base)) and "refine" (IndexRefineFlat over a pq / sq / pca base) are served; anything else is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
-        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca"):
+        den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch,
+                   "refine": RefineFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
-        den_kwargs = {}
-        if faiss_search_map == "pq":                  # (the reference passes its **kwargs through to the searcher)
-            den_kwargs = {a: kwargs[a] for a in ("num_of_centroids", "code_size", "use_rotation", "similarity_metric") if a in kwargs}
-        if faiss_search_map == "sq":
-            den_kwargs = {a: kwargs[a] for a in ("quantizer_type", "similarity_metric") if a in kwargs}
-        if faiss_search_map == "binary":
-            den_kwargs = {a: kwargs[a] for a in ("binary_k", "threshold") if a in kwargs}
-        if faiss_search_map == "pca":
-            if kwargs.get("output_dimension") is None:
-                raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
-            den_kwargs = {a: kwargs[a] for a in ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation") if a in kwargs}
+        # (the reference passes its **kwargs through to the searcher)
+        passed = {"pq": ("num_of_centroids", "code_size", "use_rotation", "similarity_metric"), "sq": ("quantizer_type", "similarity_metric"),
+                  "binary": ("binary_k", "threshold"), "pca": ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation")}
+        den_kwargs = {a: kwargs[a] for a in passed.get(faiss_search_map, ()) if a in kwargs}
+        if faiss_search_map == "pca" and kwargs.get("output_dimension") is None:
+            raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
+        if faiss_search_map == "refine":              # its own arguments and those of the base searcher it names
+            names = ("refine_base", "k_factor", "refine_type") + passed.get(kwargs.get("refine_base"), ())
+            den_kwargs = {a: kwargs[a] for a in names if a in kwargs}
         self.dense_search = den_cls(model, batch_size=batch_size, corpus_chunk_size=corpus_chunk_size, use_multiple_gpu=use_multiple_gpu, **den_kwargs)
         self.dense_search.encode_kwargs = dict(self._encode_kwargs)
         self.return_all_results = return_all_results

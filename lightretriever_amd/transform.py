@@ -290,21 +290,23 @@ class PreTransformIndex:
         return self.transform.reverse_transform(rows)
 
     # -- persistence (faiss.write_index / read_index of an IndexPreTransform, see index_io.py) ------------------------
-    def save(self, fname: str):
+    def save(self, fname: str, prefix: bytes = b"", append: bool = False):
+        """prefix / append, load's offset / end: the record inside an enclosing one (RefineFlatIndex.save)."""
         from .index_io import write_pre_transform
-        write_pre_transform(fname, self.transform.state(), self.ntotal, self.is_trained, lambda f, prefix: self.index.save(f, prefix=prefix))
+        write_pre_transform(fname, self.transform.state(), self.ntotal, self.is_trained,
+                            lambda f, pre: self.index.save(f, prefix=pre, append=append), prefix=prefix)
 
     @classmethod
-    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "PreTransformIndex":
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, offset: int = 0, end: Optional[int] = None) -> "PreTransformIndex":
         from .index_io import FOURCC_FLAT_IP, FOURCC_PQ, QT_FP16, read_pre_transform
-        st, base = read_pre_transform(fname)
+        st, base = read_pre_transform(fname, offset, end)
         if base["fourcc"] == FOURCC_FLAT_IP:
             base_cls = FlatIPIndex
         elif base["fourcc"] == FOURCC_PQ:
             base_cls = PQIndex
         else:
             base_cls = SQFp16Index if base["qtype"] == QT_FP16 else SQ8Index
-        index = base_cls.load(fname, device=device, id_base=id_base, offset=base["offset"])
+        index = base_cls.load(fname, device=device, id_base=id_base, offset=base["offset"], end=end)
         if index.ntotal != base["ntotal"]:
             raise ValueError(f"{fname}: the pre-transform header says {base['ntotal']} rows, its base index holds {index.ntotal}")
         return cls(PCAMatrix.from_state(st, device=index.device), index)
