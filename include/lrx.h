@@ -210,7 +210,8 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
 /* Number of out-of-range token ids any embedding gather (stand-alone or inside lrx_encode_*) has met since the last reset, plus the
  * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
- * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped; -1 if the read
+ * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search counts (probe entries >= nlist,
+ * queries over max_scan_rows, stored rows outside the shard); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -756,6 +757,38 @@ int lrx_flat_ip_rerank(const float* X, int64_t n_rows, int64_t ldx, int32_t dim,
 int lrx_sq_fp16_ip_rerank(const void* codes, int64_t n_rows, int32_t dim, const float* q, int32_t n_queries, const int64_t* cand_rows,
                           int32_t n_cand, int64_t ld_cand, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* (added in ABI 8, additively) INVERTED FILE: the exact top k over the rows of the cells a query probes -- the scan of faiss IndexIVFFlat
+ * with METRIC_INNER_PRODUCT (IVFFlatIndex).  The caller owns the coarse quantiser: it passes the probe lists.
+ *   rows        X[pos * ldx + c], fp32, stored CELL BY CELL: cell c holds positions [list_off[c], list_off[c + 1]) (int64 [nlist + 1], device,
+ *               ascending, list_off[nlist] <= n_rows).  row_ids[pos] (int64 [n_rows], device) is the ORIGINAL row of a position; NULL: the
+ *               position itself.  A position whose original row is outside [0, n_rows) is dropped and counted in lrx_device_error_count.
+ *   probes      probes[i * ld_probe + j], j < nprobe: the cells of query i (what a coarse search with id_base = 0 returns).  An entry < 0 (the
+ *               coarse search's padding) is skipped.  An entry >= nlist is NEVER dereferenced: it is skipped and counted once in
+ *               lrx_device_error_count.  A cell named twice by one query is scanned once for it.
+ *   max_scan_rows   the caller's bound on the rows any one query scans (IVFFlatIndex: the sum of its nprobe largest cells); it sizes the
+ *               workspace.  A query whose cells hold more writes nothing, is counted once in lrx_device_error_count and returns padding.
+ *   score       the flat index's: (float) of the fp64 sum of the fp32 products, by the device function of lrx_flat_ip_rerank's family
+ *               (exact_dot_lds_row): bit for bit what lrx_flat_ip_search_bounded / lrx_flat_ip_rerank report for that (query, row).  No filter
+ *               pass, no error band: every scanned row is scored exactly, once per query that probes its cell.
+ *   order       score descending, ties to the lower ORIGINAL row; (-FLT_MAX, -1) where the probed cells hold fewer than k rows.  out_ids =
+ *               id_base + row, or row_map[row] when row_map != NULL (int64 [>= n_rows], device).  out_scores / out_ids: [n_queries, k].
+ *   a query's result depends on its own rows of q and probes alone: not on n_queries, its position in the call or the chunking below.
+ *   limits      dim % 32 == 0, 32 <= dim <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); ld_probe >= nprobe; 1 <= k <= 2048;
+ *               0 <= n_rows < 2^32; 0 <= max_scan_rows < 2^31; ldx >= dim, ldx % 4 == 0, X and q 16-byte aligned ([n_queries, dim] contiguous).
+ *               n_queries == 0 launches nothing.  Anything else is LRX_ERR_INVALID before any device work; a workspace under
+ *               lrx_ivf_flat_ip_workspace_bytes: LRX_ERR_WORKSPACE.
+ * Per chunk of queries (min(n_queries, 1024, 768 MiB / (8 max_scan_rows)): the workspace stays under 1 GiB and stops growing there) six
+ * launches on `stream` (kernels only: no memset or copy node), no host synchronisation, capturable in a HIP graph: the counters' clear, the
+ * probe plan (one workgroup per query), a counting sort of the (query, cell) pairs by cell that also lays out the work items (a probed cell =
+ * groups of up to 64 KiB of consecutive stored rows), the CELL-MAJOR persistent scan -- a workgroup stages a group in LDS once and scores it
+ * against every query that probes its cell, query rows streamed from L2; cells nobody probes cost nothing -- and one workgroup per query that
+ * selects and sorts the top k of the query's packed (score, row) words. */
+size_t lrx_ivf_flat_ip_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int32_t k, int64_t max_scan_rows);
+int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                           const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
+                           int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

@@ -1,1 +1,1 @@
-from lightretriever_amd.retriever import BinaryFaissSearch, DenseRetrievalFaissSearch, FlatIPFaissSearch, PCAFaissSearch, PQFaissSearch, RefineFaissSearch, SQFaissSearch  # noqa: F401
+from lightretriever_amd.retriever import BinaryFaissSearch, DenseRetrievalFaissSearch, FlatIPFaissSearch, IVFFaissSearch, PCAFaissSearch, PQFaissSearch, RefineFaissSearch, SQFaissSearch  # noqa: F401

@@ -5,3 +5,4 @@ from .impact_index import ImpactIndex  # noqa: F401
 from .sparse_rows import SparseRows  # noqa: F401
 from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
 from .refine import RefineFlatIndex  # noqa: F401
+from .ivf import IVFFlatIndex  # noqa: F401

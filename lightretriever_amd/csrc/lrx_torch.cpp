@@ -338,6 +338,40 @@ std::tuple<at::Tensor, at::Tensor> sq_fp16_ip_rerank(const at::Tensor& q, const 
   return {o.d, o.i};
 }
 
+// Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell, list_off int64 [nlist + 1], row_ids int64 [n_rows] (the
+// original row of a position) or None, probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted),
+// max_scan_rows = the caller's bound on the rows one query scans.  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, int64_t k, int64_t max_scan_rows,
+                                                    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(x, "x", at::kFloat, 2);
+  need(list_off, "list_off", at::kLong, 1);
+  need(probes, "probes", at::kLong, 2);
+  const int64_t n_rows = x.size(0), dim = x.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
+  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
+                  (probes.size(1) == 0 || probes.stride(1) == 1) && (n_rows <= 1 || x.stride(1) == 1),
+              "ivf_flat_ip_topk: q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_flat_ip_topk: sizes out of range");
+  const int64_t* ri = nullptr;
+  if (row_ids.has_value() && row_ids->defined()) {
+    need(*row_ids, "row_ids", at::kLong, 1);
+    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, "ivf_flat_ip_topk: row_ids int64 [>= n_rows] contiguous");
+    ri = row_ids->data_ptr<int64_t>();
+  }
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_flat_ip_topk: row_map int64 [>= n_rows] contiguous");
+  const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  TopK o = topk_out(q, k);
+  lrx_check(lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(), ri,
+                                   (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), (int32_t)nprobe,
+                                   probes.size(0) > 1 ? probes.stride(0) : nprobe, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                   o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
+            "ivf_flat_ip_topk");
+  return {o.d, o.i};
+}
+
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
 // centroids [M, 256, D / M] fp32.  Returns (D, I).
 std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
@@ -615,6 +649,8 @@ TORCH_LIBRARY(lrx, m) {
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
   m.def("flat_ip_rerank(Tensor q, Tensor x, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq_fp16_ip_rerank(Tensor q, Tensor codes, int n_rows, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_flat_ip_topk(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, int k, int max_scan_rows, int id_base=0, "
+        "Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
@@ -645,6 +681,7 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("flat_ip_rerank", &flat_ip_rerank);
   m.impl("sq_fp16_ip_rerank", &sq_fp16_ip_rerank);
+  m.impl("ivf_flat_ip_topk", &ivf_flat_ip_topk);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);

@@ -94,7 +94,23 @@ IndexRefine, same source:
 It too is **unverified against a Faiss build**.  Here a record is followed by more: every reader takes, next to `offset`, an optional `end`
 (default: the end of the file) that its record must fill exactly, index_record_end finds where a record stops, and every writer can continue
 a file (`append=True`).  Truncated files, a base or refine index whose d / ntotal disagree with the header and other record types are
-rejected."""
+rejected.
+
+An inverted-file flat index (IVFFlatIndex, faiss IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT)) is written as Faiss's
+serialisation of IndexIVFFlat (write_ivf_header, write_direct_map, write_InvertedLists of an ArrayInvertedLists), same source:
+
+    u32   fourcc 'IwFl'
+          the index header of 'IxFI' above (d, ntotal, two dummies, is_trained, metric_type = 0)
+    u64   nlist,  u64 nprobe
+          the quantiser: a complete 'IxFI' record over the nlist centroids (0 rows when untrained)
+    u8    direct-map type = 0 (NoMap),  u64 0                  (an empty i64 vector)
+    u32   fourcc 'ilar',  u64 nlist,  u64 code_size = 4 d
+    u32   'full', u64 nlist, u64 sizes[nlist]       when more than nlist / 2 cells are non-empty (faiss: n_non0 > nlist / 2, integer division)
+    u32   'sprs', u64 2 m, u64 (cell, size)[m]      otherwise: the m non-empty cells in ascending order
+          then for every non-empty cell, in ascending order: f32 rows[size][d], i64 ids[size]
+
+Real faiss bytes cannot be produced here (faiss is not installed): like the others the layout is **unverified against a Faiss build**.  The
+reader accepts both list-size forms and refuses any other by name."""
 from __future__ import annotations
 
 import csv
@@ -517,6 +533,104 @@ def read_refine(fname: str):
         f.seek(body_end)
         (k_factor,) = struct.unpack("<f", f.read(4))
     return dict(d=d, ntotal=ntotal, is_trained=is_trained, k_factor=k_factor, base=parts[0], store=parts[1])
+
+
+FOURCC_IVF_FLAT = b"IwFl"
+_ILAR, _FULL, _SPRS = b"ilar", b"full", b"sprs"
+
+
+def write_ivf_flat(fname: str, centroids: np.ndarray, list_sizes, rows, row_ids, nprobe: int = 1, is_trained: bool = True) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; rows: the fp32 rows in CELL ORDER, anything whose slice
+    rows[a:b] np.asarray turns into [b - a, d] (read one cell at a time: the index comes off the GPU in pieces); row_ids int64 [ntotal], the
+    original row (faiss's id) of each stored position.  Written as faiss's 'IwFl' record (the layout at the head of this file; faiss is not
+    installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname."""
+    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+    nlist, ntotal = sizes.shape[0], int(sizes.sum())
+    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
+    cent = np.ascontiguousarray(centroids, dtype="<f4")
+    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
+        raise ValueError(f"write_ivf_flat: centroids {cent.shape} do not match nlist={nlist}")
+    d = cent.shape[1]
+    if ids.shape[0] != ntotal or (sizes < 0).any():
+        raise ValueError(f"write_ivf_flat: {ids.shape[0]} row ids, the list sizes sum to {ntotal}")
+    head = _index_header(FOURCC_IVF_FLAT, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
+    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
+    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
+    head += _ILAR + struct.pack("<QQ", nlist, 4 * d)
+    non0 = np.flatnonzero(sizes)
+    if len(non0) > nlist // 2:
+        head += _FULL + struct.pack("<Q", nlist) + sizes.astype("<u8").tobytes()
+    else:
+        head += _SPRS + struct.pack("<Q", 2 * len(non0)) + np.stack([non0, sizes[non0]], axis=1).astype("<u8").tobytes()
+    tmp = fname + ".tmp"
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    with open(tmp, "wb") as f:
+        f.write(head)
+        for c in non0:
+            a, b = int(off[c]), int(off[c + 1])
+            block = np.ascontiguousarray(np.asarray(rows[a:b]), dtype="<f4")
+            if block.shape != (b - a, d):
+                raise ValueError(f"write_ivf_flat: rows[{a}:{b}] has shape {block.shape}, expected {(b - a, d)}")
+            f.write(block.tobytes())
+            f.write(ids[a:b].tobytes())
+    os.replace(tmp, fname)
+
+
+def read_ivf_flat(fname: str):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, centroids fp32 [nlist, d] ([0, d] when untrained), list_off int64 [nlist + 1], rows fp32
+    [ntotal, d] in cell order, row_ids int64 [ntotal]).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
+    size = os.path.getsize(fname)
+    with open(fname, "rb") as f:
+        def take(n: int, what: str) -> bytes:
+            b = f.read(n)
+            if len(b) != n:
+                raise ValueError(f"{fname}: truncated inverted-file index ({what})")
+            return b
+        if size < 2 * _HEADER.size + 16:
+            raise ValueError(f"{fname}: too short for an inverted-file index header")
+        d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_FLAT, "an inverted-file flat index")
+        nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
+        if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
+            raise ValueError(f"{fname}: inconsistent inverted-file index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
+        qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file index")
+        (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
+        if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
+            raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
+        centroids = np.frombuffer(take(4 * n_floats, "centroids"), dtype="<f4").reshape(qn, d)
+        dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
+        if dm_type != 0 or dm_n != 0:
+            raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
+        il = take(4, "inverted lists")
+        if il != _ILAR:
+            raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
+        il_nlist, code_size = struct.unpack("<QQ", take(16, "inverted lists header"))
+        if il_nlist != nlist or code_size != 4 * d:
+            raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={code_size} do not match nlist={nlist}, d={d}")
+        form = take(4, "list sizes")
+        (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
+        sizes = np.zeros(nlist, dtype=np.int64)
+        if form == _FULL:
+            if n_words != nlist:
+                raise ValueError(f"{fname}: {n_words} list sizes for nlist={nlist}")
+            sizes[:] = np.frombuffer(take(8 * nlist, "list sizes"), dtype="<u8")
+        elif form == _SPRS:
+            pairs = np.frombuffer(take(8 * n_words, "list sizes"), dtype="<u8").reshape(-1, 2).astype(np.int64) if n_words % 2 == 0 else None
+            if pairs is None or (pairs[:, 0] >= nlist).any() or len(np.unique(pairs[:, 0])) != len(pairs):
+                raise ValueError(f"{fname}: inconsistent sparse list sizes")
+            sizes[pairs[:, 0]] = pairs[:, 1]
+        else:
+            raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
+        if int(sizes.sum()) != ntotal or f.tell() + ntotal * (4 * d + 8) != size:
+            raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal} (file bytes={size})")
+        rows = np.empty((ntotal, d), dtype=np.float32)
+        row_ids = np.empty(ntotal, dtype=np.int64)
+        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        for c in np.flatnonzero(sizes):
+            a, b = int(list_off[c]), int(list_off[c + 1])
+            rows[a:b] = np.frombuffer(take((b - a) * 4 * d, "rows"), dtype="<f4").reshape(b - a, d)
+            row_ids[a:b] = np.frombuffer(take((b - a) * 8, "ids"), dtype="<i8")
+    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), centroids=centroids, list_off=list_off, rows=rows,
+                row_ids=row_ids)
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

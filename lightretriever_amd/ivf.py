@@ -1,0 +1,289 @@
+"""Inverted-file flat index: the faiss IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) surface over lrx_ivf_flat_ip_search
+(csrc/lrx_search_ivf.h).
+
+    idx = IVFFlatIndex(2048, nlist=1024, nprobe=32); idx.train(x); idx.add(x)
+    D, I = idx.search(q, 100)            # the exact top 100 over the rows of each query's 32 best cells
+
+k-means cells, the fp32 rows stored once, cell by cell, and only the `nprobe` best cells of a query scanned: at nprobe / nlist = 1/32 a single
+query reads about 1/32 of the rows.  No fp16 shadow is kept.  Every scanned (query, row) pair is scored exactly -- the flat index's own bits --
+so with nprobe == nlist the result IS FlatIPIndex.search's."""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .index import FlatIPIndex, _as_rows, _check_range, _grown, _pq_update
+from .transform import linear_transform
+
+MAX_NPROBE = 2048
+MAX_K = 2048
+
+_CAPTURE_WS_ERROR = ("IVFFlatIndex.search under graph capture: the search workspaces must exist before the capture starts -- run one eager "
+                     "search with the same number of queries, k and nprobe first")
+
+
+def check_ivf_args(d: int, nlist: int, nprobe: int):
+    if d % 32 != 0 or not 32 <= d <= 8192:
+        raise ValueError(f"IVFFlatIndex: d={d} must be a multiple of 32 (32 .. 8192)")
+    if nlist < 1:
+        raise ValueError(f"IVFFlatIndex: nlist={nlist} must be >= 1")
+    check_nprobe(nprobe, nlist)
+
+
+def check_nprobe(nprobe: int, nlist: int) -> int:
+    if not 1 <= nprobe <= min(nlist, MAX_NPROBE):
+        raise ValueError(f"IVFFlatIndex: nprobe={nprobe} out of range (1..min(nlist={nlist}, {MAX_NPROBE}))")
+    return int(nprobe)
+
+
+class IVFFlatIndex:
+    """faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT): d, nlist, nprobe, ntotal, is_trained, id_base; train / add / search /
+    reset / reconstruct_n / save / load / set_contents, and append_slot / commit as the other trainable shards have.
+    d % 32 == 0, 32 <= d <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
+
+    Training: Lloyd k-means on the L2 objective (what faiss's Clustering minimises for a non-spherical IP index) with PQIndex's rules --
+    np.random.default_rng(1234), at most 256 x nlist rows (sampled without replacement, row numbers sorted), initial centroids = nlist distinct
+    sampled rows, NITER = 10, deterministic fp64 segmented sums, faiss's split of empty cells; niter=0 leaves the initial centroids.  The
+    assignment is argmax_j (x . c_j - |c_j|^2 / 2), ties to the lower j: lrx_linear_transform (A = centroids, b = -|c|^2 / 2) over row chunks and
+    an arg-max.  The same input and seed give the same centroid bits; they are not faiss's (its RNG differs).
+    Coarse quantiser: a FlatIPIndex over the centroids (`quantizer`).  A row's cell at add() and a query's probe list at search() are its exact
+    top-1 / top-nprobe by INNER PRODUCT, ties to the lower cell.
+    Rows: fp32, held once, in cell order; inside a cell in ascending original row (faiss's insertion order).  `list_off` int64 [nlist + 1] and
+    `row_ids` int64 [ntotal] (position -> original row) sit beside them, `list_sizes` (numpy) is the host copy of the cell sizes, so a search
+    sizes its workspace without a device sync.  add() appends the rows as they come (one coarse search, one host read of the new cell sizes);
+    the cell order is rebuilt lazily, at the first search after an add: a stable sort of the cell numbers and a gather of the rows in chunks
+    of `rebuild_chunk_rows` into a second buffer -- two copies of the rows while it runs, never a third.
+    Memory: 4 B/element + 16 B per row (row_ids, the row's cell) + the centroids (6 B/element: the quantiser keeps its shadow) + the search
+    workspace (8 bytes per scanned row and query of a chunk, under 1 GiB).  NOT thread-safe."""
+
+    NITER = 10
+    MAX_POINTS_PER_CENTROID = 256
+    SEED = 1234
+    ASSIGN_CHUNK_BYTES = 256 << 20      # score matrix [rows, nlist] of one assignment chunk
+
+    def __init__(self, d: int, nlist: int, nprobe: int = 1, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        check_ivf_args(d, nlist, nprobe)
+        _lib.require_gpu()
+        self.lib = _lib.lib()
+        self.d, self.nlist, self.nprobe = int(d), int(nlist), int(nprobe)
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        self.id_base = id_base
+        self.ntotal = 0
+        self.is_trained = False
+        self.rebuild_chunk_rows = 262144
+        self.quantizer = FlatIPIndex(d, capacity=nlist, device=self.device)
+        self._x = torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device)
+        self._assign = torch.empty(max(capacity, 0), dtype=torch.int64, device=self.device)   # cell of ORIGINAL row r
+        self._clear_rows()
+        self._stage = None
+        self._ws = None
+
+    def _clear_rows(self):
+        self.ntotal = 0
+        self._nsorted = 0                 # positions [0, _nsorted) are in cell order; [_nsorted, ntotal) hold original rows _nsorted .. as added
+        self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        self.row_ids = torch.empty(0, dtype=torch.int64, device=self.device)
+        self.list_sizes = np.zeros(self.nlist, dtype=np.int64)
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        return self.quantizer.vectors
+
+    # -- training ------------------------------------------------------------------------------------------------
+    def _rows(self, x, where: str = "") -> torch.Tensor:
+        x = _as_rows(x, self.d, where).to(device=self.device, dtype=torch.float32)
+        return x if x.shape[0] == 0 or (x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) % 4 == 0)) else x.contiguous()
+
+    def _assign_l2(self, x: torch.Tensor, cent: torch.Tensor) -> torch.Tensor:
+        """argmax_j (x . c_j - |c_j|^2 / 2) per row (the nearest centroid in L2), ties to the lower j -> int64 [n]."""
+        b = (-(cent.double() ** 2).sum(dim=1) / 2).float().contiguous()
+        chunk = max(1, self.ASSIGN_CHUNK_BYTES // (4 * self.nlist))
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=self.device)
+        for s in range(0, x.shape[0], chunk):
+            torch.argmax(linear_transform(x[s:s + chunk], cent, b), dim=1, out=out[s:s + chunk])
+        return out
+
+    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
+        """Lloyd k-means (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
+        x = self._rows(x, "train: ")
+        n = x.shape[0]
+        if n < self.nlist:
+            raise ValueError(f"IVFFlatIndex.train: {n} training rows < nlist={self.nlist}")
+        niter = self.NITER if niter is None else niter
+        rng = np.random.default_rng(self.SEED if seed is None else seed)
+        max_pts = self.nlist * self.MAX_POINTS_PER_CENTROID
+        if n > max_pts:
+            x = x[torch.from_numpy(np.sort(rng.permutation(n)[:max_pts])).to(self.device)]
+            n = max_pts
+        cent = x[torch.from_numpy(rng.permutation(n)[:self.nlist]).to(self.device)].contiguous()       # [nlist, d] distinct rows
+        if niter > 0:
+            x_t = x.double()[None]                                                         # [1, n, d]
+            for _ in range(niter):
+                codes = self._assign_l2(x, cent)
+                cent = _pq_update(x_t, codes[None], self.nlist, cent[None], rng)[0].contiguous()
+        self._set_centroids(cent)
+
+    def _set_centroids(self, cent: torch.Tensor):
+        self.quantizer.reset()
+        self.quantizer.add(cent.to(self.device, torch.float32).reshape(self.nlist, self.d))
+        self.is_trained = True
+
+    # -- rows ------------------------------------------------------------------------------------------------------
+    def _reserve(self, n_rows: int):
+        if n_rows > self._x.shape[0]:
+            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+            new[:self.ntotal].copy_(self._x[:self.ntotal])
+            self._x = new
+        if n_rows > self._assign.shape[0]:
+            new = torch.empty(n_rows, dtype=torch.int64, device=self.device)
+            new[:self.ntotal].copy_(self._assign[:self.ntotal])
+            self._assign = new
+
+    def add(self, x):
+        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product (raises before train(), as faiss does)."""
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIndex.add: the index is not trained (call train() first)")
+        x = self._rows(x, "add: ")
+        n = x.shape[0]
+        if n == 0:
+            return
+        if self.ntotal + n > self._x.shape[0]:
+            self._reserve(_grown(self._x.shape[0], self.ntotal + n))
+        a, b = self.ntotal, self.ntotal + n
+        for s in range(0, n, 262144):
+            self._assign[a + s:min(a + s + 262144, b)].copy_(self.quantizer.search(x[s:s + 262144], 1)[1][:, 0])
+        self._x[a:b].copy_(x)
+        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
+        self.ntotal = b
+
+    def _finalize(self):
+        """The rows back into cell order (see the class note): a no-op unless rows were added since the last search."""
+        if self._nsorted == self.ntotal:
+            return
+        n, ns = self.ntotal, self._nsorted
+        # the cell of every stored position: the ordered part by its original row, the new rows as they stand
+        orig = torch.cat([self.row_ids[:ns], torch.arange(ns, n, dtype=torch.int64, device=self.device)])
+        perm = torch.argsort(self._assign[orig], stable=True)          # within a cell: old rows (ascending) before new rows (ascending)
+        new = torch.empty(max(self._x.shape[0], n), self.d, dtype=torch.float32, device=self.device)
+        for s in range(0, n, self.rebuild_chunk_rows):
+            e = min(s + self.rebuild_chunk_rows, n)
+            torch.index_select(self._x, 0, perm[s:e], out=new[s:e])
+        self._x = new
+        self.row_ids = orig[perm]
+        self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+        self.list_off[1:] = torch.from_numpy(np.cumsum(self.list_sizes)).to(self.device)
+        self._nsorted = n
+
+    def append_slot(self, n_rows: int) -> torch.Tensor:
+        """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
+        if self._stage is None or self._stage.shape[0] < n_rows:
+            self._stage = None
+            self._stage = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+        return self._stage[:n_rows]
+
+    def commit(self, n_rows: int):
+        if n_rows > 0:
+            if self._stage is None or n_rows > self._stage.shape[0]:
+                raise ValueError(f"commit({n_rows}): only {0 if self._stage is None else self._stage.shape[0]} staged rows")
+            rows = self._stage[:n_rows]
+            if not self.is_trained:
+                self.train(rows)
+            self.add(rows)
+        self._stage = None                             # staging released (stream-ordered by the allocator)
+
+    def reset(self):
+        """faiss reset(): drops the rows, keeps the training."""
+        self._clear_rows()
+        self._stage = None
+
+    def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
+        """ORIGINAL rows [i0, i0 + n) as an fp32 device tensor [n, d]."""
+        _check_range(i0, n, self.ntotal)
+        self._finalize()
+        if n == 0:
+            return torch.empty(0, self.d, dtype=torch.float32, device=self.device)
+        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
+        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
+        return self._x[pos[i0:i0 + n]]
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
+    def stored_rows(self) -> torch.Tensor:
+        """The rows as stored, cell by cell: fp32 [ntotal, d] (a view)."""
+        self._finalize()
+        return self._x[:self.ntotal]
+
+    def set_contents(self, centroids, rows, list_off, row_ids):
+        """Replace the centroids ([nlist, d]) and the rows: `rows` fp32 [n, d] already in cell order, list_off int64 [nlist + 1] (ascending from
+        0 to n), row_ids int64 [n] a permutation of 0 .. n - 1 (position -> original row): load() and tests."""
+        rows = torch.as_tensor(rows)
+        lo = np.asarray(torch.as_tensor(list_off).cpu().numpy(), dtype=np.int64).reshape(-1)
+        ri = np.asarray(torch.as_tensor(row_ids).cpu().numpy(), dtype=np.int64).reshape(-1)
+        n = rows.shape[0]
+        if rows.ndim != 2 or rows.shape[1] != self.d:
+            raise ValueError(f"set_contents: rows must be [n, {self.d}], got {tuple(rows.shape)}")
+        if lo.shape[0] != self.nlist + 1 or lo[0] != 0 or lo[-1] != n or (np.diff(lo) < 0).any():
+            raise ValueError(f"set_contents: list_off must ascend from 0 to n={n} over nlist + 1 = {self.nlist + 1} entries")
+        if ri.shape[0] != n or not np.array_equal(np.sort(ri), np.arange(n)):
+            raise ValueError(f"set_contents: row_ids must be a permutation of 0 .. {n - 1}")
+        self._set_centroids(torch.as_tensor(centroids))
+        self._clear_rows()
+        self._x = rows.to(self.device, torch.float32).contiguous().clone()
+        self.row_ids = torch.from_numpy(ri).to(self.device)
+        self.list_off = torch.from_numpy(lo).to(self.device)
+        self.list_sizes = np.diff(lo)
+        self._assign = torch.empty(max(n, 0), dtype=torch.int64, device=self.device)
+        self._assign[self.row_ids] = torch.repeat_interleave(torch.arange(self.nlist, device=self.device), torch.from_numpy(self.list_sizes).to(self.device))
+        self.ntotal = self._nsorted = n
+
+    # -- search --------------------------------------------------------------------------------------------------
+    def max_scan_rows(self, nprobe: Optional[int] = None) -> int:
+        """The most rows one query can scan: the sum of the nprobe largest cells (from the host copy of the sizes)."""
+        nprobe = self.nprobe if nprobe is None else nprobe
+        return int(np.sort(self.list_sizes)[::-1][:nprobe].sum())
+
+    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
+        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the exact top k over the rows of each query's nprobe best cells (by inner product with
+        the centroids), score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
+        I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIndex.search: the index is not trained")
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"search: k={k} out of range (1..{MAX_K})")
+        nprobe = check_nprobe(self.nprobe if nprobe is None else nprobe, self.nlist)
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        if q.shape[0] == 0:
+            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
+        if self._nsorted != self.ntotal:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.LrxError("IVFFlatIndex.search under graph capture: rows were added since the last search (run one eager search first)")
+            self._finalize()
+        _, probes = self.quantizer.search(q, nprobe)
+        return ops.ivf_flat_ip_topk(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, k, self.max_scan_rows(nprobe), self.id_base, row_map,
+                                    ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+
+    def range_search(self, q, radius: float):
+        raise NotImplementedError("IVFFlatIndex.range_search is not served (range search over the probed cells is a follow-up)")
+
+    # -- persistence (faiss.write_index / read_index of an IndexIVFFlat, see index_io.py) -------------------------------
+    def save(self, fname: str):
+        from .index_io import write_ivf_flat
+        self._finalize()
+        write_ivf_flat(fname, self.centroids.cpu().numpy(), self.list_sizes, self._x[:self.ntotal].cpu().numpy(), self.row_ids.cpu().numpy(), self.nprobe,
+                       self.is_trained)
+
+    @classmethod
+    def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "IVFFlatIndex":
+        from .index_io import read_ivf_flat
+        st = read_ivf_flat(fname)
+        idx = cls(st["d"], st["nlist"], nprobe=min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE), device=device, id_base=id_base)
+        if st["is_trained"]:
+            idx.set_contents(np.array(st["centroids"], copy=True), st["rows"], st["list_off"], st["row_ids"])
+        return idx

@@ -282,3 +282,30 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
     weights = torch.empty(nnz, dtype=torch.int32, device=reps.device)
     _lib.check(lib.lrx_sparse_csr_fill(_lib.ptr(reps), B, V, ld, q, mark, _lib.ptr(row_off), _lib.ptr(terms), _lib.ptr(weights), _s()))
     return SparseRows(row_off, terms, weights, V)
+
+
+# -- inverted file (IndexIVFFlat) ---------------------------------------------------------------------------------------------
+def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor, k: int,
+                     max_scan_rows: int, id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None,
+                     capture_error: Optional[str] = None):
+    """lrx_ivf_flat_ip_search -> (D f32[Q,k], I i64[Q,k]): the exact top k over the rows of the cells probes[i] names.  q fp32 [Q, d]
+    contiguous; X fp32 [n, d] rows stored cell by cell; list_off int64 [nlist + 1]; row_ids int64 [n] (original row of a position) or None;
+    probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted in lrx_device_error_count); max_scan_rows: the
+    caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
+    from .index import _workspace
+    lib = _lib.lib()
+    Q, nprobe = probes.shape
+    n, d = X.shape
+    nlist = list_off.numel() - 1
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError("ivf_flat_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
+    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
+    if Q == 0:
+        return D, I
+    need = int(lib.lrx_ivf_flat_ip_workspace_bytes(n, nlist, d, Q, nprobe, k, int(max_scan_rows)))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
+    _lib.check(lib.lrx_ivf_flat_ip_search(_lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                          _lib.ptr(q), Q, _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), k,
+                                          int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+    return D, I

@@ -8,6 +8,7 @@
     BinaryFaissSearch   <- retriever/faiss_search.py:296-323             (IndexBinaryFlat, `dot` rerank only)
     PCAFaissSearch      <- retriever/faiss_search.py:512-565             (IndexPreTransform(PCAMatrix, base) over PreTransformIndex)
     RefineFaissSearch   (no counterpart in the reference)                (faiss IndexRefineFlat over a PQ / SQ / PCA base: RefineFlatIndex)
+    IVFFaissSearch      (no counterpart in the reference)                (faiss IndexIVFFlat, inner product: IVFFlatIndex)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
     ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
@@ -33,6 +34,7 @@ import torch
 from .impact_index import ImpactIndex, query_csr
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 from .sparse_rows import SparseRows, identity_term
+from .ivf import IVFFlatIndex
 from .refine import RefineFlatIndex, check_k_factor, check_k_base
 from .transform import BASES as _PCA_BASES, PCAMatrix, PreTransformIndex
 
@@ -535,6 +537,40 @@ class RefineFaissSearch(FlatIPFaissSearch):
         return "refine_faiss_index"
 
 
+class IVFFaissSearch(FlatIPFaissSearch):
+    """faiss IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) as a searcher, served by IVFFlatIndex: every chunk is clustered into
+    nlist k-means cells (at most its row count) and a search scans the rows of each query's nprobe best cells, scored exactly.  index() trains
+    on the chunk and then adds it; _index_in_place trains on the encoded chunk when its staging slot is committed.  index / load / save behave
+    like FlatIPFaissSearch's with that shard; load() takes nlist and nprobe from the file.  Not served: the L2 metric, shards on RPC workers."""
+    index_cls = IVFFlatIndex
+    index_ext = "ivf"
+    serves_rpc_shards = False
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32, similarity_metric=0,
+                 **kwargs):
+        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
+            raise NotImplementedError(f"IVFFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        if nlist < 1 or nprobe < 1:
+            raise ValueError(f"IVFFaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.nlist, self.nprobe = int(nlist), int(nprobe)
+        self.similarity_metric = 0
+
+    def _new_index(self, dim: int, capacity: int) -> IVFFlatIndex:
+        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
+        return IVFFlatIndex(dim, nlist, nprobe=min(self.nprobe, nlist, 2048), capacity=capacity)
+
+    def _train(self, idx: IVFFlatIndex, corpus_emb):
+        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        self.nlist, self.nprobe = self.faiss_index.index.nlist, self.faiss_index.index.nprobe
+
+    def get_index_name(self):
+        return "ivf_faiss_index"
+
+
 class ImpactSearch:
     """The sparse engine HybridSearch calls, with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
     `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`), over an HBM-resident ImpactIndex instead of Lucene behind a JVM: impact
@@ -697,15 +733,17 @@ class HybridSearch:
         self.show_progress_bar = kwargs.get("show_progress_bar", True)
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
         # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank),
-        # "pca" (IndexPreTransform(PCAMatrix, base)) and "refine" (IndexRefineFlat over a pq / sq / pca base) are served; anything else is served flat
+        # "pca" (IndexPreTransform(PCAMatrix, base)), "refine" (IndexRefineFlat over a pq / sq / pca base) and "ivf" (IndexIVFFlat) are served;
+        # anything else ("hnsw", "hnswsq") is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
         den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch,
-                   "refine": RefineFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine"):
+                   "refine": RefineFaissSearch, "ivf": IVFFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine", "ivf"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
         # (the reference passes its **kwargs through to the searcher)
         passed = {"pq": ("num_of_centroids", "code_size", "use_rotation", "similarity_metric"), "sq": ("quantizer_type", "similarity_metric"),
-                  "binary": ("binary_k", "threshold"), "pca": ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation")}
+                  "binary": ("binary_k", "threshold"), "pca": ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation"),
+                  "ivf": ("nlist", "nprobe", "similarity_metric")}
         den_kwargs = {a: kwargs[a] for a in passed.get(faiss_search_map, ()) if a in kwargs}
         if faiss_search_map == "pca" and kwargs.get("output_dimension") is None:
             raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
