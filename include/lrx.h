@@ -210,8 +210,8 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
 /* Number of out-of-range token ids any embedding gather (stand-alone or inside lrx_encode_*) has met since the last reset, plus the
  * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
- * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search counts (probe entries >= nlist,
- * queries over max_scan_rows, stored rows outside the shard); -1 if the read
+ * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search count
+ * (probe entries >= nlist, queries over max_scan_rows, stored rows outside the shard); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -789,6 +789,46 @@ int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t 
                            const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
                            int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* (added in ABI 8, additively) INVERTED FILE over PRODUCT-QUANTISED codes: the top k under the ADC score over the rows of the cells a query
+ * probes -- the scan of faiss IndexIVFPQ(quantizer, d, nlist, M, 8, METRIC_INNER_PRODUCT) (IVFPQIndex).  The caller owns the
+ * coarse quantiser: it passes the probe lists and, with by_residual, the coarse scores of the probed cells.
+ *   codes       the blocked PQ layout of lrx_pq_ip_search (128-row blocks, 16-sub-space groups, Mp = ceil(M / 16) * 16 bytes per row, whole
+ *               blocks for n_rows rows), indexed by STORED POSITION, CELL BY CELL: cell c holds positions [list_off[c], list_off[c + 1]) (int64
+ *               [nlist + 1], device, ascending, list_off[nlist] <= n_rows) -- a cell usually starts in the middle of a block.  row_ids[pos]
+ *               (int64 [n_rows], device) is the ORIGINAL row of a position; NULL: the position itself.  A position whose original row is
+ *               outside [0, n_rows) is dropped and counted in lrx_device_error_count.  lrx_pq_encode and lrx_pq_decode_rows work on this
+ *               buffer unchanged, with row0 = the position.  pq_centroids: [M, 256, dim / M] fp32.
+ *   probes      probes[i * ld_probe + j], j < nprobe: the cells of query i (what a coarse search with id_base = 0 returns).  An entry < 0 is
+ *               skipped.  An entry >= nlist is NEVER dereferenced: it is skipped and counted once in lrx_device_error_count.  A cell named
+ *               twice by one query is scanned once for it, with the base term of its FIRST occurrence.
+ *   score       of (query i, position p in the probed cell probes[i][j]), fp32:
+ *                   acc = by_residual ? probe_scores[i * ld_probe + j] : 0.f;   acc += LUT[i][m][code_m(p)]  for m = 0 .. M - 1, in order,
+ *               one fp32 add each; LUT[i][m][c] = (float) of the fp64 sum in order of q_i's sub-vector m times centroid c of sub-space m
+ *               (lrx_pq_lut).  For the inner product the residual table does not depend on the cell: <q, c + r> = <q, c> + sum_m <q_m,
+ *               cb_m[code_m]>, so there is ONE table per query and the caller passes the cell term (IVFPQIndex: the coarse search's own exact
+ *               scores).  probe_scores (fp32, the layout of probes) may be NULL when by_residual == 0; then a (query, row) score is bit for
+ *               bit lrx_pq_ip_search's.
+ *   max_scan_rows   the caller's bound on the rows any one query scans (IVFPQIndex: the sum of its nprobe largest cells); it sizes the
+ *               workspace.  A query whose cells hold more writes nothing, is counted once in lrx_device_error_count and returns padding.
+ *   order       score descending, ties to the lower ORIGINAL row; (-FLT_MAX, -1) where the probed cells hold fewer than k rows.  out_ids =
+ *               id_base + row, or row_map[row] when row_map != NULL (int64 [>= n_rows], device).  out_scores / out_ids: [n_queries, k].
+ *   a query's result depends on its own rows of q, probes and probe_scores alone: not on n_queries, its position in the call or the chunking.
+ *   limits      dim % M == 0; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); ld_probe >= nprobe; 1 <= k <= 2048; 0 <= n_rows < 2^32;
+ *               0 <= max_scan_rows < 2^31; q [n_queries, dim] contiguous.  n_queries == 0 launches nothing.  Anything else is LRX_ERR_INVALID
+ *               with a message before any device work; a workspace under lrx_ivf_pq_ip_workspace_bytes: LRX_ERR_WORKSPACE.
+ * Per chunk of queries (lrx_ivf_flat_ip_search's chunk) four launches on `stream` (kernels only: no memset or copy node, nothing to clear), no
+ * host synchronisation, capturable in a HIP graph: the chunk's lookup tables into the head of the workspace, the probe plan (one workgroup per
+ * query: a dense, ascending offset per probe slot), the QUERY-MAJOR scan -- grid (tiles, queries): a workgroup keeps its query's table in LDS
+ * (in passes above 128 sub-spaces) and walks 1024-position tiles of the query's segment, the concatenation of its probed cells in probe order;
+ * a lane finds its slot by a binary search over the slot offsets in LDS and reads its codes as 16-byte pieces -- and the selection of
+ * lrx_ivf_flat_ip_search over the packed (score, row) words.  The workspace size never decreases in n_queries or max_scan_rows. */
+size_t lrx_ivf_pq_ip_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t M, int32_t n_queries, int32_t nprobe, int32_t k,
+                                     int64_t max_scan_rows);
+int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                         const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
+                         int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base,
+                         float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

@@ -6,3 +6,4 @@ from .sparse_rows import SparseRows  # noqa: F401
 from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
 from .refine import RefineFlatIndex  # noqa: F401
 from .ivf import IVFFlatIndex  # noqa: F401
+from .ivfpq import IVFPQIndex  # noqa: F401

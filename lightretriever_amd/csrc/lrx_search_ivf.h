@@ -50,6 +50,10 @@ __global__ void k_ivf_clear(unsigned int* __restrict__ ints, int n) {
 
 // Plan of one query (see the head of the file).  pairs: (cell << 32 | slot), slot = query * nprobe + j; seg_off[slot]: where the cell's rows
 // start in the query's segment (cells in probe order); q_tot[query]: words of the segment, -1 = over max_scan_rows.
+// DENSE (the query-major scan of lrx_search_ivfpq.h): seg_off is written for EVERY slot of a query that is not over the bound -- a skipped
+// entry (< 0, >= nlist, a repeat, an empty cell) holds no words, so its offset is its successor's and the offsets ascend -- and nothing
+// else is: no pairs, no per-cell counts (pairs / total / cell_cnt may be NULL).  DENSE = false is the plan of the cell-major scan, unchanged.
+template <bool DENSE>
 __global__ void __launch_bounds__(IVF_PLAN_THREADS)
 k_ivf_plan(const int64_t* __restrict__ probes, int nprobe, int64_t ld_probe, const int64_t* __restrict__ list_off, int nlist, int64_t max_scan,
            unsigned long long* __restrict__ pairs, unsigned int pair_cap, unsigned int* __restrict__ total, unsigned int* __restrict__ cell_cnt,
@@ -113,13 +117,18 @@ k_ivf_plan(const int64_t* __restrict__ probes, int nprobe, int64_t ld_probe, con
     q_tot[qi] = over ? -1 : tot;
     const unsigned int bad = s_bad + (over ? 1u : 0u);
     if (bad) atomicAdd(&g_ivf_bad, bad);
-    s_base = (!over && npairs) ? atomicAdd(total, npairs) : 0u;
+    s_base = (!DENSE && !over && npairs) ? atomicAdd(total, npairs) : 0u;
   }
   __syncthreads();
   if (over) return;
   const unsigned int base = s_base;
   for (int j = j0; j < j1; ++j) {
     const int64_t sz = s_size[j];
+    if (DENSE) {
+      seg_off[(unsigned int)qi * (unsigned int)nprobe + (unsigned int)j] = (unsigned int)run;
+      if (sz > 0) run += sz;
+      continue;
+    }
     if (sz <= 0) continue;
     const unsigned int slot = (unsigned int)qi * (unsigned int)nprobe + (unsigned int)j;
     const unsigned int c = (unsigned int)s_cell[j];
@@ -400,7 +409,7 @@ extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ld
     const float* qc = q + (int64_t)q0 * dim;
     hipLaunchKernelGGL(k_ivf_clear, dim3((unsigned)lrx_cdiv((int64_t)nlist + 1, 256)), dim3(256), 0, s, total, (int)nlist + 1);
     LRX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_ivf_plan, dim3(nq), dim3(IVF_PLAN_THREADS), 0, s, probes + (int64_t)q0 * ld_probe, (int)nprobe, ld_probe, list_off, (int)nlist,
+    hipLaunchKernelGGL(k_ivf_plan<false>, dim3(nq), dim3(IVF_PLAN_THREADS), 0, s, probes + (int64_t)q0 * ld_probe, (int)nprobe, ld_probe, list_off, (int)nlist,
                        max_scan_rows, pairs, (unsigned int)((int64_t)nq * nprobe), total, cell_cnt, seg_off, q_tot);
     LRX_LAUNCH_CHECK();
     if (ngroups > 0) {

@@ -810,18 +810,27 @@ class PQIndex(_CodeIndex):
         return self.blocked_to_rows(blocked, x.shape[0])
 
     # -- training ------------------------------------------------------------------------------------------------
-    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
-        """Lloyd k-means per sub-space (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
+    def sample_rows(self, n: int, seed: Optional[int] = None):
+        """(rng, rows): the first draw of train() over n rows -- the sorted numbers of the at most 256 x 256 rows it trains on (None: all of
+        them) -- and the generator that made it, for a caller that derives the training rows from that draw (IVFPQIndex: their residuals)
+        and hands both to train(sample, rng=rng)."""
+        rng = np.random.default_rng(self.SEED if seed is None else seed)
+        max_pts = self.KSUB * self.MAX_POINTS_PER_CENTROID
+        return rng, (np.sort(rng.permutation(n)[:max_pts]) if n > max_pts else None)
+
+    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None, rng=None):
+        """Lloyd k-means per sub-space (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows).
+        rng: x is already the sample of sample_rows(), whose generator this is."""
         x = self._rows(x)
         n = x.shape[0]
         if n < self.KSUB:
             raise ValueError(f"PQIndex.train: {n} training rows < {self.KSUB} centroids")
         niter = self.NITER if niter is None else niter
-        rng = np.random.default_rng(self.SEED if seed is None else seed)
-        max_pts = self.KSUB * self.MAX_POINTS_PER_CENTROID
-        if n > max_pts:
-            x = x[torch.from_numpy(np.sort(rng.permutation(n)[:max_pts])).to(self.device)]
-            n = max_pts
+        if rng is None:
+            rng, rows = self.sample_rows(n, seed)
+            if rows is not None:
+                x = x[torch.from_numpy(rows).to(self.device)]
+                n = rows.shape[0]
         M, K, ds = self.M, self.KSUB, self.dsub
         xs = x.view(n, M, ds)
         init = np.stack([rng.permutation(n)[:K] for _ in range(M)])                       # [M, K] distinct rows per sub-space

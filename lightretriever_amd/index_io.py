@@ -110,7 +110,22 @@ serialisation of IndexIVFFlat (write_ivf_header, write_direct_map, write_Inverte
           then for every non-empty cell, in ascending order: f32 rows[size][d], i64 ids[size]
 
 Real faiss bytes cannot be produced here (faiss is not installed): like the others the layout is **unverified against a Faiss build**.  The
-reader accepts both list-size forms and refuses any other by name."""
+reader accepts both list-size forms and refuses any other by name.
+
+An inverted-file product-quantised index (IVFPQIndex, faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8, METRIC_INNER_PRODUCT)) is written as
+Faiss's serialisation of IndexIVFPQ (write_ivf_header, then by_residual, code_size, write_ProductQuantizer, write_InvertedLists), same source:
+
+    u32   fourcc 'IwPQ'
+          the IVF header exactly as in 'IwFl' above: index header, u64 nlist, u64 nprobe, the 'IxFI' quantiser, the empty direct map
+    u8    by_residual
+    u64   code_size = M
+    u64   d,  u64 M,  u64 nbits = 8,  u64 n = 256 d,  f32 centroids[M][256][d / M]     (the ProductQuantizer of 'IxPq' above)
+    u32   fourcc 'ilar',  u64 nlist,  u64 code_size = M
+          the list sizes, 'full' or 'sprs', as in 'IwFl'
+          then for every non-empty cell, in ascending order: u8 codes[size][M] (row-major), i64 ids[size]
+
+Like 'IwFl' it is **unverified against a Faiss build** (faiss is not installed here).  The reader accepts both list-size forms and refuses any
+other by name; index_record_end knows the record, so a refine index can hold it as its base."""
 from __future__ import annotations
 
 import csv
@@ -447,7 +462,8 @@ def read_pre_transform(fname: str, offset: int = 0, end: Optional[int] = None):
 
 
 FOURCC_REFINE = b"IxRF"
-_REFINE_BASES = (FOURCC_PQ, FOURCC_SQ, FOURCC_PRE_TRANSFORM)
+FOURCC_IVF_PQ = b"IwPQ"
+_REFINE_BASES = (FOURCC_PQ, FOURCC_SQ, FOURCC_PRE_TRANSFORM, FOURCC_IVF_PQ)
 
 
 def refine_prefix(d: int, ntotal: int, is_trained: bool = True) -> bytes:
@@ -466,15 +482,20 @@ def peek_index_header(fname: str, offset: int = 0, end: Optional[int] = None):
 
 
 def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> int:
-    """Where the 'IxFI', 'IxSQ', 'IxPq' or 'IxPT' record that starts at `offset` stops, from its own size words; ValueError when that is past
+    """Where the 'IxFI', 'IxSQ', 'IxPq', 'IxPT' or 'IwPQ' record that starts at `offset` stops, from its own size words; ValueError when that is past
     `end` (default: the end of the file) or the record is of another type.  The reader of the record's class then validates it against
     [offset, the returned end)."""
     size = _end(fname, end)
     fourcc = peek_index_header(fname, offset, end)[0]
     if fourcc == FOURCC_PRE_TRANSFORM:
         return index_record_end(fname, read_pre_transform(fname, offset, end)[1]["offset"], end)
+    if fourcc == FOURCC_IVF_PQ:
+        with open(fname, "rb") as f:
+            f.seek(offset)
+            st = _read_ivf_pq_head(f, fname, size - offset)
+        return offset + st["data"] + st["ntotal"] * (st["M"] + 8)
     if fourcc not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
-        raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT')")
+        raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ')")
     with open(fname, "rb") as f:
         pos = offset + _HEADER.size + {FOURCC_FLAT_IP: 0, FOURCC_SQ: _SQ.size, FOURCC_PQ: _PQ.size}[fourcc]
         # the vectors that follow: (bytes per element, ...) -- each a u64 count and its elements
@@ -503,7 +524,7 @@ def write_refine(fname: str, d: int, ntotal: int, is_trained: bool, k_factor: fl
 
 def read_refine(fname: str):
     """-> dict(d, ntotal, is_trained, k_factor, base, store); base / store = dict(offset, end, fourcc, qtype): where each record lies, its
-    fourcc (base: 'IxPq', 'IxSQ' or 'IxPT'; store: 'IxFI', or 'IxSQ' with qtype QT_fp16) and the ScalarQuantizer type of an 'IxSQ' record
+    fourcc (base: 'IxPq', 'IxSQ', 'IxPT' or 'IwPQ'; store: 'IxFI', or 'IxSQ' with qtype QT_fp16) and the ScalarQuantizer type of an 'IxSQ' record
     (else None).  The caller reads each with the reader of its class at (offset, end)."""
     size = os.path.getsize(fname)
     if size < _HEADER.size + 4:
@@ -631,6 +652,134 @@ def read_ivf_flat(fname: str):
             row_ids[a:b] = np.frombuffer(take((b - a) * 8, "ids"), dtype="<i8")
     return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), centroids=centroids, list_off=list_off, rows=rows,
                 row_ids=row_ids)
+
+
+def _list_sizes_bytes(sizes: np.ndarray) -> bytes:
+    """The list sizes of an 'ilar' record: 'full' when more than nlist / 2 cells are non-empty (faiss's rule), 'sprs' otherwise."""
+    nlist = sizes.shape[0]
+    non0 = np.flatnonzero(sizes)
+    if len(non0) > nlist // 2:
+        return _FULL + struct.pack("<Q", nlist) + sizes.astype("<u8").tobytes()
+    return _SPRS + struct.pack("<Q", 2 * len(non0)) + np.stack([non0, sizes[non0]], axis=1).astype("<u8").tobytes()
+
+
+def write_ivf_pq(fname: str, centroids: np.ndarray, pq_centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True,
+                 is_trained: bool = True, prefix: bytes = b"", append: bool = False) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); pq_centroids fp32 [M, 256, d / M]; list_sizes [nlist]; codes uint8 [ntotal, M]
+    row-major in CELL ORDER; row_ids int64 [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwPQ' record
+    (the layout at the head of this file; faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as
+    fname.tmp and renamed over fname; `prefix` / `append` as in _write_index (the enclosing record of write_refine)."""
+    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+    nlist, ntotal = sizes.shape[0], int(sizes.sum())
+    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
+    cent = np.ascontiguousarray(centroids, dtype="<f4")
+    pqc = np.ascontiguousarray(pq_centroids, dtype="<f4")
+    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
+        raise ValueError(f"write_ivf_pq: centroids {cent.shape} do not match nlist={nlist}")
+    d = cent.shape[1]
+    if pqc.ndim != 3 or pqc.shape[1] != 256 or pqc.shape[0] * pqc.shape[2] != d:
+        raise ValueError(f"write_ivf_pq: codebooks {pqc.shape} are not [M, 256, d / M] for d={d}")
+    M = pqc.shape[0]
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, M):
+        raise ValueError(f"write_ivf_pq: {ids.shape[0]} row ids and codes {codes.shape}, the list sizes sum to {ntotal} (M={M})")
+    head = _index_header(FOURCC_IVF_PQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
+    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
+    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
+    head += struct.pack("<BQ", int(bool(by_residual)), M)              # by_residual, code_size
+    head += _PQ.pack(d, M, 8) + struct.pack("<Q", pqc.size) + pqc.tobytes()
+    head += _ILAR + struct.pack("<QQ", nlist, M) + _list_sizes_bytes(sizes)
+    tmp = fname if append else fname + ".tmp"
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    with open(tmp, "ab" if append else "wb") as f:
+        f.write(prefix)
+        f.write(head)
+        for c in np.flatnonzero(sizes):
+            a, b = int(off[c]), int(off[c + 1])
+            f.write(codes[a:b].tobytes())
+            f.write(ids[a:b].tobytes())
+    if not append:
+        os.replace(tmp, fname)
+
+
+def _read_ivf_pq_head(f, fname: str, size: int):
+    """An 'IwPQ' record from the file position up to its list sizes (`size`: the bytes the record may fill) -> dict(d, nlist, nprobe, ntotal,
+    is_trained, by_residual, M, centroids, pq_centroids, sizes, data: the record's bytes before the first cell's codes)."""
+    start = f.tell()
+
+    def take(n: int, what: str) -> bytes:
+        b = f.read(n) if f.tell() - start + n <= size else b""
+        if len(b) != n:
+            raise ValueError(f"{fname}: truncated inverted-file PQ index ({what})")
+        return b
+    if size < 2 * _HEADER.size + 16:
+        raise ValueError(f"{fname}: too short for an inverted-file PQ index header")
+    d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_PQ, "an inverted-file product-quantiser index")
+    nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
+    if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
+        raise ValueError(f"{fname}: inconsistent inverted-file PQ index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
+    qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file PQ index")
+    (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
+    if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
+        raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
+    centroids = np.frombuffer(take(4 * n_floats, "centroids"), dtype="<f4").reshape(qn, d)
+    dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
+    if dm_type != 0 or dm_n != 0:
+        raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
+    by_residual, code_size = struct.unpack("<BQ", take(9, "by_residual, code_size"))
+    pq_d, M, nbits = _PQ.unpack(take(_PQ.size, "product quantiser"))
+    if nbits != 8:
+        raise ValueError(f"{fname}: ProductQuantizer nbits={nbits} is not served (only 8)")
+    (n_c,) = struct.unpack("<Q", take(8, "codebook size"))
+    if pq_d != d or M <= 0 or d % M or code_size != M or n_c != d * 256 or by_residual not in (0, 1):
+        raise ValueError(f"{fname}: inconsistent IndexIVFPQ quantiser (pq.d={pq_d}, M={M}, code_size={code_size}, floats={n_c}, by_residual={by_residual}; d={d})")
+    pq_centroids = np.frombuffer(take(4 * n_c, "codebooks"), dtype="<f4").reshape(M, 256, d // M)
+    il = take(4, "inverted lists")
+    if il != _ILAR:
+        raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
+    il_nlist, il_code = struct.unpack("<QQ", take(16, "inverted lists header"))
+    if il_nlist != nlist or il_code != M:
+        raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, M={M}")
+    form = take(4, "list sizes")
+    (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == _FULL:
+        if n_words != nlist:
+            raise ValueError(f"{fname}: {n_words} list sizes for nlist={nlist}")
+        sizes[:] = np.frombuffer(take(8 * nlist, "list sizes"), dtype="<u8")
+    elif form == _SPRS:
+        pairs = np.frombuffer(take(8 * n_words, "list sizes"), dtype="<u8").reshape(-1, 2).astype(np.int64) if n_words % 2 == 0 else None
+        if pairs is None or (pairs[:, 0] >= nlist).any() or len(np.unique(pairs[:, 0])) != len(pairs):
+            raise ValueError(f"{fname}: inconsistent sparse list sizes")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
+    if int(sizes.sum()) != ntotal:
+        raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}")
+    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), by_residual=bool(by_residual), M=int(M),
+                centroids=centroids, pq_centroids=pq_centroids, sizes=sizes, data=f.tell() - start)
+
+
+def read_ivf_pq(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, M, centroids fp32 [nlist, d] ([0, d] when untrained), pq_centroids fp32
+    [M, 256, d / M], list_off int64 [nlist + 1], codes uint8 [ntotal, M] in cell order, row_ids int64 [ntotal]).  offset: where the record starts;
+    it runs to `end` (default: the end of the file).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
+    size = _end(fname, end) - offset
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        st = _read_ivf_pq_head(f, fname, size)
+        ntotal, M, sizes = st["ntotal"], st["M"], st.pop("sizes")
+        if st.pop("data") + ntotal * (M + 8) != size:
+            raise ValueError(f"{fname}: {ntotal} rows of {M} + 8 bytes do not fill the record (bytes={size})")
+        codes = np.empty((ntotal, M), dtype=np.uint8)
+        row_ids = np.empty(ntotal, dtype=np.int64)
+        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        for c in np.flatnonzero(sizes):
+            a, b = int(list_off[c]), int(list_off[c + 1])
+            codes[a:b] = np.frombuffer(f.read((b - a) * M), dtype=np.uint8).reshape(b - a, M)
+            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
+    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
+    return st
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

@@ -25,47 +25,32 @@ _CAPTURE_WS_ERROR = ("IVFFlatIndex.search under graph capture: the search worksp
                      "search with the same number of queries, k and nprobe first")
 
 
-def check_ivf_args(d: int, nlist: int, nprobe: int):
+def check_ivf_args(d: int, nlist: int, nprobe: int, who: str = "IVFFlatIndex"):
     if d % 32 != 0 or not 32 <= d <= 8192:
-        raise ValueError(f"IVFFlatIndex: d={d} must be a multiple of 32 (32 .. 8192)")
+        raise ValueError(f"{who}: d={d} must be a multiple of 32 (32 .. 8192)")
     if nlist < 1:
-        raise ValueError(f"IVFFlatIndex: nlist={nlist} must be >= 1")
-    check_nprobe(nprobe, nlist)
+        raise ValueError(f"{who}: nlist={nlist} must be >= 1")
+    check_nprobe(nprobe, nlist, who)
 
 
-def check_nprobe(nprobe: int, nlist: int) -> int:
+def check_nprobe(nprobe: int, nlist: int, who: str = "IVFFlatIndex") -> int:
     if not 1 <= nprobe <= min(nlist, MAX_NPROBE):
-        raise ValueError(f"IVFFlatIndex: nprobe={nprobe} out of range (1..min(nlist={nlist}, {MAX_NPROBE}))")
+        raise ValueError(f"{who}: nprobe={nprobe} out of range (1..min(nlist={nlist}, {MAX_NPROBE}))")
     return int(nprobe)
 
 
-class IVFFlatIndex:
-    """faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT): d, nlist, nprobe, ntotal, is_trained, id_base; train / add / search /
-    reset / reconstruct_n / save / load / set_contents, and append_slot / commit as the other trainable shards have.
-    d % 32 == 0, 32 <= d <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
-
-    Training: Lloyd k-means on the L2 objective (what faiss's Clustering minimises for a non-spherical IP index) with PQIndex's rules --
-    np.random.default_rng(1234), at most 256 x nlist rows (sampled without replacement, row numbers sorted), initial centroids = nlist distinct
-    sampled rows, NITER = 10, deterministic fp64 segmented sums, faiss's split of empty cells; niter=0 leaves the initial centroids.  The
-    assignment is argmax_j (x . c_j - |c_j|^2 / 2), ties to the lower j: lrx_linear_transform (A = centroids, b = -|c|^2 / 2) over row chunks and
-    an arg-max.  The same input and seed give the same centroid bits; they are not faiss's (its RNG differs).
-    Coarse quantiser: a FlatIPIndex over the centroids (`quantizer`).  A row's cell at add() and a query's probe list at search() are its exact
-    top-1 / top-nprobe by INNER PRODUCT, ties to the lower cell.
-    Rows: fp32, held once, in cell order; inside a cell in ascending original row (faiss's insertion order).  `list_off` int64 [nlist + 1] and
-    `row_ids` int64 [ntotal] (position -> original row) sit beside them, `list_sizes` (numpy) is the host copy of the cell sizes, so a search
-    sizes its workspace without a device sync.  add() appends the rows as they come (one coarse search, one host read of the new cell sizes);
-    the cell order is rebuilt lazily, at the first search after an add: a stable sort of the cell numbers and a gather of the rows in chunks
-    of `rebuild_chunk_rows` into a second buffer -- two copies of the rows while it runs, never a third.
-    Memory: 4 B/element + 16 B per row (row_ids, the row's cell) + the centroids (6 B/element: the quantiser keeps its shadow) + the search
-    workspace (8 bytes per scanned row and query of a chunk, under 1 GiB).  NOT thread-safe."""
+class _IVFCells:
+    """What the inverted-file indexes (IVFFlatIndex here, IVFPQIndex in ivfpq.py) share: the coarse quantiser -- a FlatIPIndex over k-means
+    centroids -- and its training, the cell bookkeeping (`list_off`, `row_ids`, the host `list_sizes`, the cell `_assign` of every original
+    row, `_nsorted`), the staging of append_slot / commit, and the search prologue.  A subclass keeps what is its own: the stored rows or
+    codes, add, the rebuild of the cell order (_finalize), the library call of search, persistence."""
 
     NITER = 10
     MAX_POINTS_PER_CENTROID = 256
     SEED = 1234
     ASSIGN_CHUNK_BYTES = 256 << 20      # score matrix [rows, nlist] of one assignment chunk
 
-    def __init__(self, d: int, nlist: int, nprobe: int = 1, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
-        check_ivf_args(d, nlist, nprobe)
+    def _init_cells(self, d: int, nlist: int, nprobe: int, capacity: int, device: Optional[torch.device], id_base: int):
         _lib.require_gpu()
         self.lib = _lib.lib()
         self.d, self.nlist, self.nprobe = int(d), int(nlist), int(nprobe)
@@ -73,9 +58,7 @@ class IVFFlatIndex:
         self.id_base = id_base
         self.ntotal = 0
         self.is_trained = False
-        self.rebuild_chunk_rows = 262144
         self.quantizer = FlatIPIndex(d, capacity=nlist, device=self.device)
-        self._x = torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device)
         self._assign = torch.empty(max(capacity, 0), dtype=torch.int64, device=self.device)   # cell of ORIGINAL row r
         self._clear_rows()
         self._stage = None
@@ -106,12 +89,11 @@ class IVFFlatIndex:
             torch.argmax(linear_transform(x[s:s + chunk], cent, b), dim=1, out=out[s:s + chunk])
         return out
 
-    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
-        """Lloyd k-means (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
-        x = self._rows(x, "train: ")
+    def _train_cells(self, x: torch.Tensor, niter: Optional[int] = None, seed: Optional[int] = None):
+        """Lloyd k-means of the coarse quantiser over the rows x (IVFFlatIndex's class note has the rules)."""
         n = x.shape[0]
         if n < self.nlist:
-            raise ValueError(f"IVFFlatIndex.train: {n} training rows < nlist={self.nlist}")
+            raise ValueError(f"{type(self).__name__}.train: {n} training rows < nlist={self.nlist}")
         niter = self.NITER if niter is None else niter
         rng = np.random.default_rng(self.SEED if seed is None else seed)
         max_pts = self.nlist * self.MAX_POINTS_PER_CENTROID
@@ -131,51 +113,48 @@ class IVFFlatIndex:
         self.quantizer.add(cent.to(self.device, torch.float32).reshape(self.nlist, self.d))
         self.is_trained = True
 
-    # -- rows ------------------------------------------------------------------------------------------------------
-    def _reserve(self, n_rows: int):
-        if n_rows > self._x.shape[0]:
-            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
-            new[:self.ntotal].copy_(self._x[:self.ntotal])
-            self._x = new
+    def _cells_of(self, x: torch.Tensor, out: torch.Tensor):
+        """out[i] = the cell of row i: its best centroid by inner product, ties to the lower cell (one coarse search per 262144 rows)."""
+        for s in range(0, x.shape[0], 262144):
+            out[s:s + 262144].copy_(self.quantizer.search(x[s:s + 262144], 1)[1][:, 0])
+
+    def _reserve_assign(self, n_rows: int):
         if n_rows > self._assign.shape[0]:
             new = torch.empty(n_rows, dtype=torch.int64, device=self.device)
             new[:self.ntotal].copy_(self._assign[:self.ntotal])
             self._assign = new
 
-    def add(self, x):
-        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFFlatIndex.add: the index is not trained (call train() first)")
-        x = self._rows(x, "add: ")
-        n = x.shape[0]
-        if n == 0:
-            return
-        if self.ntotal + n > self._x.shape[0]:
-            self._reserve(_grown(self._x.shape[0], self.ntotal + n))
-        a, b = self.ntotal, self.ntotal + n
-        for s in range(0, n, 262144):
-            self._assign[a + s:min(a + s + 262144, b)].copy_(self.quantizer.search(x[s:s + 262144], 1)[1][:, 0])
-        self._x[a:b].copy_(x)
-        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
-        self.ntotal = b
-
-    def _finalize(self):
-        """The rows back into cell order (see the class note): a no-op unless rows were added since the last search."""
-        if self._nsorted == self.ntotal:
-            return
+    def _cell_order(self):
+        """(orig, perm) of the rebuild: orig[pos] = the original row of every stored position as it stands (the ordered part, then the new
+        rows as added), perm = the stable sort of their cells -- within a cell old rows (ascending) before new rows (ascending)."""
         n, ns = self.ntotal, self._nsorted
-        # the cell of every stored position: the ordered part by its original row, the new rows as they stand
         orig = torch.cat([self.row_ids[:ns], torch.arange(ns, n, dtype=torch.int64, device=self.device)])
-        perm = torch.argsort(self._assign[orig], stable=True)          # within a cell: old rows (ascending) before new rows (ascending)
-        new = torch.empty(max(self._x.shape[0], n), self.d, dtype=torch.float32, device=self.device)
-        for s in range(0, n, self.rebuild_chunk_rows):
-            e = min(s + self.rebuild_chunk_rows, n)
-            torch.index_select(self._x, 0, perm[s:e], out=new[s:e])
-        self._x = new
+        return orig, torch.argsort(self._assign[orig], stable=True)
+
+    def _set_cell_order(self, orig: torch.Tensor, perm: torch.Tensor):
         self.row_ids = orig[perm]
         self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
         self.list_off[1:] = torch.from_numpy(np.cumsum(self.list_sizes)).to(self.device)
-        self._nsorted = n
+        self._nsorted = self.ntotal
+
+    def _check_cells(self, n: int, list_off, row_ids):
+        """set_contents' validation of (list_off, row_ids) for n stored rows -> the two as int64 numpy arrays."""
+        lo = np.asarray(torch.as_tensor(list_off).cpu().numpy(), dtype=np.int64).reshape(-1)
+        ri = np.asarray(torch.as_tensor(row_ids).cpu().numpy(), dtype=np.int64).reshape(-1)
+        if lo.shape[0] != self.nlist + 1 or lo[0] != 0 or lo[-1] != n or (np.diff(lo) < 0).any():
+            raise ValueError(f"set_contents: list_off must ascend from 0 to n={n} over nlist + 1 = {self.nlist + 1} entries")
+        if ri.shape[0] != n or not np.array_equal(np.sort(ri), np.arange(n)):
+            raise ValueError(f"set_contents: row_ids must be a permutation of 0 .. {n - 1}")
+        return lo, ri
+
+    def _set_cells(self, lo: np.ndarray, ri: np.ndarray):
+        n = ri.shape[0]
+        self.row_ids = torch.from_numpy(ri).to(self.device)
+        self.list_off = torch.from_numpy(lo).to(self.device)
+        self.list_sizes = np.diff(lo)
+        self._assign = torch.empty(max(n, 0), dtype=torch.int64, device=self.device)
+        self._assign[self.row_ids] = torch.repeat_interleave(torch.arange(self.nlist, device=self.device), torch.from_numpy(self.list_sizes).to(self.device))
+        self.ntotal = self._nsorted = n
 
     def append_slot(self, n_rows: int) -> torch.Tensor:
         """A transient fp32 staging view for the next n rows: write them, then commit(n)."""
@@ -198,6 +177,96 @@ class IVFFlatIndex:
         """faiss reset(): drops the rows, keeps the training."""
         self._clear_rows()
         self._stage = None
+
+    def max_scan_rows(self, nprobe: Optional[int] = None) -> int:
+        """The most rows one query can scan: the sum of the nprobe largest cells (from the host copy of the sizes)."""
+        nprobe = self.nprobe if nprobe is None else nprobe
+        return int(np.sort(self.list_sizes)[::-1][:nprobe].sum())
+
+    def _begin_search(self, q, k: int, nprobe: Optional[int], row_map: Optional[torch.Tensor]):
+        """The checks every search starts with -> (q fp32 [Q, d] on the device, nprobe); the cell order is rebuilt when rows were added."""
+        who = type(self).__name__
+        if not self.is_trained:
+            raise RuntimeError(f"{who}.search: the index is not trained")
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"search: k={k} out of range (1..{MAX_K})")
+        nprobe = check_nprobe(self.nprobe if nprobe is None else nprobe, self.nlist, who)
+        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
+            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
+        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        if q.shape[0] and self._nsorted != self.ntotal:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.LrxError(f"{who}.search under graph capture: rows were added since the last search (run one eager search first)")
+            self._finalize()
+        return q, nprobe
+
+
+class IVFFlatIndex(_IVFCells):
+    """faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT): d, nlist, nprobe, ntotal, is_trained, id_base; train / add / search /
+    reset / reconstruct_n / save / load / set_contents, and append_slot / commit as the other trainable shards have.
+    d % 32 == 0, 32 <= d <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
+
+    Training: Lloyd k-means on the L2 objective (what faiss's Clustering minimises for a non-spherical IP index) with PQIndex's rules --
+    np.random.default_rng(1234), at most 256 x nlist rows (sampled without replacement, row numbers sorted), initial centroids = nlist distinct
+    sampled rows, NITER = 10, deterministic fp64 segmented sums, faiss's split of empty cells; niter=0 leaves the initial centroids.  The
+    assignment is argmax_j (x . c_j - |c_j|^2 / 2), ties to the lower j: lrx_linear_transform (A = centroids, b = -|c|^2 / 2) over row chunks and
+    an arg-max.  The same input and seed give the same centroid bits; they are not faiss's (its RNG differs).
+    Coarse quantiser: a FlatIPIndex over the centroids (`quantizer`).  A row's cell at add() and a query's probe list at search() are its exact
+    top-1 / top-nprobe by INNER PRODUCT, ties to the lower cell.
+    Rows: fp32, held once, in cell order; inside a cell in ascending original row (faiss's insertion order).  `list_off` int64 [nlist + 1] and
+    `row_ids` int64 [ntotal] (position -> original row) sit beside them, `list_sizes` (numpy) is the host copy of the cell sizes, so a search
+    sizes its workspace without a device sync.  add() appends the rows as they come (one coarse search, one host read of the new cell sizes);
+    the cell order is rebuilt lazily, at the first search after an add: a stable sort of the cell numbers and a gather of the rows in chunks
+    of `rebuild_chunk_rows` into a second buffer -- two copies of the rows while it runs, never a third.
+    Memory: 4 B/element + 16 B per row (row_ids, the row's cell) + the centroids (6 B/element: the quantiser keeps its shadow) + the search
+    workspace (8 bytes per scanned row and query of a chunk, under 1 GiB).  NOT thread-safe."""
+
+    def __init__(self, d: int, nlist: int, nprobe: int = 1, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
+        check_ivf_args(d, nlist, nprobe)
+        self._init_cells(d, nlist, nprobe, capacity, device, id_base)
+        self.rebuild_chunk_rows = 262144
+        self._x = torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device)
+
+    def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
+        """Lloyd k-means (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
+        self._train_cells(self._rows(x, "train: "), niter, seed)
+
+    # -- rows ------------------------------------------------------------------------------------------------------
+    def _reserve(self, n_rows: int):
+        if n_rows > self._x.shape[0]:
+            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
+            new[:self.ntotal].copy_(self._x[:self.ntotal])
+            self._x = new
+        self._reserve_assign(n_rows)
+
+    def add(self, x):
+        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product (raises before train(), as faiss does)."""
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIndex.add: the index is not trained (call train() first)")
+        x = self._rows(x, "add: ")
+        n = x.shape[0]
+        if n == 0:
+            return
+        if self.ntotal + n > self._x.shape[0]:
+            self._reserve(_grown(self._x.shape[0], self.ntotal + n))
+        a, b = self.ntotal, self.ntotal + n
+        self._cells_of(x, self._assign[a:b])
+        self._x[a:b].copy_(x)
+        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
+        self.ntotal = b
+
+    def _finalize(self):
+        """The rows back into cell order (see the class note): a no-op unless rows were added since the last search."""
+        if self._nsorted == self.ntotal:
+            return
+        n = self.ntotal
+        orig, perm = self._cell_order()
+        new = torch.empty(max(self._x.shape[0], n), self.d, dtype=torch.float32, device=self.device)
+        for s in range(0, n, self.rebuild_chunk_rows):
+            e = min(s + self.rebuild_chunk_rows, n)
+            torch.index_select(self._x, 0, perm[s:e], out=new[s:e])
+        self._x = new
+        self._set_cell_order(orig, perm)
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """ORIGINAL rows [i0, i0 + n) as an fp32 device tensor [n, d]."""
@@ -222,49 +291,22 @@ class IVFFlatIndex:
         """Replace the centroids ([nlist, d]) and the rows: `rows` fp32 [n, d] already in cell order, list_off int64 [nlist + 1] (ascending from
         0 to n), row_ids int64 [n] a permutation of 0 .. n - 1 (position -> original row): load() and tests."""
         rows = torch.as_tensor(rows)
-        lo = np.asarray(torch.as_tensor(list_off).cpu().numpy(), dtype=np.int64).reshape(-1)
-        ri = np.asarray(torch.as_tensor(row_ids).cpu().numpy(), dtype=np.int64).reshape(-1)
-        n = rows.shape[0]
         if rows.ndim != 2 or rows.shape[1] != self.d:
             raise ValueError(f"set_contents: rows must be [n, {self.d}], got {tuple(rows.shape)}")
-        if lo.shape[0] != self.nlist + 1 or lo[0] != 0 or lo[-1] != n or (np.diff(lo) < 0).any():
-            raise ValueError(f"set_contents: list_off must ascend from 0 to n={n} over nlist + 1 = {self.nlist + 1} entries")
-        if ri.shape[0] != n or not np.array_equal(np.sort(ri), np.arange(n)):
-            raise ValueError(f"set_contents: row_ids must be a permutation of 0 .. {n - 1}")
+        lo, ri = self._check_cells(rows.shape[0], list_off, row_ids)
         self._set_centroids(torch.as_tensor(centroids))
         self._clear_rows()
         self._x = rows.to(self.device, torch.float32).contiguous().clone()
-        self.row_ids = torch.from_numpy(ri).to(self.device)
-        self.list_off = torch.from_numpy(lo).to(self.device)
-        self.list_sizes = np.diff(lo)
-        self._assign = torch.empty(max(n, 0), dtype=torch.int64, device=self.device)
-        self._assign[self.row_ids] = torch.repeat_interleave(torch.arange(self.nlist, device=self.device), torch.from_numpy(self.list_sizes).to(self.device))
-        self.ntotal = self._nsorted = n
+        self._set_cells(lo, ri)
 
     # -- search --------------------------------------------------------------------------------------------------
-    def max_scan_rows(self, nprobe: Optional[int] = None) -> int:
-        """The most rows one query can scan: the sum of the nprobe largest cells (from the host copy of the sizes)."""
-        nprobe = self.nprobe if nprobe is None else nprobe
-        return int(np.sort(self.list_sizes)[::-1][:nprobe].sum())
-
     def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
         """-> (D f32[Q,k], I i64[Q,k]) device tensors: the exact top k over the rows of each query's nprobe best cells (by inner product with
         the centroids), score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
         I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFFlatIndex.search: the index is not trained")
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"search: k={k} out of range (1..{MAX_K})")
-        nprobe = check_nprobe(self.nprobe if nprobe is None else nprobe, self.nlist)
-        if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
-            raise ValueError("row_map must be a contiguous int64 CUDA tensor of >= ntotal entries")
-        q = _as_rows(q, self.d, "search: ", "Q").to(device=self.device, dtype=torch.float32).contiguous()
+        q, nprobe = self._begin_search(q, k, nprobe, row_map)
         if q.shape[0] == 0:
             return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
-        if self._nsorted != self.ntotal:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.LrxError("IVFFlatIndex.search under graph capture: rows were added since the last search (run one eager search first)")
-            self._finalize()
         _, probes = self.quantizer.search(q, nprobe)
         return ops.ivf_flat_ip_topk(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, k, self.max_scan_rows(nprobe), self.id_base, row_map,
                                     ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)

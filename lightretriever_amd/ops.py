@@ -309,3 +309,42 @@ def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, r
                                           _lib.ptr(q), Q, _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), k,
                                           int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
     return D, I
+
+
+def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
+                   probes: torch.Tensor, probe_scores: Optional[torch.Tensor], by_residual: bool, k: int, max_scan_rows: int, id_base: int = 0,
+                   row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None, capture_error: Optional[str] = None):
+    """lrx_ivf_pq_ip_search -> (D f32[Q,k], I i64[Q,k]): the top k under the ADC score over the rows of the cells probes[i] names.  q fp32 [Q, d]
+    contiguous; codes: the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by cell; pq_centroids fp32 [M, 256, d / M];
+    list_off int64 [nlist + 1] (list_off[nlist] = the rows held); row_ids int64 [n] (original row of a position) or None; probes int64
+    [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not by_residual): a scanned row's score
+    starts at its cell's probe score when by_residual, at 0 otherwise; max_scan_rows: the caller's bound on the rows one query scans.
+    ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
+    from .index import _workspace
+    lib = _lib.lib()
+    Q, nprobe = probes.shape
+    d = q.shape[1]
+    M = pq_centroids.shape[0]
+    nlist = list_off.numel() - 1
+    n = codes.numel() // (-(-M // 16) * 16) if row_ids is None else row_ids.numel()
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError("ivf_pq_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
+    if codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous() or codes.numel() < -(-n // 128) * 128 * (-(-M // 16) * 16):
+        raise ValueError("ivf_pq_ip_topk: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)")
+    if pq_centroids.dtype != torch.float32 or not pq_centroids.is_contiguous() or tuple(pq_centroids.shape) != (M, 256, d // max(M, 1)) or d % M:
+        raise ValueError("ivf_pq_ip_topk: pq_centroids must be fp32 [M, 256, d / M] contiguous with d % M == 0")
+    ld = probes.stride(0) if Q > 1 else nprobe
+    if by_residual:
+        if probe_scores is None or probe_scores.dtype != torch.float32 or probe_scores.shape != probes.shape or (nprobe and probe_scores.stride(1) != 1) or \
+                (Q > 1 and probe_scores.stride(0) != ld):
+            raise ValueError("ivf_pq_ip_topk: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
+    if Q == 0:
+        return D, I
+    need = int(lib.lrx_ivf_pq_ip_workspace_bytes(n, nlist, d, M, Q, nprobe, k, int(max_scan_rows)))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
+    _lib.check(lib.lrx_ivf_pq_ip_search(_lib.ptr(codes) if n else None, n, _lib.ptr(pq_centroids), d, M, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                        _lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
+                                        int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+    return D, I
