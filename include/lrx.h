@@ -210,8 +210,9 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
 /* Number of out-of-range token ids any embedding gather (stand-alone or inside lrx_encode_*) has met since the last reset, plus the
  * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
- * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search count
- * (probe entries >= nlist, queries over max_scan_rows, stored rows outside the shard); -1 if the read
+ * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search /
+ * lrx_ivf_sq_fp16_ip_search / lrx_ivf_sq_fp16_encode_rows count (probe entries >= nlist, queries over max_scan_rows, stored rows outside the
+ * shard, rows encoded for a cell outside [0, nlist)); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -829,6 +830,47 @@ int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const float* pq_cent
                          const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
                          int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base,
                          float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (added in ABI 8, additively) INVERTED FILE over fp16 SCALAR-QUANTISED codes: the exact top k, under the fp16 store's score, over the rows of
+ * the cells a query probes -- the scan of faiss IndexIVFScalarQuantizer(quantizer, d, nlist, QT_fp16, METRIC_INNER_PRODUCT) (IVFSQIndex, DESIGN
+ * 5.4.12).  The caller owns the coarse quantiser: it passes the probe lists and, with by_residual, the coarse scores of the probed cells.
+ *   cells, probes, ids   lrx_ivf_flat_ip_search's, unchanged: list_off, row_ids, probes, ld_probe, max_scan_rows, id_base and row_map keep their
+ *               meaning; score descending, ties to the lower ORIGINAL row; (-FLT_MAX, -1) padding; an entry < 0 is skipped; an entry >= nlist is
+ *               NEVER dereferenced and is counted once in lrx_device_error_count; a cell named twice by one query is scanned once for it (with
+ *               the base term of its FIRST occurrence); a query whose cells hold more than max_scan_rows returns padding and is counted once; a
+ *               position whose original row is outside [0, n_rows) is dropped and counted.
+ *   codes       fp16, ROW-MAJOR [n_rows, dim] by stored position, CELL BY CELL, 2 dim bytes per row (not the tiled layout of lrx_sq_fp16_ip_search);
+ *               the base pointer 16-byte aligned.  A row's code is fp16(v_i) under lrx_shard_commit_rows' rounding rule -- round-to-nearest-even,
+ *               saturating at +-65504 where faiss gives inf.  Without by_residual v = x; with it v_i = fl32(x_i - c_i), ONE fp32 subtraction of
+ *               the centroid of the row's cell, then the fp16 rounding.  lrx_ivf_sq_fp16_encode_rows writes them.
+ *   score       of a scanned (query i, row) pair of the probed cell probes[i][j]:  (float)(B + sum_e (double)q_e * (double)(float)code_e).  The
+ *               sum is exact_dot's: lane `sub` of a half-wave takes elements 4 sub + 128 u + 0..3 of each 2048-element block, fp64
+ *               accumulation, the xor tree 16, 8, 4, 2, 1; B joins the reduced sum; ONE rounding.  B = 0 without by_residual; with it
+ *               B = (double)probe_scores[i * ld_probe + j], the caller's fp32 score of the cell for that query (faiss: coarse_dis).  by_residual
+ *               with probe_scores == NULL is LRX_ERR_INVALID.  Without by_residual a pair's score is bit for bit what lrx_sq_fp16_ip_search
+ *               and lrx_sq_fp16_ip_rerank report for the same code.  Every scanned row is scored exactly, once per query that probes its cell.
+ *   a query's result depends on its own rows of q, probes and probe_scores alone: not on n_queries, its position in the call or the chunking.
+ *   limits      dim % 32 == 0, 32 <= dim <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); ld_probe >= nprobe; 1 <= k <= 2048;
+ *               0 <= n_rows < 2^32; 0 <= max_scan_rows < 2^31; codes and q 16-byte aligned (q [n_queries, dim] contiguous).  n_queries == 0
+ *               launches nothing.  Anything else is LRX_ERR_INVALID with a message before any device work; a workspace under
+ *               lrx_ivf_sq_fp16_ip_workspace_bytes (= lrx_ivf_flat_ip_workspace_bytes of the same arguments): LRX_ERR_WORKSPACE.
+ * Per chunk of queries (lrx_ivf_flat_ip_search's chunk) that entry's six launches on `stream` (kernels only: no memset or copy node), no host
+ * synchronisation, every size from the arguments alone, capturable in a HIP graph: clear, plan, work items, scatter, the CELL-MAJOR persistent
+ * scan over groups of lrx_ivf_sq_fp16_group_rows(dim) = min(128, 32768 / dim) consecutive code rows staged in LDS as fp16 (64 KiB: twice the
+ * rows of the fp32 scan), and the selection.
+ * lrx_ivf_sq_fp16_encode_rows: one kernel -- code rows [row0, row0 + n) from x[i * ldx + e] (fp32; ldx >= dim, ldx % 4 == 0, 16-byte aligned):
+ * gather the centroid of cells[i] (int64 [n], device; centroids fp32 [nlist, dim] contiguous, NULL: no residual, and then cells may be NULL),
+ * subtract, round, saturate.  A cells[i] outside [0, nlist) is never dereferenced: its codes are written as zeros and it is counted in
+ * lrx_device_error_count.  row0 + n < 2^32. */
+int32_t lrx_ivf_sq_fp16_group_rows(int32_t dim);
+size_t lrx_ivf_sq_fp16_ip_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int32_t k,
+                                          int64_t max_scan_rows);
+int lrx_ivf_sq_fp16_ip_search(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                              const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe, int64_t ld_probe,
+                              int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
+                              const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_sq_fp16_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim, const float* centroids, const int64_t* cells, int32_t nlist,
+                                void* codes, int64_t row0, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

@@ -7,3 +7,4 @@ from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
 from .refine import RefineFlatIndex  # noqa: F401
 from .ivf import IVFFlatIndex  # noqa: F401
 from .ivfpq import IVFPQIndex  # noqa: F401
+from .ivfsq import IVFSQIndex  # noqa: F401

@@ -15,7 +15,8 @@
 //                  the cell -- one half-wave per (query, row), the query row streamed from L2 (exact_dot_lds_row: the bits of exact_dot) --
 //                  writing packed (score, ORIGINAL row) words into the queries' segments.  Cells nobody probes cost nothing.
 //   k_ivf_select   one workgroup per query: sorted top k of its segment (counting ranks / register sort up to 2048 words, radix select above).
-// Every size depends on the arguments alone; nothing is read back to the host.
+// Every size depends on the arguments alone; nothing is read back to the host.  The host driver of this chain is ivf_cell_major_search, shared
+// with the scan over fp16 codes (lrx_search_ivfsq.h): an entry brings its row check, its group size and the launch of its scan.
 #pragma once
 
 #define IVF_MAX_NPROBE 2048
@@ -363,28 +364,44 @@ extern "C" size_t lrx_ivf_flat_ip_workspace_bytes(int64_t n_rows, int32_t nlist,
   return ivf_plan(nlist, ivf_chunk_queries(n_queries, max_scan_rows), nprobe, max_scan_rows).total;
 }
 
-extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
-                                      const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
-                                      int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  LRX_CHECK_ARG(dim >= 32 && dim <= 8192 && dim % 32 == 0, "ivf_flat_ip_search: dim=%d must be a multiple of 32 in 32..8192", dim);
-  LRX_CHECK_ARG(k >= 1 && k <= SEL_MAXK, "ivf_flat_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
-  LRX_CHECK_ARG(nlist >= 1, "ivf_flat_ip_search: nlist=%d must be >= 1", nlist);
-  LRX_CHECK_ARG(nprobe >= 1 && nprobe <= IVF_MAX_NPROBE && nprobe <= nlist, "ivf_flat_ip_search: nprobe=%d out of range (1..min(nlist=%d, %d))", nprobe, nlist,
+// What a cell-major scan is handed per chunk (ivf_cell_major_search below): the chunk's queries start at q0 of the call's.
+struct IvfScanArgs {
+  hipStream_t stream;
+  unsigned int grid;
+  int q0, G;
+  const float* q;                           // the chunk's query rows
+  const unsigned long long* sorted;
+  const unsigned int *cell_off, *item_off, *seg_off;
+  unsigned int item_cap;
+  unsigned long long* words;
+};
+
+// The host driver of the CELL-MAJOR chain, shared by lrx_ivf_flat_ip_search and lrx_ivf_sq_fp16_ip_search (lrx_search_ivfsq.h): the argument
+// checks both contracts have in common (`who` names the entry in the messages; rows_ok / rows_why: the entry's own check of its row store, made
+// by the caller), the workspace, and per chunk k_ivf_clear, k_ivf_plan<false>, k_ivf_items, k_pairs_scatter, the entry's scan -- launched by
+// `scan(const IvfScanArgs&)` over groups of G stored rows -- and k_ivf_select.  Kernels only, one stream, nothing read back.
+template <class Scan>
+static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok, const char* rows_why, int G, int64_t n_rows, int32_t dim,
+                                 const int64_t* list_off, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe,
+                                 int64_t ld_probe, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
+                                 const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream, Scan scan) {
+  LRX_CHECK_ARG(dim >= 32 && dim <= 8192 && dim % 32 == 0, "%s: dim=%d must be a multiple of 32 in 32..8192", who, dim);
+  LRX_CHECK_ARG(k >= 1 && k <= SEL_MAXK, "%s: k=%d out of range (1..%d)", who, k, SEL_MAXK);
+  LRX_CHECK_ARG(nlist >= 1, "%s: nlist=%d must be >= 1", who, nlist);
+  LRX_CHECK_ARG(nprobe >= 1 && nprobe <= IVF_MAX_NPROBE && nprobe <= nlist, "%s: nprobe=%d out of range (1..min(nlist=%d, %d))", who, nprobe, nlist,
                 IVF_MAX_NPROBE);
-  LRX_CHECK_ARG(ld_probe >= nprobe, "ivf_flat_ip_search: ld_probe=%lld < nprobe=%d", (long long)ld_probe, nprobe);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "ivf_flat_ip_search: rows=%lld out of range", (long long)n_rows);
-  LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "ivf_flat_ip_search: max_scan_rows=%lld out of range (0..2^31 - 1)", (long long)max_scan_rows);
-  LRX_CHECK_ARG(ldx >= dim && ldx % 4 == 0 && (uintptr_t)X % 16 == 0, "ivf_flat_ip_search: rows must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)",
-                (long long)ldx, dim);
-  LRX_CHECK_ARG(n_queries >= 0, "ivf_flat_ip_search: n_queries=%d", n_queries);
+  LRX_CHECK_ARG(ld_probe >= nprobe, "%s: ld_probe=%lld < nprobe=%d", who, (long long)ld_probe, nprobe);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "%s: rows=%lld out of range", who, (long long)n_rows);
+  LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "%s: max_scan_rows=%lld out of range (0..2^31 - 1)", who, (long long)max_scan_rows);
+  LRX_CHECK_ARG(rows_ok, "%s: %s", who, rows_why);
+  LRX_CHECK_ARG(n_queries >= 0, "%s: n_queries=%d", who, n_queries);
   if (n_queries == 0) return LRX_OK;
-  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && out_scores != nullptr && out_ids != nullptr && (X != nullptr || n_rows == 0),
-                "ivf_flat_ip_search: null pointer");
-  LRX_CHECK_ARG((uintptr_t)q % 16 == 0, "ivf_flat_ip_search: q must be 16-byte aligned");
+  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && out_scores != nullptr && out_ids != nullptr && (rows != nullptr || n_rows == 0),
+                "%s: null pointer", who);
+  LRX_CHECK_ARG((uintptr_t)q % 16 == 0, "%s: q must be 16-byte aligned", who);
   const size_t need = lrx_ivf_flat_ip_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, k, max_scan_rows);
   if (workspace == nullptr || workspace_bytes < need) {
-    lrx_set_error("ivf_flat_ip_search: workspace %zu B < required %zu B", workspace_bytes, need);
+    lrx_set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, need);
     return LRX_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -400,13 +417,11 @@ extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ld
   unsigned int* seg_off = (unsigned int*)(ws + p.off_seg);
   int64_t* q_tot = (int64_t*)(ws + p.off_tot);
   unsigned long long* words = (unsigned long long*)(ws + p.off_words);
-  const int G = ivf_group_rows(dim);
   const int64_t ngroups = lrx_cdiv(n_rows, G);
   const int64_t item_cap = ngroups + nlist;                  // a cell's last group may be partial
   const int64_t scan_wgs = item_cap < 8 * (int64_t)lrx_cu_count() ? item_cap : 8 * (int64_t)lrx_cu_count();
   for (int q0 = 0; q0 < n_queries; q0 += chunk) {
     const int nq = n_queries - q0 < chunk ? n_queries - q0 : chunk;
-    const float* qc = q + (int64_t)q0 * dim;
     hipLaunchKernelGGL(k_ivf_clear, dim3((unsigned)lrx_cdiv((int64_t)nlist + 1, 256)), dim3(256), 0, s, total, (int)nlist + 1);
     LRX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_ivf_plan<false>, dim3(nq), dim3(IVF_PLAN_THREADS), 0, s, probes + (int64_t)q0 * ld_probe, (int)nprobe, ld_probe, list_off, (int)nlist,
@@ -419,9 +434,12 @@ extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ld
       hipLaunchKernelGGL(k_pairs_scatter, dim3((unsigned)(sb < 1024 ? sb : 1024)), dim3(256), 0, s, (const unsigned long long*)pairs, (const unsigned int*)total,
                          cell_cnt, (const unsigned int*)cell_off, 0, sorted);
       LRX_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_ivf_scan, dim3((unsigned)scan_wgs), dim3(ROWGRP_THREADS), 0, s, X, n_rows, ldx, (int)dim, G, list_off, row_ids, (int)nlist, qc,
-                         (int)nprobe, (const unsigned long long*)sorted, (const unsigned int*)cell_off, (const unsigned int*)item_off,
-                         (unsigned int)(item_cap < 0xFFFFFFFFll ? item_cap : 0xFFFFFFFFll), (const unsigned int*)seg_off, max_scan_rows, words);
+      IvfScanArgs a;
+      a.stream = s; a.grid = (unsigned)scan_wgs; a.q0 = q0; a.G = G; a.q = q + (int64_t)q0 * dim;
+      a.sorted = sorted; a.cell_off = cell_off; a.item_off = item_off; a.seg_off = seg_off;
+      a.item_cap = (unsigned int)(item_cap < 0xFFFFFFFFll ? item_cap : 0xFFFFFFFFll);
+      a.words = words;
+      scan(a);
       LRX_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_ivf_select, dim3(nq), dim3(1024), 0, s, (const unsigned long long*)words, max_scan_rows, (const int64_t*)q_tot, (int)k, id_base, row_map,
@@ -429,4 +447,18 @@ extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ld
     LRX_LAUNCH_CHECK();
   }
   return LRX_OK;
+}
+
+extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                      const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
+                                      int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  char why[128];
+  snprintf(why, sizeof(why), "rows must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)", (long long)ldx, dim);
+  return ivf_cell_major_search("ivf_flat_ip_search", X, ldx >= dim && ldx % 4 == 0 && (uintptr_t)X % 16 == 0, why, dim > 0 ? ivf_group_rows(dim) : 1, n_rows,
+                               dim, list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, k, id_base, out_scores, out_ids, row_map,
+                               workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
+    hipLaunchKernelGGL(k_ivf_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, X, n_rows, ldx, (int)dim, a.G, list_off, row_ids, (int)nlist, a.q,
+                       (int)nprobe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+  });
 }

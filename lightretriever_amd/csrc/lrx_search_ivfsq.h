@@ -1,0 +1,163 @@
+// liblrx search, part N -- INVERTED FILE over fp16 SCALAR-QUANTISED codes (faiss IndexIVFScalarQuantizer, QT_fp16, inner product): the exact
+// top k under the fp16 store's score over the rows of the cells a query probes.  k_ivf_sq_scan, k_ivf_sq_encode, lrx_ivf_sq_fp16_ip_search,
+// lrx_ivf_sq_fp16_encode_rows (contract: include/lrx.h).
+// Part of the ONE translation unit lrx_search.hip (included at its end, after lrx_search_ivfpq.h: it reuses the whole cell-major chain of
+// lrx_search_ivf.h -- ivf_cell_major_search: clear, plan, items, scatter, select, the chunking, the workspace and the error counter -- and
+// f2h_sat of lrx_search_filter.h).  Not a stand-alone header.
+//
+// The only kernel of the chain that is this file's is the scan: k_ivf_scan's item walk over codes of 2 bytes per element, row-major [n_rows, dim]
+// by stored position (NOT the tiled layout of the flat fp16 index: a cell's rows are consecutive, so a group is one contiguous run of bytes).
+#pragma once
+
+#define IVFSQ_LDS_HALVES 32768            // 64 KiB of codes per workgroup, as k_ivf_scan's rows: twice its rows per group
+
+static int ivf_sq_group_rows(int32_t dim) {
+  const int g = IVFSQ_LDS_HALVES / dim;
+  return g > IVF_MAX_GROUP_ROWS ? IVF_MAX_GROUP_ROWS : (g < 1 ? 1 : g);
+}
+extern "C" int32_t lrx_ivf_sq_fp16_group_rows(int32_t dim) { return dim >= 1 ? ivf_sq_group_rows(dim) : 0; }
+
+// exact_dot_codes with the code row in LDS (row-major) and the query row in global memory: the SAME partial products in the same order (lane
+// sub of a half-wave: elements i0 + 128 u + (0..3), i0 = 4 sub, 2048-element blocks), each code decoded exactly to fp32, fp64 accumulation,
+// the same xor tree; `base` joins the reduced sum before the one rounding.  base = 0: bit-identical to exact_dot_codes (the sum is never -0).
+__device__ __forceinline__ float exact_dot_lds_codes(const _Float16* c_lds, const float* __restrict__ qglob, int D, int lane, double base) {
+  const int sub = lane & 31;
+  double acc = 0.0;
+  for (int i0 = sub * 4; i0 < D; i0 += 2048) {
+    f32x4 qv[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = i0 + u * 128;
+      qv[u] = i < D ? *(const f32x4*)(qglob + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const int i = i0 + u * 128;
+      if (i < D) {
+        const f16x4 xv = *(const f16x4*)(c_lds + i);
+        acc += (double)(float)xv[0] * (double)qv[u][0] + (double)(float)xv[1] * (double)qv[u][1] + (double)(float)xv[2] * (double)qv[u][2] +
+               (double)(float)xv[3] * (double)qv[u][3];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  return (float)(base + acc);
+}
+
+// The scan: k_ivf_scan's walk (persistent, cell-major, the same items, pairs and word positions) over fp16 codes.  Per item its G consecutive
+// code rows -- one contiguous run of nrows * D halves, 16-byte aligned since D % 32 == 0 -- are staged in LDS AS fp16 (coalesced non-temporal
+// 16-byte loads) and scored against every query that probes the cell, one half-wave per (pair, row).  The base term of a pair is the caller's
+// score of the cell for that query, read through the pair's slot: probe_scores[query * ld_probe + slot % nprobe] (NULL: 0).  Rows outside
+// [0, N) are never read; an original row outside it becomes a word of 0 and is counted.
+__global__ void __launch_bounds__(ROWGRP_THREADS)
+k_ivf_sq_scan(const _Float16* __restrict__ C, int64_t N, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist,
+              const float* __restrict__ q, const float* __restrict__ probe_scores, int nprobe, int64_t ld_probe,
+              const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off, const unsigned int* __restrict__ item_off,
+              unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words) {
+  __shared__ __attribute__((aligned(16))) _Float16 s_c[IVFSQ_LDS_HALVES];
+  const int tid = threadIdx.x, lane = tid & 63, hw = tid >> 5;
+  const unsigned int n_items = min(item_off[nlist], item_cap);
+  unsigned int bad = 0;
+  for (unsigned int it = blockIdx.x; it < n_items; it += gridDim.x) {
+    int lo = 0, hi = nlist;                                  // the last cell with item_off[c] <= it
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (item_off[mid] <= it) lo = mid; else hi = mid;
+    }
+    const int c = lo;
+    const int64_t ca = list_off[c], cb = list_off[c + 1];
+    const int64_t ra = ca + (int64_t)(it - item_off[c]) * G;
+    int64_t rb = ra + G;
+    rb = rb < cb ? rb : cb;
+    rb = rb < N ? rb : N;
+    const unsigned int p0 = cell_off[c], np = cell_off[c + 1] - p0;
+    if (ra < ca || ra < 0 || rb <= ra || np == 0) continue;  // (workgroup-uniform)
+    const int nrows = (int)(rb - ra);                        // (<= G: nrows * D <= IVFSQ_LDS_HALVES)
+    __syncthreads();                                         // the previous item's codes are no longer read
+    const _Float16* src = C + ra * D;
+    for (int i = tid * 8; i < nrows * D; i += ROWGRP_THREADS * 8) *(f16x8*)(s_c + i) = __builtin_nontemporal_load((const f16x8*)(src + i));
+    __syncthreads();
+    const unsigned int units = np * (unsigned int)nrows;     // (at most IVF_MAX_CHUNK pairs x 128 rows)
+    for (unsigned int u = hw; u < units; u += ROWGRP_THREADS / 32) {
+      const unsigned int pi = u / (unsigned int)nrows;
+      const int rr = (int)(u - pi * (unsigned int)nrows);
+      const int64_t r = ra + rr;
+      const unsigned int slot = (unsigned int)sorted[p0 + pi];
+      const unsigned int qi = slot / (unsigned int)nprobe;
+      const double base = probe_scores != nullptr ? (double)probe_scores[(int64_t)qi * ld_probe + (slot - qi * (unsigned int)nprobe)] : 0.0;
+      const float sc = exact_dot_lds_codes(s_c + rr * D, q + (int64_t)qi * D, D, lane, base);
+      if ((lane & 31) == 0) {
+        const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
+        const bool ok = orig >= 0 && orig < N;               // (a word of 0 is nobody's row: the selection drops it)
+        if (!ok) ++bad;
+        words[(int64_t)qi * max_scan + seg_off[slot] + (r - ca)] = ok ? sel_pack(f2key(sc), orig) : 0ull;
+      }
+    }
+  }
+  if (bad) atomicAdd(&g_ivf_bad, bad);
+}
+
+// The codes of n rows, one workgroup per row in turn: v = x - centroid[cell] (one fp32 subtraction; cent == NULL: v = x), code = fp16(v) by
+// f2h_sat (round-to-nearest-even, saturating at +-65504), into code row row0 + i.  A cell outside [0, nlist) is never dereferenced: the row's
+// codes are zeros and it is counted.
+__global__ void __launch_bounds__(256)
+k_ivf_sq_encode(const float* __restrict__ x, int64_t ldx, int64_t n, int D, const float* __restrict__ cent, const int64_t* __restrict__ cells, int nlist,
+                _Float16* __restrict__ codes, int64_t row0) {
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+    const int64_t c = cells != nullptr ? cells[i] : 0;
+    const bool ok = cells == nullptr || (c >= 0 && c < (int64_t)nlist);
+    const float* xr = x + i * ldx;
+    const float* cr = (ok && cent != nullptr) ? cent + c * D : nullptr;
+    _Float16* o = codes + (row0 + i) * D;
+    for (int e = threadIdx.x * 4; e < D; e += 256 * 4) {
+      f16x4 h = {0, 0, 0, 0};
+      if (ok) {
+        const f32x4 xv = *(const f32x4*)(xr + e);
+        const f32x4 cv = cr != nullptr ? *(const f32x4*)(cr + e) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) h[t] = f2h_sat(cr != nullptr ? xv[t] - cv[t] : xv[t]);
+      }
+      *(f16x4*)(o + e) = h;
+    }
+    if (!ok && threadIdx.x == 0) atomicAdd(&g_ivf_bad, 1u);
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------
+extern "C" size_t lrx_ivf_sq_fp16_ip_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int32_t k,
+                                                     int64_t max_scan_rows) {
+  return lrx_ivf_flat_ip_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, k, max_scan_rows);
+}
+
+extern "C" int lrx_ivf_sq_fp16_ip_search(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                         const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe,
+                                         int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores,
+                                         int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "ivf_sq_fp16_ip_search: by_residual=%d needs probe_scores", by_residual);
+  return ivf_cell_major_search("ivf_sq_fp16_ip_search", codes, (uintptr_t)codes % 16 == 0, "codes must be 16-byte aligned", dim > 0 ? ivf_sq_group_rows(dim) : 1,
+                               n_rows, dim, list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, k, id_base, out_scores, out_ids, row_map,
+                               workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
+    hipLaunchKernelGGL(k_ivf_sq_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const _Float16*)codes, n_rows, (int)dim, a.G, list_off, row_ids,
+                       (int)nlist, a.q, by_residual ? probe_scores + (int64_t)a.q0 * ld_probe : (const float*)nullptr, (int)nprobe, ld_probe, a.sorted,
+                       a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+  });
+}
+
+extern "C" int lrx_ivf_sq_fp16_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim, const float* centroids, const int64_t* cells, int32_t nlist,
+                                           void* codes, int64_t row0, void* stream) {
+  LRX_CHECK_ARG(dim >= 32 && dim <= 8192 && dim % 32 == 0, "ivf_sq_fp16_encode_rows: dim=%d must be a multiple of 32 in 32..8192", dim);
+  LRX_CHECK_ARG(n >= 0 && row0 >= 0 && row0 + n < (1ll << 32), "ivf_sq_fp16_encode_rows: rows [%lld, %lld + %lld) out of range", (long long)row0,
+                (long long)row0, (long long)n);
+  LRX_CHECK_ARG(nlist >= 1, "ivf_sq_fp16_encode_rows: nlist=%d must be >= 1", nlist);
+  LRX_CHECK_ARG(centroids == nullptr || cells != nullptr, "ivf_sq_fp16_encode_rows: centroids need cells");
+  if (n == 0) return LRX_OK;
+  LRX_CHECK_ARG(x != nullptr && codes != nullptr, "ivf_sq_fp16_encode_rows: null pointer");
+  LRX_CHECK_ARG(ldx >= dim && ldx % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)centroids % 16 == 0 && (uintptr_t)codes % 16 == 0,
+                "ivf_sq_fp16_encode_rows: x, centroids and codes must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)", (long long)ldx, dim);
+  const int64_t wgs = n < 8 * (int64_t)lrx_cu_count() * 8 ? n : 8 * (int64_t)lrx_cu_count() * 8;
+  hipLaunchKernelGGL(k_ivf_sq_encode, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, x, ldx, n, (int)dim, centroids, cells, (int)nlist,
+                     (_Float16*)codes, row0);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}

@@ -125,7 +125,25 @@ Faiss's serialisation of IndexIVFPQ (write_ivf_header, then by_residual, code_si
           then for every non-empty cell, in ascending order: u8 codes[size][M] (row-major), i64 ids[size]
 
 Like 'IwFl' it is **unverified against a Faiss build** (faiss is not installed here).  The reader accepts both list-size forms and refuses any
-other by name; index_record_end knows the record, so a refine index can hold it as its base."""
+other by name; index_record_end knows the record, so a refine index can hold it as its base.
+
+An inverted-file fp16 scalar-quantised index (IVFSQIndex, faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_fp16,
+METRIC_INNER_PRODUCT)) is written as Faiss's serialisation of IndexIVFScalarQuantizer (write_ivf_header, write_ScalarQuantizer, then code_size,
+by_residual, write_InvertedLists), same source:
+
+    u32   fourcc 'IwSq'
+          the IVF header exactly as in 'IwFl' above: index header, u64 nlist, u64 nprobe, the 'IxFI' quantiser, the empty direct map
+    i32   qtype = 4 (QT_fp16),  i32 rangestat = 0,  f32 rangestat_arg = 0,  u64 d,  u64 code_size = 2 d     (the ScalarQuantizer of 'IxSQ' above)
+    u64   0                                   (`trained`: an empty float vector)
+    u64   code_size = 2 d
+    u8    by_residual
+    u32   fourcc 'ilar',  u64 nlist,  u64 code_size = 2 d
+          the list sizes, 'full' or 'sprs', as in 'IwFl'
+          then for every non-empty cell, in ascending order: f16 codes[size][d] (row-major, little-endian), i64 ids[size]
+
+Like 'IwFl' and 'IwPQ' it is **unverified against a Faiss build** (faiss is not installed here).  The reader accepts both list-size forms and
+refuses any other qtype, a non-empty direct map and other inverted lists by name; index_record_end knows the record, so a refine index can hold
+it as its base."""
 from __future__ import annotations
 
 import csv
@@ -463,7 +481,8 @@ def read_pre_transform(fname: str, offset: int = 0, end: Optional[int] = None):
 
 FOURCC_REFINE = b"IxRF"
 FOURCC_IVF_PQ = b"IwPQ"
-_REFINE_BASES = (FOURCC_PQ, FOURCC_SQ, FOURCC_PRE_TRANSFORM, FOURCC_IVF_PQ)
+FOURCC_IVF_SQ = b"IwSq"
+_REFINE_BASES = (FOURCC_PQ, FOURCC_SQ, FOURCC_PRE_TRANSFORM, FOURCC_IVF_PQ, FOURCC_IVF_SQ)
 
 
 def refine_prefix(d: int, ntotal: int, is_trained: bool = True) -> bytes:
@@ -482,7 +501,7 @@ def peek_index_header(fname: str, offset: int = 0, end: Optional[int] = None):
 
 
 def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> int:
-    """Where the 'IxFI', 'IxSQ', 'IxPq', 'IxPT' or 'IwPQ' record that starts at `offset` stops, from its own size words; ValueError when that is past
+    """Where the 'IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ' or 'IwSq' record that starts at `offset` stops, from its own size words; ValueError when that is past
     `end` (default: the end of the file) or the record is of another type.  The reader of the record's class then validates it against
     [offset, the returned end)."""
     size = _end(fname, end)
@@ -494,8 +513,13 @@ def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> 
             f.seek(offset)
             st = _read_ivf_pq_head(f, fname, size - offset)
         return offset + st["data"] + st["ntotal"] * (st["M"] + 8)
+    if fourcc == FOURCC_IVF_SQ:
+        with open(fname, "rb") as f:
+            f.seek(offset)
+            st = _read_ivf_sq_head(f, fname, size - offset)
+        return offset + st["data"] + st["ntotal"] * (2 * st["d"] + 8)
     if fourcc not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
-        raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ')")
+        raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ', 'IwSq')")
     with open(fname, "rb") as f:
         pos = offset + _HEADER.size + {FOURCC_FLAT_IP: 0, FOURCC_SQ: _SQ.size, FOURCC_PQ: _PQ.size}[fourcc]
         # the vectors that follow: (bytes per element, ...) -- each a u64 count and its elements
@@ -524,7 +548,7 @@ def write_refine(fname: str, d: int, ntotal: int, is_trained: bool, k_factor: fl
 
 def read_refine(fname: str):
     """-> dict(d, ntotal, is_trained, k_factor, base, store); base / store = dict(offset, end, fourcc, qtype): where each record lies, its
-    fourcc (base: 'IxPq', 'IxSQ', 'IxPT' or 'IwPQ'; store: 'IxFI', or 'IxSQ' with qtype QT_fp16) and the ScalarQuantizer type of an 'IxSQ' record
+    fourcc (base: 'IxPq', 'IxSQ', 'IxPT', 'IwPQ' or 'IwSq'; store: 'IxFI', or 'IxSQ' with qtype QT_fp16) and the ScalarQuantizer type of an 'IxSQ' record
     (else None).  The caller reads each with the reader of its class at (offset, end)."""
     size = os.path.getsize(fname)
     if size < _HEADER.size + 4:
@@ -777,6 +801,122 @@ def read_ivf_pq(fname: str, offset: int = 0, end: Optional[int] = None):
         for c in np.flatnonzero(sizes):
             a, b = int(list_off[c]), int(list_off[c + 1])
             codes[a:b] = np.frombuffer(f.read((b - a) * M), dtype=np.uint8).reshape(b - a, M)
+            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
+    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
+    return st
+
+
+def write_ivf_sq(fname: str, centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True, is_trained: bool = True,
+                 prefix: bytes = b"", append: bool = False) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; codes fp16 [ntotal, d] row-major in CELL ORDER; row_ids int64
+    [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwSq' record (the layout at the head of this file;
+    faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname; `prefix` /
+    `append` as in _write_index (the enclosing record of write_refine)."""
+    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+    nlist, ntotal = sizes.shape[0], int(sizes.sum())
+    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
+    cent = np.ascontiguousarray(centroids, dtype="<f4")
+    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
+        raise ValueError(f"write_ivf_sq: centroids {cent.shape} do not match nlist={nlist}")
+    d = cent.shape[1]
+    codes = np.asarray(codes)
+    if codes.dtype != np.float16 or ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, d):
+        raise ValueError(f"write_ivf_sq: {ids.shape[0]} row ids and codes {codes.dtype} {codes.shape}, the list sizes sum to {ntotal} (fp16, d={d})")
+    codes = np.ascontiguousarray(codes, dtype="<f2")
+    head = _index_header(FOURCC_IVF_SQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
+    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
+    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
+    head += _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<Q", 0)  # the ScalarQuantizer, its empty `trained`
+    head += struct.pack("<QB", 2 * d, int(bool(by_residual)))          # code_size, by_residual
+    head += _ILAR + struct.pack("<QQ", nlist, 2 * d) + _list_sizes_bytes(sizes)
+    tmp = fname if append else fname + ".tmp"
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    with open(tmp, "ab" if append else "wb") as f:
+        f.write(prefix)
+        f.write(head)
+        for c in np.flatnonzero(sizes):
+            a, b = int(off[c]), int(off[c + 1])
+            f.write(codes[a:b].tobytes())
+            f.write(ids[a:b].tobytes())
+    if not append:
+        os.replace(tmp, fname)
+
+
+def _read_ivf_sq_head(f, fname: str, size: int):
+    """An 'IwSq' record from the file position up to its list sizes (`size`: the bytes the record may fill) -> dict(d, nlist, nprobe, ntotal,
+    is_trained, by_residual, centroids, sizes, data: the record's bytes before the first cell's codes)."""
+    start = f.tell()
+
+    def take(n: int, what: str) -> bytes:
+        b = f.read(n) if f.tell() - start + n <= size else b""
+        if len(b) != n:
+            raise ValueError(f"{fname}: truncated inverted-file scalar-quantiser index ({what})")
+        return b
+    if size < 2 * _HEADER.size + 16:
+        raise ValueError(f"{fname}: too short for an inverted-file scalar-quantiser index header")
+    d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_SQ, "an inverted-file scalar-quantiser index")
+    nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
+    if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
+        raise ValueError(f"{fname}: inconsistent inverted-file scalar-quantiser index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
+    qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file scalar-quantiser index")
+    (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
+    if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
+        raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
+    centroids = np.frombuffer(take(4 * n_floats, "centroids"), dtype="<f4").reshape(qn, d)
+    dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
+    if dm_type != 0 or dm_n != 0:
+        raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
+    qtype, _, _, sq_d, sq_code = _SQ.unpack(take(_SQ.size, "scalar quantiser"))
+    if qtype != QT_FP16:
+        raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served over cells (only QT_fp16 = {QT_FP16})")
+    (n_trained,) = struct.unpack("<Q", take(8, "trained size"))
+    code_size, by_residual = struct.unpack("<QB", take(9, "code_size, by_residual"))
+    if sq_d != d or sq_code != 2 * d or n_trained != 0 or code_size != 2 * d or by_residual not in (0, 1):
+        raise ValueError(f"{fname}: inconsistent IndexIVFScalarQuantizer quantiser (sq.d={sq_d}, sq.code_size={sq_code}, trained={n_trained}, "
+                         f"code_size={code_size}, by_residual={by_residual}; d={d})")
+    il = take(4, "inverted lists")
+    if il != _ILAR:
+        raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
+    il_nlist, il_code = struct.unpack("<QQ", take(16, "inverted lists header"))
+    if il_nlist != nlist or il_code != 2 * d:
+        raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, d={d}")
+    form = take(4, "list sizes")
+    (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if form == _FULL:
+        if n_words != nlist:
+            raise ValueError(f"{fname}: {n_words} list sizes for nlist={nlist}")
+        sizes[:] = np.frombuffer(take(8 * nlist, "list sizes"), dtype="<u8")
+    elif form == _SPRS:
+        pairs = np.frombuffer(take(8 * n_words, "list sizes"), dtype="<u8").reshape(-1, 2).astype(np.int64) if n_words % 2 == 0 else None
+        if pairs is None or (pairs[:, 0] >= nlist).any() or len(np.unique(pairs[:, 0])) != len(pairs):
+            raise ValueError(f"{fname}: inconsistent sparse list sizes")
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
+    if int(sizes.sum()) != ntotal:
+        raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}")
+    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), by_residual=bool(by_residual),
+                centroids=centroids, sizes=sizes, data=f.tell() - start)
+
+
+def read_ivf_sq(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, centroids fp32 [nlist, d] ([0, d] when untrained), list_off int64 [nlist + 1],
+    codes fp16 [ntotal, d] in cell order, row_ids int64 [ntotal]).  offset: where the record starts; it runs to `end` (default: the end of the
+    file).  Both list-size forms ('full', 'sprs') are read; another qtype, a direct map and other inverted lists are refused by name."""
+    size = _end(fname, end) - offset
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        st = _read_ivf_sq_head(f, fname, size)
+        ntotal, d, sizes = st["ntotal"], st["d"], st.pop("sizes")
+        if st.pop("data") + ntotal * (2 * d + 8) != size:
+            raise ValueError(f"{fname}: {ntotal} rows of {2 * d} + 8 bytes do not fill the record (bytes={size})")
+        codes = np.empty((ntotal, d), dtype=np.float16)
+        row_ids = np.empty(ntotal, dtype=np.int64)
+        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        for c in np.flatnonzero(sizes):
+            a, b = int(list_off[c]), int(list_off[c + 1])
+            codes[a:b] = np.frombuffer(f.read((b - a) * 2 * d), dtype="<f2").reshape(b - a, d)
             row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
     st.update(list_off=list_off, codes=codes, row_ids=row_ids)
     return st

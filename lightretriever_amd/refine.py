@@ -16,9 +16,10 @@ import torch
 from . import _lib
 from .index import FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, _as_rows, _check_range, _workspace
 from .ivfpq import IVFPQIndex
+from .ivfsq import IVFSQIndex
 from .transform import PreTransformIndex
 
-BASES = (PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex)
+BASES = (PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex, IVFSQIndex)
 STORES = (FlatIPIndex, SQFp16Index)
 MAX_K_BASE = 2048         # candidates per query the rerank takes: the most any base search delivers
 
@@ -74,7 +75,7 @@ def rerank(q: torch.Tensor, store, cand: torch.Tensor, k: int, id_base: int = 0,
 class RefineFlatIndex:
     """faiss.IndexRefineFlat(base_index) / faiss.IndexRefine(base_index, refine_index): d, ntotal, device, is_trained (the base's), id_base
     (applied to the results only), k_factor; train / add / reset / reconstruct_n / append_slot / commit / search / save / load.
-    base_index: a PQIndex, SQ8Index, SQFp16Index, PreTransformIndex or IVFPQIndex with id_base 0 (this index owns the id offset); anything else:
+    base_index: a PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex or IVFSQIndex with id_base 0 (this index owns the id offset); anything else:
     TypeError.  refine_index (the store): None -- a fresh FlatIPIndex(d) WITHOUT its fp16 shadow (the rows are gathered, never streamed:
     4 B/element, not 6) -- or a FlatIPIndex, or an SQFp16Index (2 B/element: faiss IndexRefine(base, IndexScalarQuantizer(QT_fp16))); same d
     (a PreTransformIndex's d is d_in) and the same ntotal as the base.  k_factor >= 1.
@@ -182,7 +183,7 @@ class RefineFlatIndex:
 
     @classmethod
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "RefineFlatIndex":
-        from .index_io import FOURCC_FLAT_IP, FOURCC_IVF_PQ, FOURCC_PQ, FOURCC_PRE_TRANSFORM, QT_FP16, read_refine
+        from .index_io import FOURCC_FLAT_IP, FOURCC_IVF_PQ, FOURCC_IVF_SQ, FOURCC_PQ, FOURCC_PRE_TRANSFORM, QT_FP16, read_refine
         st = read_refine(fname)
         b, r = st["base"], st["store"]
         if b["fourcc"] == FOURCC_PQ:
@@ -191,6 +192,8 @@ class RefineFlatIndex:
             base_cls = PreTransformIndex
         elif b["fourcc"] == FOURCC_IVF_PQ:
             base_cls = IVFPQIndex
+        elif b["fourcc"] == FOURCC_IVF_SQ:
+            base_cls = IVFSQIndex
         else:
             base_cls = SQFp16Index if b["qtype"] == QT_FP16 else SQ8Index
         base = base_cls.load(fname, device=device, offset=b["offset"], end=b["end"])
