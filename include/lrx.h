@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define LRX_ABI_VERSION 8
+#define LRX_ABI_VERSION 9
 
 enum {
   LRX_OK = 0,
@@ -483,6 +483,21 @@ int64_t lrx_search_fallback_count(int32_t reset);
 int32_t lrx_flat_ip_bounded_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags, int32_t has_shadow);
 int lrx_flat_ip_bounded_list_counts(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
                                     int32_t has_shadow, uint32_t* counts_out, void* stream);
+/* (ABI 9) The stage state the last chunk of the last bounded search (flat or fp16-SQ) left in `workspace`, read-only: tests compare every
+ * stage of the filter chain with an fp64 model.  Arguments as for lrx_flat_ip_bounded_list_counts + that search's ldx (dim for the
+ * fp16-SQ index).  Copy kernels on `stream` only: no synchronisation, no allocation, nothing written to the workspace.
+ *   plan_out    HOST int32[LRX_CHUNK_STATE_PLAN_INTS], filled before the call returns: {lists kept (score-free filter), fused launch, GEMM main
+ *               pass, sample stride ss (every ss-th unit of rb rows is a sample unit), rb, list capacity, parts per query of the refine step,
+ *               row-grouped rescoring, rows per entry of the sample's maxima (16 / 128), sample units, plain path (nothing else is written), 0}
+ *   thr_eps_out device float[2 n_queries]: thr = T' - 2 eps as stored, then eps (zeros without lists)
+ *   ints_out    device int32[3 n_queries + 8]: list count (uint32, raw: an overflowing list shows more than the capacity), flags, band size
+ *               (sum of the parts' counts, -1 when a part reported overflow), then any_flag[8]
+ *   entry_scores / entry_rows  device float / int64 [n_queries, max_entries]: the first min(count, capacity, max_entries) entries of each
+ *               list as (fp32 filter score, row); the rest is left as the caller initialised it.  max_entries = 0: none.                       */
+#define LRX_CHUNK_STATE_PLAN_INTS 12
+int lrx_flat_ip_bounded_chunk_state(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
+                                    int32_t has_shadow, int64_t ldx, int32_t* plan_out, float* thr_eps_out, int32_t* ints_out,
+                                    int32_t max_entries, float* entry_scores, int64_t* entry_rows, void* stream);
 
 /* (added in ABI 8, additively) Exact inner-product RANGE search (faiss IndexFlatIP::range_search): every row whose exact score -- the value
  * every search path reports, (float) of the fp64-accumulated sum of the fp32 products -- is STRICTLY greater than `radius`.  Result in faiss's

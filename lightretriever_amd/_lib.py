@@ -6,7 +6,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LRX_LIB_DEV_VARIANT") or os.path.join(HERE, "liblrx.so")   # env override: tools/ diagnostics only
 LRX_PROF_CLASSES = 8
-ABI_VERSION = 8   # LRX_ABI_VERSION of include/lrx.h
+ABI_VERSION = 9   # LRX_ABI_VERSION of include/lrx.h
 # lrx_flat_ip_search_bounded flags (LRX_SEARCH_FILTER_*): A/B runs and tests; the hits do not depend on them
 SEARCH_FILTER_AUTO, SEARCH_FILTER_MATRIX, SEARCH_FILTER_SCORE_FREE, SEARCH_FILTER_SCORE_FREE_NO_GEMM = 0, 1, 2, 3
 SEARCH_FUSED_ALWAYS, SEARCH_FUSED_NEVER = 4, 8
@@ -71,6 +71,7 @@ SIGNATURES = {
     "lrx_search_fallback_count": (_I64, [_I32]),
     "lrx_flat_ip_bounded_chunk_queries": (_I32, [_I64, _I32, _I32, _I32, _I32, _I32]),
     "lrx_flat_ip_bounded_list_counts": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "lrx_flat_ip_bounded_chunk_state": (_I32, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _I32, _P, _P, _P]),
     "lrx_flat_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "lrx_flat_ip_range_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _P, _I32, _F, _I64, _P, _P, _P, _I64, _P, _SZ, _P]),
     "lrx_sq_fp16_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32]),

@@ -515,6 +515,21 @@ extern "C" int lrx_flat_ip_search_bounded(const float* X, int64_t n_rows, int64_
                                          workspace, workspace_bytes, flags, stream);
 }
 
+// Two decisions of the emit path that depend on the chunk alone (bounded_search below; lrx_flat_ip_bounded_chunk_state reports them).
+// Parts per query of the refine step (the measurements are at their use in bounded_search):
+static int refine_nsplit(int nq) { return (int64_t)nq * REF_SPLIT <= lrx_cu_count() ? REF_SPLIT : ((int64_t)nq * 2 <= lrx_cu_count() ? 2 : 1); }
+// ... and whether the band rows are rescored grouped by row: the pairs must fit the score region, the rule is the measured one (there)
+static int row_group_shift(int32_t dim) { return dim <= 512 ? 5 : (dim <= 1024 ? 4 : (dim <= 2048 ? 3 : 2)); }
+static bool rescore_by_row_groups(const BoundedPlan& p, int64_t n_rows, int64_t ldx, int32_t dim, int32_t nq, int32_t k, int32_t flags) {
+  const int gshift = row_group_shift(dim);
+  const int64_t ngroups = (n_rows + ((int64_t)1 << gshift) - 1) >> gshift;
+  const size_t pair_bytes = align256((size_t)nq * REF_CAND * 8);
+  const size_t need = 2 * pair_bytes + align256((size_t)(ngroups + 2) * 4) * 2 + 256;
+  const bool fits = need <= p.off_qsplit && ((int64_t)1 << gshift) * dim <= ROWGRP_LDS_FLOATS && dim % 4 == 0 && ldx % 4 == 0 && ngroups < (1 << 30);
+  const bool rule = dim >= 2048 && (int64_t)nq * k * 5 / 4 >= (5 * n_rows) / 2;
+  return fits && !(flags & 32) && (rule || (flags & 16));
+}
+
 // The bounded search over either row source (lrx_search_select.h, row_dot): RS = ROWS_F32 -- X = fp32 rows (stride ldx), X_shadow = their
 // optional tiled fp16 shadow (lrx_flat_ip_search_bounded_wire); RS = ROWS_F16T -- X = X_shadow = the tiled fp16 codes of a scalar-quantised
 // index, nothing else resident (lrx_sq_fp16_ip_search): the filter is the same pass over the same layout, the exact rescoring reads the
@@ -650,23 +665,20 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
       // more than the merge launch saves.)
       // (Round 3, measured and not kept: the number of parts, 1..8, that leaves the fewest CUs idle over whole rounds -- 5 for 100 queries:
       // top-1000 0.959 ms against 0.951 with 2 parts, top-100 0.730 against 0.719, 8 parts 1.00 / 0.747: the gather is bound chip-wide.)
-      nsplit = (int64_t)nq * REF_SPLIT <= lrx_cu_count() ? REF_SPLIT : ((int64_t)nq * 2 <= lrx_cu_count() ? 2 : 1);
+      nsplit = refine_nsplit(nq);
       // (Round 4, re-measured on the per-rank shard sizes, 100 queries: 125 k x 2048 0.190 / 0.178-0.181 / 0.190 / 0.191-0.192 ms for 1 / 2 / 3 / 4 parts,
       // 1.25M x 256 0.202 / 0.196-0.198 / 0.208 / 0.202-0.208, 1M x 2048 0.741 / 0.722-0.726 / 0.735 / 0.738-0.743: two parts everywhere.)
       // Row-grouped rescoring where the chunk wants every row more than twice on average (~1.2 k band rows per query): the pairs and the
       // group counters live in the score region, which nothing reads between the sample's selection and the gated fallback.
       RowPairs rp = {nullptr, nullptr, nullptr, 0};
       {
-        const int gshift = dim <= 512 ? 5 : (dim <= 1024 ? 4 : (dim <= 2048 ? 3 : 2));
+        const int gshift = row_group_shift(dim);
         const int64_t ngroups = (n_rows + ((int64_t)1 << gshift) - 1) >> gshift;
         const size_t pair_bytes = align256((size_t)nq * REF_CAND * 8);
-        const size_t need = 2 * pair_bytes + align256((size_t)(ngroups + 2) * 4) * 2 + 256;
-        const bool fits = need <= p.off_qsplit && ((int64_t)1 << gshift) * dim <= ROWGRP_LDS_FLOATS && dim % 4 == 0 && ldx % 4 == 0 && ngroups < (1 << 30);
         // measured (tools/exp/refine_rows_ab.py, profiles/r05_refine_rows_ab.txt; gather / by row, ms): 1000 queries, k = 1000 over 50 k x 2048 1.98 / 1.47,
         // 100 k x 2048 2.20 / 2.14, 100 k x 4096 4.50 / 4.02, but 100 k x 1024 1.46 / 1.57, 200 k x 2048 2.82 / 3.49, k = 100 0.81 / 1.51: rows of
         // >= 8 KiB that the chunk wants >= 2.5 times on average (~1.25 k band rows per query)
-        const bool rule = dim >= 2048 && (int64_t)nq * k * 5 / 4 >= (5 * n_rows) / 2;
-        if (fits && !(flags & 32) && (rule || (flags & 16))) {
+        if (rescore_by_row_groups(p, n_rows, ldx, dim, nq, k, flags)) {
           char* b = ws;
           rp.pairs = (unsigned long long*)b;
           unsigned long long* sorted = (unsigned long long*)(b + pair_bytes);
@@ -831,6 +843,68 @@ extern "C" int lrx_flat_ip_bounded_list_counts(const void* workspace, int64_t n_
   const bool plain = (qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0;
   const unsigned int* cnt = p.emit && !plain ? (const unsigned int*)(flg + ints_before_cnt(n_queries)) : nullptr;
   hipLaunchKernelGGL(k_copy_list_counts, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream, cnt, n_queries, counts_out);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
+// The stage state of the LAST chunk of the last bounded search that used `workspace` (tests: every stage against an fp64 model, not only the
+// final result).  Same arguments as that search (and as lrx_flat_ip_bounded_list_counts) + its ldx; the layout is re-derived by plan_chunk.
+// Read-only: copy kernels on `stream`, no synchronisation, no allocation, nothing written to the workspace.  include/lrx.h has the outputs.
+// grid (nq, y): every workgroup copies a slice of its query's list entries; workgroup (q, 0) also writes the query's scalars, (0, 0) any_flag.
+__global__ void __launch_bounds__(256)
+k_copy_chunk_state(const int* __restrict__ flg, const int* __restrict__ any_flag, const unsigned int* __restrict__ cnt, const int* __restrict__ part_cnt,
+                   const float* __restrict__ thr, const float* __restrict__ eps, const unsigned long long* __restrict__ cand, int nq, int nsplit,
+                   unsigned int cap, int max_entries, float* __restrict__ thr_eps_out, int32_t* __restrict__ ints_out, float* __restrict__ entry_scores,
+                   int64_t* __restrict__ entry_rows) {
+  const int qi = blockIdx.x;
+  const unsigned int n = cnt != nullptr ? cnt[(size_t)qi * CNT_STRIDE] : 0u;
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
+    thr_eps_out[qi] = cnt != nullptr ? thr[qi] : 0.f;        // (the score-matrix filter has no threshold and no eps in the workspace)
+    thr_eps_out[nq + qi] = cnt != nullptr ? eps[qi] : 0.f;
+    ints_out[qi] = (int32_t)n;                               // raw: an overflowing list shows > cap (read as uint32)
+    ints_out[nq + qi] = flg[qi];
+    int band = 0;
+    for (int p = 0; p < nsplit; ++p) {
+      const int c = part_cnt[qi * nsplit + p];
+      band = (band < 0 || c < 0) ? -1 : band + c;
+    }
+    ints_out[2 * nq + qi] = band;
+    if (qi == 0)
+      for (int g = 0; g < ANY_FLAG_GROUPS; ++g) ints_out[3 * nq + g] = any_flag[g];
+  }
+  unsigned int ne = n < cap ? n : cap;
+  ne = ne < (unsigned int)max_entries ? ne : (unsigned int)max_entries;
+  for (unsigned int i = blockIdx.y * blockDim.x + threadIdx.x; i < ne; i += gridDim.y * blockDim.x) {
+    const unsigned long long e = cand[(int64_t)qi * cap + i];
+    entry_scores[(int64_t)qi * max_entries + i] = key2f((uint32_t)(e >> 32));
+    entry_rows[(int64_t)qi * max_entries + i] = sel_row(e);
+  }
+}
+extern "C" int lrx_flat_ip_bounded_chunk_state(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
+                                               int32_t has_shadow, int64_t ldx, int32_t* plan_out, float* thr_eps_out, int32_t* ints_out,
+                                               int32_t max_entries, float* entry_scores, int64_t* entry_rows, void* stream) {
+  const bool shadow = has_shadow && dim % 64 == 0;
+  LRX_CHECK_ARG(workspace && plan_out && thr_eps_out && ints_out && n_queries > 0 && n_queries <= (shadow ? LRX_EMIT_MAX_QUERIES : 128),
+                "bounded_chunk_state: one query chunk only (n_queries=%d)", n_queries);
+  LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK && max_entries >= 0 && (max_entries == 0 || (entry_scores && entry_rows)), "bounded_chunk_state: k=%d max_entries=%d", k, max_entries);
+  const BoundedPlan p = plan_chunk(n_rows, dim, n_queries, k, shadow, flags & 3, fused_pref_of(flags));
+  const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;     // (the plain-path test of bounded_search, as in the list counts above)
+  const bool plain = (qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0;
+  const bool lists = p.emit && !plain;
+  const int nsplit = lists ? refine_nsplit(n_queries) : REF_SPLIT;
+  const int32_t plan[LRX_CHUNK_STATE_PLAN_INTS] = {lists, lists && p.fused, lists && p.gemm, p.ss, p.rb, (int32_t)p.cap, nsplit,
+                                                   lists && rescore_by_row_groups(p, n_rows, ldx, dim, n_queries, k, flags), shadow ? 16 : 128,
+                                                   (int32_t)p.nsamp_wg, plain, 0};
+  memcpy(plan_out, plan, sizeof(plan));
+  if (plain) return LRX_OK;                                                // (the plain path keeps nothing of this layout in the workspace: plan_out says so)
+  const int* flg = (const int*)((const char*)workspace + p.off_ints);
+  const unsigned int* cnt = (const unsigned int*)(flg + ints_before_cnt(n_queries));
+  const int* part_cnt = (const int*)(cnt + (size_t)n_queries * CNT_STRIDE);
+  const float* thr = (const float*)(part_cnt + (size_t)n_queries * REF_SPLIT);
+  const int ny = lists && max_entries > 0 ? (max_entries < 16 * 256 ? (max_entries + 255) / 256 : 16) : 1;
+  hipLaunchKernelGGL(k_copy_chunk_state, dim3(n_queries, ny), dim3(256), 0, (hipStream_t)stream, flg, flg + n_queries, lists ? cnt : (const unsigned int*)nullptr,
+                     part_cnt, thr, thr + n_queries, (const unsigned long long*)((const char*)workspace + p.off_cand), n_queries, nsplit, p.cap,
+                     lists ? max_entries : 0, thr_eps_out, ints_out, entry_scores, entry_rows);
   LRX_LAUNCH_CHECK();
   return LRX_OK;
 }

@@ -278,7 +278,7 @@ class _TiledIPIndex:
         # (nq of the last library chunk of the last host chunk, the ntotal / mode the workspace was planned for, and the workspace itself)
         last_ws = lane_ws[((Q - 1) // chunk) % self.chunk_lanes] if fork else ws
         n_last_call = (Q - 1) % chunk + 1                                    # queries of the last library call ...
-        self._last_search = ((n_last_call - 1) % lib_chunk_of(n_last_call) + 1, k, flags, xb is not None, last_ws, self.ntotal, bool(self.two_pass))   # ... and of its last chunk
+        self._last_search = ((n_last_call - 1) % lib_chunk_of(n_last_call) + 1, k, flags, xb is not None, last_ws, self.ntotal, bool(self.two_pass), ldx)   # ... and of its last chunk
         return D, I
 
     def _run_chunks(self, q, D, I, k, chunk, fork, lane_ws, ws, start, xb, ldx, flags, row_map, wire_out):
@@ -301,12 +301,50 @@ class _TiledIPIndex:
         not a two-pass search (no candidate lists exist); raises before the first search."""
         if self._last_search is None:
             raise _lib.LrxError("last_list_counts(): no search has run on this index yet")
-        nq, k, flags, has_shadow, ws, ntotal, two_pass = self._last_search
+        nq, k, flags, has_shadow, ws, ntotal, two_pass, _ = self._last_search
         out = torch.zeros(nq, dtype=torch.int32, device=self.device)
         if two_pass:                    # the workspace layout is the one planned for the ntotal of THAT search (add() / reset() since do not matter)
             _lib.check(self.lib.lrx_flat_ip_bounded_list_counts(_lib.ptr(ws), ntotal, self.d, nq, k, flags, int(has_shadow), _lib.ptr(out),
                                                                 _lib.current_stream()))
         return out.to(torch.int64)
+
+    def last_chunk_state(self, max_entries: Optional[int] = None) -> dict:
+        """What the stages of the last chunk of the last two-pass search left in its workspace (lrx_flat_ip_bounded_chunk_state; read-only,
+        for tests of the single stages): plan facts `emit`, `fused`, `gemm`, `ss`, `rb`, `cap`, `nsplit`, `row_grouped`, `group_rows`
+        (rows per entry of the sample's maxima), `nsamp` (sample units) and `nq`, `k`, `ntotal`; per query (host tensors) `thr` (= T' - 2 eps
+        as stored), `eps`, `count` (raw: an overflowing list shows more than `cap`), `flags`, `band` (sum of the parts' counts, -1 when a part
+        overflowed); `any_flag` [8]; and the lists: `scores` f32 / `rows` i64 [nq, max_entries] holding the first min(count, cap,
+        max_entries) entries of each list (rows = -1 beyond; max_entries defaults to cap).  Raises before the first search, after a search
+        with two_pass = False or down the plain path, and -- naming the reason -- when the last search kept no lists (score-matrix filter)."""
+        if self._last_search is None:
+            raise _lib.LrxError("last_chunk_state(): no search has run on this index yet")
+        nq, k, flags, has_shadow, ws, ntotal, two_pass, ldx = self._last_search
+        if not two_pass:
+            raise _lib.LrxError("last_chunk_state(): the last search was not a two-pass search (two_pass = False): no stage state")
+        plan = (C.c_int32 * 12)()
+        probe = torch.zeros(3 * nq + 8, dtype=torch.int32, device=self.device)
+        fprobe = torch.zeros(2 * nq, dtype=torch.float32, device=self.device)
+        call = lambda m, es, er: _lib.check(self.lib.lrx_flat_ip_bounded_chunk_state(
+            _lib.ptr(ws), ntotal, self.d, nq, k, flags, int(has_shadow), ldx, plan, _lib.ptr(fprobe), _lib.ptr(probe), m, _lib.ptr(es), _lib.ptr(er),
+            _lib.current_stream()))
+        call(0, None, None)                      # the plan facts (host side) and the scalars; the lists below once their capacity is known
+        emit, fused, gemm, ss, rb, cap, nsplit, row_grouped, group_rows, nsamp, plain = list(plan)[:11]
+        if plain:
+            raise _lib.LrxError(f"last_chunk_state(): the last search took the plain path ({ntotal} rows, d={self.d}): no stage state")
+        if not emit:
+            raise _lib.LrxError("last_chunk_state(): the last search kept no candidate lists (score-matrix filter: "
+                                f"{ntotal} rows, search_flags={flags})")
+        m = cap if max_entries is None else max(0, min(int(max_entries), cap))
+        scores = torch.zeros(nq, max(m, 1), dtype=torch.float32, device=self.device)
+        rows = torch.full((nq, max(m, 1)), -1, dtype=torch.int64, device=self.device)
+        if m:
+            call(m, scores, rows)
+        ints = probe.cpu()
+        thr_eps = fprobe.cpu()
+        return dict(emit=bool(emit), fused=bool(fused), gemm=bool(gemm), ss=ss, rb=rb, cap=cap, nsplit=nsplit, row_grouped=bool(row_grouped),
+                    group_rows=group_rows, nsamp=nsamp, nq=nq, k=k, ntotal=ntotal,
+                    thr=thr_eps[:nq].clone(), eps=thr_eps[nq:].clone(), count=ints[:nq].to(torch.int64) & 0xFFFFFFFF, flags=ints[nq:2 * nq].clone(),
+                    band=ints[2 * nq:3 * nq].clone(), any_flag=ints[3 * nq:3 * nq + 8].clone(), scores=scores[:, :m].cpu(), rows=rows[:, :m].cpu())
 
 
 class FlatIPIndex(_TiledIPIndex):

@@ -107,7 +107,7 @@ def test_c_abi_argument_errors_without_a_gpu():
     for s in ("lrx_binary_pack_rows", "lrx_binary_store_rows", "lrx_binary_decode_rows", "lrx_binary_workspace_bytes", "lrx_binary_hamming_search",
               "lrx_binary_ip_search"):
         assert s in _lib.SIGNATURES, s
-    assert l.lrx_abi_version() == 8
+    assert l.lrx_abi_version() == 9
     assert l.lrx_binary_workspace_bytes(1000, 2048, 10, 1000) > 0 and l.lrx_binary_workspace_bytes(1000, 100, 10, 1000) == 0
     assert l.lrx_binary_ip_search(None, 10, 64, None, 1, 0.0, None, 5, 4, 0, None, None, None, None, 0, 0, None) == -1   # k > binary_k
     assert b"binary_k" in l.lrx_last_error()

@@ -147,7 +147,7 @@ def test_header_ctypes_table_and_torch_op_agree():
         params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1).split(",")
         assert len(params) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(l, name)
-    assert _lib.ABI_VERSION == 8 and l.lrx_abi_version() == 8                                           # additive: the version stays
+    assert _lib.ABI_VERSION == 9 and l.lrx_abi_version() == 9                                           # additive: the version stays
     # argument errors come back on the host
     assert l.lrx_impact_search(None, None, 0, 10, None, None, None, 1, 0, 0, None, None, None, None, 0, 0, None) == -1 and b"k=0" in l.lrx_last_error()
     assert l.lrx_impact_search(None, None, 0, 10, None, None, None, 1, 5, 0, None, None, None, None, 0, 100, None) == -1 and b"window_rows" in l.lrx_last_error()

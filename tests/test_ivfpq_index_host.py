@@ -242,7 +242,7 @@ def test_searcher_arguments_and_routes():
 def test_both_symbols_are_exported():
     l = _lib.lib()
     assert callable(l.lrx_ivf_pq_ip_search) and callable(l.lrx_ivf_pq_ip_workspace_bytes)
-    assert l.lrx_abi_version() == 8
+    assert l.lrx_abi_version() == 9
 
 
 def _search(l, n_rows=1000, dim=64, M=8, nlist=16, n_queries=4, nprobe=4, ld_probe=None, by_residual=1, max_scan=500, k=10, ws_bytes=1 << 30,

@@ -282,7 +282,7 @@ def test_the_symbols_are_exported():
     l = _lib.lib()
     for name in ("lrx_ivf_sq_fp16_ip_search", "lrx_ivf_sq_fp16_ip_workspace_bytes", "lrx_ivf_sq_fp16_group_rows", "lrx_ivf_sq_fp16_encode_rows"):
         assert callable(getattr(l, name)) and name in _lib.SIGNATURES
-    assert l.lrx_abi_version() == 8
+    assert l.lrx_abi_version() == 9
 
 
 def _search(l, codes=FAKE, n_rows=1000, dim=64, nlist=16, n_queries=4, nprobe=4, ld_probe=None, by_residual=1, max_scan=500, k=10, ws_bytes=1 << 30,

@@ -295,7 +295,7 @@ def test_symbol_declared_exported_and_bound():
     l = ctypes.CDLL(build.build(verbose=False))
     assert "lrx_linear_transform(" in hdr and hasattr(l, "lrx_linear_transform") and "lrx_linear_transform" in _lib.SIGNATURES
     assert len(_lib.SIGNATURES["lrx_linear_transform"][1]) == 10
-    assert "#define LRX_ABI_VERSION 8" in hdr and _lib.lib().lrx_abi_version() == _lib.ABI_VERSION == 8
+    assert "#define LRX_ABI_VERSION 9" in hdr and _lib.lib().lrx_abi_version() == _lib.ABI_VERSION == 9
     assert "lrx_transform.hip" in build.SOURCES
     src = open(os.path.join(ROOT, "lightretriever_amd", "csrc", "lrx_search.hip")).read()
     assert "k_lt_" not in src and "lrx_transform" not in src                            # (tests count that file's kernels by prefix)

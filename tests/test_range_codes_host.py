@@ -24,7 +24,7 @@ def test_symbols_declared_exported_and_bound():
         assert s + "(" in hdr, s
         assert hasattr(l, s), s
         assert s in _lib.SIGNATURES, s
-    assert "#define LRX_ABI_VERSION 8" in hdr
+    assert "#define LRX_ABI_VERSION 9" in hdr
     assert os.path.exists(build.build_torch_ops(verbose=False))
     from lightretriever_amd import torch_ops
     for op in ("sq_fp16_ip_range_search", "pq_ip_range_search", "impact_range_search"):

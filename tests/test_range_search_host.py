@@ -17,7 +17,7 @@ def test_range_symbols_declared_exported_and_bound():
         assert s + "(" in hdr, s
         assert hasattr(l, s), s
         assert s in _lib.SIGNATURES, s
-    assert "#define LRX_ABI_VERSION 8" in hdr
+    assert "#define LRX_ABI_VERSION 9" in hdr
 
 
 def test_range_workspace_grows_with_rows_and_queries_up_to_one_chunk():

@@ -63,7 +63,7 @@ def test_symbols_declared_exported_and_bound():
     for name in NAMES:
         assert name + "(" in hdr and hasattr(l, name) and name in _lib.SIGNATURES, name
     assert [len(_lib.SIGNATURES[n][1]) for n in NAMES] == [3, 17, 16]
-    assert "#define LRX_ABI_VERSION 8" in hdr and _lib.lib().lrx_abi_version() == _lib.ABI_VERSION == 8
+    assert "#define LRX_ABI_VERSION 9" in hdr and _lib.lib().lrx_abi_version() == _lib.ABI_VERSION == 9
     assert '#include "lrx_search_rerank.h"' in open(os.path.join(ROOT, "lightretriever_amd", "csrc", "lrx_search.hip")).read()
     assert os.path.exists(build.build_torch_ops(verbose=False))
     import torch

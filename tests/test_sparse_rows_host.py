@@ -162,7 +162,7 @@ def test_header_ctypes_table_and_torch_op_agree():
     for name in names:
         params = re.search(r"\b%s\s*\(([^)]*)\)" % name, src).group(1).split(",")
         assert len(params) == len(_lib.SIGNATURES[name][1]) and hasattr(l, name), name
-    assert _lib.ABI_VERSION == 8 and l.lrx_abi_version() == 8                       # additive: the version stays
+    assert _lib.ABI_VERSION == 9 and l.lrx_abi_version() == 9                       # additive: the version stays
     # argument errors come back on the host, nothing is launched
     assert l.lrx_sparse_csr_count(None, 1, 8, 8, 100, 1, None, None) == -1 and b"sparse_csr_count" in l.lrx_last_error()
     assert l.lrx_sparse_csr_fill(None, 1, 8, 8, 100, 1, None, None, None, None) == -1 and b"sparse_csr_fill" in l.lrx_last_error()
