@@ -211,7 +211,7 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
  * attention work lists whose builder ran out of room (lrx_attn_build_items: their launches then compute nothing), plus the sequences
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
  * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search /
- * lrx_ivf_sq_fp16_ip_search / lrx_ivf_sq_fp16_encode_rows count (probe entries >= nlist, queries over max_scan_rows, stored rows outside the
+ * lrx_ivf_sq_fp16_ip_search / lrx_ivf_sq_fp16_encode_rows / lrx_ivf_sq8_ip_search / lrx_ivf_sq8_encode_rows / lrx_ivf_sq8_decode_rows count (probe entries >= nlist, queries over max_scan_rows, stored rows outside the
  * shard, rows encoded for a cell outside [0, nlist)); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
@@ -886,6 +886,49 @@ int lrx_ivf_sq_fp16_ip_search(const void* codes, int64_t n_rows, int32_t dim, co
                               const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
 int lrx_ivf_sq_fp16_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim, const float* centroids, const int64_t* cells, int32_t nlist,
                                 void* codes, int64_t row0, void* stream);
+
+/* (added in ABI 9, additively) INVERTED FILE over 8-BIT SCALAR-QUANTISED codes: the exact top k, under the 8-bit store's score, over the rows of
+ * the cells a query probes -- the scan of faiss IndexIVFScalarQuantizer(quantizer, d, nlist, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT)
+ * (IVFSQ8Index).  The caller owns the coarse quantiser: it passes the probe lists and, with by_residual, the coarse scores.
+ *   cells, probes, ids, limits, errors, capture   lrx_ivf_sq_fp16_ip_search's, unchanged (the same host driver): list_off, row_ids, probes,
+ *               ld_probe, max_scan_rows, id_base and row_map keep their meaning; score descending, ties to the lower ORIGINAL row; (-FLT_MAX, -1)
+ *               padding; an entry < 0 is skipped; an entry >= nlist is NEVER dereferenced and is counted once in lrx_device_error_count; a cell
+ *               named twice by one query is scanned once for it (with the base term of its FIRST occurrence); a query whose cells hold more
+ *               than max_scan_rows returns padding and is counted once; a position whose original row is outside [0, n_rows) is dropped and
+ *               counted.  dim % 32 == 0, 32 <= dim <= 8192; by_residual with probe_scores == NULL is LRX_ERR_INVALID; a workspace under
+ *               lrx_ivf_sq8_ip_workspace_bytes (= lrx_ivf_flat_ip_workspace_bytes of the same arguments): LRX_ERR_WORKSPACE; argument errors
+ *               are reported before any device work; no allocation, no host synchronisation, one stream, kernels only.
+ *   qtype       0 (QT_8bit) or 2 (QT_8bit_uniform); anything else is LRX_ERR_INVALID, naming it.
+ *   trained     vmin ++ vdiff, fp32, 16-byte aligned: 2 dim floats for QT_8bit, 2 for QT_8bit_uniform -- lrx_sq8_ip_search's `trained`.
+ *   codes       uint8, ROW-MAJOR [n_rows, dim] by stored position, CELL BY CELL, dim bytes per row (not the tiled layout of lrx_sq8_ip_search);
+ *               the base pointer 16-byte aligned.  The code of v_i is lrx_sq8_encode's: u = fl32((v_i - vmin_i) / vdiff_i) (IEEE division),
+ *               u = 0 where vdiff_i == 0, where v_i is below the range or NaN, u clamped to 1, code = (int)(255.f * u) by truncation.  Without
+ *               centroids v = x; with them v_i = fl32(x_i - c_i), ONE fp32 subtraction of the centroid of the row's cell.
+ *   decoded     y_i = fl32(vmin_i + fl32(t * vdiff_i)), t = fl32(((float)code + 0.5f) / 255) with IEEE division, no contraction: lrx_sq8_decode_rows'.
+ *   score       of a scanned (query i, row) pair of the probed cell probes[i][j]:  (float)(B + sum_e (double)q_e * (double)y_e).  The sum is
+ *               exact_dot's: lane `sub` of a half-wave takes elements 4 sub + 128 u + 0..3 of each 2048-element block, fp64 accumulation,
+ *               the xor tree 16, 8, 4, 2, 1; B joins the reduced sum; ONE rounding.  B = 0 without by_residual; with it
+ *               B = (double)probe_scores[i * ld_probe + j].  So without by_residual the result equals lrx_ivf_flat_ip_search over the fp32 rows
+ *               that lrx_ivf_sq8_decode_rows returns, bit for bit, on any probe lists.
+ * The chain is lrx_ivf_flat_ip_search's six launches per chunk of queries; the scan walks groups of lrx_ivf_sq8_group_rows(dim) =
+ * min(128, 16384 / dim) consecutive code rows, loaded once (16 bytes per lane, non-temporal) and DECODED ONCE to fp32 in LDS (64 KiB), then
+ * scored against every query that probes the cell.
+ * lrx_ivf_sq8_encode_rows: one kernel -- code rows [row0, row0 + n) from x[i * ldx + e] (fp32; ldx >= dim, ldx % 4 == 0, 16-byte aligned) under
+ * the rule above; cells int64 [n] (device) and centroids fp32 [nlist, dim] contiguous (NULL: no residual, and then cells may be NULL).
+ * lrx_ivf_sq8_decode_rows: one kernel -- out[i * ldo + e] (fp32, ldo >= dim) = the decoded element of code row row0 + i, plus the centroid of
+ * cells[i] (ONE fp32 add) when centroids are given.  In both a cells[i] outside [0, nlist) is never dereferenced: the row's codes (or decoded
+ * row) are zeros and it is counted in lrx_device_error_count.  row0 + n < 2^32. */
+int32_t lrx_ivf_sq8_group_rows(int32_t dim);
+size_t lrx_ivf_sq8_ip_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int32_t k,
+                                      int64_t max_scan_rows);
+int lrx_ivf_sq8_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                          const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
+                          int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base,
+                          float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_sq8_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim, const float* centroids, const int64_t* cells, int32_t nlist,
+                            const float* trained, int32_t qtype, void* codes, int64_t row0, void* stream);
+int lrx_ivf_sq8_decode_rows(const void* codes, int64_t row0, int64_t n, int32_t dim, const float* trained, int32_t qtype, const float* centroids,
+                            const int64_t* cells, int32_t nlist, float* out, int64_t ldo, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

@@ -8,3 +8,4 @@ from .refine import RefineFlatIndex  # noqa: F401
 from .ivf import IVFFlatIndex  # noqa: F401
 from .ivfpq import IVFPQIndex  # noqa: F401
 from .ivfsq import IVFSQIndex  # noqa: F401
+from .ivfsq8 import IVFSQ8Index  # noqa: F401

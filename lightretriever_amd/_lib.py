@@ -95,6 +95,11 @@ SIGNATURES = {
     "lrx_ivf_sq_fp16_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_sq_fp16_ip_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "lrx_ivf_sq_fp16_encode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P]),
+    "lrx_ivf_sq8_group_rows": (_I32, [_I32]),
+    "lrx_ivf_sq8_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
+    "lrx_ivf_sq8_ip_search": (_I32, [_P, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_ivf_sq8_encode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _I64, _P]),
+    "lrx_ivf_sq8_decode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I64, _P]),
     "lrx_pq_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
     "lrx_pq_ip_chunk_queries": (_I32, [_I64, _I32, _I32, _I32, _I32]),
     "lrx_pq_ip_search": (_I32, [_P, _I64, _P, _I32, _I32, _P, _I32, _I32, _I64, _P, _P, _P, _P, _SZ, _I32, _P]),

@@ -1344,3 +1344,4 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
 #include "lrx_search_ivf.h"       // inverted file (faiss IndexIVFFlat): exact top-k over the rows of the probed cells, cell-major scan
 #include "lrx_search_ivfpq.h"     // inverted file over PQ codes (faiss IndexIVFPQ): ADC top-k over the rows of the probed cells, query-major scan
 #include "lrx_search_ivfsq.h"     // inverted file over fp16 codes (faiss IndexIVFScalarQuantizer, QT_fp16): the cell-major chain over 2-byte codes
+#include "lrx_search_ivfsq8.h"    // inverted file over 8-bit codes (faiss IndexIVFScalarQuantizer, QT_8bit[_uniform]): the chain over 1-byte codes, decoded once per group

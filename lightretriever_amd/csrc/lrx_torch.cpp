@@ -468,6 +468,53 @@ std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, cons
   return {o.d, o.i};
 }
 
+// Inverted file over 8-bit codes (lrx_ivf_sq8_ip_search): codes uint8 [n_rows, D] contiguous, row-major by stored position, cell by cell;
+// trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2); the rest as ivf_sq_fp16_ip_topk.  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
+                                                   const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                                                   const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
+                                                   int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  need(q, "q", at::kFloat, 2);
+  need(codes, "codes", at::kByte, 2);
+  need(trained, "trained", at::kFloat, 1);
+  need(list_off, "list_off", at::kLong, 1);
+  need(probes, "probes", at::kLong, 2);
+  const int64_t n_rows = codes.size(0), dim = codes.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
+  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && codes.is_contiguous() && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
+                  (nprobe == 0 || probes.stride(1) == 1),
+              "ivf_sq8_ip_topk: q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+  TORCH_CHECK((qtype == 0 || qtype == 2) && trained.is_contiguous() && trained.numel() == (qtype == 0 ? 2 * dim : 2),
+              "ivf_sq8_ip_topk: qtype ", qtype, " (0: QT_8bit, 2: QT_8bit_uniform) with trained fp32 [2 D] or [2] contiguous");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_sq8_ip_topk: sizes out of range");
+  const int64_t* ri = nullptr;
+  if (row_ids.has_value() && row_ids->defined()) {
+    need(*row_ids, "row_ids", at::kLong, 1);
+    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, "ivf_sq8_ip_topk: row_ids int64 [>= n_rows] contiguous");
+    ri = row_ids->data_ptr<int64_t>();
+  }
+  const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
+  const float* ps = nullptr;
+  if (by_residual) {
+    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), "ivf_sq8_ip_topk: by_residual needs probe_scores");
+    need(*probe_scores, "probe_scores", at::kFloat, 2);
+    TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
+                    (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
+                "ivf_sq8_ip_topk: probe_scores fp32 [Q, nprobe] with the row stride of probes");
+    ps = probe_scores->data_ptr<float>();
+  }
+  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_sq8_ip_topk: row_map int64 [>= n_rows] contiguous");
+  const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  TopK o = topk_out(q, k);
+  lrx_check(lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                  list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps,
+                                  (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                  o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
+            "ivf_sq8_ip_topk");
+  return {o.d, o.i};
+}
+
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
 // centroids [M, 256, D / M] fp32.  Returns (D, I).
 std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
@@ -751,6 +798,8 @@ TORCH_LIBRARY(lrx, m) {
         "bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("ivf_sq_fp16_ip_topk(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, bool by_residual, int k, "
         "int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_sq8_ip_topk(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
+        "bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
@@ -784,6 +833,7 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("ivf_flat_ip_topk", &ivf_flat_ip_topk);
   m.impl("ivf_pq_ip_topk", &ivf_pq_ip_topk);
   m.impl("ivf_sq_fp16_ip_topk", &ivf_sq_fp16_ip_topk);
+  m.impl("ivf_sq8_ip_topk", &ivf_sq8_ip_topk);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);

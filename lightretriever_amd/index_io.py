@@ -143,7 +143,21 @@ by_residual, write_InvertedLists), same source:
 
 Like 'IwFl' and 'IwPQ' it is **unverified against a Faiss build** (faiss is not installed here).  The reader accepts both list-size forms and
 refuses any other qtype, a non-empty direct map and other inverted lists by name; index_record_end knows the record, so a refine index can hold
-it as its base."""
+it as its base.
+
+An inverted-file 8-bit scalar-quantised index (IVFSQ8Index, faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit | QT_8bit_uniform,
+METRIC_INNER_PRODUCT)) is the same 'IwSq' record with the 8-bit ScalarQuantizer of 'IxSQ' above:
+
+    i32   qtype = 0 (QT_8bit) or 2 (QT_8bit_uniform),  i32 rangestat = 0,  f32 rangestat_arg = 0,  u64 d,  u64 code_size = d
+    u64   len(trained),  f32 trained[len(trained)]        (vmin ++ vdiff: 2 d floats for QT_8bit, 2 for QT_8bit_uniform)
+    u64   code_size = d
+    u8    by_residual
+    u32   fourcc 'ilar',  u64 nlist,  u64 code_size = d
+          the list sizes, 'full' or 'sprs', then for every non-empty cell: u8 codes[size][d] (row-major), i64 ids[size]
+
+It too is **unverified against a Faiss build**.  write_ivf_sq8 / read_ivf_sq8 serve it; read_ivf_sq keeps refusing qtype 0 / 2 and
+read_ivf_sq8 refuses qtype 4 pointing to read_ivf_sq; ivf_sq_qtype(fname) tells a caller which reader a record needs (as sq_qtype does for
+'IxSQ'), and index_record_end knows both lengths, so a refine index can hold either as its base."""
 from __future__ import annotations
 
 import csv
@@ -516,8 +530,8 @@ def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> 
     if fourcc == FOURCC_IVF_SQ:
         with open(fname, "rb") as f:
             f.seek(offset)
-            st = _read_ivf_sq_head(f, fname, size - offset)
-        return offset + st["data"] + st["ntotal"] * (2 * st["d"] + 8)
+            st = _read_ivf_sq_head(f, fname, size - offset, served="any")
+        return offset + st["data"] + st["ntotal"] * (st["code_size"] + 8)
     if fourcc not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
         raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ', 'IwSq')")
     with open(fname, "rb") as f:
@@ -842,9 +856,10 @@ def write_ivf_sq(fname: str, centroids: np.ndarray, list_sizes, codes, row_ids, 
         os.replace(tmp, fname)
 
 
-def _read_ivf_sq_head(f, fname: str, size: int):
+def _read_ivf_sq_head(f, fname: str, size: int, served: str = "fp16"):
     """An 'IwSq' record from the file position up to its list sizes (`size`: the bytes the record may fill) -> dict(d, nlist, nprobe, ntotal,
-    is_trained, by_residual, centroids, sizes, data: the record's bytes before the first cell's codes)."""
+    is_trained, by_residual, qtype, trained, code_size, centroids, sizes, data: the record's bytes before the first cell's codes).  served:
+    "fp16" (read_ivf_sq: QT_fp16 alone), "8bit" (read_ivf_sq8: QT_8bit / QT_8bit_uniform) or "any" (index_record_end: the three of them)."""
     start = f.tell()
 
     def take(n: int, what: str) -> bytes:
@@ -867,18 +882,28 @@ def _read_ivf_sq_head(f, fname: str, size: int):
     if dm_type != 0 or dm_n != 0:
         raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
     qtype, _, _, sq_d, sq_code = _SQ.unpack(take(_SQ.size, "scalar quantiser"))
-    if qtype != QT_FP16:
+    if served == "8bit" and qtype == QT_FP16:
+        raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} (QT_fp16) is not an 8-bit record: read it with read_ivf_sq (IVFSQIndex)")
+    if served != "fp16" and qtype not in (QT_FP16, QT_8BIT, QT_8BIT_UNIFORM):
+        raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served over cells (only QT_8bit = {QT_8BIT}, QT_8bit_uniform = "
+                         f"{QT_8BIT_UNIFORM} and QT_fp16 = {QT_FP16})")
+    if served == "fp16" and qtype != QT_FP16:
         raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} is not served over cells (only QT_fp16 = {QT_FP16})")
     (n_trained,) = struct.unpack("<Q", take(8, "trained size"))
+    want_code, want_trained = (2 * d, 0) if qtype == QT_FP16 else (d, _sq8_trained_len(qtype, d))
+    if sq_d != d or sq_code != want_code or n_trained != want_trained:
+        raise ValueError(f"{fname}: inconsistent IndexIVFScalarQuantizer quantiser (sq.d={sq_d}, sq.code_size={sq_code}, trained={n_trained}, "
+                         f"qtype={qtype}; d={d})")
+    trained = np.frombuffer(take(4 * n_trained, "trained"), dtype="<f4").copy()
     code_size, by_residual = struct.unpack("<QB", take(9, "code_size, by_residual"))
-    if sq_d != d or sq_code != 2 * d or n_trained != 0 or code_size != 2 * d or by_residual not in (0, 1):
+    if code_size != want_code or by_residual not in (0, 1):
         raise ValueError(f"{fname}: inconsistent IndexIVFScalarQuantizer quantiser (sq.d={sq_d}, sq.code_size={sq_code}, trained={n_trained}, "
                          f"code_size={code_size}, by_residual={by_residual}; d={d})")
     il = take(4, "inverted lists")
     if il != _ILAR:
         raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
     il_nlist, il_code = struct.unpack("<QQ", take(16, "inverted lists header"))
-    if il_nlist != nlist or il_code != 2 * d:
+    if il_nlist != nlist or il_code != want_code:
         raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, d={d}")
     form = take(4, "list sizes")
     (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
@@ -897,7 +922,7 @@ def _read_ivf_sq_head(f, fname: str, size: int):
     if int(sizes.sum()) != ntotal:
         raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}")
     return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), by_residual=bool(by_residual),
-                centroids=centroids, sizes=sizes, data=f.tell() - start)
+                qtype=int(qtype), trained=trained, code_size=int(want_code), centroids=centroids, sizes=sizes, data=f.tell() - start)
 
 
 def read_ivf_sq(fname: str, offset: int = 0, end: Optional[int] = None):
@@ -909,6 +934,8 @@ def read_ivf_sq(fname: str, offset: int = 0, end: Optional[int] = None):
         f.seek(offset)
         st = _read_ivf_sq_head(f, fname, size)
         ntotal, d, sizes = st["ntotal"], st["d"], st.pop("sizes")
+        for key in ("qtype", "trained", "code_size"):
+            st.pop(key)
         if st.pop("data") + ntotal * (2 * d + 8) != size:
             raise ValueError(f"{fname}: {ntotal} rows of {2 * d} + 8 bytes do not fill the record (bytes={size})")
         codes = np.empty((ntotal, d), dtype=np.float16)
@@ -920,6 +947,87 @@ def read_ivf_sq(fname: str, offset: int = 0, end: Optional[int] = None):
             row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
     st.update(list_off=list_off, codes=codes, row_ids=row_ids)
     return st
+
+
+def write_ivf_sq8(fname: str, centroids: np.ndarray, trained: np.ndarray, qtype: int, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True,
+                  is_trained: bool = True, prefix: bytes = b"", append: bool = False) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); trained fp32 vmin ++ vdiff (2 d floats for qtype QT_8bit = 0, 2 for QT_8bit_uniform = 2);
+    list_sizes [nlist]; codes uint8 [ntotal, d] row-major in CELL ORDER; row_ids int64 [ntotal], the original row (faiss's id) of each stored
+    position.  Written as faiss's 'IwSq' record with an 8-bit ScalarQuantizer (the layout at the head of this file; faiss is not installed here,
+    so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname; `prefix` / `append` as in _write_index."""
+    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
+    nlist, ntotal = sizes.shape[0], int(sizes.sum())
+    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
+    cent = np.ascontiguousarray(centroids, dtype="<f4")
+    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
+        raise ValueError(f"write_ivf_sq8: centroids {cent.shape} do not match nlist={nlist}")
+    d = cent.shape[1]
+    t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    if t.size != _sq8_trained_len(qtype, d):
+        raise ValueError(f"write_ivf_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8 or ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, d):
+        raise ValueError(f"write_ivf_sq8: {ids.shape[0]} row ids and codes {codes.dtype} {codes.shape}, the list sizes sum to {ntotal} (uint8, d={d})")
+    codes = np.ascontiguousarray(codes)
+    head = _index_header(FOURCC_IVF_SQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
+    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
+    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
+    head += _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes()   # the ScalarQuantizer and its `trained`
+    head += struct.pack("<QB", d, int(bool(by_residual)))              # code_size, by_residual
+    head += _ILAR + struct.pack("<QQ", nlist, d) + _list_sizes_bytes(sizes)
+    tmp = fname if append else fname + ".tmp"
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    with open(tmp, "ab" if append else "wb") as f:
+        f.write(prefix)
+        f.write(head)
+        for c in np.flatnonzero(sizes):
+            a, b = int(off[c]), int(off[c + 1])
+            f.write(codes[a:b].tobytes())
+            f.write(ids[a:b].tobytes())
+    if not append:
+        os.replace(tmp, fname)
+
+
+def read_ivf_sq8(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, qtype (0 / 2), trained fp32 [2 d] or [2], centroids fp32 [nlist, d] ([0, d] when
+    untrained), list_off int64 [nlist + 1], codes uint8 [ntotal, d] in cell order, row_ids int64 [ntotal]).  offset: where the record starts; it
+    runs to `end` (default: the end of the file).  Both list-size forms ('full', 'sprs') are read; another qtype (QT_fp16 = 4: that record is
+    read_ivf_sq's), a direct map and other inverted lists are refused by name."""
+    size = _end(fname, end) - offset
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        st = _read_ivf_sq_head(f, fname, size, served="8bit")
+        ntotal, d, sizes = st["ntotal"], st["d"], st.pop("sizes")
+        st.pop("code_size")
+        if st.pop("data") + ntotal * (d + 8) != size:
+            raise ValueError(f"{fname}: {ntotal} rows of {d} + 8 bytes do not fill the record (bytes={size})")
+        codes = np.empty((ntotal, d), dtype=np.uint8)
+        row_ids = np.empty(ntotal, dtype=np.int64)
+        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        for c in np.flatnonzero(sizes):
+            a, b = int(list_off[c]), int(list_off[c + 1])
+            codes[a:b] = np.frombuffer(f.read((b - a) * d), dtype=np.uint8).reshape(b - a, d)
+            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
+    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
+    return st
+
+
+def ivf_sq_qtype(fname: str, offset: int = 0, end: Optional[int] = None) -> int:
+    """The ScalarQuantizer qtype of an 'IwSq' record (faiss's enum: 0 8bit, 2 8bit_uniform, 4 fp16, ...), as sq_qtype for 'IxSQ': which of
+    read_ivf_sq (4) and read_ivf_sq8 (0, 2) the record needs.  The record is read up to its quantiser and no further."""
+    size = _end(fname, end) - offset
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        if size < 2 * _HEADER.size + 16 + 8:
+            raise ValueError(f"{fname}: too short for an inverted-file scalar-quantiser index header")
+        d, _, _, _ = _read_header(f, fname, FOURCC_IVF_SQ, "an inverted-file scalar-quantiser index")
+        f.seek(16, 1)                                                     # nlist, nprobe
+        _, qn, _, _ = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file scalar-quantiser index")
+        pos = f.tell() - offset + 8 + 4 * max(qn, 0) * max(d, 0) + 9      # the centroids, the direct map
+        if pos + 4 > size:
+            raise ValueError(f"{fname}: truncated inverted-file scalar-quantiser index (scalar quantiser)")
+        f.seek(offset + pos)
+        return struct.unpack("<i", f.read(4))[0]
 
 
 def save_dict_to_tsv(mapping: dict, output_path: str, keys: Optional[list] = None) -> None:

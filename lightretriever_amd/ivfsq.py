@@ -5,7 +5,7 @@ over lrx_ivf_sq_fp16_ip_search (csrc/lrx_search_ivfsq.h).
     D, I = idx.search(q, 100)            # the exact top 100, under the fp16 store's score, over the rows of each query's 32 best cells
 
 IVFFlatIndex's cells over SQFp16Index's codes: 2 bytes per element instead of 4, every scanned (query, row) pair scored exactly over the codes.
-With by_residual (faiss's default) a row is coded as its residual to its cell's centroid and a scanned row's score starts at the coarse score
+(8-bit codes over the same cells: IVFSQ8Index, ivfsq8.py.)  With by_residual (faiss's default) a row is coded as its residual to its cell's centroid and a scanned row's score starts at the coarse score
 of its cell; without, the codes and -- probing every cell -- the result are SQFp16Index's, bit for bit."""
 from __future__ import annotations
 

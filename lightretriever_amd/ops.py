@@ -385,3 +385,43 @@ def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Te
                                              _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
                                              int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
     return D, I
+
+
+def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
+                    probes: torch.Tensor, probe_scores: Optional[torch.Tensor], by_residual: bool, k: int, max_scan_rows: int, id_base: int = 0,
+                    row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None, capture_error: Optional[str] = None):
+    """lrx_ivf_sq8_ip_search -> (D f32[Q,k], I i64[Q,k]): the exact top k under the 8-bit store's score over the rows of the cells probes[i]
+    names.  q fp32 [Q, d] contiguous; codes uint8 [n, d] contiguous, row-major by stored position, cell by cell; trained fp32 vmin ++ vdiff
+    (2 d floats for qtype 0 = QT_8bit, 2 for qtype 2 = QT_8bit_uniform); list_off int64 [nlist + 1]; row_ids int64 [n] (original row of a
+    position) or None; probes int64 [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not
+    by_residual): a scanned row's score is its cell's probe score plus q . decoded row when by_residual, the product alone otherwise;
+    max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
+    from .index import _workspace
+    lib = _lib.lib()
+    Q, nprobe = probes.shape
+    nlist = list_off.numel() - 1
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
+        raise ValueError("ivf_sq8_ip_topk: codes must be uint8 [n, d] contiguous with q's d")
+    n, d = codes.shape
+    if qtype not in (0, 2) or trained.dtype != torch.float32 or not trained.is_contiguous() or trained.numel() != (2 * d if qtype == 0 else 2):
+        raise ValueError(f"ivf_sq8_ip_topk: qtype {qtype} (0: QT_8bit, 2: QT_8bit_uniform) needs trained fp32 [2 d] or [2] contiguous")
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError("ivf_sq8_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
+    if row_ids is not None and (row_ids.dtype != torch.int64 or not row_ids.is_contiguous() or row_ids.numel() < n):
+        raise ValueError("ivf_sq8_ip_topk: row_ids must be int64 [>= n] contiguous")
+    ld = probes.stride(0) if Q > 1 else nprobe
+    if by_residual:
+        if probe_scores is None or probe_scores.dtype != torch.float32 or probe_scores.shape != probes.shape or (nprobe and probe_scores.stride(1) != 1) or \
+                (Q > 1 and probe_scores.stride(0) != ld):
+            raise ValueError("ivf_sq8_ip_topk: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
+    if Q == 0:
+        return D, I
+    need = int(lib.lrx_ivf_sq8_ip_workspace_bytes(n, nlist, d, Q, nprobe, k, int(max_scan_rows)))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
+    _lib.check(lib.lrx_ivf_sq8_ip_search(_lib.ptr(codes) if n else None, n, d, _lib.ptr(trained), int(qtype), _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                         _lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld,
+                                         int(bool(by_residual)), int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws),
+                                         ws.numel(), _s()))
+    return D, I

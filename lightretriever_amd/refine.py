@@ -17,9 +17,10 @@ from . import _lib
 from .index import FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, _as_rows, _check_range, _workspace
 from .ivfpq import IVFPQIndex
 from .ivfsq import IVFSQIndex
+from .ivfsq8 import IVFSQ8Index
 from .transform import PreTransformIndex
 
-BASES = (PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex, IVFSQIndex)
+BASES = (PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex, IVFSQIndex, IVFSQ8Index)
 STORES = (FlatIPIndex, SQFp16Index)
 MAX_K_BASE = 2048         # candidates per query the rerank takes: the most any base search delivers
 
@@ -75,7 +76,7 @@ def rerank(q: torch.Tensor, store, cand: torch.Tensor, k: int, id_base: int = 0,
 class RefineFlatIndex:
     """faiss.IndexRefineFlat(base_index) / faiss.IndexRefine(base_index, refine_index): d, ntotal, device, is_trained (the base's), id_base
     (applied to the results only), k_factor; train / add / reset / reconstruct_n / append_slot / commit / search / save / load.
-    base_index: a PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex or IVFSQIndex with id_base 0 (this index owns the id offset); anything else:
+    base_index: a PQIndex, SQ8Index, SQFp16Index, PreTransformIndex, IVFPQIndex, IVFSQIndex or IVFSQ8Index with id_base 0 (this index owns the id offset); anything else:
     TypeError.  refine_index (the store): None -- a fresh FlatIPIndex(d) WITHOUT its fp16 shadow (the rows are gathered, never streamed:
     4 B/element, not 6) -- or a FlatIPIndex, or an SQFp16Index (2 B/element: faiss IndexRefine(base, IndexScalarQuantizer(QT_fp16))); same d
     (a PreTransformIndex's d is d_in) and the same ntotal as the base.  k_factor >= 1.
@@ -183,7 +184,7 @@ class RefineFlatIndex:
 
     @classmethod
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "RefineFlatIndex":
-        from .index_io import FOURCC_FLAT_IP, FOURCC_IVF_PQ, FOURCC_IVF_SQ, FOURCC_PQ, FOURCC_PRE_TRANSFORM, QT_FP16, read_refine
+        from .index_io import FOURCC_FLAT_IP, FOURCC_IVF_PQ, FOURCC_IVF_SQ, FOURCC_PQ, FOURCC_PRE_TRANSFORM, QT_FP16, ivf_sq_qtype, read_refine
         st = read_refine(fname)
         b, r = st["base"], st["store"]
         if b["fourcc"] == FOURCC_PQ:
@@ -193,7 +194,7 @@ class RefineFlatIndex:
         elif b["fourcc"] == FOURCC_IVF_PQ:
             base_cls = IVFPQIndex
         elif b["fourcc"] == FOURCC_IVF_SQ:
-            base_cls = IVFSQIndex
+            base_cls = IVFSQIndex if ivf_sq_qtype(fname, b["offset"], b["end"]) == QT_FP16 else IVFSQ8Index   # (each reader refuses the other's record by name)
         else:
             base_cls = SQFp16Index if b["qtype"] == QT_FP16 else SQ8Index
         base = base_cls.load(fname, device=device, offset=b["offset"], end=b["end"])

@@ -11,6 +11,7 @@
     IVFFaissSearch      (no counterpart in the reference)                (faiss IndexIVFFlat, inner product: IVFFlatIndex)
     IVFPQFaissSearch    (no counterpart in the reference)                (faiss IndexIVFPQ, inner product: IVFPQIndex)
     IVFSQFaissSearch    (no counterpart in the reference)                (faiss IndexIVFScalarQuantizer, QT_fp16, inner product: IVFSQIndex)
+    IVFSQ8FaissSearch   (no counterpart in the reference)                (faiss IndexIVFScalarQuantizer, QT_8bit / QT_8bit_uniform, inner product: IVFSQ8Index)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
     ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
@@ -39,6 +40,7 @@ from .sparse_rows import SparseRows, identity_term
 from .ivf import IVFFlatIndex
 from .ivfpq import IVFPQIndex
 from .ivfsq import IVFSQIndex
+from .ivfsq8 import IVFSQ8Index
 from .refine import RefineFlatIndex, check_k_factor, check_k_base
 from .transform import BASES as _PCA_BASES, PCAMatrix, PreTransformIndex
 
@@ -533,7 +535,7 @@ class IVFSQFaissSearch(FlatIPFaissSearch):
     """faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, quantizer_type, METRIC_INNER_PRODUCT) as a searcher, served by IVFSQIndex: every
     chunk is clustered into nlist k-means cells (at most its row count), its rows are stored as fp16 codes (of their residuals to the cell's
     centroid with by_residual) and a search scans the codes of each query's nprobe best cells, every scanned row scored exactly over its code.
-    quantizer_type: only "QT_fp16".  index() trains on the chunk and then adds it; _index_in_place trains on the encoded chunk when its staging
+    quantizer_type: only "QT_fp16" (the 8-bit types are IVFSQ8FaissSearch's).  index() trains on the chunk and then adds it; _index_in_place trains on the encoded chunk when its staging
     slot is committed.  load() takes nlist, nprobe and by_residual from the file.  Not served: other quantiser types, the L2 metric, shards on
     RPC workers."""
     index_cls = IVFSQIndex
@@ -569,18 +571,62 @@ class IVFSQFaissSearch(FlatIPFaissSearch):
         return "ivfsq_faiss_index"
 
 
+class IVFSQ8FaissSearch(FlatIPFaissSearch):
+    """faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT) ("IVF...,SQ8") as a searcher, served by
+    IVFSQ8Index: every chunk is clustered into nlist k-means cells (at most its row count), the range of the 8-bit quantiser is trained on the
+    chunk's residuals (its rows without by_residual), the rows are stored as 1-byte codes and a search scans the codes of each query's nprobe best
+    cells, every scanned row scored exactly over its decoded code.  quantizer_type: "QT_8bit" or "QT_8bit_uniform" ("QT_fp16" is
+    IVFSQFaissSearch's).  index() trains on the chunk and then adds it; _index_in_place trains on the encoded chunk when its staging slot is
+    committed.  load() takes nlist, nprobe, quantizer_type and by_residual from the file.  Not served: other quantiser types, the L2 metric,
+    shards on RPC workers."""
+    index_cls = IVFSQ8Index
+    index_ext = "ivfsq8"
+    serves_rpc_shards = False
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32,
+                 quantizer_type: str = "QT_8bit", by_residual: bool = True, similarity_metric=0, **kwargs):
+        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
+            raise NotImplementedError(f"IVFSQ8FaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        if quantizer_type == "QT_fp16":
+            raise NotImplementedError("IVFSQ8FaissSearch: quantizer_type 'QT_fp16' is served by IVFSQFaissSearch (faiss_search_map='ivfsq')")
+        if quantizer_type not in ("QT_8bit", "QT_8bit_uniform"):
+            raise NotImplementedError(f"IVFSQ8FaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_8bit' and 'QT_8bit_uniform')")
+        if nlist < 1 or nprobe < 1:
+            raise ValueError(f"IVFSQ8FaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.nlist, self.nprobe = int(nlist), int(nprobe)
+        self.quantizer_type, self.by_residual = quantizer_type, bool(by_residual)
+        self.similarity_metric = 0
+
+    def _new_index(self, dim: int, capacity: int) -> IVFSQ8Index:
+        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
+        return IVFSQ8Index(dim, nlist, self.quantizer_type, nprobe=min(self.nprobe, nlist, 2048), by_residual=self.by_residual, capacity=capacity)
+
+    def _train(self, idx: IVFSQ8Index, corpus_emb):
+        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        idx = self.faiss_index.index
+        self.nlist, self.nprobe, self.quantizer_type, self.by_residual = idx.nlist, idx.nprobe, idx.qtype, idx.by_residual
+
+    def get_index_name(self):
+        return "ivfsq8_faiss_index"
+
+
 class RefineFaissSearch(FlatIPFaissSearch):
     """faiss IndexRefineFlat(base) / IndexRefine(base, IndexScalarQuantizer(QT_fp16)) as a searcher, served by RefineFlatIndex: every chunk is
     indexed twice -- into a lossy base shard and into a full-precision row store -- and searched in two stages: the base's top
-    int(top_k * k_factor) rows, rescored exactly from the store, best top_k.  refine_base: "pq", "sq", "pca", "ivfpq" or "ivfsq" -- the searcher (PQFaissSearch,
-    SQFaissSearch, PCAFaissSearch, IVFPQFaissSearch, IVFSQFaissSearch) whose shard is the base; its own arguments go through **kwargs unchanged, so its refusals (use_rotation,
+    int(top_k * k_factor) rows, rescored exactly from the store, best top_k.  refine_base: "pq", "sq", "pca", "ivfpq", "ivfsq" or "ivfsq8" -- the searcher (PQFaissSearch,
+    SQFaissSearch, PCAFaissSearch, IVFPQFaissSearch, IVFSQFaissSearch, IVFSQ8FaissSearch) whose shard is the base; its own arguments go through **kwargs unchanged, so its refusals (use_rotation,
     QT_8bit, random_rotation, ...) apply unchanged, and so does PCAFaissSearch's reuse of the first chunk's matrix.  refine_type: "flat" (fp32
     rows without a shadow, 4 B/element) or "fp16" (SQFp16Index codes, 2 B/element).  index / _index_in_place / load / save behave like
     FlatIPFaissSearch's with that shard; load() takes k_factor and the shard classes from the file.  Not served: shards on RPC workers."""
     index_cls = RefineFlatIndex
     index_ext = "refine"
     serves_rpc_shards = False
-    BASE_SEARCHERS = {"pq": PQFaissSearch, "sq": SQFaissSearch, "pca": PCAFaissSearch, "ivfpq": IVFPQFaissSearch, "ivfsq": IVFSQFaissSearch}
+    BASE_SEARCHERS = {"pq": PQFaissSearch, "sq": SQFaissSearch, "pca": PCAFaissSearch, "ivfpq": IVFPQFaissSearch, "ivfsq": IVFSQFaissSearch,
+                      "ivfsq8": IVFSQ8FaissSearch}
 
     def __init__(self, model, refine_base: Optional[str] = None, k_factor: float = 1.0, refine_type: str = "flat", batch_size: int = 128,
                  corpus_chunk_size: Optional[int] = None, **kwargs):
@@ -824,19 +870,21 @@ class HybridSearch:
         self.convert_to_tensor = kwargs.get("convert_to_tensor", True)
         # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank),
         # "pca" (IndexPreTransform(PCAMatrix, base)), "refine" (IndexRefineFlat over a pq / sq / pca / ivfpq / ivfsq base), "ivf" (IndexIVFFlat), "ivfpq"
-        # (IndexIVFPQ) and "ivfsq" (IndexIVFScalarQuantizer, QT_fp16) are served;
+        # (IndexIVFPQ), "ivfsq" (IndexIVFScalarQuantizer, QT_fp16) and "ivfsq8" (IndexIVFScalarQuantizer, QT_8bit / QT_8bit_uniform) are served;
         # anything else ("hnsw", "hnswsq") is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
         den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch,
-                   "refine": RefineFaissSearch, "ivf": IVFFaissSearch, "ivfpq": IVFPQFaissSearch, "ivfsq": IVFSQFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine", "ivf", "ivfpq", "ivfsq"):
+                   "refine": RefineFaissSearch, "ivf": IVFFaissSearch, "ivfpq": IVFPQFaissSearch, "ivfsq": IVFSQFaissSearch,
+                   "ivfsq8": IVFSQ8FaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine", "ivf", "ivfpq", "ivfsq", "ivfsq8"):
             logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
         # (the reference passes its **kwargs through to the searcher)
         passed = {"pq": ("num_of_centroids", "code_size", "use_rotation", "similarity_metric"), "sq": ("quantizer_type", "similarity_metric"),
                   "binary": ("binary_k", "threshold"), "pca": ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation"),
                   "ivf": ("nlist", "nprobe", "similarity_metric"),
                   "ivfpq": ("nlist", "nprobe", "num_of_centroids", "code_size", "by_residual", "similarity_metric"),
-                  "ivfsq": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric")}
+                  "ivfsq": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric"),
+                  "ivfsq8": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric")}
         den_kwargs = {a: kwargs[a] for a in passed.get(faiss_search_map, ()) if a in kwargs}
         if faiss_search_map == "pca" and kwargs.get("output_dimension") is None:
             raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
