@@ -368,6 +368,47 @@ int lrx_row_rscale(const void* x, int32_t rows, int32_t hidden_size, float eps, 
 int lrx_finalize_rscale(const float* ss_part, int32_t n_parts, int32_t rows, int32_t hidden_size, float eps, float* rscale_out,
                         void* stream);
 
+/* (added in ABI 9, additively) The FP16-OPERAND forms of the encoder kernels: what lrx_encode_* launches under lrx_encoder_config.precise_stream
+ * = 2 (every projection) and = 3 (the QKV projection only), exported so that each can be tested on its own.  Each is the entry point named
+ * with one or two format flags more; with every flag 0 it IS that entry point (same kernel, same bits).  "fp16 operand" means: the 16-bit
+ * elements of that matrix are IEEE binary16 instead of bf16, multiplied on the f16 MFMA with fp32 accumulation; biases, norm weights (gamma)
+ * and the embedding table stay bf16 in every mode.
+ * The fp16 STORE RULE of the GEMM and embedding outputs: one rounding (to nearest even) of the fp32 value, SATURATING -- a value beyond
+ * +-65504 is stored as +-65504 by sign, a NaN as -65504 -- and every such event is counted by lrx_device_saturation_count (the GEMMs: once per
+ * wave instruction that saw any; the embedding: once per element).  No inf and no NaN is ever stored.
+ *   lrx_gemm_nt_fused_ex        lrx_gemm_bf16_nt_fused; f16 != 0: A and B are fp16 and C [M, N / 2] is written as fp16 under the store rule.
+ *                               Served for epilogue 2 (SwiGLU) only: f16 != 0 with epilogue 0 or 1 is LRX_ERR_INVALID, nothing is written.
+ *   lrx_gemm_qkv_rope_slice_ex  lrx_gemm_qkv_rope_slice; f16 != 0: A and Wqkv are fp16 (bias bf16, rscale / cos / sin fp32).  C is fp16 under
+ *                               the store rule either way.
+ *   lrx_gemm_nt_resid32_ex      lrx_gemm_bf16_nt_resid32; f16 != 0: A and B are fp16 (x32 fp32 and gamma bf16 as before); out_f16 != 0:
+ *                               a16_out = fp16(x32 * gamma[n]) under the store rule instead of bf16(..).  The two flags are independent
+ *                               except that fp16 operands never write a bf16 operand: f16 != 0 with out_f16 == 0 and a16_out != NULL is
+ *                               LRX_ERR_INVALID, nothing is written.  (precise_stream = 3 runs its down-projection with f16 = 0, out_f16 = 1.)
+ *   lrx_embed_stream32_ex       lrx_embed_stream32; f16 != 0: a16 = fp16(x32 * gamma) under the store rule (the product of two bf16 numbers is
+ *                               exact in fp32: one rounding in all).  x32 and rscale_out do not depend on the flag.
+ *   lrx_attn_varlen_causal_ex   lrx_attn_varlen_causal (items == NULL, items_bytes ignored) / lrx_attn_varlen_causal_items (items != NULL);
+ *                               out_f16 != 0: `out` is written as fp16.
+ *   lrx_attn_prefix_suffix_ex   lrx_attn_prefix_suffix; out_f16 != 0: `out` is written as fp16.
+ * The attention store is one rounding of the fp32 value and is NOT saturating: a row of the output is a convex combination of rows of v,
+ * |o| <= max |v|, up to the rounding of the probabilities -- the kernels form (sum fp16(p_i) v_i) / (sum p_i), at most (1 + 2^-11) max |v| --
+ * so it is finite for every max |v| <= 65472, the second largest fp16 number, and nothing is counted.  Only v = +-65504 itself can be stored
+ * as inf; lrx_gemm_qkv_rope* writes that value only where it saturated, and counted it.  qkv / prefix_kv are fp16 in every mode.
+ * Every other refusal is the one of the entry point without the flags.                                                                      */
+int lrx_gemm_nt_fused_ex(const void* A, const void* B, void* C, const void* bias, const void* resid, int32_t M, int32_t N, int32_t K,
+                         int32_t epilogue, const float* rscale, float* ss_part, int32_t f16, void* stream);
+int lrx_gemm_qkv_rope_slice_ex(const void* A, const void* Wqkv, void* C, const void* bias, const int32_t* positions, const float* cos,
+                               const float* sin, int32_t M, int32_t K, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                               const float* rscale, int32_t head0, int32_t n_heads, int32_t f16, void* stream);
+int lrx_gemm_nt_resid32_ex(const void* A, const void* B, float* x32, void* a16_out, const void* gamma, int32_t M, int32_t N, int32_t K,
+                           float* ss_part, int32_t f16, int32_t out_f16, void* stream);
+int lrx_embed_stream32_ex(const void* table, const int32_t* ids, int32_t n_tokens, int32_t hidden, int32_t vocab, const void* gamma,
+                          float* x32, void* a16, float* rscale_out, float eps, int32_t f16, void* stream);
+int lrx_attn_varlen_causal_ex(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs,
+                              int32_t total_tokens, int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                              void* out, int32_t last_tile_only, int32_t out_f16, void* stream);
+int lrx_attn_prefix_suffix_ex(const void* qkv, const void* prefix_kv, int32_t n_seqs, int32_t suffix_len, int32_t prefix_len,
+                              int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out, int32_t out_f16, void* stream);
+
 /* dst[b, :] = src[cu_seqlens[b+1]-1, :]  (bf16 rows of `width` elements): the last-token rows, compacted. */
 int lrx_gather_last_rows(const void* src, const int32_t* cu_seqlens, int32_t n_seqs, int32_t width, void* dst, void* stream);
 /* (ABI 6) the inverse: dst[cu_seqlens[b+1]-1, 0:width] = src[b, 0:width]  (16-bit elements; rows of dst are dst_row_stride elements apart) */

@@ -127,6 +127,13 @@ SIGNATURES = {
     "lrx_gemm_bf16_nt_resid32": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P]),
     "lrx_embed_stream32": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _F, _P]),
     "lrx_rmsnorm_f32": (_I32, [_P, _P, _P, _I32, _I32, _F, _P]),
+    # the fp16-operand forms (precise_stream = 2 / 3): the entry point named + format flags
+    "lrx_gemm_nt_fused_ex": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _I32, _P]),
+    "lrx_gemm_qkv_rope_slice_ex": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _P]),
+    "lrx_gemm_nt_resid32_ex": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "lrx_embed_stream32_ex": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _F, _I32, _P]),
+    "lrx_attn_varlen_causal_ex": (_I32, [_P, _P, _P, _SZ, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "lrx_attn_prefix_suffix_ex": (_I32, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P]),
     "lrx_gemm_bf16_nt_fused": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "lrx_gemm_qkv_rope_fused": (_I32, [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
     "lrx_row_rscale": (_I32, [_P, _I32, _I32, C.c_float, _P, _P]),

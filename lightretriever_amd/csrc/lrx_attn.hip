@@ -53,7 +53,9 @@ constexpr int attn_dma_waves(int insts, int nw) {   // largest divisor of insts 
   return d;
 }
 
-// the 16-bit output element: bf16, or (out_f16, the precise stream's fp16 GEMM operands) fp16 -- |o| <= max |v| <= 65504: no saturation to count
+// the 16-bit output element: bf16, or (out_f16, the precise stream's fp16 GEMM operands) fp16 -- |o| <= (1 + 2^-11) max |v| (the numerator sums
+// fp16-rounded probabilities, the row sum the unrounded ones): finite for every max |v| <= 65472, no saturation to count; v = +-65504 itself -- which
+// the QKV store writes only where it saturated, and counted -- can round to inf (include/lrx.h; tests/test_gpu_attn_reference.py pins both)
 __device__ __forceinline__ __bf16 o16(float v, int out_f16) { return out_f16 ? __builtin_bit_cast(__bf16, (_Float16)v) : f2bf(v); }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1120,8 +1122,8 @@ extern "C" int lrx_attn_prefix_suffix(const void* qkv, const void* prefix_kv, in
   return lrx_attn_prefix_suffix_ex(qkv, prefix_kv, n_seqs, suffix_len, prefix_len, num_q_heads, num_kv_heads, head_dim, out, 0, stream);
 }
 // (out_f16 != 0: the output rows are written as fp16 -- the O-projection's operand under lrx_encoder_config.precise_stream = 2)
-int lrx_attn_prefix_suffix_ex(const void* qkv, const void* prefix_kv, int32_t n_seqs, int32_t suffix_len, int32_t prefix_len, int32_t num_q_heads,
-                              int32_t num_kv_heads, int32_t head_dim, void* out, int out_f16, void* stream) {
+extern "C" int lrx_attn_prefix_suffix_ex(const void* qkv, const void* prefix_kv, int32_t n_seqs, int32_t suffix_len, int32_t prefix_len, int32_t num_q_heads,
+                                         int32_t num_kv_heads, int32_t head_dim, void* out, int32_t out_f16, void* stream) {
   LRX_CHECK_ARG(head_dim == 64 || head_dim == 128, "attn_prefix: head_dim=%d unsupported", head_dim);
   LRX_CHECK_ARG(num_kv_heads > 0 && num_q_heads % num_kv_heads == 0 && num_q_heads / num_kv_heads <= 8, "attn_prefix: bad head counts");
   LRX_CHECK_ARG(suffix_len > 0 && prefix_len >= 0, "attn_prefix: bad lengths");
@@ -1281,9 +1283,9 @@ extern "C" int lrx_attn_varlen_causal_items(const void* qkv, const int32_t* cu_s
 }
 // items == nullptr: the tiled kernel walks its items itself (attn_next_item), otherwise it reads them from the list lrx_attn_build_items wrote.
 // (out_f16 != 0: the output rows are written as fp16 -- the O-projection's operand under lrx_encoder_config.precise_stream = 2)
-int lrx_attn_varlen_causal_ex(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs, int32_t total_tokens,
-                              int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out, int32_t last_tile_only,
-                              int out_f16, void* stream) {
+extern "C" int lrx_attn_varlen_causal_ex(const void* qkv, const int32_t* cu_seqlens, const void* items, size_t items_bytes, int32_t n_seqs, int32_t total_tokens,
+                                         int32_t max_seqlen, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, void* out, int32_t last_tile_only,
+                                         int32_t out_f16, void* stream) {
   int rc = attn_check_layout(num_q_heads, num_kv_heads, head_dim);
   if (rc) return rc;
   LRX_CHECK_ARG(max_seqlen > 0 || total_tokens == 0, "attn: max_seqlen must be > 0");

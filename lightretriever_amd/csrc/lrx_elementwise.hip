@@ -84,8 +84,8 @@ extern "C" int lrx_embed_stream32(const void* table, const int32_t* ids, int32_t
                                   float* x32, void* a16, float* rscale_out, float eps, void* stream) {
   return lrx_embed_stream32_ex(table, ids, n_tokens, hidden, vocab, gamma, x32, a16, rscale_out, eps, 0, stream);
 }
-int lrx_embed_stream32_ex(const void* table, const int32_t* ids, int32_t n_tokens, int32_t hidden, int32_t vocab, const void* gamma, float* x32, void* a16,
-                          float* rscale_out, float eps, int f16, void* stream) {
+extern "C" int lrx_embed_stream32_ex(const void* table, const int32_t* ids, int32_t n_tokens, int32_t hidden, int32_t vocab, const void* gamma, float* x32, void* a16,
+                                     float* rscale_out, float eps, int32_t f16, void* stream) {
   LRX_CHECK_ARG(hidden % 8 == 0 && n_tokens >= 0 && vocab > 0 && gamma && x32 && a16 && rscale_out, "embed_stream32: bad operand");
   if (n_tokens == 0) return LRX_OK;
   if (f16)

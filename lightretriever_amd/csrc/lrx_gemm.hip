@@ -713,8 +713,8 @@ extern "C" int lrx_gemm_bf16_nt_fused(const void* A, const void* B, void* C, con
 }
 
 // (f16 != 0: fp16 operands, SwiGLU epilogue only -- the gate-up projection of precise_stream = 2; the output is fp16 then)
-int lrx_gemm_nt_fused_ex(const void* A, const void* B, void* C, const void* bias, const void* resid, int32_t M, int32_t N, int32_t K, int32_t epilogue,
-                         const float* rscale, float* ss_part, int f16, void* stream) {
+extern "C" int lrx_gemm_nt_fused_ex(const void* A, const void* B, void* C, const void* bias, const void* resid, int32_t M, int32_t N, int32_t K, int32_t epilogue,
+                                    const float* rscale, float* ss_part, int32_t f16, void* stream) {
   LRX_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm: bad shape M=%d N=%d K=%d", M, N, K);
   LRX_CHECK_ARG(!f16 || epilogue == EPI_SWIGLU, "gemm: fp16 operands are served for the SwiGLU epilogue (epilogue %d)", epilogue);
   LRX_CHECK_ARG(K % GBK == 0, "gemm: K=%d must be a multiple of %d", K, GBK);
@@ -769,9 +769,9 @@ extern "C" int lrx_gemm_qkv_rope_slice(const void* A, const void* Wqkv, void* C,
 }
 
 // (f16 != 0: A and Wqkv hold fp16 values -- precise_stream = 2; the bias stays bf16, the output is fp16 either way)
-int lrx_gemm_qkv_rope_slice_ex(const void* A, const void* Wqkv, void* C, const void* bias, const int32_t* positions, const float* cos, const float* sin,
-                               int32_t M, int32_t K, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, const float* rscale, int32_t head0,
-                               int32_t n_heads, int f16, void* stream) {
+extern "C" int lrx_gemm_qkv_rope_slice_ex(const void* A, const void* Wqkv, void* C, const void* bias, const int32_t* positions, const float* cos, const float* sin,
+                                          int32_t M, int32_t K, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, const float* rscale, int32_t head0,
+                                          int32_t n_heads, int32_t f16, void* stream) {
   const int n_all = num_q_heads + 2 * num_kv_heads;
   LRX_CHECK_ARG(M >= 0 && K > 0 && K % GBK == 0, "gemm_qkv_rope: bad shape M=%d K=%d", M, K);
   LRX_CHECK_ARG(head_dim == 64 || head_dim == 128, "gemm_qkv_rope: head_dim=%d unsupported", head_dim);
@@ -806,8 +806,8 @@ extern "C" int lrx_gemm_bf16_nt_resid32(const void* A, const void* B, float* x32
 
 // (f16 != 0: A and B hold fp16 values -- precise_stream = 2; out_f16 != 0: a16_out = fp16(x32 * gamma) -- always with f16, and for the GEMM that feeds the
 // QKV projection under precise_stream = 3; gamma stays bf16)
-int lrx_gemm_nt_resid32_ex(const void* A, const void* B, float* x32, void* a16_out, const void* gamma, int32_t M, int32_t N, int32_t K, float* ss_part,
-                           int f16, int out_f16, void* stream) {
+extern "C" int lrx_gemm_nt_resid32_ex(const void* A, const void* B, float* x32, void* a16_out, const void* gamma, int32_t M, int32_t N, int32_t K, float* ss_part,
+                                      int32_t f16, int32_t out_f16, void* stream) {
   LRX_CHECK_ARG(!f16 || out_f16 || a16_out == nullptr, "gemm_resid32: fp16 operands write an fp16 operand");
   LRX_CHECK_ARG(M >= 0 && N > 0 && K > 0 && K % GBK == 0 && N % 8 == 0, "gemm_resid32: bad shape M=%d N=%d K=%d", M, N, K);
   LRX_CHECK_ARG(x32 != nullptr, "gemm_resid32: null residual stream");

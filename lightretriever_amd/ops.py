@@ -35,15 +35,38 @@ def gemm_bf16_nt(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] 
     return out
 
 
+def _operand_flag(operands: str, what: str, *tensors) -> int:
+    """"bf16" -> 0, "fp16" -> 1 (the f16 flag of the lrx_*_ex entry points); the 16-bit operands must hold that format"""
+    if operands not in ("bf16", "fp16"):
+        raise ValueError(f"{what}: operands must be 'bf16' or 'fp16', not {operands!r}")
+    want = torch.float16 if operands == "fp16" else torch.bfloat16
+    for t in tensors:
+        if t.dtype != want:
+            raise TypeError(f"{what}: operands={operands!r} takes {want} matrices, got {t.dtype}")
+    return int(operands == "fp16")
+
+
+def _a16_flag(a16_dtype, what: str) -> int:
+    if a16_dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: the 16-bit output is torch.bfloat16 or torch.float16, not {a16_dtype}")
+    return int(a16_dtype == torch.float16)
+
+
 def gemm_bf16_nt_fused(A: torch.Tensor, B: torch.Tensor, bias: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None, epilogue: int = 0,
-                       rscale: Optional[torch.Tensor] = None, want_ss: bool = False):
-    """lrx_gemm_bf16_nt_fused: -> (out bf16, ss_part fp32 [ceil(N/256), M] or None)."""
+                       rscale: Optional[torch.Tensor] = None, want_ss: bool = False, operands: str = "bf16", out: Optional[torch.Tensor] = None):
+    """lrx_gemm_bf16_nt_fused: -> (out bf16, ss_part fp32 [ceil(N/256), M] or None).  operands="fp16" (lrx_gemm_nt_fused_ex, SwiGLU epilogue
+    only): A and B hold fp16 and `out` is fp16, saturating.  out: a contiguous tensor of the result's shape and dtype to write into."""
+    f16 = _operand_flag(operands, "gemm_bf16_nt_fused", A, B)
     M, K = A.shape
     N = B.shape[0]
-    out = torch.empty(M, N // 2 if epilogue == 2 else N, dtype=torch.bfloat16, device=A.device)
+    shape, dtype = (M, N // 2 if epilogue == 2 else N), (torch.float16 if f16 else torch.bfloat16)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=A.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"gemm_bf16_nt_fused: out must be contiguous {dtype} {list(shape)}")
     ss = torch.full(((N + 255) // 256, M), float("nan"), dtype=torch.float32, device=A.device) if want_ss else None
-    _lib.check(_lib.lib().lrx_gemm_bf16_nt_fused(_lib.ptr(A), _lib.ptr(B), _lib.ptr(out), _lib.ptr(bias), _lib.ptr(resid), M, N, K, epilogue,
-                                                 _lib.ptr(rscale), _lib.ptr(ss), _s()))
+    _lib.check(_lib.lib().lrx_gemm_nt_fused_ex(_lib.ptr(A), _lib.ptr(B), _lib.ptr(out), _lib.ptr(bias), _lib.ptr(resid), M, N, K, epilogue,
+                                               _lib.ptr(rscale), _lib.ptr(ss), f16, _s()))
     return out, ss
 
 
@@ -82,35 +105,44 @@ def gemm_qkv_rope(A: torch.Tensor, Wqkv: torch.Tensor, positions: torch.Tensor, 
 
 def gemm_qkv_rope_slice(A: torch.Tensor, Wqkv: torch.Tensor, positions: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, nq: int, nkv: int,
                         d: int, head0: int, n_heads: int, out: torch.Tensor, bias: Optional[torch.Tensor] = None,
-                        rscale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        rscale: Optional[torch.Tensor] = None, operands: str = "bf16") -> torch.Tensor:
     """lrx_gemm_qkv_rope_slice: heads [head0, head0 + n_heads) of the projection (Wqkv / bias are the FULL matrices) into their columns of
-    `out`, fp16 [M, (nq+2nkv)d]; every other column of `out` is left alone."""
+    `out`, fp16 [M, (nq+2nkv)d]; every other column of `out` is left alone.  operands="fp16" (lrx_gemm_qkv_rope_slice_ex): A and Wqkv hold
+    fp16; the bias stays bf16."""
+    f16 = _operand_flag(operands, "gemm_qkv_rope_slice", A, Wqkv)
     M, K = A.shape
     if out.dtype != torch.float16 or out.shape != (M, (nq + 2 * nkv) * d) or not out.is_contiguous():
         raise ValueError("gemm_qkv_rope_slice: out must be contiguous fp16 [M, (nq+2nkv)d]")
-    _lib.check(_lib.lib().lrx_gemm_qkv_rope_slice(_lib.ptr(A), _lib.ptr(Wqkv), _lib.ptr(out), _lib.ptr(bias), _lib.ptr(positions), _lib.ptr(cos),
-                                                  _lib.ptr(sin), M, K, nq, nkv, d, _lib.ptr(rscale), head0, n_heads, _s()))
+    _lib.check(_lib.lib().lrx_gemm_qkv_rope_slice_ex(_lib.ptr(A), _lib.ptr(Wqkv), _lib.ptr(out), _lib.ptr(bias), _lib.ptr(positions), _lib.ptr(cos),
+                                                     _lib.ptr(sin), M, K, nq, nkv, d, _lib.ptr(rscale), head0, n_heads, f16, _s()))
     return out
 
 
-def gemm_resid32(A: torch.Tensor, B: torch.Tensor, x32: torch.Tensor, gamma: Optional[torch.Tensor] = None, want_a16: bool = True, want_ss: bool = False):
-    """lrx_gemm_bf16_nt_resid32: x32 (fp32 [M,N], in place) += A . B^T -> (a16 bf16 [M,N] = bf16(x32 * gamma) or None, ss_part or None)."""
+def gemm_resid32(A: torch.Tensor, B: torch.Tensor, x32: torch.Tensor, gamma: Optional[torch.Tensor] = None, want_a16: bool = True, want_ss: bool = False,
+                 operands: str = "bf16", a16_dtype=torch.bfloat16):
+    """lrx_gemm_bf16_nt_resid32: x32 (fp32 [M,N], in place) += A . B^T -> (a16 bf16 [M,N] = bf16(x32 * gamma) or None, ss_part or None).
+    operands="fp16" / a16_dtype=torch.float16 (lrx_gemm_nt_resid32_ex): A and B hold fp16 / a16 = fp16(x32 * gamma), saturating; fp16
+    operands with a bf16 a16 are refused."""
+    f16, out_f16 = _operand_flag(operands, "gemm_resid32", A, B), _a16_flag(a16_dtype, "gemm_resid32")
     M, K = A.shape
     N = B.shape[0]
-    a16 = torch.empty(M, N, dtype=torch.bfloat16, device=A.device) if want_a16 else None
+    a16 = torch.empty(M, N, dtype=a16_dtype, device=A.device) if want_a16 else None
     ss = torch.full(((N + 255) // 256, M), float("nan"), dtype=torch.float32, device=A.device) if want_ss else None
-    _lib.check(_lib.lib().lrx_gemm_bf16_nt_resid32(_lib.ptr(A), _lib.ptr(B), _lib.ptr(x32), _lib.ptr(a16), _lib.ptr(gamma), M, N, K, _lib.ptr(ss), _s()))
+    _lib.check(_lib.lib().lrx_gemm_nt_resid32_ex(_lib.ptr(A), _lib.ptr(B), _lib.ptr(x32), _lib.ptr(a16), _lib.ptr(gamma), M, N, K, _lib.ptr(ss), f16, out_f16,
+                                                 _s()))
     return a16, ss
 
 
-def embed_stream32(table: torch.Tensor, ids: torch.Tensor, gamma: torch.Tensor, eps: float):
-    """lrx_embed_stream32 -> (x32 fp32 [T,H], a16 bf16 [T,H], rscale fp32 [T])."""
+def embed_stream32(table: torch.Tensor, ids: torch.Tensor, gamma: torch.Tensor, eps: float, a16_dtype=torch.bfloat16):
+    """lrx_embed_stream32 -> (x32 fp32 [T,H], a16 bf16 [T,H], rscale fp32 [T]).  a16_dtype=torch.float16 (lrx_embed_stream32_ex): a16 =
+    fp16(x32 * gamma), saturating."""
+    f16 = _a16_flag(a16_dtype, "embed_stream32")
     T, H = ids.numel(), table.shape[1]
     x32 = torch.empty(T, H, dtype=torch.float32, device=table.device)
-    a16 = torch.empty(T, H, dtype=torch.bfloat16, device=table.device)
+    a16 = torch.empty(T, H, dtype=a16_dtype, device=table.device)
     rs = torch.empty(T, dtype=torch.float32, device=table.device)
-    _lib.check(_lib.lib().lrx_embed_stream32(_lib.ptr(table), _lib.ptr(ids), T, H, table.shape[0], _lib.ptr(gamma), _lib.ptr(x32), _lib.ptr(a16), _lib.ptr(rs),
-                                             float(eps), _s()))
+    _lib.check(_lib.lib().lrx_embed_stream32_ex(_lib.ptr(table), _lib.ptr(ids), T, H, table.shape[0], _lib.ptr(gamma), _lib.ptr(x32), _lib.ptr(a16), _lib.ptr(rs),
+                                                float(eps), f16, _s()))
     return x32, a16, rs
 
 
@@ -138,36 +170,41 @@ def attn_work_list(cu_seqlens: torch.Tensor, total_tokens: int, max_seqlen: int,
 
 
 def attn_varlen_causal(qkv: torch.Tensor, cu_seqlens: torch.Tensor, max_seqlen: int, nq: int, nkv: int, d: int,
-                       last_tile_only: bool = False, work_list=None) -> torch.Tensor:
+                       last_tile_only: bool = False, work_list=None, out_dtype=torch.bfloat16) -> torch.Tensor:
     """work_list: None -> built here (one extra small launch); a tensor from `attn_work_list` with the SAME layout arguments; False -> the
-    launch without a list (`lrx_attn_varlen_causal`: the same kernel walks its items itself; same bits, ~5 % longer on the tiled path)."""
+    launch without a list (`lrx_attn_varlen_causal`: the same kernel walks its items itself; same bits, ~5 % longer on the tiled path).
+    out_dtype=torch.float16 (lrx_attn_varlen_causal_ex): the output rows are written as fp16."""
     if qkv.dtype != torch.float16:
         raise TypeError("attn_varlen_causal: qkv must be fp16 (the fused QKV + RoPE projection writes fp16)")
+    out_f16 = _a16_flag(out_dtype, "attn_varlen_causal")
     T = qkv.shape[0]
-    out = (torch.zeros if last_tile_only else torch.empty)(T, nq * d, dtype=torch.bfloat16, device=qkv.device)
+    out = (torch.zeros if last_tile_only else torch.empty)(T, nq * d, dtype=out_dtype, device=qkv.device)
     n_seqs = cu_seqlens.numel() - 1
     if work_list is False:
-        _lib.check(_lib.lib().lrx_attn_varlen_causal(_lib.ptr(qkv), _lib.ptr(cu_seqlens), n_seqs, T, max_seqlen, nq, nkv, d,
-                                                     _lib.ptr(out), int(last_tile_only), _s()))
+        _lib.check(_lib.lib().lrx_attn_varlen_causal_ex(_lib.ptr(qkv), _lib.ptr(cu_seqlens), None, 0, n_seqs, T, max_seqlen, nq, nkv, d,
+                                                        _lib.ptr(out), int(last_tile_only), out_f16, _s()))
         return out
     if T == 0 or n_seqs == 0:
         return out
     if work_list is None:
         work_list = attn_work_list(cu_seqlens, T, max_seqlen, nq, nkv, d, last_tile_only)
-    _lib.check(_lib.lib().lrx_attn_varlen_causal_items(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(work_list), work_list.numel(), n_seqs, T, max_seqlen,
-                                                       nq, nkv, d, _lib.ptr(out), int(last_tile_only), _s()))
+    _lib.check(_lib.lib().lrx_attn_varlen_causal_ex(_lib.ptr(qkv), _lib.ptr(cu_seqlens), _lib.ptr(work_list), work_list.numel(), n_seqs, T, max_seqlen,
+                                                    nq, nkv, d, _lib.ptr(out), int(last_tile_only), out_f16, _s()))
     return out
 
 
-def attn_prefix_suffix(qkv: torch.Tensor, prefix_kv: torch.Tensor, n_seqs: int, suffix_len: int, nq: int, nkv: int, d: int) -> torch.Tensor:
-    """qkv [n_seqs*suffix_len, (nq+2nkv)d] fp16, prefix_kv [P1, 2*nkv*d] fp16 (k | v) -> [n_seqs*suffix_len, nq*d] bf16."""
+def attn_prefix_suffix(qkv: torch.Tensor, prefix_kv: torch.Tensor, n_seqs: int, suffix_len: int, nq: int, nkv: int, d: int,
+                       out_dtype=torch.bfloat16) -> torch.Tensor:
+    """qkv [n_seqs*suffix_len, (nq+2nkv)d] fp16, prefix_kv [P1, 2*nkv*d] fp16 (k | v) -> [n_seqs*suffix_len, nq*d] bf16, or fp16 with
+    out_dtype=torch.float16 (lrx_attn_prefix_suffix_ex)."""
+    out_f16 = _a16_flag(out_dtype, "attn_prefix_suffix")
     if qkv.dtype != torch.float16 or prefix_kv.dtype != torch.float16:
         raise TypeError("attn_prefix_suffix: qkv and prefix_kv must be fp16")
     if qkv.shape != (n_seqs * suffix_len, (nq + 2 * nkv) * d) or prefix_kv.shape[1:] != (2 * nkv * d,):
         raise ValueError("attn_prefix_suffix: operand shapes do not match the head layout")
-    out = torch.empty(n_seqs * suffix_len, nq * d, dtype=torch.bfloat16, device=qkv.device)
-    _lib.check(_lib.lib().lrx_attn_prefix_suffix(_lib.ptr(qkv), _lib.ptr(prefix_kv) if prefix_kv.shape[0] else None, n_seqs, suffix_len,
-                                                 prefix_kv.shape[0], nq, nkv, d, _lib.ptr(out), _s()))
+    out = torch.empty(n_seqs * suffix_len, nq * d, dtype=out_dtype, device=qkv.device)
+    _lib.check(_lib.lib().lrx_attn_prefix_suffix_ex(_lib.ptr(qkv), _lib.ptr(prefix_kv) if prefix_kv.shape[0] else None, n_seqs, suffix_len,
+                                                    prefix_kv.shape[0], nq, nkv, d, _lib.ptr(out), out_f16, _s()))
     return out
 
 

@@ -12,7 +12,15 @@ The bound, for every output element (O the exact result, A = P.|V| the same conv
 2^-8 is bf16's unit roundoff (the one rounding of the output), 2^-11 fp16's (each probability is rounded once before P.V; the row sum l
 keeps the unrounded ones, so numerator and denominator differ by exactly that rounding, weighted like A), one more unit of 2^-11 for
 everything done in fp32 (score accumulation over d, exp2, the running rescale, the fp32 sums over the keys), 1e-6 for probabilities that
-are denormal in fp16 (spacing 2^-24 each).  Derived, not tuned: the measured ratios are in tests/test_gpu_attn_reference.py's docstring."""
+are denormal in fp16 (spacing 2^-24 each).  Derived, not tuned: the measured ratios are in tests/test_gpu_attn_reference.py's docstring.
+
+fp16 output (out_f16, the O-projection's operand under precise_stream = 2): the same formula with the output term at fp16's unit roundoff,
+
+    |got - O| <= 2^-11 |O| + c 2^-11 A + 1e-6,    c = 2 unchanged
+
+-- only the last conversion differs, so only its term does.  With the 2^-8 term gone the bound is 2.7 to 8 times tighter (A >= |O|): the
+kernels' internal error, which a bf16-output comparison sees under a rounding eight times its size, is resolved.  The restatement with an
+fp16 output stays inside it on every host regime (tests/test_attn_reference_host.py; figures in the GPU file's docstring)."""
 import math
 
 import torch
@@ -21,6 +29,8 @@ C_BOUND = 2.0
 U_BF16 = 2.0 ** -8
 U_FP16 = 2.0 ** -11
 _BUDGET = 1 << 25      # fp64 score elements per chunk (256 MiB)
+_DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16}
+_U_OUT = {"bf16": U_BF16, "fp16": U_FP16}
 
 
 def _cu_list(cu):
@@ -91,17 +101,18 @@ def prefix_suffix_fp64(suffix_qkv, prefix_kv, n, S2, nq, nkv, d):
     return out[0], out[1]
 
 
-def restated(qkv, cu, nq, nkv, d, lazy_t=8.0):
+def restated(qkv, cu, nq, nkv, d, lazy_t=8.0, fmt="bf16"):
     """The kernels' documented arithmetic on the CPU, bf16 [T, nq d]: fp16 q | k | v, fp32 scores, online softmax per 32-key sub-tile in the
     exp2 domain with the 1/sqrt(d) log2(e) scale folded into the exponent, a reference maximum that moves only once the row maximum has
     outgrown it by 2^lazy_t, the row sum l taken from the unrounded probabilities, P rounded to fp16 before P.V, fp32 accumulation, one
-    bf16 rounding of O / l.  The calibration object of the bound; it touches no project kernel and is not under test."""
+    bf16 rounding of O / l (fmt = "fp16": one fp16 rounding, the out_f16 launches).  The calibration object of the bound; it touches no
+    project kernel and is not under test."""
     cu = _cu_list(cu)
     x = qkv.detach().cpu().to(torch.float16).float()
     T = x.shape[0]
     grp = nq // nkv
     c = torch.tensor((1.0 / math.sqrt(d)) * 1.4426950408889634, dtype=torch.float32)
-    out = torch.zeros(T, nq * d, dtype=torch.bfloat16)
+    out = torch.zeros(T, nq * d, dtype=_DTYPE[fmt])
     for b in range(len(cu) - 1):
         s0, L = cu[b], cu[b + 1] - cu[b]
         if L <= 0:
@@ -127,18 +138,32 @@ def restated(qkv, cu, nq, nkv, d, lazy_t=8.0):
             o[:, :, rs] = o[:, :, rs] * alpha[..., None] + p.to(torch.float16).float() @ v[:, :, u0:u1]
             m[:, :, rs] = mnew
         res = o * (1.0 / l)[..., None]
-        out[s0:s0 + L] = res.permute(2, 0, 1, 3).reshape(L, nq * d).to(torch.bfloat16)
+        out[s0:s0 + L] = res.permute(2, 0, 1, 3).reshape(L, nq * d).to(_DTYPE[fmt])
     return out
 
 
-def bound(O, A, c=C_BOUND):
-    return U_BF16 * O.abs() + c * U_FP16 * A + 1e-6
+def bound(O, A, c=C_BOUND, fmt="bf16"):
+    return _U_OUT[fmt] * O.abs() + c * U_FP16 * A + 1e-6
 
 
-def worst_ratio(got, O, A, c=C_BOUND):
+def worst_ratio(got, O, A, c=C_BOUND, fmt="bf16"):
     """max over the elements of |got - O| / bound (nan if got holds one)"""
-    r = (got.double() - O).abs() / bound(O, A, c)
+    r = (got.double() - O).abs() / bound(O, A, c, fmt)
     return float(r.max()) if r.numel() else 0.0
+
+
+def bf16_of_fp16_allowed(h):
+    """The two roundings of one number.  A launch with fp16 output and the same launch with bf16 output round the SAME fp32 value v: fp16
+    keeps 11 significant bits of it, bf16 8, and fp16's grid contains bf16's wherever the fp16 value is normal, so
+    bf16(v) = bf16(fp16(v)) -- unless fp16(v) is exactly the midpoint of two bf16 numbers: then v may lie on either side of it (or on it)
+    and either neighbour is allowed.  h: the fp16 output.  -> (a, b, checked): the bf16 numbers the bf16 launch may hold (a == b away from
+    midpoints; at one, a is the neighbour towards zero and b the one away from it), and where the statement applies (|h| >= 2^-14; below,
+    fp16's spacing is no finer than bf16's).  Integer arithmetic on the fp32 bit pattern: an fp16 number is an fp32 number whose low 13
+    bits are zero, a bf16 number one whose low 16 are -- no power function of the device is trusted with an exact result."""
+    bits = h.float().view(torch.int32)
+    rem = bits & 0xFFFF
+    toward, away = (bits - rem).view(torch.float32).double(), (bits - rem + 0x10000).view(torch.float32).double()
+    return torch.where(rem > 0x8000, away, toward), torch.where(rem >= 0x8000, away, toward), h.float().abs() >= 2.0 ** -14
 
 
 def norm_ratio(got, O):

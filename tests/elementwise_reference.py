@@ -57,6 +57,21 @@ def fp16_round(v):
     return np.clip(np.asarray(v, np.float64), -65504.0, 65504.0).astype(np.float16).astype(np.float64)
 
 
+def fp16_sat(v):
+    """float64 -> fp16 under the STORE RULE of the kernels that write an fp16 GEMM operand (f2h_bits in lrx_gemm.hip, the clamp of
+    k_embed_stream32<true>: fminf(fmaxf(v, -65504), 65504), then one RNE rounding): beyond the range +-65504 by sign, and a NaN -65504 --
+    fmaxf(NaN, -65504) is -65504.  Never an inf, never a NaN.  Equal to fp16_round on every number."""
+    v = np.asarray(v, np.float64)
+    return fp16_round(np.where(np.isnan(v), -65504.0, v))
+
+
+def fp16_ieee(v):
+    """float64 -> fp16 as a plain conversion gives it (RNE; inf beyond 65520, NaN kept): what a store WITHOUT the clamp would write -- the
+    wrong kernel the saturation inputs must tell from fp16_sat"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.asarray(v, np.float64).astype(np.float16).astype(np.float64)
+
+
 def rstd_budget(H):
     return (-(-H // 64) + 10) * U32 / 2 + R_RSQRT
 
@@ -102,7 +117,7 @@ def embed_stream32(table, ids, gamma, eps, f16=False):
     ok = (ids >= 0) & (ids < table.shape[0])
     x = np.where(ok[:, None], table[np.where(ok, ids, 0)], 0.0)
     pre = x * np.asarray(gamma, np.float64)
-    return x, (fp16_round(pre) if f16 else bf16_round(pre)), row_rscale(x, eps)
+    return x, (fp16_sat(pre) if f16 else bf16_round(pre)), row_rscale(x, eps)
 
 
 def pooled_tokens(cu, pooling):

@@ -23,7 +23,7 @@ following addition into one fma, which rounds once instead of twice: the bound c
 import numpy as np
 
 from oracle import lrx_oracle as O
-from elementwise_reference import NEAR_CAP, U32, bf16_round, fp16_round
+from elementwise_reference import NEAR_CAP, U32, bf16_round, fp16_ieee, fp16_round, fp16_sat
 
 TILE, GBK = 256, 64
 BF16_MIN = float(O.BF16_MIN)
@@ -116,8 +116,10 @@ def interleave_gate_up(Wg, Wu):
     return np.stack([Wg.reshape(I // 16, 16, H), Wu.reshape(I // 16, 16, H)], 1).reshape(2 * I, H)
 
 
-def swiglu(A, Bi, rscale=None):
+def swiglu(A, Bi, rscale=None, fmt="bf16"):
     """lrx_gemm_bf16_nt_fused, epilogue 2 on the interleaved weight Bi [N, K]: C[M, N / 2] = bf16(silu(g rs) (u rs)).
+    fmt = "fp16": the fp16-operand form (lrx_gemm_nt_fused_ex, f16 = 1; k_gemm_bf16_nt<EPI_SWIGLU, true>) -- the same fp32 arithmetic
+    behind the accumulator, the same budget; only the stored format changes: fp16 under the store rule (fp16_sat).
     Kernel: g = acc_g * rs, up = acc_u * rs (fp32 products); sg = v_rcp_f32(1 + v_exp_f32(g * c32)), c32 = fp32(-log2 e); t = g * sg * up.
     Budget, with s(x) = 1 / (1 + exp(-x)) and e = exp(-g):
       the exponent argument g c32 carries the rounding of the constant (u) and of the product (u): 2 u |g| log2 e in the argument, i.e.
@@ -136,7 +138,7 @@ def swiglu(A, Bi, rscale=None):
     s = 1.0 / (1.0 + np.exp(-g))
     pre = g * s * up
     budget = np.abs(up * s * (1.0 + g * (1.0 - s))) * eg + np.abs(g * s) * eu + np.abs(pre) * U32 * ((2.0 * np.abs(g) + 2.0) * (1.0 - s) + 5.0)
-    return bf16_round(pre), pre, budget
+    return (fp16_sat(pre) if fmt == "fp16" else bf16_round(pre)), pre, budget
 
 
 def rotary_pair_order(nq, nkv, d):
@@ -189,8 +191,13 @@ def qkv_rope(A, Wp, positions, cos, sin, nq, nkv, d, bias_p=None, rscale=None, h
     return fp16_round(pre[:, sl]), pre[:, sl], bud[:, sl]
 
 
-def resid32(A, B, x32, gamma=None):
+def resid32(A, B, x32, gamma=None, fmt="bf16"):
     """lrx_gemm_bf16_nt_resid32: x32 = fp32(x32 + acc); a16 = bf16(fp32(x32 gamma[n])); ss_part from the fp32 row.
+    fmt = "fp16" (lrx_gemm_nt_resid32_ex, out_f16 = 1; the OUTH branch): a16 = fp16(fp32(x32 gamma[n])) under the store rule.  Two
+    roundings of one number: an exact product within half an fp32 ulp of an fp16 midpoint (one element in 2^13) rounds otherwise than
+    fp16(x32 gamma) would, so the value handed to the comparison as `pre_a` is the fp32 PRODUCT, restated in numpy float32 -- the kernel's
+    own sequence -- and the budget stays zero.  (The bf16 form keeps the exact product as pre_a: there the two differ in one element in
+    2^16.)  fp16 operands (f16 = 1) change nothing here: the accumulator is exact either way.
     Kernel (EPI_RESID32): v = staged acc + x32 (one fp32 addition of exactly known operands), stored; f2bf(v * gm) -- one fp32 product, one
     rounding to bf16, nothing an fma could merge.  Each step is one IEEE rounding, restated in numpy float32: budget ZERO for both outputs.
     ss_part: float64 sum of the new row's squares per tile (kernel: SS_ROUNDINGS_RESID32 roundings per term).
@@ -198,8 +205,12 @@ def resid32(A, B, x32, gamma=None):
     acc = acc64(A, B)
     x = _f32(x32) + acc.astype(np.float32)
     g = np.ones(x.shape[1], np.float32) if gamma is None else _f32(gamma)
-    a16 = O.round_bf16(x * g[None, :])
     x64 = _f64(x)
+    if fmt == "fp16":
+        with np.errstate(over="ignore", invalid="ignore"):
+            pa = _f64(x * g[None, :])
+        return x64, fp16_sat(pa), _f64(x32) + acc, pa, np.zeros_like(x64), tile_sums(x64 * x64, x.shape[1])
+    a16 = O.round_bf16(x * g[None, :])
     return x64, _f64(a16), _f64(x32) + acc, x64 * _f64(g)[None, :], np.zeros_like(x64), tile_sums(x64 * x64, x.shape[1])
 
 
@@ -229,7 +240,7 @@ def max_aggregate(A, B, bias, row_seg, n_seqs, init=BF16_MIN):
 # the comparison rule
 # ---------------------------------------------------------------------------------------------------------------
 def _round(fmt):
-    return {"bf16": bf16_round, "fp16": fp16_round, "fp32": lambda v: np.asarray(v, np.float64).astype(np.float32).astype(np.float64)}[fmt]
+    return {"bf16": bf16_round, "fp16": fp16_sat, "fp32": lambda v: np.asarray(v, np.float64).astype(np.float32).astype(np.float64)}[fmt]
 
 
 def ulp(v, fmt):
@@ -298,6 +309,41 @@ def exact_operands(rng, M, N, K, a_scale=2.0 ** -3, b_scale=2.0 ** -4):
     """A [M, K], B [N, K]: integers in [-int_range, int_range] times a power of two: bf16-exact, no subnormals, |sum| < 2^24 units"""
     r = int_range(K)
     return (rng.integers(-r, r + 1, (M, K)) * a_scale).astype(np.float32), (rng.integers(-r, r + 1, (N, K)) * b_scale).astype(np.float32)
+
+
+def wide_operands(rng, M, N, K):
+    """The wide-mantissa exact family, which no bf16 operand can express: A = integers in +-1023 times 2^-10 (all 11 significant bits of
+    fp16; 3 more than bf16 holds), B = integers in +-15 times 2^-4.  K <= 512: |sum| <= 1023 * 15 * 512 < 2^23 units of 2^-14."""
+    assert K <= 512
+    return (rng.integers(-1023, 1024, (M, K)) * 2.0 ** -10).astype(np.float32), (rng.integers(-15, 16, (N, K)) * 2.0 ** -4).astype(np.float32)
+
+
+def one_hot_rows_wide(M, N, K):
+    """one_hot_rows with 11-bit B values: B[n, k] = +-(1024 + (53 n + 7 k) mod 1023), odd and even, every one of them needing bits that bf16
+    drops; C[m, n] = B[n, pi(m)] names the K element and the row that were read, to the last of fp16's 11 bits"""
+    A, _ = one_hot_rows(M, N, K)
+    n, k = np.arange(N)[:, None], np.arange(K)[None, :]
+    return A, ((1024 + (53 * n + 7 * k) % 1023) * np.where((n + k) % 2, -1.0, 1.0)).astype(np.float32)
+
+
+def subnormal_probe(M, K):
+    """fp16-SUBNORMAL operands: one-hot A (pi of one_hot_rows), B[n, k] = j 2^-24 with j = 1 + (n K + k) mod 1023 -- every fp16 subnormal
+    1 .. 1023 for N K >= 1023.  IEEE arithmetic gives C[m, n] = B[n, pi(m)] exactly (1 x a subnormal, summed with zeros)."""
+    N = 16
+    A, _ = one_hot_rows(M, N, K)
+    j = 1 + (np.arange(N)[:, None] * K + np.arange(K)[None, :]) % 1023
+    return A, (j * 2.0 ** -24).astype(np.float32)
+
+
+def is_fp16_exact(a):
+    a = np.asarray(a, np.float32)
+    with np.errstate(over="ignore"):
+        return bool((a.astype(np.float16).astype(np.float32) == a).all())
+
+
+def has_fp16_subnormals(a):
+    a = np.abs(np.asarray(a, np.float64))
+    return bool(((a > 0) & (a < 2.0 ** -14)).any())
 
 
 def sum_units(A, B):
@@ -395,7 +441,76 @@ def gpu_cases():
     return cs
 
 
+def gpu_cases_f16():
+    """the fp16-operand / fp16-output instantiations (lrx_*_ex): the shapes above and nothing larger.  f16: A and B are fp16; out_f16
+    (resid32): a16 is fp16; the SwiGLU output is fp16 with f16.  The operands are the SAME arrays as the bf16 case of the same shape would
+    get (the seed is taken from `base`), all fp16-exact."""
+    cs = []
+    for d, nq, nkv, b, r, M, K in ROPE:
+        for pos0 in (False, True):
+            if pos0 and (b or r):
+                continue
+            base = f"rope-d{d}-q{nq}kv{nkv}-b{int(b)}r{int(r)}-{M}x{K}" + ("-pos0" if pos0 else "")
+            cs.append(_case("f16-" + base, "rope", "exact" if pos0 else "general", M, (nq + 2 * nkv) * d, K, d=d, nq=nq, nkv=nkv, bias=b, rscale=r,
+                            pos0=pos0, f16=1, base=base))
+    for M, N, K in EDGES:
+        for fam in ("exact", "general"):
+            for f16, oh in ((1, 1), (0, 1)):
+                cs.append(_case(f"resid32-f{f16}h{oh}-{fam}-{M}x{N}x{K}", "resid32", fam, M, N, K, f16=f16, out_f16=oh, base=f"resid32-{fam}-{M}x{N}x{K}"))
+    # the last layer's down-projection: fp16 operands, nothing written for a next projection
+    cs.append(_case("resid32-f1h1-noa16-exact-129x504x192", "resid32", "exact", 129, 504, 192, f16=1, out_f16=1, no_a16=True, base="resid32-exact-129x504x192"))
+    for M, N, K in EDGES_SWIGLU:
+        cs.append(_case(f"f16-swiglu-{M}x{N}x{K}", "swiglu", "general", M, N, K, f16=1, base=f"swiglu-{M}x{N}x{K}"))
+    cs.append(_case("f16-swiglu-tilemap-3333x544x64", "swiglu", "general", 3333, 544, 64, f16=1, base="swiglu-tilemap-3333x544x64"))
+    for M, N, K in K_LOOP:                                           # the fp32 x32 output shows the accumulator exactly
+        cs.append(_case(f"kloop-resid32-f1h1-nk{K // GBK}", "resid32", "exact", M, N, K, f16=1, out_f16=1))
+    cs.append(_case("resid32-f1h1-tilemap-3333x520x64", "resid32", "exact", 3333, 520, 64, f16=1, out_f16=1))
+    # the wide-mantissa family: every M % 256 / N % 256 class once more, nk = 3, 4, 8
+    for M, N, K in ((129, 504, 192), (255, 520, 256), (300, 264, 512)):
+        cs.append(_case(f"resid32-f1h1-wide-{M}x{N}x{K}", "resid32", "exact", M, N, K, f16=1, out_f16=1, wide=True))
+    return cs
+
+
+F16_CASES_BY_NAME = None
+
+
+def f16_case(name):
+    global F16_CASES_BY_NAME
+    if F16_CASES_BY_NAME is None:
+        F16_CASES_BY_NAME = {c["name"]: c for c in gpu_cases_f16()}
+    return F16_CASES_BY_NAME[name]
+
+
+SATURATION = ("swiglu-f1", "resid32-f1h1", "resid32-f0h1")
+
+
+def saturation_inputs(which):
+    """Inputs on which the fp16 stores of the SwiGLU (f16) and resid32 (out_f16) epilogues leave fp16's range -- defined behaviour with finite
+    stores: +-65504 by sign, a NaN as -65504.  -> (case, inp, ref without ss_part)
+      swiglu:   rows 3, 100, 128 under a row scale of 2^10 (a power of two: g and u stay exact; |silu(g) u| reaches 1e8 where g > 0, and is 0
+                where g << 0); row 7 is a zero row of A under an infinite row scale: 0 x inf = NaN in every column.
+      resid32:  gamma = +-2^14 on columns 5 and 300 (|x32| <= 110: saturated wherever |x32| > 3.998, exact below), and a NaN, a +inf and a
+                -inf in the incoming x32 (x32 keeps them; a16 holds -65504, or +-65504 by the sign of inf x gamma, or -65504 for inf x 0)."""
+    if which == "swiglu-f1":
+        case = dict(f16_case("f16-swiglu-129x544x192"), name="saturation-" + which)
+        inp = {k: (None if v is None else v.copy()) for k, v in case_inputs(case).items()}
+        inp["A"][7] = 0.0
+        inp["rscale"] = np.ones(case["M"], np.float32)
+        inp["rscale"][[3, 100, 128]] = 2.0 ** 10
+        inp["rscale"][7] = np.inf
+    else:
+        case = dict(f16_case(which + "-exact-129x504x192"), name="saturation-" + which)
+        inp = {k: v.copy() for k, v in case_inputs(case).items()}
+        inp["gamma"][5], inp["gamma"][300] = 2.0 ** 14, -2.0 ** 14
+        inp["x32"][7, 9], inp["x32"][7, 10], inp["x32"][8, 10], inp["x32"][8, 5] = np.nan, np.inf, -np.inf, np.inf
+    with np.errstate(all="ignore"):
+        ref = case_reference(case, inp)
+    ref.pop("ss", None)
+    return case, inp, ref
+
+
 def _seed(case):
+    case = dict(case, name=case.get("base", case["name"]))
     return int(np.frombuffer(case["name"].encode().ljust(64, b"\0")[:64], np.uint32).sum() % (2 ** 31))
 
 
@@ -427,7 +542,7 @@ def case_inputs(case):
         _, Wu = exact_operands(rng, 1, N // 2, K, b_scale=swiglu_b_scale(K))
         inp.update(A=A, B=interleave_gate_up(Wg, Wu), rscale=rng.uniform(0.2, 3.0, M).astype(np.float32) if M % 2 else None)
         return inp
-    A, B = exact_operands(rng, M, N, K)
+    A, B = wide_operands(rng, M, N, K) if case.get("wide") else exact_operands(rng, M, N, K)
     if case.get("negative"):
         A, B = np.abs(A) + np.float32(2.0 ** -3), -np.abs(B) - np.float32(2.0 ** -4)
     inp.update(A=A, B=B)
@@ -469,10 +584,15 @@ def case_reference(case, inp):
         C, pre, b, ss = resid(inp["A"], inp["B"], inp["R"])
         return {"C": (C, pre, b, "bf16"), "ss": (ss, SS_ROUNDINGS_RESID)}
     if epi == "swiglu":
-        return {"C": swiglu(inp["A"], inp["B"], inp["rscale"]) + ("bf16",)}
+        fmt = "fp16" if case.get("f16") else "bf16"
+        return {"C": swiglu(inp["A"], inp["B"], inp["rscale"], fmt) + (fmt,)}
     if epi == "resid32":
-        x, a, px, pa, b, ss = resid32(inp["A"], inp["B"], inp["x32"], inp["gamma"])
-        return {"x32": (x, px, b, "fp32"), "a16": (a, pa, b, "bf16"), "ss": (ss, SS_ROUNDINGS_RESID32)}
+        fmt = "fp16" if case.get("out_f16") else "bf16"
+        x, a, px, pa, b, ss = resid32(inp["A"], inp["B"], inp["x32"], inp["gamma"], fmt)
+        ref = {"x32": (x, px, b, "fp32"), "a16": (a, pa, b, fmt), "ss": (ss, SS_ROUNDINGS_RESID32)}
+        if case.get("no_a16"):
+            del ref["a16"]
+        return ref
     if epi == "maxagg":
         out, _, b = max_aggregate(inp["A"], inp["B"], inp["bias"], row_segments(inp["cu"], inp["mask"]), len(inp["cu"]) - 1)
         return {"out": (_f64(out), _f64(out), b, "fp32")}

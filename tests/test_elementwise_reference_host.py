@@ -27,6 +27,11 @@ def test_bf16_rounding_is_the_oracles_and_the_neighbours_bracket():
     np.testing.assert_allclose(rel[fin], np.abs(v - mid)[fin] / np.abs(v)[fin], rtol=1e-9)
     assert ER.bf16_neighbours(1.00390625)[2] == 0.0 and ER.bf16_round(1.00390625) == 1.0 and ER.bf16_round(1.01171875) == 1.015625   # ties go to even
     np.testing.assert_array_equal(ER.fp16_round([70000.0, -1e9, 0.1]), [65504.0, -65504.0, float(np.float16(0.1))])
+    # the store rule of the fp16-operand kernels: the same on every number, a NaN as -65504, subnormals rounded once (RNE at 2^-24)
+    np.testing.assert_array_equal(ER.fp16_sat([70000.0, -1e9, 0.1, np.nan, np.inf, -np.inf, 65519.9, 65520.0, 3 * 2.0 ** -25, 5 * 2.0 ** -25, 2.0 ** -26]),
+                                  [65504.0, -65504.0, float(np.float16(0.1)), -65504.0, 65504.0, -65504.0, 65504.0, 65504.0, 2 * 2.0 ** -24, 2 * 2.0 ** -24, 0.0])
+    np.testing.assert_array_equal(ER.fp16_sat(v), ER.fp16_round(v))
+    assert np.isinf(ER.fp16_ieee(65520.0)) and np.isnan(ER.fp16_ieee(np.nan)) and ER.fp16_ieee(65519.9) == 65504.0
 
 
 @pytest.mark.parametrize("rows,H", [(1, 64), (37, 256), (300, 2048), (9, 4096)])
@@ -110,6 +115,14 @@ def test_impossible_sequences_and_the_shard_form():
     assert (d2[cu[1:] - 1, :8] == g).all() and (d2[:, 8:] == -7.0).all() and (d2 != -7.0).sum() == g.size
     x3, a16, rs = ER.embed_stream32(*ER.embed_inputs(8), 1e-5)
     assert (x3[2:4] == 0).all() and (a16[2:4] == 0).all() and np.allclose(rs[2:4], 1e-5 ** -0.5)
+    # the fp16 operand of the same inputs: x32 and rs unchanged; a16 is NOT the bf16 operand converted, on most elements, at every GPU shape
+    for H in ER.EMBED_H:
+        table, ids, gamma = ER.embed_inputs(H)
+        xb, ab, rb = ER.embed_stream32(table, ids, gamma, 1e-5)
+        xh, ah, rh = ER.embed_stream32(table, ids, gamma, 1e-5, f16=True)
+        np.testing.assert_array_equal(xb, xh), np.testing.assert_array_equal(rb, rh)
+        assert (ah != ER.fp16_round(ab)).mean() > 0.5 and np.abs(ah).max() < 65504 and (ah[2:4] == 0).all()
+        np.testing.assert_array_equal(ah, (xh * gamma.astype(np.float64)).astype(np.float16).astype(np.float64))
 
 
 def test_exact_probes_are_exact_in_the_reference_too():

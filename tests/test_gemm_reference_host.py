@@ -1,7 +1,9 @@
 """Host-side checks of tests/gemm_reference.py: the reference agrees with what is already pinned (the oracle, the expectations the existing GEMM
 tests compute inline), the accumulator of every GPU case is exact in fp32 in two summation orders, the comparison rule exempts at most 2 %
 of any case (nothing where the budget is zero), and the rule has teeth: a float32 stand-in of each epilogue passes it, every listed mutant of
-the stand-in fails it."""
+the stand-in fails it.  The fp16-operand / fp16-output cases (GR.gpu_cases_f16) on top of that: their operands are fp16-exact without
+subnormals, and for every fp16 output the rule rejects the two likeliest wrong kernels computed from the reference itself -- the value
+rounded through bf16 first, and (on the saturation inputs) the store without the clamp."""
 import functools
 
 import numpy as np
@@ -12,11 +14,13 @@ from oracle import lrx_oracle as O
 
 CASES = GR.gpu_cases()
 IDS = [c["name"] for c in CASES]
+CASES_F16 = GR.gpu_cases_f16()
+IDS_F16 = [c["name"] for c in CASES_F16]
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
-    case = CASES[IDS.index(name)]
+    case = CASES[IDS.index(name)] if name in IDS else CASES_F16[IDS_F16.index(name)]
     inp = GR.case_inputs(case)
     return case, inp, GR.case_reference(case, inp)
 
@@ -100,9 +104,19 @@ def _two_orders(A, B):
     return fwd, parts[0]
 
 
-@pytest.mark.parametrize("name", IDS)
+@pytest.mark.parametrize("name", IDS + IDS_F16)
 def test_accumulator_is_exact_and_the_rule_exempts_little(name):
     case, inp, ref = _case(name)
+    if name in IDS_F16:
+        # what the bf16 cases cannot require: the operands survive the conversion to fp16 unchanged, none of them subnormal (the subnormal
+        # probe is a test of its own), and the same arrays serve the bf16 case of the same shape
+        assert GR.is_fp16_exact(inp["A"]) and GR.is_fp16_exact(inp["B"]), name
+        assert not GR.has_fp16_subnormals(inp["A"]) and not GR.has_fp16_subnormals(inp["B"]), name
+        if "base" in case:
+            base = _case(case["base"])[1]
+            assert all(np.array_equal(inp[k], base[k]) if inp[k] is not None else base[k] is None for k in inp), name
+        if case.get("wide"):
+            assert not (O.round_bf16(inp["A"]) == inp["A"]).all() and np.abs(inp["A"]).max() * 2 ** 10 > 1000, "the wide family must not be bf16-exact"
     units, _ = GR.sum_units(inp["A"], inp["B"])
     assert units < 2 ** 24
     fwd, pair = _two_orders(inp["A"], inp["B"])
@@ -119,6 +133,62 @@ def test_accumulator_is_exact_and_the_rule_exempts_little(name):
     if case["epi"] == "swiglu":
         g = acc[:, GR.gate_up_columns(case["N"])[0]] * (1.0 if inp["rscale"] is None else inp["rscale"].astype(np.float64)[:, None])
         assert (np.abs(g) < 8).mean() > 0.6 and np.abs(g).max() < 80, ((np.abs(g) < 8).mean(), np.abs(g).max())
+
+
+@pytest.mark.parametrize("name", IDS_F16)
+def test_fp16_outputs_tell_a_rounding_through_bf16_from_the_right_answer(name):
+    """the likeliest wrong kernel of an fp16 store: fp16(bf16(x)), a conversion that went through the bf16 path first"""
+    case, inp, ref = _case(name)
+    n = 0
+    for key, val in ref.items():
+        if key != "ss" and val[3] == "fp16":
+            want, pre, budget, fmt = val
+            GR.check(want, pre, budget, fmt, f"{name} {key}")
+            with pytest.raises(AssertionError):
+                GR.check(GR.fp16_round(GR.bf16_round(pre)), pre, budget, fmt, f"{name} {key}")
+            # ... and not by a hair: the mutant differs in far more elements than the rule exempts
+            assert (GR.fp16_round(GR.bf16_round(pre)) != want).mean() > 0.25, name
+            n += 1
+    assert n == (0 if case.get("no_a16") else 1)
+
+
+def test_fp16_swiglu_outputs_reach_into_the_subnormals():
+    """0.1 % to 0.8 % of the SwiGLU outputs at K >= 192 are fp16 subnormals: the conversion's subnormal rounding is exercised"""
+    shares = {}
+    for name in IDS_F16:
+        case, inp, ref = _case(name)
+        if case["epi"] == "swiglu":
+            want = np.abs(ref["C"][0])
+            shares[name] = float(((want > 0) & (want < 2.0 ** -14)).mean())
+    print(shares)
+    assert sum(v >= 1e-3 for v in shares.values()) >= 4 and max(shares.values()) < 1e-2
+
+
+@pytest.mark.parametrize("which", GR.SATURATION)
+def test_saturation_inputs_tell_a_store_without_the_clamp_from_the_right_answer(which):
+    case, inp, ref = GR.saturation_inputs(which)
+    key = "C" if case["epi"] == "swiglu" else "a16"
+    want, pre, budget, fmt = ref[key]
+    with np.errstate(all="ignore"):
+        out = ~(np.abs(pre) <= 65504)
+        assert fmt == "fp16" and np.isfinite(want).all() and out.sum() >= 100 and np.isnan(pre).any()
+        assert (want[out & (pre > 0)] == 65504).all() and (want[out & ~(pre > 0)] == -65504).all()         # by sign; NaN as -65504
+        assert (want == 65504).any() and (want[~np.isnan(pre)] == -65504).any() and (np.abs(want[~out]) < 65504).all() and (~out).mean() > 0.9
+        GR.check(want, pre, budget, fmt, which)
+        with pytest.raises(AssertionError):
+            GR.check(GR.fp16_ieee(pre), pre, budget, fmt, which)
+        with pytest.raises(AssertionError):                              # a clamp that lets the NaN through
+            GR.check(np.where(np.isnan(pre), np.nan, want), pre, budget, fmt, which)
+
+
+def test_wide_and_subnormal_probes_are_what_their_docstrings_say():
+    A, B = GR.one_hot_rows_wide(300, 264, 192)
+    assert GR.is_fp16_exact(B) and (O.round_bf16(B) != B).mean() > 0.8 and np.abs(B).min() >= 1024 and np.abs(B).max() <= 2046
+    np.testing.assert_array_equal(GR.acc64(A, B), B[:, (37 * np.arange(300) + 11) % 192].T)
+    A, B = GR.subnormal_probe(300, 128)
+    j = np.abs(B.astype(np.float64)) * 2.0 ** 24
+    assert GR.is_fp16_exact(B) and sorted(set(j.ravel().tolist())) == list(range(1, 1024)) and (np.abs(B) < 2.0 ** -14).all()
+    np.testing.assert_array_equal(GR.acc64(A, B), B[:, (37 * np.arange(300) + 11) % 128].T.astype(np.float64))
 
 
 @pytest.mark.parametrize("M,N", GR.TILE_MAP)
@@ -154,6 +224,10 @@ def _bf(x):
     return O.round_bf16(np.asarray(x, np.float32))
 
 
+def _h(x):
+    return np.clip(np.asarray(x, np.float32), np.float32(-65504), np.float32(65504)).astype(np.float16)
+
+
 def standin(case, inp, mutant=None):
     """the epilogue in numpy float32, step by step as the kernel does it -> {output: array}"""
     epi = case["epi"]
@@ -180,10 +254,19 @@ def standin(case, inp, mutant=None):
         rs = np.float32(1) if inp["rscale"] is None else inp["rscale"][:, None]
         g, u = acc[:, gc] * rs, acc[:, uc] * rs
         sg = np.float32(1) / (np.float32(1) + np.exp2(g * np.float32(-1.4426950408889634)))
-        return {"C": _bf(g * sg * u)}
+        t = g * sg * u
+        if mutant == "through_bf16":
+            t = _bf(t)
+        return {"C": _h(t) if case.get("f16") else _bf(t)}
     if epi == "resid32":
         x = inp["x32"] + acc
-        return {"x32": x, "a16": _bf(x * inp["gamma"][None, :]), "ss": GR.tile_sums(x.astype(np.float64) ** 2, case["N"])}
+        t = x * inp["gamma"][None, :]
+        if mutant == "through_bf16":
+            t = _bf(t)
+        out = {"x32": x, "a16": _h(t) if case.get("out_f16") else _bf(t), "ss": GR.tile_sums(x.astype(np.float64) ** 2, case["N"])}
+        if case.get("no_a16"):
+            del out["a16"]
+        return out
     if epi == "rope":
         d, nq, nkv = case["d"], case["nq"], case["nkv"]
         x = acc
@@ -218,12 +301,17 @@ def _judge(case, inp, ref, got):
 
 
 STANDIN_CASES = ["store-exact-129x504x192", "store-general-129x504x192", "resid-exact-129x504x192", "resid-general-255x520x256", "swiglu-129x544x192",
-                 "resid32-general-128x264x64", "rope-d128-q2kv1-b1r1-127x192", "rope-d64-q4kv2-b0r0-257x64", "rope-d64-q4kv2-b0r0-257x64-pos0"]
+                 "resid32-general-128x264x64", "rope-d128-q2kv1-b1r1-127x192", "rope-d64-q4kv2-b0r0-257x64", "rope-d64-q4kv2-b0r0-257x64-pos0",
+                 "f16-swiglu-129x544x192", "resid32-f1h1-general-128x264x64", "resid32-f0h1-exact-129x504x192", "resid32-f1h1-wide-300x264x512",
+                 "resid32-f1h1-noa16-exact-129x504x192", "kloop-resid32-f1h1-nk5", "f16-rope-d128-q2kv1-b1r1-127x192"]
 MUTANTS = [("store-exact-129x504x192", "drop_last_k_tile"), ("store-exact-129x504x192", "k_tile_twice"), ("store-exact-129x504x192", "bias_after_rounding"),
            ("store-general-129x504x192", "bias_after_rounding"), ("store-exact-129x504x192", "rscale_after_bias"), ("store-general-129x504x192", "rscale_after_bias"),
            ("resid-exact-129x504x192", "resid_before_inner_rounding"), ("swiglu-129x544x192", "gate_up_swapped"),
            ("rope-d128-q2kv1-b1r1-127x192", "rotation_sign_flipped"), ("rope-d128-q2kv1-b1r1-127x192", "partner_j_plus_16"),
-           ("store-exact-129x504x192", "tile_transposed"), ("resid-exact-129x504x192", "ss_before_resid")]
+           ("store-exact-129x504x192", "tile_transposed"), ("resid-exact-129x504x192", "ss_before_resid"),
+           ("f16-swiglu-129x544x192", "through_bf16"), ("f16-swiglu-129x544x192", "gate_up_swapped"), ("resid32-f1h1-general-128x264x64", "through_bf16"),
+           ("resid32-f0h1-exact-129x504x192", "through_bf16"), ("resid32-f1h1-wide-300x264x512", "drop_last_k_tile"),
+           ("kloop-resid32-f1h1-nk5", "k_tile_twice"), ("f16-rope-d128-q2kv1-b1r1-127x192", "rotation_sign_flipped")]
 
 
 @pytest.mark.parametrize("name", STANDIN_CASES)

@@ -27,6 +27,28 @@ restatement of the kernels' arithmetic on inputs of the same regime (tests/test_
   kernel    tiled d64                           0.876           0.822
   kernel    tiled d128                          0.865           0.867
 
+The same with fp16 OUTPUT (out_f16: all five kernels; bound 2^-11 |O| + c 2^-11 A + 1e-6, c = 2 -- only the output term changes, so the
+kernels' internal error is resolved eight times finer than above):
+
+                                        flat    large scores
+  kernel    resident d64                0.558   0.641
+  kernel    tiled d64                   0.579   0.646
+  kernel    tiled d128                  0.594   0.644
+  kernel    tiled d128 last tile        0.574   0.638
+  restated  d = 64                      0.393   0.616              (peaky 0.573, offset 0.346, q x 8: 0.608, q x 4 with v + 30: 0.560)
+  restated  d = 128                     0.469   0.622              (peaky 0.572, offset 0.277, q x 8: 0.582, q x 4 with v + 30: 0.544)
+
+                                        parity  masked extremes
+  kernel    prefix/suffix matrix-core   0.430   0.423
+  kernel    prefix/suffix VALU          0.421   0.407
+  kernel    resident d64                        0.562
+  kernel    tiled d64                           0.581
+  kernel    tiled d128                          0.574
+
+  fp16 out    the parity cases above also run the bf16-output launch: it must hold bf16(fp16 output) -- either neighbour where that is a bf16
+              midpoint -- so the two launches differ in the last conversion only; first row = v_0 to all 11 bits; constant v = c to one fp16
+              step; masked rows hold +-65504 (the fp16 store does not saturate: see test_fp16_output_masked_rows_hold_extremes)
+
 c = 2 as derived, never adjusted: the kernels' worst ratio (0.888) sits 0.03 above the restatement's (0.862) over some hundred times as many
 elements, and both stay under the 0.9 that one worst-case bf16 rounding plus one worst-case fp16 rounding of a dominant probability reach
 ((2^-8 + 2^-11) / (2^-8 + 2 2^-11)).
@@ -48,8 +70,8 @@ def _note(group, ratio):
     _WORST[group] = max(_WORST.get(group, 0.0), ratio) if ratio == ratio else float("nan")
 
 
-def _check(group, got, O, A, norm=True):
-    ratio = R.worst_ratio(got, O, A)
+def _check(group, got, O, A, norm=True, fmt="bf16"):
+    ratio = R.worst_ratio(got, O, A, fmt=fmt)
     _note(group, ratio)
     print(f"{group}: worst |err| / bound = {ratio:.3f}" + (f", norm ratio - 1 = {R.norm_ratio(got, O) - 1:+.2e}" if norm else ""))
     assert ratio <= 1.0, f"{group}: worst |err| / bound = {ratio:.3f}"
@@ -356,6 +378,171 @@ def test_prefix_suffix_masked_rows_hold_extremes(d, nq, nkv, P1, S2, n):
     O, A = R.prefix_suffix_fp64(suf[keep].contiguous(), pre, (n + 1) // 2, cut, nq, nkv, d)
     assert A.max() < 20
     _check(f"masked extremes, {_prefix_path(d, nq, nkv, P1, S2)}", got[keep], O, A)
+
+
+# ---- fp16 output (out_f16: the O-projection's operand under precise_stream = 2), all five kernels.  Bound: 2^-11 |O| + c 2^-11 A + 1e-6.
+def _two_roundings(what, got16, got_bf):
+    """the bf16-output launch of the same inputs holds bf16(fp16 output) wherever that is normal; either neighbour where the fp16 value is a
+    bf16 midpoint: the two launches differ in the last conversion only"""
+    lo, hi, checked = R.bf16_of_fp16_allowed(got16)
+    b = got_bf.double()
+    bad = checked & (b != lo) & (b != hi)
+    assert not bad.any(), f"{what}: {int(bad.sum())} / {bad.numel()} elements of the bf16-output launch are not the bf16 rounding of the fp16-output launch's"
+    assert checked.float().mean() > 0.9
+
+
+F16_PARITY = ["d64_resident_ignores_the_list", "d64_g4_long", "d128_g2_long", "d128_g6_two_parts", "8b_last_tile", "tiny"]
+
+
+@pytest.mark.parametrize("regime", ["flat", "large_scores"])
+@pytest.mark.parametrize("name", F16_PARITY)
+def test_fp16_output_against_fp64_and_against_the_bf16_launch(name, regime):
+    from lightretriever_amd import ops
+    _, nq, nkv, d, lens, last = _BY_NAME[name]
+    qkv, cu = _inputs(nq, nkv, d, lens)
+    qkv = _regime(qkv, nq, nkv, d, regime)
+    got = ops.attn_varlen_causal(qkv, cu, max(lens), nq, nkv, d, last_tile_only=last, out_dtype=torch.float16)
+    got_bf = ops.attn_varlen_causal(qkv, cu, max(lens), nq, nkv, d, last_tile_only=last)
+    _no_overflow()
+    assert got.dtype == torch.float16
+    # the launch without a list (the kernel walks its items itself: another instantiation of the same store) writes the same bits
+    assert torch.equal(got, ops.attn_varlen_causal(qkv, cu, max(lens), nq, nkv, d, last_tile_only=last, work_list=False, out_dtype=torch.float16))
+    O, A = R.causal_gqa_fp64(qkv, cu, nq, nkv, d)
+    if last:
+        ln = torch.tensor(lens, device="cuda")
+        start = torch.repeat_interleave(cu[:-1].long(), ln)
+        keep = torch.arange(sum(lens), device="cuda") - start >= torch.repeat_interleave(((ln - 1) // 64) * 64, ln)
+        assert (got[~keep] == 0).all()
+        got, got_bf, O, A = got[keep], got_bf[keep], O[keep], A[keep]
+    _check(f"{_path(d, lens, last)}, {regime}, fp16 out", got, O, A, fmt="fp16")
+    _two_roundings(f"{name} {regime}", got, got_bf)
+
+
+@pytest.mark.parametrize("d,nq,nkv,P1,S2,n", PREFIX_EDGE_CASES)
+def test_prefix_suffix_fp16_output_against_fp64_and_against_the_bf16_launch(d, nq, nkv, P1, S2, n):
+    from lightretriever_amd import ops
+    suf, pre = _prefix_inputs(d, nq, nkv, P1, S2, n, d + nq + P1 + n)
+    got = ops.attn_prefix_suffix(suf, pre, n, S2, nq, nkv, d, out_dtype=torch.float16)
+    assert got.dtype == torch.float16
+    _check(_prefix_path(d, nq, nkv, P1, S2) + ", fp16 out", got, *R.prefix_suffix_fp64(suf, pre, n, S2, nq, nkv, d), fmt="fp16")
+    _two_roundings(f"prefix {(d, nq, nkv, P1, S2, n)}", got, ops.attn_prefix_suffix(suf, pre, n, S2, nq, nkv, d))
+
+
+def _attn16(qkv, lens, nq, nkv, d):
+    from lightretriever_amd import ops
+    out = ops.attn_varlen_causal(qkv, _cu(lens), max(lens), nq, nkv, d, out_dtype=torch.float16)
+    _no_overflow()
+    return out
+
+
+@_probe
+def test_fp16_output_first_row_is_its_own_value_row_to_all_11_bits(name, nq, nkv, d, lens):
+    """One visible key: p = 1, l = 1 to an fp32 rounding, O = v_0.  v is ANY fp16 number here: v (1 - 2^-24) is no fp16 midpoint, so the
+    fp16 rounding returns v itself -- all 11 bits, where the bf16-output probe needs bf16-exact values and sees 8."""
+    qkv = _randn16(sum(lens), (nq + 2 * nkv) * d, 31)
+    got = _attn16(qkv, lens, nq, nkv, d)
+    first = _cu(lens)[:-1].long()
+    want = _of_kv_head(qkv[first, (nq + nkv) * d:].view(len(lens), nkv, d), nq, nkv)
+    assert (want.to(torch.bfloat16).to(torch.float16) != want).float().mean() > 0.5      # (most values need more than bf16's bits)
+    assert torch.equal(got[first], want)
+
+
+def test_prefix_suffix_fp16_output_first_row_without_a_prefix():
+    d, nq, nkv, P1, S2, n = PREFIX_PROBE_LAYOUTS[-1]
+    suf, pre = _prefix_inputs(d, nq, nkv, P1, S2, n, 41)
+    from lightretriever_amd import ops
+    got = ops.attn_prefix_suffix(suf, pre, n, S2, nq, nkv, d, out_dtype=torch.float16)
+    assert torch.equal(got[::S2], _of_kv_head(suf[::S2, (nq + nkv) * d:].view(n, nkv, d), nq, nkv))
+
+
+def _within_one_fp16_step(got, want):
+    """got is `want` or one of its two fp16 neighbours: fp16 numbers of one sign are consecutive as bit patterns.  -> (all?, share != want)"""
+    g, w = got.to(torch.float16).view(torch.int16).int(), want.to(torch.float16).view(torch.int16).int()
+    assert (want.to(torch.float16).double() == want).all() and (want != 0).all()
+    return bool(((g - w).abs() <= 1).all()), float((g != w).double().mean())
+
+
+@_probe
+def test_fp16_output_constant_value_per_sequence_and_kv_head(name, nq, nkv, d, lens):
+    """v = c: O = c exactly, A = |c|.  Before the output rounding the kernel holds c (sum fp16(p_i)) / (sum p_i): within 2^-11 |c| of c (each
+    probability is rounded once, the weights are a convex combination) plus fp32 terms a thousand times smaller -- less than one and a half
+    fp16 steps at c, so the one fp16 rounding that follows lands on c or on an fp16 NEIGHBOUR of c, never farther.  (The bf16-output probe
+    can require c itself: there the internal error is an eighth of the output step.)  A neighbouring sequence's or head's c is a factor away."""
+    qkv = _randn16(sum(lens), (nq + 2 * nkv) * d, 32, scale=1.5)
+    c = _constants(len(lens) * nkv).view(len(lens), nkv)
+    assert c.abs().max() < 6e4 and torch.equal(c.to(torch.float16).double(), c) and c.unique().numel() == c.numel()
+    seq = torch.repeat_interleave(torch.arange(len(lens), device="cuda"), torch.tensor(lens, device="cuda"))
+    qkv[:, (nq + nkv) * d:] = c[seq][:, :, None].expand(-1, -1, d).reshape(sum(lens), nkv * d).to(torch.float16)
+    got = _attn16(qkv, lens, nq, nkv, d).double()
+    want = _of_kv_head(c[seq][:, :, None].expand(-1, -1, d), nq, nkv).contiguous()
+    ok, moved = _within_one_fp16_step(got, want)
+    print(f"{name}: {moved:.4f} of the outputs are a neighbour of c")
+    assert ok, ((got - want).abs() / want.abs()).max()
+    first = _cu(lens)[:-1].long()
+    assert torch.equal(got[first], want[first])                       # one key: nothing is rounded, c itself
+
+
+def _masked_extremes_fp16(name, nq, nkv, d, lens, top):
+    W, kcol = (nq + 2 * nkv) * d, nq * d
+    all_lens, keep_rows, ref_lens = [], [], []
+    s0 = 0
+    for i, n in enumerate(lens):
+        all_lens.append(40)
+        s0 += 40
+        cut = n if i == len(lens) - 1 or n < 4 else n - min(n // 2, 21)
+        all_lens.append(n)
+        keep_rows.append(torch.arange(s0, s0 + cut, device="cuda"))
+        ref_lens.append(cut)
+        s0 += n
+    T = sum(all_lens)
+    keep = torch.cat(keep_rows)
+    qkv = _randn16(T, W, 34, scale=1.5)
+    filled = torch.ones(T, dtype=torch.bool, device="cuda")
+    filled[keep] = False
+    qkv[filled, kcol:] = (_extremes(T, W - kcol)[filled].float() * (top / 65504.0)).to(torch.float16)
+    assert float(qkv[filled, kcol:].float().abs().min()) == top
+    got = _attn16(qkv, all_lens, nq, nkv, d)
+    return got, keep, all_lens, qkv, ref_lens
+
+
+@_probe
+def test_fp16_output_masked_rows_hold_extremes(name, nq, nkv, d, lens):
+    """test_masked_rows_hold_extremes with the fp16 store: +-65504 in every k / v row a compared row must not see.
+    Finiteness is required of the COMPARED rows only.  The fp16 store does not saturate, and |o| <= max |v| holds up to the rounding of
+    the probabilities: the kernel forms (sum fp16(p_i) v_i) / (sum p_i), and a dominant p_i (up to 2^8 under the lazy maximum) may be
+    rounded UP by 2^-11 of itself, so a filler row whose visible values are +-65504 -- fp16's largest number -- can reach 65504 (1 + 2^-11) >
+    65520 and is stored as inf.  Measured: the filler rows of every layout hold some.  One fp16 step below (the test after this one)
+    nothing can overflow.  In the encoder v = +-65504 exists only after the QKV store saturated, which lrx_device_saturation_count reports."""
+    got, keep, all_lens, qkv, ref_lens = _masked_extremes_fp16(name, nq, nkv, d, lens, 65504.0)
+    assert torch.isfinite(got[keep].float()).all()
+    print(f"{name}: {int((~torch.isfinite(got.float())).sum())} non-finite outputs in the filler rows (v = +-65504)")
+    O, A = R.causal_gqa_fp64(qkv[keep].contiguous(), _cu(ref_lens), nq, nkv, d)
+    assert A.max() < 20
+    _check(f"masked extremes, {_path(d, all_lens, False)}, fp16 out", got[keep], O, A, fmt="fp16")
+
+
+@pytest.mark.parametrize("name,nq,nkv,d,lens", [PROBE_LAYOUTS[0], PROBE_LAYOUTS[3]], ids=[PROBE_LAYOUTS[0][0], PROBE_LAYOUTS[3][0]])
+def test_fp16_output_is_finite_for_every_value_below_fp16s_largest(name, nq, nkv, d, lens):
+    """|v| <= 65472, the second largest fp16 number: 65472 (1 + 2^-11) (1 + a few 2^-24) < 65520, the smallest value that rounds to inf --
+    every output of every row, fillers included, is finite: the unsaturating store needs no clamp below fp16's largest number"""
+    got, keep, all_lens, qkv, ref_lens = _masked_extremes_fp16(name, nq, nkv, d, lens, 65472.0)
+    assert torch.isfinite(got.float()).all() and float(got.float().abs().max()) >= 65472.0
+
+
+@_prefix_probe
+def test_prefix_suffix_fp16_output_masked_rows_hold_extremes(d, nq, nkv, P1, S2, n):
+    from lightretriever_amd import ops
+    suf, pre = _prefix_inputs(d, nq, nkv, P1, S2, n, 44)
+    cut = S2 - 1
+    row = torch.arange(n * S2, device="cuda")
+    keep = ((row // S2) % 2 == 0) & (row % S2 < cut)
+    kcol = nq * d
+    suf[~keep, kcol:] = _extremes(n * S2, suf.shape[1] - kcol)[~keep]
+    got = ops.attn_prefix_suffix(suf, pre, n, S2, nq, nkv, d, out_dtype=torch.float16)
+    assert torch.isfinite(got[keep].float()).all()                   # (the filler rows: see test_fp16_output_masked_rows_hold_extremes)
+    O, A = R.prefix_suffix_fp64(suf[keep].contiguous(), pre, (n + 1) // 2, cut, nq, nkv, d)
+    assert A.max() < 20
+    _check(f"masked extremes, {_prefix_path(d, nq, nkv, P1, S2)}, fp16 out", got[keep], O, A, fmt="fp16")
 
 
 def test_zz_worst_ratio_per_case_group(request, capsys):

@@ -160,6 +160,52 @@ def test_embed_stream32(H):
     _record("embed_stream32", [len(ids), H], rstd_max_rel=worst, budget=ER.rstd_budget(H))
 
 
+def saturations():
+    from lightretriever_amd import _lib
+    return int(_lib.lib().lrx_device_saturation_count(1))
+
+
+@pytest.mark.parametrize("H", ER.EMBED_H)
+def test_embed_stream32_fp16_operand(H):
+    """k_embed_stream32<true> (lrx_embed_stream32_ex, f16 = 1: the first launch of every default encoder): a16 is bit-equal to the
+    saturating fp16 rounding of x * gamma -- the product of two bf16 numbers is exact in fp32, one rounding in all, budget zero -- and x32
+    and rs are the bits the bf16 variant writes for the same inputs; a bad id gives a zero row and is counted"""
+    from lightretriever_amd import ops
+    table, ids, gamma = ER.embed_inputs(H)
+    x32, a16, rs = ER.embed_stream32(table, ids, gamma, ER.EPS, f16=True)
+    td, idd, gd = bf(table), i32(ids), bf(gamma)
+    bx, ba, br = ops.embed_stream32(td, idd, gd, ER.EPS)
+    errors(), saturations()
+    gx, ga, gr = ops.embed_stream32(td, idd, gd, ER.EPS, a16_dtype=torch.float16)
+    assert ga.dtype == torch.float16
+    np.testing.assert_array_equal(host(ga), a16)
+    np.testing.assert_array_equal(host(gx), x32)
+    assert torch.equal(gx, bx) and torch.equal(gr, br)                                     # the flag changes a16 alone
+    assert (host(ga)[[2, 3]] == 0).all() and errors() == 2 and saturations() == 0
+    # what the test can see: the fp16 operand is not the bf16 operand converted (3 more bits survive), on a large share of the elements
+    assert (host(ga) != host(ba)).mean() > 0.5
+
+
+def test_embed_stream32_fp16_operand_saturates_by_sign_and_counts_every_element():
+    """a norm weight of +-2^18 on two columns: |x * gamma| > 65504 wherever |x| >= 0.25 -- stored as +-65504 by sign, counted once per
+    ELEMENT (this kernel has no wave vote); everything else bit-exact; the counter reads 0 after the reset"""
+    from lightretriever_amd import ops
+    H = 896
+    table, ids, gamma = ER.embed_inputs(H)
+    gamma = gamma.copy()
+    gamma[5], gamma[H - 3] = 2.0 ** 18, -2.0 ** 18
+    x32, a16, _ = ER.embed_stream32(table, ids, gamma, ER.EPS, f16=True)
+    pre = x32 * gamma.astype(np.float64)
+    n_sat = int((np.abs(pre) > 65504).sum())
+    assert n_sat >= 4 and (a16 == 65504).any() and (a16 == -65504).any() and (np.abs(pre[:, [5, H - 3]]) < 65504).sum() >= 4       # (two zero rows)
+    assert (ER.fp16_ieee(pre) != a16).sum() == n_sat                                       # the store without the clamp differs exactly there
+    saturations()
+    _, ga, _ = ops.embed_stream32(bf(table), i32(ids), bf(gamma), ER.EPS, a16_dtype=torch.float16)
+    np.testing.assert_array_equal(host(ga), a16)
+    assert saturations() == n_sat
+    assert saturations() == 0
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # pooling + final norm
 # ---------------------------------------------------------------------------------------------------------------
