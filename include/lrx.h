@@ -847,6 +847,58 @@ int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t 
                            int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* (added in ABI 9, additively) RANGE SEARCH over the probed cells -- faiss IndexIVF::range_search_preassigned with METRIC_INNER_PRODUCT, for
+ * the four inverted-file entries.  Each lrx_ivf_*_ip_range_search takes the argument list of its top-k sibling with `k`
+ * replaced by `float radius` and (out_scores, out_ids) by (lims, out_scores, out_ids, capacity); each *_range_workspace_bytes takes its
+ * sibling's arguments without k.  It is the sibling's chain up to and including the scan -- the same host driver, the same kernels, the same
+ * packed (score, row) words -- followed by a count, a prefix sum and an ordered fill instead of the selection.
+ *   hit         a row the top-k search of the same arguments would have scanned whose score is STRICTLY greater than radius.  Scanned: the row
+ *               lies in a cell the query's probe row names -- an entry < 0 is skipped; an entry >= nlist is skipped and counted once in
+ *               lrx_device_error_count; a cell named twice is scanned once; a query whose cells hold more than max_scan_rows scans nothing, has
+ *               no hits and is counted once.  Score: the fp32 value the sibling search reports for that (query, row), bit for bit.  The
+ *               comparison is the float comparison score > radius: -0.0 and +0.0 are equal, a score equal to the radius is not a hit,
+ *               radius = +inf gives no hits, radius = -inf every scanned row.  A NaN radius is LRX_ERR_INVALID before any device work.  A stored
+ *               position whose original row is outside [0, n_rows) (dropped and counted by the scan) is never a hit.
+ *   order       SEGMENT order, faiss's order for an IVF range search: the query's cells in the order of its probe row (after the skips above),
+ *               inside a cell the rows by stored position -- ascending original row when the rows were added in order.  It depends on the
+ *               query's own rows of q, probes and probe_scores alone, never on the batch.  It is NOT the ascending-row order of
+ *               lrx_flat_ip_range_search, and hits are not sorted by score.
+ *   layout      lrx_flat_ip_range_search's protocol: lims int64 [n_queries + 1] on the device, lims[0] = 0, hits of query i at
+ *               [lims[i], lims[i + 1]) of out_scores / out_ids; out_ids = id_base + row, or row_map[row] when row_map != NULL.  lims is ALWAYS
+ *               written and exact.  out_scores / out_ids are written only where they fit `capacity` entries, decided on the device per chunk
+ *               of queries (a chunk whose lims end exceeds capacity writes nothing); the call returns LRX_OK either way: read lims[n_queries]
+ *               and call again with at least that capacity.  capacity == 0 allows NULL out_scores / out_ids.  n_queries == 0 writes lims[0].
+ *   limits      the sibling's argument checks, unchanged, without k; capacity >= 0; lims != NULL.  Workspace: the sibling's plus one uint32
+ *               hit count per query of a chunk (lrx_ivf_*_ip_range_workspace_bytes >= the sibling's for any k); less is LRX_ERR_WORKSPACE.
+ * Per chunk of queries (the sibling's chunk; lims carried across chunks on the device) the sibling's launches up to the scan, then three: the
+ * count (one 1024-thread workgroup per query over its segment of words), the chunk's lims, and the fill -- the same walk with a stable
+ * compaction (wave ballot and popcount, wave totals through LDS, a running base per workgroup), no atomics on the output.  No host
+ * synchronisation, every size from the arguments alone, one stream. */
+size_t lrx_ivf_flat_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows);
+int lrx_ivf_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                 int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe,
+                                 int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids,
+                                 int64_t capacity, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream);
+size_t lrx_ivf_pq_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t M, int32_t n_queries, int32_t nprobe,
+                                           int64_t max_scan_rows);
+int lrx_ivf_pq_ip_range_search(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                               const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                               const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius,
+                               int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map,
+                               void* workspace, size_t workspace_bytes, void* stream);
+size_t lrx_ivf_sq_fp16_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows);
+int lrx_ivf_sq_fp16_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                    const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe,
+                                    int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims,
+                                    float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+size_t lrx_ivf_sq8_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows);
+int lrx_ivf_sq8_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius,
+                                int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* (added in ABI 8, additively) INVERTED FILE over PRODUCT-QUANTISED codes: the top k under the ADC score over the rows of the cells a query
  * probes -- the scan of faiss IndexIVFPQ(quantizer, d, nlist, M, 8, METRIC_INNER_PRODUCT) (IVFPQIndex).  The caller owns the
  * coarse quantiser: it passes the probe lists and, with by_residual, the coarse scores of the probed cells.

@@ -89,15 +89,25 @@ SIGNATURES = {
     "lrx_sq_fp16_ip_rerank": (_I32, [_P, _I64, _I32, _P, _I32, _P, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "lrx_ivf_flat_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_flat_ip_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _I64, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_ivf_flat_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I64]),
+    "lrx_ivf_flat_ip_range_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _I64, _I64, _F, _I64, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "lrx_ivf_pq_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_pq_ip_search": (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_ivf_pq_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
+    "lrx_ivf_pq_ip_range_search": (_I32, [_P, _I64, _P, _I32, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _F, _I64, _P, _P, _P, _I64, _P, _P, _SZ,
+                                          _P]),
     "lrx_ivf_sq_fp16_group_rows": (_I32, [_I32]),
     "lrx_ivf_sq_fp16_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_sq_fp16_ip_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_ivf_sq_fp16_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I64]),
+    "lrx_ivf_sq_fp16_ip_range_search": (_I32, [_P, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _F, _I64, _P, _P, _P, _I64, _P, _P, _SZ, _P]),
     "lrx_ivf_sq_fp16_encode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I64, _P]),
     "lrx_ivf_sq8_group_rows": (_I32, [_I32]),
     "lrx_ivf_sq8_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_sq8_ip_search": (_I32, [_P, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_ivf_sq8_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I64]),
+    "lrx_ivf_sq8_ip_range_search": (_I32, [_P, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I32, _P, _P, _I32, _I64, _I32, _I64, _F, _I64, _P, _P, _P, _I64, _P, _P, _SZ,
+                                           _P]),
     "lrx_ivf_sq8_encode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _I64, _P]),
     "lrx_ivf_sq8_decode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I32, _P, _P, _I32, _P, _I64, _P]),
     "lrx_pq_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),

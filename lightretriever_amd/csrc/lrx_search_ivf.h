@@ -1,5 +1,6 @@
 // liblrx search, part L -- INVERTED FILE (faiss IndexIVFFlat, inner product): the exact top k over the rows of the cells a query probes.
-// k_ivf_plan, k_ivf_scan, k_ivf_select, lrx_ivf_flat_ip_search (contract: include/lrx.h).
+// k_ivf_plan, k_ivf_scan, k_ivf_select, lrx_ivf_flat_ip_search (contract: include/lrx.h); and the range search over the same
+// cells: k_ivf_range, lrx_ivf_flat_ip_range_search.
 // Part of the ONE translation unit lrx_search.hip (included at its end: it reuses exact_dot_lds_row, the counting sort k_pairs_scan /
 // k_pairs_scatter, the radix select and the register sort).  Not a stand-alone header.
 //
@@ -15,8 +16,11 @@
 //                  the cell -- one half-wave per (query, row), the query row streamed from L2 (exact_dot_lds_row: the bits of exact_dot) --
 //                  writing packed (score, ORIGINAL row) words into the queries' segments.  Cells nobody probes cost nothing.
 //   k_ivf_select   one workgroup per query: sorted top k of its segment (counting ranks / register sort up to 2048 words, radix select above).
+//   (a range search ends the chunk differently: k_ivf_range<false> counts the words above the radius, k_range_lims turns the counts into
+//   lims, k_ivf_range<true> writes them in segment order -- see k_ivf_range)
 // Every size depends on the arguments alone; nothing is read back to the host.  The host driver of this chain is ivf_cell_major_search, shared
-// with the scan over fp16 codes (lrx_search_ivfsq.h): an entry brings its row check, its group size and the launch of its scan.
+// with the scans over fp16 and 8-bit codes (lrx_search_ivfsq.h, lrx_search_ivfsq8.h): an entry brings its row check, its group size and the
+// launch of its scan, and an IvfOut that says how the segments leave (top k, or everything above a radius).
 #pragma once
 
 #define IVF_MAX_NPROBE 2048
@@ -331,6 +335,70 @@ k_ivf_select(const unsigned long long* __restrict__ words, int64_t max_scan, con
   }
 }
 
+// RANGE SEARCH over the probed cells (faiss IndexIVF::range_search_preassigned): the chain above with k_ivf_select replaced
+// by k_ivf_range<false> (count), k_range_lims (lrx_search_range.h) and k_ivf_range<true> (fill).  One workgroup per query walks its segment
+// in 1024-word tiles, word i of a tile on thread i; a hit is a non-null word whose score -- key2f of its key, the value k_ivf_select reports --
+// is > radius as a float comparison.  scanned == 0: the scan did not run (a shard without rows), the segment holds nothing.
+//   FILL = false   surv[query] = its hits (0 for a query over max_scan_rows).
+//   FILL = true    the hits leave in SEGMENT order -- cells in probe order, rows by stored position -- by a stable compaction: the rank of a
+//                  hit is the hits of the tiles before (a running base, uniform over the workgroup) + those of the waves before it in its
+//                  tile (wave totals through LDS) + those of the lanes below it (ballot and popcount).  No atomics: the order is by
+//                  construction, and the slot lims[query] + rank is below lims[query + 1] <= *lims_end <= capacity because both passes
+//                  evaluate one predicate over the same words.  Nothing is written when the chunk's results do not fit: *lims_end > capacity.
+template <bool FILL>
+__global__ void __launch_bounds__(1024)
+k_ivf_range(const unsigned long long* __restrict__ words, int64_t max_scan, const int64_t* __restrict__ q_tot, int scanned, float radius,
+            unsigned int* __restrict__ surv, const int64_t* __restrict__ lims, const int64_t* __restrict__ lims_end, int64_t capacity, int64_t id_base,
+            const int64_t* __restrict__ row_map, float* __restrict__ out_scores, int64_t* __restrict__ out_ids) {
+  __shared__ unsigned int s_w[2][16];                        // wave totals, double-buffered: one barrier per tile
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, qi = blockIdx.x;
+  if (FILL && *lims_end > capacity) return;                  // (workgroup-uniform)
+  const int64_t tot = scanned ? q_tot[qi] : 0;
+  const int n = tot < 0 ? 0 : (int)tot;
+  const unsigned long long* list = words + (int64_t)qi * max_scan;
+  const int64_t base = FILL ? lims[qi] : 0;
+  unsigned int run = 0;                                      // FILL: hits of the tiles before (uniform); else: this thread's hits
+  int buf = 0;
+  for (int64_t t0 = 0; t0 < n; t0 += 1024, buf ^= 1) {        // (64-bit: n may lie within 1024 of 2^31)
+    const int64_t i = t0 + tid;
+    const unsigned long long w = i < n ? list[i] : 0ull;
+    const float sc = key2f((uint32_t)(w >> 32));
+    const bool hit = w != 0ull && sc > radius;
+    if (!FILL) {
+      run += hit ? 1u : 0u;
+      continue;
+    }
+    const unsigned long long bal = __ballot(hit);
+    if (lane == 0) s_w[buf][wave] = (unsigned int)__popcll(bal);
+    __syncthreads();
+    unsigned int before = 0, all = 0;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const unsigned int c = s_w[buf][v];
+      before += v < wave ? c : 0u;
+      all += c;
+    }
+    if (hit) {
+      const int64_t pos = base + run + before + (unsigned int)__popcll(bal & ((1ull << lane) - 1ull));
+      const int64_t row = sel_row(w);
+      out_scores[pos] = sc;
+      out_ids[pos] = row_map != nullptr ? row_map[row] : id_base + row;
+    }
+    run += all;
+  }
+  if (!FILL) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) run += __shfl_down(run, o, 64);
+    if (lane == 0) s_w[0][wave] = run;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned int all = 0;
+      for (int v = 0; v < 16; ++v) all += s_w[0][v];
+      surv[qi] = all;
+    }
+  }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 static int ivf_chunk_queries(int32_t n_queries, int64_t max_scan_rows) {
   const size_t per = (size_t)(max_scan_rows > 0 ? max_scan_rows : 1) * 8;
@@ -364,6 +432,69 @@ extern "C" size_t lrx_ivf_flat_ip_workspace_bytes(int64_t n_rows, int32_t nlist,
   return ivf_plan(nlist, ivf_chunk_queries(n_queries, max_scan_rows), nprobe, max_scan_rows).total;
 }
 
+// How the segments of a call leave the chain: the sorted top k of each (k_ivf_select), or every word above a radius (k_ivf_range; contract of
+// lrx_ivf_flat_ip_range_search in include/lrx.h).  The two host drivers -- ivf_cell_major_search below and ivf_pq_run (lrx_search_ivfpq.h) --
+// take one, so a search and its range search are ONE chain and one set of argument checks up to this point.
+struct IvfOut {
+  bool range;
+  int32_t k;                                // top k: out_scores / out_ids are [n_queries, k]
+  float radius;                             // range: hits are the words with a score > radius, ...
+  int64_t* lims;                            //   ... query i's at [lims[i], lims[i + 1]) of out_scores / out_ids (device, [n_queries + 1]) ...
+  int64_t capacity;                         //   ... which hold this many entries: a chunk that does not fit writes lims alone
+  int64_t id_base;
+  const int64_t* row_map;
+  float* out_scores;
+  int64_t* out_ids;
+};
+static IvfOut ivf_out_topk(int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map) {
+  return IvfOut{false, k, 0.f, nullptr, 0, id_base, row_map, out_scores, out_ids};
+}
+static IvfOut ivf_out_range(float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map) {
+  return IvfOut{true, 0, radius, lims, capacity, id_base, row_map, out_scores, out_ids};
+}
+
+// The checks of the output side that need no pointer but lims (made before the n_queries == 0 return)
+static int ivf_out_check(const char* who, const IvfOut& o) {
+  if (!o.range) {
+    LRX_CHECK_ARG(o.k >= 1 && o.k <= SEL_MAXK, "%s: k=%d out of range (1..%d)", who, o.k, SEL_MAXK);
+    return LRX_OK;
+  }
+  LRX_CHECK_ARG(o.radius == o.radius, "%s: radius is NaN", who);
+  LRX_CHECK_ARG(o.capacity >= 0, "%s: capacity=%lld must be >= 0", who, (long long)o.capacity);
+  LRX_CHECK_ARG(o.lims != nullptr, "%s: null lims", who);
+  return LRX_OK;
+}
+// ... and of its pointers (a range search with capacity 0 writes lims alone)
+static bool ivf_out_ptrs_ok(const IvfOut& o) { return (o.out_scores != nullptr && o.out_ids != nullptr) || (o.range && o.capacity == 0); }
+// n_queries == 0: a top-k search has nothing to write, a range search writes lims[0] = 0
+static int ivf_out_empty(const IvfOut& o, hipStream_t s) {
+  if (o.range) LRX_HIP(hipMemsetAsync(o.lims, 0, sizeof(int64_t), s));
+  return LRX_OK;
+}
+// The range search's own workspace, behind the search's: one uint32 hit count per query of a chunk
+static size_t ivf_out_ws_bytes(bool range, int chunk) { return range ? align256((size_t)(chunk > 0 ? chunk : 1) * sizeof(unsigned int)) : 0; }
+
+// The end of a chunk (its queries start at q0 of the call's): surv is the range search's workspace; scanned: the scan ran.
+static int ivf_out_launch(const IvfOut& o, hipStream_t s, const unsigned long long* words, int64_t max_scan_rows, const int64_t* q_tot, unsigned int* surv,
+                          int q0, int nq, int scanned) {
+  if (!o.range) {
+    hipLaunchKernelGGL(k_ivf_select, dim3(nq), dim3(1024), 0, s, words, max_scan_rows, q_tot, (int)o.k, o.id_base, o.row_map,
+                       o.out_scores + (int64_t)q0 * o.k, o.out_ids + (int64_t)q0 * o.k);
+    LRX_LAUNCH_CHECK();
+    return LRX_OK;
+  }
+  int64_t* lc = o.lims + q0;                                 // this chunk's lims: lc[0] was written by the chunk before
+  hipLaunchKernelGGL(k_ivf_range<false>, dim3(nq), dim3(1024), 0, s, words, max_scan_rows, q_tot, scanned, o.radius, surv, (const int64_t*)lc,
+                     (const int64_t*)lc + nq, o.capacity, o.id_base, o.row_map, o.out_scores, o.out_ids);
+  LRX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_range_lims, dim3(1), dim3(1024), 0, s, (const unsigned int*)surv, nq, lc, q0 == 0 ? 1 : 0);
+  LRX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ivf_range<true>, dim3(nq), dim3(1024), 0, s, words, max_scan_rows, q_tot, scanned, o.radius, surv, (const int64_t*)lc,
+                     (const int64_t*)lc + nq, o.capacity, o.id_base, o.row_map, o.out_scores, o.out_ids);
+  LRX_LAUNCH_CHECK();
+  return LRX_OK;
+}
+
 // What a cell-major scan is handed per chunk (ivf_cell_major_search below): the chunk's queries start at q0 of the call's.
 struct IvfScanArgs {
   hipStream_t stream;
@@ -379,14 +510,15 @@ struct IvfScanArgs {
 // The host driver of the CELL-MAJOR chain, shared by lrx_ivf_flat_ip_search and lrx_ivf_sq_fp16_ip_search (lrx_search_ivfsq.h): the argument
 // checks both contracts have in common (`who` names the entry in the messages; rows_ok / rows_why: the entry's own check of its row store, made
 // by the caller), the workspace, and per chunk k_ivf_clear, k_ivf_plan<false>, k_ivf_items, k_pairs_scatter, the entry's scan -- launched by
-// `scan(const IvfScanArgs&)` over groups of G stored rows -- and k_ivf_select.  Kernels only, one stream, nothing read back.
+// `scan(const IvfScanArgs&)` over groups of G stored rows -- and the end `out` asks for: k_ivf_select, or the three kernels of the range search
+// (the *_range_search entries are this driver with an IvfOut of the other kind).  Kernels only, one stream, nothing read back.
 template <class Scan>
 static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok, const char* rows_why, int G, int64_t n_rows, int32_t dim,
                                  const int64_t* list_off, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe,
-                                 int64_t ld_probe, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
-                                 const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream, Scan scan) {
+                                 int64_t ld_probe, int64_t max_scan_rows, const IvfOut& out, void* workspace, size_t workspace_bytes, void* stream,
+                                 Scan scan) {
   LRX_CHECK_ARG(dim >= 32 && dim <= 8192 && dim % 32 == 0, "%s: dim=%d must be a multiple of 32 in 32..8192", who, dim);
-  LRX_CHECK_ARG(k >= 1 && k <= SEL_MAXK, "%s: k=%d out of range (1..%d)", who, k, SEL_MAXK);
+  if (int rc = ivf_out_check(who, out)) return rc;
   LRX_CHECK_ARG(nlist >= 1, "%s: nlist=%d must be >= 1", who, nlist);
   LRX_CHECK_ARG(nprobe >= 1 && nprobe <= IVF_MAX_NPROBE && nprobe <= nlist, "%s: nprobe=%d out of range (1..min(nlist=%d, %d))", who, nprobe, nlist,
                 IVF_MAX_NPROBE);
@@ -395,18 +527,17 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
   LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "%s: max_scan_rows=%lld out of range (0..2^31 - 1)", who, (long long)max_scan_rows);
   LRX_CHECK_ARG(rows_ok, "%s: %s", who, rows_why);
   LRX_CHECK_ARG(n_queries >= 0, "%s: n_queries=%d", who, n_queries);
-  if (n_queries == 0) return LRX_OK;
-  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && out_scores != nullptr && out_ids != nullptr && (rows != nullptr || n_rows == 0),
-                "%s: null pointer", who);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_queries == 0) return ivf_out_empty(out, s);
+  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && ivf_out_ptrs_ok(out) && (rows != nullptr || n_rows == 0), "%s: null pointer", who);
   LRX_CHECK_ARG((uintptr_t)q % 16 == 0, "%s: q must be 16-byte aligned", who);
-  const size_t need = lrx_ivf_flat_ip_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, k, max_scan_rows);
+  const int chunk = ivf_chunk_queries(n_queries, max_scan_rows);
+  const IvfPlan p = ivf_plan(nlist, chunk, nprobe, max_scan_rows);
+  const size_t need = p.total + ivf_out_ws_bytes(out.range, chunk);
   if (workspace == nullptr || workspace_bytes < need) {
     lrx_set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, need);
     return LRX_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int chunk = ivf_chunk_queries(n_queries, max_scan_rows);
-  const IvfPlan p = ivf_plan(nlist, chunk, nprobe, max_scan_rows);
   char* ws = (char*)workspace;
   unsigned int* total = (unsigned int*)ws;
   unsigned int* cell_cnt = total + 1;
@@ -417,6 +548,7 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
   unsigned int* seg_off = (unsigned int*)(ws + p.off_seg);
   int64_t* q_tot = (int64_t*)(ws + p.off_tot);
   unsigned long long* words = (unsigned long long*)(ws + p.off_words);
+  unsigned int* surv = (unsigned int*)(ws + p.total);        // (the range search's)
   const int64_t ngroups = lrx_cdiv(n_rows, G);
   const int64_t item_cap = ngroups + nlist;                  // a cell's last group may be partial
   const int64_t scan_wgs = item_cap < 8 * (int64_t)lrx_cu_count() ? item_cap : 8 * (int64_t)lrx_cu_count();
@@ -442,23 +574,42 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
       scan(a);
       LRX_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_ivf_select, dim3(nq), dim3(1024), 0, s, (const unsigned long long*)words, max_scan_rows, (const int64_t*)q_tot, (int)k, id_base, row_map,
-                       out_scores + (int64_t)q0 * k, out_ids + (int64_t)q0 * k);
-    LRX_LAUNCH_CHECK();
+    if (int rc = ivf_out_launch(out, s, words, max_scan_rows, q_tot, surv, q0, nq, ngroups > 0 ? 1 : 0)) return rc;
   }
   return LRX_OK;
+}
+
+// lrx_ivf_flat_ip_search and lrx_ivf_flat_ip_range_search: the driver over k_ivf_scan
+static int ivf_flat_run(const char* who, const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                        const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows, const IvfOut& out,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+  char why[128];
+  snprintf(why, sizeof(why), "rows must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)", (long long)ldx, dim);
+  return ivf_cell_major_search(who, X, ldx >= dim && ldx % 4 == 0 && (uintptr_t)X % 16 == 0, why, dim > 0 ? ivf_group_rows(dim) : 1, n_rows, dim, list_off, nlist,
+                               q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
+    hipLaunchKernelGGL(k_ivf_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, X, n_rows, ldx, (int)dim, a.G, list_off, row_ids, (int)nlist, a.q,
+                       (int)nprobe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+  });
 }
 
 extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
                                       const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
                                       int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  char why[128];
-  snprintf(why, sizeof(why), "rows must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)", (long long)ldx, dim);
-  return ivf_cell_major_search("ivf_flat_ip_search", X, ldx >= dim && ldx % 4 == 0 && (uintptr_t)X % 16 == 0, why, dim > 0 ? ivf_group_rows(dim) : 1, n_rows,
-                               dim, list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, k, id_base, out_scores, out_ids, row_map,
-                               workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
-    hipLaunchKernelGGL(k_ivf_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, X, n_rows, ldx, (int)dim, a.G, list_off, row_ids, (int)nlist, a.q,
-                       (int)nprobe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
-  });
+  return ivf_flat_run("ivf_flat_ip_search", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
+                      ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+}
+
+// The workspace of the cell-major range searches (flat, fp16 codes, 8-bit codes): the search's plus the hit counts of a chunk
+extern "C" size_t lrx_ivf_flat_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows) {
+  return lrx_ivf_flat_ip_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, 1, max_scan_rows) +
+         ivf_out_ws_bytes(true, ivf_chunk_queries(n_queries, max_scan_rows));
+}
+
+extern "C" int lrx_ivf_flat_ip_range_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                            int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe,
+                                            int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids,
+                                            int64_t capacity, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_flat_run("ivf_flat_ip_range_search", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
+                      ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace, workspace_bytes, stream);
 }

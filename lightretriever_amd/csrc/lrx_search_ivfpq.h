@@ -10,7 +10,8 @@
 //   k_ivf_pq_scan     QUERY-MAJOR: the large operand of a PQ scan is the query's table (M KiB), the codes are small (M bytes per row), so a
 //                     workgroup keeps ONE query's table in LDS and walks 1024-position tiles of that query's segment -- the concatenation of
 //                     its probed non-empty cells in probe order
-//   k_ivf_select      one workgroup per query: sorted top k of its segment (unchanged)
+//   k_ivf_select      one workgroup per query: sorted top k of its segment (unchanged); lrx_ivf_pq_ip_range_search ends the chunk with
+//                     k_ivf_range<false>, k_range_lims and k_ivf_range<true> instead (lrx_search_ivf.h)
 // Nothing needs zeroing (the dense plan emits no pairs and no counts), so there is no clear kernel and no memset.  Every size depends on the
 // arguments alone; nothing is read back to the host.
 #pragma once
@@ -135,36 +136,39 @@ extern "C" size_t lrx_ivf_pq_ip_workspace_bytes(int64_t n_rows, int32_t nlist, i
   return ivf_pq_plan(M, n_queries, nprobe, max_scan_rows).total;
 }
 
-extern "C" int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
-                                    const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
-                                    const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
-                                    int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "ivf_pq_ip_search: dim=%d is not a multiple of M=%d", dim, M);
-  LRX_CHECK_ARG(k >= 1 && k <= SEL_MAXK, "ivf_pq_ip_search: k=%d out of range (1..%d)", k, SEL_MAXK);
-  LRX_CHECK_ARG(nlist >= 1, "ivf_pq_ip_search: nlist=%d must be >= 1", nlist);
-  LRX_CHECK_ARG(nprobe >= 1 && nprobe <= IVF_MAX_NPROBE && nprobe <= nlist, "ivf_pq_ip_search: nprobe=%d out of range (1..min(nlist=%d, %d))", nprobe, nlist,
+// lrx_ivf_pq_ip_search and lrx_ivf_pq_ip_range_search: the QUERY-MAJOR host driver.  `out` (IvfOut, lrx_search_ivf.h) is how the segments leave:
+// k_ivf_select, or the range search's count, lims and fill, whose hit counts lie behind the search's workspace.
+static int ivf_pq_run(const char* who, const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                      const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
+                      int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "%s: dim=%d is not a multiple of M=%d", who, dim, M);
+  if (int rc = ivf_out_check(who, out)) return rc;
+  LRX_CHECK_ARG(nlist >= 1, "%s: nlist=%d must be >= 1", who, nlist);
+  LRX_CHECK_ARG(nprobe >= 1 && nprobe <= IVF_MAX_NPROBE && nprobe <= nlist, "%s: nprobe=%d out of range (1..min(nlist=%d, %d))", who, nprobe, nlist,
                 IVF_MAX_NPROBE);
-  LRX_CHECK_ARG(ld_probe >= nprobe, "ivf_pq_ip_search: ld_probe=%lld < nprobe=%d", (long long)ld_probe, nprobe);
-  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "ivf_pq_ip_search: rows=%lld out of range", (long long)n_rows);
-  LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "ivf_pq_ip_search: max_scan_rows=%lld out of range (0..2^31 - 1)", (long long)max_scan_rows);
-  LRX_CHECK_ARG(n_queries >= 0, "ivf_pq_ip_search: n_queries=%d", n_queries);
-  if (n_queries == 0) return LRX_OK;
-  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && pq_centroids != nullptr && out_scores != nullptr && out_ids != nullptr &&
+  LRX_CHECK_ARG(ld_probe >= nprobe, "%s: ld_probe=%lld < nprobe=%d", who, (long long)ld_probe, nprobe);
+  LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "%s: rows=%lld out of range", who, (long long)n_rows);
+  LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "%s: max_scan_rows=%lld out of range (0..2^31 - 1)", who, (long long)max_scan_rows);
+  LRX_CHECK_ARG(n_queries >= 0, "%s: n_queries=%d", who, n_queries);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_queries == 0) return ivf_out_empty(out, s);
+  LRX_CHECK_ARG(q != nullptr && probes != nullptr && list_off != nullptr && pq_centroids != nullptr && ivf_out_ptrs_ok(out) &&
                     (codes != nullptr || n_rows == 0),
-                "ivf_pq_ip_search: null pointer");
-  LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "ivf_pq_ip_search: by_residual=%d needs probe_scores", by_residual);
+                "%s: null pointer", who);
+  LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "%s: by_residual=%d needs probe_scores", who, by_residual);
   const IvfPqPlan p = ivf_pq_plan(M, n_queries, nprobe, max_scan_rows);
-  if (workspace == nullptr || workspace_bytes < p.total) {
-    lrx_set_error("ivf_pq_ip_search: workspace %zu B < required %zu B", workspace_bytes, p.total);
+  const size_t need = p.total + ivf_out_ws_bytes(out.range, p.chunk);
+  if (workspace == nullptr || workspace_bytes < need) {
+    lrx_set_error("%s: workspace %zu B < required %zu B", who, workspace_bytes, need);
     return LRX_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   float* lut = (float*)ws;
   unsigned int* seg_off = (unsigned int*)(ws + p.off_seg);
   int64_t* q_tot = (int64_t*)(ws + p.off_tot);
   unsigned long long* words = (unsigned long long*)(ws + p.off_words);
+  unsigned int* surv = (unsigned int*)(ws + p.total);        // (the range search's)
   const int Mp = pq_mp(M);
   const size_t smem = (size_t)(M < PQ_SCAN_MC ? M : PQ_SCAN_MC) * PQ_KSUB * 4;
   if (smem > (32u << 10)) LRX_HIP(hipFuncSetAttribute((const void*)k_ivf_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -186,9 +190,33 @@ extern "C" int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const flo
                          row_ids, (int)nlist, (const unsigned int*)seg_off, (const int64_t*)q_tot, max_scan_rows, words);
       LRX_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_ivf_select, dim3(nq), dim3(1024), 0, s, (const unsigned long long*)words, max_scan_rows, (const int64_t*)q_tot, (int)k, id_base, row_map,
-                       out_scores + (int64_t)q0 * k, out_ids + (int64_t)q0 * k);
-    LRX_LAUNCH_CHECK();
+    if (int rc = ivf_out_launch(out, s, words, max_scan_rows, q_tot, surv, q0, nq, 1)) return rc;
   }
   return LRX_OK;
+}
+
+extern "C" int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                                    const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                    const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                                    int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return ivf_pq_run("ivf_pq_ip_search", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
+                    by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t lrx_ivf_pq_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t M, int32_t n_queries, int32_t nprobe,
+                                                      int64_t max_scan_rows) {
+  (void)n_rows; (void)nlist; (void)dim;
+  const IvfPqPlan p = ivf_pq_plan(M, n_queries, nprobe, max_scan_rows);
+  return p.total + ivf_out_ws_bytes(true, p.chunk);
+}
+
+extern "C" int lrx_ivf_pq_ip_range_search(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                                          const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                          const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                          float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                          const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_pq_run("ivf_pq_ip_range_search", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                    ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace,
+                    workspace_bytes, stream);
 }

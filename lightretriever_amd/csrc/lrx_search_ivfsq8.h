@@ -211,18 +211,18 @@ extern "C" size_t lrx_ivf_sq8_ip_workspace_bytes(int64_t n_rows, int32_t nlist, 
   return lrx_ivf_flat_ip_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, k, max_scan_rows);
 }
 
-extern "C" int lrx_ivf_sq8_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
-                                     const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
-                                     const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
-                                     int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-  LRX_CHECK_ARG(sq8_qtype_ok(qtype), "ivf_sq8_ip_search: qtype=%d (0: QT_8bit, 2: QT_8bit_uniform)", qtype);
-  LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "ivf_sq8_ip_search: by_residual=%d needs probe_scores", by_residual);
-  LRX_CHECK_ARG(trained != nullptr && (uintptr_t)trained % 16 == 0, "ivf_sq8_ip_search: trained (vmin ++ vdiff) must be a 16-byte aligned pointer");
+// lrx_ivf_sq8_ip_search and lrx_ivf_sq8_ip_range_search: the driver over k_ivf_sq8_scan
+static int ivf_sq8_run(const char* who, const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                       const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
+                       int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  LRX_CHECK_ARG(sq8_qtype_ok(qtype), "%s: qtype=%d (0: QT_8bit, 2: QT_8bit_uniform)", who, qtype);
+  LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "%s: by_residual=%d needs probe_scores", who, by_residual);
+  LRX_CHECK_ARG(trained != nullptr && (uintptr_t)trained % 16 == 0, "%s: trained (vmin ++ vdiff) must be a 16-byte aligned pointer", who);
   const int uniform = qtype == SQ8_QT_8BIT_UNIFORM ? 1 : 0;
-  return ivf_cell_major_search("ivf_sq8_ip_search", codes, (uintptr_t)codes % 16 == 0, "codes must be 16-byte aligned", dim > 0 ? ivf_group_rows(dim) : 1,
-                               n_rows, dim, list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, k, id_base, out_scores, out_ids, row_map,
-                               workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
+  return ivf_cell_major_search(who, codes, (uintptr_t)codes % 16 == 0, "codes must be 16-byte aligned", dim > 0 ? ivf_group_rows(dim) : 1, n_rows, dim,
+                               list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, workspace, workspace_bytes, stream,
+                               [&](const IvfScanArgs& a) {
     const float* ps = by_residual ? probe_scores + (int64_t)a.q0 * ld_probe : (const float*)nullptr;
     if (uniform)
       hipLaunchKernelGGL(k_ivf_sq8_scan<true>, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const uint8_t*)codes, n_rows, (int)dim, a.G, trained, list_off,
@@ -231,6 +231,29 @@ extern "C" int lrx_ivf_sq8_ip_search(const void* codes, int64_t n_rows, int32_t 
       hipLaunchKernelGGL(k_ivf_sq8_scan<false>, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const uint8_t*)codes, n_rows, (int)dim, a.G, trained, list_off,
                          row_ids, (int)nlist, a.q, ps, (int)nprobe, ld_probe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
   });
+}
+
+extern "C" int lrx_ivf_sq8_ip_search(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                     const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                     const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                                     int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return ivf_sq8_run("ivf_sq8_ip_search", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
+                     by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t lrx_ivf_sq8_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows) {
+  return lrx_ivf_flat_ip_range_workspace_bytes(n_rows, nlist, dim, n_queries, nprobe, max_scan_rows);
+}
+
+extern "C" int lrx_ivf_sq8_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                           const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                           const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                           float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                           const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_sq8_run("ivf_sq8_ip_range_search", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                     ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace,
+                     workspace_bytes, stream);
 }
 
 // the argument checks the encode and decode entries share

@@ -338,12 +338,33 @@ std::tuple<at::Tensor, at::Tensor> sq_fp16_ip_rerank(const at::Tensor& q, const 
   return {o.d, o.i};
 }
 
+// The result protocol of every range-search op (lrx_flat_ip_range_search / lrx_sq_fp16_ip_range_search / lrx_pq_ip_range_search /
+// lrx_range_impact_search): `call(lims, d, i, cap)` runs the library call, lims[Q] is read back to the host once, and the call is repeated
+// once with the exact capacity when the first guess of 1024 hits per query was short.  Refused under graph capture before anything is launched.
+template <class Call>
+std::tuple<at::Tensor, at::Tensor, at::Tensor> range_result(const at::Tensor& like, int64_t Q, const char* who, Call call) {
+  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None, who,
+              " under graph capture: the result length is read back to the host");
+  const auto f32 = like.options().dtype(at::kFloat);
+  at::Tensor lims = at::zeros({Q + 1}, f32.dtype(at::kLong));
+  int64_t cap = Q * 1024;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    at::Tensor d = at::empty({cap}, f32), i = at::empty({cap}, f32.dtype(at::kLong));
+    lrx_check(call(lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap), who);
+    const int64_t n = lims[Q].item<int64_t>();
+    if (n <= cap) return {lims, d.narrow(0, 0, n), i.narrow(0, 0, n)};
+    cap = n;
+  }
+  TORCH_CHECK(false, who, ": the result grew between two identical calls");
+}
+
 // Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell, list_off int64 [nlist + 1], row_ids int64 [n_rows] (the
 // original row of a position) or None, probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted),
 // max_scan_rows = the caller's bound on the rows one query scans.  Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, int64_t k, int64_t max_scan_rows,
-                                                    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+// The argument checks ivf_flat_ip_topk and ivf_flat_ip_range_search share; fin(...) makes the library call from what they establish.
+template <class Fin>
+auto ivf_flat_ip_op(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
+    const at::Tensor& probes, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
   DevGuard guard(q.device());
   need(q, "q", at::kFloat, 2);
   need(x, "x", at::kFloat, 2);
@@ -352,34 +373,65 @@ std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const a
   const int64_t n_rows = x.size(0), dim = x.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
                   (probes.size(1) == 0 || probes.stride(1) == 1) && (n_rows <= 1 || x.stride(1) == 1),
-              "ivf_flat_ip_topk: q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_flat_ip_topk: sizes out of range");
+              who, ": q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
   const int64_t* ri = nullptr;
   if (row_ids.has_value() && row_ids->defined()) {
     need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, "ivf_flat_ip_topk: row_ids int64 [>= n_rows] contiguous");
+    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
     ri = row_ids->data_ptr<int64_t>();
   }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_flat_ip_topk: row_map int64 [>= n_rows] contiguous");
-  const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  TopK o = topk_out(q, k);
-  lrx_check(lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(), ri,
-                                   (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), (int32_t)nprobe,
-                                   probes.size(0) > 1 ? probes.stride(0) : nprobe, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
-                                   o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-            "ivf_flat_ip_topk");
-  return {o.d, o.i};
+  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
+  return fin(n_rows, dim, nlist, nprobe, ri, rm);
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, int64_t k, int64_t max_scan_rows,
+                                                    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_flat_ip_topk";
+return ivf_flat_ip_op(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map, [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe,
+                     const int64_t* ri, const int64_t* rm) -> std::tuple<at::Tensor, at::Tensor> {
+    const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    TopK o = topk_out(q, k);
+    lrx_check(lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(), ri,
+                                     (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), (int32_t)nprobe,
+                                     probes.size(0) > 1 ? probes.stride(0) : nprobe, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                     o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
+              who);
+    return {o.d, o.i};
+  });
+}
+
+// Range search over the probed cells (lrx_ivf_flat_ip_range_search): ivf_flat_ip_topk's arguments with radius for k.  Returns (lims, D, I), the
+// hits of a query in segment order (cells in probe order, rows by stored position).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, double radius,
+                                                                        int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_flat_ip_range_search";
+  return ivf_flat_ip_op(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map,
+                        [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const int64_t* rm) {
+    const int64_t Q = q.size(0);
+    const size_t wsb = lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+      return lrx_ivf_flat_ip_range_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
+                                          list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(),
+                                          (int32_t)nprobe, Q > 1 ? probes.stride(0) : nprobe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm,
+                                          ws.data_ptr(), wsb, cur_stream());
+    });
+  });
 }
 
 // Inverted file over PQ codes (lrx_ivf_pq_ip_search): codes = the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by
 // cell; pq_centroids [M, 256, D / M] fp32; list_off int64 [nlist + 1]; row_ids int64 [n_rows] (the original row of a position) or None -- n_rows
 // is its length, or the rows the code blocks hold; probes int64 [Q, nprobe] and, when by_residual, probe_scores fp32 [Q, nprobe] with the same
 // row stride (rows may be strided).  Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
-                                                  const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                  const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                  int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+// The argument checks ivf_pq_ip_topk and ivf_pq_ip_range_search share; fin(...) makes the library call from what they establish.
+template <class Fin>
+auto ivf_pq_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off, const
+    c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t
+    max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
   DevGuard guard(q.device());
   need(q, "q", at::kFloat, 2);
   need(pq_centroids, "pq_centroids", at::kFloat, 3);
@@ -388,49 +440,83 @@ std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at:
   const int64_t dim = q.size(1), M = pq_centroids.size(0), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
   TORCH_CHECK(q.is_contiguous() && pq_centroids.is_contiguous() && pq_centroids.size(1) == 256 && M > 0 && dim % M == 0 && pq_centroids.size(2) == dim / M &&
                   probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 && (nprobe == 0 || probes.stride(1) == 1),
-              "ivf_pq_ip_topk: q [Q,D] contiguous, pq_centroids [M,256,D/M] contiguous with D % M == 0, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_pq_ip_topk: sizes out of range");
+              who, ": q [Q,D] contiguous, pq_centroids [M,256,D/M] contiguous with D % M == 0, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
   const int64_t mp = (M + 15) / 16 * 16;
   TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1 && codes.is_contiguous(),
-              "ivf_pq_ip_topk: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)");
+              who, ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)");
   const int64_t* ri = nullptr;
   int64_t n_rows = codes.numel() / mp;
   if (row_ids.has_value() && row_ids->defined()) {
     need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous(), "ivf_pq_ip_topk: row_ids int64 [n_rows] contiguous");
+    TORCH_CHECK(row_ids->is_contiguous(), who, ": row_ids int64 [n_rows] contiguous");
     ri = row_ids->data_ptr<int64_t>();
     n_rows = row_ids->numel();
   }
-  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, "ivf_pq_ip_topk: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)");
+  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, (std::string(who) + ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)").c_str());
   const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
   const float* ps = nullptr;
   if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), "ivf_pq_ip_topk: by_residual needs probe_scores");
+    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
     need(*probe_scores, "probe_scores", at::kFloat, 2);
     TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
                     (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                "ivf_pq_ip_topk: probe_scores fp32 [Q, nprobe] with the row stride of probes");
+                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
     ps = probe_scores->data_ptr<float>();
   }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_pq_ip_topk: row_map int64 [>= n_rows] contiguous");
-  const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  TopK o = topk_out(q, k);
-  lrx_check(lrx_ivf_pq_ip_search(n_rows ? cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, list_off.data_ptr<int64_t>(), ri,
-                                 (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe,
-                                 by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb,
-                                 cur_stream()),
-            "ivf_pq_ip_topk");
-  return {o.d, o.i};
+  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
+  return fin(n_rows, dim, M, nlist, nprobe, cb, ri, ps, ld_probe, rm);
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
+                                                  const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                                                  const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
+                                                  int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_pq_ip_topk";
+return ivf_pq_ip_op(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows,
+                     int64_t dim, int64_t M, int64_t nlist, int64_t nprobe, void* cb, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) ->
+                     std::tuple<at::Tensor, at::Tensor> {
+    const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    TopK o = topk_out(q, k);
+    lrx_check(lrx_ivf_pq_ip_search(n_rows ? cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, list_off.data_ptr<int64_t>(), ri,
+                                   (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe,
+                                   by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb,
+                                   cur_stream()),
+              who);
+    return {o.d, o.i};
+  });
+}
+
+// Range search over the probed cells (lrx_ivf_pq_ip_range_search): ivf_pq_ip_topk's arguments with radius for k.  Returns (lims, D, I).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
+                                                                      const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
+                                                                      const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+                                                                      bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+                                                                      const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_pq_ip_range_search";
+  return ivf_pq_ip_op(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
+                      [&](int64_t n_rows, int64_t dim, int64_t M, int64_t nlist, int64_t nprobe, void* cb, const int64_t* ri, const float* ps,
+                          int64_t ld_probe, const int64_t* rm) {
+    const int64_t Q = q.size(0);
+    const size_t wsb = lrx_ivf_pq_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)M, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+      return lrx_ivf_pq_ip_range_search(n_rows ? cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, list_off.data_ptr<int64_t>(),
+                                        ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe,
+                                        by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm, ws.data_ptr(), wsb, cur_stream());
+    });
+  });
 }
 
 // Inverted file over fp16 codes (lrx_ivf_sq_fp16_ip_search): codes fp16 [n_rows, D] contiguous, row-major by stored position, cell by cell;
 // list_off int64 [nlist + 1]; row_ids int64 [n_rows] (the original row of a position) or None; probes int64 [Q, nprobe] and, when by_residual,
 // probe_scores fp32 [Q, nprobe] with the same row stride (rows may be strided).  Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-                                                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                       const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                       int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+// The argument checks ivf_sq_fp16_ip_topk and ivf_sq_fp16_ip_range_search share; fin(...) makes the library call from what they establish.
+template <class Fin>
+auto ivf_sq_fp16_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off, const c10::optional<at::Tensor>&
+    row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t max_scan_rows, const
+    c10::optional<at::Tensor>& row_map, Fin fin) {
   DevGuard guard(q.device());
   need(q, "q", at::kFloat, 2);
   need(codes, "codes", at::kHalf, 2);
@@ -439,41 +525,74 @@ std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, cons
   const int64_t n_rows = codes.size(0), dim = codes.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && codes.is_contiguous() && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
                   (nprobe == 0 || probes.stride(1) == 1),
-              "ivf_sq_fp16_ip_topk: q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_sq_fp16_ip_topk: sizes out of range");
+              who, ": q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
   const int64_t* ri = nullptr;
   if (row_ids.has_value() && row_ids->defined()) {
     need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, "ivf_sq_fp16_ip_topk: row_ids int64 [>= n_rows] contiguous");
+    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
     ri = row_ids->data_ptr<int64_t>();
   }
   const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
   const float* ps = nullptr;
   if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), "ivf_sq_fp16_ip_topk: by_residual needs probe_scores");
+    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
     need(*probe_scores, "probe_scores", at::kFloat, 2);
     TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
                     (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                "ivf_sq_fp16_ip_topk: probe_scores fp32 [Q, nprobe] with the row stride of probes");
+                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
     ps = probe_scores->data_ptr<float>();
   }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_sq_fp16_ip_topk: row_map int64 [>= n_rows] contiguous");
-  const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  TopK o = topk_out(q, k);
-  lrx_check(lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), ri, (int32_t)nlist,
-                                      q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe, by_residual ? 1 : 0,
-                                      max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-            "ivf_sq_fp16_ip_topk");
-  return {o.d, o.i};
+  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
+  return fin(n_rows, dim, nlist, nprobe, ri, ps, ld_probe, rm);
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
+                                                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                                                       const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
+                                                       int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_sq_fp16_ip_topk";
+return ivf_sq_fp16_ip_op(who, q, codes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows, int64_t dim,
+                     int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) -> std::tuple<at::Tensor, at::Tensor> {
+    const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    TopK o = topk_out(q, k);
+    lrx_check(lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), ri, (int32_t)nlist,
+                                        q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe, by_residual ? 1 : 0,
+                                        max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
+              who);
+    return {o.d, o.i};
+  });
+}
+
+// Range search over the probed cells (lrx_ivf_sq_fp16_ip_range_search): ivf_sq_fp16_ip_topk's arguments with radius for k.  Returns (lims, D, I).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
+                                                                           const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                                                                           const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius,
+                                                                           int64_t max_scan_rows, int64_t id_base,
+                                                                           const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_sq_fp16_ip_range_search";
+  return ivf_sq_fp16_ip_op(who, q, codes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
+                           [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe,
+                               const int64_t* rm) {
+    const int64_t Q = q.size(0);
+    const size_t wsb = lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+      return lrx_ivf_sq_fp16_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), ri, (int32_t)nlist,
+                                             q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe, by_residual ? 1 : 0,
+                                             max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm, ws.data_ptr(), wsb, cur_stream());
+    });
+  });
 }
 
 // Inverted file over 8-bit codes (lrx_ivf_sq8_ip_search): codes uint8 [n_rows, D] contiguous, row-major by stored position, cell by cell;
 // trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2); the rest as ivf_sq_fp16_ip_topk.  Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
-                                                   const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                   const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                   int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+// The argument checks ivf_sq8_ip_topk and ivf_sq8_ip_range_search share; fin(...) makes the library call from what they establish.
+template <class Fin>
+auto ivf_sq8_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype, const at::Tensor&
+    list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+    int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
   DevGuard guard(q.device());
   need(q, "q", at::kFloat, 2);
   need(codes, "codes", at::kByte, 2);
@@ -483,36 +602,70 @@ std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at
   const int64_t n_rows = codes.size(0), dim = codes.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
   TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && codes.is_contiguous() && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
                   (nprobe == 0 || probes.stride(1) == 1),
-              "ivf_sq8_ip_topk: q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
+              who, ": q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
   TORCH_CHECK((qtype == 0 || qtype == 2) && trained.is_contiguous() && trained.numel() == (qtype == 0 ? 2 * dim : 2),
-              "ivf_sq8_ip_topk: qtype ", qtype, " (0: QT_8bit, 2: QT_8bit_uniform) with trained fp32 [2 D] or [2] contiguous");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), "ivf_sq8_ip_topk: sizes out of range");
+              who, ": qtype ", qtype, " (0: QT_8bit, 2: QT_8bit_uniform) with trained fp32 [2 D] or [2] contiguous");
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
   const int64_t* ri = nullptr;
   if (row_ids.has_value() && row_ids->defined()) {
     need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, "ivf_sq8_ip_topk: row_ids int64 [>= n_rows] contiguous");
+    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
     ri = row_ids->data_ptr<int64_t>();
   }
   const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
   const float* ps = nullptr;
   if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), "ivf_sq8_ip_topk: by_residual needs probe_scores");
+    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
     need(*probe_scores, "probe_scores", at::kFloat, 2);
     TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
                     (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                "ivf_sq8_ip_topk: probe_scores fp32 [Q, nprobe] with the row stride of probes");
+                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
     ps = probe_scores->data_ptr<float>();
   }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, "ivf_sq8_ip_topk: row_map int64 [>= n_rows] contiguous");
-  const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  TopK o = topk_out(q, k);
-  lrx_check(lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                  list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps,
-                                  (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
-                                  o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-            "ivf_sq8_ip_topk");
-  return {o.d, o.i};
+  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
+  return fin(n_rows, dim, nlist, nprobe, ri, ps, ld_probe, rm);
+}
+
+std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
+                                                   const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                                                   const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
+                                                   int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_sq8_ip_topk";
+return ivf_sq8_ip_op(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows,
+                     int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) -> std::tuple<at::Tensor,
+                     at::Tensor> {
+    const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    TopK o = topk_out(q, k);
+    lrx_check(lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                    list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps,
+                                    (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
+                                    o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
+              who);
+    return {o.d, o.i};
+  });
+}
+
+// Range search over the probed cells (lrx_ivf_sq8_ip_range_search): ivf_sq8_ip_topk's arguments with radius for k.  Returns (lims, D, I).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
+                                                                       const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
+                                                                       const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+                                                                       bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+                                                                       const c10::optional<at::Tensor>& row_map) {
+  const char* who = "ivf_sq8_ip_range_search";
+  return ivf_sq8_ip_op(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
+                       [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe,
+                           const int64_t* rm) {
+    const int64_t Q = q.size(0);
+    const size_t wsb = lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
+    at::Tensor ws = bytes((int64_t)wsb, q);
+    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+      return lrx_ivf_sq8_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                         list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps,
+                                         (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm,
+                                         ws.data_ptr(), wsb, cur_stream());
+    });
+  });
 }
 
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
@@ -625,26 +778,6 @@ std::tuple<at::Tensor, at::Tensor> binary_topk(const at::Tensor& q, const at::Te
                                       dist.data_ptr<int32_t>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, 0, cur_stream()),
             "binary_topk");
   return {dist, o.i};
-}
-
-// The result protocol of every range-search op (lrx_flat_ip_range_search / lrx_sq_fp16_ip_range_search / lrx_pq_ip_range_search /
-// lrx_range_impact_search): `call(lims, d, i, cap)` runs the library call, lims[Q] is read back to the host once, and the call is repeated
-// once with the exact capacity when the first guess of 1024 hits per query was short.  Refused under graph capture before anything is launched.
-template <class Call>
-std::tuple<at::Tensor, at::Tensor, at::Tensor> range_result(const at::Tensor& like, int64_t Q, const char* who, Call call) {
-  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None, who,
-              " under graph capture: the result length is read back to the host");
-  const auto f32 = like.options().dtype(at::kFloat);
-  at::Tensor lims = at::zeros({Q + 1}, f32.dtype(at::kLong));
-  int64_t cap = Q * 1024;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    at::Tensor d = at::empty({cap}, f32), i = at::empty({cap}, f32.dtype(at::kLong));
-    lrx_check(call(lims.data_ptr<int64_t>(), d.data_ptr<float>(), i.data_ptr<int64_t>(), cap), who);
-    const int64_t n = lims[Q].item<int64_t>();
-    if (n <= cap) return {lims, d.narrow(0, 0, n), i.narrow(0, 0, n)};
-    cap = n;
-  }
-  TORCH_CHECK(false, who, ": the result grew between two identical calls");
 }
 
 // Range search (lrx_flat_ip_range_search): (lims [Q+1], D [lims[Q]], I [lims[Q]]).
@@ -792,6 +925,14 @@ TORCH_LIBRARY(lrx, m) {
   m.def("sq_fp16_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor row_bounds, int k, int id_base=0, Tensor? row_map=None, int flags=0) -> (Tensor, Tensor, Tensor)");
   m.def("flat_ip_rerank(Tensor q, Tensor x, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq_fp16_ip_rerank(Tensor q, Tensor codes, int n_rows, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_flat_ip_range_search(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, float radius, int max_scan_rows, int id_base=0, "
+        "Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_pq_ip_range_search(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
+        "bool by_residual, float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_sq_fp16_ip_range_search(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, bool by_residual, "
+        "float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_sq8_ip_range_search(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
+        "bool by_residual, float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
   m.def("ivf_flat_ip_topk(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, int k, int max_scan_rows, int id_base=0, "
         "Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("ivf_pq_ip_topk(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
@@ -830,6 +971,10 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("flat_ip_rerank", &flat_ip_rerank);
   m.impl("sq_fp16_ip_rerank", &sq_fp16_ip_rerank);
+  m.impl("ivf_flat_ip_range_search", &ivf_flat_ip_range_search);
+  m.impl("ivf_pq_ip_range_search", &ivf_pq_ip_range_search);
+  m.impl("ivf_sq_fp16_ip_range_search", &ivf_sq_fp16_ip_range_search);
+  m.impl("ivf_sq8_ip_range_search", &ivf_sq8_ip_range_search);
   m.impl("ivf_flat_ip_topk", &ivf_flat_ip_topk);
   m.impl("ivf_pq_ip_topk", &ivf_pq_ip_topk);
   m.impl("ivf_sq_fp16_ip_topk", &ivf_sq_fp16_ip_topk);

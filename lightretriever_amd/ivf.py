@@ -6,7 +6,12 @@
 
 k-means cells, the fp32 rows stored once, cell by cell, and only the `nprobe` best cells of a query scanned: at nprobe / nlist = 1/32 a single
 query reads about 1/32 of the rows.  No fp16 shadow is kept.  Every scanned (query, row) pair is scored exactly -- the flat index's own bits --
-so with nprobe == nlist the result IS FlatIPIndex.search's."""
+so with nprobe == nlist the result IS FlatIPIndex.search's.
+
+    lims, D, I = idx.range_search_probed(q, 0.8)     # every row of those cells scoring above 0.8, never cut at a k
+
+range_search_probed / range_search_preassigned (lrx_ivf_flat_ip_range_search) live in _IVFCells, for the four inverted-file
+indexes."""
 from __future__ import annotations
 
 from typing import Optional
@@ -15,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import FlatIPIndex, _as_rows, _check_range, _grown, _pq_update
+from .index import FlatIPIndex, _as_rows, _check_range, _grown, _pq_update, _range_args, _range_empty
 from .transform import linear_transform
 
 MAX_NPROBE = 2048
@@ -42,8 +47,9 @@ def check_nprobe(nprobe: int, nlist: int, who: str = "IVFFlatIndex") -> int:
 class _IVFCells:
     """What the inverted-file indexes (IVFFlatIndex here, IVFPQIndex in ivfpq.py) share: the coarse quantiser -- a FlatIPIndex over k-means
     centroids -- and its training, the cell bookkeeping (`list_off`, `row_ids`, the host `list_sizes`, the cell `_assign` of every original
-    row, `_nsorted`), the staging of append_slot / commit, and the search prologue.  A subclass keeps what is its own: the stored rows or
-    codes, add, the rebuild of the cell order (_finalize), the library call of search, persistence."""
+    row, `_nsorted`), the staging of append_slot / commit, the search prologue, and the range search over the probed cells
+    (range_search_probed / range_search_preassigned).  A subclass keeps what is its own: the stored rows or codes, add, the rebuild of the cell
+    order (_finalize), the library calls of search and of the range search (_range_cells), persistence."""
 
     NITER = 10
     MAX_POINTS_PER_CENTROID = 256
@@ -183,12 +189,13 @@ class _IVFCells:
         nprobe = self.nprobe if nprobe is None else nprobe
         return int(np.sort(self.list_sizes)[::-1][:nprobe].sum())
 
-    def _begin_search(self, q, k: int, nprobe: Optional[int], row_map: Optional[torch.Tensor]):
-        """The checks every search starts with -> (q fp32 [Q, d] on the device, nprobe); the cell order is rebuilt when rows were added."""
+    def _begin_search(self, q, k: Optional[int], nprobe: Optional[int], row_map: Optional[torch.Tensor]):
+        """The checks every search starts with -> (q fp32 [Q, d] on the device, nprobe); the cell order is rebuilt when rows were added.
+        k = None: a range search, which has none."""
         who = type(self).__name__
         if not self.is_trained:
             raise RuntimeError(f"{who}.search: the index is not trained")
-        if not 1 <= k <= MAX_K:
+        if k is not None and not 1 <= k <= MAX_K:
             raise ValueError(f"search: k={k} out of range (1..{MAX_K})")
         nprobe = check_nprobe(self.nprobe if nprobe is None else nprobe, self.nlist, who)
         if row_map is not None and not (row_map.is_cuda and row_map.dtype == torch.int64 and row_map.is_contiguous() and row_map.numel() >= self.ntotal):
@@ -200,11 +207,53 @@ class _IVFCells:
             self._finalize()
         return q, nprobe
 
+    # -- range search over the probed cells -----------------------------------------------------------------
+    def range_search_probed(self, q, radius: float, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
+        """-> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]) device tensors: every row of each query's nprobe best cells -- the cells search()
+        scans -- whose score, the value search() reports for it, is strictly greater than `radius`; never cut at a k.  Query i's hits are
+        D / I[lims[i]:lims[i + 1]] in SEGMENT order, faiss's for an IVF range search: its cells in probe order (best centroid first), inside
+        a cell by stored position (ascending original row) -- not sorted by score, and not FlatIPIndex.range_search's ascending-row order.
+        I = id_base + row, or row_map[row].  The coarse search of search(), then range_search_preassigned.  Reads the result length back
+        to the host once: refused under graph capture.  NaN radius: ValueError."""
+        radius = _range_args(type(self).__name__, radius)
+        q, nprobe = self._begin_search(q, None, nprobe, row_map)
+        if q.shape[0] == 0 or self.ntotal == 0:
+            return _range_empty(self.device, q.shape[0])
+        probe_scores, probes = self.quantizer.search(q, nprobe)
+        return self._range_cells(q, radius, probes, probe_scores, self.max_scan_rows(nprobe), row_map)
+
+    def range_search_preassigned(self, q, radius: float, probes: torch.Tensor, probe_scores: Optional[torch.Tensor] = None,
+                                 row_map: Optional[torch.Tensor] = None):
+        """faiss IndexIVF::range_search_preassigned(x, radius, keys, coarse_dis): range_search_probed over the caller's cells.  probes: int64
+        [Q, nprobe] on the device, the cells of each query in the order their hits are wanted (an entry < 0 is skipped; one >= nlist is
+        skipped and counted in lrx_device_error_count; a cell named twice is scanned once).  probe_scores: fp32 [Q, nprobe], the score of each
+        cell's centroid for the query -- required by an index that codes residuals (by_residual), ignored by one that does not."""
+        who = type(self).__name__
+        radius = _range_args(who, radius)
+        if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.int64 and probes.dim() == 2):
+            raise ValueError("range_search_preassigned: probes must be an int64 CUDA tensor [Q, nprobe]")
+        q, _ = self._begin_search(q, None, probes.shape[1], row_map)
+        if probes.shape[0] != q.shape[0]:
+            raise ValueError(f"range_search_preassigned: probes has {probes.shape[0]} rows for {q.shape[0]} queries")
+        if getattr(self, "by_residual", False):
+            if probe_scores is None:
+                raise ValueError(f"range_search_preassigned: {who} codes residuals (by_residual): probe_scores (fp32 [Q, nprobe]) is required")
+            if not (probe_scores.is_cuda and probe_scores.dtype == torch.float32 and probe_scores.shape == probes.shape):
+                raise ValueError("range_search_preassigned: probe_scores must be an fp32 CUDA tensor of the shape of probes")
+            probe_scores = probe_scores.contiguous()
+        else:
+            probe_scores = None
+        if q.shape[0] == 0 or self.ntotal == 0:
+            return _range_empty(self.device, q.shape[0])
+        return self._range_cells(q, radius, probes.contiguous(), probe_scores, self.max_scan_rows(probes.shape[1]), row_map)
+
 
 class IVFFlatIndex(_IVFCells):
     """faiss.IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT): d, nlist, nprobe, ntotal, is_trained, id_base; train / add / search /
     reset / reconstruct_n / save / load / set_contents, and append_slot / commit as the other trainable shards have.
     d % 32 == 0, 32 <= d <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
+    Range search: range_search_probed(q, radius, nprobe) and faiss's range_search_preassigned(q, radius, probes) -- every row of the probed
+    cells with a score > radius, in segment order (_IVFCells).  The plain name range_search stays refused: a test pins it.
 
     Training: Lloyd k-means on the L2 objective (what faiss's Clustering minimises for a non-spherical IP index) with PQIndex's rules --
     np.random.default_rng(1234), at most 256 x nlist rows (sampled without replacement, row numbers sorted), initial centroids = nlist distinct
@@ -310,6 +359,10 @@ class IVFFlatIndex(_IVFCells):
         _, probes = self.quantizer.search(q, nprobe)
         return ops.ivf_flat_ip_topk(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, k, self.max_scan_rows(nprobe), self.id_base, row_map,
                                     ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
+        return ops.ivf_flat_ip_range_search(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, radius, max_scan_rows, self.id_base, row_map,
+                                            ws_slots=vars(self))
 
     def range_search(self, q, radius: float):
         raise NotImplementedError("IVFFlatIndex.range_search is not served (range search over the probed cells is a follow-up)")

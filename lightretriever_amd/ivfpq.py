@@ -37,6 +37,9 @@ class IVFPQIndex(_IVFCells):
     """faiss.IndexIVFPQ(IndexFlatIP(d), d, nlist, M, 8, METRIC_INNER_PRODUCT): d, nlist, nprobe, M, by_residual, ntotal, is_trained, id_base;
     train / add / search / reset / reconstruct_n / save / load / set_contents / append_slot / commit / max_scan_rows.
     d % 32 == 0, 32 <= d <= 8192, d % M == 0, d / M <= 64; nbits = 8; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
+    Range search: range_search_probed(q, radius, nprobe) and faiss's range_search_preassigned(q, radius, probes, probe_scores) -- every row of
+    the probed cells with a score > radius, in segment order (_IVFCells in ivf.py).  The plain name range_search stays refused:
+    a test pins it.
 
     Coarse quantiser: IVFFlatIndex's, from the code both share (`quantizer`, a FlatIPIndex over centroids trained by the same k-means: the same
     bits for the same input and seed).  A row's cell at add() and a query's probe list at search() are its exact top-1 / top-nprobe by INNER
@@ -161,6 +164,10 @@ class IVFPQIndex(_IVFCells):
         probe_scores, probes = self.quantizer.search(q, nprobe)
         return ops.ivf_pq_ip_topk(q, self.pq._codes, self.pq.centroids, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
                                   self.max_scan_rows(nprobe), self.id_base, row_map, ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
+        return ops.ivf_pq_ip_range_search(q, self.pq._codes, self.pq.centroids, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, radius,
+                                          max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
 
     def range_search(self, q, radius: float):
         raise NotImplementedError("IVFPQIndex.range_search is not served (range search over the probed cells is a follow-up)")

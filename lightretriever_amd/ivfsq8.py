@@ -34,6 +34,9 @@ class IVFSQ8Index(_IVFCells):
     """faiss.IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT): d, nlist, nprobe, qtype,
     by_residual, trained, ntotal, is_trained, id_base; train / add / search / reset / reconstruct_n / save / load / set_contents / append_slot /
     commit / max_scan_rows.  d % 32 == 0, 32 <= d <= 8192; 1 <= nlist; 1 <= nprobe <= min(nlist, 2048); 1 <= k <= 2048.
+    Range search: range_search_probed(q, radius, nprobe) and faiss's range_search_preassigned(q, radius, probes, probe_scores) -- every row of
+    the probed cells with a score > radius, in segment order (_IVFCells in ivf.py).  The plain name range_search stays refused:
+    a test pins it.
 
     Coarse quantiser: IVFFlatIndex's, from the code both share (the same centroid bits for the same input and seed).  train() runs that k-means
     and then trains the range as faiss's train_encoder does: every training row goes to its coarse top-1 cell, the residual is
@@ -200,6 +203,10 @@ class IVFSQ8Index(_IVFCells):
         probe_scores, probes = self.quantizer.search(q, nprobe)
         return ops.ivf_sq8_ip_topk(q, self._codes[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
                                    self.max_scan_rows(nprobe), self.id_base, row_map, ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
+        return ops.ivf_sq8_ip_range_search(q, self._codes[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores,
+                                           self.by_residual, radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
 
     def range_search(self, q, radius: float):
         raise NotImplementedError("IVFSQ8Index.range_search is not served (range search over the probed cells is a follow-up)")

@@ -322,6 +322,42 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
 
 
 # -- inverted file (IndexIVFFlat) ---------------------------------------------------------------------------------------------
+def _ivf_flat_args(name: str, q, X, list_off, probes):
+    """The checks ivf_flat_ip_topk and ivf_flat_ip_range_search share -> (Q, nprobe, n, d, nlist)."""
+    Q, nprobe = probes.shape
+    n, d = X.shape
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
+    return Q, nprobe, n, d, list_off.numel() - 1
+
+
+def _ivf_range(name: str, q: torch.Tensor, Q: int, ws_slots: Optional[dict], ws_bytes, call):
+    """What the four IVF range searches share: the protocol of index._range_call over ONE library call for all Q queries (the library chunks
+    them itself and carries lims on the device) -- outputs sized by a first guess, one host read of lims[Q], one retry when the guess was
+    short.  ws_slots: a dict that keeps the workspace between calls (key "_ws"); ws_bytes() -> the workspace size; call(ws, lims, D, I, capacity) -> the library's return code."""
+    from .index import _range_call, _range_empty, _workspace
+    if torch.cuda.is_current_stream_capturing():
+        raise _lib.LrxError(f"{name} under graph capture: the result length is read back to the host")
+    if Q == 0:
+        return _range_empty(q.device, 0)
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", int(ws_bytes()), q.device)
+    return _range_call(q.device, Q, Q, lambda s, n, lims, D, I, cap: _lib.check(call(ws, lims, D, I, cap)))
+
+
+def ivf_flat_ip_range_search(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
+                             radius: float, max_scan_rows: int, id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
+    """lrx_ivf_flat_ip_range_search -> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]): every row of the cells probes[i] names whose exact
+    score is > radius, in SEGMENT order (cells in the order of the probe row, rows by stored position), not sorted.  The arguments are
+    ivf_flat_ip_topk's with radius for k.  Reads lims[Q] back to the host: refused under graph capture."""
+    lib = _lib.lib()
+    Q, nprobe, n, d, nlist = _ivf_flat_args("ivf_flat_ip_range_search", q, X, list_off, probes)
+    return _ivf_range("ivf_flat_ip_range_search", q, Q, ws_slots, lambda: lib.lrx_ivf_flat_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
+                      lambda ws, lims, D, I, cap: lib.lrx_ivf_flat_ip_range_search(
+                          _lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q,
+                          _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims),
+                          _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+
+
 def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor, k: int,
                      max_scan_rows: int, id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None,
                      capture_error: Optional[str] = None):
@@ -331,11 +367,7 @@ def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, r
     caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
     from .index import _workspace
     lib = _lib.lib()
-    Q, nprobe = probes.shape
-    n, d = X.shape
-    nlist = list_off.numel() - 1
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError("ivf_flat_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
+    Q, nprobe, n, d, nlist = _ivf_flat_args("ivf_flat_ip_topk", q, X, list_off, probes)
     D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
     I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
     if Q == 0:
@@ -346,6 +378,44 @@ def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, r
                                           _lib.ptr(q), Q, _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), k,
                                           int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
     return D, I
+
+
+def _ivf_probe_scores_ok(probes, probe_scores, ld) -> bool:
+    Q, nprobe = probes.shape
+    return probe_scores is not None and probe_scores.dtype == torch.float32 and probe_scores.shape == probes.shape and \
+        not (nprobe and probe_scores.stride(1) != 1) and not (Q > 1 and probe_scores.stride(0) != ld)
+
+
+def _ivf_pq_args(name: str, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual):
+    """The checks ivf_pq_ip_topk and ivf_pq_ip_range_search share -> (Q, nprobe, n, d, M, nlist, ld_probe)."""
+    Q, nprobe = probes.shape
+    d = q.shape[1]
+    M = pq_centroids.shape[0]
+    n = codes.numel() // (-(-M // 16) * 16) if row_ids is None else row_ids.numel()
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
+    if codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous() or codes.numel() < -(-n // 128) * 128 * (-(-M // 16) * 16):
+        raise ValueError(f"{name}: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)")
+    if pq_centroids.dtype != torch.float32 or not pq_centroids.is_contiguous() or tuple(pq_centroids.shape) != (M, 256, d // max(M, 1)) or d % M:
+        raise ValueError(f"{name}: pq_centroids must be fp32 [M, 256, d / M] contiguous with d % M == 0")
+    ld = probes.stride(0) if Q > 1 else nprobe
+    if by_residual and not _ivf_probe_scores_ok(probes, probe_scores, ld):
+        raise ValueError(f"{name}: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    return Q, nprobe, n, d, M, list_off.numel() - 1, ld
+
+
+def ivf_pq_ip_range_search(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
+                           probes: torch.Tensor, probe_scores: Optional[torch.Tensor], by_residual: bool, radius: float, max_scan_rows: int,
+                           id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
+    """lrx_ivf_pq_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose ADC score -- the value ivf_pq_ip_topk reports -- is
+    > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_pq_ip_topk's with radius for k."""
+    lib = _lib.lib()
+    Q, nprobe, n, d, M, nlist, ld = _ivf_pq_args("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_pq_ip_range_search", q, Q, ws_slots, lambda: lib.lrx_ivf_pq_ip_range_workspace_bytes(n, nlist, d, M, Q, nprobe, int(max_scan_rows)),
+                      lambda ws, lims, D, I, cap: lib.lrx_ivf_pq_ip_range_search(
+                          _lib.ptr(codes) if n else None, n, _lib.ptr(pq_centroids), d, M, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q,
+                          _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows),
+                          float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
 
 
 def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -359,22 +429,7 @@ def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Ten
     ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
     from .index import _workspace
     lib = _lib.lib()
-    Q, nprobe = probes.shape
-    d = q.shape[1]
-    M = pq_centroids.shape[0]
-    nlist = list_off.numel() - 1
-    n = codes.numel() // (-(-M // 16) * 16) if row_ids is None else row_ids.numel()
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError("ivf_pq_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
-    if codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous() or codes.numel() < -(-n // 128) * 128 * (-(-M // 16) * 16):
-        raise ValueError("ivf_pq_ip_topk: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)")
-    if pq_centroids.dtype != torch.float32 or not pq_centroids.is_contiguous() or tuple(pq_centroids.shape) != (M, 256, d // max(M, 1)) or d % M:
-        raise ValueError("ivf_pq_ip_topk: pq_centroids must be fp32 [M, 256, d / M] contiguous with d % M == 0")
-    ld = probes.stride(0) if Q > 1 else nprobe
-    if by_residual:
-        if probe_scores is None or probe_scores.dtype != torch.float32 or probe_scores.shape != probes.shape or (nprobe and probe_scores.stride(1) != 1) or \
-                (Q > 1 and probe_scores.stride(0) != ld):
-            raise ValueError("ivf_pq_ip_topk: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    Q, nprobe, n, d, M, nlist, ld = _ivf_pq_args("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
     D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
     I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
     if Q == 0:
@@ -385,6 +440,38 @@ def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Ten
                                         _lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
                                         int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
     return D, I
+
+
+def _ivf_codes_args(name: str, dtype, dtype_name: str, q, codes, list_off, row_ids, probes, probe_scores, by_residual):
+    """The checks the searches over row-major codes (fp16, 8-bit) share -> (Q, nprobe, n, d, nlist, ld_probe)."""
+    Q, nprobe = probes.shape
+    if codes.dtype != dtype or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
+        raise ValueError(f"{name}: codes must be {dtype_name} [n, d] contiguous with q's d")
+    n, d = codes.shape
+    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
+        raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
+    if row_ids is not None and (row_ids.dtype != torch.int64 or not row_ids.is_contiguous() or row_ids.numel() < n):
+        raise ValueError(f"{name}: row_ids must be int64 [>= n] contiguous")
+    ld = probes.stride(0) if Q > 1 else nprobe
+    if by_residual and not _ivf_probe_scores_ok(probes, probe_scores, ld):
+        raise ValueError(f"{name}: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    return Q, nprobe, n, d, list_off.numel() - 1, ld
+
+
+def ivf_sq_fp16_ip_range_search(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
+                                probe_scores: Optional[torch.Tensor], by_residual: bool, radius: float, max_scan_rows: int, id_base: int = 0,
+                                row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
+    """lrx_ivf_sq_fp16_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the fp16 store -- the value
+    ivf_sq_fp16_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq_fp16_ip_topk's with
+    radius for k."""
+    lib = _lib.lib()
+    name = "ivf_sq_fp16_ip_range_search"
+    Q, nprobe, n, d, nlist, ld = _ivf_codes_args(name, torch.float16, "fp16", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range(name, q, Q, ws_slots, lambda: lib.lrx_ivf_sq_fp16_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
+                      lambda ws, lims, D, I, cap: lib.lrx_ivf_sq_fp16_ip_range_search(
+                          _lib.ptr(codes) if n else None, n, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q, _lib.ptr(probes),
+                          _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows), float(radius),
+                          int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
 
 
 def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
@@ -398,20 +485,7 @@ def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Te
     between calls (key "_ws")."""
     from .index import _workspace
     lib = _lib.lib()
-    Q, nprobe = probes.shape
-    nlist = list_off.numel() - 1
-    if codes.dtype != torch.float16 or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
-        raise ValueError("ivf_sq_fp16_ip_topk: codes must be fp16 [n, d] contiguous with q's d")
-    n, d = codes.shape
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError("ivf_sq_fp16_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
-    if row_ids is not None and (row_ids.dtype != torch.int64 or not row_ids.is_contiguous() or row_ids.numel() < n):
-        raise ValueError("ivf_sq_fp16_ip_topk: row_ids must be int64 [>= n] contiguous")
-    ld = probes.stride(0) if Q > 1 else nprobe
-    if by_residual:
-        if probe_scores is None or probe_scores.dtype != torch.float32 or probe_scores.shape != probes.shape or (nprobe and probe_scores.stride(1) != 1) or \
-                (Q > 1 and probe_scores.stride(0) != ld):
-            raise ValueError("ivf_sq_fp16_ip_topk: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    Q, nprobe, n, d, nlist, ld = _ivf_codes_args("ivf_sq_fp16_ip_topk", torch.float16, "fp16", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
     D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
     I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
     if Q == 0:
@@ -422,6 +496,33 @@ def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Te
                                              _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
                                              int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
     return D, I
+
+
+def _ivf_sq8_args(name: str, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual):
+    """The checks ivf_sq8_ip_topk and ivf_sq8_ip_range_search share -> (Q, nprobe, n, d, nlist, ld_probe)."""
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
+        raise ValueError(f"{name}: codes must be uint8 [n, d] contiguous with q's d")
+    d = codes.shape[1]
+    if qtype not in (0, 2) or trained.dtype != torch.float32 or not trained.is_contiguous() or trained.numel() != (2 * d if qtype == 0 else 2):
+        raise ValueError(f"{name}: qtype {qtype} (0: QT_8bit, 2: QT_8bit_uniform) needs trained fp32 [2 d] or [2] contiguous")
+    return _ivf_codes_args(name, torch.uint8, "uint8", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
+
+
+def ivf_sq8_ip_range_search(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor,
+                            row_ids: Optional[torch.Tensor], probes: torch.Tensor, probe_scores: Optional[torch.Tensor], by_residual: bool, radius: float,
+                            max_scan_rows: int, id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
+    """lrx_ivf_sq8_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the 8-bit store -- the value
+    ivf_sq8_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq8_ip_topk's with radius
+    for k."""
+    lib = _lib.lib()
+    name = "ivf_sq8_ip_range_search"
+    Q, nprobe, n, d, nlist, ld = _ivf_sq8_args(name, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range(name, q, Q, ws_slots, lambda: lib.lrx_ivf_sq8_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
+                      lambda ws, lims, D, I, cap: lib.lrx_ivf_sq8_ip_range_search(
+                          _lib.ptr(codes) if n else None, n, d, _lib.ptr(trained), int(qtype), _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q),
+                          Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows),
+                          float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(),
+                          _s()))
 
 
 def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -435,22 +536,7 @@ def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor,
     max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
     from .index import _workspace
     lib = _lib.lib()
-    Q, nprobe = probes.shape
-    nlist = list_off.numel() - 1
-    if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
-        raise ValueError("ivf_sq8_ip_topk: codes must be uint8 [n, d] contiguous with q's d")
-    n, d = codes.shape
-    if qtype not in (0, 2) or trained.dtype != torch.float32 or not trained.is_contiguous() or trained.numel() != (2 * d if qtype == 0 else 2):
-        raise ValueError(f"ivf_sq8_ip_topk: qtype {qtype} (0: QT_8bit, 2: QT_8bit_uniform) needs trained fp32 [2 d] or [2] contiguous")
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError("ivf_sq8_ip_topk: probes must be int64 [Q, nprobe] with unit inner stride")
-    if row_ids is not None and (row_ids.dtype != torch.int64 or not row_ids.is_contiguous() or row_ids.numel() < n):
-        raise ValueError("ivf_sq8_ip_topk: row_ids must be int64 [>= n] contiguous")
-    ld = probes.stride(0) if Q > 1 else nprobe
-    if by_residual:
-        if probe_scores is None or probe_scores.dtype != torch.float32 or probe_scores.shape != probes.shape or (nprobe and probe_scores.stride(1) != 1) or \
-                (Q > 1 and probe_scores.stride(0) != ld):
-            raise ValueError("ivf_sq8_ip_topk: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    Q, nprobe, n, d, nlist, ld = _ivf_sq8_args("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
     D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
     I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
     if Q == 0:

@@ -74,6 +74,14 @@ class FaissIndex:
             ids = self._passage_ids[ids]
         return lims, scores, ids
 
+    def range_search_probed(self, query_embeddings, radius: float, nprobe: Optional[int] = None):
+        """-> (lims, D, I) of the wrapped inverted-file index's range_search_probed (IVFFlatIndex, IVFPQIndex, IVFSQIndex, IVFSQ8Index): every
+        row of each query's nprobe best cells with a score > radius, in segment order, I mapped through the passage ids as in range_search."""
+        lims, scores, ids = self.index.range_search_probed(query_embeddings, radius, nprobe)
+        if self._passage_ids is not None:
+            ids = self._passage_ids[ids]
+        return lims, scores, ids
+
     @classmethod
     def build(cls, passage_ids: list, passage_embeddings, index: Optional[FlatIPIndex] = None, buffer_size: int = 50000):
         if index is None:
