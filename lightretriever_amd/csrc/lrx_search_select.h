@@ -249,7 +249,9 @@ __device__ void select_topk_sorted(const float* __restrict__ row, int64_t N, int
         }
       }
       __syncthreads();
-      if (sh.ngt <= SEL_CAND) { ncand = (int)sh.ngt; done = true; }
+      // (fewer than keff: only a row of NaN scores -- the block maxima, taken with fmaxf, do not see them, and a NaN with its sign bit set
+      // has the lowest keys of all -- so no row reaches the threshold.  The exact path below ranks by key whatever the keys are.)
+      if (sh.ngt <= SEL_CAND && sh.ngt >= (unsigned int)keff) { ncand = (int)sh.ngt; done = true; }
     }
     __syncthreads();
   }
