@@ -732,6 +732,16 @@ int lrx_binary_decode_rows(const void* codes, int64_t row0, int64_t n_rows, int3
  *   synchronisation.  out_ids: id_base + row, or row_map[row] when row_map != NULL.  Workspace: lrx_sq8_ip_workspace_bytes.  flags: 0.      */
 size_t lrx_sq8_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k);
 int32_t lrx_sq8_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k);
+/* (added in ABI 9, additively; host only, for tests of the single stages) Where lrx_sq8_ip_search of the same arguments keeps the state of a query
+ * chunk in the caller's workspace.  out = {queries per chunk qc, rows per score matrix rc, its row stride ld, the block maxima's row stride nblk_ld,
+ * padded queries of a full chunk (16 x the scan's query tiles of qc), then byte offsets: digit tiles (0), scale (double[qc]), bias (double[qc]),
+ * eps (float[qc]), score matrix (float[qc][ld]), block maxima (float[qc][nblk_ld]; one per 128 rows), and the workspace's size
+ * (= lrx_sq8_ip_workspace_bytes)}.  Digit tile of (16-query tile t, 64-column slice c, plane p: 0 = hi, 1 = lo), n = 128 hi + lo: 1 KiB at
+ * ((t dim / 64 + c) 2 + p) 1024, [16-column piece][query % 16][16 bytes].  A chunk of nq <= qc queries prepares the tiles of its own
+ * 16 x (1, 2, 4 or 8 tiles >= nq / 16) queries, the padding queries with zero digits.  Every region is rewritten per query chunk and the matrix
+ * per row chunk: after a search they show its last query chunk and last row chunk.  Returns LRX_OK or an argument error. */
+#define LRX_SQ8_LAYOUT_INTS 12
+int lrx_sq8_ip_workspace_layout(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int64_t out[LRX_SQ8_LAYOUT_INTS]);
 int lrx_sq8_ip_search(const void* codes, int64_t n_rows, const float* trained, int32_t dim, int32_t qtype, const float* q, int32_t n_queries,
                       int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                       size_t workspace_bytes, int32_t flags, void* stream);

@@ -124,6 +124,7 @@ SIGNATURES = {
     "lrx_binary_decode_rows": (_I32, [_P, _I64, _I64, _I32, _P, _I64, _P]),
     "lrx_sq8_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "lrx_sq8_ip_chunk_queries": (_I32, [_I64, _I32, _I32, _I32]),
+    "lrx_sq8_ip_workspace_layout": (_I32, [_I64, _I32, _I32, _I32, _P]),
     "lrx_sq8_ip_search": (_I32, [_P, _I64, _P, _I32, _I32, _P, _I32, _I32, _I64, _P, _P, _P, _P, _SZ, _I32, _P]),
     "lrx_sq8_train_minmax": (_I32, [_P, _I64, _I64, _I32, _P, _P]),
     "lrx_sq8_encode": (_I32, [_P, _I64, _I64, _P, _I32, _I32, _P, _I64, _P]),

@@ -185,7 +185,7 @@ k_sq8_prep(const float* __restrict__ q, int nq, const float* __restrict__ traine
   if (tid == 0) {
     qscale[qi] = scale;
     qbias[qi] = sv + 128.5 * sw;
-    qeps[qi] = (float)((128.0 * err + st * 4.76837158203125e-07 + sa * 4.2e-45) * 1.01) * 1.0000002f;
+    qeps[qi] = (float)((128.0 * err + st * 4.76837158203125e-07 + sa * (3.0 * 0x1p-149)) * 1.01) * 1.0000002f;   // (2^-21, 3 2^-149)
   }
 }
 
@@ -354,6 +354,19 @@ extern "C" size_t lrx_sq8_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_
 
 extern "C" int32_t lrx_sq8_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k) {
   return sq8_plan(n_rows, dim > 0 ? dim : 64, n_queries, k).qc;
+}
+
+// Where a search of these arguments keeps the state of a query chunk in its workspace (host only; the regions are rewritten per query chunk and
+// the matrix per row chunk, so after a search they show its last query chunk and last row chunk).
+extern "C" int lrx_sq8_ip_workspace_layout(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int64_t out[LRX_SQ8_LAYOUT_INTS]) {
+  LRX_CHECK_ARG(out != nullptr && dim > 0 && dim % 64 == 0 && dim <= 65536 && n_rows >= 0 && n_queries > 0 && k > 0,
+                "sq8_ip_workspace_layout: bad arguments (n_rows=%lld, dim=%d, n_queries=%d, k=%d)", (long long)n_rows, dim, n_queries, k);
+  const ScanPlan p = sq8_plan(n_rows, dim, n_queries, k);
+  const SQ8Lead l = sq8_lead(p.qc, dim);
+  const int64_t v[LRX_SQ8_LAYOUT_INTS] = {p.qc, p.rc, p.ld, p.nblk_ld, 16ll * sq8_scan_tiles(p.qc), 0, (int64_t)l.scale_off, (int64_t)l.bias_off,
+                                          (int64_t)l.eps_off, (int64_t)p.sc_off, (int64_t)p.bm_off, (int64_t)p.total};
+  for (int i = 0; i < LRX_SQ8_LAYOUT_INTS; ++i) out[i] = v[i];
+  return LRX_OK;
 }
 
 extern "C" int lrx_sq8_train_minmax(const float* x, int64_t n_rows, int64_t ldx, int32_t dim, float* minmax, void* stream) {

@@ -987,6 +987,7 @@ class SQ8Index(_CodeIndex):
         self.is_trained = False
         self.trained = torch.zeros(2 if self.uniform else 2 * d, dtype=torch.float32, device=self.device)
         self._minmax = None                            # [2, d] running column min / max of the training pieces
+        self._last_search = None                       # (Q, k, ntotal, workspace) of the last search: last_chunk_state()
 
     def _layout(self):
         # a block: [64-column slice][16-row group][16-column piece][row][byte] -> [row group][row][slice][piece][byte]
@@ -1090,7 +1091,44 @@ class SQ8Index(_CodeIndex):
         _lib.check(self.lib.lrx_sq8_ip_search(_lib.ptr(self._codes), self.ntotal, _lib.ptr(self.trained), self.d, self._qt, _lib.ptr(q), Q, k,
                                               int(self.id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), 0,
                                               _lib.current_stream()))
+        self._last_search = (Q, k, self.ntotal, ws)
         return D, I
+
+    def _layout_of(self, ntotal: int, Q: int, k: int) -> dict:
+        out = (C.c_int64 * 12)()
+        _lib.check(self.lib.lrx_sq8_ip_workspace_layout(ntotal, self.d, Q, k, out))
+        return dict(zip(("qc", "rc", "ld", "nblk_ld", "qpad", "digits_off", "scale_off", "bias_off", "eps_off", "scores_off", "blkmax_off", "total"),
+                        (int(v) for v in out)))
+
+    def last_chunk_state(self) -> dict:
+        """What the stages of the last search left in its workspace for its LAST query chunk and LAST row chunk (lrx_sq8_ip_workspace_layout;
+        read-only, for tests of the single stages), as host tensors: `q0`, `nq` (the chunk's queries [q0, q0 + nq) of the call), `qpad` (the
+        queries k_sq8_prep wrote digits for: nq padded to 16 x (1, 2, 4, 8) tiles), `row0`, `rows` (the row chunk), `k`, `ntotal`, `layout`;
+        `hi`, `lo` int8 [qpad, d] (the digit planes un-tiled, padding queries included) and `n` int32 [nq, d] = 128 hi + lo; `scale`, `bias`
+        fp64 [nq]; `eps` fp32 [nq]; `scores` fp32 [nq, ld] (filter scores; columns >= rows are whatever the scan made of the codes there) and
+        `blkmax` fp32 [nq, ceil(rows / 128)].  Raises before the first search."""
+        if self._last_search is None:
+            raise _lib.LrxError("last_chunk_state(): no search has run on this index yet")
+        Q, k, ntotal, ws = self._last_search
+        L = self._layout_of(ntotal, Q, k)
+        qc, rc, ld, nblk_ld = L["qc"], L["rc"], L["ld"], L["nblk_ld"]
+        q0 = (Q - 1) // qc * qc
+        nq = Q - q0
+        qpad = self._layout_of(ntotal, nq, k)["qpad"]                     # the tiles k_sq8_prep prepares for a chunk of nq queries
+        row0 = (max(ntotal, 1) - 1) // rc * rc
+        rows = ntotal - row0
+        KC = self.d // 64
+        region = lambda off, count, dtype, size: ws[off:off + count * size].view(dtype)
+        tiles = region(L["digits_off"], qpad * self.d * 2, torch.int8, 1).view(qpad // 16, KC, 2, 4, 16, 16)
+        planes = tiles.permute(2, 0, 4, 1, 3, 5).reshape(2, qpad, self.d).cpu()  # [plane][query tile, query][slice, piece, byte]
+        hi, lo = planes[0].contiguous(), planes[1].contiguous()
+        nblk = -(-rows // 128)
+        return dict(q0=q0, nq=nq, qpad=qpad, row0=row0, rows=rows, k=k, ntotal=ntotal, layout=L, hi=hi, lo=lo,
+                    n=(128 * hi[:nq].to(torch.int32) + lo[:nq].to(torch.int32)),
+                    scale=region(L["scale_off"], nq, torch.float64, 8).cpu(), bias=region(L["bias_off"], nq, torch.float64, 8).cpu(),
+                    eps=region(L["eps_off"], nq, torch.float32, 4).cpu(),
+                    scores=region(L["scores_off"], nq * ld, torch.float32, 4).view(nq, ld).cpu(),
+                    blkmax=region(L["blkmax_off"], nq * nblk_ld, torch.float32, 4).view(nq, nblk_ld)[:, :nblk].cpu())
 
     def range_search(self, q, radius: float):
         raise NotImplementedError("SQ8Index.range_search is not served yet (a follow-up: the scan's matrix holds filter scores, so the range "

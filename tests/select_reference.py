@@ -235,7 +235,7 @@ def sq8_eps() -> float:
     err = np.abs(w - scale * n).sum()
     st = (np.abs(q) * (abs(vmin) + abs(vdiff))).sum()
     sa = np.abs(q).sum()
-    return float(F32((128.0 * err + st * 2.0 ** -21 + sa * 4.2e-45) * 1.01) * F32(1.0000002))
+    return float(F32((128.0 * err + st * 2.0 ** -21 + sa * 3 * 2.0 ** -149) * 1.01) * F32(1.0000002))
 
 
 BAND_EPS = {"flat": flat_eps, "sq8": sq8_eps}
