@@ -12,9 +12,10 @@
 //                  non-empty cell is emitted; a query whose cells hold more than max_scan_rows emits nothing and is counted
 //   k_ivf_items / k_pairs_scatter   the pairs grouped by cell (the counting sort of k_pairs_scan / k_pairs_scatter; the scan kernel here also
 //                  lays out the work items: a probed cell is ceil(rows / G) groups of G consecutive stored rows)
-//   k_ivf_scan     CELL-MAJOR, persistent: a workgroup stages a group of a probed cell in LDS once and scores it against every query that probes
-//                  the cell -- one half-wave per (query, row), the query row streamed from L2 (exact_dot_lds_row: the bits of exact_dot) --
-//                  writing packed (score, ORIGINAL row) words into the queries' segments.  Cells nobody probes cost nothing.
+//   k_ivf_scan     CELL-MAJOR, persistent (ivf_scan_items, the walk of the three scans): a workgroup stages a group of a probed cell in LDS once
+//                  and scores it against every query that probes the cell -- one half-wave per (query, row), the query row streamed from L2
+//                  (exact_dot_lds_row: the bits of exact_dot) -- writing packed (score, ORIGINAL row) words into the queries' segments.
+//                  Cells nobody probes cost nothing.
 //   k_ivf_select   one workgroup per query: sorted top k of its segment (counting ranks / register sort up to 2048 words, radix select above).
 //   (a range search ends the chunk differently: k_ivf_range<false> counts the words above the radius, k_range_lims turns the counts into
 //   lims, k_ivf_range<true> writes them in segment order -- see k_ivf_range)
@@ -183,19 +184,20 @@ k_ivf_items(const unsigned int* __restrict__ cell_cnt, const int64_t* __restrict
   }
 }
 
-// The scan, CELL-MAJOR and persistent: the workgroups walk the work items (item i of the grid-strided list belongs to the cell c with
-// item_off[c] <= i < item_off[c + 1]: a binary search) -- only rows somebody probes are ever touched, so a call's cost follows the rows it
-// scans, not the shard.  Per item: stage its G consecutive stored rows in LDS ONCE (coalesced: the store is in cell order) and score them
-// against every query that probes the cell, one half-wave per (query, row), the query row streamed from L2.  The word goes to
-// words[query * max_scan + seg_off[slot] + (row's position inside its cell)] -- inside the query's segment by the plan's own sums over the same
-// list_off, whatever list_off holds; rows outside [0, N) are never read.
-__global__ void __launch_bounds__(ROWGRP_THREADS)
-k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids,
-           int nlist, const float* __restrict__ q, int nprobe, const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off,
-           const unsigned int* __restrict__ item_off, unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan,
-           unsigned long long* __restrict__ words) {
-  __shared__ __attribute__((aligned(16))) float s_x[ROWGRP_LDS_FLOATS];
-  const int tid = threadIdx.x, lane = tid & 63, hw = tid >> 5;
+// The walk of the CELL-MAJOR scans (k_ivf_scan below, k_ivf_sq_scan, k_ivf_sq8_scan), persistent: the workgroups walk the work items (item i
+// of the grid-strided list belongs to the cell c with item_off[c] <= i < item_off[c + 1]: a binary search) -- only rows somebody probes are
+// ever touched, so a call's cost follows the rows it scans, not the shard.  Per item: `stage(ra, nrows)` puts its nrows <= G consecutive stored
+// rows, from position ra, in the kernel's LDS ONCE (coalesced: the store is in cell order), between two barriers; then every (pair, row) unit
+// -- a query that probes the cell, named by the pair's slot = query * nprobe + j, and row rr of the group -- is scored by one half-wave:
+// `score(rr, query, slot)`, the query row streamed from L2.  The word goes to words[query * max_scan + seg_off[slot] + (row's position inside
+// its cell)] -- the contract with k_ivf_plan, k_ivf_select and k_ivf_range: inside the query's segment by the plan's own sums over the same
+// list_off, whatever list_off holds; rows outside [0, N) are never read, and an original row outside it becomes a word of 0 and is counted.
+template <class Stage, class Score>
+__device__ __forceinline__ void ivf_scan_items(int64_t N, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist,
+                                               int nprobe, const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off,
+                                               const unsigned int* __restrict__ item_off, unsigned int item_cap, const unsigned int* __restrict__ seg_off,
+                                               int64_t max_scan, unsigned long long* __restrict__ words, Stage stage, Score score) {
+  const int lane = threadIdx.x & 63, hw = threadIdx.x >> 5;
   const unsigned int n_items = min(item_off[nlist], item_cap);
   unsigned int bad = 0;
   for (unsigned int it = blockIdx.x; it < n_items; it += gridDim.x) {
@@ -214,10 +216,7 @@ k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, co
     if (ra < ca || ra < 0 || rb <= ra || np == 0) continue;  // (workgroup-uniform)
     const int nrows = (int)(rb - ra);
     __syncthreads();                                         // the previous item's rows are no longer read
-    for (int i = tid * 4; i < nrows * D; i += ROWGRP_THREADS * 4) {
-      const int rr = i / D, cc = i - rr * D;
-      *(f32x4*)(s_x + i) = REF_ROW_LOAD((const f32x4*)(X + (ra + rr) * ldx + cc));
-    }
+    stage(ra, nrows);
     __syncthreads();
     const unsigned int units = np * (unsigned int)nrows;     // (at most IVF_MAX_CHUNK pairs x 128 rows)
     for (unsigned int u = hw; u < units; u += ROWGRP_THREADS / 32) {
@@ -226,7 +225,7 @@ k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, co
       const int64_t r = ra + rr;
       const unsigned int slot = (unsigned int)sorted[p0 + pi];
       const unsigned int qi = slot / (unsigned int)nprobe;
-      const float sc = exact_dot_lds_row(s_x + rr * D, q + (int64_t)qi * D, D, lane);
+      const float sc = score(rr, qi, slot);
       if ((lane & 31) == 0) {
         const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
         const bool ok = orig >= 0 && orig < N;               // (a word of 0 is nobody's row: the selection drops it)
@@ -236,6 +235,30 @@ k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, co
     }
   }
   if (bad) atomicAdd(&g_ivf_bad, bad);
+}
+
+// The base term of a pair in the scans over residual codes: the caller's score of the cell for that query, read through the pair's slot --
+// probe_scores[query * ld_probe + slot % nprobe] (NULL: 0).
+__device__ __forceinline__ double ivf_probe_base(const float* __restrict__ probe_scores, int64_t ld_probe, int nprobe, unsigned int qi, unsigned int slot) {
+  return probe_scores != nullptr ? (double)probe_scores[(int64_t)qi * ld_probe + (slot - qi * (unsigned int)nprobe)] : 0.0;
+}
+
+// The scan over fp32 rows: a group is staged as it is stored, a pair's score is exact_dot_lds_row's (the bits of exact_dot).
+__global__ void __launch_bounds__(ROWGRP_THREADS)
+k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids,
+           int nlist, const float* __restrict__ q, int nprobe, const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off,
+           const unsigned int* __restrict__ item_off, unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan,
+           unsigned long long* __restrict__ words) {
+  __shared__ __attribute__((aligned(16))) float s_x[ROWGRP_LDS_FLOATS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+    [&](int64_t ra, int nrows) {
+      for (int i = tid * 4; i < nrows * D; i += ROWGRP_THREADS * 4) {
+        const int rr = i / D, cc = i - rr * D;
+        *(f32x4*)(s_x + i) = REF_ROW_LOAD((const f32x4*)(X + (ra + rr) * ldx + cc));
+      }
+    },
+    [&](int rr, unsigned int qi, unsigned int) { return exact_dot_lds_row(s_x + rr * D, q + (int64_t)qi * D, D, lane); });
 }
 
 // radix_select_kth_list over the LOW words of the entries whose key is `key_hi`: the kk-th largest of them (ties inside one score)

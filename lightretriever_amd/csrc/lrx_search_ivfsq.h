@@ -17,85 +17,31 @@ static int ivf_sq_group_rows(int32_t dim) {
 }
 extern "C" int32_t lrx_ivf_sq_fp16_group_rows(int32_t dim) { return dim >= 1 ? ivf_sq_group_rows(dim) : 0; }
 
-// exact_dot_codes with the code row in LDS (row-major) and the query row in global memory: the SAME partial products in the same order (lane
-// sub of a half-wave: elements i0 + 128 u + (0..3), i0 = 4 sub, 2048-element blocks), each code decoded exactly to fp32, fp64 accumulation,
-// the same xor tree; `base` joins the reduced sum before the one rounding.  base = 0: bit-identical to exact_dot_codes (the sum is never -0).
+// exact_dot_lds over a row of fp16 codes (row-major in LDS), each code decoded exactly to fp32: the partial products and their order are
+// exact_dot_codes', and with base = 0 so are the bits.
 __device__ __forceinline__ float exact_dot_lds_codes(const _Float16* c_lds, const float* __restrict__ qglob, int D, int lane, double base) {
-  const int sub = lane & 31;
-  double acc = 0.0;
-  for (int i0 = sub * 4; i0 < D; i0 += 2048) {
-    f32x4 qv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = i0 + u * 128;
-      qv[u] = i < D ? *(const f32x4*)(qglob + i) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = i0 + u * 128;
-      if (i < D) {
-        const f16x4 xv = *(const f16x4*)(c_lds + i);
-        acc += (double)(float)xv[0] * (double)qv[u][0] + (double)(float)xv[1] * (double)qv[u][1] + (double)(float)xv[2] * (double)qv[u][2] +
-               (double)(float)xv[3] * (double)qv[u][3];
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  return (float)(base + acc);
+  return exact_dot_lds<true>([=](int i) { const f16x4 h = *(const f16x4*)(c_lds + i); return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]}; },
+                             qglob, D, lane, base);
 }
 
-// The scan: k_ivf_scan's walk (persistent, cell-major, the same items, pairs and word positions) over fp16 codes.  Per item its G consecutive
-// code rows -- one contiguous run of nrows * D halves, 16-byte aligned since D % 32 == 0 -- are staged in LDS AS fp16 (coalesced non-temporal
-// 16-byte loads) and scored against every query that probes the cell, one half-wave per (pair, row).  The base term of a pair is the caller's
-// score of the cell for that query, read through the pair's slot: probe_scores[query * ld_probe + slot % nprobe] (NULL: 0).  Rows outside
-// [0, N) are never read; an original row outside it becomes a word of 0 and is counted.
+// The scan: ivf_scan_items (lrx_search_ivf.h) over fp16 codes.  A group's code rows -- one contiguous run of nrows * D halves, 16-byte aligned
+// since D % 32 == 0, nrows * D <= IVFSQ_LDS_HALVES -- are staged in LDS AS fp16 (coalesced non-temporal 16-byte loads); a pair's score is
+// the dot over the codes plus its base term (ivf_probe_base).
 __global__ void __launch_bounds__(ROWGRP_THREADS)
 k_ivf_sq_scan(const _Float16* __restrict__ C, int64_t N, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist,
               const float* __restrict__ q, const float* __restrict__ probe_scores, int nprobe, int64_t ld_probe,
               const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off, const unsigned int* __restrict__ item_off,
               unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words) {
   __shared__ __attribute__((aligned(16))) _Float16 s_c[IVFSQ_LDS_HALVES];
-  const int tid = threadIdx.x, lane = tid & 63, hw = tid >> 5;
-  const unsigned int n_items = min(item_off[nlist], item_cap);
-  unsigned int bad = 0;
-  for (unsigned int it = blockIdx.x; it < n_items; it += gridDim.x) {
-    int lo = 0, hi = nlist;                                  // the last cell with item_off[c] <= it
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (item_off[mid] <= it) lo = mid; else hi = mid;
-    }
-    const int c = lo;
-    const int64_t ca = list_off[c], cb = list_off[c + 1];
-    const int64_t ra = ca + (int64_t)(it - item_off[c]) * G;
-    int64_t rb = ra + G;
-    rb = rb < cb ? rb : cb;
-    rb = rb < N ? rb : N;
-    const unsigned int p0 = cell_off[c], np = cell_off[c + 1] - p0;
-    if (ra < ca || ra < 0 || rb <= ra || np == 0) continue;  // (workgroup-uniform)
-    const int nrows = (int)(rb - ra);                        // (<= G: nrows * D <= IVFSQ_LDS_HALVES)
-    __syncthreads();                                         // the previous item's codes are no longer read
-    const _Float16* src = C + ra * D;
-    for (int i = tid * 8; i < nrows * D; i += ROWGRP_THREADS * 8) *(f16x8*)(s_c + i) = __builtin_nontemporal_load((const f16x8*)(src + i));
-    __syncthreads();
-    const unsigned int units = np * (unsigned int)nrows;     // (at most IVF_MAX_CHUNK pairs x 128 rows)
-    for (unsigned int u = hw; u < units; u += ROWGRP_THREADS / 32) {
-      const unsigned int pi = u / (unsigned int)nrows;
-      const int rr = (int)(u - pi * (unsigned int)nrows);
-      const int64_t r = ra + rr;
-      const unsigned int slot = (unsigned int)sorted[p0 + pi];
-      const unsigned int qi = slot / (unsigned int)nprobe;
-      const double base = probe_scores != nullptr ? (double)probe_scores[(int64_t)qi * ld_probe + (slot - qi * (unsigned int)nprobe)] : 0.0;
-      const float sc = exact_dot_lds_codes(s_c + rr * D, q + (int64_t)qi * D, D, lane, base);
-      if ((lane & 31) == 0) {
-        const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
-        const bool ok = orig >= 0 && orig < N;               // (a word of 0 is nobody's row: the selection drops it)
-        if (!ok) ++bad;
-        words[(int64_t)qi * max_scan + seg_off[slot] + (r - ca)] = ok ? sel_pack(f2key(sc), orig) : 0ull;
-      }
-    }
-  }
-  if (bad) atomicAdd(&g_ivf_bad, bad);
+  const int tid = threadIdx.x, lane = tid & 63;
+  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+    [&](int64_t ra, int nrows) {
+      const _Float16* src = C + ra * D;
+      for (int i = tid * 8; i < nrows * D; i += ROWGRP_THREADS * 8) *(f16x8*)(s_c + i) = __builtin_nontemporal_load((const f16x8*)(src + i));
+    },
+    [&](int rr, unsigned int qi, unsigned int slot) {
+      return exact_dot_lds_codes(s_c + rr * D, q + (int64_t)qi * D, D, lane, ivf_probe_base(probe_scores, ld_probe, nprobe, qi, slot));
+    });
 }
 
 // The codes of n rows, one workgroup per row in turn: v = x - centroid[cell] (one fp32 subtraction; cent == NULL: v = x), code = fp16(v) by

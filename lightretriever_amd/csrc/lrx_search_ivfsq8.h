@@ -8,7 +8,7 @@
 // The only kernel of the chain that is this file's is the scan: k_ivf_scan's item walk over codes of 1 byte per element, row-major [n_rows, dim]
 // by stored position (NOT the tiled layout of the flat 8-bit index: a cell's rows are consecutive, so a group is one contiguous run of bytes).
 // Unlike the fp16 scan, which converts a code once per (query, row) pair, the group is DECODED ONCE per item, to fp32 in LDS, and every pair is
-// then scored by exact_dot_lds_row's loop: k_ivf_scan's per-pair work over a quarter of its HBM bytes.
+// then scored by exact_dot_lds, the dot of the fp32 scan: k_ivf_scan's per-pair work over a quarter of its HBM bytes.
 #pragma once
 
 extern "C" int32_t lrx_ivf_sq8_group_rows(int32_t dim) { return dim >= 1 ? ivf_group_rows(dim) : 0; }   // (the fp32 scan's: the group is staged as fp32)
@@ -20,47 +20,23 @@ __device__ __forceinline__ float sq8_dec_t(float t, float vmin, float vdiff) {
   return vmin + m;
 }
 
-// exact_dot_lds_row with a base term over a row of the scan's SWIZZLED LDS image (k_ivf_sq8_scan: the 16-byte slot s of the 64-byte chunk c
-// lies at slot s ^ (c / 2) % 4; `swz` is that xor for this lane's chunks of this row, the same for all of them since a lane's chunks are 8
-// apart): the SAME partial products in the same order -- lane sub still multiplies elements 4 sub + 128 u + 0..3 of each 2048-element block --
-// fp64 accumulation, the same xor tree; `base` joins the reduced sum before the one rounding.  base = 0: bit-identical to exact_dot_lds_row
-// over the same values (a lane's sum starts at +0, so the total is never -0).
+// exact_dot_lds over a row of the scan's SWIZZLED LDS image (k_ivf_sq8_scan: the 16-byte slot s of the 64-byte chunk c lies at slot
+// s ^ (c / 2) % 4; `swz` is that xor for this lane's chunks of this row, the same for all of them since a lane's chunks are 8 apart): lane
+// sub still multiplies elements 4 sub + 128 u + 0..3 of each 2048-element block, read from where the swizzle put them.
 __device__ __forceinline__ float exact_dot_lds_row_base(const float* x_lds, const float* __restrict__ qglob, int D, int lane, int swz, double base) {
   const int sub = lane & 31;
   const int x0 = 4 * ((sub & ~3) | ((sub & 3) ^ swz)) - 4 * sub;   // where this lane's elements lie, relative to their logical place
-  double acc = 0.0;
-  for (int i0 = sub * 4; i0 < D; i0 += 2048) {
-    f32x4 qv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = i0 + u * 128;
-      qv[u] = i < D ? *(const f32x4*)(qglob + i) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = i0 + u * 128;
-      if (i < D) {
-        const f32x4 xv = *(const f32x4*)(x_lds + i + x0);
-        acc += (double)xv[0] * (double)qv[u][0] + (double)xv[1] * (double)qv[u][1] + (double)xv[2] * (double)qv[u][2] +
-               (double)xv[3] * (double)qv[u][3];
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  return (float)(base + acc);
+  return exact_dot_lds<true>([=](int i) { return *(const f32x4*)(x_lds + i + x0); }, qglob, D, lane, base);
 }
 
-// The scan: k_ivf_scan's walk (persistent, cell-major, the same items, pairs and word positions) over 8-bit codes.  Per item its G consecutive
-// code rows -- one contiguous run of nrows * D bytes, 16-byte aligned since D % 32 == 0 -- are loaded with coalesced non-temporal 16-byte loads
+// The scan: ivf_scan_items (lrx_search_ivf.h) over 8-bit codes.  A group's code rows -- one contiguous run of nrows * D bytes, 16-byte aligned
+// since D % 32 == 0, nrows * D <= ROWGRP_LDS_FLOATS -- are loaded with coalesced non-temporal 16-byte loads
 // (16 codes per lane) and decoded ONCE into LDS as fp32 (64 KiB): y = vmin_i + t[code] * vdiff_i, t from a 256-entry LDS table of
 // fl32((c + 0.5) / 255) (IEEE division, built by the workgroup), vmin / vdiff per dimension from `trained` (two scalars for the uniform type: UNIFORM).
 // A lane's 16 floats -- one 64-byte chunk c = i / 16 of the image -- are four 16-byte LDS stores; slot s goes to slot s ^ (c / 2) % 4, so the
 // eight lanes that one store cycle serves (banks (a / 4) % 32, 64 B per lane: unswizzled they would hit two slots four times over) hit eight
-// distinct 16-byte slots; the half-wave that reads a row undoes it per lane.  Every (pair, row) of the cell is then scored by
-// one half-wave from the fp32 rows (exact_dot_lds_row_base).  The base term of a pair is the caller's score of the cell for that query, read
-// through the pair's slot: probe_scores[query * ld_probe + slot % nprobe] (NULL: 0).  Rows outside [0, N) are never read; an original row
-// outside it becomes a word of 0 and is counted.
+// distinct 16-byte slots; the half-wave that reads a row undoes it per lane (exact_dot_lds_row_base).  A pair's score is the dot over the
+// fp32 rows plus its base term (ivf_probe_base).
 template <bool UNIFORM>
 __global__ void __launch_bounds__(ROWGRP_THREADS, 4)          // (4 waves per SIMD = two workgroups per CU, as k_ivf_scan has: at most 128 VGPRs)
 k_ivf_sq8_scan(const uint8_t* __restrict__ C, int64_t N, int D, int G, const float* __restrict__ trained,
@@ -70,68 +46,38 @@ k_ivf_sq8_scan(const uint8_t* __restrict__ C, int64_t N, int D, int G, const flo
                const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words) {
   __shared__ __attribute__((aligned(16))) float s_x[ROWGRP_LDS_FLOATS];
   __shared__ float s_t[256];
-  const int tid = threadIdx.x, lane = tid & 63, hw = tid >> 5;
-  if (tid < 256) s_t[tid] = __fdiv_rn((float)tid + 0.5f, 255.f);   // (read after the barrier in front of the first item's staging)
-  const unsigned int n_items = min(item_off[nlist], item_cap);
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid < 256) s_t[tid] = __fdiv_rn((float)tid + 0.5f, 255.f);   // (read after the walk's barrier in front of the first item's staging)
   const int col0 = (tid * 16) % D, col_step = (ROWGRP_THREADS * 16) % D;   // the dimension of a lane's first code, pass by pass (no division per item)
-  unsigned int bad = 0;
-  for (unsigned int it = blockIdx.x; it < n_items; it += gridDim.x) {
-    int lo = 0, hi = nlist;                                  // the last cell with item_off[c] <= it
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (item_off[mid] <= it) lo = mid; else hi = mid;
-    }
-    const int c = lo;
-    const int64_t ca = list_off[c], cb = list_off[c + 1];
-    const int64_t ra = ca + (int64_t)(it - item_off[c]) * G;
-    int64_t rb = ra + G;
-    rb = rb < cb ? rb : cb;
-    rb = rb < N ? rb : N;
-    const unsigned int p0 = cell_off[c], np = cell_off[c + 1] - p0;
-    if (ra < ca || ra < 0 || rb <= ra || np == 0) continue;  // (workgroup-uniform)
-    const int nrows = (int)(rb - ra);                        // (<= G: nrows * D <= ROWGRP_LDS_FLOATS)
-    __syncthreads();                                         // the previous item's rows are no longer read (and s_t is written)
-    int col = col0;                                          // (D % 32 == 0: a lane's 16 codes are 16 consecutive dimensions of one row)
-    const uint8_t* src = C + ra * D;
-    for (int i = tid * 16; i < nrows * D; i += ROWGRP_THREADS * 16, col += col_step, col -= col >= D ? D : 0) {
-      const sq8_i32x4 cw = __builtin_nontemporal_load((const sq8_i32x4*)(src + i));
-      const int swz = (i >> 5) & 3;                          // the chunk's slot xor
+  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+    [&](int64_t ra, int nrows) {
+      int col = col0;                                        // (D % 32 == 0: a lane's 16 codes are 16 consecutive dimensions of one row)
+      const uint8_t* src = C + ra * D;
+      for (int i = tid * 16; i < nrows * D; i += ROWGRP_THREADS * 16, col += col_step, col -= col >= D ? D : 0) {
+        const sq8_i32x4 cw = __builtin_nontemporal_load((const sq8_i32x4*)(src + i));
+        const int swz = (i >> 5) & 3;                        // the chunk's slot xor
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const uint32_t w = (uint32_t)cw[g];
-        f32x4 mn, df;
-        if (UNIFORM) {
-          mn = f32x4{trained[0], trained[0], trained[0], trained[0]};
-          df = f32x4{trained[1], trained[1], trained[1], trained[1]};
-        } else {
-          mn = *(const f32x4*)(trained + col + 4 * g);
-          df = *(const f32x4*)(trained + D + col + 4 * g);
+        for (int g = 0; g < 4; ++g) {
+          const uint32_t w = (uint32_t)cw[g];
+          f32x4 mn, df;
+          if (UNIFORM) {
+            mn = f32x4{trained[0], trained[0], trained[0], trained[0]};
+            df = f32x4{trained[1], trained[1], trained[1], trained[1]};
+          } else {
+            mn = *(const f32x4*)(trained + col + 4 * g);
+            df = *(const f32x4*)(trained + D + col + 4 * g);
+          }
+          f32x4 y;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) y[e] = sq8_dec_t(s_t[(w >> (8 * e)) & 255u], mn[e], df[e]);
+          *(f32x4*)(s_x + i + 4 * (g ^ swz)) = y;
         }
-        f32x4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = sq8_dec_t(s_t[(w >> (8 * e)) & 255u], mn[e], df[e]);
-        *(f32x4*)(s_x + i + 4 * (g ^ swz)) = y;
       }
-    }
-    __syncthreads();
-    const unsigned int units = np * (unsigned int)nrows;     // (at most IVF_MAX_CHUNK pairs x 128 rows)
-    for (unsigned int u = hw; u < units; u += ROWGRP_THREADS / 32) {
-      const unsigned int pi = u / (unsigned int)nrows;
-      const int rr = (int)(u - pi * (unsigned int)nrows);
-      const int64_t r = ra + rr;
-      const unsigned int slot = (unsigned int)sorted[p0 + pi];
-      const unsigned int qi = slot / (unsigned int)nprobe;
-      const double base = probe_scores != nullptr ? (double)probe_scores[(int64_t)qi * ld_probe + (slot - qi * (unsigned int)nprobe)] : 0.0;
-      const float sc = exact_dot_lds_row_base(s_x + rr * D, q + (int64_t)qi * D, D, lane, (rr * (D >> 5) + ((lane & 31) >> 3)) & 3, base);
-      if ((lane & 31) == 0) {
-        const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
-        const bool ok = orig >= 0 && orig < N;               // (a word of 0 is nobody's row: the selection drops it)
-        if (!ok) ++bad;
-        words[(int64_t)qi * max_scan + seg_off[slot] + (r - ca)] = ok ? sel_pack(f2key(sc), orig) : 0ull;
-      }
-    }
-  }
-  if (bad) atomicAdd(&g_ivf_bad, bad);
+    },
+    [&](int rr, unsigned int qi, unsigned int slot) {
+      return exact_dot_lds_row_base(s_x + rr * D, q + (int64_t)qi * D, D, lane, (rr * (D >> 5) + ((lane & 31) >> 3)) & 3,
+                                    ivf_probe_base(probe_scores, ld_probe, nprobe, qi, slot));
+    });
 }
 
 // The codes of n rows, one thread per 16-column piece of a row (64 B of fp32 in, ONE 16-byte store out, row-major): v = x - centroid[cell]

@@ -125,8 +125,13 @@ k_pairs_scatter(const unsigned long long* __restrict__ pairs, const unsigned int
   }
 }
 // exact_dot with the row in LDS and the query row in global memory: the SAME partial products in the same order (lane sub of a half-wave:
-// elements i0 + 128 u + (0..3), i0 = 4 sub, 2048-element blocks), fp64 accumulation, the same xor tree -- bit-identical to exact_dot
-__device__ __forceinline__ float exact_dot_lds_row(const float* x_lds, const float* __restrict__ qglob, int D, int lane) {
+// elements i0 + 128 u + (0..3), i0 = 4 sub, 2048-element blocks; the 16 query loads of a block are issued ahead of use), fp64 accumulation,
+// the same xor tree -- bit-identical to exact_dot.  `load(i)` gives elements i .. i + 3 of the LDS row as fp32 (exactly: a plain fp32 read, one
+// through the 8-bit scan's slot swizzle, or fp16 codes widened).  BASE: `base` joins the reduced sum before the one rounding (the scans over
+// residual codes: lrx_search_ivfsq.h, lrx_search_ivfsq8.h); base = 0 gives the bits of BASE = false, since a lane's sum starts at +0 and the
+// total is never -0.
+template <bool BASE, class Load>
+__device__ __forceinline__ float exact_dot_lds(Load load, const float* __restrict__ qglob, int D, int lane, double base = 0.0) {
   const int sub = lane & 31;
   double acc = 0.0;
   for (int i0 = sub * 4; i0 < D; i0 += 2048) {
@@ -140,7 +145,7 @@ __device__ __forceinline__ float exact_dot_lds_row(const float* x_lds, const flo
     for (int u = 0; u < 16; ++u) {
       const int i = i0 + u * 128;
       if (i < D) {
-        const f32x4 xv = *(const f32x4*)(x_lds + i);
+        const f32x4 xv = load(i);
         acc += (double)xv[0] * (double)qv[u][0] + (double)xv[1] * (double)qv[u][1] + (double)xv[2] * (double)qv[u][2] +
                (double)xv[3] * (double)qv[u][3];
       }
@@ -148,7 +153,11 @@ __device__ __forceinline__ float exact_dot_lds_row(const float* x_lds, const flo
   }
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  return (float)acc;
+  return BASE ? (float)(base + acc) : (float)acc;
+}
+// ... over a plain fp32 row (k_rescore_row_groups below, k_ivf_scan)
+__device__ __forceinline__ float exact_dot_lds_row(const float* x_lds, const float* __restrict__ qglob, int D, int lane) {
+  return exact_dot_lds<false>([=](int i) { return *(const f32x4*)(x_lds + i); }, qglob, D, lane);
 }
 #define ROWGRP_LDS_FLOATS 16384          // 64 KiB of rows per workgroup (two workgroups per CU: one stages while the other multiplies): 8 rows at D = 2048, 4 at 4096
 #define ROWGRP_THREADS 512

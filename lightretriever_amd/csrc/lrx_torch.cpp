@@ -358,48 +358,73 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> range_result(const at::Tensor& li
   TORCH_CHECK(false, who, ": the result grew between two identical calls");
 }
 
-// Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell, list_off int64 [nlist + 1], row_ids int64 [n_rows] (the
-// original row of a position) or None, probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted),
-// max_scan_rows = the caller's bound on the rows one query scans.  Returns (D, I).
-// The argument checks ivf_flat_ip_topk and ivf_flat_ip_range_search share; fin(...) makes the library call from what they establish.
-template <class Fin>
-auto ivf_flat_ip_op(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
-    const at::Tensor& probes, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
-  DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(x, "x", at::kFloat, 2);
+// ---- inverted file: the four families (flat, PQ, fp16, 8-bit) ------------------------------------------------------------------
+// The result of a top-k op, as range_result is of a range op: `call(d, i)` runs the library call over the outputs.
+template <class Call>
+std::tuple<at::Tensor, at::Tensor> topk_result(const at::Tensor& q, int64_t k, const char* who, Call call) {
+  TopK o = topk_out(q, k);
+  lrx_check(call(o.d.data_ptr<float>(), o.i.data_ptr<int64_t>()), who);
+  return {o.d, o.i};
+}
+
+// What the four families check alike, after need() on q and on their own store: list_off int64 [nlist + 1], probes int64 [Q, nprobe] (rows may
+// be strided; < 0 skipped, >= nlist skipped and counted), max_scan_rows = the caller's bound on the rows one query scans, row_ids int64 (the
+// original row of a position) or None, probe_scores fp32 [Q, nprobe] with the row stride of probes when by_residual, row_map.  `store_ok` is the
+// family's own part of the shape check and `shapes` the sentence that names every operand of it.
+struct IvfArgs {
+  int64_t Q, nlist, nprobe, ld_probe;
+  const int64_t *ri, *rm;
+  const float* ps;
+};
+IvfArgs ivf_args(const char* who, const at::Tensor& q, bool store_ok, const char* shapes, int64_t n_rows, const at::Tensor& list_off,
+                 const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+                 int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
   need(list_off, "list_off", at::kLong, 1);
   need(probes, "probes", at::kLong, 2);
-  const int64_t n_rows = x.size(0), dim = x.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
-                  (probes.size(1) == 0 || probes.stride(1) == 1) && (n_rows <= 1 || x.stride(1) == 1),
-              who, ": q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
-  const int64_t* ri = nullptr;
+  IvfArgs a{q.size(0), list_off.size(0) - 1, probes.size(1), 0, nullptr, nullptr, nullptr};
+  TORCH_CHECK(q.is_contiguous() && store_ok && probes.size(0) == a.Q && list_off.is_contiguous() && a.nlist >= 1 && (a.nprobe == 0 || probes.stride(1) == 1),
+              who, shapes);
+  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && a.nlist < (1ll << 31) && a.nprobe < (1ll << 31), who, ": sizes out of range");
   if (row_ids.has_value() && row_ids->defined()) {
     need(*row_ids, "row_ids", at::kLong, 1);
     TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
-    ri = row_ids->data_ptr<int64_t>();
+    a.ri = row_ids->data_ptr<int64_t>();
   }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
-  return fin(n_rows, dim, nlist, nprobe, ri, rm);
+  a.ld_probe = a.Q > 1 ? probes.stride(0) : a.nprobe;
+  if (by_residual) {
+    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
+    need(*probe_scores, "probe_scores", at::kFloat, 2);
+    TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (a.nprobe == 0 || probe_scores->stride(1) == 1) && (a.Q <= 1 || probe_scores->stride(0) == a.ld_probe),
+                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
+    a.ps = probe_scores->data_ptr<float>();
+  }
+  a.rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
+  return a;
+}
+
+// Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell.  Returns (D, I).
+IvfArgs ivf_flat_ip_args(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
+                         const at::Tensor& probes, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
+  need(q, "q", at::kFloat, 2);
+  need(x, "x", at::kFloat, 2);
+  return ivf_args(who, q, q.size(1) == x.size(1) && (x.size(0) <= 1 || x.stride(1) == 1),
+                  ": q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]", x.size(0), list_off, row_ids, probes, c10::nullopt,
+                  false, max_scan_rows, row_map);
 }
 
 std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
                                                     const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, int64_t k, int64_t max_scan_rows,
                                                     int64_t id_base, const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_flat_ip_topk";
-return ivf_flat_ip_op(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map, [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe,
-                     const int64_t* ri, const int64_t* rm) -> std::tuple<at::Tensor, at::Tensor> {
-    const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    TopK o = topk_out(q, k);
-    lrx_check(lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(), ri,
-                                     (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), (int32_t)nprobe,
-                                     probes.size(0) > 1 ? probes.stride(0) : nprobe, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
-                                     o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-              who);
-    return {o.d, o.i};
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
+  const int64_t n_rows = x.size(0), dim = x.size(1);
+  const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    return lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(),
+                                  a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe,
+                                  max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
 }
 
@@ -409,63 +434,40 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search(const at
                                                                         const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, double radius,
                                                                         int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_flat_ip_range_search";
-  return ivf_flat_ip_op(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map,
-                        [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const int64_t* rm) {
-    const int64_t Q = q.size(0);
-    const size_t wsb = lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-      return lrx_ivf_flat_ip_range_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
-                                          list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(),
-                                          (int32_t)nprobe, Q > 1 ? probes.stride(0) : nprobe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm,
-                                          ws.data_ptr(), wsb, cur_stream());
-    });
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
+  const int64_t n_rows = x.size(0), dim = x.size(1);
+  const size_t wsb = lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_ivf_flat_ip_range_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
+                                        list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(),
+                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(), wsb,
+                                        cur_stream());
   });
 }
 
 // Inverted file over PQ codes (lrx_ivf_pq_ip_search): codes = the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by
-// cell; pq_centroids [M, 256, D / M] fp32; list_off int64 [nlist + 1]; row_ids int64 [n_rows] (the original row of a position) or None -- n_rows
-// is its length, or the rows the code blocks hold; probes int64 [Q, nprobe] and, when by_residual, probe_scores fp32 [Q, nprobe] with the same
-// row stride (rows may be strided).  Returns (D, I).
-// The argument checks ivf_pq_ip_topk and ivf_pq_ip_range_search share; fin(...) makes the library call from what they establish.
-template <class Fin>
-auto ivf_pq_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off, const
-    c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t
-    max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
-  DevGuard guard(q.device());
+// cell; pq_centroids [M, 256, D / M] fp32; n_rows is the length of row_ids, or the rows the code blocks hold.  Returns (D, I).
+struct IvfPqStore {
+  int64_t n_rows, dim, M;
+  void* cb;
+};
+IvfArgs ivf_pq_ip_args(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
+                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+                       int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, IvfPqStore& st) {
   need(q, "q", at::kFloat, 2);
   need(pq_centroids, "pq_centroids", at::kFloat, 3);
-  need(list_off, "list_off", at::kLong, 1);
-  need(probes, "probes", at::kLong, 2);
-  const int64_t dim = q.size(1), M = pq_centroids.size(0), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
-  TORCH_CHECK(q.is_contiguous() && pq_centroids.is_contiguous() && pq_centroids.size(1) == 256 && M > 0 && dim % M == 0 && pq_centroids.size(2) == dim / M &&
-                  probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 && (nprobe == 0 || probes.stride(1) == 1),
-              who, ": q [Q,D] contiguous, pq_centroids [M,256,D/M] contiguous with D % M == 0, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
+  const std::string blocked = std::string(who) + ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)";
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1 && codes.is_contiguous(), blocked);
+  const int64_t dim = q.size(1), M = pq_centroids.size(0);
+  const bool store_ok = pq_centroids.is_contiguous() && pq_centroids.size(1) == 256 && M > 0 && dim % M == 0 && pq_centroids.size(2) == dim / M;
   const int64_t mp = (M + 15) / 16 * 16;
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1 && codes.is_contiguous(),
-              who, ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)");
-  const int64_t* ri = nullptr;
-  int64_t n_rows = codes.numel() / mp;
-  if (row_ids.has_value() && row_ids->defined()) {
-    need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous(), who, ": row_ids int64 [n_rows] contiguous");
-    ri = row_ids->data_ptr<int64_t>();
-    n_rows = row_ids->numel();
-  }
-  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, (std::string(who) + ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)").c_str());
-  const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
-  const float* ps = nullptr;
-  if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
-    need(*probe_scores, "probe_scores", at::kFloat, 2);
-    TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
-                    (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
-    ps = probe_scores->data_ptr<float>();
-  }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
-  return fin(n_rows, dim, M, nlist, nprobe, cb, ri, ps, ld_probe, rm);
+  const int64_t n_rows = row_ids.has_value() && row_ids->defined() ? row_ids->numel() : (store_ok ? codes.numel() / mp : 0);
+  const IvfArgs a = ivf_args(who, q, store_ok, ": q [Q,D] contiguous, pq_centroids [M,256,D/M] contiguous with D % M == 0, list_off int64 [nlist + 1], probes int64 [Q, nprobe]",
+                             n_rows, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
+  st = IvfPqStore{n_rows, dim, M, tiled_rows(codes, at::kByte, n_rows, mp, blocked.c_str())};
+  return a;
 }
 
 std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
@@ -473,18 +475,17 @@ std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at:
                                                   const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
                                                   int64_t id_base, const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_pq_ip_topk";
-return ivf_pq_ip_op(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows,
-                     int64_t dim, int64_t M, int64_t nlist, int64_t nprobe, void* cb, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) ->
-                     std::tuple<at::Tensor, at::Tensor> {
-    const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    TopK o = topk_out(q, k);
-    lrx_check(lrx_ivf_pq_ip_search(n_rows ? cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, list_off.data_ptr<int64_t>(), ri,
-                                   (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe,
-                                   by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb,
-                                   cur_stream()),
-              who);
-    return {o.d, o.i};
+  DevGuard guard(q.device());
+  IvfPqStore st;
+  const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
+  const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k,
+                                                   max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    return lrx_ivf_pq_ip_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
+                                list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb,
+                                cur_stream());
   });
 }
 
@@ -495,73 +496,47 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search(const at::
                                                                       bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
                                                                       const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_pq_ip_range_search";
-  return ivf_pq_ip_op(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
-                      [&](int64_t n_rows, int64_t dim, int64_t M, int64_t nlist, int64_t nprobe, void* cb, const int64_t* ri, const float* ps,
-                          int64_t ld_probe, const int64_t* rm) {
-    const int64_t Q = q.size(0);
-    const size_t wsb = lrx_ivf_pq_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)M, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-      return lrx_ivf_pq_ip_range_search(n_rows ? cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)dim, (int32_t)M, list_off.data_ptr<int64_t>(),
-                                        ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe,
-                                        by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm, ws.data_ptr(), wsb, cur_stream());
-    });
+  DevGuard guard(q.device());
+  IvfPqStore st;
+  const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
+  const size_t wsb = lrx_ivf_pq_ip_range_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe,
+                                                         max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_ivf_pq_ip_range_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
+                                      list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm,
+                                      ws.data_ptr(), wsb, cur_stream());
   });
 }
 
-// Inverted file over fp16 codes (lrx_ivf_sq_fp16_ip_search): codes fp16 [n_rows, D] contiguous, row-major by stored position, cell by cell;
-// list_off int64 [nlist + 1]; row_ids int64 [n_rows] (the original row of a position) or None; probes int64 [Q, nprobe] and, when by_residual,
-// probe_scores fp32 [Q, nprobe] with the same row stride (rows may be strided).  Returns (D, I).
-// The argument checks ivf_sq_fp16_ip_topk and ivf_sq_fp16_ip_range_search share; fin(...) makes the library call from what they establish.
-template <class Fin>
-auto ivf_sq_fp16_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off, const c10::optional<at::Tensor>&
-    row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t max_scan_rows, const
-    c10::optional<at::Tensor>& row_map, Fin fin) {
-  DevGuard guard(q.device());
+// Inverted file over row-major codes [n_rows, D] contiguous, by stored position, cell by cell: fp16 (lrx_ivf_sq_fp16_ip_search) and 8-bit
+// (lrx_ivf_sq8_ip_search).  `shapes`: the family's sentence for the shape check.
+IvfArgs ivf_codes_args(const char* who, const at::Tensor& q, const at::Tensor& codes, at::ScalarType code_type, const char* shapes,
+                       const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+                       const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
   need(q, "q", at::kFloat, 2);
-  need(codes, "codes", at::kHalf, 2);
-  need(list_off, "list_off", at::kLong, 1);
-  need(probes, "probes", at::kLong, 2);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && codes.is_contiguous() && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
-                  (nprobe == 0 || probes.stride(1) == 1),
-              who, ": q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
-  const int64_t* ri = nullptr;
-  if (row_ids.has_value() && row_ids->defined()) {
-    need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
-    ri = row_ids->data_ptr<int64_t>();
-  }
-  const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
-  const float* ps = nullptr;
-  if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
-    need(*probe_scores, "probe_scores", at::kFloat, 2);
-    TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
-                    (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
-    ps = probe_scores->data_ptr<float>();
-  }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
-  return fin(n_rows, dim, nlist, nprobe, ri, ps, ld_probe, rm);
+  need(codes, "codes", code_type, 2);
+  return ivf_args(who, q, q.size(1) == codes.size(1) && codes.is_contiguous(), shapes, codes.size(0), list_off, row_ids, probes, probe_scores, by_residual,
+                  max_scan_rows, row_map);
 }
+const char* const kIvfSqShapes = ": q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
+const char* const kIvfSq8Shapes = ": q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
 
 std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
                                                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
                                                        const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
                                                        int64_t id_base, const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_sq_fp16_ip_topk";
-return ivf_sq_fp16_ip_op(who, q, codes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows, int64_t dim,
-                     int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) -> std::tuple<at::Tensor, at::Tensor> {
-    const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    TopK o = topk_out(q, k);
-    lrx_check(lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), ri, (int32_t)nlist,
-                                        q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe, by_residual ? 1 : 0,
-                                        max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(), o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-              who);
-    return {o.d, o.i};
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
+  const int64_t n_rows = codes.size(0), dim = codes.size(1);
+  const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    return lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
+                                     q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
+                                     max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
 }
 
@@ -572,58 +547,28 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search(const
                                                                            int64_t max_scan_rows, int64_t id_base,
                                                                            const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_sq_fp16_ip_range_search";
-  return ivf_sq_fp16_ip_op(who, q, codes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
-                           [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe,
-                               const int64_t* rm) {
-    const int64_t Q = q.size(0);
-    const size_t wsb = lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-      return lrx_ivf_sq_fp16_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), ri, (int32_t)nlist,
-                                             q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps, (int32_t)nprobe, ld_probe, by_residual ? 1 : 0,
-                                             max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm, ws.data_ptr(), wsb, cur_stream());
-    });
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
+  const int64_t n_rows = codes.size(0), dim = codes.size(1);
+  const size_t wsb = lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_ivf_sq_fp16_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
+                                           q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe,
+                                           by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
 }
 
-// Inverted file over 8-bit codes (lrx_ivf_sq8_ip_search): codes uint8 [n_rows, D] contiguous, row-major by stored position, cell by cell;
-// trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2); the rest as ivf_sq_fp16_ip_topk.  Returns (D, I).
-// The argument checks ivf_sq8_ip_topk and ivf_sq8_ip_range_search share; fin(...) makes the library call from what they establish.
-template <class Fin>
-auto ivf_sq8_ip_op(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype, const at::Tensor&
-    list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-    int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, Fin fin) {
-  DevGuard guard(q.device());
+// The 8-bit family's own operands: trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2).
+IvfArgs ivf_sq8_ip_args(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype, const at::Tensor& list_off,
+                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+                        int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
   need(q, "q", at::kFloat, 2);
   need(codes, "codes", at::kByte, 2);
   need(trained, "trained", at::kFloat, 1);
-  need(list_off, "list_off", at::kLong, 1);
-  need(probes, "probes", at::kLong, 2);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1), nlist = list_off.size(0) - 1, nprobe = probes.size(1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == dim && codes.is_contiguous() && probes.size(0) == q.size(0) && list_off.is_contiguous() && nlist >= 1 &&
-                  (nprobe == 0 || probes.stride(1) == 1),
-              who, ": q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]");
-  TORCH_CHECK((qtype == 0 || qtype == 2) && trained.is_contiguous() && trained.numel() == (qtype == 0 ? 2 * dim : 2),
+  TORCH_CHECK((qtype == 0 || qtype == 2) && trained.is_contiguous() && trained.numel() == (qtype == 0 ? 2 * codes.size(1) : 2),
               who, ": qtype ", qtype, " (0: QT_8bit, 2: QT_8bit_uniform) with trained fp32 [2 D] or [2] contiguous");
-  TORCH_CHECK(max_scan_rows >= 0 && max_scan_rows < (1ll << 31) && nlist < (1ll << 31) && nprobe < (1ll << 31), who, ": sizes out of range");
-  const int64_t* ri = nullptr;
-  if (row_ids.has_value() && row_ids->defined()) {
-    need(*row_ids, "row_ids", at::kLong, 1);
-    TORCH_CHECK(row_ids->is_contiguous() && row_ids->numel() >= n_rows, who, ": row_ids int64 [>= n_rows] contiguous");
-    ri = row_ids->data_ptr<int64_t>();
-  }
-  const int64_t ld_probe = probes.size(0) > 1 ? probes.stride(0) : nprobe;
-  const float* ps = nullptr;
-  if (by_residual) {
-    TORCH_CHECK(probe_scores.has_value() && probe_scores->defined(), who, ": by_residual needs probe_scores");
-    need(*probe_scores, "probe_scores", at::kFloat, 2);
-    TORCH_CHECK(probe_scores->sizes() == probes.sizes() && (nprobe == 0 || probe_scores->stride(1) == 1) &&
-                    (probes.size(0) <= 1 || probe_scores->stride(0) == ld_probe),
-                who, ": probe_scores fp32 [Q, nprobe] with the row stride of probes");
-    ps = probe_scores->data_ptr<float>();
-  }
-  const int64_t* rm = row_map_ptr(row_map, n_rows, (std::string(who) + ": row_map int64 [>= n_rows] contiguous").c_str());
-  return fin(n_rows, dim, nlist, nprobe, ri, ps, ld_probe, rm);
+  return ivf_codes_args(who, q, codes, at::kByte, kIvfSq8Shapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
 }
 
 std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
@@ -631,18 +576,16 @@ std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at
                                                    const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
                                                    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_sq8_ip_topk";
-return ivf_sq8_ip_op(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, [&](int64_t n_rows,
-                     int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe, const int64_t* rm) -> std::tuple<at::Tensor,
-                     at::Tensor> {
-    const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)q.size(0), (int32_t)nprobe, (int32_t)k, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    TopK o = topk_out(q, k);
-    lrx_check(lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                    list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)q.size(0), probes.data_ptr<int64_t>(), ps,
-                                    (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, o.d.data_ptr<float>(),
-                                    o.i.data_ptr<int64_t>(), rm, ws.data_ptr(), wsb, cur_stream()),
-              who);
-    return {o.d, o.i};
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
+  const int64_t n_rows = codes.size(0), dim = codes.size(1);
+  const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    return lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                 list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb,
+                                 cur_stream());
   });
 }
 
@@ -653,18 +596,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search(const at:
                                                                        bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
                                                                        const c10::optional<at::Tensor>& row_map) {
   const char* who = "ivf_sq8_ip_range_search";
-  return ivf_sq8_ip_op(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map,
-                       [&](int64_t n_rows, int64_t dim, int64_t nlist, int64_t nprobe, const int64_t* ri, const float* ps, int64_t ld_probe,
-                           const int64_t* rm) {
-    const int64_t Q = q.size(0);
-    const size_t wsb = lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)nlist, (int32_t)dim, (int32_t)Q, (int32_t)nprobe, max_scan_rows);
-    at::Tensor ws = bytes((int64_t)wsb, q);
-    return range_result(q, Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-      return lrx_ivf_sq8_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                         list_off.data_ptr<int64_t>(), ri, (int32_t)nlist, q.data_ptr<float>(), (int32_t)Q, probes.data_ptr<int64_t>(), ps,
-                                         (int32_t)nprobe, ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, rm,
-                                         ws.data_ptr(), wsb, cur_stream());
-    });
+  DevGuard guard(q.device());
+  const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
+  const int64_t n_rows = codes.size(0), dim = codes.size(1);
+  const size_t wsb = lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  at::Tensor ws = bytes((int64_t)wsb, q);
+  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return lrx_ivf_sq8_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                       list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm,
+                                       ws.data_ptr(), wsb, cur_stream());
   });
 }
 

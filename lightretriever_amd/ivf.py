@@ -26,10 +26,6 @@ from .transform import linear_transform
 MAX_NPROBE = 2048
 MAX_K = 2048
 
-_CAPTURE_WS_ERROR = ("IVFFlatIndex.search under graph capture: the search workspaces must exist before the capture starts -- run one eager "
-                     "search with the same number of queries, k and nprobe first")
-
-
 def check_ivf_args(d: int, nlist: int, nprobe: int, who: str = "IVFFlatIndex"):
     if d % 32 != 0 or not 32 <= d <= 8192:
         raise ValueError(f"{who}: d={d} must be a multiple of 32 (32 .. 8192)")
@@ -45,11 +41,14 @@ def check_nprobe(nprobe: int, nlist: int, who: str = "IVFFlatIndex") -> int:
 
 
 class _IVFCells:
-    """What the inverted-file indexes (IVFFlatIndex here, IVFPQIndex in ivfpq.py) share: the coarse quantiser -- a FlatIPIndex over k-means
-    centroids -- and its training, the cell bookkeeping (`list_off`, `row_ids`, the host `list_sizes`, the cell `_assign` of every original
-    row, `_nsorted`), the staging of append_slot / commit, the search prologue, and the range search over the probed cells
-    (range_search_probed / range_search_preassigned).  A subclass keeps what is its own: the stored rows or codes, add, the rebuild of the cell
-    order (_finalize), the library calls of search and of the range search (_range_cells), persistence."""
+    """What the inverted-file indexes (IVFFlatIndex here, IVFPQIndex, IVFSQIndex, IVFSQ8Index) share: the coarse quantiser -- a FlatIPIndex over
+    k-means centroids -- and its training, the cell bookkeeping (`list_off`, `row_ids`, the host `list_sizes`, the cell `_assign` of every
+    original row, `_nsorted`), the staging of append_slot / commit, add() and the rebuild of the cell order (_finalize) around two hooks, search()
+    around one, and the range search over the probed cells (range_search_probed / range_search_preassigned).
+    The three cell-major indexes keep their rows or codes in `_store`, row-major [capacity, d] by stored position (_init_store), which is
+    reserved, permuted and mapped here; IVFPQIndex overrides _reserve / _permute over the blocked codes of its PQIndex.  A subclass brings
+    _put (rows [a, b) into the store: a copy, or an encode), _topk_cells and _range_cells (the library calls), set_contents, reconstruct_n and
+    persistence."""
 
     NITER = 10
     MAX_POINTS_PER_CENTROID = 256
@@ -130,6 +129,68 @@ class _IVFCells:
             new[:self.ntotal].copy_(self._assign[:self.ntotal])
             self._assign = new
 
+    # -- rows ------------------------------------------------------------------------------------------------------
+    def _init_store(self, capacity: int, dtype: torch.dtype):
+        self.rebuild_chunk_rows = 262144
+        self._store = torch.empty(max(capacity, 0), self.d, dtype=dtype, device=self.device)
+
+    def _reserve(self, n_rows: int):
+        """Room for n_rows rows: the store and `_assign` grow together."""
+        if n_rows > self._store.shape[0]:
+            new = torch.empty(n_rows, self.d, dtype=self._store.dtype, device=self.device)
+            new[:self.ntotal].copy_(self._store[:self.ntotal])
+            self._store = new
+        self._reserve_assign(n_rows)
+
+    def add(self, x):
+        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product and is stored (coded) at its arrival
+        position -- _put -- (raises before train(), as faiss does)."""
+        if not self.is_trained:
+            raise RuntimeError(f"{type(self).__name__}.add: the index is not trained (call train() first)")
+        x = self._rows(x, "add: ")
+        n = x.shape[0]
+        if n == 0:
+            return
+        a, b = self.ntotal, self.ntotal + n
+        if b > self._assign.shape[0]:
+            self._reserve(_grown(self._assign.shape[0], b))
+        self._cells_of(x, self._assign[a:b])
+        self._put(x, a, b)
+        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
+        self.ntotal = b
+
+    def _finalize(self):
+        """The rows back into cell order (see IVFFlatIndex's class note): a no-op unless rows were added since the last search."""
+        if self._nsorted == self.ntotal:
+            return
+        orig, perm = self._cell_order()
+        self._permute(perm)
+        self._set_cell_order(orig, perm)
+
+    def _permute(self, perm: torch.Tensor):
+        """Store row i becomes row perm[i] of the old store: a gather in chunks of `rebuild_chunk_rows` into a second buffer."""
+        n = self.ntotal
+        new = torch.empty(max(self._store.shape[0], n), self.d, dtype=self._store.dtype, device=self.device)
+        for s in range(0, n, self.rebuild_chunk_rows):
+            e = min(s + self.rebuild_chunk_rows, n)
+            torch.index_select(self._store, 0, perm[s:e], out=new[s:e])
+        self._store = new
+
+    def _stored(self) -> torch.Tensor:
+        """The store as it stands, cell by cell: [ntotal, d] (a view)."""
+        self._finalize()
+        return self._store[:self.ntotal]
+
+    def _positions(self, i0: int, n: int) -> torch.Tensor:
+        """The stored positions of ORIGINAL rows [i0, i0 + n)."""
+        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
+        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
+        return pos[i0:i0 + n]
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        return self.reconstruct_n(0, self.ntotal)
+
     def _cell_order(self):
         """(orig, perm) of the rebuild: orig[pos] = the original row of every stored position as it stands (the ordered part, then the new
         rows as added), perm = the stable sort of their cells -- within a cell old rows (ascending) before new rows (ascending)."""
@@ -207,6 +268,27 @@ class _IVFCells:
             self._finalize()
         return q, nprobe
 
+    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
+        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the top k, under the index's score of a scanned row (its class note), over the rows of each
+        query's nprobe best cells (by inner product with the centroids), score descending, ties to the lower original row, (-FLT_MAX, -1)
+        padding where those cells hold fewer than k rows.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).
+        nprobe: this call's (default: the index's)."""
+        q, nprobe = self._begin_search(q, k, nprobe, row_map)
+        if q.shape[0] == 0:
+            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
+        probe_scores, probes = self.quantizer.search(q, nprobe)
+        capture_error = (f"{type(self).__name__}.search under graph capture: the search workspaces must exist before the capture starts -- run one "
+                         "eager search with the same number of queries, k and nprobe first")
+        return self._topk_cells(q, k, probes, probe_scores, self.max_scan_rows(nprobe), row_map, capture_error)
+
+    def range_search(self, q, radius: float):
+        raise NotImplementedError(f"{type(self).__name__}.range_search is not served (range search over the probed cells is a follow-up)")
+
+    @staticmethod
+    def _load_nprobe(st: dict) -> int:
+        """A file's nprobe, clamped to what the constructor accepts."""
+        return min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE)
+
     # -- range search over the probed cells (DESIGN §5.4.14) -----------------------------------------------------------------
     def range_search_probed(self, q, radius: float, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
         """-> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]) device tensors: every row of each query's nprobe best cells -- the cells search()
@@ -273,49 +355,15 @@ class IVFFlatIndex(_IVFCells):
     def __init__(self, d: int, nlist: int, nprobe: int = 1, capacity: int = 0, device: Optional[torch.device] = None, id_base: int = 0):
         check_ivf_args(d, nlist, nprobe)
         self._init_cells(d, nlist, nprobe, capacity, device, id_base)
-        self.rebuild_chunk_rows = 262144
-        self._x = torch.empty(max(capacity, 0), d, dtype=torch.float32, device=self.device)
+        self._init_store(capacity, torch.float32)
 
     def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
         """Lloyd k-means (see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
         self._train_cells(self._rows(x, "train: "), niter, seed)
 
     # -- rows ------------------------------------------------------------------------------------------------------
-    def _reserve(self, n_rows: int):
-        if n_rows > self._x.shape[0]:
-            new = torch.empty(n_rows, self.d, dtype=torch.float32, device=self.device)
-            new[:self.ntotal].copy_(self._x[:self.ntotal])
-            self._x = new
-        self._reserve_assign(n_rows)
-
-    def add(self, x):
-        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFFlatIndex.add: the index is not trained (call train() first)")
-        x = self._rows(x, "add: ")
-        n = x.shape[0]
-        if n == 0:
-            return
-        if self.ntotal + n > self._x.shape[0]:
-            self._reserve(_grown(self._x.shape[0], self.ntotal + n))
-        a, b = self.ntotal, self.ntotal + n
-        self._cells_of(x, self._assign[a:b])
-        self._x[a:b].copy_(x)
-        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
-        self.ntotal = b
-
-    def _finalize(self):
-        """The rows back into cell order (see the class note): a no-op unless rows were added since the last search."""
-        if self._nsorted == self.ntotal:
-            return
-        n = self.ntotal
-        orig, perm = self._cell_order()
-        new = torch.empty(max(self._x.shape[0], n), self.d, dtype=torch.float32, device=self.device)
-        for s in range(0, n, self.rebuild_chunk_rows):
-            e = min(s + self.rebuild_chunk_rows, n)
-            torch.index_select(self._x, 0, perm[s:e], out=new[s:e])
-        self._x = new
-        self._set_cell_order(orig, perm)
+    def _put(self, x: torch.Tensor, a: int, b: int):
+        self._store[a:b].copy_(x)
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """ORIGINAL rows [i0, i0 + n) as an fp32 device tensor [n, d]."""
@@ -323,18 +371,11 @@ class IVFFlatIndex(_IVFCells):
         self._finalize()
         if n == 0:
             return torch.empty(0, self.d, dtype=torch.float32, device=self.device)
-        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
-        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
-        return self._x[pos[i0:i0 + n]]
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
+        return self._store[self._positions(i0, n)]
 
     def stored_rows(self) -> torch.Tensor:
         """The rows as stored, cell by cell: fp32 [ntotal, d] (a view)."""
-        self._finalize()
-        return self._x[:self.ntotal]
+        return self._stored()
 
     def set_contents(self, centroids, rows, list_off, row_ids):
         """Replace the centroids ([nlist, d]) and the rows: `rows` fp32 [n, d] already in cell order, list_off int64 [nlist + 1] (ascending from
@@ -345,40 +386,29 @@ class IVFFlatIndex(_IVFCells):
         lo, ri = self._check_cells(rows.shape[0], list_off, row_ids)
         self._set_centroids(torch.as_tensor(centroids))
         self._clear_rows()
-        self._x = rows.to(self.device, torch.float32).contiguous().clone()
+        self._store = rows.to(self.device, torch.float32).contiguous().clone()
         self._set_cells(lo, ri)
 
-    # -- search --------------------------------------------------------------------------------------------------
-    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
-        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the exact top k over the rows of each query's nprobe best cells (by inner product with
-        the centroids), score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
-        I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
-        q, nprobe = self._begin_search(q, k, nprobe, row_map)
-        if q.shape[0] == 0:
-            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
-        _, probes = self.quantizer.search(q, nprobe)
-        return ops.ivf_flat_ip_topk(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, k, self.max_scan_rows(nprobe), self.id_base, row_map,
-                                    ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+    # -- search: the exact top k, every scanned (query, row) pair scored with the flat index's own bits --------------------------
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+        return ops.ivf_flat_ip_topk(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, k, max_scan_rows, self.id_base, row_map,
+                                    ws_slots=vars(self), capture_error=capture_error)
 
     def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
-        return ops.ivf_flat_ip_range_search(q, self._x[:self.ntotal], self.list_off, self.row_ids, probes, radius, max_scan_rows, self.id_base, row_map,
+        return ops.ivf_flat_ip_range_search(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, radius, max_scan_rows, self.id_base, row_map,
                                             ws_slots=vars(self))
-
-    def range_search(self, q, radius: float):
-        raise NotImplementedError("IVFFlatIndex.range_search is not served (range search over the probed cells is a follow-up)")
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFFlat, see index_io.py) -------------------------------
     def save(self, fname: str):
         from .index_io import write_ivf_flat
-        self._finalize()
-        write_ivf_flat(fname, self.centroids.cpu().numpy(), self.list_sizes, self._x[:self.ntotal].cpu().numpy(), self.row_ids.cpu().numpy(), self.nprobe,
+        write_ivf_flat(fname, self.centroids.cpu().numpy(), self.list_sizes, self.stored_rows().cpu().numpy(), self.row_ids.cpu().numpy(), self.nprobe,
                        self.is_trained)
 
     @classmethod
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0) -> "IVFFlatIndex":
         from .index_io import read_ivf_flat
         st = read_ivf_flat(fname)
-        idx = cls(st["d"], st["nlist"], nprobe=min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE), device=device, id_base=id_base)
+        idx = cls(st["d"], st["nlist"], nprobe=cls._load_nprobe(st), device=device, id_base=id_base)
         if st["is_trained"]:
             idx.set_contents(np.array(st["centroids"], copy=True), st["rows"], st["list_off"], st["row_ids"])
         return idx

@@ -15,12 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import PQIndex, _check_range, _grown
-from .ivf import MAX_NPROBE, _IVFCells, check_ivf_args
-
-_CAPTURE_WS_ERROR = ("IVFPQIndex.search under graph capture: the search workspaces must exist before the capture starts -- run one eager "
-                     "search with the same number of queries, k and nprobe first")
-
+from .index import PQIndex, _check_range
+from .ivf import _IVFCells, check_ivf_args
 
 def check_ivfpq_args(d: int, nlist: int, M: int, nbits: int = 8, nprobe: int = 1):
     """The constructor's refusals (no GPU is needed): nbits != 8, d / M > 64, d outside what IVFFlatIndex and PQIndex both accept, nprobe."""
@@ -86,31 +82,15 @@ class IVFPQIndex(_IVFCells):
         self.pq.train(self._residuals(sample), niter=niter, rng=rng)
 
     # -- rows ------------------------------------------------------------------------------------------------------
-    def add(self, x):
-        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product and is coded (its residual to that centroid
-        with by_residual) at its arrival position (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFPQIndex.add: the index is not trained (call train() first)")
-        x = self._rows(x, "add: ")
-        n = x.shape[0]
-        if n == 0:
-            return
-        a, b = self.ntotal, self.ntotal + n
-        if b > self._assign.shape[0]:
-            self._reserve_assign(_grown(self._assign.shape[0], b))
-        self._cells_of(x, self._assign[a:b])
-        for s in range(0, n, 262144):
-            self.pq.add(self._residuals(x[s:s + 262144], self._assign[a + s:min(a + s + 262144, b)]))
-        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
-        self.ntotal = b
+    def _reserve(self, n_rows: int):
+        self._reserve_assign(n_rows)                   # (the codes grow inside `pq`)
 
-    def _finalize(self):
-        """The codes back into cell order (see the class note): a no-op unless rows were added since the last search."""
-        if self._nsorted == self.ntotal:
-            return
-        orig, perm = self._cell_order()
+    def _put(self, x: torch.Tensor, a: int, b: int):
+        for s in range(0, b - a, 262144):
+            self.pq.add(self._residuals(x[s:s + 262144], self._assign[a + s:min(a + s + 262144, b)]))
+
+    def _permute(self, perm: torch.Tensor):
         self.pq._codes = self.pq.rows_to_blocked(self.pq.blocked_to_rows(self.pq._codes, self.ntotal)[perm])
-        self._set_cell_order(orig, perm)
 
     def reset(self):
         """faiss reset(): drops the rows, keeps the training."""
@@ -130,16 +110,10 @@ class IVFPQIndex(_IVFCells):
         out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
         if n == 0:
             return out
-        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
-        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
-        picked = self.pq.rows_to_blocked(self.pq.blocked_to_rows(self.pq._codes, self.ntotal)[pos[i0:i0 + n]])
+        picked = self.pq.rows_to_blocked(self.pq.blocked_to_rows(self.pq._codes, self.ntotal)[self._positions(i0, n)])
         _lib.check(self.lib.lrx_pq_decode_rows(_lib.ptr(picked), 0, n, _lib.ptr(self.pq.centroids), self.d, self.M, _lib.ptr(out), self.d,
                                                _lib.current_stream()))
         return self.centroids[self._assign[i0:i0 + n]] + out if self.by_residual else out
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
 
     def set_contents(self, centroids, pq_centroids, codes, list_off, row_ids):
         """Replace the centroids ([nlist, d]), the codebooks ([M, 256, d / M]) and the rows: `codes` uint8 [n, M] already in cell order, list_off
@@ -153,24 +127,14 @@ class IVFPQIndex(_IVFCells):
         self.pq.set_contents(pq_centroids, codes)
         self._set_cells(lo, ri)
 
-    # -- search --------------------------------------------------------------------------------------------------
-    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
-        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the top k under the ADC score (see the class note) over the rows of each query's nprobe
-        best cells, score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
-        I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
-        q, nprobe = self._begin_search(q, k, nprobe, row_map)
-        if q.shape[0] == 0:
-            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
-        probe_scores, probes = self.quantizer.search(q, nprobe)
-        return ops.ivf_pq_ip_topk(q, self.pq._codes, self.pq.centroids, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
-                                  self.max_scan_rows(nprobe), self.id_base, row_map, ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+    # -- search: the top k under the ADC score of the class note ------------------------------------------------------------
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+        return ops.ivf_pq_ip_topk(q, self.pq._codes, self.pq.centroids, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k, max_scan_rows,
+                                  self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
 
     def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
         return ops.ivf_pq_ip_range_search(q, self.pq._codes, self.pq.centroids, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, radius,
                                           max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
-
-    def range_search(self, q, radius: float):
-        raise NotImplementedError("IVFPQIndex.range_search is not served (range search over the probed cells is a follow-up)")
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFPQ, see index_io.py) ---------------------------------
     def save(self, fname: str, prefix: bytes = b"", append: bool = False):
@@ -183,7 +147,7 @@ class IVFPQIndex(_IVFCells):
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, offset: int = 0, end: Optional[int] = None) -> "IVFPQIndex":
         from .index_io import read_ivf_pq
         st = read_ivf_pq(fname, offset, end)
-        idx = cls(st["d"], st["nlist"], st["M"], nprobe=min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE), by_residual=st["by_residual"], device=device,
+        idx = cls(st["d"], st["nlist"], st["M"], nprobe=cls._load_nprobe(st), by_residual=st["by_residual"], device=device,
                   id_base=id_base)
         if st["is_trained"]:
             idx.set_contents(np.array(st["centroids"], copy=True), np.array(st["pq_centroids"], copy=True), torch.from_numpy(np.array(st["codes"], copy=True)),

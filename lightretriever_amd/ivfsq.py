@@ -15,12 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import _check_range, _grown
-from .ivf import MAX_NPROBE, _IVFCells, check_ivf_args
-
-_CAPTURE_WS_ERROR = ("IVFSQIndex.search under graph capture: the search workspaces must exist before the capture starts -- run one eager "
-                     "search with the same number of queries, k and nprobe first")
-
+from .index import _check_range
+from .ivf import _IVFCells, check_ivf_args
 
 def check_ivfsq_args(d: int, nlist: int, qtype: str = "QT_fp16", nprobe: int = 1):
     """The constructor's refusals (no GPU is needed): any quantiser type but QT_fp16, and what IVFFlatIndex refuses."""
@@ -55,21 +51,13 @@ class IVFSQIndex(_IVFCells):
         check_ivfsq_args(d, nlist, qtype, nprobe)
         self._init_cells(d, nlist, nprobe, capacity, device, id_base)
         self.qtype, self.by_residual = qtype, bool(by_residual)
-        self.rebuild_chunk_rows = 262144
-        self._codes = torch.empty(max(capacity, 0), d, dtype=torch.float16, device=self.device)
+        self._init_store(capacity, torch.float16)
 
     def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
         """The coarse k-means (IVFFlatIndex.train's; see the class note).  niter=0 leaves the initial centroids (distinct sampled rows)."""
         self._train_cells(self._rows(x, "train: "), niter, seed)
 
     # -- rows ------------------------------------------------------------------------------------------------------
-    def _reserve(self, n_rows: int):
-        if n_rows > self._codes.shape[0]:
-            new = torch.empty(n_rows, self.d, dtype=torch.float16, device=self.device)
-            new[:self.ntotal].copy_(self._codes[:self.ntotal])
-            self._codes = new
-        self._reserve_assign(n_rows)
-
     def _encode_into(self, x: torch.Tensor, cells: torch.Tensor, codes: torch.Tensor, row0: int):
         """Code rows [row0, row0 + len(x)) of `codes` from the fp32 rows x and their cells (one kernel)."""
         n = x.shape[0]
@@ -79,40 +67,12 @@ class IVFSQIndex(_IVFCells):
         _lib.check(self.lib.lrx_ivf_sq_fp16_encode_rows(_lib.ptr(x), x.stride(0) if n > 1 else self.d, n, self.d, _lib.ptr(cent), _lib.ptr(cells), self.nlist,
                                                         _lib.ptr(codes), row0, _lib.current_stream()))
 
-    def add(self, x):
-        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product and is coded (its residual to that centroid
-        with by_residual) at its arrival position (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFSQIndex.add: the index is not trained (call train() first)")
-        x = self._rows(x, "add: ")
-        n = x.shape[0]
-        if n == 0:
-            return
-        if self.ntotal + n > self._codes.shape[0]:
-            self._reserve(_grown(self._codes.shape[0], self.ntotal + n))
-        a, b = self.ntotal, self.ntotal + n
-        self._cells_of(x, self._assign[a:b])
-        self._encode_into(x, self._assign[a:b], self._codes, a)
-        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
-        self.ntotal = b
-
-    def _finalize(self):
-        """The codes back into cell order (see the class note): a no-op unless rows were added since the last search."""
-        if self._nsorted == self.ntotal:
-            return
-        n = self.ntotal
-        orig, perm = self._cell_order()
-        new = torch.empty(max(self._codes.shape[0], n), self.d, dtype=torch.float16, device=self.device)
-        for s in range(0, n, self.rebuild_chunk_rows):
-            e = min(s + self.rebuild_chunk_rows, n)
-            torch.index_select(self._codes, 0, perm[s:e], out=new[s:e])
-        self._codes = new
-        self._set_cell_order(orig, perm)
+    def _put(self, x: torch.Tensor, a: int, b: int):
+        self._encode_into(x, self._assign[a:b], self._store, a)
 
     def stored_codes(self) -> torch.Tensor:
         """The codes as stored, cell by cell: fp16 [ntotal, d] (a view)."""
-        self._finalize()
-        return self._codes[:self.ntotal]
+        return self._stored()
 
     def reconstruct_n(self, i0: int, n: int) -> torch.Tensor:
         """ORIGINAL rows [i0, i0 + n) decoded to fp32 [n, d]: float(code), plus centroid[cell] (one fp32 add) with by_residual."""
@@ -120,14 +80,8 @@ class IVFSQIndex(_IVFCells):
         self._finalize()
         if n == 0:
             return torch.empty(0, self.d, dtype=torch.float32, device=self.device)
-        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
-        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
-        out = self._codes[pos[i0:i0 + n]].float()
+        out = self._store[self._positions(i0, n)].float()
         return out + self.centroids[self._assign[i0:i0 + n]] if self.by_residual else out
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
 
     def set_contents(self, centroids, codes, list_off, row_ids):
         """Replace the centroids ([nlist, d]) and the rows: `codes` fp16 [n, d] already in cell order, list_off int64 [nlist + 1] (ascending from
@@ -138,27 +92,17 @@ class IVFSQIndex(_IVFCells):
         lo, ri = self._check_cells(codes.shape[0], list_off, row_ids)
         self._set_centroids(torch.as_tensor(centroids))
         self._clear_rows()
-        self._codes = codes.to(self.device).contiguous().clone()
+        self._store = codes.to(self.device).contiguous().clone()
         self._set_cells(lo, ri)
 
-    # -- search --------------------------------------------------------------------------------------------------
-    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
-        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the exact top k under the score of the class note over the rows of each query's nprobe
-        best cells, score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
-        I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
-        q, nprobe = self._begin_search(q, k, nprobe, row_map)
-        if q.shape[0] == 0:
-            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
-        probe_scores, probes = self.quantizer.search(q, nprobe)
-        return ops.ivf_sq_fp16_ip_topk(q, self._codes[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
-                                       self.max_scan_rows(nprobe), self.id_base, row_map, ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+    # -- search: the exact top k under the score of the class note -----------------------------------------------------------
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+        return ops.ivf_sq_fp16_ip_topk(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k, max_scan_rows,
+                                       self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
 
     def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
-        return ops.ivf_sq_fp16_ip_range_search(q, self._codes[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, radius,
+        return ops.ivf_sq_fp16_ip_range_search(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, radius,
                                                max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
-
-    def range_search(self, q, radius: float):
-        raise NotImplementedError("IVFSQIndex.range_search is not served (range search over the probed cells is a follow-up)")
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFScalarQuantizer, see index_io.py) ----------------------
     def save(self, fname: str, prefix: bytes = b"", append: bool = False):
@@ -171,7 +115,7 @@ class IVFSQIndex(_IVFCells):
     def load(cls, fname: str, device: Optional[torch.device] = None, id_base: int = 0, offset: int = 0, end: Optional[int] = None) -> "IVFSQIndex":
         from .index_io import read_ivf_sq
         st = read_ivf_sq(fname, offset, end)
-        idx = cls(st["d"], st["nlist"], nprobe=min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE), by_residual=st["by_residual"], device=device,
+        idx = cls(st["d"], st["nlist"], nprobe=cls._load_nprobe(st), by_residual=st["by_residual"], device=device,
                   id_base=id_base)
         if st["is_trained"]:
             idx.set_contents(np.array(st["centroids"], copy=True), torch.from_numpy(np.array(st["codes"], copy=True)), st["list_off"], st["row_ids"])

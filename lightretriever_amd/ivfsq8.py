@@ -15,12 +15,10 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import _check_range, _grown
-from .ivf import MAX_NPROBE, _IVFCells, check_ivf_args
+from .index import _check_range
+from .ivf import _IVFCells, check_ivf_args
 
 QTYPES = {"QT_8bit": 0, "QT_8bit_uniform": 2}     # faiss ScalarQuantizer::QuantizerType
-_CAPTURE_WS_ERROR = ("IVFSQ8Index.search under graph capture: the search workspaces must exist before the capture starts -- run one eager "
-                     "search with the same number of queries, k and nprobe first")
 
 
 def check_ivfsq8_args(d: int, nlist: int, qtype: str = "QT_8bit", nprobe: int = 1):
@@ -58,9 +56,8 @@ class IVFSQ8Index(_IVFCells):
         self._init_cells(d, nlist, nprobe, capacity, device, id_base)
         self.qtype, self._qt, self.by_residual = qtype, QTYPES[qtype], bool(by_residual)
         self.uniform = self._qt == 2
-        self.rebuild_chunk_rows = 262144
         self.trained = torch.zeros(2 if self.uniform else 2 * d, dtype=torch.float32, device=self.device)
-        self._codes = torch.empty(max(capacity, 0), d, dtype=torch.uint8, device=self.device)
+        self._init_store(capacity, torch.uint8)
 
     def train(self, x, niter: Optional[int] = None, seed: Optional[int] = None):
         """The coarse k-means (IVFFlatIndex.train's), then the range of the training rows' residuals (see the class note)."""
@@ -84,13 +81,6 @@ class IVFSQ8Index(_IVFCells):
         self.trained = torch.cat([mn, mx - mn]).contiguous()
 
     # -- rows ------------------------------------------------------------------------------------------------------
-    def _reserve(self, n_rows: int):
-        if n_rows > self._codes.shape[0]:
-            new = torch.empty(n_rows, self.d, dtype=torch.uint8, device=self.device)
-            new[:self.ntotal].copy_(self._codes[:self.ntotal])
-            self._codes = new
-        self._reserve_assign(n_rows)
-
     def _encode_into(self, x: torch.Tensor, cells: torch.Tensor, codes: torch.Tensor, row0: int):
         """Code rows [row0, row0 + len(x)) of `codes` from the fp32 rows x and their cells (one kernel)."""
         n = x.shape[0]
@@ -100,40 +90,12 @@ class IVFSQ8Index(_IVFCells):
         _lib.check(self.lib.lrx_ivf_sq8_encode_rows(_lib.ptr(x), x.stride(0) if n > 1 else self.d, n, self.d, _lib.ptr(cent), _lib.ptr(cells), self.nlist,
                                                     _lib.ptr(self.trained), self._qt, _lib.ptr(codes), row0, _lib.current_stream()))
 
-    def add(self, x):
-        """faiss add(x f32[n, d]): each row goes to the cell of its best centroid by inner product and is coded (its residual to that centroid
-        with by_residual) at its arrival position (raises before train(), as faiss does)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFSQ8Index.add: the index is not trained (call train() first)")
-        x = self._rows(x, "add: ")
-        n = x.shape[0]
-        if n == 0:
-            return
-        if self.ntotal + n > self._codes.shape[0]:
-            self._reserve(_grown(self._codes.shape[0], self.ntotal + n))
-        a, b = self.ntotal, self.ntotal + n
-        self._cells_of(x, self._assign[a:b])
-        self._encode_into(x, self._assign[a:b], self._codes, a)
-        self.list_sizes = self.list_sizes + torch.bincount(self._assign[a:b], minlength=self.nlist).cpu().numpy()
-        self.ntotal = b
-
-    def _finalize(self):
-        """The codes back into cell order (see the class note): a no-op unless rows were added since the last search."""
-        if self._nsorted == self.ntotal:
-            return
-        n = self.ntotal
-        orig, perm = self._cell_order()
-        new = torch.empty(max(self._codes.shape[0], n), self.d, dtype=torch.uint8, device=self.device)
-        for s in range(0, n, self.rebuild_chunk_rows):
-            e = min(s + self.rebuild_chunk_rows, n)
-            torch.index_select(self._codes, 0, perm[s:e], out=new[s:e])
-        self._codes = new
-        self._set_cell_order(orig, perm)
+    def _put(self, x: torch.Tensor, a: int, b: int):
+        self._encode_into(x, self._assign[a:b], self._store, a)
 
     def stored_codes(self) -> torch.Tensor:
         """The codes as stored, cell by cell: uint8 [ntotal, d] (a view)."""
-        self._finalize()
-        return self._codes[:self.ntotal]
+        return self._stored()
 
     def decode_stored(self, p0: int = 0, n: Optional[int] = None, residual: bool = False) -> torch.Tensor:
         """Stored POSITIONS [p0, p0 + n) decoded to fp32 [n, d] (lrx_ivf_sq8_decode_rows): the rows themselves, or with residual=True what the
@@ -147,7 +109,7 @@ class IVFSQ8Index(_IVFCells):
         add = self.by_residual and not residual
         cells = self._assign[self.row_ids[p0:p0 + n]].contiguous() if add else None
         cent = self.centroids.contiguous() if add else None
-        _lib.check(self.lib.lrx_ivf_sq8_decode_rows(_lib.ptr(self._codes), p0, n, self.d, _lib.ptr(self.trained), self._qt, _lib.ptr(cent), _lib.ptr(cells),
+        _lib.check(self.lib.lrx_ivf_sq8_decode_rows(_lib.ptr(self._store), p0, n, self.d, _lib.ptr(self.trained), self._qt, _lib.ptr(cent), _lib.ptr(cells),
                                                     self.nlist, _lib.ptr(out), self.d, _lib.current_stream()))
         return out
 
@@ -161,19 +123,13 @@ class IVFSQ8Index(_IVFCells):
         if out is not None:                            # every row: decode in stored order, scatter to the original rows
             out[self.row_ids] = self.decode_stored()
             return out
-        pos = torch.empty(self.ntotal, dtype=torch.int64, device=self.device)
-        pos[self.row_ids] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
-        codes = self._codes[pos[i0:i0 + n]].contiguous()
+        codes = self._store[self._positions(i0, n)].contiguous()
         cells = self._assign[i0:i0 + n].contiguous() if self.by_residual else None
         cent = self.centroids.contiguous() if self.by_residual else None
         out = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.lrx_ivf_sq8_decode_rows(_lib.ptr(codes), 0, n, self.d, _lib.ptr(self.trained), self._qt, _lib.ptr(cent), _lib.ptr(cells), self.nlist,
                                                     _lib.ptr(out), self.d, _lib.current_stream()))
         return out
-
-    @property
-    def vectors(self) -> torch.Tensor:
-        return self.reconstruct_n(0, self.ntotal)
 
     def set_contents(self, centroids, trained, codes, list_off, row_ids):
         """Replace the centroids ([nlist, d]), the range (`trained`: vmin ++ vdiff) and the rows: `codes` uint8 [n, d] already in cell order,
@@ -189,27 +145,17 @@ class IVFSQ8Index(_IVFCells):
         self._set_centroids(torch.as_tensor(centroids))
         self.trained = t.to(self.device).contiguous().clone()
         self._clear_rows()
-        self._codes = codes.to(self.device).contiguous().clone()
+        self._store = codes.to(self.device).contiguous().clone()
         self._set_cells(lo, ri)
 
-    # -- search --------------------------------------------------------------------------------------------------
-    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
-        """-> (D f32[Q,k], I i64[Q,k]) device tensors: the exact top k under the score of the class note over the rows of each query's nprobe
-        best cells, score descending, ties to the lower original row, (-FLT_MAX, -1) padding where those cells hold fewer than k rows.
-        I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).  nprobe: this call's (default: the index's)."""
-        q, nprobe = self._begin_search(q, k, nprobe, row_map)
-        if q.shape[0] == 0:
-            return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
-        probe_scores, probes = self.quantizer.search(q, nprobe)
-        return ops.ivf_sq8_ip_topk(q, self._codes[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
-                                   self.max_scan_rows(nprobe), self.id_base, row_map, ws_slots=vars(self), capture_error=_CAPTURE_WS_ERROR)
+    # -- search: the exact top k under the score of the class note -----------------------------------------------------------
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+        return ops.ivf_sq8_ip_topk(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
+                                   max_scan_rows, self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
 
     def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
-        return ops.ivf_sq8_ip_range_search(q, self._codes[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores,
+        return ops.ivf_sq8_ip_range_search(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores,
                                            self.by_residual, radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
-
-    def range_search(self, q, radius: float):
-        raise NotImplementedError("IVFSQ8Index.range_search is not served (range search over the probed cells is a follow-up)")
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFScalarQuantizer, see index_io.py) ----------------------
     def save(self, fname: str, prefix: bytes = b"", append: bool = False):
@@ -223,7 +169,7 @@ class IVFSQ8Index(_IVFCells):
         from .index_io import read_ivf_sq8
         st = read_ivf_sq8(fname, offset, end)
         qtype = {v: k for k, v in QTYPES.items()}[st["qtype"]]
-        idx = cls(st["d"], st["nlist"], qtype, nprobe=min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE), by_residual=st["by_residual"], device=device,
+        idx = cls(st["d"], st["nlist"], qtype, nprobe=cls._load_nprobe(st), by_residual=st["by_residual"], device=device,
                   id_base=id_base)
         if st["is_trained"]:
             idx.set_contents(np.array(st["centroids"], copy=True), np.array(st["trained"], copy=True), torch.from_numpy(np.array(st["codes"], copy=True)),

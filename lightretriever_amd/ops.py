@@ -322,26 +322,66 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
 
 
 # -- inverted file (IndexIVFFlat) ---------------------------------------------------------------------------------------------
-def _ivf_flat_args(name: str, q, X, list_off, probes):
-    """The checks ivf_flat_ip_topk and ivf_flat_ip_range_search share -> (Q, nprobe, n, d, nlist)."""
+# Every family below checks its arguments ONCE, in its _ivf_*_args: -> (Q, dims, head), the leading arguments of its two workspace functions
+# (up to nprobe) and of its two library entries (up to ld_probe / by_residual).  _ivf_topk and _ivf_range add the rest, the same for all four:
+# lrx_<fam>_workspace_bytes(*dims, k, max_scan_rows) and lrx_<fam>_search(*head, max_scan_rows, k, id_base, D, I, row_map, ws, bytes, stream),
+# or lrx_<fam>_range_workspace_bytes(*dims, max_scan_rows) and lrx_<fam>_range_search(*head, max_scan_rows, radius, id_base, lims, D, I,
+# capacity, row_map, ws, bytes, stream).
+def _ivf_probes(name: str, q, probes):
     Q, nprobe = probes.shape
-    n, d = X.shape
     if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
         raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
-    return Q, nprobe, n, d, list_off.numel() - 1
+    return Q, nprobe, probes.stride(0) if Q > 1 else nprobe
 
 
-def _ivf_range(name: str, q: torch.Tensor, Q: int, ws_slots: Optional[dict], ws_bytes, call):
+def _ivf_probe_args(name: str, q, Q, probes, probe_scores, nprobe, ld, by_residual):
+    """The query and probe arguments of the three entries over residual codes (the check of probe_scores included)."""
+    ok = probe_scores is not None and probe_scores.dtype == torch.float32 and probe_scores.shape == probes.shape and \
+        not (nprobe and probe_scores.stride(1) != 1) and not (Q > 1 and probe_scores.stride(0) != ld)
+    if by_residual and not ok:
+        raise ValueError(f"{name}: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
+    return (_lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)))
+
+
+def _ivf_topk(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, k: int, id_base: int, row_map, ws_slots: Optional[dict],
+              capture_error: Optional[str]):
+    """What the four IVF searches share: the outputs, the workspace (ws_slots: a dict that keeps it between calls, key "_ws") and the call."""
+    from .index import _workspace
+    lib = _lib.lib()
+    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
+    if Q == 0:
+        return D, I
+    need = int(getattr(lib, f"lrx_{fam}_workspace_bytes")(*dims, k, int(max_scan_rows)))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
+    _lib.check(getattr(lib, f"lrx_{fam}_search")(*head, int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws),
+                                                 ws.numel(), _s()))
+    return D, I
+
+
+def _ivf_range(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, radius: float, id_base: int, row_map, ws_slots: Optional[dict]):
     """What the four IVF range searches share: the protocol of index._range_call over ONE library call for all Q queries (the library chunks
     them itself and carries lims on the device) -- outputs sized by a first guess, one host read of lims[Q], one retry when the guess was
-    short.  ws_slots: a dict that keeps the workspace between calls (key "_ws"); ws_bytes() -> the workspace size; call(ws, lims, D, I, capacity) -> the library's return code."""
+    short.  ws_slots: as _ivf_topk's."""
     from .index import _range_call, _range_empty, _workspace
+    lib = _lib.lib()
     if torch.cuda.is_current_stream_capturing():
-        raise _lib.LrxError(f"{name} under graph capture: the result length is read back to the host")
+        raise _lib.LrxError(f"{fam}_range_search under graph capture: the result length is read back to the host")
     if Q == 0:
         return _range_empty(q.device, 0)
-    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", int(ws_bytes()), q.device)
-    return _range_call(q.device, Q, Q, lambda s, n, lims, D, I, cap: _lib.check(call(ws, lims, D, I, cap)))
+    need = int(getattr(lib, f"lrx_{fam}_range_workspace_bytes")(*dims, int(max_scan_rows)))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device)
+    fn = getattr(lib, f"lrx_{fam}_range_search")
+    return _range_call(q.device, Q, Q, lambda s, n, lims, D, I, cap: _lib.check(fn(
+        *head, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s())))
+
+
+def _ivf_flat_args(name: str, q, X, list_off, row_ids, probes):
+    Q, nprobe, ld = _ivf_probes(name, q, probes)
+    n, d = X.shape
+    nlist = list_off.numel() - 1
+    return Q, (n, nlist, d, Q, nprobe), (_lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                         _lib.ptr(q), Q, _lib.ptr(probes), nprobe, ld)
 
 
 def ivf_flat_ip_range_search(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
@@ -349,13 +389,8 @@ def ivf_flat_ip_range_search(q: torch.Tensor, X: torch.Tensor, list_off: torch.T
     """lrx_ivf_flat_ip_range_search -> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]): every row of the cells probes[i] names whose exact
     score is > radius, in SEGMENT order (cells in the order of the probe row, rows by stored position), not sorted.  The arguments are
     ivf_flat_ip_topk's with radius for k.  Reads lims[Q] back to the host: refused under graph capture."""
-    lib = _lib.lib()
-    Q, nprobe, n, d, nlist = _ivf_flat_args("ivf_flat_ip_range_search", q, X, list_off, probes)
-    return _ivf_range("ivf_flat_ip_range_search", q, Q, ws_slots, lambda: lib.lrx_ivf_flat_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
-                      lambda ws, lims, D, I, cap: lib.lrx_ivf_flat_ip_range_search(
-                          _lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q,
-                          _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims),
-                          _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+    Q, dims, head = _ivf_flat_args("ivf_flat_ip_range_search", q, X, list_off, row_ids, probes)
+    return _ivf_range("ivf_flat_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
 
 
 def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor, k: int,
@@ -365,43 +400,22 @@ def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, r
     contiguous; X fp32 [n, d] rows stored cell by cell; list_off int64 [nlist + 1]; row_ids int64 [n] (original row of a position) or None;
     probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted in lrx_device_error_count); max_scan_rows: the
     caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    from .index import _workspace
-    lib = _lib.lib()
-    Q, nprobe, n, d, nlist = _ivf_flat_args("ivf_flat_ip_topk", q, X, list_off, probes)
-    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
-    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
-    if Q == 0:
-        return D, I
-    need = int(lib.lrx_ivf_flat_ip_workspace_bytes(n, nlist, d, Q, nprobe, k, int(max_scan_rows)))
-    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    _lib.check(lib.lrx_ivf_flat_ip_search(_lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
-                                          _lib.ptr(q), Q, _lib.ptr(probes), nprobe, probes.stride(0) if Q > 1 else nprobe, int(max_scan_rows), k,
-                                          int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
-    return D, I
-
-
-def _ivf_probe_scores_ok(probes, probe_scores, ld) -> bool:
-    Q, nprobe = probes.shape
-    return probe_scores is not None and probe_scores.dtype == torch.float32 and probe_scores.shape == probes.shape and \
-        not (nprobe and probe_scores.stride(1) != 1) and not (Q > 1 and probe_scores.stride(0) != ld)
+    Q, dims, head = _ivf_flat_args("ivf_flat_ip_topk", q, X, list_off, row_ids, probes)
+    return _ivf_topk("ivf_flat_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
 
 
 def _ivf_pq_args(name: str, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual):
-    """The checks ivf_pq_ip_topk and ivf_pq_ip_range_search share -> (Q, nprobe, n, d, M, nlist, ld_probe)."""
-    Q, nprobe = probes.shape
+    Q, nprobe, ld = _ivf_probes(name, q, probes)
     d = q.shape[1]
     M = pq_centroids.shape[0]
     n = codes.numel() // (-(-M // 16) * 16) if row_ids is None else row_ids.numel()
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
     if codes.dtype != torch.uint8 or codes.dim() != 1 or not codes.is_contiguous() or codes.numel() < -(-n // 128) * 128 * (-(-M // 16) * 16):
         raise ValueError(f"{name}: codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)")
     if pq_centroids.dtype != torch.float32 or not pq_centroids.is_contiguous() or tuple(pq_centroids.shape) != (M, 256, d // max(M, 1)) or d % M:
         raise ValueError(f"{name}: pq_centroids must be fp32 [M, 256, d / M] contiguous with d % M == 0")
-    ld = probes.stride(0) if Q > 1 else nprobe
-    if by_residual and not _ivf_probe_scores_ok(probes, probe_scores, ld):
-        raise ValueError(f"{name}: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
-    return Q, nprobe, n, d, M, list_off.numel() - 1, ld
+    nlist = list_off.numel() - 1
+    return Q, (n, nlist, d, M, Q, nprobe), (_lib.ptr(codes) if n else None, n, _lib.ptr(pq_centroids), d, M, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                            *_ivf_probe_args(name, q, Q, probes, probe_scores, nprobe, ld, by_residual))
 
 
 def ivf_pq_ip_range_search(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -409,13 +423,8 @@ def ivf_pq_ip_range_search(q: torch.Tensor, codes: torch.Tensor, pq_centroids: t
                            id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
     """lrx_ivf_pq_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose ADC score -- the value ivf_pq_ip_topk reports -- is
     > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_pq_ip_topk's with radius for k."""
-    lib = _lib.lib()
-    Q, nprobe, n, d, M, nlist, ld = _ivf_pq_args("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_pq_ip_range_search", q, Q, ws_slots, lambda: lib.lrx_ivf_pq_ip_range_workspace_bytes(n, nlist, d, M, Q, nprobe, int(max_scan_rows)),
-                      lambda ws, lims, D, I, cap: lib.lrx_ivf_pq_ip_range_search(
-                          _lib.ptr(codes) if n else None, n, _lib.ptr(pq_centroids), d, M, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q,
-                          _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows),
-                          float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+    Q, dims, head = _ivf_pq_args("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_pq_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
 
 
 def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -427,35 +436,21 @@ def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Ten
     [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not by_residual): a scanned row's score
     starts at its cell's probe score when by_residual, at 0 otherwise; max_scan_rows: the caller's bound on the rows one query scans.
     ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    from .index import _workspace
-    lib = _lib.lib()
-    Q, nprobe, n, d, M, nlist, ld = _ivf_pq_args("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
-    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
-    if Q == 0:
-        return D, I
-    need = int(lib.lrx_ivf_pq_ip_workspace_bytes(n, nlist, d, M, Q, nprobe, k, int(max_scan_rows)))
-    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    _lib.check(lib.lrx_ivf_pq_ip_search(_lib.ptr(codes) if n else None, n, _lib.ptr(pq_centroids), d, M, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
-                                        _lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
-                                        int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
-    return D, I
+    Q, dims, head = _ivf_pq_args("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_pq_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
 
 
-def _ivf_codes_args(name: str, dtype, dtype_name: str, q, codes, list_off, row_ids, probes, probe_scores, by_residual):
-    """The checks the searches over row-major codes (fp16, 8-bit) share -> (Q, nprobe, n, d, nlist, ld_probe)."""
-    Q, nprobe = probes.shape
+def _ivf_codes_args(name: str, dtype, dtype_name: str, q, codes, store, list_off, row_ids, probes, probe_scores, by_residual):
+    """The searches over row-major codes (fp16, 8-bit); `store`: what the entry takes between d and list_off."""
     if codes.dtype != dtype or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
         raise ValueError(f"{name}: codes must be {dtype_name} [n, d] contiguous with q's d")
     n, d = codes.shape
-    if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
-        raise ValueError(f"{name}: probes must be int64 [Q, nprobe] with unit inner stride")
+    Q, nprobe, ld = _ivf_probes(name, q, probes)
     if row_ids is not None and (row_ids.dtype != torch.int64 or not row_ids.is_contiguous() or row_ids.numel() < n):
         raise ValueError(f"{name}: row_ids must be int64 [>= n] contiguous")
-    ld = probes.stride(0) if Q > 1 else nprobe
-    if by_residual and not _ivf_probe_scores_ok(probes, probe_scores, ld):
-        raise ValueError(f"{name}: by_residual needs probe_scores fp32 [Q, nprobe] with the row stride of probes")
-    return Q, nprobe, n, d, list_off.numel() - 1, ld
+    nlist = list_off.numel() - 1
+    return Q, (n, nlist, d, Q, nprobe), (_lib.ptr(codes) if n else None, n, d, *store, _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
+                                         *_ivf_probe_args(name, q, Q, probes, probe_scores, nprobe, ld, by_residual))
 
 
 def ivf_sq_fp16_ip_range_search(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
@@ -464,14 +459,8 @@ def ivf_sq_fp16_ip_range_search(q: torch.Tensor, codes: torch.Tensor, list_off: 
     """lrx_ivf_sq_fp16_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the fp16 store -- the value
     ivf_sq_fp16_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq_fp16_ip_topk's with
     radius for k."""
-    lib = _lib.lib()
-    name = "ivf_sq_fp16_ip_range_search"
-    Q, nprobe, n, d, nlist, ld = _ivf_codes_args(name, torch.float16, "fp16", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range(name, q, Q, ws_slots, lambda: lib.lrx_ivf_sq_fp16_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
-                      lambda ws, lims, D, I, cap: lib.lrx_ivf_sq_fp16_ip_range_search(
-                          _lib.ptr(codes) if n else None, n, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q, _lib.ptr(probes),
-                          _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows), float(radius),
-                          int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
+    Q, dims, head = _ivf_codes_args("ivf_sq_fp16_ip_range_search", torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
 
 
 def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
@@ -483,29 +472,17 @@ def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Te
     (rows may be strided; None when not by_residual): a scanned row's score is its cell's probe score plus q . float(code) when by_residual,
     the product alone otherwise; max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace
     between calls (key "_ws")."""
-    from .index import _workspace
-    lib = _lib.lib()
-    Q, nprobe, n, d, nlist, ld = _ivf_codes_args("ivf_sq_fp16_ip_topk", torch.float16, "fp16", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
-    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
-    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
-    if Q == 0:
-        return D, I
-    need = int(lib.lrx_ivf_sq_fp16_ip_workspace_bytes(n, nlist, d, Q, nprobe, k, int(max_scan_rows)))
-    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    _lib.check(lib.lrx_ivf_sq_fp16_ip_search(_lib.ptr(codes) if n else None, n, d, _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q), Q,
-                                             _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)),
-                                             int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s()))
-    return D, I
+    Q, dims, head = _ivf_codes_args("ivf_sq_fp16_ip_topk", torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
 
 
 def _ivf_sq8_args(name: str, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual):
-    """The checks ivf_sq8_ip_topk and ivf_sq8_ip_range_search share -> (Q, nprobe, n, d, nlist, ld_probe)."""
     if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_contiguous() or codes.shape[1] != q.shape[1]:
         raise ValueError(f"{name}: codes must be uint8 [n, d] contiguous with q's d")
     d = codes.shape[1]
     if qtype not in (0, 2) or trained.dtype != torch.float32 or not trained.is_contiguous() or trained.numel() != (2 * d if qtype == 0 else 2):
         raise ValueError(f"{name}: qtype {qtype} (0: QT_8bit, 2: QT_8bit_uniform) needs trained fp32 [2 d] or [2] contiguous")
-    return _ivf_codes_args(name, torch.uint8, "uint8", q, codes, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_codes_args(name, torch.uint8, "uint8", q, codes, (_lib.ptr(trained), int(qtype)), list_off, row_ids, probes, probe_scores, by_residual)
 
 
 def ivf_sq8_ip_range_search(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor,
@@ -514,15 +491,8 @@ def ivf_sq8_ip_range_search(q: torch.Tensor, codes: torch.Tensor, trained: torch
     """lrx_ivf_sq8_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the 8-bit store -- the value
     ivf_sq8_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq8_ip_topk's with radius
     for k."""
-    lib = _lib.lib()
-    name = "ivf_sq8_ip_range_search"
-    Q, nprobe, n, d, nlist, ld = _ivf_sq8_args(name, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range(name, q, Q, ws_slots, lambda: lib.lrx_ivf_sq8_ip_range_workspace_bytes(n, nlist, d, Q, nprobe, int(max_scan_rows)),
-                      lambda ws, lims, D, I, cap: lib.lrx_ivf_sq8_ip_range_search(
-                          _lib.ptr(codes) if n else None, n, d, _lib.ptr(trained), int(qtype), _lib.ptr(list_off), _lib.ptr(row_ids), nlist, _lib.ptr(q),
-                          Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)), int(max_scan_rows),
-                          float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(),
-                          _s()))
+    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_range_search", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
 
 
 def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -534,17 +504,5 @@ def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor,
     position) or None; probes int64 [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not
     by_residual): a scanned row's score is its cell's probe score plus q . decoded row when by_residual, the product alone otherwise;
     max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    from .index import _workspace
-    lib = _lib.lib()
-    Q, nprobe, n, d, nlist, ld = _ivf_sq8_args("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
-    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
-    if Q == 0:
-        return D, I
-    need = int(lib.lrx_ivf_sq8_ip_workspace_bytes(n, nlist, d, Q, nprobe, k, int(max_scan_rows)))
-    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    _lib.check(lib.lrx_ivf_sq8_ip_search(_lib.ptr(codes) if n else None, n, d, _lib.ptr(trained), int(qtype), _lib.ptr(list_off), _lib.ptr(row_ids), nlist,
-                                         _lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld,
-                                         int(bool(by_residual)), int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws),
-                                         ws.numel(), _s()))
-    return D, I
+    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)

@@ -100,9 +100,9 @@ if __name__ == "__main__":
                 topk_ms = timed(lambda: idx.search(q, 100, nprobe=nprobe))
                 coarse_ms = timed(lambda: idx.quantizer.search(q, nprobe))
                 if name == "ivfflat":
-                    topk_cells = lambda: ops.ivf_flat_ip_topk(q, idx._x[:idx.ntotal], idx.list_off, idx.row_ids, probes, 100, scan, 0, None, ws_slots=vars(idx))
+                    topk_cells = lambda: ops.ivf_flat_ip_topk(q, idx.stored_rows(), idx.list_off, idx.row_ids, probes, 100, scan, 0, None, ws_slots=vars(idx))
                 else:
-                    topk_cells = lambda: ops.ivf_sq_fp16_ip_topk(q, idx._codes[:idx.ntotal], idx.list_off, idx.row_ids, probes, coarse, True, 100, scan, 0, None,
+                    topk_cells = lambda: ops.ivf_sq_fp16_ip_topk(q, idx.stored_codes(), idx.list_off, idx.row_ids, probes, coarse, True, 100, scan, 0, None,
                                                                  ws_slots=vars(idx))
                 topk_cells_ms = timed(topk_cells)
                 c = {"Q": Q, "nprobe": nprobe, "max_scan_rows": scan, "scanned_per_query": round(scanned / Q, 1), "topk_ms": round(topk_ms, 4),
