@@ -212,7 +212,7 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
  * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search /
  * lrx_ivf_sq_fp16_ip_search / lrx_ivf_sq_fp16_encode_rows / lrx_ivf_sq8_ip_search / lrx_ivf_sq8_encode_rows / lrx_ivf_sq8_decode_rows count (probe entries >= nlist, queries over max_scan_rows, stored rows outside the
- * shard, rows encoded for a cell outside [0, nlist)); -1 if the read
+ * shard, rows encoded for a cell outside [0, nlist)), plus the rows outside [0, n_bits) that lrx_selector_set_rows skipped; -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -908,6 +908,78 @@ int lrx_ivf_sq8_ip_range_search(const void* codes, int64_t n_rows, int32_t dim, 
                                 const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius,
                                 int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map,
                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* (added under ABI 9, additively) ROW SELECTOR for the four inverted-file entries -- faiss SearchParameters(sel = IDSelectorBatch /
+ * IDSelectorBitmap / IDSelectorRange / IDSelectorNot) (RowSelector): search a subset of the rows.
+ *   selector    a bitmap over the ORIGINAL rows 0 .. n_bits - 1 of an index: the number a search reports before id_base / row_map -- not a
+ *               stored position, not a mapped id.  Bit r is (bits[r >> 5] >> (r & 31)) & 1; bits: uint32 [ceil(n_bits / 32)] on the device.
+ *               The bits at or beyond n_bits in the last word are written as 0 by every lrx_selector_* entry; no search reads them.
+ *               0 <= n_bits < 2^32; n_bits == 0 launches nothing.  One kernel each on `stream`, capturable.
+ *   lrx_selector_fill        every bit below n_bits = (value != 0).
+ *   lrx_selector_from_mask   bit r = (mask[r] != 0), mask: n_bits bytes on the device; one thread packs the 32 bytes of a word (plain store).
+ *   lrx_selector_set_rows    bit rows[i] is SET for i < n (int64, device; duplicates are fine; bits already set stay: fill first for a fresh
+ *               selector).  A row outside [0, n_bits) is never turned into an address: it is skipped and counted in lrx_device_error_count.
+ *   lrx_selector_invert      out = NOT in below n_bits, 0 at and beyond it; in == out is allowed.
+ * Each lrx_ivf_*_ip_search_sel / lrx_ivf_*_ip_range_search_sel takes the argument list of its plain sibling with
+ * (const uint32_t* sel_bits, int64_t sel_rows) inserted before `workspace`, and the sibling's *_workspace_bytes.
+ *   sel_bits == NULL   the plain entry: the same kernels, the same bits (sel_rows is ignored).
+ *   sel_bits != NULL   sel_rows must equal n_rows (LRX_ERR_INVALID otherwise, with the other argument checks and before the workspace
+ *               check).  The result is the sibling's over the SELECTED rows of the probed cells: top k -- score descending, ties to the lower
+ *               original row, (-FLT_MAX, -1) where fewer than k selected rows were scanned; range -- every selected row with a score >
+ *               radius, in segment order.  Every scanned (query, row) pair is scored independently of the others, so a filtered result is the
+ *               unfiltered full result restricted to the selected rows, bit for bit.  One selector per call, shared by its queries.
+ *   unchanged   the probe-list rules (entries < 0, >= nlist, repeats), probe_scores / by_residual, the segment layout and max_scan_rows, which
+ *               go by the UNFILTERED cell sizes: a query whose cells hold more than max_scan_rows is padding and counted whatever the
+ *               selector says.  id_base / row_map apply after the filter.  A stored position whose original row is outside [0, n_rows) has no
+ *               bit: it is dropped and counted as without a selector.
+ * The chain is the sibling's with the scan kernel's selector instantiation: a deselected (query, row) pair becomes the null word 0 -- the word
+ * the selection and the range kernels already drop -- before its score is computed; the cell-major scans test a staged group's rows once per
+ * work item and do not read a group with no selected row from memory at all. */
+int lrx_selector_fill(uint32_t* bits, int64_t n_bits, int32_t value, void* stream);
+int lrx_selector_from_mask(const uint8_t* mask, int64_t n_bits, uint32_t* bits, void* stream);
+int lrx_selector_set_rows(const int64_t* rows, int64_t n, int64_t n_bits, uint32_t* bits, void* stream);
+int lrx_selector_invert(const uint32_t* in, uint32_t* out, int64_t n_bits, void* stream);
+int lrx_ivf_flat_ip_search_sel(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                               const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows,
+                               int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits,
+                               int64_t sel_rows, void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_flat_ip_range_search_sel(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                     int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe,
+                                     int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids,
+                                     int64_t capacity, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+int lrx_ivf_pq_ip_search_sel(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                             const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                             const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                             int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_pq_ip_range_search_sel(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                                   const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                   const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                   float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                   const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+int lrx_ivf_sq_fp16_ip_search_sel(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                  const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe,
+                                  int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores,
+                                  int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+int lrx_ivf_sq_fp16_ip_range_search_sel(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                        const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe,
+                                        int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims,
+                                        float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map, const uint32_t* sel_bits,
+                                        int64_t sel_rows, void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_sq8_ip_search_sel(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                              const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                              const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                              int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int lrx_ivf_sq8_ip_range_search_sel(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                    const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                    const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                    float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                    const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace, size_t workspace_bytes,
+                                    void* stream);
 
 /* (added in ABI 8, additively) INVERTED FILE over PRODUCT-QUANTISED codes: the top k under the ADC score over the rows of the cells a query
  * probes -- the scan of faiss IndexIVFPQ(quantizer, d, nlist, M, 8, METRIC_INNER_PRODUCT) (IVFPQIndex).  The caller owns the

@@ -6,6 +6,7 @@ from .sparse_rows import SparseRows  # noqa: F401
 from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
 from .refine import RefineFlatIndex  # noqa: F401
 from .ivf import IVFFlatIndex  # noqa: F401
+from .selector import RowSelector  # noqa: F401
 from .ivfpq import IVFPQIndex  # noqa: F401
 from .ivfsq import IVFSQIndex  # noqa: F401
 from .ivfsq8 import IVFSQ8Index  # noqa: F401

@@ -178,7 +178,16 @@ SIGNATURES = {
     "lrx_merge_topk": (_I32, [_P, _P, _I32, _I32, _I32, _P, _P, _P]),
     "lrx_pack_topk": (_I32, [_P, _P, _P, _I64, _I64, _P, _P]),
     "lrx_merge_topk_packed": (_I32, [_P, _I32, _I32, _I32, _P, _P, _P]),
+    "lrx_selector_fill": (_I32, [_P, _I64, _I32, _P]),
+    "lrx_selector_from_mask": (_I32, [_P, _I64, _P, _P]),
+    "lrx_selector_set_rows": (_I32, [_P, _I64, _I64, _P, _P]),
+    "lrx_selector_invert": (_I32, [_P, _P, _I64, _P]),
 }
+# the searches under a row selector: the plain entry's arguments with (sel_bits, sel_rows) in front of (workspace, workspace_bytes, stream)
+for _fam in ("flat", "pq", "sq_fp16", "sq8"):
+    for _kind in ("search", "range_search"):
+        _res, _args = SIGNATURES[f"lrx_ivf_{_fam}_ip_{_kind}"]
+        SIGNATURES[f"lrx_ivf_{_fam}_ip_{_kind}_sel"] = (_res, _args[:-3] + [_P, _I64] + _args[-3:])
 
 _lib = None
 

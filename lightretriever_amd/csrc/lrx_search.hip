@@ -12,6 +12,7 @@
 //     lrx_search_rerank.h   K. rerank: exact rescoring of a caller's candidate rows (refine_rescore) + sorted top-k (with its host driver)
 //     lrx_search_ivf.h      L. inverted file (IndexIVFFlat): probe plan, cell-major exact scan of the probed cells, per-query top-k (with its host driver)
 //     lrx_search_ivfpq.h    M. inverted file over PQ codes (IndexIVFPQ): dense probe plan, query-major ADC scan of the probed cells (with its host driver)
+//     lrx_search_selector.h P. row selector (IDSelector*): the bitmap over original rows the four inverted-file scans test, and its four kernels
 // Map of the unit:
 //
 //  A. Score kernels (what a search streams the shard through)
@@ -1341,6 +1342,7 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
 #include "lrx_search_sq8.h"      // 8-bit scalar-quantised index: min/max, encode, i8-MFMA filter scan, band rescoring from the codes, decode
 #include "lrx_search_impact.h"   // impact (sparse) index: term-at-a-time scan of the posting lists into LDS row windows (-> k_topk_select), hit filter
 #include "lrx_search_rerank.h"    // rerank (faiss IndexRefineFlat's second stage): exact scores of a caller's candidate rows, sorted top-k
+#include "lrx_search_selector.h"  // row selector (faiss IDSelector*): the bitmap over original rows that the four inverted-file scans test
 #include "lrx_search_ivf.h"       // inverted file (faiss IndexIVFFlat): exact top-k over the rows of the probed cells, cell-major scan
 #include "lrx_search_ivfpq.h"     // inverted file over PQ codes (faiss IndexIVFPQ): ADC top-k over the rows of the probed cells, query-major scan
 #include "lrx_search_ivfsq.h"     // inverted file over fp16 codes (faiss IndexIVFScalarQuantizer, QT_fp16): the cell-major chain over 2-byte codes

@@ -192,11 +192,17 @@ k_ivf_items(const unsigned int* __restrict__ cell_cnt, const int64_t* __restrict
 // `score(rr, query, slot)`, the query row streamed from L2.  The word goes to words[query * max_scan + seg_off[slot] + (row's position inside
 // its cell)] -- the contract with k_ivf_plan, k_ivf_select and k_ivf_range: inside the query's segment by the plan's own sums over the same
 // list_off, whatever list_off holds; rows outside [0, N) are never read, and an original row outside it becomes a word of 0 and is counted.
-template <class Stage, class Score>
+// SEL (the *_sel entries): `sel` is a row selector's bitmap over the original rows [0, N) (lrx_search_selector.h).  Per item the
+// first two waves test the group's rows ONCE -- row_ids[r] -> bit, a ballot per wave -- into a workgroup-shared mask of <= 128 bits; a group
+// with no selected row is NOT staged (the skip is workgroup-uniform and both barriers stay), and a unit whose row is deselected writes the
+// null word 0ull WITHOUT calling score(): the words are not cleared between calls or chunks, so a word left unwritten would be an earlier
+// search's hit.  An original row outside [0, N) has no bit: it stays on the unfiltered path (a word of 0, counted).  SEL = false is the walk
+// without a selector, the only one the plain entries launch: no mask, no extra barrier, `sel` never read.
+template <bool SEL, class Stage, class Score>
 __device__ __forceinline__ void ivf_scan_items(int64_t N, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist,
                                                int nprobe, const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off,
                                                const unsigned int* __restrict__ item_off, unsigned int item_cap, const unsigned int* __restrict__ seg_off,
-                                               int64_t max_scan, unsigned long long* __restrict__ words, Stage stage, Score score) {
+                                               int64_t max_scan, unsigned long long* __restrict__ words, const uint32_t* __restrict__ sel, Stage stage, Score score) {
   const int lane = threadIdx.x & 63, hw = threadIdx.x >> 5;
   const unsigned int n_items = min(item_off[nlist], item_cap);
   unsigned int bad = 0;
@@ -216,7 +222,24 @@ __device__ __forceinline__ void ivf_scan_items(int64_t N, int G, const int64_t* 
     if (ra < ca || ra < 0 || rb <= ra || np == 0) continue;  // (workgroup-uniform)
     const int nrows = (int)(rb - ra);
     __syncthreads();                                         // the previous item's rows are no longer read
-    stage(ra, nrows);
+    unsigned long long m0 = ~0ull, m1 = ~0ull;               // SEL: rows 0..63 / 64..127 of the group that are scored
+    if constexpr (SEL) {
+      __shared__ unsigned long long s_on[IVF_MAX_GROUP_ROWS / 64];
+      if (threadIdx.x < IVF_MAX_GROUP_ROWS) {                // (two whole waves)
+        bool on = false;
+        if ((int)threadIdx.x < nrows) {
+          const int64_t r = ra + threadIdx.x;
+          const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
+          on = !(orig >= 0 && orig < N) || sel_test(sel, orig);
+        }
+        const unsigned long long bal = __ballot(on);
+        if (lane == 0) s_on[threadIdx.x >> 6] = bal;
+      }
+      __syncthreads();
+      m0 = s_on[0];
+      m1 = s_on[1];
+    }
+    if (!SEL || (m0 | m1) != 0ull) stage(ra, nrows);         // (workgroup-uniform: the mask is the workgroup's)
     __syncthreads();
     const unsigned int units = np * (unsigned int)nrows;     // (at most IVF_MAX_CHUNK pairs x 128 rows)
     for (unsigned int u = hw; u < units; u += ROWGRP_THREADS / 32) {
@@ -225,6 +248,12 @@ __device__ __forceinline__ void ivf_scan_items(int64_t N, int G, const int64_t* 
       const int64_t r = ra + rr;
       const unsigned int slot = (unsigned int)sorted[p0 + pi];
       const unsigned int qi = slot / (unsigned int)nprobe;
+      if constexpr (SEL) {
+        if (!(((rr < 64 ? m0 : m1) >> (rr & 63)) & 1ull)) {  // (uniform over the half-wave)
+          if ((lane & 31) == 0) words[(int64_t)qi * max_scan + seg_off[slot] + (r - ca)] = 0ull;
+          continue;
+        }
+      }
       const float sc = score(rr, qi, slot);
       if ((lane & 31) == 0) {
         const int64_t orig = row_ids != nullptr ? row_ids[r] : r;
@@ -244,14 +273,15 @@ __device__ __forceinline__ double ivf_probe_base(const float* __restrict__ probe
 }
 
 // The scan over fp32 rows: a group is staged as it is stored, a pair's score is exact_dot_lds_row's (the bits of exact_dot).
+template <bool SEL>
 __global__ void __launch_bounds__(ROWGRP_THREADS)
 k_ivf_scan(const float* __restrict__ X, int64_t N, int64_t ldx, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids,
            int nlist, const float* __restrict__ q, int nprobe, const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off,
            const unsigned int* __restrict__ item_off, unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan,
-           unsigned long long* __restrict__ words) {
+           unsigned long long* __restrict__ words, const uint32_t* __restrict__ sel) {
   __shared__ __attribute__((aligned(16))) float s_x[ROWGRP_LDS_FLOATS];
   const int tid = threadIdx.x, lane = tid & 63;
-  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+  ivf_scan_items<SEL>(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words, sel,
     [&](int64_t ra, int nrows) {
       for (int i = tid * 4; i < nrows * D; i += ROWGRP_THREADS * 4) {
         const int rr = i / D, cc = i - rr * D;
@@ -528,7 +558,20 @@ struct IvfScanArgs {
   const unsigned int *cell_off, *item_off, *seg_off;
   unsigned int item_cap;
   unsigned long long* words;
+  const uint32_t* sel;                      // the selector's bitmap (the scan's SEL instantiation), or NULL (the plain one)
 };
+
+// A row selector as the *_sel entries take it: `bits` NULL = none (the plain entry); otherwise a bitmap over `rows` == n_rows original rows.
+struct IvfSel {
+  const uint32_t* bits;
+  int64_t rows;
+};
+static const IvfSel IVF_NO_SEL = {nullptr, 0};
+static int ivf_sel_check(const char* who, const IvfSel& sel, int64_t n_rows) {
+  LRX_CHECK_ARG(sel.bits == nullptr || sel.rows == n_rows, "%s: sel_rows=%lld is not the rows of the index (n_rows=%lld)", who, (long long)sel.rows,
+                (long long)n_rows);
+  return LRX_OK;
+}
 
 // The host driver of the CELL-MAJOR chain, shared by lrx_ivf_flat_ip_search and lrx_ivf_sq_fp16_ip_search (lrx_search_ivfsq.h): the argument
 // checks both contracts have in common (`who` names the entry in the messages; rows_ok / rows_why: the entry's own check of its row store, made
@@ -538,8 +581,8 @@ struct IvfScanArgs {
 template <class Scan>
 static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok, const char* rows_why, int G, int64_t n_rows, int32_t dim,
                                  const int64_t* list_off, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe,
-                                 int64_t ld_probe, int64_t max_scan_rows, const IvfOut& out, void* workspace, size_t workspace_bytes, void* stream,
-                                 Scan scan) {
+                                 int64_t ld_probe, int64_t max_scan_rows, const IvfOut& out, const IvfSel& sel, void* workspace, size_t workspace_bytes,
+                                 void* stream, Scan scan) {
   LRX_CHECK_ARG(dim >= 32 && dim <= 8192 && dim % 32 == 0, "%s: dim=%d must be a multiple of 32 in 32..8192", who, dim);
   if (int rc = ivf_out_check(who, out)) return rc;
   LRX_CHECK_ARG(nlist >= 1, "%s: nlist=%d must be >= 1", who, nlist);
@@ -549,6 +592,7 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
   LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "%s: rows=%lld out of range", who, (long long)n_rows);
   LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "%s: max_scan_rows=%lld out of range (0..2^31 - 1)", who, (long long)max_scan_rows);
   LRX_CHECK_ARG(rows_ok, "%s: %s", who, rows_why);
+  if (int rc = ivf_sel_check(who, sel, n_rows)) return rc;
   LRX_CHECK_ARG(n_queries >= 0, "%s: n_queries=%d", who, n_queries);
   hipStream_t s = (hipStream_t)stream;
   if (n_queries == 0) return ivf_out_empty(out, s);
@@ -594,6 +638,7 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
       a.sorted = sorted; a.cell_off = cell_off; a.item_off = item_off; a.seg_off = seg_off;
       a.item_cap = (unsigned int)(item_cap < 0xFFFFFFFFll ? item_cap : 0xFFFFFFFFll);
       a.words = words;
+      a.sel = sel.bits;
       scan(a);
       LRX_LAUNCH_CHECK();
     }
@@ -605,13 +650,14 @@ static int ivf_cell_major_search(const char* who, const void* rows, bool rows_ok
 // lrx_ivf_flat_ip_search and lrx_ivf_flat_ip_range_search: the driver over k_ivf_scan
 static int ivf_flat_run(const char* who, const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
                         const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe, int64_t max_scan_rows, const IvfOut& out,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+                        const IvfSel& sel, void* workspace, size_t workspace_bytes, void* stream) {
   char why[128];
   snprintf(why, sizeof(why), "rows must be 16-byte aligned (ldx=%lld >= dim=%d, ldx %% 4 == 0)", (long long)ldx, dim);
   return ivf_cell_major_search(who, X, ldx >= dim && ldx % 4 == 0 && (uintptr_t)X % 16 == 0, why, dim > 0 ? ivf_group_rows(dim) : 1, n_rows, dim, list_off, nlist,
-                               q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
-    hipLaunchKernelGGL(k_ivf_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, X, n_rows, ldx, (int)dim, a.G, list_off, row_ids, (int)nlist, a.q,
-                       (int)nprobe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+                               q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, sel, workspace, workspace_bytes, stream, [&](const IvfScanArgs& a) {
+    auto* kern = a.sel != nullptr ? k_ivf_scan<true> : k_ivf_scan<false>;
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, X, n_rows, ldx, (int)dim, a.G, list_off, row_ids, (int)nlist, a.q,
+                       (int)nprobe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words, a.sel);
   });
 }
 
@@ -620,7 +666,16 @@ extern "C" int lrx_ivf_flat_ip_search(const float* X, int64_t n_rows, int64_t ld
                                       int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   return ivf_flat_run("ivf_flat_ip_search", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
-                      ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+                      ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IVF_NO_SEL, workspace, workspace_bytes, stream);
+}
+
+// The search under a row selector (lrx_search_selector.h): sel_bits == NULL is lrx_ivf_flat_ip_search.
+extern "C" int lrx_ivf_flat_ip_search_sel(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                          int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe,
+                                          int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map,
+                                          const uint32_t* sel_bits, int64_t sel_rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_flat_run("ivf_flat_ip_search_sel", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
+                      ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IvfSel{sel_bits, sel_rows}, workspace, workspace_bytes, stream);
 }
 
 // The workspace of the cell-major range searches (flat, fp16 codes, 8-bit codes): the search's plus the hit counts of a chunk
@@ -634,5 +689,15 @@ extern "C" int lrx_ivf_flat_ip_range_search(const float* X, int64_t n_rows, int6
                                             int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids,
                                             int64_t capacity, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
   return ivf_flat_run("ivf_flat_ip_range_search", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
-                      ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace, workspace_bytes, stream);
+                      ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IVF_NO_SEL, workspace, workspace_bytes, stream);
+}
+
+extern "C" int lrx_ivf_flat_ip_range_search_sel(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                                int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, int32_t nprobe, int64_t ld_probe,
+                                                int64_t max_scan_rows, float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids,
+                                                int64_t capacity, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+  return ivf_flat_run("ivf_flat_ip_range_search_sel", X, n_rows, ldx, dim, list_off, row_ids, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows,
+                      ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IvfSel{sel_bits, sel_rows}, workspace, workspace_bytes,
+                      stream);
 }

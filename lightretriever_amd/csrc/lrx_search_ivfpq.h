@@ -30,11 +30,15 @@
 //                   order of the adds is the same.  The lookups are k_pq_scan's, its M % 16 != 0 tail included.
 // The lane writes sel_pack(score, original row) to words[q * max_scan + s]; a position outside [0, n_rows) or an original row outside it
 // becomes a word of 0 (nobody's row: the selection drops it) and is counted.  No position outside [0, n_rows) is read.
+// SEL (the *_sel entries): `sel` is a row selector's bitmap over the original rows (lrx_search_selector.h); the lane tests the bit
+// of its position's original row BEFORE the adds and, when the row is deselected, does none and writes the null word 0ull (the words are not
+// cleared between calls).  The table passes and their barriers stay workgroup-uniform.  SEL = false is the scan without a selector, unchanged.
+template <bool SEL>
 __global__ void __launch_bounds__(PQ_SCAN_THREADS)
 k_ivf_pq_scan(const uint8_t* __restrict__ codes, int64_t n_rows, int M, int Mp, const float* __restrict__ lut, const int64_t* __restrict__ probes,
               const float* __restrict__ probe_scores, int nprobe, int64_t ld_probe, const int64_t* __restrict__ list_off,
               const int64_t* __restrict__ row_ids, int nlist, const unsigned int* __restrict__ seg_off, const int64_t* __restrict__ q_tot,
-              int64_t max_scan, unsigned long long* __restrict__ words) {
+              int64_t max_scan, unsigned long long* __restrict__ words, const uint32_t* __restrict__ sel) {
   extern __shared__ __attribute__((aligned(16))) float ivfpq_lut_s[];
   __shared__ unsigned int s_off[IVF_MAX_NPROBE];
   __shared__ int s_cell[IVF_MAX_NPROBE];
@@ -70,6 +74,13 @@ k_ivf_pq_scan(const uint8_t* __restrict__ codes, int64_t n_rows, int M, int Mp, 
     const bool valid = in_seg && p >= 0 && p < n_rows;
     const int64_t pv = valid ? p : 0;
     const uint8_t* rc = codes + (pv / PQ_BLK) * PQ_BLK * Mp + (pv % PQ_BLK) * PQ_GRP;   // (dereferenced only when valid)
+    bool skip = false;                                       // SEL: an original row inside the shard whose bit is clear
+    if constexpr (SEL) {
+      if (valid) {
+        const int64_t o = row_ids != nullptr ? row_ids[p] : p;
+        skip = o >= 0 && o < n_rows && !sel_test(sel, o);
+      }
+    }
     float acc = s_base[lo];
     for (int m0 = 0; m0 < M; m0 += mc) {
       const int m1 = m0 + mc < M ? m0 + mc : M;
@@ -79,7 +90,7 @@ k_ivf_pq_scan(const uint8_t* __restrict__ codes, int64_t n_rows, int M, int Mp, 
           *(float4*)(ivfpq_lut_s + e) = *(const float4*)(lq + (int64_t)m0 * PQ_KSUB + e);
         __syncthreads();
       }
-      if (valid) {
+      if (valid && !skip) {
         uint4 cur = *(const uint4*)(rc + (int64_t)(m0 / PQ_GRP) * (PQ_BLK * PQ_GRP));
         for (int g = m0; g < m1; g += PQ_GRP) {
           uint4 nxt = cur;
@@ -102,7 +113,7 @@ k_ivf_pq_scan(const uint8_t* __restrict__ codes, int64_t n_rows, int M, int Mp, 
       const int64_t orig = valid ? (row_ids != nullptr ? row_ids[p] : p) : -1;
       const bool ok = orig >= 0 && orig < n_rows;
       if (!ok) ++bad;
-      wq[s] = ok ? sel_pack(f2key(acc), orig) : 0ull;
+      wq[s] = (ok && !skip) ? sel_pack(f2key(acc), orig) : 0ull;
     }
   }
   if (bad) atomicAdd(&g_ivf_bad, bad);
@@ -140,7 +151,7 @@ extern "C" size_t lrx_ivf_pq_ip_workspace_bytes(int64_t n_rows, int32_t nlist, i
 // k_ivf_select, or the range search's count, lims and fill, whose hit counts lie behind the search's workspace.
 static int ivf_pq_run(const char* who, const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
                       const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
-                      int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, void* workspace,
+                      int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, const IvfSel& sel, void* workspace,
                       size_t workspace_bytes, void* stream) {
   LRX_CHECK_ARG(M > 0 && dim > 0 && dim % M == 0, "%s: dim=%d is not a multiple of M=%d", who, dim, M);
   if (int rc = ivf_out_check(who, out)) return rc;
@@ -150,6 +161,7 @@ static int ivf_pq_run(const char* who, const void* codes, int64_t n_rows, const 
   LRX_CHECK_ARG(ld_probe >= nprobe, "%s: ld_probe=%lld < nprobe=%d", who, (long long)ld_probe, nprobe);
   LRX_CHECK_ARG(n_rows >= 0 && n_rows < (1ll << 32), "%s: rows=%lld out of range", who, (long long)n_rows);
   LRX_CHECK_ARG(max_scan_rows >= 0 && max_scan_rows < (1ll << 31), "%s: max_scan_rows=%lld out of range (0..2^31 - 1)", who, (long long)max_scan_rows);
+  if (int rc = ivf_sel_check(who, sel, n_rows)) return rc;
   LRX_CHECK_ARG(n_queries >= 0, "%s: n_queries=%d", who, n_queries);
   hipStream_t s = (hipStream_t)stream;
   if (n_queries == 0) return ivf_out_empty(out, s);
@@ -171,7 +183,8 @@ static int ivf_pq_run(const char* who, const void* codes, int64_t n_rows, const 
   unsigned int* surv = (unsigned int*)(ws + p.total);        // (the range search's)
   const int Mp = pq_mp(M);
   const size_t smem = (size_t)(M < PQ_SCAN_MC ? M : PQ_SCAN_MC) * PQ_KSUB * 4;
-  if (smem > (32u << 10)) LRX_HIP(hipFuncSetAttribute((const void*)k_ivf_pq_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  auto* scan = sel.bits != nullptr ? k_ivf_pq_scan<true> : k_ivf_pq_scan<false>;
+  if (smem > (32u << 10)) LRX_HIP(hipFuncSetAttribute((const void*)scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   const int64_t max_tiles = lrx_cdiv(max_scan_rows, IVFPQ_TILE);
   const int ncu = lrx_cu_count();
   for (int q0 = 0; q0 < n_queries; q0 += p.chunk) {
@@ -185,9 +198,9 @@ static int ivf_pq_run(const char* who, const void* codes, int64_t n_rows, const 
     if (max_tiles > 0) {                                       // (no rows: every word of a segment becomes 0 and is counted)
       int64_t gx = lrx_cdiv(2 * (int64_t)ncu, nq);             // two workgroups' worth of tiles per CU over the chunk, as k_pq_scan's grid
       gx = gx > max_tiles ? max_tiles : gx;
-      hipLaunchKernelGGL(k_ivf_pq_scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, s, (const uint8_t*)codes, n_rows, (int)M, Mp,
+      hipLaunchKernelGGL(scan, dim3((unsigned)gx, (unsigned)nq), dim3(PQ_SCAN_THREADS), smem, s, (const uint8_t*)codes, n_rows, (int)M, Mp,
                          (const float*)lut, pc, by_residual ? probe_scores + (int64_t)q0 * ld_probe : (const float*)nullptr, (int)nprobe, ld_probe, list_off,
-                         row_ids, (int)nlist, (const unsigned int*)seg_off, (const int64_t*)q_tot, max_scan_rows, words);
+                         row_ids, (int)nlist, (const unsigned int*)seg_off, (const int64_t*)q_tot, max_scan_rows, words, sel.bits);
       LRX_LAUNCH_CHECK();
     }
     if (int rc = ivf_out_launch(out, s, words, max_scan_rows, q_tot, surv, q0, nq, 1)) return rc;
@@ -201,7 +214,18 @@ extern "C" int lrx_ivf_pq_ip_search(const void* codes, int64_t n_rows, const flo
                                     int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace,
                                     size_t workspace_bytes, void* stream) {
   return ivf_pq_run("ivf_pq_ip_search", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
-                    by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+                    by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IVF_NO_SEL, workspace, workspace_bytes, stream);
+}
+
+// The search under a row selector (lrx_search_selector.h): sel_bits == NULL is lrx_ivf_pq_ip_search.
+extern "C" int lrx_ivf_pq_ip_search_sel(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                                        const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                        const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                                        int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits,
+                                        int64_t sel_rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_pq_run("ivf_pq_ip_search_sel", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                    ld_probe, by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IvfSel{sel_bits, sel_rows}, workspace,
+                    workspace_bytes, stream);
 }
 
 extern "C" size_t lrx_ivf_pq_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t M, int32_t n_queries, int32_t nprobe,
@@ -217,6 +241,17 @@ extern "C" int lrx_ivf_pq_ip_range_search(const void* codes, int64_t n_rows, con
                                           float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
                                           const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
   return ivf_pq_run("ivf_pq_ip_range_search", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
-                    ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace,
+                    ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IVF_NO_SEL, workspace,
                     workspace_bytes, stream);
+}
+
+extern "C" int lrx_ivf_pq_ip_range_search_sel(const void* codes, int64_t n_rows, const float* pq_centroids, int32_t dim, int32_t M, const int64_t* list_off,
+                                              const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                              const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                              float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                              const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  return ivf_pq_run("ivf_pq_ip_range_search_sel", codes, n_rows, pq_centroids, dim, M, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                    ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map),
+                    IvfSel{sel_bits, sel_rows}, workspace, workspace_bytes, stream);
 }

@@ -26,15 +26,17 @@ __device__ __forceinline__ float exact_dot_lds_codes(const _Float16* c_lds, cons
 
 // The scan: ivf_scan_items (lrx_search_ivf.h) over fp16 codes.  A group's code rows -- one contiguous run of nrows * D halves, 16-byte aligned
 // since D % 32 == 0, nrows * D <= IVFSQ_LDS_HALVES -- are staged in LDS AS fp16 (coalesced non-temporal 16-byte loads); a pair's score is
-// the dot over the codes plus its base term (ivf_probe_base).
+// the dot over the codes plus its base term (ivf_probe_base).  SEL: the walk under a row selector (ivf_scan_items).
+template <bool SEL>
 __global__ void __launch_bounds__(ROWGRP_THREADS)
 k_ivf_sq_scan(const _Float16* __restrict__ C, int64_t N, int D, int G, const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist,
               const float* __restrict__ q, const float* __restrict__ probe_scores, int nprobe, int64_t ld_probe,
               const unsigned long long* __restrict__ sorted, const unsigned int* __restrict__ cell_off, const unsigned int* __restrict__ item_off,
-              unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words) {
+              unsigned int item_cap, const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words,
+              const uint32_t* __restrict__ sel) {
   __shared__ __attribute__((aligned(16))) _Float16 s_c[IVFSQ_LDS_HALVES];
   const int tid = threadIdx.x, lane = tid & 63;
-  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+  ivf_scan_items<SEL>(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words, sel,
     [&](int64_t ra, int nrows) {
       const _Float16* src = C + ra * D;
       for (int i = tid * 8; i < nrows * D; i += ROWGRP_THREADS * 8) *(f16x8*)(s_c + i) = __builtin_nontemporal_load((const f16x8*)(src + i));
@@ -79,14 +81,15 @@ extern "C" size_t lrx_ivf_sq_fp16_ip_workspace_bytes(int64_t n_rows, int32_t nli
 // lrx_ivf_sq_fp16_ip_search and lrx_ivf_sq_fp16_ip_range_search: the driver over k_ivf_sq_scan
 static int ivf_sq_run(const char* who, const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
                       const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe, int64_t ld_probe,
-                      int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, void* workspace, size_t workspace_bytes, void* stream) {
+                      int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, const IvfSel& sel, void* workspace, size_t workspace_bytes, void* stream) {
   LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "%s: by_residual=%d needs probe_scores", who, by_residual);
   return ivf_cell_major_search(who, codes, (uintptr_t)codes % 16 == 0, "codes must be 16-byte aligned", dim > 0 ? ivf_sq_group_rows(dim) : 1, n_rows, dim,
-                               list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, workspace, workspace_bytes, stream,
+                               list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, sel, workspace, workspace_bytes, stream,
                                [&](const IvfScanArgs& a) {
-    hipLaunchKernelGGL(k_ivf_sq_scan, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const _Float16*)codes, n_rows, (int)dim, a.G, list_off, row_ids,
+    auto* kern = a.sel != nullptr ? k_ivf_sq_scan<true> : k_ivf_sq_scan<false>;
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const _Float16*)codes, n_rows, (int)dim, a.G, list_off, row_ids,
                        (int)nlist, a.q, by_residual ? probe_scores + (int64_t)a.q0 * ld_probe : (const float*)nullptr, (int)nprobe, ld_probe, a.sorted,
-                       a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+                       a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words, a.sel);
   });
 }
 
@@ -95,7 +98,18 @@ extern "C" int lrx_ivf_sq_fp16_ip_search(const void* codes, int64_t n_rows, int3
                                          int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores,
                                          int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
   return ivf_sq_run("ivf_sq_fp16_ip_search", codes, n_rows, dim, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe, by_residual,
-                    max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+                    max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IVF_NO_SEL, workspace, workspace_bytes, stream);
+}
+
+// The search under a row selector (lrx_search_selector.h): sel_bits == NULL is lrx_ivf_sq_fp16_ip_search.
+extern "C" int lrx_ivf_sq_fp16_ip_search_sel(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids, int32_t nlist,
+                                             const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores, int32_t nprobe,
+                                             int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k, int64_t id_base, float* out_scores,
+                                             int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+  return ivf_sq_run("ivf_sq_fp16_ip_search_sel", codes, n_rows, dim, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
+                    by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IvfSel{sel_bits, sel_rows}, workspace, workspace_bytes,
+                    stream);
 }
 
 extern "C" size_t lrx_ivf_sq_fp16_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe,
@@ -109,7 +123,19 @@ extern "C" int lrx_ivf_sq_fp16_ip_range_search(const void* codes, int64_t n_rows
                                                float* out_scores, int64_t* out_ids, int64_t capacity, const int64_t* row_map, void* workspace,
                                                size_t workspace_bytes, void* stream) {
   return ivf_sq_run("ivf_sq_fp16_ip_range_search", codes, n_rows, dim, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
-                    by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace, workspace_bytes, stream);
+                    by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IVF_NO_SEL, workspace,
+                    workspace_bytes, stream);
+}
+
+extern "C" int lrx_ivf_sq_fp16_ip_range_search_sel(const void* codes, int64_t n_rows, int32_t dim, const int64_t* list_off, const int64_t* row_ids,
+                                                   int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
+                                                   int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, float radius,
+                                                   int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                                   const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace,
+                                                   size_t workspace_bytes, void* stream) {
+  return ivf_sq_run("ivf_sq_fp16_ip_range_search_sel", codes, n_rows, dim, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
+                    by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IvfSel{sel_bits, sel_rows},
+                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int lrx_ivf_sq_fp16_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim, const float* centroids, const int64_t* cells, int32_t nlist,

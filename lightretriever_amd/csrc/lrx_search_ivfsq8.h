@@ -36,20 +36,20 @@ __device__ __forceinline__ float exact_dot_lds_row_base(const float* x_lds, cons
 // A lane's 16 floats -- one 64-byte chunk c = i / 16 of the image -- are four 16-byte LDS stores; slot s goes to slot s ^ (c / 2) % 4, so the
 // eight lanes that one store cycle serves (banks (a / 4) % 32, 64 B per lane: unswizzled they would hit two slots four times over) hit eight
 // distinct 16-byte slots; the half-wave that reads a row undoes it per lane (exact_dot_lds_row_base).  A pair's score is the dot over the
-// fp32 rows plus its base term (ivf_probe_base).
-template <bool UNIFORM>
+// fp32 rows plus its base term (ivf_probe_base).  SEL: the walk under a row selector (ivf_scan_items).
+template <bool UNIFORM, bool SEL>
 __global__ void __launch_bounds__(ROWGRP_THREADS, 4)          // (4 waves per SIMD = two workgroups per CU, as k_ivf_scan has: at most 128 VGPRs)
 k_ivf_sq8_scan(const uint8_t* __restrict__ C, int64_t N, int D, int G, const float* __restrict__ trained,
                const int64_t* __restrict__ list_off, const int64_t* __restrict__ row_ids, int nlist, const float* __restrict__ q,
                const float* __restrict__ probe_scores, int nprobe, int64_t ld_probe, const unsigned long long* __restrict__ sorted,
                const unsigned int* __restrict__ cell_off, const unsigned int* __restrict__ item_off, unsigned int item_cap,
-               const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words) {
+               const unsigned int* __restrict__ seg_off, int64_t max_scan, unsigned long long* __restrict__ words, const uint32_t* __restrict__ sel) {
   __shared__ __attribute__((aligned(16))) float s_x[ROWGRP_LDS_FLOATS];
   __shared__ float s_t[256];
   const int tid = threadIdx.x, lane = tid & 63;
   if (tid < 256) s_t[tid] = __fdiv_rn((float)tid + 0.5f, 255.f);   // (read after the walk's barrier in front of the first item's staging)
   const int col0 = (tid * 16) % D, col_step = (ROWGRP_THREADS * 16) % D;   // the dimension of a lane's first code, pass by pass (no division per item)
-  ivf_scan_items(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words,
+  ivf_scan_items<SEL>(N, G, list_off, row_ids, nlist, nprobe, sorted, cell_off, item_off, item_cap, seg_off, max_scan, words, sel,
     [&](int64_t ra, int nrows) {
       int col = col0;                                        // (D % 32 == 0: a lane's 16 codes are 16 consecutive dimensions of one row)
       const uint8_t* src = C + ra * D;
@@ -160,22 +160,20 @@ extern "C" size_t lrx_ivf_sq8_ip_workspace_bytes(int64_t n_rows, int32_t nlist, 
 // lrx_ivf_sq8_ip_search and lrx_ivf_sq8_ip_range_search: the driver over k_ivf_sq8_scan
 static int ivf_sq8_run(const char* who, const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
                        const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes, const float* probe_scores,
-                       int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, void* workspace,
+                       int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, const IvfOut& out, const IvfSel& sel, void* workspace,
                        size_t workspace_bytes, void* stream) {
   LRX_CHECK_ARG(sq8_qtype_ok(qtype), "%s: qtype=%d (0: QT_8bit, 2: QT_8bit_uniform)", who, qtype);
   LRX_CHECK_ARG(by_residual == 0 || probe_scores != nullptr, "%s: by_residual=%d needs probe_scores", who, by_residual);
   LRX_CHECK_ARG(trained != nullptr && (uintptr_t)trained % 16 == 0, "%s: trained (vmin ++ vdiff) must be a 16-byte aligned pointer", who);
   const int uniform = qtype == SQ8_QT_8BIT_UNIFORM ? 1 : 0;
   return ivf_cell_major_search(who, codes, (uintptr_t)codes % 16 == 0, "codes must be 16-byte aligned", dim > 0 ? ivf_group_rows(dim) : 1, n_rows, dim,
-                               list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, workspace, workspace_bytes, stream,
+                               list_off, nlist, q, n_queries, probes, nprobe, ld_probe, max_scan_rows, out, sel, workspace, workspace_bytes, stream,
                                [&](const IvfScanArgs& a) {
     const float* ps = by_residual ? probe_scores + (int64_t)a.q0 * ld_probe : (const float*)nullptr;
-    if (uniform)
-      hipLaunchKernelGGL(k_ivf_sq8_scan<true>, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const uint8_t*)codes, n_rows, (int)dim, a.G, trained, list_off,
-                         row_ids, (int)nlist, a.q, ps, (int)nprobe, ld_probe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
-    else
-      hipLaunchKernelGGL(k_ivf_sq8_scan<false>, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const uint8_t*)codes, n_rows, (int)dim, a.G, trained, list_off,
-                         row_ids, (int)nlist, a.q, ps, (int)nprobe, ld_probe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words);
+    auto* kern = uniform ? (a.sel != nullptr ? k_ivf_sq8_scan<true, true> : k_ivf_sq8_scan<true, false>)
+                         : (a.sel != nullptr ? k_ivf_sq8_scan<false, true> : k_ivf_sq8_scan<false, false>);
+    hipLaunchKernelGGL(kern, dim3(a.grid), dim3(ROWGRP_THREADS), 0, a.stream, (const uint8_t*)codes, n_rows, (int)dim, a.G, trained, list_off, row_ids,
+                       (int)nlist, a.q, ps, (int)nprobe, ld_probe, a.sorted, a.cell_off, a.item_off, a.item_cap, a.seg_off, max_scan_rows, a.words, a.sel);
   });
 }
 
@@ -185,7 +183,18 @@ extern "C" int lrx_ivf_sq8_ip_search(const void* codes, int64_t n_rows, int32_t 
                                      int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, void* workspace, size_t workspace_bytes,
                                      void* stream) {
   return ivf_sq8_run("ivf_sq8_ip_search", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe, ld_probe,
-                     by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), workspace, workspace_bytes, stream);
+                     by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IVF_NO_SEL, workspace, workspace_bytes, stream);
+}
+
+// The search under a row selector (lrx_search_selector.h): sel_bits == NULL is lrx_ivf_sq8_ip_search.
+extern "C" int lrx_ivf_sq8_ip_search_sel(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                         const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                         const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows, int32_t k,
+                                         int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, const uint32_t* sel_bits,
+                                         int64_t sel_rows, void* workspace, size_t workspace_bytes, void* stream) {
+  return ivf_sq8_run("ivf_sq8_ip_search_sel", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                     ld_probe, by_residual, max_scan_rows, ivf_out_topk(k, id_base, out_scores, out_ids, row_map), IvfSel{sel_bits, sel_rows}, workspace,
+                     workspace_bytes, stream);
 }
 
 extern "C" size_t lrx_ivf_sq8_ip_range_workspace_bytes(int64_t n_rows, int32_t nlist, int32_t dim, int32_t n_queries, int32_t nprobe, int64_t max_scan_rows) {
@@ -198,8 +207,19 @@ extern "C" int lrx_ivf_sq8_ip_range_search(const void* codes, int64_t n_rows, in
                                            float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
                                            const int64_t* row_map, void* workspace, size_t workspace_bytes, void* stream) {
   return ivf_sq8_run("ivf_sq8_ip_range_search", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
-                     ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), workspace,
+                     ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map), IVF_NO_SEL, workspace,
                      workspace_bytes, stream);
+}
+
+extern "C" int lrx_ivf_sq8_ip_range_search_sel(const void* codes, int64_t n_rows, int32_t dim, const float* trained, int32_t qtype, const int64_t* list_off,
+                                               const int64_t* row_ids, int32_t nlist, const float* q, int32_t n_queries, const int64_t* probes,
+                                               const float* probe_scores, int32_t nprobe, int64_t ld_probe, int32_t by_residual, int64_t max_scan_rows,
+                                               float radius, int64_t id_base, int64_t* lims, float* out_scores, int64_t* out_ids, int64_t capacity,
+                                               const int64_t* row_map, const uint32_t* sel_bits, int64_t sel_rows, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  return ivf_sq8_run("ivf_sq8_ip_range_search_sel", codes, n_rows, dim, trained, qtype, list_off, row_ids, nlist, q, n_queries, probes, probe_scores, nprobe,
+                     ld_probe, by_residual, max_scan_rows, ivf_out_range(radius, id_base, lims, out_scores, out_ids, capacity, row_map),
+                     IvfSel{sel_bits, sel_rows}, workspace, workspace_bytes, stream);
 }
 
 // the argument checks the encode and decode entries share

@@ -402,6 +402,18 @@ IvfArgs ivf_args(const char* who, const at::Tensor& q, bool store_ok, const char
   return a;
 }
 
+// The selector of a *_sel op (include/lrx.h, ROW SELECTOR): the int32 words of a bitmap over the n_rows original rows, [ceil(n_rows / 32)]
+// contiguous on the device, or None (no filter).  sel == nullptr: the plain op, which calls the plain entry.
+using OptTensor = c10::optional<at::Tensor>;
+const uint32_t* ivf_sel_bits(const char* who, const OptTensor* sel, int64_t n_rows) {
+  if (sel == nullptr || !sel->has_value() || !(*sel)->defined()) return nullptr;
+  const at::Tensor& t = **sel;
+  need(t, "sel", at::kInt, 1);
+  TORCH_CHECK(t.is_contiguous() && t.numel() == (n_rows + 31) / 32, who, ": sel must be the int32 words of a selector over the ", n_rows,
+              " rows of the index: [", (n_rows + 31) / 32, "] contiguous");
+  return (const uint32_t*)t.data_ptr<int32_t>();
+}
+
 // Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell.  Returns (D, I).
 IvfArgs ivf_flat_ip_args(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
                          const at::Tensor& probes, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
@@ -412,39 +424,69 @@ IvfArgs ivf_flat_ip_args(const char* who, const at::Tensor& q, const at::Tensor&
                   false, max_scan_rows, row_map);
 }
 
-std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, int64_t k, int64_t max_scan_rows,
-                                                    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_flat_ip_topk";
+std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                         const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
   const int64_t n_rows = x.size(0), dim = x.size(1);
   const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    if (sel != nullptr)
+      return lrx_ivf_flat_ip_search_sel(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
+                                        list_off.data_ptr<int64_t>(),
+                                  a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe,
+                                  max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(),
                                   a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe,
                                   max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
 }
+std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_flat_ip_topk_impl("ivf_flat_ip_topk", q, x, list_off, row_ids, probes, k, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk_sel(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+                                                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& sel, int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_flat_ip_topk_impl("ivf_flat_ip_topk_sel", q, x, list_off, row_ids, probes, k, max_scan_rows, id_base, row_map, &sel);
+}
 
 // Range search over the probed cells (lrx_ivf_flat_ip_range_search): ivf_flat_ip_topk's arguments with radius for k.  Returns (lims, D, I), the
 // hits of a query in segment order (cells in probe order, rows by stored position).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, double radius,
-                                                                        int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_flat_ip_range_search";
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& x,
+    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
   const int64_t n_rows = x.size(0), dim = x.size(1);
   const size_t wsb = lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    if (sel != nullptr)
+      return lrx_ivf_flat_ip_range_search_sel(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
+                                        list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(),
+                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, sb, n_rows,
+                                         ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_flat_ip_range_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
                                         list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(),
-                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(), wsb,
-                                        cur_stream());
+                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(),
+                                         wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_flat_ip_range_search_impl("ivf_flat_ip_range_search", q, x, list_off, row_ids, probes, radius, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search_sel(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& sel, double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_flat_ip_range_search_impl("ivf_flat_ip_range_search_sel", q, x, list_off, row_ids, probes, radius, max_scan_rows, id_base, row_map, &sel);
 }
 
 // Inverted file over PQ codes (lrx_ivf_pq_ip_search): codes = the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by
@@ -470,44 +512,78 @@ IvfArgs ivf_pq_ip_args(const char* who, const at::Tensor& q, const at::Tensor& c
   return a;
 }
 
-std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
-                                                  const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                  const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                  int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_pq_ip_topk";
+std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
+                                                       const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
+    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   IvfPqStore st;
   const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
   const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k,
                                                    max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, st.n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    if (sel != nullptr)
+      return lrx_ivf_pq_ip_search_sel(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
+                                list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, st.n_rows,
+                                 ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_pq_ip_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
                                 list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb,
-                                cur_stream());
+                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(),
+                                 wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
+    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_pq_ip_topk_impl("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
+                                                      const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+    const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_pq_ip_topk_impl("ivf_pq_ip_topk_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
 }
 
 // Range search over the probed cells (lrx_ivf_pq_ip_range_search): ivf_pq_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
-                                                                      const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
-                                                                      const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-                                                                      bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-                                                                      const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_pq_ip_range_search";
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
+    const at::Tensor& pq_centroids, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   IvfPqStore st;
   const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
   const size_t wsb = lrx_ivf_pq_ip_range_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe,
                                                          max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, st.n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    if (sel != nullptr)
+      return lrx_ivf_pq_ip_range_search_sel(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
+                                      list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
+                                       a.rm, sb, st.n_rows, ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_pq_ip_range_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
                                       list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm,
-                                      ws.data_ptr(), wsb, cur_stream());
+                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
+                                       a.rm, ws.data_ptr(), wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
+                                                                      const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_pq_ip_range_search_impl("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes,
+    const at::Tensor& pq_centroids, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+    const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_pq_ip_range_search_impl("ivf_pq_ip_range_search_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
 }
 
 // Inverted file over row-major codes [n_rows, D] contiguous, by stored position, cell by cell: fp16 (lrx_ivf_sq_fp16_ip_search) and 8-bit
@@ -523,40 +599,75 @@ IvfArgs ivf_codes_args(const char* who, const at::Tensor& q, const at::Tensor& c
 const char* const kIvfSqShapes = ": q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
 const char* const kIvfSq8Shapes = ": q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
 
-std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-                                                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                       const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                       int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_sq_fp16_ip_topk";
+std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
+                                                            const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
+                                                            const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
   const int64_t n_rows = codes.size(0), dim = codes.size(1);
   const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    if (sel != nullptr)
+      return lrx_ivf_sq_fp16_ip_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri,
+                                           (int32_t)a.nlist,
+                                     q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
+                                     max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
                                      q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
                                      max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
 }
+std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
+                                                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq_fp16_ip_topk_impl("ivf_sq_fp16_ip_topk", q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
+                                                           const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows,
+    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq_fp16_ip_topk_impl("ivf_sq_fp16_ip_topk_sel", q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
+}
 
 // Range search over the probed cells (lrx_ivf_sq_fp16_ip_range_search): ivf_sq_fp16_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-                                                                           const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                                           const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius,
-                                                                           int64_t max_scan_rows, int64_t id_base,
-                                                                           const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_sq_fp16_ip_range_search";
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
+    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
   const int64_t n_rows = codes.size(0), dim = codes.size(1);
   const size_t wsb = lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    if (sel != nullptr)
+      return lrx_ivf_sq_fp16_ip_range_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri,
+                                                 (int32_t)a.nlist,
+                                           q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe,
+                                           by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, sb, n_rows,
+                                               ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_sq_fp16_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
                                            q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe,
                                            by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(), wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq_fp16_ip_range_search_impl("ivf_sq_fp16_ip_range_search", q, codes, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes,
+    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
+    const c10::optional<at::Tensor>& probe_scores, const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows,
+    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq_fp16_ip_range_search_impl("ivf_sq_fp16_ip_range_search_sel", q, codes, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
 }
 
 // The 8-bit family's own operands: trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2).
@@ -571,42 +682,77 @@ IvfArgs ivf_sq8_ip_args(const char* who, const at::Tensor& q, const at::Tensor& 
   return ivf_codes_args(who, q, codes, at::kByte, kIvfSq8Shapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
 }
 
-std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
-                                                   const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                                                   const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows,
-                                                   int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_sq8_ip_topk";
+std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
+                                                        int64_t qtype, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
+    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
   const int64_t n_rows = codes.size(0), dim = codes.size(1);
   const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return topk_result(q, k, who, [&](float* d, int64_t* i) {
+    if (sel != nullptr)
+      return lrx_ivf_sq8_ip_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                 list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows,
+                                  ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
                                  list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb,
-                                 cur_stream());
+                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(),
+                                  wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
+                                                   const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
+    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq8_ip_topk_impl("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
+                                                       const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+    const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq8_ip_topk_impl("ivf_sq8_ip_topk_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
 }
 
 // Range search over the probed cells (lrx_ivf_sq8_ip_range_search): ivf_sq8_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
-                                                                       const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
-                                                                       const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-                                                                       bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-                                                                       const c10::optional<at::Tensor>& row_map) {
-  const char* who = "ivf_sq8_ip_range_search";
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
+    const at::Tensor& trained, int64_t qtype, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
   DevGuard guard(q.device());
   const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
   const int64_t n_rows = codes.size(0), dim = codes.size(1);
   const size_t wsb = lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    if (sel != nullptr)
+      return lrx_ivf_sq8_ip_range_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
+                                       list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
+                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
+                                        a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
     return lrx_ivf_sq8_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
                                        list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm,
-                                       ws.data_ptr(), wsb, cur_stream());
+                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
+                                        a.rm, ws.data_ptr(), wsb, cur_stream());
   });
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
+    int64_t qtype, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
+    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq8_ip_range_search_impl("ivf_sq8_ip_range_search", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
+    int64_t qtype, const at::Tensor& list_off,
+    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
+    const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
+    const c10::optional<at::Tensor>& row_map) {
+  return ivf_sq8_ip_range_search_impl("ivf_sq8_ip_range_search_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
 }
 
 // Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
@@ -868,20 +1014,40 @@ TORCH_LIBRARY(lrx, m) {
   m.def("sq_fp16_ip_rerank(Tensor q, Tensor codes, int n_rows, Tensor cand, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("ivf_flat_ip_range_search(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, float radius, int max_scan_rows, int id_base=0, "
         "Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_flat_ip_range_search_sel(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? sel, float radius, "
+        "int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
   m.def("ivf_pq_ip_range_search(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
         "bool by_residual, float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_pq_ip_range_search_sel(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, "
+        "Tensor? probe_scores, Tensor? sel, bool by_residual, float radius, int max_scan_rows, int id_base=0, "
+        "Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
   m.def("ivf_sq_fp16_ip_range_search(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, bool by_residual, "
         "float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_sq_fp16_ip_range_search_sel(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
+        "Tensor? sel, bool by_residual, float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
   m.def("ivf_sq8_ip_range_search(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
         "bool by_residual, float radius, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
+  m.def("ivf_sq8_ip_range_search_sel(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, "
+        "Tensor? probe_scores, Tensor? sel, bool by_residual, float radius, int max_scan_rows, int id_base=0, "
+        "Tensor? row_map=None) -> (Tensor, Tensor, Tensor)");
   m.def("ivf_flat_ip_topk(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, int k, int max_scan_rows, int id_base=0, "
         "Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_flat_ip_topk_sel(Tensor q, Tensor x, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? sel, int k, int max_scan_rows, "
+        "int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("ivf_pq_ip_topk(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
         "bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_pq_ip_topk_sel(Tensor q, Tensor codes, Tensor pq_centroids, Tensor list_off, Tensor? row_ids, Tensor probes, "
+        "Tensor? probe_scores, Tensor? sel, bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, "
+        "Tensor)");
   m.def("ivf_sq_fp16_ip_topk(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, bool by_residual, int k, "
         "int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_sq_fp16_ip_topk_sel(Tensor q, Tensor codes, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
+        "Tensor? sel, bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("ivf_sq8_ip_topk(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, Tensor? probe_scores, "
         "bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
+  m.def("ivf_sq8_ip_topk_sel(Tensor q, Tensor codes, Tensor trained, int qtype, Tensor list_off, Tensor? row_ids, Tensor probes, "
+        "Tensor? probe_scores, Tensor? sel, bool by_residual, int k, int max_scan_rows, int id_base=0, Tensor? row_map=None) -> (Tensor, "
+        "Tensor)");
   m.def("pq_ip_topk(Tensor q, Tensor codes, Tensor centroids, int n_rows, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("sq8_ip_topk(Tensor q, Tensor codes, int n_rows, Tensor trained, int k, int id_base=0, Tensor? row_map=None) -> (Tensor, Tensor)");
   m.def("impact_topk(Tensor postings, Tensor term_off, int n_rows, Tensor q_off, Tensor q_term, Tensor q_cnt, int k, int id_base=0, Tensor? row_map=None, "
@@ -913,13 +1079,21 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("flat_ip_rerank", &flat_ip_rerank);
   m.impl("sq_fp16_ip_rerank", &sq_fp16_ip_rerank);
   m.impl("ivf_flat_ip_range_search", &ivf_flat_ip_range_search);
+  m.impl("ivf_flat_ip_range_search_sel", &ivf_flat_ip_range_search_sel);
   m.impl("ivf_pq_ip_range_search", &ivf_pq_ip_range_search);
+  m.impl("ivf_pq_ip_range_search_sel", &ivf_pq_ip_range_search_sel);
   m.impl("ivf_sq_fp16_ip_range_search", &ivf_sq_fp16_ip_range_search);
+  m.impl("ivf_sq_fp16_ip_range_search_sel", &ivf_sq_fp16_ip_range_search_sel);
   m.impl("ivf_sq8_ip_range_search", &ivf_sq8_ip_range_search);
+  m.impl("ivf_sq8_ip_range_search_sel", &ivf_sq8_ip_range_search_sel);
   m.impl("ivf_flat_ip_topk", &ivf_flat_ip_topk);
+  m.impl("ivf_flat_ip_topk_sel", &ivf_flat_ip_topk_sel);
   m.impl("ivf_pq_ip_topk", &ivf_pq_ip_topk);
+  m.impl("ivf_pq_ip_topk_sel", &ivf_pq_ip_topk_sel);
   m.impl("ivf_sq_fp16_ip_topk", &ivf_sq_fp16_ip_topk);
+  m.impl("ivf_sq_fp16_ip_topk_sel", &ivf_sq_fp16_ip_topk_sel);
   m.impl("ivf_sq8_ip_topk", &ivf_sq8_ip_topk);
+  m.impl("ivf_sq8_ip_topk_sel", &ivf_sq8_ip_topk_sel);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib, ops
 from .index import FlatIPIndex, _as_rows, _check_range, _grown, _pq_update, _range_args, _range_empty
+from .selector import RowSelector, check_selector
 from .transform import linear_transform
 
 MAX_NPROBE = 2048
@@ -268,18 +269,23 @@ class _IVFCells:
             self._finalize()
         return q, nprobe
 
-    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
+    def search(self, q, k: int, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None, sel: Optional[RowSelector] = None):
         """-> (D f32[Q,k], I i64[Q,k]) device tensors: the top k, under the index's score of a scanned row (its class note), over the rows of each
         query's nprobe best cells (by inner product with the centroids), score descending, ties to the lower original row, (-FLT_MAX, -1)
         padding where those cells hold fewer than k rows.  I = id_base + row, or row_map[row] (int64 CUDA tensor of >= ntotal entries).
-        nprobe: this call's (default: the index's)."""
+        nprobe: this call's (default: the index's).
+        sel: a RowSelector over the ntotal ORIGINAL rows (faiss SearchParameters(sel=...)) -- the top k over the SELECTED rows
+        of those cells, padding where fewer than k of them were scanned; the unfiltered result restricted to the selected rows, bit for bit.
+        One selector for all queries; id_base / row_map apply after it.  Allowed under graph capture as a search without one: set_mask_ /
+        set_rows_ between replays change the filter."""
         q, nprobe = self._begin_search(q, k, nprobe, row_map)
+        sel = check_selector(sel, self.ntotal, self.device, f"{type(self).__name__}.search")
         if q.shape[0] == 0:
             return (torch.empty(0, k, dtype=torch.float32, device=self.device), torch.empty(0, k, dtype=torch.int64, device=self.device))
         probe_scores, probes = self.quantizer.search(q, nprobe)
         capture_error = (f"{type(self).__name__}.search under graph capture: the search workspaces must exist before the capture starts -- run one "
                          "eager search with the same number of queries, k and nprobe first")
-        return self._topk_cells(q, k, probes, probe_scores, self.max_scan_rows(nprobe), row_map, capture_error)
+        return self._topk_cells(q, k, probes, probe_scores, self.max_scan_rows(nprobe), row_map, capture_error, sel)
 
     def range_search(self, q, radius: float):
         raise NotImplementedError(f"{type(self).__name__}.range_search is not served (range search over the probed cells is a follow-up)")
@@ -290,31 +296,36 @@ class _IVFCells:
         return min(max(st["nprobe"], 1), st["nlist"], MAX_NPROBE)
 
     # -- range search over the probed cells -----------------------------------------------------------------
-    def range_search_probed(self, q, radius: float, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None):
+    def range_search_probed(self, q, radius: float, nprobe: Optional[int] = None, row_map: Optional[torch.Tensor] = None,
+                            sel: Optional[RowSelector] = None):
         """-> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]) device tensors: every row of each query's nprobe best cells -- the cells search()
         scans -- whose score, the value search() reports for it, is strictly greater than `radius`; never cut at a k.  Query i's hits are
         D / I[lims[i]:lims[i + 1]] in SEGMENT order, faiss's for an IVF range search: its cells in probe order (best centroid first), inside
         a cell by stored position (ascending original row) -- not sorted by score, and not FlatIPIndex.range_search's ascending-row order.
         I = id_base + row, or row_map[row].  The coarse search of search(), then range_search_preassigned.  Reads the result length back
-        to the host once: refused under graph capture.  NaN radius: ValueError."""
+        to the host once: refused under graph capture.  NaN radius: ValueError.  sel: a RowSelector over the ntotal original rows (see
+        search): only selected rows are hits, the order is unchanged."""
         radius = _range_args(type(self).__name__, radius)
         q, nprobe = self._begin_search(q, None, nprobe, row_map)
+        sel = check_selector(sel, self.ntotal, self.device, f"{type(self).__name__}.range_search_probed")
         if q.shape[0] == 0 or self.ntotal == 0:
             return _range_empty(self.device, q.shape[0])
         probe_scores, probes = self.quantizer.search(q, nprobe)
-        return self._range_cells(q, radius, probes, probe_scores, self.max_scan_rows(nprobe), row_map)
+        return self._range_cells(q, radius, probes, probe_scores, self.max_scan_rows(nprobe), row_map, sel)
 
     def range_search_preassigned(self, q, radius: float, probes: torch.Tensor, probe_scores: Optional[torch.Tensor] = None,
-                                 row_map: Optional[torch.Tensor] = None):
+                                 row_map: Optional[torch.Tensor] = None, sel: Optional[RowSelector] = None):
         """faiss IndexIVF::range_search_preassigned(x, radius, keys, coarse_dis): range_search_probed over the caller's cells.  probes: int64
         [Q, nprobe] on the device, the cells of each query in the order their hits are wanted (an entry < 0 is skipped; one >= nlist is
         skipped and counted in lrx_device_error_count; a cell named twice is scanned once).  probe_scores: fp32 [Q, nprobe], the score of each
-        cell's centroid for the query -- required by an index that codes residuals (by_residual), ignored by one that does not."""
+        cell's centroid for the query -- required by an index that codes residuals (by_residual), ignored by one that does not.  sel: as
+        range_search_probed's."""
         who = type(self).__name__
         radius = _range_args(who, radius)
         if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.int64 and probes.dim() == 2):
             raise ValueError("range_search_preassigned: probes must be an int64 CUDA tensor [Q, nprobe]")
         q, _ = self._begin_search(q, None, probes.shape[1], row_map)
+        sel = check_selector(sel, self.ntotal, self.device, f"{who}.range_search_preassigned")
         if probes.shape[0] != q.shape[0]:
             raise ValueError(f"range_search_preassigned: probes has {probes.shape[0]} rows for {q.shape[0]} queries")
         if getattr(self, "by_residual", False):
@@ -327,7 +338,7 @@ class _IVFCells:
             probe_scores = None
         if q.shape[0] == 0 or self.ntotal == 0:
             return _range_empty(self.device, q.shape[0])
-        return self._range_cells(q, radius, probes.contiguous(), probe_scores, self.max_scan_rows(probes.shape[1]), row_map)
+        return self._range_cells(q, radius, probes.contiguous(), probe_scores, self.max_scan_rows(probes.shape[1]), row_map, sel)
 
 
 class IVFFlatIndex(_IVFCells):
@@ -390,11 +401,17 @@ class IVFFlatIndex(_IVFCells):
         self._set_cells(lo, ri)
 
     # -- search: the exact top k, every scanned (query, row) pair scored with the flat index's own bits --------------------------
-    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error, sel=None):
+        if sel is not None:
+            return ops.ivf_flat_ip_topk_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, sel, k, max_scan_rows, self.id_base, row_map,
+                                            ws_slots=vars(self), capture_error=capture_error)
         return ops.ivf_flat_ip_topk(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, k, max_scan_rows, self.id_base, row_map,
                                     ws_slots=vars(self), capture_error=capture_error)
 
-    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map, sel=None):
+        if sel is not None:
+            return ops.ivf_flat_ip_range_search_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, sel, radius, max_scan_rows, self.id_base,
+                                                    row_map, ws_slots=vars(self))
         return ops.ivf_flat_ip_range_search(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, radius, max_scan_rows, self.id_base, row_map,
                                             ws_slots=vars(self))
 

@@ -149,11 +149,17 @@ class IVFSQ8Index(_IVFCells):
         self._set_cells(lo, ri)
 
     # -- search: the exact top k under the score of the class note -----------------------------------------------------------
-    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error):
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error, sel=None):
+        if sel is not None:
+            return ops.ivf_sq8_ip_topk_sel(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, sel,
+                                           self.by_residual, k, max_scan_rows, self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
         return ops.ivf_sq8_ip_topk(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k,
                                    max_scan_rows, self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
 
-    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map):
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map, sel=None):
+        if sel is not None:
+            return ops.ivf_sq8_ip_range_search_sel(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores, sel,
+                                                   self.by_residual, radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
         return ops.ivf_sq8_ip_range_search(q, self._store[:self.ntotal], self.trained, self._qt, self.list_off, self.row_ids, probes, probe_scores,
                                            self.by_residual, radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
 

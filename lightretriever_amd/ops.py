@@ -326,7 +326,16 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
 # (up to nprobe) and of its two library entries (up to ld_probe / by_residual).  _ivf_topk and _ivf_range add the rest, the same for all four:
 # lrx_<fam>_workspace_bytes(*dims, k, max_scan_rows) and lrx_<fam>_search(*head, max_scan_rows, k, id_base, D, I, row_map, ws, bytes, stream),
 # or lrx_<fam>_range_workspace_bytes(*dims, max_scan_rows) and lrx_<fam>_range_search(*head, max_scan_rows, radius, id_base, lims, D, I,
-# capacity, row_map, ws, bytes, stream).
+# capacity, row_map, ws, bytes, stream).  The *_sel wrappers (a search under a row selector, selector.RowSelector) call lrx_<fam>_search_sel /
+# lrx_<fam>_range_search_sel: the same lists with (sel words, n) in front of ws -- `sel` here is (words or None, n), None for the plain wrappers.
+def _ivf_sel(name: str, sel_words, n: int):
+    """(words, n) of a *_sel wrapper's selector: int32 [ceil(n / 32)] contiguous on the device, or None (no filter)."""
+    if sel_words is not None and (sel_words.dtype != torch.int32 or not sel_words.is_cuda or not sel_words.is_contiguous() or
+                                  sel_words.dim() != 1 or sel_words.numel() != (n + 31) // 32):
+        raise ValueError(f"{name}: sel must be the int32 words of a selector over the {n} rows of the index: [{(n + 31) // 32}] contiguous")
+    return (sel_words, n)
+
+
 def _ivf_probes(name: str, q, probes):
     Q, nprobe = probes.shape
     if probes.dtype != torch.int64 or (nprobe and probes.stride(1) != 1) or q.shape[0] != Q:
@@ -344,7 +353,7 @@ def _ivf_probe_args(name: str, q, Q, probes, probe_scores, nprobe, ld, by_residu
 
 
 def _ivf_topk(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, k: int, id_base: int, row_map, ws_slots: Optional[dict],
-              capture_error: Optional[str]):
+              capture_error: Optional[str], sel=None):
     """What the four IVF searches share: the outputs, the workspace (ws_slots: a dict that keeps it between calls, key "_ws") and the call."""
     from .index import _workspace
     lib = _lib.lib()
@@ -354,12 +363,13 @@ def _ivf_topk(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int,
         return D, I
     need = int(getattr(lib, f"lrx_{fam}_workspace_bytes")(*dims, k, int(max_scan_rows)))
     ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    _lib.check(getattr(lib, f"lrx_{fam}_search")(*head, int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), _lib.ptr(ws),
-                                                 ws.numel(), _s()))
+    fn, sel_args = (getattr(lib, f"lrx_{fam}_search"), ()) if sel is None else (getattr(lib, f"lrx_{fam}_search_sel"), (_lib.ptr(sel[0]), sel[1]))
+    _lib.check(fn(*head, int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), *sel_args, _lib.ptr(ws), ws.numel(), _s()))
     return D, I
 
 
-def _ivf_range(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, radius: float, id_base: int, row_map, ws_slots: Optional[dict]):
+def _ivf_range(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, radius: float, id_base: int, row_map, ws_slots: Optional[dict],
+               sel=None):
     """What the four IVF range searches share: the protocol of index._range_call over ONE library call for all Q queries (the library chunks
     them itself and carries lims on the device) -- outputs sized by a first guess, one host read of lims[Q], one retry when the guess was
     short.  ws_slots: as _ivf_topk's."""
@@ -371,9 +381,10 @@ def _ivf_range(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int
         return _range_empty(q.device, 0)
     need = int(getattr(lib, f"lrx_{fam}_range_workspace_bytes")(*dims, int(max_scan_rows)))
     ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device)
-    fn = getattr(lib, f"lrx_{fam}_range_search")
+    fn, sel_args = (getattr(lib, f"lrx_{fam}_range_search"), ()) if sel is None else (getattr(lib, f"lrx_{fam}_range_search_sel"), (_lib.ptr(sel[0]), sel[1]))
     return _range_call(q.device, Q, Q, lambda s, n, lims, D, I, cap: _lib.check(fn(
-        *head, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), _lib.ptr(ws), ws.numel(), _s())))
+        *head, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), *sel_args, _lib.ptr(ws),
+        ws.numel(), _s())))
 
 
 def _ivf_flat_args(name: str, q, X, list_off, row_ids, probes):
@@ -506,3 +517,55 @@ def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor,
     max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
     Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
     return _ivf_topk("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
+
+
+# -- the searches under a row selector (selector.RowSelector; DESIGN §5.4.15) -----------------------------------------------------------
+# Each wrapper is its plain sibling with `sel` -- the selector's int32 words over the ORIGINAL rows, or None for no filter -- after the last
+# positional tensor, as in torch.ops.lrx.*_sel: the top k (or every hit above the radius) over the SELECTED rows of the probed cells.
+def ivf_flat_ip_topk_sel(q, X, list_off, row_ids, probes, sel, k: int, max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None,
+                         capture_error=None):
+    Q, dims, head = _ivf_flat_args("ivf_flat_ip_topk_sel", q, X, list_off, row_ids, probes)
+    return _ivf_topk("ivf_flat_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_flat_ip_topk_sel", sel, dims[0]))
+
+
+def ivf_flat_ip_range_search_sel(q, X, list_off, row_ids, probes, sel, radius: float, max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None):
+    Q, dims, head = _ivf_flat_args("ivf_flat_ip_range_search_sel", q, X, list_off, row_ids, probes)
+    return _ivf_range("ivf_flat_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_flat_ip_range_search_sel", sel, dims[0]))
+
+
+def ivf_pq_ip_topk_sel(q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int,
+                       id_base: int = 0, row_map=None, ws_slots=None, capture_error=None):
+    Q, dims, head = _ivf_pq_args("ivf_pq_ip_topk_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_pq_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_pq_ip_topk_sel", sel, dims[0]))
+
+
+def ivf_pq_ip_range_search_sel(q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float, max_scan_rows: int,
+                               id_base: int = 0, row_map=None, ws_slots=None):
+    Q, dims, head = _ivf_pq_args("ivf_pq_ip_range_search_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_pq_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_pq_ip_range_search_sel", sel, dims[0]))
+
+
+def ivf_sq_fp16_ip_topk_sel(q, codes, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int, id_base: int = 0,
+                            row_map=None, ws_slots=None, capture_error=None):
+    name = "ivf_sq_fp16_ip_topk_sel"
+    Q, dims, head = _ivf_codes_args(name, torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel(name, sel, dims[0]))
+
+
+def ivf_sq_fp16_ip_range_search_sel(q, codes, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float, max_scan_rows: int,
+                                    id_base: int = 0, row_map=None, ws_slots=None):
+    name = "ivf_sq_fp16_ip_range_search_sel"
+    Q, dims, head = _ivf_codes_args(name, torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel(name, sel, dims[0]))
+
+
+def ivf_sq8_ip_topk_sel(q, codes, trained, qtype: int, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int,
+                        id_base: int = 0, row_map=None, ws_slots=None, capture_error=None):
+    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_topk_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_topk("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_sq8_ip_topk_sel", sel, dims[0]))
+
+
+def ivf_sq8_ip_range_search_sel(q, codes, trained, qtype: int, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float,
+                                max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None):
+    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_range_search_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
+    return _ivf_range("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_sq8_ip_range_search_sel", sel, dims[0]))

@@ -55,10 +55,20 @@ class FaissIndex:
         self.index = index
         self._passage_ids = None if passage_ids is None else torch.as_tensor(np.asarray(passage_ids, dtype=np.int64), device=index.device)
 
-    def search(self, query_embeddings, k: int, **kwargs):
+    def _selector_index(self, what: str):
+        """The wrapped index, if it takes a row selector (the four inverted-file indexes); TypeError otherwise."""
+        if not isinstance(self.index, (IVFFlatIndex, IVFPQIndex, IVFSQIndex, IVFSQ8Index)):
+            raise TypeError(f"FaissIndex.{what}(sel=...): {type(self.index).__name__} takes no row selector (the inverted-file indexes do)")
+        return self.index
+
+    def search(self, query_embeddings, k: int, sel=None, **kwargs):
+        """sel: a RowSelector over the wrapped inverted-file index's rows (faiss SearchParameters(sel=...)): row numbers, not passage ids."""
         n = query_embeddings.shape[0]
         t0 = time.time()
-        scores, ids = self.index.search(query_embeddings, k)
+        if sel is not None:
+            scores, ids = self._selector_index("search").search(query_embeddings, k, sel=sel)
+        else:
+            scores, ids = self.index.search(query_embeddings, k)
         if self._passage_ids is not None:
             ids = torch.where(ids >= 0, self._passage_ids[ids.clamp(min=0)], ids)
         torch.cuda.synchronize(self.index.device)
@@ -74,10 +84,14 @@ class FaissIndex:
             ids = self._passage_ids[ids]
         return lims, scores, ids
 
-    def range_search_probed(self, query_embeddings, radius: float, nprobe: Optional[int] = None):
+    def range_search_probed(self, query_embeddings, radius: float, nprobe: Optional[int] = None, sel=None):
         """-> (lims, D, I) of the wrapped inverted-file index's range_search_probed (IVFFlatIndex, IVFPQIndex, IVFSQIndex, IVFSQ8Index): every
-        row of each query's nprobe best cells with a score > radius, in segment order, I mapped through the passage ids as in range_search."""
-        lims, scores, ids = self.index.range_search_probed(query_embeddings, radius, nprobe)
+        row of each query's nprobe best cells with a score > radius, in segment order, I mapped through the passage ids as in range_search.
+        sel: a RowSelector over the index's rows, as search() takes it."""
+        if sel is not None:
+            lims, scores, ids = self._selector_index("range_search_probed").range_search_probed(query_embeddings, radius, nprobe, sel=sel)
+        else:
+            lims, scores, ids = self.index.range_search_probed(query_embeddings, radius, nprobe)
         if self._passage_ids is not None:
             ids = self._passage_ids[ids]
         return lims, scores, ids

@@ -20,7 +20,9 @@ OPS = ("encode_packed", "rmsnorm", "rope_qkv_gemm", "attn_varlen", "swiglu_gemm"
        "flat_ip_range_search", "sq_fp16_ip_topk", "pq_ip_topk", "binary_topk", "sq8_ip_topk", "impact_topk",
        "sparse_compact_csr", "sq_fp16_ip_range_search", "pq_ip_range_search", "impact_range_search", "linear_transform",
        "flat_ip_rerank", "sq_fp16_ip_rerank", "ivf_flat_ip_topk", "ivf_pq_ip_topk", "ivf_sq_fp16_ip_topk", "ivf_sq8_ip_topk",
-       "ivf_flat_ip_range_search", "ivf_pq_ip_range_search", "ivf_sq_fp16_ip_range_search", "ivf_sq8_ip_range_search")
+       "ivf_flat_ip_range_search", "ivf_pq_ip_range_search", "ivf_sq_fp16_ip_range_search", "ivf_sq8_ip_range_search",
+       "ivf_flat_ip_topk_sel", "ivf_pq_ip_topk_sel", "ivf_sq_fp16_ip_topk_sel", "ivf_sq8_ip_topk_sel",
+       "ivf_flat_ip_range_search_sel", "ivf_pq_ip_range_search_sel", "ivf_sq_fp16_ip_range_search_sel", "ivf_sq8_ip_range_search_sel")
 
 _loaded = False
 
