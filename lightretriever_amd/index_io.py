@@ -163,7 +163,7 @@ from __future__ import annotations
 import csv
 import os
 import struct
-from typing import Iterable, Optional
+from typing import Callable, Iterable, NamedTuple, Optional
 
 import numpy as np
 
@@ -522,16 +522,11 @@ def index_record_end(fname: str, offset: int = 0, end: Optional[int] = None) -> 
     fourcc = peek_index_header(fname, offset, end)[0]
     if fourcc == FOURCC_PRE_TRANSFORM:
         return index_record_end(fname, read_pre_transform(fname, offset, end)[1]["offset"], end)
-    if fourcc == FOURCC_IVF_PQ:
+    if fourcc in _IVF_BASES:
         with open(fname, "rb") as f:
             f.seek(offset)
-            st = _read_ivf_pq_head(f, fname, size - offset)
-        return offset + st["data"] + st["ntotal"] * (st["M"] + 8)
-    if fourcc == FOURCC_IVF_SQ:
-        with open(fname, "rb") as f:
-            f.seek(offset)
-            st = _read_ivf_sq_head(f, fname, size - offset, served="any")
-        return offset + st["data"] + st["ntotal"] * (st["code_size"] + 8)
+            st, _, code_size, data = _read_ivf_head(f, fname, size - offset, _IVF_BASES[fourcc], served="any")
+        return offset + data + st["ntotal"] * (code_size + 8)
     if fourcc not in (FOURCC_FLAT_IP, FOURCC_SQ, FOURCC_PQ):
         raise ValueError(f"{fname}: index record {fourcc!r} at byte {offset} is not served ('IxFI', 'IxSQ', 'IxPq', 'IxPT', 'IwPQ', 'IwSq')")
     with open(fname, "rb") as f:
@@ -597,99 +592,36 @@ def read_refine(fname: str):
 FOURCC_IVF_FLAT = b"IwFl"
 _ILAR, _FULL, _SPRS = b"ilar", b"full", b"sprs"
 
+# ---- the inverted-file records: one preamble, one family-specific middle, one 'ilar' record and the cells, written and read once ----------
 
-def write_ivf_flat(fname: str, centroids: np.ndarray, list_sizes, rows, row_ids, nprobe: int = 1, is_trained: bool = True) -> None:
-    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; rows: the fp32 rows in CELL ORDER, anything whose slice
-    rows[a:b] np.asarray turns into [b - a, d] (read one cell at a time: the index comes off the GPU in pieces); row_ids int64 [ntotal], the
-    original row (faiss's id) of each stored position.  Written as faiss's 'IwFl' record (the layout at the head of this file; faiss is not
-    installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname."""
+
+class _IVFFamily(NamedTuple):
+    """What one inverted-file record has of its own: its fourcc, the words its messages differ in, and the reader of its middle."""
+    fourcc: bytes
+    noun: str          # "truncated <noun> (...)", "too short for an <noun> header", "the flat quantiser of an <noun>"
+    what: str          # _read_header's name for the record
+    middle: Callable   # (take, fname, d, served) -> (the family's fields, code_size, what code_size follows from)
+    sum_tail: str      # closes "the list sizes sum to ..."
+    unfilled: str      # the record's length is not that of its cells
+
+
+def _ivf_write_args(who: str, centroids, list_sizes, row_ids):
+    """The arguments every inverted-file writer takes -> (sizes int64 [nlist], ids <i8 [n], centroids <f4 [nlist or 0, d], d, ntotal)."""
     sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
     nlist, ntotal = sizes.shape[0], int(sizes.sum())
     ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
     cent = np.ascontiguousarray(centroids, dtype="<f4")
     if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
-        raise ValueError(f"write_ivf_flat: centroids {cent.shape} do not match nlist={nlist}")
+        raise ValueError(f"{who}: centroids {cent.shape} do not match nlist={nlist}")
+    return sizes, ids, cent, cent.shape[1], ntotal
+
+
+def _ivf_preamble_bytes(fourcc: bytes, cent: np.ndarray, sizes: np.ndarray, nprobe: int, is_trained: bool) -> bytes:
+    """An inverted-file record up to its family's own fields: index header, nlist, nprobe, the 'IxFI' quantiser, the empty direct map."""
     d = cent.shape[1]
-    if ids.shape[0] != ntotal or (sizes < 0).any():
-        raise ValueError(f"write_ivf_flat: {ids.shape[0]} row ids, the list sizes sum to {ntotal}")
-    head = _index_header(FOURCC_IVF_FLAT, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
-    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
-    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
-    head += _ILAR + struct.pack("<QQ", nlist, 4 * d)
-    non0 = np.flatnonzero(sizes)
-    if len(non0) > nlist // 2:
-        head += _FULL + struct.pack("<Q", nlist) + sizes.astype("<u8").tobytes()
-    else:
-        head += _SPRS + struct.pack("<Q", 2 * len(non0)) + np.stack([non0, sizes[non0]], axis=1).astype("<u8").tobytes()
-    tmp = fname + ".tmp"
-    off = np.concatenate([[0], np.cumsum(sizes)])
-    with open(tmp, "wb") as f:
-        f.write(head)
-        for c in non0:
-            a, b = int(off[c]), int(off[c + 1])
-            block = np.ascontiguousarray(np.asarray(rows[a:b]), dtype="<f4")
-            if block.shape != (b - a, d):
-                raise ValueError(f"write_ivf_flat: rows[{a}:{b}] has shape {block.shape}, expected {(b - a, d)}")
-            f.write(block.tobytes())
-            f.write(ids[a:b].tobytes())
-    os.replace(tmp, fname)
-
-
-def read_ivf_flat(fname: str):
-    """-> dict(d, nlist, nprobe, ntotal, is_trained, centroids fp32 [nlist, d] ([0, d] when untrained), list_off int64 [nlist + 1], rows fp32
-    [ntotal, d] in cell order, row_ids int64 [ntotal]).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
-    size = os.path.getsize(fname)
-    with open(fname, "rb") as f:
-        def take(n: int, what: str) -> bytes:
-            b = f.read(n)
-            if len(b) != n:
-                raise ValueError(f"{fname}: truncated inverted-file index ({what})")
-            return b
-        if size < 2 * _HEADER.size + 16:
-            raise ValueError(f"{fname}: too short for an inverted-file index header")
-        d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_FLAT, "an inverted-file flat index")
-        nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
-        if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
-            raise ValueError(f"{fname}: inconsistent inverted-file index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
-        qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file index")
-        (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
-        if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
-            raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
-        centroids = np.frombuffer(take(4 * n_floats, "centroids"), dtype="<f4").reshape(qn, d)
-        dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
-        if dm_type != 0 or dm_n != 0:
-            raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
-        il = take(4, "inverted lists")
-        if il != _ILAR:
-            raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
-        il_nlist, code_size = struct.unpack("<QQ", take(16, "inverted lists header"))
-        if il_nlist != nlist or code_size != 4 * d:
-            raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={code_size} do not match nlist={nlist}, d={d}")
-        form = take(4, "list sizes")
-        (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
-        sizes = np.zeros(nlist, dtype=np.int64)
-        if form == _FULL:
-            if n_words != nlist:
-                raise ValueError(f"{fname}: {n_words} list sizes for nlist={nlist}")
-            sizes[:] = np.frombuffer(take(8 * nlist, "list sizes"), dtype="<u8")
-        elif form == _SPRS:
-            pairs = np.frombuffer(take(8 * n_words, "list sizes"), dtype="<u8").reshape(-1, 2).astype(np.int64) if n_words % 2 == 0 else None
-            if pairs is None or (pairs[:, 0] >= nlist).any() or len(np.unique(pairs[:, 0])) != len(pairs):
-                raise ValueError(f"{fname}: inconsistent sparse list sizes")
-            sizes[pairs[:, 0]] = pairs[:, 1]
-        else:
-            raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
-        if int(sizes.sum()) != ntotal or f.tell() + ntotal * (4 * d + 8) != size:
-            raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal} (file bytes={size})")
-        rows = np.empty((ntotal, d), dtype=np.float32)
-        row_ids = np.empty(ntotal, dtype=np.int64)
-        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        for c in np.flatnonzero(sizes):
-            a, b = int(list_off[c]), int(list_off[c + 1])
-            rows[a:b] = np.frombuffer(take((b - a) * 4 * d, "rows"), dtype="<f4").reshape(b - a, d)
-            row_ids[a:b] = np.frombuffer(take((b - a) * 8, "ids"), dtype="<i8")
-    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), centroids=centroids, list_off=list_off, rows=rows,
-                row_ids=row_ids)
+    return (_index_header(fourcc, d, int(sizes.sum()), is_trained) + struct.pack("<QQ", sizes.shape[0], int(nprobe))
+            + _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
+            + struct.pack("<BQ", 0, 0))                                # direct map: NoMap, empty array
 
 
 def _list_sizes_bytes(sizes: np.ndarray) -> bytes:
@@ -701,32 +633,14 @@ def _list_sizes_bytes(sizes: np.ndarray) -> bytes:
     return _SPRS + struct.pack("<Q", 2 * len(non0)) + np.stack([non0, sizes[non0]], axis=1).astype("<u8").tobytes()
 
 
-def write_ivf_pq(fname: str, centroids: np.ndarray, pq_centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True,
-                 is_trained: bool = True, prefix: bytes = b"", append: bool = False) -> None:
-    """centroids fp32 [nlist, d] ([0, d] when untrained); pq_centroids fp32 [M, 256, d / M]; list_sizes [nlist]; codes uint8 [ntotal, M]
-    row-major in CELL ORDER; row_ids int64 [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwPQ' record
-    (the layout at the head of this file; faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as
-    fname.tmp and renamed over fname; `prefix` / `append` as in _write_index (the enclosing record of write_refine)."""
-    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
-    nlist, ntotal = sizes.shape[0], int(sizes.sum())
-    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
-    cent = np.ascontiguousarray(centroids, dtype="<f4")
-    pqc = np.ascontiguousarray(pq_centroids, dtype="<f4")
-    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
-        raise ValueError(f"write_ivf_pq: centroids {cent.shape} do not match nlist={nlist}")
-    d = cent.shape[1]
-    if pqc.ndim != 3 or pqc.shape[1] != 256 or pqc.shape[0] * pqc.shape[2] != d:
-        raise ValueError(f"write_ivf_pq: codebooks {pqc.shape} are not [M, 256, d / M] for d={d}")
-    M = pqc.shape[0]
-    codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    if ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, M):
-        raise ValueError(f"write_ivf_pq: {ids.shape[0]} row ids and codes {codes.shape}, the list sizes sum to {ntotal} (M={M})")
-    head = _index_header(FOURCC_IVF_PQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
-    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
-    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
-    head += struct.pack("<BQ", int(bool(by_residual)), M)              # by_residual, code_size
-    head += _PQ.pack(d, M, 8) + struct.pack("<Q", pqc.size) + pqc.tobytes()
-    head += _ILAR + struct.pack("<QQ", nlist, M) + _list_sizes_bytes(sizes)
+def _ilar_bytes(sizes: np.ndarray, code_size: int) -> bytes:
+    return _ILAR + struct.pack("<QQ", sizes.shape[0], code_size) + _list_sizes_bytes(sizes)
+
+
+def _write_ivf_cells(fname: str, head: bytes, sizes: np.ndarray, cell_bytes, ids: np.ndarray, prefix: bytes = b"", append: bool = False) -> None:
+    """`prefix`, `head` (the record up to and including its list sizes), then for every non-empty cell the bytes of its rows --
+    cell_bytes(a, b) for the stored positions [a, b), called one cell at a time -- and its ids; to a .tmp file renamed over fname, or
+    (`append`) continuing the existing file fname, as in _write_index."""
     tmp = fname if append else fname + ".tmp"
     off = np.concatenate([[0], np.cumsum(sizes)])
     with open(tmp, "ab" if append else "wb") as f:
@@ -734,29 +648,21 @@ def write_ivf_pq(fname: str, centroids: np.ndarray, pq_centroids: np.ndarray, li
         f.write(head)
         for c in np.flatnonzero(sizes):
             a, b = int(off[c]), int(off[c + 1])
-            f.write(codes[a:b].tobytes())
+            f.write(cell_bytes(a, b))
             f.write(ids[a:b].tobytes())
     if not append:
         os.replace(tmp, fname)
 
 
-def _read_ivf_pq_head(f, fname: str, size: int):
-    """An 'IwPQ' record from the file position up to its list sizes (`size`: the bytes the record may fill) -> dict(d, nlist, nprobe, ntotal,
-    is_trained, by_residual, M, centroids, pq_centroids, sizes, data: the record's bytes before the first cell's codes)."""
-    start = f.tell()
-
-    def take(n: int, what: str) -> bytes:
-        b = f.read(n) if f.tell() - start + n <= size else b""
-        if len(b) != n:
-            raise ValueError(f"{fname}: truncated inverted-file PQ index ({what})")
-        return b
+def _read_ivf_preamble(f, take, fname: str, size: int, fam: _IVFFamily):
+    """An inverted-file record from its index header through its direct map -> (d, ntotal, is_trained, nlist, nprobe, centroids)."""
     if size < 2 * _HEADER.size + 16:
-        raise ValueError(f"{fname}: too short for an inverted-file PQ index header")
-    d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_PQ, "an inverted-file product-quantiser index")
+        raise ValueError(f"{fname}: too short for an {fam.noun} header")
+    d, ntotal, is_trained, metric = _read_header(f, fname, fam.fourcc, fam.what)
     nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
     if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
-        raise ValueError(f"{fname}: inconsistent inverted-file PQ index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
-    qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file PQ index")
+        raise ValueError(f"{fname}: inconsistent {fam.noun} header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
+    qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, f"the flat quantiser of an {fam.noun}")
     (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
     if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
         raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
@@ -764,20 +670,18 @@ def _read_ivf_pq_head(f, fname: str, size: int):
     dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
     if dm_type != 0 or dm_n != 0:
         raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
-    by_residual, code_size = struct.unpack("<BQ", take(9, "by_residual, code_size"))
-    pq_d, M, nbits = _PQ.unpack(take(_PQ.size, "product quantiser"))
-    if nbits != 8:
-        raise ValueError(f"{fname}: ProductQuantizer nbits={nbits} is not served (only 8)")
-    (n_c,) = struct.unpack("<Q", take(8, "codebook size"))
-    if pq_d != d or M <= 0 or d % M or code_size != M or n_c != d * 256 or by_residual not in (0, 1):
-        raise ValueError(f"{fname}: inconsistent IndexIVFPQ quantiser (pq.d={pq_d}, M={M}, code_size={code_size}, floats={n_c}, by_residual={by_residual}; d={d})")
-    pq_centroids = np.frombuffer(take(4 * n_c, "codebooks"), dtype="<f4").reshape(M, 256, d // M)
+    return d, ntotal, is_trained, nlist, nprobe, centroids
+
+
+def _read_ilar(take, fname: str, nlist: int, ntotal: int, code_size: int, versus: str, sum_tail: str = "") -> np.ndarray:
+    """The 'ilar' record up to its list sizes, 'full' or 'sprs' -> sizes int64 [nlist], which sum to ntotal.  versus: what code_size follows
+    from, for the message ("d=32", "M=8")."""
     il = take(4, "inverted lists")
     if il != _ILAR:
         raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
     il_nlist, il_code = struct.unpack("<QQ", take(16, "inverted lists header"))
-    if il_nlist != nlist or il_code != M:
-        raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, M={M}")
+    if il_nlist != nlist or il_code != code_size:
+        raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, {versus}")
     form = take(4, "list sizes")
     (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
     sizes = np.zeros(nlist, dtype=np.int64)
@@ -793,94 +697,40 @@ def _read_ivf_pq_head(f, fname: str, size: int):
     else:
         raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
     if int(sizes.sum()) != ntotal:
-        raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}")
-    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), by_residual=bool(by_residual), M=int(M),
-                centroids=centroids, pq_centroids=pq_centroids, sizes=sizes, data=f.tell() - start)
+        raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}{sum_tail}")
+    return sizes
 
 
-def read_ivf_pq(fname: str, offset: int = 0, end: Optional[int] = None):
-    """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, M, centroids fp32 [nlist, d] ([0, d] when untrained), pq_centroids fp32
-    [M, 256, d / M], list_off int64 [nlist + 1], codes uint8 [ntotal, M] in cell order, row_ids int64 [ntotal]).  offset: where the record starts;
-    it runs to `end` (default: the end of the file).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
-    size = _end(fname, end) - offset
-    with open(fname, "rb") as f:
-        f.seek(offset)
-        st = _read_ivf_pq_head(f, fname, size)
-        ntotal, M, sizes = st["ntotal"], st["M"], st.pop("sizes")
-        if st.pop("data") + ntotal * (M + 8) != size:
-            raise ValueError(f"{fname}: {ntotal} rows of {M} + 8 bytes do not fill the record (bytes={size})")
-        codes = np.empty((ntotal, M), dtype=np.uint8)
-        row_ids = np.empty(ntotal, dtype=np.int64)
-        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        for c in np.flatnonzero(sizes):
-            a, b = int(list_off[c]), int(list_off[c + 1])
-            codes[a:b] = np.frombuffer(f.read((b - a) * M), dtype=np.uint8).reshape(b - a, M)
-            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
-    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
-    return st
+def _read_ivf_cells(f, sizes: np.ndarray, dtype, width: int):
+    """The cells from the file position, one read per cell -> (list_off int64 [nlist + 1], rows `dtype` [ntotal, width] in cell order,
+    row_ids int64 [ntotal])."""
+    dtype = np.dtype(dtype)
+    list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    rows = np.empty((int(list_off[-1]), width), dtype=dtype.newbyteorder("="))
+    row_ids = np.empty(int(list_off[-1]), dtype=np.int64)
+    for c in np.flatnonzero(sizes):
+        a, b = int(list_off[c]), int(list_off[c + 1])
+        rows[a:b] = np.frombuffer(f.read((b - a) * width * dtype.itemsize), dtype=dtype).reshape(b - a, width)
+        row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
+    return list_off, rows, row_ids
 
 
-def write_ivf_sq(fname: str, centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True, is_trained: bool = True,
-                 prefix: bytes = b"", append: bool = False) -> None:
-    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; codes fp16 [ntotal, d] row-major in CELL ORDER; row_ids int64
-    [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwSq' record (the layout at the head of this file;
-    faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname; `prefix` /
-    `append` as in _write_index (the enclosing record of write_refine)."""
-    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
-    nlist, ntotal = sizes.shape[0], int(sizes.sum())
-    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
-    cent = np.ascontiguousarray(centroids, dtype="<f4")
-    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
-        raise ValueError(f"write_ivf_sq: centroids {cent.shape} do not match nlist={nlist}")
-    d = cent.shape[1]
-    codes = np.asarray(codes)
-    if codes.dtype != np.float16 or ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, d):
-        raise ValueError(f"write_ivf_sq: {ids.shape[0]} row ids and codes {codes.dtype} {codes.shape}, the list sizes sum to {ntotal} (fp16, d={d})")
-    codes = np.ascontiguousarray(codes, dtype="<f2")
-    head = _index_header(FOURCC_IVF_SQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
-    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
-    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
-    head += _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<Q", 0)  # the ScalarQuantizer, its empty `trained`
-    head += struct.pack("<QB", 2 * d, int(bool(by_residual)))          # code_size, by_residual
-    head += _ILAR + struct.pack("<QQ", nlist, 2 * d) + _list_sizes_bytes(sizes)
-    tmp = fname if append else fname + ".tmp"
-    off = np.concatenate([[0], np.cumsum(sizes)])
-    with open(tmp, "ab" if append else "wb") as f:
-        f.write(prefix)
-        f.write(head)
-        for c in np.flatnonzero(sizes):
-            a, b = int(off[c]), int(off[c + 1])
-            f.write(codes[a:b].tobytes())
-            f.write(ids[a:b].tobytes())
-    if not append:
-        os.replace(tmp, fname)
+def _read_ivf_pq_middle(take, fname: str, d: int, served):
+    """'IwPQ' between the direct map and 'ilar': by_residual, code_size, the ProductQuantizer."""
+    by_residual, code_size = struct.unpack("<BQ", take(9, "by_residual, code_size"))
+    pq_d, M, nbits = _PQ.unpack(take(_PQ.size, "product quantiser"))
+    if nbits != 8:
+        raise ValueError(f"{fname}: ProductQuantizer nbits={nbits} is not served (only 8)")
+    (n_c,) = struct.unpack("<Q", take(8, "codebook size"))
+    if pq_d != d or M <= 0 or d % M or code_size != M or n_c != d * 256 or by_residual not in (0, 1):
+        raise ValueError(f"{fname}: inconsistent IndexIVFPQ quantiser (pq.d={pq_d}, M={M}, code_size={code_size}, floats={n_c}, by_residual={by_residual}; d={d})")
+    pq_centroids = np.frombuffer(take(4 * n_c, "codebooks"), dtype="<f4").reshape(M, 256, d // M)
+    return dict(by_residual=bool(by_residual), M=int(M), pq_centroids=pq_centroids), int(M), f"M={M}"
 
 
-def _read_ivf_sq_head(f, fname: str, size: int, served: str = "fp16"):
-    """An 'IwSq' record from the file position up to its list sizes (`size`: the bytes the record may fill) -> dict(d, nlist, nprobe, ntotal,
-    is_trained, by_residual, qtype, trained, code_size, centroids, sizes, data: the record's bytes before the first cell's codes).  served:
-    "fp16" (read_ivf_sq: QT_fp16 alone), "8bit" (read_ivf_sq8: QT_8bit / QT_8bit_uniform) or "any" (index_record_end: the three of them)."""
-    start = f.tell()
-
-    def take(n: int, what: str) -> bytes:
-        b = f.read(n) if f.tell() - start + n <= size else b""
-        if len(b) != n:
-            raise ValueError(f"{fname}: truncated inverted-file scalar-quantiser index ({what})")
-        return b
-    if size < 2 * _HEADER.size + 16:
-        raise ValueError(f"{fname}: too short for an inverted-file scalar-quantiser index header")
-    d, ntotal, is_trained, metric = _read_header(f, fname, FOURCC_IVF_SQ, "an inverted-file scalar-quantiser index")
-    nlist, nprobe = struct.unpack("<QQ", take(16, "nlist, nprobe"))
-    if metric != 0 or d <= 0 or ntotal < 0 or nlist < 1:
-        raise ValueError(f"{fname}: inconsistent inverted-file scalar-quantiser index header (d={d}, ntotal={ntotal}, nlist={nlist}, metric={metric})")
-    qd, qn, _, qmetric = _read_header(f, fname, FOURCC_FLAT_IP, "the flat quantiser of an inverted-file scalar-quantiser index")
-    (n_floats,) = struct.unpack("<Q", take(8, "quantiser size"))
-    if qd != d or qn not in (0, nlist) or n_floats != qn * d or qmetric != 0:
-        raise ValueError(f"{fname}: the quantiser (d={qd}, ntotal={qn}, floats={n_floats}) does not match d={d}, nlist={nlist}")
-    centroids = np.frombuffer(take(4 * n_floats, "centroids"), dtype="<f4").reshape(qn, d)
-    dm_type, dm_n = struct.unpack("<BQ", take(9, "direct map"))
-    if dm_type != 0 or dm_n != 0:
-        raise ValueError(f"{fname}: direct map type {dm_type} with {dm_n} entries is not served (only NoMap)")
+def _read_ivf_sq_middle(take, fname: str, d: int, served: str):
+    """'IwSq' between the direct map and 'ilar': the ScalarQuantizer, `trained`, code_size, by_residual.  served: "fp16" (read_ivf_sq: QT_fp16
+    alone), "8bit" (read_ivf_sq8: QT_8bit / QT_8bit_uniform) or "any" (index_record_end: the three of them)."""
     qtype, _, _, sq_d, sq_code = _SQ.unpack(take(_SQ.size, "scalar quantiser"))
     if served == "8bit" and qtype == QT_FP16:
         raise ValueError(f"{fname}: ScalarQuantizer qtype {qtype} (QT_fp16) is not an 8-bit record: read it with read_ivf_sq (IVFSQIndex)")
@@ -899,53 +749,121 @@ def _read_ivf_sq_head(f, fname: str, size: int, served: str = "fp16"):
     if code_size != want_code or by_residual not in (0, 1):
         raise ValueError(f"{fname}: inconsistent IndexIVFScalarQuantizer quantiser (sq.d={sq_d}, sq.code_size={sq_code}, trained={n_trained}, "
                          f"code_size={code_size}, by_residual={by_residual}; d={d})")
-    il = take(4, "inverted lists")
-    if il != _ILAR:
-        raise ValueError(f"{fname}: inverted lists {il!r} are not served (only {_ILAR.decode()!r})")
-    il_nlist, il_code = struct.unpack("<QQ", take(16, "inverted lists header"))
-    if il_nlist != nlist or il_code != want_code:
-        raise ValueError(f"{fname}: inverted lists of nlist={il_nlist}, code_size={il_code} do not match nlist={nlist}, d={d}")
-    form = take(4, "list sizes")
-    (n_words,) = struct.unpack("<Q", take(8, "list sizes"))
-    sizes = np.zeros(nlist, dtype=np.int64)
-    if form == _FULL:
-        if n_words != nlist:
-            raise ValueError(f"{fname}: {n_words} list sizes for nlist={nlist}")
-        sizes[:] = np.frombuffer(take(8 * nlist, "list sizes"), dtype="<u8")
-    elif form == _SPRS:
-        pairs = np.frombuffer(take(8 * n_words, "list sizes"), dtype="<u8").reshape(-1, 2).astype(np.int64) if n_words % 2 == 0 else None
-        if pairs is None or (pairs[:, 0] >= nlist).any() or len(np.unique(pairs[:, 0])) != len(pairs):
-            raise ValueError(f"{fname}: inconsistent sparse list sizes")
-        sizes[pairs[:, 0]] = pairs[:, 1]
-    else:
-        raise ValueError(f"{fname}: list-size form {form!r} is not served (only {_FULL.decode()!r} and {_SPRS.decode()!r})")
-    if int(sizes.sum()) != ntotal:
-        raise ValueError(f"{fname}: the list sizes sum to {int(sizes.sum())}, the header says ntotal={ntotal}")
-    return dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), by_residual=bool(by_residual),
-                qtype=int(qtype), trained=trained, code_size=int(want_code), centroids=centroids, sizes=sizes, data=f.tell() - start)
+    return dict(by_residual=bool(by_residual), qtype=int(qtype), trained=trained), int(want_code), f"d={d}"
+
+
+_ROWS_UNFILLED = "{fname}: {ntotal} rows of {code_size} + 8 bytes do not fill the record (bytes={size})"
+_IVF_FLAT = _IVFFamily(FOURCC_IVF_FLAT, "inverted-file index", "an inverted-file flat index", lambda take, fname, d, served: ({}, 4 * d, f"d={d}"),
+                       " (file bytes={size})", "{fname}: the list sizes sum to {ntotal}, the header says ntotal={ntotal} (file bytes={size})")
+_IVF_PQ = _IVFFamily(FOURCC_IVF_PQ, "inverted-file PQ index", "an inverted-file product-quantiser index", _read_ivf_pq_middle, "", _ROWS_UNFILLED)
+_IVF_SQ = _IVFFamily(FOURCC_IVF_SQ, "inverted-file scalar-quantiser index", "an inverted-file scalar-quantiser index", _read_ivf_sq_middle, "",
+                     _ROWS_UNFILLED)
+_IVF_BASES = {fam.fourcc: fam for fam in (_IVF_PQ, _IVF_SQ)}      # the records index_record_end knows: a refine index can hold them as its base
+
+
+def _read_ivf_head(f, fname: str, size: int, fam: _IVFFamily, served: Optional[str] = None):
+    """An inverted-file record from the file position up to its list sizes (`size`: the bytes the record may fill) -> (dict(d, nlist, nprobe,
+    ntotal, is_trained, the family's fields, centroids), sizes, code_size, the record's bytes before the first cell's rows)."""
+    start = f.tell()
+
+    def take(n: int, what: str) -> bytes:
+        b = f.read(n) if f.tell() - start + n <= size else b""
+        if len(b) != n:
+            raise ValueError(f"{fname}: truncated {fam.noun} ({what})")
+        return b
+    d, ntotal, is_trained, nlist, nprobe, centroids = _read_ivf_preamble(f, take, fname, size, fam)
+    fields, code_size, versus = fam.middle(take, fname, d, served)
+    sizes = _read_ilar(take, fname, nlist, ntotal, code_size, versus, fam.sum_tail.format(size=size))
+    st = dict(d=d, nlist=int(nlist), nprobe=int(nprobe), ntotal=ntotal, is_trained=bool(is_trained), **fields, centroids=centroids)
+    return st, sizes, code_size, f.tell() - start
+
+
+def _read_ivf(fname: str, fam: _IVFFamily, dtype, rows_key: str, offset: int = 0, end: Optional[int] = None, served: Optional[str] = None) -> dict:
+    """The record at [offset, end) (default: to the end of the file), which it must fill exactly -> _read_ivf_head's dict with list_off, the
+    rows (`dtype`, under rows_key) and row_ids of _read_ivf_cells."""
+    size = _end(fname, end) - offset
+    with open(fname, "rb") as f:
+        f.seek(offset)
+        st, sizes, code_size, data = _read_ivf_head(f, fname, size, fam, served)
+        if data + st["ntotal"] * (code_size + 8) != size:
+            raise ValueError(fam.unfilled.format(fname=fname, ntotal=st["ntotal"], code_size=code_size, size=size))
+        st["list_off"], st[rows_key], st["row_ids"] = _read_ivf_cells(f, sizes, dtype, code_size // np.dtype(dtype).itemsize)
+    return st
+
+
+def write_ivf_flat(fname: str, centroids: np.ndarray, list_sizes, rows, row_ids, nprobe: int = 1, is_trained: bool = True) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; rows: the fp32 rows in CELL ORDER, anything whose slice
+    rows[a:b] np.asarray turns into [b - a, d] (read one cell at a time: the index comes off the GPU in pieces); row_ids int64 [ntotal], the
+    original row (faiss's id) of each stored position.  Written as faiss's 'IwFl' record (the layout at the head of this file; faiss is not
+    installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname."""
+    sizes, ids, cent, d, ntotal = _ivf_write_args("write_ivf_flat", centroids, list_sizes, row_ids)
+    if ids.shape[0] != ntotal or (sizes < 0).any():
+        raise ValueError(f"write_ivf_flat: {ids.shape[0]} row ids, the list sizes sum to {ntotal}")
+
+    def cell_bytes(a: int, b: int) -> bytes:
+        block = np.ascontiguousarray(np.asarray(rows[a:b]), dtype="<f4")
+        if block.shape != (b - a, d):
+            raise ValueError(f"write_ivf_flat: rows[{a}:{b}] has shape {block.shape}, expected {(b - a, d)}")
+        return block.tobytes()
+    _write_ivf_cells(fname, _ivf_preamble_bytes(FOURCC_IVF_FLAT, cent, sizes, nprobe, is_trained) + _ilar_bytes(sizes, 4 * d), sizes, cell_bytes, ids)
+
+
+def read_ivf_flat(fname: str):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, centroids fp32 [nlist, d] ([0, d] when untrained), list_off int64 [nlist + 1], rows fp32
+    [ntotal, d] in cell order, row_ids int64 [ntotal]).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
+    return _read_ivf(fname, _IVF_FLAT, "<f4", "rows")
+
+
+def write_ivf_pq(fname: str, centroids: np.ndarray, pq_centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True,
+                 is_trained: bool = True, prefix: bytes = b"", append: bool = False) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); pq_centroids fp32 [M, 256, d / M]; list_sizes [nlist]; codes uint8 [ntotal, M]
+    row-major in CELL ORDER; row_ids int64 [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwPQ' record
+    (the layout at the head of this file; faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as
+    fname.tmp and renamed over fname; `prefix` / `append` as in _write_index (the enclosing record of write_refine)."""
+    sizes, ids, cent, d, ntotal = _ivf_write_args("write_ivf_pq", centroids, list_sizes, row_ids)
+    pqc = np.ascontiguousarray(pq_centroids, dtype="<f4")
+    if pqc.ndim != 3 or pqc.shape[1] != 256 or pqc.shape[0] * pqc.shape[2] != d:
+        raise ValueError(f"write_ivf_pq: codebooks {pqc.shape} are not [M, 256, d / M] for d={d}")
+    M = pqc.shape[0]
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    if ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, M):
+        raise ValueError(f"write_ivf_pq: {ids.shape[0]} row ids and codes {codes.shape}, the list sizes sum to {ntotal} (M={M})")
+    head = _ivf_preamble_bytes(FOURCC_IVF_PQ, cent, sizes, nprobe, is_trained)
+    head += struct.pack("<BQ", int(bool(by_residual)), M)              # by_residual, code_size
+    head += _PQ.pack(d, M, 8) + struct.pack("<Q", pqc.size) + pqc.tobytes()
+    _write_ivf_cells(fname, head + _ilar_bytes(sizes, M), sizes, lambda a, b: codes[a:b].tobytes(), ids, prefix, append)
+
+
+def read_ivf_pq(fname: str, offset: int = 0, end: Optional[int] = None):
+    """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, M, centroids fp32 [nlist, d] ([0, d] when untrained), pq_centroids fp32
+    [M, 256, d / M], list_off int64 [nlist + 1], codes uint8 [ntotal, M] in cell order, row_ids int64 [ntotal]).  offset: where the record starts;
+    it runs to `end` (default: the end of the file).  Both list-size forms ('full', 'sprs') are read; anything else is refused by name."""
+    return _read_ivf(fname, _IVF_PQ, np.uint8, "codes", offset, end)
+
+
+def write_ivf_sq(fname: str, centroids: np.ndarray, list_sizes, codes, row_ids, nprobe: int = 1, by_residual: bool = True, is_trained: bool = True,
+                 prefix: bytes = b"", append: bool = False) -> None:
+    """centroids fp32 [nlist, d] ([0, d] when untrained); list_sizes [nlist]; codes fp16 [ntotal, d] row-major in CELL ORDER; row_ids int64
+    [ntotal], the original row (faiss's id) of each stored position.  Written as faiss's 'IwSq' record (the layout at the head of this file;
+    faiss is not installed here, so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname; `prefix` /
+    `append` as in _write_index (the enclosing record of write_refine)."""
+    sizes, ids, cent, d, ntotal = _ivf_write_args("write_ivf_sq", centroids, list_sizes, row_ids)
+    codes = np.asarray(codes)
+    if codes.dtype != np.float16 or ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, d):
+        raise ValueError(f"write_ivf_sq: {ids.shape[0]} row ids and codes {codes.dtype} {codes.shape}, the list sizes sum to {ntotal} (fp16, d={d})")
+    codes = np.ascontiguousarray(codes, dtype="<f2")
+    head = _ivf_preamble_bytes(FOURCC_IVF_SQ, cent, sizes, nprobe, is_trained)
+    head += _SQ.pack(QT_FP16, 0, 0.0, d, 2 * d) + struct.pack("<Q", 0)  # the ScalarQuantizer, its empty `trained`
+    head += struct.pack("<QB", 2 * d, int(bool(by_residual)))          # code_size, by_residual
+    _write_ivf_cells(fname, head + _ilar_bytes(sizes, 2 * d), sizes, lambda a, b: codes[a:b].tobytes(), ids, prefix, append)
 
 
 def read_ivf_sq(fname: str, offset: int = 0, end: Optional[int] = None):
     """-> dict(d, nlist, nprobe, ntotal, is_trained, by_residual, centroids fp32 [nlist, d] ([0, d] when untrained), list_off int64 [nlist + 1],
     codes fp16 [ntotal, d] in cell order, row_ids int64 [ntotal]).  offset: where the record starts; it runs to `end` (default: the end of the
     file).  Both list-size forms ('full', 'sprs') are read; another qtype, a direct map and other inverted lists are refused by name."""
-    size = _end(fname, end) - offset
-    with open(fname, "rb") as f:
-        f.seek(offset)
-        st = _read_ivf_sq_head(f, fname, size)
-        ntotal, d, sizes = st["ntotal"], st["d"], st.pop("sizes")
-        for key in ("qtype", "trained", "code_size"):
-            st.pop(key)
-        if st.pop("data") + ntotal * (2 * d + 8) != size:
-            raise ValueError(f"{fname}: {ntotal} rows of {2 * d} + 8 bytes do not fill the record (bytes={size})")
-        codes = np.empty((ntotal, d), dtype=np.float16)
-        row_ids = np.empty(ntotal, dtype=np.int64)
-        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        for c in np.flatnonzero(sizes):
-            a, b = int(list_off[c]), int(list_off[c + 1])
-            codes[a:b] = np.frombuffer(f.read((b - a) * 2 * d), dtype="<f2").reshape(b - a, d)
-            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
-    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
+    st = _read_ivf(fname, _IVF_SQ, "<f2", "codes", offset, end, served="fp16")
+    del st["qtype"], st["trained"]
     return st
 
 
@@ -955,13 +873,7 @@ def write_ivf_sq8(fname: str, centroids: np.ndarray, trained: np.ndarray, qtype:
     list_sizes [nlist]; codes uint8 [ntotal, d] row-major in CELL ORDER; row_ids int64 [ntotal], the original row (faiss's id) of each stored
     position.  Written as faiss's 'IwSq' record with an 8-bit ScalarQuantizer (the layout at the head of this file; faiss is not installed here,
     so the bytes are unverified against a Faiss build).  Built as fname.tmp and renamed over fname; `prefix` / `append` as in _write_index."""
-    sizes = np.asarray(list_sizes, dtype=np.int64).reshape(-1)
-    nlist, ntotal = sizes.shape[0], int(sizes.sum())
-    ids = np.ascontiguousarray(row_ids, dtype="<i8").reshape(-1)
-    cent = np.ascontiguousarray(centroids, dtype="<f4")
-    if cent.ndim != 2 or cent.shape[0] not in (0, nlist) or nlist < 1:
-        raise ValueError(f"write_ivf_sq8: centroids {cent.shape} do not match nlist={nlist}")
-    d = cent.shape[1]
+    sizes, ids, cent, d, ntotal = _ivf_write_args("write_ivf_sq8", centroids, list_sizes, row_ids)
     t = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
     if t.size != _sq8_trained_len(qtype, d):
         raise ValueError(f"write_ivf_sq8: {t.size} trained floats, expected {_sq8_trained_len(qtype, d)}")
@@ -969,23 +881,10 @@ def write_ivf_sq8(fname: str, centroids: np.ndarray, trained: np.ndarray, qtype:
     if codes.dtype != np.uint8 or ids.shape[0] != ntotal or (sizes < 0).any() or codes.shape != (ntotal, d):
         raise ValueError(f"write_ivf_sq8: {ids.shape[0]} row ids and codes {codes.dtype} {codes.shape}, the list sizes sum to {ntotal} (uint8, d={d})")
     codes = np.ascontiguousarray(codes)
-    head = _index_header(FOURCC_IVF_SQ, d, ntotal, is_trained) + struct.pack("<QQ", nlist, int(nprobe))
-    head += _index_header(FOURCC_FLAT_IP, d, cent.shape[0]) + struct.pack("<Q", cent.size) + cent.tobytes()
-    head += struct.pack("<BQ", 0, 0)                                   # direct map: NoMap, empty array
+    head = _ivf_preamble_bytes(FOURCC_IVF_SQ, cent, sizes, nprobe, is_trained)
     head += _SQ.pack(qtype, 0, 0.0, d, d) + struct.pack("<Q", t.size) + t.tobytes()   # the ScalarQuantizer and its `trained`
     head += struct.pack("<QB", d, int(bool(by_residual)))              # code_size, by_residual
-    head += _ILAR + struct.pack("<QQ", nlist, d) + _list_sizes_bytes(sizes)
-    tmp = fname if append else fname + ".tmp"
-    off = np.concatenate([[0], np.cumsum(sizes)])
-    with open(tmp, "ab" if append else "wb") as f:
-        f.write(prefix)
-        f.write(head)
-        for c in np.flatnonzero(sizes):
-            a, b = int(off[c]), int(off[c + 1])
-            f.write(codes[a:b].tobytes())
-            f.write(ids[a:b].tobytes())
-    if not append:
-        os.replace(tmp, fname)
+    _write_ivf_cells(fname, head + _ilar_bytes(sizes, d), sizes, lambda a, b: codes[a:b].tobytes(), ids, prefix, append)
 
 
 def read_ivf_sq8(fname: str, offset: int = 0, end: Optional[int] = None):
@@ -993,23 +892,7 @@ def read_ivf_sq8(fname: str, offset: int = 0, end: Optional[int] = None):
     untrained), list_off int64 [nlist + 1], codes uint8 [ntotal, d] in cell order, row_ids int64 [ntotal]).  offset: where the record starts; it
     runs to `end` (default: the end of the file).  Both list-size forms ('full', 'sprs') are read; another qtype (QT_fp16 = 4: that record is
     read_ivf_sq's), a direct map and other inverted lists are refused by name."""
-    size = _end(fname, end) - offset
-    with open(fname, "rb") as f:
-        f.seek(offset)
-        st = _read_ivf_sq_head(f, fname, size, served="8bit")
-        ntotal, d, sizes = st["ntotal"], st["d"], st.pop("sizes")
-        st.pop("code_size")
-        if st.pop("data") + ntotal * (d + 8) != size:
-            raise ValueError(f"{fname}: {ntotal} rows of {d} + 8 bytes do not fill the record (bytes={size})")
-        codes = np.empty((ntotal, d), dtype=np.uint8)
-        row_ids = np.empty(ntotal, dtype=np.int64)
-        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        for c in np.flatnonzero(sizes):
-            a, b = int(list_off[c]), int(list_off[c + 1])
-            codes[a:b] = np.frombuffer(f.read((b - a) * d), dtype=np.uint8).reshape(b - a, d)
-            row_ids[a:b] = np.frombuffer(f.read((b - a) * 8), dtype="<i8")
-    st.update(list_off=list_off, codes=codes, row_ids=row_ids)
-    return st
+    return _read_ivf(fname, _IVF_SQ, np.uint8, "codes", offset, end, served="8bit")
 
 
 def ivf_sq_qtype(fname: str, offset: int = 0, end: Optional[int] = None) -> int:

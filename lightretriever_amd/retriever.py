@@ -327,6 +327,12 @@ class FlatIPFaissSearch(DenseRetrievalFaissSearch):
         return "flat_faiss_index"
 
 
+def _inner_product_only(who: str, similarity_metric) -> None:
+    """The refusal of every searcher that takes a similarity_metric: only inner product is served."""
+    if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
+        raise NotImplementedError(f"{who}: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+
+
 class SQFaissSearch(FlatIPFaissSearch):
     """faiss_search.py:567-611: IndexScalarQuantizer(d, quantizer_type, METRIC_INNER_PRODUCT).  "QT_fp16" (the default) is served by
     SQFp16Index -- 2 B/element resident, exact inner products of the fp32 query with the decoded codes -- and "QT_8bit_uniform" by SQ8Index:
@@ -344,8 +350,7 @@ class SQFaissSearch(FlatIPFaissSearch):
                  **kwargs):
         if quantizer_type not in ("QT_fp16", "QT_8bit_uniform"):
             raise NotImplementedError(f"SQFaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_fp16' and 'QT_8bit_uniform')")
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"SQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        _inner_product_only("SQFaissSearch", similarity_metric)
         super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
         self.similarity_metric = 0
         self.qname = quantizer_type
@@ -387,8 +392,7 @@ class PQFaissSearch(FlatIPFaissSearch):
                  similarity_metric=0, use_rotation: bool = False, **kwargs):
         if use_rotation:
             raise NotImplementedError("PQFaissSearch: use_rotation (OPQ) is not served")
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"PQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        _inner_product_only("PQFaissSearch", similarity_metric)
         if code_size != 8:
             raise NotImplementedError(f"PQFaissSearch: code_size (nbits) {code_size} is not served (only 8)")
         super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
@@ -508,7 +512,37 @@ class PCAFaissSearch(FlatIPFaissSearch):
         return "pca_faiss_index"
 
 
-class IVFPQFaissSearch(FlatIPFaissSearch):
+class _IVFFaissSearch(FlatIPFaissSearch):
+    """What the four inverted-file searchers share: nlist / nprobe and their refusal, the clamp of both to a chunk, training on the chunk
+    before its rows are added, and a load() that takes the parameters back from the file.  A subclass refuses the metric and its own
+    arguments first, then hands nlist / nprobe to this constructor."""
+    serves_rpc_shards = False
+    loaded: dict = {}                # load(): attribute of the searcher <- attribute of the loaded index, besides nlist and nprobe
+
+    def __init__(self, model, batch_size, corpus_chunk_size, nlist: int, nprobe: int, **kwargs):
+        if nlist < 1 or nprobe < 1:
+            raise ValueError(f"{type(self).__name__}: nlist={nlist} and nprobe={nprobe} must be >= 1")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.nlist, self.nprobe = int(nlist), int(nprobe)
+        self.similarity_metric = 0
+
+    def _cells(self, capacity: int):
+        """-> (nlist, nprobe) of a shard of `capacity` rows."""
+        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
+        return nlist, min(self.nprobe, nlist, 2048)
+
+    def _train(self, idx, corpus_emb):
+        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        idx = self.faiss_index.index
+        self.nlist, self.nprobe = idx.nlist, idx.nprobe
+        for mine, theirs in self.loaded.items():
+            setattr(self, mine, getattr(idx, theirs))
+
+
+class IVFPQFaissSearch(_IVFFaissSearch):
     """faiss IndexIVFPQ(IndexFlatIP(d), d, nlist, num_of_centroids, code_size, METRIC_INNER_PRODUCT) as a searcher, served by IVFPQIndex: every
     chunk is clustered into nlist k-means cells (at most its row count), its rows are stored as num_of_centroids bytes of PQ codes (of their
     residuals to the cell's centroid with by_residual) and a search scans the codes of each query's nprobe best cells.  num_of_centroids is
@@ -517,43 +551,30 @@ class IVFPQFaissSearch(FlatIPFaissSearch):
     M and by_residual from the file.  Not served: the L2 metric, shards on RPC workers."""
     index_cls = IVFPQIndex
     index_ext = "ivfpq"
-    serves_rpc_shards = False
+    loaded = dict(num_of_centroids="M", by_residual="by_residual")
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32,
                  num_of_centroids: int = 96, code_size: int = 8, by_residual: bool = True, similarity_metric=0, **kwargs):
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"IVFPQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        _inner_product_only("IVFPQFaissSearch", similarity_metric)
         if code_size != 8:
             raise NotImplementedError(f"IVFPQFaissSearch: code_size (nbits) {code_size} is not served (only 8)")
-        if nlist < 1 or nprobe < 1:
-            raise ValueError(f"IVFPQFaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
-        if num_of_centroids < 1:
+        super().__init__(model, batch_size, corpus_chunk_size, nlist, nprobe, **kwargs)
+        if num_of_centroids < 1:                      # (after nlist / nprobe, which the base refuses before it sets anything up)
             raise ValueError(f"IVFPQFaissSearch: num_of_centroids={num_of_centroids} must be >= 1")
-        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
-        self.nlist, self.nprobe = int(nlist), int(nprobe)
         self.num_of_centroids, self.code_size, self.by_residual = int(num_of_centroids), code_size, bool(by_residual)
-        self.similarity_metric = 0
 
     def _new_index(self, dim: int, capacity: int) -> IVFPQIndex:
         if dim % self.num_of_centroids:
             raise ValueError(f"IVFPQFaissSearch: dimension {dim} is not a multiple of num_of_centroids={self.num_of_centroids}")
-        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
-        return IVFPQIndex(dim, nlist, self.num_of_centroids, self.code_size, nprobe=min(self.nprobe, nlist, 2048), by_residual=self.by_residual,
+        nlist, nprobe = self._cells(capacity)
+        return IVFPQIndex(dim, nlist, self.num_of_centroids, self.code_size, nprobe=nprobe, by_residual=self.by_residual,
                           capacity=capacity)
-
-    def _train(self, idx: IVFPQIndex, corpus_emb):
-        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
-
-    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
-        super().load(input_dir, prefix, ext)
-        idx = self.faiss_index.index
-        self.nlist, self.nprobe, self.num_of_centroids, self.by_residual = idx.nlist, idx.nprobe, idx.M, idx.by_residual
 
     def get_index_name(self):
         return "ivfpq_faiss_index"
 
 
-class IVFSQFaissSearch(FlatIPFaissSearch):
+class IVFSQFaissSearch(_IVFFaissSearch):
     """faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, quantizer_type, METRIC_INNER_PRODUCT) as a searcher, served by IVFSQIndex: every
     chunk is clustered into nlist k-means cells (at most its row count), its rows are stored as fp16 codes (of their residuals to the cell's
     centroid with by_residual) and a search scans the codes of each query's nprobe best cells, every scanned row scored exactly over its code.
@@ -562,38 +583,25 @@ class IVFSQFaissSearch(FlatIPFaissSearch):
     RPC workers."""
     index_cls = IVFSQIndex
     index_ext = "ivfsq"
-    serves_rpc_shards = False
+    loaded = dict(by_residual="by_residual")
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32,
                  quantizer_type: str = "QT_fp16", by_residual: bool = True, similarity_metric=0, **kwargs):
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"IVFSQFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        _inner_product_only("IVFSQFaissSearch", similarity_metric)
         if quantizer_type != "QT_fp16":
             raise NotImplementedError(f"IVFSQFaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_fp16')")
-        if nlist < 1 or nprobe < 1:
-            raise ValueError(f"IVFSQFaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
-        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
-        self.nlist, self.nprobe = int(nlist), int(nprobe)
+        super().__init__(model, batch_size, corpus_chunk_size, nlist, nprobe, **kwargs)
         self.quantizer_type, self.by_residual = quantizer_type, bool(by_residual)
-        self.similarity_metric = 0
 
     def _new_index(self, dim: int, capacity: int) -> IVFSQIndex:
-        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
-        return IVFSQIndex(dim, nlist, self.quantizer_type, nprobe=min(self.nprobe, nlist, 2048), by_residual=self.by_residual, capacity=capacity)
-
-    def _train(self, idx: IVFSQIndex, corpus_emb):
-        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
-
-    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
-        super().load(input_dir, prefix, ext)
-        idx = self.faiss_index.index
-        self.nlist, self.nprobe, self.by_residual = idx.nlist, idx.nprobe, idx.by_residual
+        nlist, nprobe = self._cells(capacity)
+        return IVFSQIndex(dim, nlist, self.quantizer_type, nprobe=nprobe, by_residual=self.by_residual, capacity=capacity)
 
     def get_index_name(self):
         return "ivfsq_faiss_index"
 
 
-class IVFSQ8FaissSearch(FlatIPFaissSearch):
+class IVFSQ8FaissSearch(_IVFFaissSearch):
     """faiss IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, QT_8bit | QT_8bit_uniform, METRIC_INNER_PRODUCT) ("IVF...,SQ8") as a searcher, served by
     IVFSQ8Index: every chunk is clustered into nlist k-means cells (at most its row count), the range of the 8-bit quantiser is trained on the
     chunk's residuals (its rows without by_residual), the rows are stored as 1-byte codes and a search scans the codes of each query's nprobe best
@@ -603,34 +611,21 @@ class IVFSQ8FaissSearch(FlatIPFaissSearch):
     shards on RPC workers."""
     index_cls = IVFSQ8Index
     index_ext = "ivfsq8"
-    serves_rpc_shards = False
+    loaded = dict(quantizer_type="qtype", by_residual="by_residual")
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32,
                  quantizer_type: str = "QT_8bit", by_residual: bool = True, similarity_metric=0, **kwargs):
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"IVFSQ8FaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
+        _inner_product_only("IVFSQ8FaissSearch", similarity_metric)
         if quantizer_type == "QT_fp16":
             raise NotImplementedError("IVFSQ8FaissSearch: quantizer_type 'QT_fp16' is served by IVFSQFaissSearch (faiss_search_map='ivfsq')")
         if quantizer_type not in ("QT_8bit", "QT_8bit_uniform"):
             raise NotImplementedError(f"IVFSQ8FaissSearch: quantizer_type {quantizer_type!r} is not served (only 'QT_8bit' and 'QT_8bit_uniform')")
-        if nlist < 1 or nprobe < 1:
-            raise ValueError(f"IVFSQ8FaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
-        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
-        self.nlist, self.nprobe = int(nlist), int(nprobe)
+        super().__init__(model, batch_size, corpus_chunk_size, nlist, nprobe, **kwargs)
         self.quantizer_type, self.by_residual = quantizer_type, bool(by_residual)
-        self.similarity_metric = 0
 
     def _new_index(self, dim: int, capacity: int) -> IVFSQ8Index:
-        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
-        return IVFSQ8Index(dim, nlist, self.quantizer_type, nprobe=min(self.nprobe, nlist, 2048), by_residual=self.by_residual, capacity=capacity)
-
-    def _train(self, idx: IVFSQ8Index, corpus_emb):
-        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
-
-    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
-        super().load(input_dir, prefix, ext)
-        idx = self.faiss_index.index
-        self.nlist, self.nprobe, self.quantizer_type, self.by_residual = idx.nlist, idx.nprobe, idx.qtype, idx.by_residual
+        nlist, nprobe = self._cells(capacity)
+        return IVFSQ8Index(dim, nlist, self.quantizer_type, nprobe=nprobe, by_residual=self.by_residual, capacity=capacity)
 
     def get_index_name(self):
         return "ivfsq8_faiss_index"
@@ -694,35 +689,22 @@ class RefineFaissSearch(FlatIPFaissSearch):
         return "refine_faiss_index"
 
 
-class IVFFaissSearch(FlatIPFaissSearch):
+class IVFFaissSearch(_IVFFaissSearch):
     """faiss IndexIVFFlat(IndexFlatIP(d), d, nlist, METRIC_INNER_PRODUCT) as a searcher, served by IVFFlatIndex: every chunk is clustered into
     nlist k-means cells (at most its row count) and a search scans the rows of each query's nprobe best cells, scored exactly.  index() trains
     on the chunk and then adds it; _index_in_place trains on the encoded chunk when its staging slot is committed.  index / load / save behave
     like FlatIPFaissSearch's with that shard; load() takes nlist and nprobe from the file.  Not served: the L2 metric, shards on RPC workers."""
     index_cls = IVFFlatIndex
     index_ext = "ivf"
-    serves_rpc_shards = False
 
     def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, nlist: int = 1024, nprobe: int = 32, similarity_metric=0,
                  **kwargs):
-        if similarity_metric not in (0, "METRIC_INNER_PRODUCT", "ip"):     # faiss.METRIC_INNER_PRODUCT == 0
-            raise NotImplementedError(f"IVFFaissSearch: similarity_metric {similarity_metric!r} is not served (only inner product, faiss.METRIC_INNER_PRODUCT = 0)")
-        if nlist < 1 or nprobe < 1:
-            raise ValueError(f"IVFFaissSearch: nlist={nlist} and nprobe={nprobe} must be >= 1")
-        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
-        self.nlist, self.nprobe = int(nlist), int(nprobe)
-        self.similarity_metric = 0
+        _inner_product_only("IVFFaissSearch", similarity_metric)
+        super().__init__(model, batch_size, corpus_chunk_size, nlist, nprobe, **kwargs)
 
     def _new_index(self, dim: int, capacity: int) -> IVFFlatIndex:
-        nlist = max(1, min(self.nlist, capacity))     # a chunk of fewer rows than nlist: one cell per row at the most
-        return IVFFlatIndex(dim, nlist, nprobe=min(self.nprobe, nlist, 2048), capacity=capacity)
-
-    def _train(self, idx: IVFFlatIndex, corpus_emb):
-        idx.train(corpus_emb)                         # index() trains on the chunk, then adds it
-
-    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
-        super().load(input_dir, prefix, ext)
-        self.nlist, self.nprobe = self.faiss_index.index.nlist, self.faiss_index.index.nprobe
+        nlist, nprobe = self._cells(capacity)
+        return IVFFlatIndex(dim, nlist, nprobe=nprobe, capacity=capacity)
 
     def get_index_name(self):
         return "ivf_faiss_index"
