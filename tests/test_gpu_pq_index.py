@@ -96,6 +96,75 @@ def test_search_is_bit_identical_to_the_yardstick(d, M, nq):
         assert_same(idx.search(q, k), want_topk(q, C, codes, k))
 
 
+def want_range(q, C, codes, radius, id_base=0):
+    """Yardstick (lims, D, I) on the device: the scores of want_topk, every row with s > radius, rows ascending inside a query."""
+    S = Y.scores_torch(lut_torch(q, C), codes)
+    mask = S > radius
+    lims = torch.zeros(q.shape[0] + 1, dtype=torch.int64, device=q.device)
+    lims[1:] = torch.cumsum(mask.sum(dim=1), 0)
+    qi, rows = torch.nonzero(mask, as_tuple=True)               # row-major: queries ascending, rows ascending inside a query
+    return lims, S[qi, rows], rows + id_base
+
+
+def assert_same_range(got, want):
+    assert torch.equal(got[0], want[0]) and torch.equal(got[2], want[2])
+    assert torch.equal(got[1].view(torch.int32), want[1].view(torch.int32))
+
+
+# M = 200 > PQ_SCAN_MC = 128: k_pq_scan loads the query's table in TWO passes per tile (sub-spaces [0, 128) and [128, 200)), and 200 % 16 = 8:
+# the last 16-sub-space group of the second pass is half padding bytes (Mp = 208) -- the two at once, which M = 8 / 64 / 96 / 256 never give.
+# n = 1029: two 1024-row tiles, the second with 5 rows (its block maxima cover 1 of 8 blocks); n = 127: less than one code block.
+# (64, 8): one pass, ONE partial group and nothing else.
+@pytest.mark.parametrize("d,M", [(400, 200), (64, 8)])
+@pytest.mark.parametrize("n", [1029, 127])
+@pytest.mark.parametrize("nq", [1, 5])
+def test_two_pass_scan_with_a_padded_last_group_is_bit_identical_to_the_yardstick(d, M, n, nq):
+    idx, C, codes = make(d, M, n, seed=M + n)
+    q = torch.from_numpy(queries(nq, d, seed=d + nq)).cuda()
+    for k in (1, 100, 1029 + 3):
+        assert_same(idx.search(q, k), want_topk(q, C, codes, k))
+    idx.id_base = 70
+    S = Y.scores_torch(lut_torch(q, C), codes)
+    top = torch.sort(S.reshape(-1), descending=True).values
+    # radii: nothing passes (the largest score itself: strictly greater), ~20 rows per query, a stored score in the middle, everything
+    for radius in (float(top[0]), float(top[min(20 * nq, top.numel() - 1)]), float(top[top.numel() // 2]), float("-inf")):
+        assert_same_range(idx.range_search(q, radius), want_range(q, C, codes, radius, id_base=70))
+
+
+# dsub = 1 and 3 (row pieces of 2 and 4 floats in LDS), dsub = 64: the largest served, whose dynamic LDS of (256 * 64 + 256 * 65) * 4 =
+# 132 096 B is the only size above the 64 KiB default limit.  n = 257: a second workgroup with one row.
+@pytest.mark.parametrize("d,M", [(16, 16), (48, 16), (1024, 16)])
+def test_codes_at_the_smallest_and_largest_sub_space_widths(d, M):
+    from lightretriever_amd import PQIndex
+    rng = np.random.default_rng(d + 3)
+    C = rng.standard_normal((M, 256, d // M)).astype(np.float32)
+    C[:, 200] = C[:, 17]                                        # duplicate centroids: the lower j wins
+    C[:, 255] = C[:, 0]
+    x = rng.standard_normal((257, d)).astype(np.float32)
+    x[:40] = C[np.arange(M)[None, :], rng.choice([0, 17, 200, 255], size=(40, M))].reshape(40, d)   # rows sitting exactly on a duplicate
+    x[256] = C[np.arange(M), 255].reshape(d)                    # the lone row of the second workgroup too
+    idx = PQIndex(d, M)
+    got = idx.encode(torch.from_numpy(x), torch.from_numpy(C)).cpu().numpy()
+    assert np.array_equal(got, Y.encode(x, C))
+    assert not np.isin(got[:40], [200, 255]).any() and not np.isin(got[256], [200, 255]).any()
+    # through add(): the same codes in the index's own blocks, rows [128, 257) in a second and third code block
+    idx.set_contents(torch.from_numpy(C), torch.zeros(0, M, dtype=torch.uint8))
+    idx.add(torch.from_numpy(x))
+    assert np.array_equal(idx.codes().cpu().numpy(), got)
+
+
+def test_sub_space_width_65_is_refused_by_the_library():
+    from lightretriever_amd import _lib
+    lib = _lib.lib()
+    d, M = 65 * 16, 16
+    x = torch.zeros(4, d, device="cuda")
+    C = torch.zeros(M, 256, 65, device="cuda")
+    codes = torch.full((128 * 16,), 0xAB, dtype=torch.uint8, device="cuda")
+    with pytest.raises(_lib.LrxError, match=r"pq_encode: dsub=65 > 64 is not served"):
+        _lib.check(lib.lrx_pq_encode(_lib.ptr(x), 4, d, _lib.ptr(C), d, M, _lib.ptr(codes), 0, _lib.current_stream()))
+    assert bool((codes == 0xAB).all())                          # refused before anything was launched
+
+
 def test_fewer_rows_than_k_pads_and_duplicate_rows_tie_to_the_lower_row():
     d, M = 768, 96
     idx, C, codes = make(d, M, 300)
