@@ -17,9 +17,10 @@ def scanned_positions(probe_row, list_off, max_scan_rows=None) -> np.ndarray:
     """int64: the stored positions one query scans, in segment order (empty when they are more than max_scan_rows)."""
     list_off = np.asarray(list_off, np.int64)
     nlist = len(list_off) - 1
-    cells = []
+    cells, seen = [], set()
     for c in np.asarray(probe_row, np.int64).tolist():
-        if 0 <= c < nlist and c not in cells:
+        if 0 <= c < nlist and c not in seen:
+            seen.add(c)
             cells.append(c)
     pos = np.concatenate([np.arange(list_off[c], list_off[c + 1], dtype=np.int64) for c in cells] + [np.zeros(0, np.int64)])
     if max_scan_rows is not None and pos.size > max_scan_rows:

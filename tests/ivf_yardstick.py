@@ -122,10 +122,11 @@ def search(q, X, list_off, row_ids, probes, k: int, id_base: int = 0, row_map=No
     D = np.full((Q, k), -FLT_MAX, np.float32)
     I = np.full((Q, k), -1, np.int64)
     for i in range(Q):
-        cells = []
-        for c in probes[i]:
-            if 0 <= c < nlist and c not in cells:
-                cells.append(int(c))
+        cells, seen = [], set()
+        for c in probes[i].tolist():
+            if 0 <= c < nlist and c not in seen:
+                seen.add(c)
+                cells.append(c)
         pos = np.concatenate([np.arange(list_off[c], list_off[c + 1]) for c in cells] + [np.zeros(0, np.int64)]).astype(np.int64)
         if max_scan_rows is not None and pos.size > max_scan_rows:
             continue

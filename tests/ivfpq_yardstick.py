@@ -18,8 +18,9 @@ FLT_MAX = np.finfo(np.float32).max
 
 
 def row_scores(L, codes, base):
-    """L fp32 [M, 256] (one query's table), codes uint8 [n, M], base fp32 scalar -> fp32 [n]: base, then the M table entries in ascending m."""
-    acc = np.full(codes.shape[0], base, np.float32)
+    """L fp32 [M, 256] (one query's table), codes uint8 [n, M], base fp32 (one value, or one per row) -> fp32 [n]: base, then the M table
+    entries in ascending m."""
+    acc = np.broadcast_to(np.asarray(base, np.float32), codes.shape[:1]).copy()
     for m in range(L.shape[0]):
         acc = (acc + L[m, codes[:, m]]).astype(np.float32)
     return acc
@@ -40,15 +41,14 @@ def search(q, pq_centroids, codes, list_off, row_ids, probes, probe_scores, by_r
     D = np.full((Q, k), -FLT_MAX, np.float32)
     I = np.full((Q, k), -1, np.int64)
     for i in range(Q):
-        cells, sc, rows = [], [np.zeros(0, np.float32)], [np.zeros(0, np.int64)]
-        for j, c in enumerate(probes[i]):
-            if 0 <= c < nlist and c not in cells:
-                cells.append(int(c))
-                pos = np.arange(list_off[c], list_off[c + 1])
-                base = np.float32(probe_scores[i][j]) if by_residual else np.float32(0)
-                sc.append(row_scores(L[i], codes[pos], base))
-                rows.append(row_ids[pos])
-        sc, rows = np.concatenate(sc), np.concatenate(rows)
+        seen, pos, base = set(), [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+        for j, c in enumerate(probes[i].tolist()):
+            if 0 <= c < nlist and c not in seen:
+                seen.add(c)
+                pos.append(np.arange(list_off[c], list_off[c + 1]))
+                base.append(np.full(pos[-1].size, probe_scores[i][j] if by_residual else 0.0, np.float32))
+        pos, base = np.concatenate(pos), np.concatenate(base)
+        sc, rows = row_scores(L[i], codes[pos], base), row_ids[pos]            # one call for the query: a row's score depends on its own base alone
         if max_scan_rows is not None and rows.size > max_scan_rows:
             continue
         order = np.lexsort((rows, -sc.astype(np.float64)))[:k]

@@ -57,10 +57,10 @@ def ordered_sums(q, codes) -> np.ndarray:
 
 
 def row_scores(q, codes, base=0.0) -> np.ndarray:
-    """fp32 [n]: (float)(base + the ordered sum): one rounding."""
+    """fp32 [n]: (float)(base + the ordered sum): one rounding.  base: one value, or one per row."""
     if len(codes) == 0:
         return np.zeros(0, np.float32)
-    return (np.float64(base) + ordered_sums(q, codes)).astype(np.float32)
+    return (np.asarray(base, np.float64) + ordered_sums(q, codes)).astype(np.float32)
 
 
 def search(q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, id_base=0, row_map=None, max_scan_rows=None):
@@ -77,15 +77,14 @@ def search(q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, id
     D = np.full((Q, k), -FLT_MAX, np.float32)
     I = np.full((Q, k), -1, np.int64)
     for i in range(Q):
-        cells, sc, rows = [], [np.zeros(0, np.float32)], [np.zeros(0, np.int64)]
-        for j, c in enumerate(probes[i]):
-            if 0 <= c < nlist and c not in cells:
-                cells.append(int(c))
-                pos = np.arange(list_off[c], list_off[c + 1])
-                base = float(np.float32(probe_scores[i][j])) if by_residual else 0.0
-                sc.append(row_scores(q[i], codes[pos], base))
-                rows.append(row_ids[pos])
-        sc, rows = np.concatenate(sc), np.concatenate(rows)
+        seen, pos, base = set(), [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+        for j, c in enumerate(probes[i].tolist()):
+            if 0 <= c < nlist and c not in seen:
+                seen.add(c)
+                pos.append(np.arange(list_off[c], list_off[c + 1]))
+                base.append(np.full(pos[-1].size, probe_scores[i][j] if by_residual else 0.0, np.float32))
+        pos, base = np.concatenate(pos), np.concatenate(base)
+        sc, rows = row_scores(q[i], codes[pos], base), row_ids[pos]            # one call for the query: a row's score depends on its own base alone
         if max_scan_rows is not None and rows.size > max_scan_rows:
             continue
         order = np.lexsort((rows, -sc.astype(np.float64)))[:k]

@@ -2,14 +2,14 @@
 torch.ops.lrx.ivf_*_sel, ops.ivf_*_sel, RowSelector, search(sel=) / range_search_probed(sel=), FaissIndex).  Every comparison is
 on bits and needs no tolerance: every scanned (query, row) pair is scored independently of the others, so a filtered result IS the
 unfiltered full result restricted to the selected rows (tests/ivf_selector_yardstick.py), and with every cell probed the flat family's IS the
-flat index's over the selected rows alone.  The hand-made cells are those of tests/test_gpu_ivf_range.py (its Store)."""
+flat index's over the selected rows alone.  The hand-made cells are those of tests/test_gpu_ivf_range.py (tests/ivf_store.py's Store)."""
 import numpy as np
 import pytest
 import torch
 
 import ivf_selector_yardstick as Y
-import test_gpu_ivf_range as RG
-from test_gpu_ivf_range import FAMILIES, Store, dev, errors
+import ivf_store as RG
+from ivf_store import FAMILIES, Store, dev, errors
 
 pytestmark = pytest.mark.gpu
 
