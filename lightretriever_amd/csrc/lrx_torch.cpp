@@ -8,6 +8,9 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <string>
+#include <type_traits>
+
 #include "../../include/lrx.h"
 
 namespace {
@@ -184,16 +187,22 @@ std::tuple<at::Tensor, at::Tensor> flat_ip_topk(const at::Tensor& q, const at::T
   return {o.d, o.i};
 }
 
-// x_shadow: the shard's 1-D tiled fp16 shadow (include/lrx.h), block 0 row 0 = x row 0; flags: LRX_SEARCH_FILTER_*
-std::tuple<at::Tensor, at::Tensor> flat_ip_topk_bounded(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
-                                                        const at::Tensor& row_bounds, int64_t k, int64_t id_base, int64_t flags) {
-  DevGuard guard(q.device());
+// The store of the bounded searches (flat_ip_topk_bounded, its wire sibling and flat_ip_range_search; `op` names the one): x fp32 [N, D] rows,
+// their 1-D tiled fp16 shadow x_shadow (include/lrx.h; block 0 row 0 = x row 0) or None, row_bounds [2] -> the shadow's address, or null
+void* flat_bounded_args(const char* op, const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow, const at::Tensor& row_bounds) {
   need(q, "q", at::kFloat, 2);
   need(x, "x", at::kFloat, 2);
   need(row_bounds, "row_bounds", at::kFloat, 1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_topk_bounded: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
-                        "flat_ip_topk_bounded: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, op, ": q [Q,D] contiguous, x [N,D], row_bounds [2]");
+  return tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
+                    (std::string(op) + ": x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)").c_str());
+}
+
+// flags: LRX_SEARCH_FILTER_*
+std::tuple<at::Tensor, at::Tensor> flat_ip_topk_bounded(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
+                                                        const at::Tensor& row_bounds, int64_t k, int64_t id_base, int64_t flags) {
+  DevGuard guard(q.device());
+  void* xb = flat_bounded_args("flat_ip_topk_bounded", q, x, x_shadow, row_bounds);
   TopK o = topk_out(q, k);
   const size_t wsb = lrx_flat_ip_bounded_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
   at::Tensor ws = bytes((int64_t)wsb, q);
@@ -210,12 +219,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_topk_bounded_wire(const a
                                                                          const at::Tensor& row_bounds, int64_t k, int64_t id_base,
                                                                          const c10::optional<at::Tensor>& row_map, int64_t flags) {
   DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(x, "x", at::kFloat, 2);
-  need(row_bounds, "row_bounds", at::kFloat, 1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_topk_bounded_wire: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
-                        "flat_ip_topk_bounded_wire: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  void* xb = flat_bounded_args("flat_ip_topk_bounded_wire", q, x, x_shadow, row_bounds);
   const int64_t* rm = row_map_ptr(row_map, x.size(0), "flat_ip_topk_bounded_wire: row_map int64 [>= N] contiguous");
   TopK o = topk_out(q, k, true);
   const size_t wsb = lrx_flat_ip_bounded_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
@@ -264,16 +268,24 @@ std::tuple<at::Tensor, at::Tensor> merge_topk(const at::Tensor& d_parts, const a
   return {d, i};
 }
 
-// fp16 scalar-quantised index (lrx_sq_fp16_ip_search): codes = the 1-D tiled fp16 codes (include/lrx.h, whole 128-row blocks) holding n_rows
-// rows of q.size(1) columns; row_bounds [2] as maintained by shard_commit_rows.  Returns (D, I, wire words) like flat_ip_topk_bounded_wire.
+// The store of the fp16 scalar-quantised index (sq_fp16_ip_topk and sq_fp16_ip_range_search; `op` names the one): codes = the 1-D tiled fp16
+// codes (include/lrx.h, whole 128-row blocks) holding n_rows rows of q.size(1) columns; row_bounds [2] as maintained by shard_commit_rows
+// -> the codes' address
+void* sq_fp16_args(const char* op, const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& row_bounds) {
+  need(q, "q", at::kFloat, 2);
+  need(row_bounds, "row_bounds", at::kFloat, 1);
+  TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && q.size(1) % 64 == 0 && n_rows >= 0, op,
+              ": q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
+  return tiled_rows(codes, at::kHalf, n_rows, q.size(1),
+                    (std::string(op) + ": codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)").c_str());
+}
+
+// lrx_sq_fp16_ip_search.  Returns (D, I, wire words) like flat_ip_topk_bounded_wire.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& row_bounds,
                                                                int64_t k, int64_t id_base, const c10::optional<at::Tensor>& row_map, int64_t flags) {
   DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(row_bounds, "row_bounds", at::kFloat, 1);
+  void* cb = sq_fp16_args("sq_fp16_ip_topk", q, codes, n_rows, row_bounds);
   const int64_t dim = q.size(1);
-  TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && dim % 64 == 0 && n_rows >= 0, "sq_fp16_ip_topk: q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
-  void* cb = tiled_rows(codes, at::kHalf, n_rows, dim, "sq_fp16_ip_topk: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
   const int64_t* rm = row_map_ptr(row_map, n_rows, "sq_fp16_ip_topk: row_map int64 [>= n_rows] contiguous");
   TopK o = topk_out(q, k, true);
   const size_t wsb = lrx_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)q.size(0), (int32_t)k, (int32_t)flags);
@@ -359,6 +371,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> range_result(const at::Tensor& li
 }
 
 // ---- inverted file: the four families (flat, PQ, fp16, 8-bit) ------------------------------------------------------------------
+// Each family has four ops -- <name>_topk, <name>_range_search and a *_sel variant of each (a search under a row selector) -- over four library
+// entries that start with the same head of arguments, the family's store through ld_probe / by_residual, and end with one of two tails, the
+// same for all families (include/lrx.h).  So every list is written once: a family below is a struct that checks its operands (its *_args),
+// sizes its two workspaces, names its four entries and, in head(), spells the head; ivf_search() -- one for top-k, one for range -- holds the
+// selector check, the workspace, the outputs, the tail and the choice between the plain and the *_sel entry; IvfOp turns a family into its four
+// registered functions.  A plain op calls the plain entry, a *_sel op the *_sel entry, also when its selector is None.
+
 // The result of a top-k op, as range_result is of a range op: `call(d, i)` runs the library call over the outputs.
 template <class Call>
 std::tuple<at::Tensor, at::Tensor> topk_result(const at::Tensor& q, int64_t k, const char* who, Call call) {
@@ -371,14 +390,14 @@ std::tuple<at::Tensor, at::Tensor> topk_result(const at::Tensor& q, int64_t k, c
 // be strided; < 0 skipped, >= nlist skipped and counted), max_scan_rows = the caller's bound on the rows one query scans, row_ids int64 (the
 // original row of a position) or None, probe_scores fp32 [Q, nprobe] with the row stride of probes when by_residual, row_map.  `store_ok` is the
 // family's own part of the shape check and `shapes` the sentence that names every operand of it.
+using OptTensor = c10::optional<at::Tensor>;
 struct IvfArgs {
   int64_t Q, nlist, nprobe, ld_probe;
   const int64_t *ri, *rm;
   const float* ps;
 };
-IvfArgs ivf_args(const char* who, const at::Tensor& q, bool store_ok, const char* shapes, int64_t n_rows, const at::Tensor& list_off,
-                 const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-                 int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
+IvfArgs ivf_args(const char* who, const at::Tensor& q, bool store_ok, const char* shapes, int64_t n_rows, const at::Tensor& list_off, const OptTensor& row_ids,
+                 const at::Tensor& probes, const OptTensor& probe_scores, bool by_residual, int64_t max_scan_rows, const OptTensor& row_map) {
   need(list_off, "list_off", at::kLong, 1);
   need(probes, "probes", at::kLong, 2);
   IvfArgs a{q.size(0), list_off.size(0) - 1, probes.size(1), 0, nullptr, nullptr, nullptr};
@@ -403,8 +422,7 @@ IvfArgs ivf_args(const char* who, const at::Tensor& q, bool store_ok, const char
 }
 
 // The selector of a *_sel op (include/lrx.h, ROW SELECTOR): the int32 words of a bitmap over the n_rows original rows, [ceil(n_rows / 32)]
-// contiguous on the device, or None (no filter).  sel == nullptr: the plain op, which calls the plain entry.
-using OptTensor = c10::optional<at::Tensor>;
+// contiguous on the device, or None (no filter).  sel == nullptr: a plain op.
 const uint32_t* ivf_sel_bits(const char* who, const OptTensor* sel, int64_t n_rows) {
   if (sel == nullptr || !sel->has_value() || !(*sel)->defined()) return nullptr;
   const at::Tensor& t = **sel;
@@ -414,90 +432,103 @@ const uint32_t* ivf_sel_bits(const char* who, const OptTensor* sel, int64_t n_ro
   return (const uint32_t*)t.data_ptr<int32_t>();
 }
 
-// Inverted file (lrx_ivf_flat_ip_search): x [n_rows, D] fp32 rows stored cell by cell.  Returns (D, I).
-IvfArgs ivf_flat_ip_args(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
-                         const at::Tensor& probes, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
+// Top k over the probed cells.  Every top-k entry ends (max_scan_rows, k, id_base, D, I, row_map, [sel words, sel rows,] ws, bytes, stream).
+// Returns (D, I).
+template <class Fam>
+std::tuple<at::Tensor, at::Tensor> ivf_search(const char* who, const Fam& f, const OptTensor* sel, int64_t k, int64_t max_scan_rows, int64_t id_base) {
+  const size_t wsb = f.topk_bytes(k, max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, f.n_rows);
+  at::Tensor ws = bytes((int64_t)wsb, f.q);
+  return topk_result(f.q, k, who, [&](float* d, int64_t* i) {
+    return sel != nullptr ? f.head(Fam::topk_sel, max_scan_rows, (int32_t)k, id_base, d, i, f.a.rm, sb, f.n_rows, ws.data_ptr(), wsb, cur_stream())
+                          : f.head(Fam::topk, max_scan_rows, (int32_t)k, id_base, d, i, f.a.rm, ws.data_ptr(), wsb, cur_stream());
+  });
+}
+
+// Range search over the probed cells: the top-k op's arguments with radius for k.  Every range entry ends (max_scan_rows, radius, id_base, lims,
+// D, I, capacity, row_map, [sel words, sel rows,] ws, bytes, stream).  Returns (lims, D, I), the hits of a query in segment order (cells in
+// probe order, rows by stored position).
+template <class Fam>
+std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_search(const char* who, const Fam& f, const OptTensor* sel, double radius, int64_t max_scan_rows,
+                                                          int64_t id_base) {
+  const size_t wsb = f.range_bytes(max_scan_rows);
+  const uint32_t* sb = ivf_sel_bits(who, sel, f.n_rows);
+  at::Tensor ws = bytes((int64_t)wsb, f.q);
+  return range_result(f.q, f.a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
+    return sel != nullptr
+               ? f.head(Fam::range_sel, max_scan_rows, (float)radius, id_base, lims, d, i, cap, f.a.rm, sb, f.n_rows, ws.data_ptr(), wsb, cur_stream())
+               : f.head(Fam::range, max_scan_rows, (float)radius, id_base, lims, d, i, cap, f.a.rm, ws.data_ptr(), wsb, cur_stream());
+  });
+}
+
+// The four registered functions of a family: its ops take q, the family's Operands, `sel` (the *_sel ops only), its Flags, then k (int64: top k)
+// or radius (double: range search), max_scan_rows, id_base and row_map.  The op's name, `who`, goes into every message.
+template <class... T>
+struct Types {};
+template <class Fam, class Scalar, class Operands = typename Fam::Operands, class Flags = typename Fam::Flags>
+struct IvfOp;
+template <class Fam, class Scalar, class... Operands, class... Flags>
+struct IvfOp<Fam, Scalar, Types<Operands...>, Types<Flags...>> {
+  static auto run(const OptTensor* sel, const at::Tensor& q, Operands... o, Flags... f, Scalar scalar, int64_t max_scan_rows, int64_t id_base,
+                  const OptTensor& row_map) {
+    DevGuard guard(q.device());
+    const std::string who = std::string(Fam::name) + (std::is_same<Scalar, double>::value ? "_range_search" : "_topk") + (sel != nullptr ? "_sel" : "");
+    return ivf_search(who.c_str(), Fam(who.c_str(), q, o..., f..., max_scan_rows, row_map), sel, scalar, max_scan_rows, id_base);
+  }
+  static auto plain(const at::Tensor& q, Operands... o, Flags... f, Scalar scalar, int64_t max_scan_rows, int64_t id_base, const OptTensor& row_map) {
+    return run(nullptr, q, o..., f..., scalar, max_scan_rows, id_base, row_map);
+  }
+  static auto with_sel(const at::Tensor& q, Operands... o, const OptTensor& sel, Flags... f, Scalar scalar, int64_t max_scan_rows, int64_t id_base,
+                  const OptTensor& row_map) {
+    return run(&sel, q, o..., f..., scalar, max_scan_rows, id_base, row_map);
+  }
+};
+using TRef = const at::Tensor&;   // (the operand types of the families below)
+using ORef = const OptTensor&;
+
+// Flat: x [n_rows, D] fp32 rows stored cell by cell.
+IvfArgs ivf_flat_ip_args(const char* who, TRef q, TRef x, TRef list_off, ORef row_ids, TRef probes, int64_t max_scan_rows, ORef row_map) {
   need(q, "q", at::kFloat, 2);
   need(x, "x", at::kFloat, 2);
   return ivf_args(who, q, q.size(1) == x.size(1) && (x.size(0) <= 1 || x.stride(1) == 1),
                   ": q [Q,D] contiguous, x [n_rows,D], list_off int64 [nlist + 1], probes int64 [Q, nprobe]", x.size(0), list_off, row_ids, probes, c10::nullopt,
                   false, max_scan_rows, row_map);
 }
+struct IvfFlat {
+  static constexpr const char* name = "ivf_flat_ip";
+  static constexpr auto topk = &lrx_ivf_flat_ip_search;
+  static constexpr auto topk_sel = &lrx_ivf_flat_ip_search_sel;
+  static constexpr auto range = &lrx_ivf_flat_ip_range_search;
+  static constexpr auto range_sel = &lrx_ivf_flat_ip_range_search_sel;
+  using Operands = Types<TRef /*x*/, TRef /*list_off*/, ORef /*row_ids*/, TRef /*probes*/>;
+  using Flags = Types<>;
+  TRef q, x, list_off, probes;
+  const IvfArgs a;
+  const int64_t n_rows, dim;
+  IvfFlat(const char* who, TRef q, TRef x, TRef list_off, ORef row_ids, TRef probes, int64_t max_scan_rows, ORef row_map)
+      : q(q), x(x), list_off(list_off), probes(probes), a(ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map)),
+        n_rows(x.size(0)), dim(x.size(1)) {}
+  size_t topk_bytes(int64_t k, int64_t max_scan_rows) const {
+    return lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  }
+  size_t range_bytes(int64_t max_scan_rows) const {
+    return lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  }
+  template <class Entry, class... Tail>
+  int head(Entry entry, Tail... tail) const {
+    return entry(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri,
+                 (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe, tail...);
+  }
+};
 
-std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                         const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
-  const int64_t n_rows = x.size(0), dim = x.size(1);
-  const size_t wsb = lrx_ivf_flat_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return topk_result(q, k, who, [&](float* d, int64_t* i) {
-    if (sel != nullptr)
-      return lrx_ivf_flat_ip_search_sel(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
-                                        list_off.data_ptr<int64_t>(),
-                                  a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe,
-                                  max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_flat_ip_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim, list_off.data_ptr<int64_t>(),
-                                  a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), (int32_t)a.nprobe, a.ld_probe,
-                                  max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_flat_ip_topk_impl("ivf_flat_ip_topk", q, x, list_off, row_ids, probes, k, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor> ivf_flat_ip_topk_sel(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-                                                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& sel, int64_t k, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_flat_ip_topk_impl("ivf_flat_ip_topk_sel", q, x, list_off, row_ids, probes, k, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Range search over the probed cells (lrx_ivf_flat_ip_range_search): ivf_flat_ip_topk's arguments with radius for k.  Returns (lims, D, I), the
-// hits of a query in segment order (cells in probe order, rows by stored position).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& x,
-    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_flat_ip_args(who, q, x, list_off, row_ids, probes, max_scan_rows, row_map);
-  const int64_t n_rows = x.size(0), dim = x.size(1);
-  const size_t wsb = lrx_ivf_flat_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-    if (sel != nullptr)
-      return lrx_ivf_flat_ip_range_search_sel(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
-                                        list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(),
-                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, sb, n_rows,
-                                         ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_flat_ip_range_search(n_rows ? x.data_ptr<float>() : nullptr, n_rows, n_rows > 1 ? x.stride(0) : dim, (int32_t)dim,
-                                        list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(),
-                                        (int32_t)a.nprobe, a.ld_probe, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(),
-                                         wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_flat_ip_range_search_impl("ivf_flat_ip_range_search", q, x, list_off, row_ids, probes, radius, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_flat_ip_range_search_sel(const at::Tensor& q, const at::Tensor& x, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& sel, double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_flat_ip_range_search_impl("ivf_flat_ip_range_search_sel", q, x, list_off, row_ids, probes, radius, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Inverted file over PQ codes (lrx_ivf_pq_ip_search): codes = the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by
-// cell; pq_centroids [M, 256, D / M] fp32; n_rows is the length of row_ids, or the rows the code blocks hold.  Returns (D, I).
+// PQ codes: codes = the 1-D blocked uint8 PQ codes (whole 128-row blocks) by stored position, cell by cell; pq_centroids [M, 256, D / M] fp32;
+// n_rows is the length of row_ids, or the rows the code blocks hold.
 struct IvfPqStore {
   int64_t n_rows, dim, M;
   void* cb;
 };
-IvfArgs ivf_pq_ip_args(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
-                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-                       int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map, IvfPqStore& st) {
+IvfArgs ivf_pq_ip_args(const char* who, TRef q, TRef codes, TRef pq_centroids, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores, bool by_residual,
+                       int64_t max_scan_rows, ORef row_map, IvfPqStore& st) {
   need(q, "q", at::kFloat, 2);
   need(pq_centroids, "pq_centroids", at::kFloat, 3);
   const std::string blocked = std::string(who) + ": codes must be the 1-D blocked uint8 codes of the stored rows (whole 128-row blocks)";
@@ -511,86 +542,40 @@ IvfArgs ivf_pq_ip_args(const char* who, const at::Tensor& q, const at::Tensor& c
   st = IvfPqStore{n_rows, dim, M, tiled_rows(codes, at::kByte, n_rows, mp, blocked.c_str())};
   return a;
 }
-
-std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
-                                                       const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
-    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
+struct IvfPq {
+  static constexpr const char* name = "ivf_pq_ip";
+  static constexpr auto topk = &lrx_ivf_pq_ip_search;
+  static constexpr auto topk_sel = &lrx_ivf_pq_ip_search_sel;
+  static constexpr auto range = &lrx_ivf_pq_ip_range_search;
+  static constexpr auto range_sel = &lrx_ivf_pq_ip_range_search_sel;
+  using Operands = Types<TRef /*codes*/, TRef /*pq_centroids*/, TRef /*list_off*/, ORef /*row_ids*/, TRef /*probes*/, ORef /*probe_scores*/>;
+  using Flags = Types<bool /*by_residual*/>;
+  TRef q, pq_centroids, list_off, probes;
+  const bool by_residual;
   IvfPqStore st;
-  const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
-  const size_t wsb = lrx_ivf_pq_ip_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k,
-                                                   max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, st.n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return topk_result(q, k, who, [&](float* d, int64_t* i) {
-    if (sel != nullptr)
-      return lrx_ivf_pq_ip_search_sel(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
-                                list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, st.n_rows,
-                                 ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_pq_ip_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
-                                list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(),
-                                 wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
-    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_pq_ip_topk_impl("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor> ivf_pq_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
-                                                      const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-    const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_pq_ip_topk_impl("ivf_pq_ip_topk_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
-}
+  const IvfArgs a;
+  const int64_t n_rows;
+  IvfPq(const char* who, TRef q, TRef codes, TRef pq_centroids, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores, bool by_residual, int64_t max_scan_rows, ORef row_map)
+      : q(q), pq_centroids(pq_centroids), list_off(list_off), probes(probes), by_residual(by_residual),
+        a(ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st)), n_rows(st.n_rows) {}
+  size_t topk_bytes(int64_t k, int64_t max_scan_rows) const {
+    return lrx_ivf_pq_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  }
+  size_t range_bytes(int64_t max_scan_rows) const {
+    return lrx_ivf_pq_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  }
+  template <class Entry, class... Tail>
+  int head(Entry entry, Tail... tail) const {
+    return entry(n_rows ? st.cb : nullptr, n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M, list_off.data_ptr<int64_t>(), a.ri,
+                 (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
+                 tail...);
+  }
+};
 
-// Range search over the probed cells (lrx_ivf_pq_ip_range_search): ivf_pq_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
-    const at::Tensor& pq_centroids, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  IvfPqStore st;
-  const IvfArgs a = ivf_pq_ip_args(who, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map, st);
-  const size_t wsb = lrx_ivf_pq_ip_range_workspace_bytes(st.n_rows, (int32_t)a.nlist, (int32_t)st.dim, (int32_t)st.M, (int32_t)a.Q, (int32_t)a.nprobe,
-                                                         max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, st.n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-    if (sel != nullptr)
-      return lrx_ivf_pq_ip_range_search_sel(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
-                                      list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
-                                       a.rm, sb, st.n_rows, ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_pq_ip_range_search(st.n_rows ? st.cb : nullptr, st.n_rows, pq_centroids.data_ptr<float>(), (int32_t)st.dim, (int32_t)st.M,
-                                      list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                      (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
-                                       a.rm, ws.data_ptr(), wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& pq_centroids,
-                                                                      const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_pq_ip_range_search_impl("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_pq_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes,
-    const at::Tensor& pq_centroids, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-    const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_pq_ip_range_search_impl("ivf_pq_ip_range_search_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Inverted file over row-major codes [n_rows, D] contiguous, by stored position, cell by cell: fp16 (lrx_ivf_sq_fp16_ip_search) and 8-bit
-// (lrx_ivf_sq8_ip_search).  `shapes`: the family's sentence for the shape check.
-IvfArgs ivf_codes_args(const char* who, const at::Tensor& q, const at::Tensor& codes, at::ScalarType code_type, const char* shapes,
-                       const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-                       const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
+// Row-major codes [n_rows, D] contiguous, by stored position, cell by cell: fp16 (IvfSqFp16) and 8-bit (IvfSq8).  `shapes`: the family's sentence
+// for the shape check.
+IvfArgs ivf_codes_args(const char* who, TRef q, TRef codes, at::ScalarType code_type, const char* shapes, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores,
+                       bool by_residual, int64_t max_scan_rows, ORef row_map) {
   need(q, "q", at::kFloat, 2);
   need(codes, "codes", code_type, 2);
   return ivf_args(who, q, q.size(1) == codes.size(1) && codes.is_contiguous(), shapes, codes.size(0), list_off, row_ids, probes, probe_scores, by_residual,
@@ -599,81 +584,38 @@ IvfArgs ivf_codes_args(const char* who, const at::Tensor& q, const at::Tensor& c
 const char* const kIvfSqShapes = ": q [Q,D] contiguous, codes fp16 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
 const char* const kIvfSq8Shapes = ": q [Q,D] contiguous, codes uint8 [n_rows,D] contiguous, list_off int64 [nlist + 1], probes int64 [Q, nprobe]";
 
-std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
-                                                            const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids,
-                                                            const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1);
-  const size_t wsb = lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return topk_result(q, k, who, [&](float* d, int64_t* i) {
-    if (sel != nullptr)
-      return lrx_ivf_sq_fp16_ip_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri,
-                                           (int32_t)a.nlist,
-                                     q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
-                                     max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_sq_fp16_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
-                                     q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
-                                     max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(), wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-                                                       const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq_fp16_ip_topk_impl("ivf_sq_fp16_ip_topk", q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor> ivf_sq_fp16_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-                                                           const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows,
-    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq_fp16_ip_topk_impl("ivf_sq_fp16_ip_topk_sel", q, codes, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Range search over the probed cells (lrx_ivf_sq_fp16_ip_range_search): ivf_sq_fp16_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
-    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1);
-  const size_t wsb = lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-    if (sel != nullptr)
-      return lrx_ivf_sq_fp16_ip_range_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri,
-                                                 (int32_t)a.nlist,
-                                           q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe,
-                                           by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, sb, n_rows,
-                                               ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_sq_fp16_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist,
-                                           q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe,
-                                           by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap, a.rm, ws.data_ptr(), wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq_fp16_ip_range_search_impl("ivf_sq_fp16_ip_range_search", q, codes, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq_fp16_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes,
-    const at::Tensor& list_off, const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes,
-    const c10::optional<at::Tensor>& probe_scores, const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows,
-    int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq_fp16_ip_range_search_impl("ivf_sq_fp16_ip_range_search_sel", q, codes, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
-}
+struct IvfSqFp16 {
+  static constexpr const char* name = "ivf_sq_fp16_ip";
+  static constexpr auto topk = &lrx_ivf_sq_fp16_ip_search;
+  static constexpr auto topk_sel = &lrx_ivf_sq_fp16_ip_search_sel;
+  static constexpr auto range = &lrx_ivf_sq_fp16_ip_range_search;
+  static constexpr auto range_sel = &lrx_ivf_sq_fp16_ip_range_search_sel;
+  using Operands = Types<TRef /*codes*/, TRef /*list_off*/, ORef /*row_ids*/, TRef /*probes*/, ORef /*probe_scores*/>;
+  using Flags = Types<bool /*by_residual*/>;
+  TRef q, codes, list_off, probes;
+  const bool by_residual;
+  const IvfArgs a;
+  const int64_t n_rows, dim;
+  IvfSqFp16(const char* who, TRef q, TRef codes, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores, bool by_residual, int64_t max_scan_rows, ORef row_map)
+      : q(q), codes(codes), list_off(list_off), probes(probes), by_residual(by_residual),
+        a(ivf_codes_args(who, q, codes, at::kHalf, kIvfSqShapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map)),
+        n_rows(codes.size(0)), dim(codes.size(1)) {}
+  size_t topk_bytes(int64_t k, int64_t max_scan_rows) const {
+    return lrx_ivf_sq_fp16_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  }
+  size_t range_bytes(int64_t max_scan_rows) const {
+    return lrx_ivf_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  }
+  template <class Entry, class... Tail>
+  int head(Entry entry, Tail... tail) const {
+    return entry(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(),
+                 (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, tail...);
+  }
+};
 
 // The 8-bit family's own operands: trained fp32 vmin ++ vdiff (2 D floats for qtype 0, 2 for qtype 2).
-IvfArgs ivf_sq8_ip_args(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype, const at::Tensor& list_off,
-                        const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-                        int64_t max_scan_rows, const c10::optional<at::Tensor>& row_map) {
+IvfArgs ivf_sq8_ip_args(const char* who, TRef q, TRef codes, TRef trained, int64_t qtype, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores, bool by_residual,
+                        int64_t max_scan_rows, ORef row_map) {
   need(q, "q", at::kFloat, 2);
   need(codes, "codes", at::kByte, 2);
   need(trained, "trained", at::kFloat, 1);
@@ -681,92 +623,56 @@ IvfArgs ivf_sq8_ip_args(const char* who, const at::Tensor& q, const at::Tensor& 
               who, ": qtype ", qtype, " (0: QT_8bit, 2: QT_8bit_uniform) with trained fp32 [2 D] or [2] contiguous");
   return ivf_codes_args(who, q, codes, at::kByte, kIvfSq8Shapes, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
 }
+struct IvfSq8 {
+  static constexpr const char* name = "ivf_sq8_ip";
+  static constexpr auto topk = &lrx_ivf_sq8_ip_search;
+  static constexpr auto topk_sel = &lrx_ivf_sq8_ip_search_sel;
+  static constexpr auto range = &lrx_ivf_sq8_ip_range_search;
+  static constexpr auto range_sel = &lrx_ivf_sq8_ip_range_search_sel;
+  using Operands = Types<TRef /*codes*/, TRef /*trained*/, int64_t /*qtype*/, TRef /*list_off*/, ORef /*row_ids*/, TRef /*probes*/, ORef /*probe_scores*/>;
+  using Flags = Types<bool /*by_residual*/>;
+  TRef q, codes, trained, list_off, probes;
+  const int64_t qtype;
+  const bool by_residual;
+  const IvfArgs a;
+  const int64_t n_rows, dim;
+  IvfSq8(const char* who, TRef q, TRef codes, TRef trained, int64_t qtype, TRef list_off, ORef row_ids, TRef probes, ORef probe_scores, bool by_residual, int64_t max_scan_rows,
+         ORef row_map)
+      : q(q), codes(codes), trained(trained), list_off(list_off), probes(probes), qtype(qtype), by_residual(by_residual),
+        a(ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map)),
+        n_rows(codes.size(0)), dim(codes.size(1)) {}
+  size_t topk_bytes(int64_t k, int64_t max_scan_rows) const {
+    return lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
+  }
+  size_t range_bytes(int64_t max_scan_rows) const {
+    return lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
+  }
+  template <class Entry, class... Tail>
+  int head(Entry entry, Tail... tail) const {
+    return entry(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype, list_off.data_ptr<int64_t>(), a.ri,
+                 (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps, (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0,
+                 tail...);
+  }
+};
 
-std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk_impl(const char* who, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
-                                                        int64_t qtype, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
-    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1);
-  const size_t wsb = lrx_ivf_sq8_ip_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, (int32_t)k, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return topk_result(q, k, who, [&](float* d, int64_t* i) {
-    if (sel != nullptr)
-      return lrx_ivf_sq8_ip_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                 list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, sb, n_rows,
-                                  ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_sq8_ip_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                 list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                 (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (int32_t)k, id_base, d, i, a.rm, ws.data_ptr(),
-                                  wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
-                                                   const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual, int64_t k,
-    int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq8_ip_topk_impl("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor> ivf_sq8_ip_topk_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained, int64_t qtype,
-                                                       const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-    const c10::optional<at::Tensor>& sel, bool by_residual, int64_t k, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq8_ip_topk_impl("ivf_sq8_ip_topk_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, k, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Range search over the probed cells (lrx_ivf_sq8_ip_range_search): ivf_sq8_ip_topk's arguments with radius for k.  Returns (lims, D, I).
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search_impl(const char* who, const at::Tensor& q, const at::Tensor& codes,
-    const at::Tensor& trained, int64_t qtype, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map, const OptTensor* sel) {
-  DevGuard guard(q.device());
-  const IvfArgs a = ivf_sq8_ip_args(who, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, max_scan_rows, row_map);
-  const int64_t n_rows = codes.size(0), dim = codes.size(1);
-  const size_t wsb = lrx_ivf_sq8_ip_range_workspace_bytes(n_rows, (int32_t)a.nlist, (int32_t)dim, (int32_t)a.Q, (int32_t)a.nprobe, max_scan_rows);
-  const uint32_t* sb = ivf_sel_bits(who, sel, n_rows);
-  at::Tensor ws = bytes((int64_t)wsb, q);
-  return range_result(q, a.Q, who, [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
-    if (sel != nullptr)
-      return lrx_ivf_sq8_ip_range_search_sel(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                       list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
-                                        a.rm, sb, n_rows, ws.data_ptr(), wsb, cur_stream());
-    return lrx_ivf_sq8_ip_range_search(n_rows ? codes.data_ptr() : nullptr, n_rows, (int32_t)dim, trained.data_ptr<float>(), (int32_t)qtype,
-                                       list_off.data_ptr<int64_t>(), a.ri, (int32_t)a.nlist, q.data_ptr<float>(), (int32_t)a.Q, probes.data_ptr<int64_t>(), a.ps,
-                                       (int32_t)a.nprobe, a.ld_probe, by_residual ? 1 : 0, max_scan_rows, (float)radius, id_base, lims, d, i, cap,
-                                        a.rm, ws.data_ptr(), wsb, cur_stream());
-  });
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
-    int64_t qtype, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores, bool by_residual,
-    double radius, int64_t max_scan_rows, int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq8_ip_range_search_impl("ivf_sq8_ip_range_search", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, nullptr);
-}
-std::tuple<at::Tensor, at::Tensor, at::Tensor> ivf_sq8_ip_range_search_sel(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& trained,
-    int64_t qtype, const at::Tensor& list_off,
-    const c10::optional<at::Tensor>& row_ids, const at::Tensor& probes, const c10::optional<at::Tensor>& probe_scores,
-    const c10::optional<at::Tensor>& sel, bool by_residual, double radius, int64_t max_scan_rows, int64_t id_base,
-    const c10::optional<at::Tensor>& row_map) {
-  return ivf_sq8_ip_range_search_impl("ivf_sq8_ip_range_search_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual, radius, max_scan_rows, id_base, row_map, &sel);
-}
-
-// Product-quantised index (lrx_pq_ip_search): codes = the 1-D blocked uint8 codes (include/lrx.h, whole 128-row blocks) of n_rows rows,
-// centroids [M, 256, D / M] fp32.  Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
-                                              int64_t id_base, const c10::optional<at::Tensor>& row_map) {
-  DevGuard guard(q.device());
+// The store of the product-quantised index (pq_ip_topk and pq_ip_range_search; `op` names the one): codes = the 1-D blocked uint8 codes
+// (include/lrx.h, whole 128-row blocks) of n_rows rows, centroids [M, 256, D / M] fp32 -> the codes' address
+void* pq_args(const char* op, const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows) {
   need(q, "q", at::kFloat, 2);
   need(centroids, "centroids", at::kFloat, 3);
   const int64_t dim = q.size(1), M = centroids.size(0);
   TORCH_CHECK(q.is_contiguous() && centroids.is_contiguous() && centroids.size(1) == 256 && M > 0 && dim % M == 0 && centroids.size(2) == dim / M && n_rows >= 0,
-              "pq_ip_topk: q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
-  const int64_t mp = (M + 15) / 16 * 16;
-  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, "pq_ip_topk: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
+              op, ": q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
+  return tiled_rows(codes, at::kByte, n_rows, (M + 15) / 16 * 16,
+                    (std::string(op) + ": codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)").c_str());
+}
+
+// lrx_pq_ip_search.  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> pq_ip_topk(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows, int64_t k,
+                                              int64_t id_base, const c10::optional<at::Tensor>& row_map) {
+  DevGuard guard(q.device());
+  void* cb = pq_args("pq_ip_topk", q, codes, centroids, n_rows);
+  const int64_t dim = q.size(1), M = centroids.size(0);
   const int64_t* rm = row_map_ptr(row_map, n_rows, "pq_ip_topk: row_map int64 [>= n_rows] contiguous");
   TopK o = topk_out(q, k);
   const size_t wsb = lrx_pq_ip_workspace_bytes(n_rows, (int32_t)dim, (int32_t)M, (int32_t)q.size(0), (int32_t)k);
@@ -799,23 +705,32 @@ std::tuple<at::Tensor, at::Tensor> sq8_ip_topk(const at::Tensor& q, const at::Te
   return {o.d, o.i};
 }
 
-// Impact index (lrx_impact_search): postings int32 [nnz, 2] = {row, weight} grouped by term, ascending row inside a term; term_off int64
-// [n_terms + 1]; the queries in CSR form, q_off int32 [Q + 1], q_term / q_cnt int32 [q_off[Q]] (include/lrx.h).  Reads q_off[Q] back to the
-// host once (the CSR is checked against its arrays).  The overflow refusal of the contract is the caller's (ImpactIndex.search makes it).
-// Returns (D, I).
-std::tuple<at::Tensor, at::Tensor> impact_topk(const at::Tensor& postings, const at::Tensor& term_off, int64_t n_rows, const at::Tensor& q_off,
-                                               const at::Tensor& q_term, const at::Tensor& q_cnt, int64_t k, int64_t id_base,
-                                               const c10::optional<at::Tensor>& row_map, int64_t window_rows) {
-  DevGuard guard(postings.device());
+// The store and queries of the impact index (impact_topk and impact_range_search; `op` names the one): postings int32 [nnz, 2] = {row, weight}
+// grouped by term, ascending row inside a term; term_off int64 [n_terms + 1]; the queries in CSR form, q_off int32 [Q + 1], q_term / q_cnt
+// int32 [q_off[Q]] (include/lrx.h) -> Q.  Reads q_off[Q] back to the host once (the CSR is checked against its arrays); no_capture: the op
+// reads its result length back too, so it is refused under graph capture here, before that first read.
+int64_t impact_args(const char* op, const at::Tensor& postings, const at::Tensor& term_off, int64_t n_rows, const at::Tensor& q_off, const at::Tensor& q_term,
+                    const at::Tensor& q_cnt, bool no_capture) {
   need(postings, "postings", at::kInt, 2);
   need(term_off, "term_off", at::kLong, 1);
   need(q_off, "q_off", at::kInt, 1);
   need(q_term, "q_term", at::kInt, 1);
   need(q_cnt, "q_cnt", at::kInt, 1);
   TORCH_CHECK(postings.is_contiguous() && postings.size(1) == 2 && term_off.numel() >= 1 && q_off.numel() >= 1 && q_term.numel() == q_cnt.numel() && n_rows >= 0,
-              "impact_topk: postings int32 [nnz,2] contiguous, term_off int64 [T+1], q_off int32 [Q+1], q_term / q_cnt int32 of one length, n_rows >= 0");
+              op, ": postings int32 [nnz,2] contiguous, term_off int64 [T+1], q_off int32 [Q+1], q_term / q_cnt int32 of one length, n_rows >= 0");
+  TORCH_CHECK(!no_capture || c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None, op,
+              " under graph capture: the result length is read back to the host");
   const int64_t Q = q_off.numel() - 1;
-  TORCH_CHECK(q_off[Q].item<int32_t>() == q_term.numel(), "impact_topk: q_off[Q] must equal the length of q_term");
+  TORCH_CHECK(q_off[Q].item<int32_t>() == q_term.numel(), op, ": q_off[Q] must equal the length of q_term");
+  return Q;
+}
+
+// lrx_impact_search.  The overflow refusal of the contract is the caller's (ImpactIndex.search makes it).  Returns (D, I).
+std::tuple<at::Tensor, at::Tensor> impact_topk(const at::Tensor& postings, const at::Tensor& term_off, int64_t n_rows, const at::Tensor& q_off,
+                                               const at::Tensor& q_term, const at::Tensor& q_cnt, int64_t k, int64_t id_base,
+                                               const c10::optional<at::Tensor>& row_map, int64_t window_rows) {
+  DevGuard guard(postings.device());
+  const int64_t Q = impact_args("impact_topk", postings, term_off, n_rows, q_off, q_term, q_cnt, false);
   const int64_t* rm = row_map_ptr(row_map, n_rows, "impact_topk: row_map int64 [>= n_rows] contiguous");
   const auto f32 = postings.options().dtype(at::kFloat);
   at::Tensor d = at::empty({Q, k}, f32), i = at::empty({Q, k}, f32.dtype(at::kLong));
@@ -871,12 +786,7 @@ std::tuple<at::Tensor, at::Tensor> binary_topk(const at::Tensor& q, const at::Te
 std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Tensor& q, const at::Tensor& x, const c10::optional<at::Tensor>& x_shadow,
                                                                     const at::Tensor& row_bounds, double radius, int64_t id_base) {
   DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(x, "x", at::kFloat, 2);
-  need(row_bounds, "row_bounds", at::kFloat, 1);
-  TORCH_CHECK(q.is_contiguous() && q.size(1) == x.size(1) && row_bounds.numel() == 2, "flat_ip_range_search: q [Q,D] contiguous, x [N,D], row_bounds [2]");
-  void* xb = tiled_rows(x_shadow, at::kHalf, x.size(0), x.size(1),
-                        "flat_ip_range_search: x_shadow must be the 1-D tiled fp16 shadow of x (whole 128-row blocks)");
+  void* xb = flat_bounded_args("flat_ip_range_search", q, x, x_shadow, row_bounds);
   const int64_t Q = q.size(0);
   const size_t wsb = lrx_flat_ip_range_workspace_bytes(x.size(0), (int32_t)x.size(1), (int32_t)Q, x_shadow.has_value() ? 1 : 0);
   at::Tensor ws = bytes((int64_t)wsb, q);
@@ -890,12 +800,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> flat_ip_range_search(const at::Te
 std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_range_search(const at::Tensor& q, const at::Tensor& codes, int64_t n_rows, const at::Tensor& row_bounds,
                                                                        double radius, int64_t id_base) {
   DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(row_bounds, "row_bounds", at::kFloat, 1);
+  void* cb = sq_fp16_args("sq_fp16_ip_range_search", q, codes, n_rows, row_bounds);
   const int64_t dim = q.size(1), Q = q.size(0);
-  TORCH_CHECK(q.is_contiguous() && row_bounds.numel() == 2 && dim % 64 == 0 && n_rows >= 0,
-              "sq_fp16_ip_range_search: q [Q,D] contiguous with D % 64 == 0, row_bounds [2], n_rows >= 0");
-  void* cb = tiled_rows(codes, at::kHalf, n_rows, dim, "sq_fp16_ip_range_search: codes must be the 1-D tiled fp16 codes of n_rows rows (whole 128-row blocks)");
   const size_t wsb = lrx_sq_fp16_ip_range_workspace_bytes(n_rows, (int32_t)dim, (int32_t)Q);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, Q, "sq_fp16_ip_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
@@ -907,13 +813,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sq_fp16_ip_range_search(const at:
 std::tuple<at::Tensor, at::Tensor, at::Tensor> pq_ip_range_search(const at::Tensor& q, const at::Tensor& codes, const at::Tensor& centroids, int64_t n_rows,
                                                                   double radius, int64_t id_base, int64_t row_chunk) {
   DevGuard guard(q.device());
-  need(q, "q", at::kFloat, 2);
-  need(centroids, "centroids", at::kFloat, 3);
+  void* cb = pq_args("pq_ip_range_search", q, codes, centroids, n_rows);
   const int64_t dim = q.size(1), M = centroids.size(0), Q = q.size(0);
-  TORCH_CHECK(q.is_contiguous() && centroids.is_contiguous() && centroids.size(1) == 256 && M > 0 && dim % M == 0 && centroids.size(2) == dim / M && n_rows >= 0,
-              "pq_ip_range_search: q [Q,D] contiguous, centroids [M,256,D/M] contiguous with D % M == 0, n_rows >= 0");
-  const int64_t mp = (M + 15) / 16 * 16;
-  void* cb = tiled_rows(codes, at::kByte, n_rows, mp, "pq_ip_range_search: codes must be the 1-D blocked uint8 codes of n_rows rows (whole 128-row blocks)");
   const size_t wsb = lrx_pq_ip_range_workspace_bytes(n_rows, (int32_t)dim, (int32_t)M, (int32_t)Q, row_chunk);
   at::Tensor ws = bytes((int64_t)wsb, q);
   return range_result(q, Q, "pq_ip_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
@@ -927,17 +828,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> impact_range_search(const at::Ten
                                                                    const at::Tensor& q_term, const at::Tensor& q_cnt, double radius, int64_t id_base,
                                                                    int64_t window_rows, int64_t row_chunk) {
   DevGuard guard(postings.device());
-  need(postings, "postings", at::kInt, 2);
-  need(term_off, "term_off", at::kLong, 1);
-  need(q_off, "q_off", at::kInt, 1);
-  need(q_term, "q_term", at::kInt, 1);
-  need(q_cnt, "q_cnt", at::kInt, 1);
-  TORCH_CHECK(postings.is_contiguous() && postings.size(1) == 2 && term_off.numel() >= 1 && q_off.numel() >= 1 && q_term.numel() == q_cnt.numel() && n_rows >= 0,
-              "impact_range_search: postings int32 [nnz,2] contiguous, term_off int64 [T+1], q_off int32 [Q+1], q_term / q_cnt int32 of one length, n_rows >= 0");
-  TORCH_CHECK(c10::hip::currentStreamCaptureStatusMayInitCtx() == c10::hip::CaptureStatus::None,
-              "impact_range_search under graph capture: the result length is read back to the host");
-  const int64_t Q = q_off.numel() - 1;
-  TORCH_CHECK(q_off[Q].item<int32_t>() == q_term.numel(), "impact_range_search: q_off[Q] must equal the length of q_term");
+  const int64_t Q = impact_args("impact_range_search", postings, term_off, n_rows, q_off, q_term, q_cnt, true);
   const size_t wsb = lrx_range_impact_workspace_bytes(n_rows, (int32_t)Q, row_chunk);
   at::Tensor ws = bytes((int64_t)wsb, postings);
   return range_result(postings, Q, "impact_range_search", [&](int64_t* lims, float* d, int64_t* i, int64_t cap) {
@@ -1078,22 +969,22 @@ TORCH_LIBRARY_IMPL(lrx, CUDA, m) {   // (the ROCm build of PyTorch dispatches HI
   m.impl("sq_fp16_ip_topk", &sq_fp16_ip_topk);
   m.impl("flat_ip_rerank", &flat_ip_rerank);
   m.impl("sq_fp16_ip_rerank", &sq_fp16_ip_rerank);
-  m.impl("ivf_flat_ip_range_search", &ivf_flat_ip_range_search);
-  m.impl("ivf_flat_ip_range_search_sel", &ivf_flat_ip_range_search_sel);
-  m.impl("ivf_pq_ip_range_search", &ivf_pq_ip_range_search);
-  m.impl("ivf_pq_ip_range_search_sel", &ivf_pq_ip_range_search_sel);
-  m.impl("ivf_sq_fp16_ip_range_search", &ivf_sq_fp16_ip_range_search);
-  m.impl("ivf_sq_fp16_ip_range_search_sel", &ivf_sq_fp16_ip_range_search_sel);
-  m.impl("ivf_sq8_ip_range_search", &ivf_sq8_ip_range_search);
-  m.impl("ivf_sq8_ip_range_search_sel", &ivf_sq8_ip_range_search_sel);
-  m.impl("ivf_flat_ip_topk", &ivf_flat_ip_topk);
-  m.impl("ivf_flat_ip_topk_sel", &ivf_flat_ip_topk_sel);
-  m.impl("ivf_pq_ip_topk", &ivf_pq_ip_topk);
-  m.impl("ivf_pq_ip_topk_sel", &ivf_pq_ip_topk_sel);
-  m.impl("ivf_sq_fp16_ip_topk", &ivf_sq_fp16_ip_topk);
-  m.impl("ivf_sq_fp16_ip_topk_sel", &ivf_sq_fp16_ip_topk_sel);
-  m.impl("ivf_sq8_ip_topk", &ivf_sq8_ip_topk);
-  m.impl("ivf_sq8_ip_topk_sel", &ivf_sq8_ip_topk_sel);
+  m.impl("ivf_flat_ip_range_search", &IvfOp<IvfFlat, double>::plain);
+  m.impl("ivf_flat_ip_range_search_sel", &IvfOp<IvfFlat, double>::with_sel);
+  m.impl("ivf_pq_ip_range_search", &IvfOp<IvfPq, double>::plain);
+  m.impl("ivf_pq_ip_range_search_sel", &IvfOp<IvfPq, double>::with_sel);
+  m.impl("ivf_sq_fp16_ip_range_search", &IvfOp<IvfSqFp16, double>::plain);
+  m.impl("ivf_sq_fp16_ip_range_search_sel", &IvfOp<IvfSqFp16, double>::with_sel);
+  m.impl("ivf_sq8_ip_range_search", &IvfOp<IvfSq8, double>::plain);
+  m.impl("ivf_sq8_ip_range_search_sel", &IvfOp<IvfSq8, double>::with_sel);
+  m.impl("ivf_flat_ip_topk", &IvfOp<IvfFlat, int64_t>::plain);
+  m.impl("ivf_flat_ip_topk_sel", &IvfOp<IvfFlat, int64_t>::with_sel);
+  m.impl("ivf_pq_ip_topk", &IvfOp<IvfPq, int64_t>::plain);
+  m.impl("ivf_pq_ip_topk_sel", &IvfOp<IvfPq, int64_t>::with_sel);
+  m.impl("ivf_sq_fp16_ip_topk", &IvfOp<IvfSqFp16, int64_t>::plain);
+  m.impl("ivf_sq_fp16_ip_topk_sel", &IvfOp<IvfSqFp16, int64_t>::with_sel);
+  m.impl("ivf_sq8_ip_topk", &IvfOp<IvfSq8, int64_t>::plain);
+  m.impl("ivf_sq8_ip_topk_sel", &IvfOp<IvfSq8, int64_t>::with_sel);
   m.impl("pq_ip_topk", &pq_ip_topk);
   m.impl("sq8_ip_topk", &sq8_ip_topk);
   m.impl("impact_topk", &impact_topk);

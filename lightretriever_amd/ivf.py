@@ -48,8 +48,8 @@ class _IVFCells:
     around one, and the range search over the probed cells (range_search_probed / range_search_preassigned).
     The three cell-major indexes keep their rows or codes in `_store`, row-major [capacity, d] by stored position (_init_store), which is
     reserved, permuted and mapped here; IVFPQIndex overrides _reserve / _permute over the blocked codes of its PQIndex.  A subclass brings
-    _put (rows [a, b) into the store: a copy, or an encode), _topk_cells and _range_cells (the library calls), set_contents, reconstruct_n and
-    persistence."""
+    _put (rows [a, b) into the store: a copy, or an encode), IVF_FAMILY / CODED / _store_operands (what _cells_op, the one place that picks the
+    wrapper and lists its operands, needs to know of it), set_contents, reconstruct_n and persistence."""
 
     NITER = 10
     MAX_POINTS_PER_CENTROID = 256
@@ -287,6 +287,29 @@ class _IVFCells:
                          "eager search with the same number of queries, k and nprobe first")
         return self._topk_cells(q, k, probes, probe_scores, self.max_scan_rows(nprobe), row_map, capture_error, sel)
 
+    # -- the library calls: ops.ivf_<IVF_FAMILY>_ip_topk / _range_search, or their *_sel siblings under a selector -----------------------
+    # A subclass states IVF_FAMILY, _store_operands() (what its ops take between q and list_off) and CODED: whether its ops take probe_scores
+    # and by_residual (the three over codes) or not (the flat one).  sel: the selector's words, as check_selector returns them, or None.
+    def _cells_op(self, name: str, q, probes, probe_scores, sel):
+        """-> (the wrapper ops.<name> or, under a selector, ops.<name>_sel; its operands up to the k or radius)."""
+        a = [q, *self._store_operands(), self.list_off, self.row_ids, probes]
+        if self.CODED:
+            a.append(probe_scores)
+        if sel is not None:
+            name += "_sel"
+            a.append(sel)
+        if self.CODED:
+            a.append(self.by_residual)
+        return getattr(ops, name), a
+
+    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error, sel=None):
+        fn, a = self._cells_op(f"ivf_{self.IVF_FAMILY}_ip_topk", q, probes, probe_scores, sel)
+        return fn(*a, k, max_scan_rows, self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
+
+    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map, sel=None):
+        fn, a = self._cells_op(f"ivf_{self.IVF_FAMILY}_ip_range_search", q, probes, probe_scores, sel)
+        return fn(*a, radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
+
     def range_search(self, q, radius: float):
         raise NotImplementedError(f"{type(self).__name__}.range_search is not served (range search over the probed cells is a follow-up)")
 
@@ -401,19 +424,10 @@ class IVFFlatIndex(_IVFCells):
         self._set_cells(lo, ri)
 
     # -- search: the exact top k, every scanned (query, row) pair scored with the flat index's own bits --------------------------
-    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error, sel=None):
-        if sel is not None:
-            return ops.ivf_flat_ip_topk_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, sel, k, max_scan_rows, self.id_base, row_map,
-                                            ws_slots=vars(self), capture_error=capture_error)
-        return ops.ivf_flat_ip_topk(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, k, max_scan_rows, self.id_base, row_map,
-                                    ws_slots=vars(self), capture_error=capture_error)
+    IVF_FAMILY, CODED = "flat", False
 
-    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map, sel=None):
-        if sel is not None:
-            return ops.ivf_flat_ip_range_search_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, sel, radius, max_scan_rows, self.id_base,
-                                                    row_map, ws_slots=vars(self))
-        return ops.ivf_flat_ip_range_search(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, radius, max_scan_rows, self.id_base, row_map,
-                                            ws_slots=vars(self))
+    def _store_operands(self):
+        return (self._store[:self.ntotal],)
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFFlat, see index_io.py) -------------------------------
     def save(self, fname: str):

@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib
 from .index import _check_range
 from .ivf import _IVFCells, check_ivf_args
 
@@ -96,19 +96,10 @@ class IVFSQIndex(_IVFCells):
         self._set_cells(lo, ri)
 
     # -- search: the exact top k under the score of the class note -----------------------------------------------------------
-    def _topk_cells(self, q, k, probes, probe_scores, max_scan_rows, row_map, capture_error, sel=None):
-        if sel is not None:
-            return ops.ivf_sq_fp16_ip_topk_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, sel, self.by_residual, k,
-                                               max_scan_rows, self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
-        return ops.ivf_sq_fp16_ip_topk(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, k, max_scan_rows,
-                                       self.id_base, row_map, ws_slots=vars(self), capture_error=capture_error)
+    IVF_FAMILY, CODED = "sq_fp16", True
 
-    def _range_cells(self, q, radius, probes, probe_scores, max_scan_rows, row_map, sel=None):
-        if sel is not None:
-            return ops.ivf_sq_fp16_ip_range_search_sel(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, sel, self.by_residual,
-                                                       radius, max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
-        return ops.ivf_sq_fp16_ip_range_search(q, self._store[:self.ntotal], self.list_off, self.row_ids, probes, probe_scores, self.by_residual, radius,
-                                               max_scan_rows, self.id_base, row_map, ws_slots=vars(self))
+    def _store_operands(self):
+        return (self._store[:self.ntotal],)
 
     # -- persistence (faiss.write_index / read_index of an IndexIVFScalarQuantizer, see index_io.py) ----------------------
     def save(self, fname: str, prefix: bytes = b"", append: bool = False):

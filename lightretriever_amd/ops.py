@@ -1,11 +1,13 @@
 """Thin torch-tensor wrappers over the individual liblrx kernels (unit tests, query side, EmbeddingBag construction)."""
 from __future__ import annotations
 
+import collections
 from typing import Optional
 
 import torch
 
 from . import _lib
+from .index import _range_call, _range_empty, _workspace
 
 
 def _s():
@@ -322,18 +324,25 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
 
 
 # -- inverted file (IndexIVFFlat) ---------------------------------------------------------------------------------------------
-# Every family below checks its arguments ONCE, in its _ivf_*_args: -> (Q, dims, head), the leading arguments of its two workspace functions
-# (up to nprobe) and of its two library entries (up to ld_probe / by_residual).  _ivf_topk and _ivf_range add the rest, the same for all four:
+# Every family is described ONCE, by an _IvfFamily: `fam`, the stem of its library names; `args`, its _ivf_*_args, which checks a wrapper's
+# operands (its `n_operands` positionals before the k or radius) -> (Q, dims, head), the leading arguments of its two workspace functions (up to
+# nprobe) and of its four library entries (up to ld_probe / by_residual); `sel_at`, where a *_sel wrapper takes its selector among them.
+# _ivf_topk and _ivf_range are the bodies of all sixteen wrappers and add the rest, the same for all four families:
 # lrx_<fam>_workspace_bytes(*dims, k, max_scan_rows) and lrx_<fam>_search(*head, max_scan_rows, k, id_base, D, I, row_map, ws, bytes, stream),
 # or lrx_<fam>_range_workspace_bytes(*dims, max_scan_rows) and lrx_<fam>_range_search(*head, max_scan_rows, radius, id_base, lims, D, I,
-# capacity, row_map, ws, bytes, stream).  The *_sel wrappers (a search under a row selector, selector.RowSelector) call lrx_<fam>_search_sel /
-# lrx_<fam>_range_search_sel: the same lists with (sel words, n) in front of ws -- `sel` here is (words or None, n), None for the plain wrappers.
-def _ivf_sel(name: str, sel_words, n: int):
-    """(words, n) of a *_sel wrapper's selector: int32 [ceil(n / 32)] contiguous on the device, or None (no filter)."""
-    if sel_words is not None and (sel_words.dtype != torch.int32 or not sel_words.is_cuda or not sel_words.is_contiguous() or
-                                  sel_words.dim() != 1 or sel_words.numel() != (n + 31) // 32):
+# capacity, row_map, ws, bytes, stream).  The plain wrappers are written out: their signatures and docstrings document the operands.
+# _ivf_sel_wrapper makes the *_sel sibling of each (a search under a row selector, selector.RowSelector): `sel` is None in a plain wrapper's
+# body and (words or None,) in a *_sel one's, which calls lrx_<fam>_search_sel / _range_search_sel -- (sel words, n) in front of ws -- even
+# without words.
+_IvfFamily = collections.namedtuple("_IvfFamily", "fam args n_operands sel_at")
+
+
+def _ivf_sel(name: str, words, n: int):
+    """The (sel words, n) arguments of a *_sel entry: the words int32 [ceil(n / 32)] contiguous on the device, or None (no filter)."""
+    if words is not None and (words.dtype != torch.int32 or not words.is_cuda or not words.is_contiguous() or words.dim() != 1 or
+                              words.numel() != (n + 31) // 32):
         raise ValueError(f"{name}: sel must be the int32 words of a selector over the {n} rows of the index: [{(n + 31) // 32}] contiguous")
-    return (sel_words, n)
+    return (_lib.ptr(words), n)
 
 
 def _ivf_probes(name: str, q, probes):
@@ -352,36 +361,39 @@ def _ivf_probe_args(name: str, q, Q, probes, probe_scores, nprobe, ld, by_residu
     return (_lib.ptr(q), Q, _lib.ptr(probes), _lib.ptr(probe_scores) if by_residual else None, nprobe, ld, int(bool(by_residual)))
 
 
-def _ivf_topk(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, k: int, id_base: int, row_map, ws_slots: Optional[dict],
-              capture_error: Optional[str], sel=None):
-    """What the four IVF searches share: the outputs, the workspace (ws_slots: a dict that keeps it between calls, key "_ws") and the call."""
-    from .index import _workspace
-    lib = _lib.lib()
+def _ivf_topk(F: _IvfFamily, name: str, sel, operands, k: int, max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots: Optional[dict] = None,
+              capture_error: Optional[str] = None):
+    """The wrapper `name` of family F over its `operands` (q first): the checks, the outputs, the workspace (ws_slots: a dict that keeps it
+    between calls, key "_ws") and the call."""
+    lib, fam, q = _lib.lib(), F.fam, operands[0]
+    Q, dims, head = F.args(name, *operands)
+    sel_args, sfx = ((), "") if sel is None else (_ivf_sel(name, sel[0], dims[0]), "_sel")
     D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
     I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
     if Q == 0:
         return D, I
     need = int(getattr(lib, f"lrx_{fam}_workspace_bytes")(*dims, k, int(max_scan_rows)))
     ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error)
-    fn, sel_args = (getattr(lib, f"lrx_{fam}_search"), ()) if sel is None else (getattr(lib, f"lrx_{fam}_search_sel"), (_lib.ptr(sel[0]), sel[1]))
-    _lib.check(fn(*head, int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), *sel_args, _lib.ptr(ws), ws.numel(), _s()))
+    _lib.check(getattr(lib, f"lrx_{fam}_search{sfx}")(*head, int(max_scan_rows), k, int(id_base), _lib.ptr(D), _lib.ptr(I), _lib.ptr(row_map), *sel_args,
+                                                      _lib.ptr(ws), ws.numel(), _s()))
     return D, I
 
 
-def _ivf_range(fam: str, q: torch.Tensor, Q: int, dims, head, max_scan_rows: int, radius: float, id_base: int, row_map, ws_slots: Optional[dict],
-               sel=None):
-    """What the four IVF range searches share: the protocol of index._range_call over ONE library call for all Q queries (the library chunks
-    them itself and carries lims on the device) -- outputs sized by a first guess, one host read of lims[Q], one retry when the guess was
-    short.  ws_slots: as _ivf_topk's."""
-    from .index import _range_call, _range_empty, _workspace
-    lib = _lib.lib()
+def _ivf_range(F: _IvfFamily, name: str, sel, operands, radius: float, max_scan_rows: int, id_base: int = 0, row_map=None,
+               ws_slots: Optional[dict] = None):
+    """The range wrapper `name` of family F over its `operands` (q first): the checks, then the protocol of index._range_call over ONE library
+    call for all Q queries (the library chunks them itself and carries lims on the device) -- outputs sized by a first guess, one host read
+    of lims[Q], one retry when the guess was short.  ws_slots: as _ivf_topk's."""
+    lib, fam, q = _lib.lib(), F.fam, operands[0]
+    Q, dims, head = F.args(name, *operands)
+    sel_args, sfx = ((), "") if sel is None else (_ivf_sel(name, sel[0], dims[0]), "_sel")
     if torch.cuda.is_current_stream_capturing():
         raise _lib.LrxError(f"{fam}_range_search under graph capture: the result length is read back to the host")
     if Q == 0:
         return _range_empty(q.device, 0)
     need = int(getattr(lib, f"lrx_{fam}_range_workspace_bytes")(*dims, int(max_scan_rows)))
     ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device)
-    fn, sel_args = (getattr(lib, f"lrx_{fam}_range_search"), ()) if sel is None else (getattr(lib, f"lrx_{fam}_range_search_sel"), (_lib.ptr(sel[0]), sel[1]))
+    fn = getattr(lib, f"lrx_{fam}_range_search{sfx}")
     return _range_call(q.device, Q, Q, lambda s, n, lims, D, I, cap: _lib.check(fn(
         *head, int(max_scan_rows), float(radius), int(id_base), _lib.ptr(lims), _lib.ptr(D), _lib.ptr(I), cap, _lib.ptr(row_map), *sel_args, _lib.ptr(ws),
         ws.numel(), _s())))
@@ -400,8 +412,7 @@ def ivf_flat_ip_range_search(q: torch.Tensor, X: torch.Tensor, list_off: torch.T
     """lrx_ivf_flat_ip_range_search -> (lims i64[Q + 1], D f32[lims[Q]], I i64[lims[Q]]): every row of the cells probes[i] names whose exact
     score is > radius, in SEGMENT order (cells in the order of the probe row, rows by stored position), not sorted.  The arguments are
     ivf_flat_ip_topk's with radius for k.  Reads lims[Q] back to the host: refused under graph capture."""
-    Q, dims, head = _ivf_flat_args("ivf_flat_ip_range_search", q, X, list_off, row_ids, probes)
-    return _ivf_range("ivf_flat_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
+    return _ivf_range(_IVF_FLAT, "ivf_flat_ip_range_search", None, (q, X, list_off, row_ids, probes), radius, max_scan_rows, id_base, row_map, ws_slots)
 
 
 def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor, k: int,
@@ -411,8 +422,7 @@ def ivf_flat_ip_topk(q: torch.Tensor, X: torch.Tensor, list_off: torch.Tensor, r
     contiguous; X fp32 [n, d] rows stored cell by cell; list_off int64 [nlist + 1]; row_ids int64 [n] (original row of a position) or None;
     probes int64 [Q, nprobe] (rows may be strided; < 0 skipped, >= nlist skipped and counted in lrx_device_error_count); max_scan_rows: the
     caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    Q, dims, head = _ivf_flat_args("ivf_flat_ip_topk", q, X, list_off, row_ids, probes)
-    return _ivf_topk("ivf_flat_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
+    return _ivf_topk(_IVF_FLAT, "ivf_flat_ip_topk", None, (q, X, list_off, row_ids, probes), k, max_scan_rows, id_base, row_map, ws_slots, capture_error)
 
 
 def _ivf_pq_args(name: str, q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual):
@@ -434,8 +444,8 @@ def ivf_pq_ip_range_search(q: torch.Tensor, codes: torch.Tensor, pq_centroids: t
                            id_base: int = 0, row_map: Optional[torch.Tensor] = None, ws_slots: Optional[dict] = None):
     """lrx_ivf_pq_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose ADC score -- the value ivf_pq_ip_topk reports -- is
     > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_pq_ip_topk's with radius for k."""
-    Q, dims, head = _ivf_pq_args("ivf_pq_ip_range_search", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_pq_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
+    return _ivf_range(_IVF_PQ, "ivf_pq_ip_range_search", None, (q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual), radius,
+                      max_scan_rows, id_base, row_map, ws_slots)
 
 
 def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -447,8 +457,8 @@ def ivf_pq_ip_topk(q: torch.Tensor, codes: torch.Tensor, pq_centroids: torch.Ten
     [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not by_residual): a scanned row's score
     starts at its cell's probe score when by_residual, at 0 otherwise; max_scan_rows: the caller's bound on the rows one query scans.
     ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    Q, dims, head = _ivf_pq_args("ivf_pq_ip_topk", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_pq_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
+    return _ivf_topk(_IVF_PQ, "ivf_pq_ip_topk", None, (q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual), k, max_scan_rows,
+                     id_base, row_map, ws_slots, capture_error)
 
 
 def _ivf_codes_args(name: str, dtype, dtype_name: str, q, codes, store, list_off, row_ids, probes, probe_scores, by_residual):
@@ -470,8 +480,8 @@ def ivf_sq_fp16_ip_range_search(q: torch.Tensor, codes: torch.Tensor, list_off: 
     """lrx_ivf_sq_fp16_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the fp16 store -- the value
     ivf_sq_fp16_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq_fp16_ip_topk's with
     radius for k."""
-    Q, dims, head = _ivf_codes_args("ivf_sq_fp16_ip_range_search", torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
+    return _ivf_range(_IVF_SQ_FP16, "ivf_sq_fp16_ip_range_search", None, (q, codes, list_off, row_ids, probes, probe_scores, by_residual), radius,
+                      max_scan_rows, id_base, row_map, ws_slots)
 
 
 def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Tensor, row_ids: Optional[torch.Tensor], probes: torch.Tensor,
@@ -483,8 +493,8 @@ def ivf_sq_fp16_ip_topk(q: torch.Tensor, codes: torch.Tensor, list_off: torch.Te
     (rows may be strided; None when not by_residual): a scanned row's score is its cell's probe score plus q . float(code) when by_residual,
     the product alone otherwise; max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace
     between calls (key "_ws")."""
-    Q, dims, head = _ivf_codes_args("ivf_sq_fp16_ip_topk", torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
+    return _ivf_topk(_IVF_SQ_FP16, "ivf_sq_fp16_ip_topk", None, (q, codes, list_off, row_ids, probes, probe_scores, by_residual), k, max_scan_rows,
+                     id_base, row_map, ws_slots, capture_error)
 
 
 def _ivf_sq8_args(name: str, q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual):
@@ -502,8 +512,8 @@ def ivf_sq8_ip_range_search(q: torch.Tensor, codes: torch.Tensor, trained: torch
     """lrx_ivf_sq8_ip_range_search -> (lims, D, I): every row of the cells probes[i] names whose score under the 8-bit store -- the value
     ivf_sq8_ip_topk reports -- is > radius, in segment order (see ivf_flat_ip_range_search).  The arguments are ivf_sq8_ip_topk's with radius
     for k."""
-    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_range_search", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots)
+    return _ivf_range(_IVF_SQ8, "ivf_sq8_ip_range_search", None, (q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual), radius,
+                      max_scan_rows, id_base, row_map, ws_slots)
 
 
 def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor, qtype: int, list_off: torch.Tensor, row_ids: Optional[torch.Tensor],
@@ -515,57 +525,35 @@ def ivf_sq8_ip_topk(q: torch.Tensor, codes: torch.Tensor, trained: torch.Tensor,
     position) or None; probes int64 [Q, nprobe] and probe_scores fp32 of the same shape and row stride (rows may be strided; None when not
     by_residual): a scanned row's score is its cell's probe score plus q . decoded row when by_residual, the product alone otherwise;
     max_scan_rows: the caller's bound on the rows one query scans.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
-    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_topk", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error)
+    return _ivf_topk(_IVF_SQ8, "ivf_sq8_ip_topk", None, (q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual), k, max_scan_rows,
+                     id_base, row_map, ws_slots, capture_error)
+
+
+# -- the four families: (stem of the library names, argument check, operands of a plain wrapper, where a *_sel wrapper takes `sel`) ---------
+_IVF_FLAT = _IvfFamily("ivf_flat_ip", _ivf_flat_args, 5, 5)
+_IVF_PQ = _IvfFamily("ivf_pq_ip", _ivf_pq_args, 8, 7)
+_IVF_SQ_FP16 = _IvfFamily("ivf_sq_fp16_ip", lambda name, q, codes, *rest: _ivf_codes_args(name, torch.float16, "fp16", q, codes, (), *rest), 7, 6)
+_IVF_SQ8 = _IvfFamily("ivf_sq8_ip", _ivf_sq8_args, 9, 8)
 
 
 # -- the searches under a row selector (selector.RowSelector; DESIGN §5.4.15) -----------------------------------------------------------
 # Each wrapper is its plain sibling with `sel` -- the selector's int32 words over the ORIGINAL rows, or None for no filter -- after the last
 # positional tensor, as in torch.ops.lrx.*_sel: the top k (or every hit above the radius) over the SELECTED rows of the probed cells.
-def ivf_flat_ip_topk_sel(q, X, list_off, row_ids, probes, sel, k: int, max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None,
-                         capture_error=None):
-    Q, dims, head = _ivf_flat_args("ivf_flat_ip_topk_sel", q, X, list_off, row_ids, probes)
-    return _ivf_topk("ivf_flat_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_flat_ip_topk_sel", sel, dims[0]))
+def _ivf_sel_wrapper(body, F: _IvfFamily, plain):
+    name, at, end = plain.__name__ + "_sel", F.sel_at, F.n_operands + 1
+
+    def wrapper(*a, **kw):
+        return body(F, name, (a[at],), a[:at] + a[at + 1:end], *a[end:], **kw)
+    wrapper.__name__ = wrapper.__qualname__ = name
+    wrapper.__doc__ = f"{plain.__name__} under a row selector: its arguments with `sel` as positional {at}, its result over the selected rows."
+    return wrapper
 
 
-def ivf_flat_ip_range_search_sel(q, X, list_off, row_ids, probes, sel, radius: float, max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None):
-    Q, dims, head = _ivf_flat_args("ivf_flat_ip_range_search_sel", q, X, list_off, row_ids, probes)
-    return _ivf_range("ivf_flat_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_flat_ip_range_search_sel", sel, dims[0]))
-
-
-def ivf_pq_ip_topk_sel(q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int,
-                       id_base: int = 0, row_map=None, ws_slots=None, capture_error=None):
-    Q, dims, head = _ivf_pq_args("ivf_pq_ip_topk_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_pq_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_pq_ip_topk_sel", sel, dims[0]))
-
-
-def ivf_pq_ip_range_search_sel(q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float, max_scan_rows: int,
-                               id_base: int = 0, row_map=None, ws_slots=None):
-    Q, dims, head = _ivf_pq_args("ivf_pq_ip_range_search_sel", q, codes, pq_centroids, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_pq_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_pq_ip_range_search_sel", sel, dims[0]))
-
-
-def ivf_sq_fp16_ip_topk_sel(q, codes, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int, id_base: int = 0,
-                            row_map=None, ws_slots=None, capture_error=None):
-    name = "ivf_sq_fp16_ip_topk_sel"
-    Q, dims, head = _ivf_codes_args(name, torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel(name, sel, dims[0]))
-
-
-def ivf_sq_fp16_ip_range_search_sel(q, codes, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float, max_scan_rows: int,
-                                    id_base: int = 0, row_map=None, ws_slots=None):
-    name = "ivf_sq_fp16_ip_range_search_sel"
-    Q, dims, head = _ivf_codes_args(name, torch.float16, "fp16", q, codes, (), list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_sq_fp16_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel(name, sel, dims[0]))
-
-
-def ivf_sq8_ip_topk_sel(q, codes, trained, qtype: int, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, k: int, max_scan_rows: int,
-                        id_base: int = 0, row_map=None, ws_slots=None, capture_error=None):
-    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_topk_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_topk("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, k, id_base, row_map, ws_slots, capture_error, _ivf_sel("ivf_sq8_ip_topk_sel", sel, dims[0]))
-
-
-def ivf_sq8_ip_range_search_sel(q, codes, trained, qtype: int, list_off, row_ids, probes, probe_scores, sel, by_residual: bool, radius: float,
-                                max_scan_rows: int, id_base: int = 0, row_map=None, ws_slots=None):
-    Q, dims, head = _ivf_sq8_args("ivf_sq8_ip_range_search_sel", q, codes, trained, qtype, list_off, row_ids, probes, probe_scores, by_residual)
-    return _ivf_range("ivf_sq8_ip", q, Q, dims, head, max_scan_rows, radius, id_base, row_map, ws_slots, _ivf_sel("ivf_sq8_ip_range_search_sel", sel, dims[0]))
+ivf_flat_ip_topk_sel = _ivf_sel_wrapper(_ivf_topk, _IVF_FLAT, ivf_flat_ip_topk)
+ivf_flat_ip_range_search_sel = _ivf_sel_wrapper(_ivf_range, _IVF_FLAT, ivf_flat_ip_range_search)
+ivf_pq_ip_topk_sel = _ivf_sel_wrapper(_ivf_topk, _IVF_PQ, ivf_pq_ip_topk)
+ivf_pq_ip_range_search_sel = _ivf_sel_wrapper(_ivf_range, _IVF_PQ, ivf_pq_ip_range_search)
+ivf_sq_fp16_ip_topk_sel = _ivf_sel_wrapper(_ivf_topk, _IVF_SQ_FP16, ivf_sq_fp16_ip_topk)
+ivf_sq_fp16_ip_range_search_sel = _ivf_sel_wrapper(_ivf_range, _IVF_SQ_FP16, ivf_sq_fp16_ip_range_search)
+ivf_sq8_ip_topk_sel = _ivf_sel_wrapper(_ivf_topk, _IVF_SQ8, ivf_sq8_ip_topk)
+ivf_sq8_ip_range_search_sel = _ivf_sel_wrapper(_ivf_range, _IVF_SQ8, ivf_sq8_ip_range_search)
