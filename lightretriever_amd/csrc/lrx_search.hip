@@ -55,6 +55,7 @@
 #include "lrx_common.h"
 #include <float.h>
 #include <stdlib.h>
+#include <type_traits>
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -351,14 +352,34 @@ struct BoundedPlan {
   int64_t ld, nblk, nblk_ld;            // full shard: score row stride, 128-row blocks, blkmax row stride
   int64_t nsamp_wg, nmain_wg;           // emit: workgroups of the sample / main launch (rb rows each)
   int64_t ld_s, nblk_s, nblk_ld_s;      // emit: the compact sample matrix
-  size_t off_qsplit, off_q16, off_qs3, off_ints, off_parts, off_cand, total;   // byte offsets into the workspace (the score region starts at 0)
+  size_t off_qsplit, off_q16, off_qs3, off_ints, total;   // byte offsets into the workspace (the score region starts at 0; from off_ints on: ChunkWs)
 };
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+static bool shadow_usable(bool has_shadow, int32_t dim) { return has_shadow && dim % 64 == 0; }   // the tiled fp16 shadow: whole 64-wide k-slices only
+static size_t parts_bytes(int nq) { return align256((size_t)nq * REF_CAND * 8); }   // refine slots of a chunk (`parts`; the row-grouped rescoring: one pair per slot)
 
 // flags[nq], any_flag[8] (one per 128-query group of the chunk: the gated fallback of a group runs when one of ITS queries overflowed), ...,
 // the fused kernel's five counters in the last 8
 #define ANY_FLAG_GROUPS (LRX_EMIT_MAX_QUERIES / 128)
 static size_t ints_before_cnt(int nq) { return ((size_t)nq + ANY_FLAG_GROUPS + 8 + 63) & ~(size_t)63; }
+// One query chunk's regions of the workspace, each placed where it is declared.  carve(plan, nq, base) is what the search works on (B = char),
+// what the statistics entries read (B = const char: the same pointers, to const) and, over a null base, what plan_chunk sizes the chunk by.
+template <class B> struct ChunkWs {
+  template <class T> using P = typename std::conditional<std::is_const<B>::value, const T, T>::type*;
+  const BoundedPlan& p; int nq; B* ws;
+  P<float> scores = (P<float>)ws;         // the sample matrix, or the score matrix of the matrix filter and of the gated fallback
+  P<__bf16> qsplit = (P<__bf16>)(ws + p.off_qsplit), q16 = (P<__bf16>)(ws + p.off_q16), qs3 = (P<__bf16>)(ws + p.off_qs3);
+  // ints: flags[nq], any_flag, pad to 64 ints, cnt[nq * CNT_STRIDE] (one memset) | part_cnt[nq * REF_SPLIT] | thr[nq] | eps[nq]
+  P<int> flg = (P<int>)(ws + p.off_ints), any_flag = flg + nq;
+  P<unsigned int> cnt = (P<unsigned int>)(flg + ints_before_cnt(nq));
+  P<FusedCtl> ctl = (P<FusedCtl>)(cnt - 8);
+  P<int> part_cnt = (P<int>)(cnt + (size_t)nq * CNT_STRIDE);
+  P<float> thr = (P<float>)(part_cnt + (size_t)nq * REF_SPLIT), eps = thr + nq;
+  size_t nclear = (size_t)((p.emit ? part_cnt : (P<int>)cnt) - flg);          // the ints that start at zero
+  P<unsigned long long> parts = (P<unsigned long long>)(ws + align256((size_t)((B*)(eps + nq) - ws))), cand = (P<unsigned long long>)((B*)parts + parts_bytes(nq));
+  size_t total = (size_t)((B*)cand - ws) + (p.emit ? (size_t)nq * p.cap * 8 : 0);
+};
+template <class B> static ChunkWs<B> carve(const BoundedPlan& p, int nq, B* ws) { return ChunkWs<B>{p, nq, ws}; }
 
 // Candidate-list capacity and sample stride for top-k: ~k * ss rows reach the sample's k-th score, the fp16 band adds ~30 % -- the list
 // should end up around a third full (a list that overflows sends its query to the exact fallback).  k <= 256: 16 Ki entries and ss = 20
@@ -457,10 +478,7 @@ static BoundedPlan plan_chunk(int64_t n_rows, int32_t dim, int32_t nq, int32_t k
   const size_t nq256 = ((size_t)(nq > 256 ? nq : 256) + 255) & ~(size_t)255;   // (a wide chunk: up to LRX_EMIT_MAX_QUERIES queries)
   p.off_qs3 = align256(p.off_q16 + nq256 * dim * 2);                // planes of the gated fallback, groups of <= 128 queries
   p.off_ints = align256(p.off_qs3 + (nq256 / 128) * split_ws_bytes(dim));
-  // ints: flags[nq], any_flag, pad to 64 ints, cnt[nq * CNT_STRIDE] (one memset) | part_cnt[nq * REF_SPLIT] | thr[nq] | eps[nq]
-  p.off_parts = align256(p.off_ints + sizeof(int) * (ints_before_cnt(nq) + (size_t)nq * (CNT_STRIDE + 2 + REF_SPLIT)));
-  p.off_cand = align256(p.off_parts + (size_t)nq * REF_CAND * 8);
-  p.total = p.off_cand + (p.emit ? (size_t)nq * p.cap * 8 : 0);
+  p.total = carve(p, nq, (const char*)nullptr).total;             // (the int block, the refine slots and the candidate lists: ChunkWs)
   return p;
 }
 
@@ -480,7 +498,7 @@ static int chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t
 }
 
 extern "C" int32_t lrx_flat_ip_bounded_chunk_queries(int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags, int32_t has_shadow) {
-  return chunk_queries(n_rows, dim, n_queries > 0 ? n_queries : 1, k, has_shadow && dim % 64 == 0, flags & 3);
+  return chunk_queries(n_rows, dim, n_queries > 0 ? n_queries : 1, k, shadow_usable(has_shadow, dim), flags & 3);
 }
 
 // the largest chunk plan of a call (its full chunks and its last one, either chain: flags, LRX_SEARCH_FUSED)
@@ -520,15 +538,28 @@ extern "C" int lrx_flat_ip_search_bounded(const float* X, int64_t n_rows, int64_
 // Parts per query of the refine step (the measurements are at their use in bounded_search):
 static int refine_nsplit(int nq) { return (int64_t)nq * REF_SPLIT <= lrx_cu_count() ? REF_SPLIT : ((int64_t)nq * 2 <= lrx_cu_count() ? 2 : 1); }
 // ... and whether the band rows are rescored grouped by row: the pairs must fit the score region, the rule is the measured one (there)
-static int row_group_shift(int32_t dim) { return dim <= 512 ? 5 : (dim <= 1024 ? 4 : (dim <= 2048 ? 3 : 2)); }
-static bool rescore_by_row_groups(const BoundedPlan& p, int64_t n_rows, int64_t ldx, int32_t dim, int32_t nq, int32_t k, int32_t flags) {
-  const int gshift = row_group_shift(dim);
-  const int64_t ngroups = (n_rows + ((int64_t)1 << gshift) - 1) >> gshift;
-  const size_t pair_bytes = align256((size_t)nq * REF_CAND * 8);
-  const size_t need = 2 * pair_bytes + align256((size_t)(ngroups + 2) * 4) * 2 + 256;
-  const bool fits = need <= p.off_qsplit && ((int64_t)1 << gshift) * dim <= ROWGRP_LDS_FLOATS && dim % 4 == 0 && ldx % 4 == 0 && ngroups < (1 << 30);
+// (`use`; its buffers, in bytes from the head of the score region: pairs | sorted | grp_cnt[ngroups + 2] | grp_off[ngroups + 1], total)
+struct RowGroupLayout { bool use; int gshift; int64_t ngroups; size_t pair_bytes, off_sorted, off_grp_cnt, off_grp_off, off_total; };
+static RowGroupLayout row_group_layout(const BoundedPlan& p, int64_t n_rows, int64_t ldx, int32_t dim, int32_t nq, int32_t k, int32_t flags) {
+  RowGroupLayout g;
+  g.gshift = dim <= 512 ? 5 : (dim <= 1024 ? 4 : (dim <= 2048 ? 3 : 2));
+  g.ngroups = (n_rows + ((int64_t)1 << g.gshift) - 1) >> g.gshift;
+  g.off_sorted = g.pair_bytes = parts_bytes(nq);
+  g.off_grp_cnt = 2 * g.pair_bytes;
+  g.off_grp_off = g.off_grp_cnt + align256((size_t)(g.ngroups + 2) * 4);
+  g.off_total = g.off_grp_off + (size_t)(g.ngroups + 1) * 4;
+  const size_t need = 2 * g.pair_bytes + align256((size_t)(g.ngroups + 2) * 4) * 2 + 256;
+  const bool fits = need <= p.off_qsplit && ((int64_t)1 << g.gshift) * dim <= ROWGRP_LDS_FLOATS && dim % 4 == 0 && ldx % 4 == 0 && g.ngroups < (1 << 30);
   const bool rule = dim >= 2048 && (int64_t)nq * k * 5 / 4 >= (5 * n_rows) / 2;
-  return fits && !(flags & 32) && (rule || (flags & 16));
+  g.use = fits && !(flags & 32) && (rule || (flags & 16));
+  return g;
+}
+// Whether a call over fp32 rows takes the plain path (lrx_flat_ip_search; nothing of the chunk layout in the workspace): tiny shards and odd widths
+// do; so do small query batches without a shadow (HBM-bound on the exact-fp32 kernel already).  (The codes never take it, yet the statistics
+// entries apply it to them too: a forced score-free filter over <= REF_CAND codes keeps lists and is reported as plain, its counts as zero.)
+static bool plain_path(int64_t n_rows, int32_t dim, int32_t n_queries, bool shadow) {
+  const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;
+  return (qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0;
 }
 
 // The bounded search over either row source (lrx_search_select.h, row_dot): RS = ROWS_F32 -- X = fp32 rows (stride ldx), X_shadow = their
@@ -541,10 +572,8 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
                           const float* q, int32_t n_queries, int32_t k, int64_t id_base, float* out_scores, int64_t* out_ids,
                           const int64_t* row_map, uint64_t* out_wire, void* workspace, size_t workspace_bytes, int32_t flags, void* stream) {
   const int mode = flags & 3;
-  const bool shadow = X_shadow != nullptr && dim % 64 == 0;
-  const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;
-  // tiny shards and odd widths take the plain path; so do small query batches without a shadow (HBM-bound on the exact-fp32 kernel already)
-  if (RS == ROWS_F32 && ((qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0)) {
+  const bool shadow = shadow_usable(X_shadow != nullptr, dim);
+  if (RS == ROWS_F32 && plain_path(n_rows, dim, n_queries, shadow)) {
     for (int q0 = 0; q0 < n_queries; q0 += 128) {
       const int nq = n_queries - q0 < 128 ? n_queries - q0 : 128;
       const int rc = lrx_flat_ip_search(X, n_rows, ldx, dim, row_bounds, q + (int64_t)q0 * dim, nq, k, id_base, out_scores + (int64_t)q0 * k,
@@ -568,31 +597,19 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
     const float* qc = q + (int64_t)q0 * dim;
     float* osc = out_scores + (int64_t)q0 * k;
     int64_t* oic = out_ids + (int64_t)q0 * k;
-    char* ws = (char*)workspace;
-    float* scores = (float*)ws;
-    __bf16* qsplit = (__bf16*)(ws + p.off_qsplit);
-    int* flg = (int*)(ws + p.off_ints);
-    int* any_flag = flg + nq;                 // [ANY_FLAG_GROUPS]: one per 128-query group of the chunk
-    unsigned int* cnt = (unsigned int*)(flg + ints_before_cnt(nq));
-    int* part_cnt = (int*)(cnt + (size_t)nq * CNT_STRIDE);
-    float* thr = (float*)(part_cnt + (size_t)nq * REF_SPLIT);
-    float* eps = thr + nq;
-    unsigned long long* parts = (unsigned long long*)(ws + p.off_parts);
-    unsigned long long* cand = (unsigned long long*)(ws + p.off_cand);
+    const ChunkWs<char> w = carve(p, nq, (char*)workspace);
     // flags, any_flag, list counts start at zero: cleared by the query-packing kernel of the first filter launch when there is one
-    const size_t nclear = ints_before_cnt(nq) + (p.emit ? (size_t)nq * CNT_STRIDE : 0);
-    const bool clear_in_pack = shadow && nclear < (1u << 30);
-    if (!clear_in_pack) LRX_HIP(hipMemsetAsync(flg, 0, sizeof(int) * nclear, s));
+    const bool clear_in_pack = shadow && w.nclear < (1u << 30);
+    if (!clear_in_pack) LRX_HIP(hipMemsetAsync(w.flg, 0, sizeof(int) * w.nclear, s));
     // ... and so are the hi/mid/lo query planes of the gated six-product fallback (groups of <= 128 queries; <= 32 queries run the
     // exact-fp32 kernel, which needs none)
-    __bf16* qs3 = (__bf16*)(ws + p.off_qs3);
     const int64_t qs3_stride = (int64_t)(split_ws_bytes(dim) / sizeof(__bf16));
     // (per 256-query sub-chunk j of the chunk: the plane sets of its two 128-query groups, qs3 + (2 j + g) * stride)
     auto presplit_of = [&](int j) {
       PreSplit ps;
       if (!shadow || RS == ROWS_F16T) return ps;              // (no six-product fallback over codes)
       const int n0 = j * 256, nj = nq - n0 < 256 ? nq - n0 : 256;
-      ps.qs3 = qs3 + (int64_t)(2 * j) * qs3_stride;
+      ps.qs3 = w.qs3 + (int64_t)(2 * j) * qs3_stride;
       ps.stride = qs3_stride;
       for (int f0 = 0, g = 0; f0 < nj; f0 += 128, ++g) {
         const int nf = nj - f0 < 128 ? nj - f0 : 128, qtf = (nf + 15) / 16;
@@ -608,24 +625,23 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
     int rc;
     int nsplit = REF_SPLIT;                   // parts per query of the refine step
     if (p.emit) {
-      float* blkmax = scores + p.ld_s * (int64_t)nq;
+      float* blkmax = w.scores + p.ld_s * (int64_t)nq;
       FilterMode fs;                                          // (sample pass of the 128-row kernels; chunks on the GEMM kernel sample in 256-row tiles there)
       fs.bmode = 1; fs.ss = p.ss; fs.unit = 1; fs.nblocks = p.nsamp_wg;
       fs.group_max = shadow;                                  // the register-streaming kernels hand over the maxima of their 16-row wave groups
-      if (clear_in_pack) { fs.zero = flg; fs.nzero = (int)nclear; }
+      if (clear_in_pack) { fs.zero = w.flg; fs.nzero = (int)w.nclear; }
       fs.presplit = presplit;
       FusedArgs fa;
       if (p.fused && clear_in_pack) {
         fa.ld_s = p.ld_s; fa.nblk_s = (int)p.nblk_s; fa.nblk_ld_s = (int)p.nblk_ld_s; fa.nsamp = (int)p.nsamp_wg; fa.nmain = (int)p.nmain_wg; fa.ss = p.ss; fa.k = k;
-        fa.bounds = row_bounds; fa.thr = thr; fa.eps = eps; fa.cand = cand; fa.cnt = cnt; fa.cap = p.cap;
-        fa.ctl = (FusedCtl*)(flg + ints_before_cnt(nq) - 8);
+        fa.bounds = row_bounds; fa.thr = w.thr; fa.eps = w.eps; fa.cand = w.cand; fa.cnt = w.cnt; fa.cap = p.cap;
+        fa.ctl = w.ctl;
         // (sample + selection + main pass, always; LRX_FUSED_PHASES bit 7 in a dev build adds the per-workgroup phase stamps of lrx_probe_fused_timestamps)
         static const int fused_stamps = lrx_dev_knob("LRX_FUSED_PHASES", 0) & 128;
         fa.phases = 7 | fused_stamps;
         fa.rs = RS;
         fs.fused = &fa;
       }
-      __bf16* q16 = (__bf16*)(ws + p.off_q16);
       if (p.gemm) {
         // More than 128 queries over a shadow of D >= 1024: BOTH passes on the GEMM kernel (round 6; the 128-row register-streaming kernel needs
         // 170 us for one sample block at 16 query tiles).  The packing kernel still runs once per 256-query sub-chunk: it clears the ints of the
@@ -635,28 +651,28 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
           PreSplit ps = presplit_of(j);
           ps.nb_xb = ((dim / 64) * 2 * qtj * 64 + 255) / 256;
           hipLaunchKernelGGL(k_pack_queries_xb, dim3(ps.nb_xb + (ps.ngroups > 0 ? ps.blocks[0] + ps.blocks[1] : 0)), dim3(256), 0, s, qc + (int64_t)n0 * dim, nj, dim, qtj,
-                             qsplit, j == 0 ? fs.zero : (int*)nullptr, j == 0 ? fs.nzero : 0, ps);
+                             w.qsplit, j == 0 ? fs.zero : (int*)nullptr, j == 0 ? fs.nzero : 0, ps);
           LRX_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL(k_round_queries, dim3((unsigned)lrx_cdiv((int64_t)nq * dim, 1024)), dim3(256), 0, s, qc, (int64_t)nq * dim, q16);
+        hipLaunchKernelGGL(k_round_queries, dim3((unsigned)lrx_cdiv((int64_t)nq * dim, 1024)), dim3(256), 0, s, qc, (int64_t)nq * dim, w.q16);
         LRX_LAUNCH_CHECK();
-        rc = lrx_gemm_filter_sample_launch(X_shadow, q16, n_rows, nq, dim, p.ss, p.nsamp_wg, scores, blkmax, p.ld_s, (int)p.nblk_ld_s, s);
+        rc = lrx_gemm_filter_sample_launch(X_shadow, w.q16, n_rows, nq, dim, p.ss, p.nsamp_wg, w.scores, blkmax, p.ld_s, (int)p.nblk_ld_s, s);
       } else {
-        rc = launch_scores(X, n_rows, ldx, dim, qc, nq, scores, blkmax, qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, p.ld_s, fs);
+        rc = launch_scores(X, n_rows, ldx, dim, qc, nq, w.scores, blkmax, w.qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, p.ld_s, fs);
       }
       if (rc != LRX_OK) return rc;
       if (fs.fused == nullptr)
-      hipLaunchKernelGGL(k_sample_threshold<RS>, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld_s, p.nsamp_wg * p.rb, k, (const float*)blkmax,
-                         (int)p.nblk_s, (int)p.nblk_ld_s, qc, dim, row_bounds, p.rb, p.ss, n_rows, thr, eps, cand, cnt, fs.group_max ? 16 : 128, p.cap);
+      hipLaunchKernelGGL(k_sample_threshold<RS>, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)w.scores, p.ld_s, p.nsamp_wg * p.rb, k, (const float*)blkmax,
+                         (int)p.nblk_s, (int)p.nblk_ld_s, qc, dim, row_bounds, p.rb, p.ss, n_rows, w.thr, w.eps, w.cand, w.cnt, fs.group_max ? 16 : 128, p.cap);
       LRX_LAUNCH_CHECK();
       if (fs.fused != nullptr) {
         rc = LRX_OK;                                            // sample, selection and main pass are done
       } else if (p.gemm) {
-        rc = lrx_gemm_filter_emit_launch(X_shadow, q16, n_rows, nq, dim, p.ss, p.nmain_wg, thr, cand, cnt, p.cap, s);
+        rc = lrx_gemm_filter_emit_launch(X_shadow, w.q16, n_rows, nq, dim, p.ss, p.nmain_wg, w.thr, w.cand, w.cnt, p.cap, s);
       } else {
         FilterMode fm;
-        fm.bmode = 2; fm.ss = p.ss; fm.nblocks = p.nmain_wg; fm.thr = thr; fm.cand = cand; fm.cnt = cnt; fm.cap = p.cap;
-        rc = launch_scores(X, n_rows, ldx, dim, qc, nq, nullptr, nullptr, qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, p.ld, fm);
+        fm.bmode = 2; fm.ss = p.ss; fm.nblocks = p.nmain_wg; fm.thr = w.thr; fm.cand = w.cand; fm.cnt = w.cnt; fm.cap = p.cap;
+        rc = launch_scores(X, n_rows, ldx, dim, qc, nq, nullptr, nullptr, w.qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, p.ld, fm);
       }
       if (rc != LRX_OK) return rc;
       // parts per query: the 1024-thread workgroups of the refine step run one per CU, so REF_SPLIT x nq of them beyond the CU count take
@@ -672,76 +688,66 @@ static int bounded_search(const float* X, int64_t n_rows, int64_t ldx, int32_t d
       // Row-grouped rescoring where the chunk wants every row more than twice on average (~1.2 k band rows per query): the pairs and the
       // group counters live in the score region, which nothing reads between the sample's selection and the gated fallback.
       RowPairs rp = {nullptr, nullptr, nullptr, 0};
-      {
-        const int gshift = row_group_shift(dim);
-        const int64_t ngroups = (n_rows + ((int64_t)1 << gshift) - 1) >> gshift;
-        const size_t pair_bytes = align256((size_t)nq * REF_CAND * 8);
-        // measured (tools/exp/refine_rows_ab.py, profiles/r05_refine_rows_ab.txt; gather / by row, ms): 1000 queries, k = 1000 over 50 k x 2048 1.98 / 1.47,
-        // 100 k x 2048 2.20 / 2.14, 100 k x 4096 4.50 / 4.02, but 100 k x 1024 1.46 / 1.57, 200 k x 2048 2.82 / 3.49, k = 100 0.81 / 1.51: rows of
-        // >= 8 KiB that the chunk wants >= 2.5 times on average (~1.25 k band rows per query)
-        if (rescore_by_row_groups(p, n_rows, ldx, dim, nq, k, flags)) {
-          char* b = ws;
-          rp.pairs = (unsigned long long*)b;
-          unsigned long long* sorted = (unsigned long long*)(b + pair_bytes);
-          rp.grp_cnt = (unsigned int*)(b + 2 * pair_bytes);
-          unsigned int* grp_off = (unsigned int*)(b + 2 * pair_bytes + align256((size_t)(ngroups + 2) * 4));
-          rp.total = grp_off + ngroups + 1;
-          rp.grp_shift = gshift;
-          LRX_HIP(hipMemsetAsync(rp.grp_cnt, 0, (size_t)((char*)(rp.total + 1) - (char*)rp.grp_cnt), s));
-          hipLaunchKernelGGL(k_refine_band<RS>, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
-                             (const unsigned int*)cnt, (const float*)eps, k, parts, part_cnt, nsplit, p.cap, rp);
-          LRX_LAUNCH_CHECK();
-          hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, (const unsigned int*)rp.grp_cnt, grp_off, (int)ngroups);
-          LRX_LAUNCH_CHECK();
-          hipLaunchKernelGGL(k_pairs_scatter, dim3((unsigned)(4 * lrx_cu_count())), dim3(256), 0, s, (const unsigned long long*)rp.pairs, (const unsigned int*)rp.total,
-                             rp.grp_cnt, (const unsigned int*)grp_off, gshift, sorted);
-          LRX_LAUNCH_CHECK();
-          hipLaunchKernelGGL(k_rescore_row_groups<RS>, dim3((unsigned)ngroups), dim3(ROWGRP_THREADS), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)sorted,
-                             (const unsigned int*)grp_off, gshift, parts);
-          LRX_LAUNCH_CHECK();
-        }
+      char* b = (char*)w.scores;
+      // measured (tools/exp/refine_rows_ab.py, profiles/r05_refine_rows_ab.txt; gather / by row, ms): 1000 queries, k = 1000 over 50 k x 2048 1.98 / 1.47,
+      // 100 k x 2048 2.20 / 2.14, 100 k x 4096 4.50 / 4.02, but 100 k x 1024 1.46 / 1.57, 200 k x 2048 2.82 / 3.49, k = 100 0.81 / 1.51: rows of
+      // >= 8 KiB that the chunk wants >= 2.5 times on average (~1.25 k band rows per query)
+      const RowGroupLayout g = row_group_layout(p, n_rows, ldx, dim, nq, k, flags);
+      if (g.use) {
+        rp = {(unsigned long long*)b, (unsigned int*)(b + g.off_total), (unsigned int*)(b + g.off_grp_cnt), g.gshift};   // pairs, total, grp_cnt, grp_shift
+        LRX_HIP(hipMemsetAsync(rp.grp_cnt, 0, g.off_total + 4 - g.off_grp_cnt, s));
       }
-      if (rp.pairs == nullptr) {
-        hipLaunchKernelGGL(k_refine_band<RS>, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)cand,
-                           (const unsigned int*)cnt, (const float*)eps, k, parts, part_cnt, nsplit, p.cap, rp);
+      hipLaunchKernelGGL(k_refine_band<RS>, dim3(nq, nsplit), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)w.cand,
+                         (const unsigned int*)w.cnt, (const float*)w.eps, k, w.parts, w.part_cnt, nsplit, p.cap, rp);
+      LRX_LAUNCH_CHECK();
+      if (rp.pairs != nullptr) {
+        unsigned long long* sorted = (unsigned long long*)(b + g.off_sorted);
+        unsigned int* grp_off = (unsigned int*)(b + g.off_grp_off);
+        hipLaunchKernelGGL(k_pairs_scan, dim3(1), dim3(1024), 0, s, (const unsigned int*)rp.grp_cnt, grp_off, (int)g.ngroups);
+        LRX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_pairs_scatter, dim3((unsigned)(4 * lrx_cu_count())), dim3(256), 0, s, (const unsigned long long*)rp.pairs, (const unsigned int*)rp.total,
+                           rp.grp_cnt, (const unsigned int*)grp_off, g.gshift, sorted);
+        LRX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_rescore_row_groups<RS>, dim3((unsigned)g.ngroups), dim3(ROWGRP_THREADS), 0, s, X, n_rows, ldx, dim, qc, (const unsigned long long*)sorted,
+                           (const unsigned int*)grp_off, g.gshift, w.parts);
         LRX_LAUNCH_CHECK();
       }
     } else {
-      float* blkmax = scores + p.ld * (int64_t)nq;
+      float* blkmax = w.scores + p.ld * (int64_t)nq;
       FilterMode fa;
-      if (clear_in_pack) { fa.zero = flg; fa.nzero = (int)nclear; }
+      if (clear_in_pack) { fa.zero = w.flg; fa.nzero = (int)w.nclear; }
       fa.presplit = presplit;
-      rc = launch_scores(X, n_rows, ldx, dim, qc, nq, scores, blkmax, qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, 0, fa);
+      rc = launch_scores(X, n_rows, ldx, dim, qc, nq, w.scores, blkmax, w.qsplit, stream, 1, nullptr, shadow ? X_shadow : nullptr, 0, fa);
       if (rc != LRX_OK) return rc;
-      hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld, n_rows, k, id_base, (const float*)blkmax, (int)p.nblk,
+      hipLaunchKernelGGL(k_topk_select, dim3(nq), dim3(SEL_THREADS), 0, s, (const float*)w.scores, p.ld, n_rows, k, id_base, (const float*)blkmax, (int)p.nblk,
                          (int)p.nblk_ld, osc, oic, (const int*)nullptr, (const int*)nullptr);
       LRX_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_refine_topk<RS>, dim3(nq, REF_SPLIT), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const float*)scores, p.ld, (const float*)blkmax,
-                         (int)p.nblk, (int)p.nblk_ld, row_bounds, k, id_base, (const float*)osc, parts, part_cnt);
+      hipLaunchKernelGGL(k_refine_topk<RS>, dim3(nq, REF_SPLIT), dim3(1024), 0, s, X, n_rows, ldx, dim, qc, (const float*)w.scores, p.ld, (const float*)blkmax,
+                         (int)p.nblk, (int)p.nblk_ld, row_bounds, k, id_base, (const float*)osc, w.parts, w.part_cnt);
       LRX_LAUNCH_CHECK();
     }
     // (1024 threads: with 256 the sort of the typical 300-500 band rows took 20 instead of 14 us)
-    hipLaunchKernelGGL(k_refine_merge, dim3(nq), dim3(1024), 0, s, (const unsigned long long*)parts, (const int*)part_cnt, n_rows, k, id_base, osc, oic,
-                       flg, any_flag, nsplit);
+    hipLaunchKernelGGL(k_refine_merge, dim3(nq), dim3(1024), 0, s, (const unsigned long long*)w.parts, (const int*)w.part_cnt, n_rows, k, id_base, osc, oic,
+                       w.flg, w.any_flag, nsplit);
     LRX_LAUNCH_CHECK();
     // gated fallback for the flagged queries (every kernel returns immediately on the device when nothing overflowed), 128 queries at
     // a time over the same score region
     for (int f0 = 0; f0 < nq; f0 += 128) {
       const int nf = nq - f0 < 128 ? nq - f0 : 128;
-      float* blkmax = scores + p.ld * (int64_t)nf;
+      float* blkmax = w.scores + p.ld * (int64_t)nf;
       FilterMode ff;
       const PreSplit psf = presplit_of(f0 / 256);
       ff.planes_ready = psf.ngroups > 0;                      // written by the packing kernel(s) at the head of the chain
-      const int* gate = any_flag + f0 / 128;                  // this group's flag: raised by k_refine_merge when one of its queries overflowed
+      const int* gate = w.any_flag + f0 / 128;                // this group's flag: raised by k_refine_merge when one of its queries overflowed
       if (RS == ROWS_F16T)   // (the one-product score matrix over the codes: query_eps_block<ROWS_F16T> bounds its error)
-        rc = launch_scores(nullptr, n_rows, dim, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, qsplit, stream, 1, gate, X_shadow, 0, FilterMode());
+        rc = launch_scores(nullptr, n_rows, dim, dim, qc + (int64_t)f0 * dim, nf, w.scores, blkmax, w.qsplit, stream, 1, gate, X_shadow, 0, FilterMode());
       else
-        rc = launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, scores, blkmax, ff.planes_ready ? qs3 + (f0 / 128) * qs3_stride : qsplit, stream, 3,
+        rc = launch_scores(X, n_rows, ldx, dim, qc + (int64_t)f0 * dim, nf, w.scores, blkmax, ff.planes_ready ? w.qs3 + (f0 / 128) * qs3_stride : w.qsplit, stream, 3,
                            gate, nullptr, 0, ff);
       if (rc != LRX_OK) return rc;
-      hipLaunchKernelGGL(k_topk_select_rescore<RS>, dim3(nf), dim3(SEL_THREADS), 0, s, (const float*)scores, p.ld, n_rows, k, id_base, (const float*)blkmax,
+      hipLaunchKernelGGL(k_topk_select_rescore<RS>, dim3(nf), dim3(SEL_THREADS), 0, s, (const float*)w.scores, p.ld, n_rows, k, id_base, (const float*)blkmax,
                          (int)p.nblk, (int)p.nblk_ld, X, ldx, dim, qc + (int64_t)f0 * dim, osc + (int64_t)f0 * k, oic + (int64_t)f0 * k,
-                         gate, (const int*)(flg + f0), row_bounds,
+                         gate, (const int*)(w.flg + f0), row_bounds,
                          out_wire != nullptr ? (unsigned long long*)out_wire + ((int64_t)q0 + f0) * k : (unsigned long long*)nullptr, row_map);
       LRX_LAUNCH_CHECK();
     }
@@ -835,21 +841,17 @@ __global__ void k_copy_list_counts(const unsigned int* __restrict__ cnt, int nq,
 }
 extern "C" int lrx_flat_ip_bounded_list_counts(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
                                                int32_t has_shadow, uint32_t* counts_out, void* stream) {
-  const bool shadow = has_shadow && dim % 64 == 0;
+  const bool shadow = shadow_usable(has_shadow, dim);
   LRX_CHECK_ARG(workspace && counts_out && n_queries > 0 && n_queries <= (shadow ? LRX_EMIT_MAX_QUERIES : 128), "bounded_list_counts: one query chunk only (n_queries=%d)", n_queries);
   const BoundedPlan p = plan_chunk(n_rows, dim, n_queries, k, shadow, flags & 3, fused_pref_of(flags));
-  const int* flg = (const int*)((const char*)workspace + p.off_ints);
-  // (the same test lrx_flat_ip_search_bounded_wire uses to send a call down the plain path, which keeps no lists)
-  const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;
-  const bool plain = (qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0;
-  const unsigned int* cnt = p.emit && !plain ? (const unsigned int*)(flg + ints_before_cnt(n_queries)) : nullptr;
+  const unsigned int* cnt = p.emit && !plain_path(n_rows, dim, n_queries, shadow) ? carve(p, n_queries, (const char*)workspace).cnt : nullptr;
   hipLaunchKernelGGL(k_copy_list_counts, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream, cnt, n_queries, counts_out);
   LRX_LAUNCH_CHECK();
   return LRX_OK;
 }
 
 // The stage state of the LAST chunk of the last bounded search that used `workspace` (tests: every stage against an fp64 model, not only the
-// final result).  Same arguments as that search (and as lrx_flat_ip_bounded_list_counts) + its ldx; the layout is re-derived by plan_chunk.
+// final result).  Same arguments as that search (and as lrx_flat_ip_bounded_list_counts) + its ldx; the pointers are the search's own: carve, read-only.
 // Read-only: copy kernels on `stream`, no synchronisation, no allocation, nothing written to the workspace.  include/lrx.h has the outputs.
 // grid (nq, y): every workgroup copies a slice of its query's list entries; workgroup (q, 0) also writes the query's scalars, (0, 0) any_flag.
 __global__ void __launch_bounds__(256)
@@ -884,27 +886,23 @@ k_copy_chunk_state(const int* __restrict__ flg, const int* __restrict__ any_flag
 extern "C" int lrx_flat_ip_bounded_chunk_state(const void* workspace, int64_t n_rows, int32_t dim, int32_t n_queries, int32_t k, int32_t flags,
                                                int32_t has_shadow, int64_t ldx, int32_t* plan_out, float* thr_eps_out, int32_t* ints_out,
                                                int32_t max_entries, float* entry_scores, int64_t* entry_rows, void* stream) {
-  const bool shadow = has_shadow && dim % 64 == 0;
+  const bool shadow = shadow_usable(has_shadow, dim);
   LRX_CHECK_ARG(workspace && plan_out && thr_eps_out && ints_out && n_queries > 0 && n_queries <= (shadow ? LRX_EMIT_MAX_QUERIES : 128),
                 "bounded_chunk_state: one query chunk only (n_queries=%d)", n_queries);
   LRX_CHECK_ARG(k > 0 && k <= SEL_MAXK && max_entries >= 0 && (max_entries == 0 || (entry_scores && entry_rows)), "bounded_chunk_state: k=%d max_entries=%d", k, max_entries);
   const BoundedPlan p = plan_chunk(n_rows, dim, n_queries, k, shadow, flags & 3, fused_pref_of(flags));
-  const int qt_max = ((n_queries < 128 ? n_queries : 128) + 15) / 16;     // (the plain-path test of bounded_search, as in the list counts above)
-  const bool plain = (qt_max < SPLIT_MIN_QT && !shadow) || n_rows <= REF_CAND || dim % 4 != 0;
+  const bool plain = plain_path(n_rows, dim, n_queries, shadow);
   const bool lists = p.emit && !plain;
   const int nsplit = lists ? refine_nsplit(n_queries) : REF_SPLIT;
   const int32_t plan[LRX_CHUNK_STATE_PLAN_INTS] = {lists, lists && p.fused, lists && p.gemm, p.ss, p.rb, (int32_t)p.cap, nsplit,
-                                                   lists && rescore_by_row_groups(p, n_rows, ldx, dim, n_queries, k, flags), shadow ? 16 : 128,
+                                                   lists && row_group_layout(p, n_rows, ldx, dim, n_queries, k, flags).use, shadow ? 16 : 128,
                                                    (int32_t)p.nsamp_wg, plain, 0};
   memcpy(plan_out, plan, sizeof(plan));
   if (plain) return LRX_OK;                                                // (the plain path keeps nothing of this layout in the workspace: plan_out says so)
-  const int* flg = (const int*)((const char*)workspace + p.off_ints);
-  const unsigned int* cnt = (const unsigned int*)(flg + ints_before_cnt(n_queries));
-  const int* part_cnt = (const int*)(cnt + (size_t)n_queries * CNT_STRIDE);
-  const float* thr = (const float*)(part_cnt + (size_t)n_queries * REF_SPLIT);
+  const ChunkWs<const char> w = carve(p, n_queries, (const char*)workspace);
   const int ny = lists && max_entries > 0 ? (max_entries < 16 * 256 ? (max_entries + 255) / 256 : 16) : 1;
-  hipLaunchKernelGGL(k_copy_chunk_state, dim3(n_queries, ny), dim3(256), 0, (hipStream_t)stream, flg, flg + n_queries, lists ? cnt : (const unsigned int*)nullptr,
-                     part_cnt, thr, thr + n_queries, (const unsigned long long*)((const char*)workspace + p.off_cand), n_queries, nsplit, p.cap,
+  hipLaunchKernelGGL(k_copy_chunk_state, dim3(n_queries, ny), dim3(256), 0, (hipStream_t)stream, w.flg, w.any_flag, lists ? w.cnt : (const unsigned int*)nullptr,
+                     w.part_cnt, w.thr, w.eps, w.cand, n_queries, nsplit, p.cap,
                      lists ? max_entries : 0, thr_eps_out, ints_out, entry_scores, entry_rows);
   LRX_LAUNCH_CHECK();
   return LRX_OK;
@@ -920,7 +918,7 @@ struct RangePlan {
   size_t off_blkmax, off_qsplit, off_ints, off_cand, off_bits, off_pre, total;
 };
 static bool range_list_path(int64_t n_rows, int32_t dim, bool has_shadow) {
-  return has_shadow && dim % 64 == 0 && n_rows > REF_CAND && n_rows < (1ll << 31);
+  return shadow_usable(has_shadow, dim) && n_rows > REF_CAND && n_rows < (1ll << 31);
 }
 // ints: cnt[nq * CNT_STRIDE] | flags[nq] | any_flag[ANY_FLAG_GROUPS] | surv[nq] | thr[nq]
 static RangePlan range_plan(int64_t n_rows, int32_t dim, int32_t nq, bool list) {
