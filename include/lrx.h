@@ -212,7 +212,8 @@ int lrx_embedding_gather(const void* table, const int32_t* ids, int32_t n_tokens
  * that were empty or shorter than their pooling strategy needs (lrx_pool_norm_mode, the last-row gathers and scatter), plus the candidate
  * entries >= n_rows that lrx_flat_ip_rerank / lrx_sq_fp16_ip_rerank skipped, plus what lrx_ivf_flat_ip_search / lrx_ivf_pq_ip_search /
  * lrx_ivf_sq_fp16_ip_search / lrx_ivf_sq_fp16_encode_rows / lrx_ivf_sq8_ip_search / lrx_ivf_sq8_encode_rows / lrx_ivf_sq8_decode_rows count (probe entries >= nlist, queries over max_scan_rows, stored rows outside the
- * shard, rows encoded for a cell outside [0, nlist)), plus the rows outside [0, n_bits) that lrx_selector_set_rows skipped; -1 if the read
+ * shard, rows encoded for a cell outside [0, nlist)), plus the rows outside [0, n_bits) that lrx_selector_set_rows skipped, plus the entry-list
+ * and graph-table entries >= n_rows that lrx_graph_ip_search skipped (one per time such an entry is met); -1 if the read
  * failed.  Non-zero = the rows of those calls are not the model's.  SYNCHRONISES the device (a blocking copy): call it at a point where
  * the caller waits for results anyway (LrxExactSearchModel.encode does, once per encode call, and raises).                         */
 int64_t lrx_device_error_count(int32_t reset);
@@ -1104,6 +1105,49 @@ int lrx_ivf_sq8_encode_rows(const float* x, int64_t ldx, int64_t n, int32_t dim,
                             const float* trained, int32_t qtype, void* codes, int64_t row0, void* stream);
 int lrx_ivf_sq8_decode_rows(const void* codes, int64_t row0, int64_t n, int32_t dim, const float* trained, int32_t qtype, const float* centroids,
                             const int64_t* cells, int32_t nlist, float* out, int64_t ldo, void* stream);
+
+/* (added in ABI 9, additively) GRAPH: beam search over a fixed-degree neighbour graph -- the role faiss gives GpuIndexCagra / IndexHNSWCagra
+ * (GraphFlatIndex).  The caller owns the coarse step: it passes each query's entry rows.  Every output is fixed by this text:
+ * the traversal is a deterministic function of the scores, the graph and the entry lists.
+ *   graph       graph[u * degree + j], j < degree: int32 rows, -1 = no edge.  Row-major, contiguous.
+ *   score       the flat index's score over the fp32 rows X[row * ldx + c], (float) of the fp64 sum of the fp32 products, by the device function
+ *               of lrx_flat_ip_rerank: bit for bit what that entry reports for the (query, row) pair.
+ *   order       everywhere (beam, output): score descending, ties to the lower row.
+ *   start       the beam is the best `beam` of the query's DISTINCT VALID entry rows entry_rows[i * ld_entry + j], j < n_entry.  An entry < 0 is
+ *               skipped.  An entry >= n_rows is NEVER dereferenced: it is skipped and counted in lrx_device_error_count.
+ *   step        the first `width` beam entries not yet expanded, in beam order, are marked expanded and their graph rows gathered.  A graph
+ *               entry is skipped when it is -1, or >= n_rows (never dereferenced; counted as above), or a row already scored for this query.
+ *               Each remaining row is scored once; the beam becomes the best `beam` of (beam U new rows).  Marks travel with their entries.
+ *   stop        when no beam entry is unexpanded, or after max_iterations steps (0 = the default ceil(beam / width) + 32).  The loop is bounded
+ *               by that count alone: no spin-wait, no communication between workgroups, no grid barrier.
+ *   result      the first k beam entries, (-FLT_MAX, -1) where fewer exist.  out_ids = id_base + row, or row_map[row] when row_map != NULL
+ *               (int64 [>= n_rows], device).  out_scores / out_ids: [n_queries, k], contiguous.  out_stats: NULL or int32 [n_queries, 2] =
+ *               (steps taken, rows scored).
+ *   visited set THE KERNEL'S SET FORGETS: "already scored" is kept in a 4096-slot LDS table that holds at most 3072 rows; when the next gather
+ *               (width * degree rows, or a slice of 1024 entries) might not fit, the table is cleared and the current beam members are put
+ *               back.  A forgotten row that is met again is scored again and dropped again -- the beam's last word never decreases once the beam
+ *               is full, and nothing was dropped before that -- so ids, scores and the step count are those of an exact set; only `rows scored`
+ *               grows.  With beam <= 1024 and width * degree <= 128 a query scores ~3000 rows between clears.
+ *   a query's result depends on its own rows of q and entry_rows alone: not on n_queries or its position in the call.
+ *   limits      dim % 32 == 0, 32 <= dim <= 8192; 8 <= degree <= 128, degree % 8 == 0; 1 <= k <= beam <= 2048; 1 <= width <= 8 and
+ *               width * degree <= 1024; 0 <= n_rows < 2^31; 1 <= n_entry <= 2048, ld_entry >= n_entry; 0 <= max_iterations <= 65536; ldx >= dim,
+ *               ldx % 4 == 0, X and q 16-byte aligned (q [n_queries, dim] contiguous).  n_queries == 0 launches nothing.  Anything else is
+ *               LRX_ERR_INVALID with a message before any device work; a workspace under lrx_graph_ip_workspace_bytes: LRX_ERR_WORKSPACE.
+ * One launch on `stream`, one workgroup of 512 threads per query, no host synchronisation, no allocation, capturable in a HIP graph.  The whole
+ * traversal state (beam and candidate words, the visited table, the query row up to 4096 floats) is 56 KiB of LDS; NO global scratch is used, so
+ * lrx_graph_ip_workspace_bytes is 0 for every argument today and `workspace` may then be NULL -- callers still size by it.  One half-wave scores
+ * one row (a random gather of whole rows, non-temporal loads); graph rows are read with ordinary loads. */
+size_t lrx_graph_ip_workspace_bytes(int32_t n_queries, int32_t n_entry, int32_t degree, int32_t beam, int32_t width);
+int lrx_graph_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim, const int32_t* graph, int32_t degree, const float* q,
+                        int32_t n_queries, const int64_t* entry_rows, int32_t n_entry, int64_t ld_entry, int32_t k, int32_t beam, int32_t width,
+                        int32_t max_iterations, int64_t id_base, float* out_scores, int64_t* out_ids, const int64_t* row_map, int32_t* out_stats,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* (added in ABI 9, additively) The integer step of the graph build (GraphFlatIndex): detour counts over kNN lists.
+ * knn int32 [n_rows, K] (row-major; -1 = empty slot), counts int32 [n_rows, K].  counts[u][c] = the number of pairs (a, b) of list positions such
+ * that, with v = knn[u][a] and w = knn[v][b], w stands in knn[u] at position c > max(a, b) (a row listed twice: its first position).  Empty slots
+ * take no part; an entry >= n_rows is treated as one and never dereferenced.  1 <= K <= 256, 0 <= n_rows < 2^31 (0 rows: nothing is launched);
+ * anything else is LRX_ERR_INVALID before any device work.  One launch, one workgroup per row, integer work only. */
+int lrx_graph_detour_counts(const int32_t* knn, int64_t n_rows, int32_t K, int32_t* counts, void* stream);
 
 /* Score pass only: scores[Q, ld] fp32 with ld = lrx_flat_ip_score_ld(N); columns >= N hold -FLT_MAX. */
 int64_t lrx_flat_ip_score_ld(int64_t n_rows);

@@ -1,1 +1,1 @@
-from lightretriever_amd.retriever import FaissBinaryIndex, FaissIndex  # noqa: F401
+from lightretriever_amd.retriever import FaissBinaryIndex, FaissHNSWIndex, FaissIndex  # noqa: F401

@@ -5,6 +5,7 @@ from .impact_index import ImpactIndex  # noqa: F401
 from .sparse_rows import SparseRows  # noqa: F401
 from .transform import PCAMatrix, PreTransformIndex  # noqa: F401
 from .refine import RefineFlatIndex  # noqa: F401
+from .graph import GraphFlatIndex  # noqa: F401
 from .ivf import IVFFlatIndex  # noqa: F401
 from .selector import RowSelector  # noqa: F401
 from .ivfpq import IVFPQIndex  # noqa: F401

@@ -87,6 +87,9 @@ SIGNATURES = {
     "lrx_ip_rerank_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "lrx_flat_ip_rerank": (_I32, [_P, _I64, _I64, _I32, _P, _I32, _P, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "lrx_sq_fp16_ip_rerank": (_I32, [_P, _I64, _I32, _P, _I32, _P, _I32, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_graph_ip_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "lrx_graph_ip_search": (_I32, [_P, _I64, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _I64, _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "lrx_graph_detour_counts": (_I32, [_P, _I64, _I32, _P, _P]),
     "lrx_ivf_flat_ip_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32, _I64]),
     "lrx_ivf_flat_ip_search": (_I32, [_P, _I64, _I64, _I32, _P, _P, _I32, _P, _I32, _P, _I32, _I64, _I64, _I32, _I64, _P, _P, _P, _P, _SZ, _P]),
     "lrx_ivf_flat_ip_range_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I64]),

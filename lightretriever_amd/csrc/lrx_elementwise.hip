@@ -168,6 +168,7 @@ extern "C" int64_t lrx_device_saturation_count(int32_t reset) {
 unsigned int lrx_attn_list_overflows(int* ok, int reset);   // lrx_attn.hip: attention work lists the builder could not fit (their launches compute nothing)
 unsigned int lrx_rerank_bad_rows(int* ok, int reset);       // lrx_search_rerank.h: candidate entries >= n_rows the rerank skipped
 unsigned int lrx_ivf_bad_entries(int* ok, int reset);       // lrx_search_ivf.h: probe entries >= nlist, queries over max_scan_rows, stored rows outside the shard
+unsigned int lrx_graph_bad_rows(int* ok, int reset);        // lrx_search_graph.h: entry-list and graph entries >= n_rows the graph search skipped
 extern "C" int64_t lrx_device_error_count(int32_t reset) {
   unsigned int v = 0;
   if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_bad_token_ids), sizeof(v)) != hipSuccess) return -1;
@@ -177,6 +178,8 @@ extern "C" int64_t lrx_device_error_count(int32_t reset) {
   a += lrx_rerank_bad_rows(&ok, reset);
   if (!ok) return -1;
   a += lrx_ivf_bad_entries(&ok, reset);
+  if (!ok) return -1;
+  a += lrx_graph_bad_rows(&ok, reset);
   if (!ok) return -1;
   if (reset && v) {
     const unsigned int z = 0;

@@ -13,6 +13,7 @@
 //     lrx_search_ivf.h      L. inverted file (IndexIVFFlat): probe plan, cell-major exact scan of the probed cells, per-query top-k (with its host driver)
 //     lrx_search_ivfpq.h    M. inverted file over PQ codes (IndexIVFPQ): dense probe plan, query-major ADC scan of the probed cells (with its host driver)
 //     lrx_search_selector.h P. row selector (IDSelector*): the bitmap over original rows the four inverted-file scans test, and its four kernels
+//     lrx_search_graph.h    Q. graph index: beam search over a fixed-degree neighbour graph, all state in LDS; the build's detour counts (with their host drivers)
 // Map of the unit:
 //
 //  A. Score kernels (what a search streams the shard through)
@@ -1345,3 +1346,4 @@ extern "C" int lrx_pack_topk(const float* scores, const int64_t* ids, const int6
 #include "lrx_search_ivfpq.h"     // inverted file over PQ codes (faiss IndexIVFPQ): ADC top-k over the rows of the probed cells, query-major scan
 #include "lrx_search_ivfsq.h"     // inverted file over fp16 codes (faiss IndexIVFScalarQuantizer, QT_fp16): the cell-major chain over 2-byte codes
 #include "lrx_search_ivfsq8.h"    // inverted file over 8-bit codes (faiss IndexIVFScalarQuantizer, QT_8bit[_uniform]): the chain over 1-byte codes, decoded once per group
+#include "lrx_search_graph.h"     // graph index (the role of faiss GpuIndexCagra / IndexHNSWCagra): beam search over a fixed-degree graph, detour counts of its build

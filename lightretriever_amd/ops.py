@@ -323,6 +323,45 @@ def sparse_compact_csr(reps: torch.Tensor, quantization_factor: int = 100, empty
     return SparseRows(row_off, terms, weights, V)
 
 
+# -- graph index (fixed-degree neighbour graph + beam search) --------------------------------------------------------------------
+def graph_ip_topk(q: torch.Tensor, X: torch.Tensor, graph: torch.Tensor, entry_rows: torch.Tensor, k: int, beam: int, width: int = 4,
+                  max_iterations: int = 0, id_base: int = 0, row_map: Optional[torch.Tensor] = None, stats: bool = False,
+                  ws_slots: Optional[dict] = None, capture_error: Optional[str] = None):
+    """lrx_graph_ip_search -> (D f32[Q,k], I i64[Q,k]) or, with stats=True, (D, I, S i32[Q,2] = steps taken, rows scored): the beam search of
+    include/lrx.h over the fp32 rows X [n, d] and the neighbour table graph int32 [n, degree] (contiguous, -1 = no edge), started from
+    entry_rows int64 [Q, n_entry] (rows may be strided; < 0 skipped, >= n skipped and counted in lrx_device_error_count).  q fp32 [Q, d]
+    contiguous.  ws_slots: a dict that keeps the workspace between calls (key "_ws")."""
+    lib = _lib.lib()
+    n, d = X.shape
+    if graph.dtype != torch.int32 or graph.dim() != 2 or graph.shape[0] != n or not graph.is_contiguous():
+        raise ValueError(f"graph_ip_topk: graph must be int32 [{n}, degree] contiguous")
+    if entry_rows.dtype != torch.int64 or entry_rows.dim() != 2 or entry_rows.shape[0] != q.shape[0] or (entry_rows.shape[1] and entry_rows.stride(1) != 1):
+        raise ValueError("graph_ip_topk: entry_rows must be int64 [Q, n_entry] with unit inner stride")
+    Q, n_entry = entry_rows.shape
+    degree = graph.shape[1]
+    D = torch.empty(Q, k, dtype=torch.float32, device=q.device)
+    I = torch.empty(Q, k, dtype=torch.int64, device=q.device)
+    S = torch.empty(Q, 2, dtype=torch.int32, device=q.device) if stats else None
+    need = int(lib.lrx_graph_ip_workspace_bytes(Q, n_entry, degree, beam, width))
+    ws = _workspace({} if ws_slots is None else ws_slots, "_ws", need, q.device, capture_error) if Q else None
+    _lib.check(lib.lrx_graph_ip_search(_lib.ptr(X) if n else None, n, X.stride(0) if n > 1 else d, d, _lib.ptr(graph) if n else None, degree,
+                                       _lib.ptr(q) if Q else None, Q, _lib.ptr(entry_rows) if Q else None, n_entry,
+                                       entry_rows.stride(0) if Q > 1 else n_entry, k, beam, width, max_iterations, int(id_base), _lib.ptr(D), _lib.ptr(I),
+                                       _lib.ptr(row_map), _lib.ptr(S), _lib.ptr(ws), ws.numel() if Q else 0, _s()))
+    return (D, I, S) if stats else (D, I)
+
+
+def graph_detour_counts(knn: torch.Tensor) -> torch.Tensor:
+    """lrx_graph_detour_counts -> counts int32 [n, K]: knn int32 [n, K] contiguous, the kNN lists of the graph build (-1 = empty slot);
+    counts[u][c] = the two-hop paths u -> knn[u][a] -> knn[u][c] through list positions a, b < c (include/lrx.h)."""
+    if knn.dtype != torch.int32 or knn.dim() != 2 or not knn.is_contiguous():
+        raise ValueError("graph_detour_counts: knn must be int32 [n, K] contiguous")
+    n, K = knn.shape
+    counts = torch.empty(n, K, dtype=torch.int32, device=knn.device)
+    _lib.check(_lib.lib().lrx_graph_detour_counts(_lib.ptr(knn) if n else None, n, K, _lib.ptr(counts) if n else None, _s()))
+    return counts
+
+
 # -- inverted file (IndexIVFFlat) ---------------------------------------------------------------------------------------------
 # Every family is described ONCE, by an _IvfFamily: `fam`, the stem of its library names; `args`, its _ivf_*_args, which checks a wrapper's
 # operands (its `n_operands` positionals before the k or radius) -> (Q, dims, head), the leading arguments of its two workspace functions (up to

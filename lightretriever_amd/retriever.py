@@ -12,6 +12,8 @@
     IVFPQFaissSearch    (no counterpart in the reference)                (faiss IndexIVFPQ, inner product: IVFPQIndex)
     IVFSQFaissSearch    (no counterpart in the reference)                (faiss IndexIVFScalarQuantizer, QT_fp16, inner product: IVFSQIndex)
     IVFSQ8FaissSearch   (no counterpart in the reference)                (faiss IndexIVFScalarQuantizer, QT_8bit / QT_8bit_uniform, inner product: IVFSQ8Index)
+    FaissHNSWIndex      <- retriever/faiss_index.py:76-113               (the wrapper's name; over GraphFlatIndex, no augmented dimension)
+    HNSWFaissSearch     <- retriever/faiss_search.py:385-433             (a fixed-degree graph + beam search over GraphFlatIndex, not faiss's HNSW)
     HybridSearch        <- retriever/hybrid_search.py:25-403   (dense `den` / `emb` branches; `tok` / `spr` and their fusions with a sparse engine)
     ImpactSearch        <- retriever/anserini_search.py (AnseriniSearch's interface; impact search over ImpactIndex instead of Lucene)
 
@@ -35,6 +37,7 @@ import numpy as np
 import torch
 
 from .impact_index import ImpactIndex, query_csr
+from .graph import GraphFlatIndex
 from .index import BinaryFlatIndex, FlatIPIndex, PQIndex, SQ8Index, SQFp16Index, merge_topk
 from .sparse_rows import SparseRows, identity_term
 from .ivf import IVFFlatIndex
@@ -711,6 +714,68 @@ class IVFFaissSearch(_IVFFaissSearch):
 
 
 
+class FaissHNSWIndex(FaissIndex):
+    """`FaissHNSWIndex(index, passage_ids)` of the reference over a GraphFlatIndex.  The reference appends a dimension to every row (and a zero to
+    every query) so that faiss's L2 HNSW ranks by inner product; none is needed here: the graph is built and searched under the inner product
+    itself.  The two agree on the neighbourhoods exactly when all rows have one norm -- what the encoder emits (normalised embeddings)."""
+
+    @classmethod
+    def build(cls, passage_ids: list, passage_embeddings, index: Optional[GraphFlatIndex] = None, buffer_size: int = 50000):
+        return super().build(passage_ids, passage_embeddings, GraphFlatIndex(passage_embeddings.shape[1]) if index is None else index, buffer_size)
+
+
+class HNSWFaissSearch(FlatIPFaissSearch):
+    """faiss_search.py:385-433 (IndexHNSWFlat(d + 1, hnsw_store_n) with efSearch / efConstruction) as a searcher, served by GraphFlatIndex: a
+    fixed-degree neighbour graph built from exact kNN lists and searched by a beam search (the shape faiss itself runs on a GPU, GpuIndexCagra),
+    not faiss's sequential HNSW insertion.  The arguments keep the reference's names and defaults and map as follows:
+      degree              = min(2 * hnsw_store_n, 64) rounded down to a multiple of 8, at least 8 (faiss's level-0 degree is 2 M; the reference's
+                            default of 1024 neighbours is clamped, logged once)
+      intermediate_degree = min(max(hnsw_ef_construction, 2 * degree), 256)
+      ef_search           = hnsw_ef_search
+    and both degrees are clamped to a chunk's row count.  index / _index_in_place / save behave like FlatIPFaissSearch's with that shard (the
+    graph is built at the chunk's first search); load() takes the parameters back from the file.  No augmented dimension (FaissHNSWIndex).
+    Not served: the L2 metric, shards on RPC workers, faiss's HNSW file record."""
+    index_cls = GraphFlatIndex
+    index_ext = "hnsw"
+    serves_rpc_shards = False
+    faiss_index_cls = FaissHNSWIndex
+    _clamp_logged = False
+
+    def __init__(self, model, batch_size: int = 128, corpus_chunk_size: Optional[int] = None, hnsw_store_n: int = 512, hnsw_ef_search: int = 128,
+                 hnsw_ef_construction: int = 200, similarity_metric=0, **kwargs):
+        _inner_product_only("HNSWFaissSearch", similarity_metric)
+        if hnsw_store_n < 1 or hnsw_ef_construction < 1 or not 1 <= hnsw_ef_search <= 2048:
+            raise ValueError(f"HNSWFaissSearch: hnsw_store_n={hnsw_store_n} and hnsw_ef_construction={hnsw_ef_construction} must be >= 1, "
+                             f"hnsw_ef_search={hnsw_ef_search} in 1 .. 2048")
+        super().__init__(model, batch_size, corpus_chunk_size, **kwargs)
+        self.hnsw_store_n, self.hnsw_ef_search, self.hnsw_ef_construction = int(hnsw_store_n), int(hnsw_ef_search), int(hnsw_ef_construction)
+        self.similarity_metric = 0
+        if 2 * self.hnsw_store_n > 64 and not HNSWFaissSearch._clamp_logged:
+            HNSWFaissSearch._clamp_logged = True
+            logger.info("HNSWFaissSearch: hnsw_store_n=%d (level-0 degree %d) is served with graph degree 64", self.hnsw_store_n, 2 * self.hnsw_store_n)
+
+    def _degrees(self, capacity: Optional[int] = None):
+        """-> (degree, intermediate_degree) of a shard of `capacity` rows (None: unclamped)."""
+        degree = max(8, min(2 * self.hnsw_store_n, 64) // 8 * 8)
+        K = min(max(self.hnsw_ef_construction, 2 * degree), 256)
+        if capacity is not None:                      # a chunk of fewer rows than a degree: lists as long as the chunk, the table at least 8 wide
+            degree = max(8, min(degree, capacity) // 8 * 8)
+            K = max(degree, min(K, capacity))
+        return degree, K
+
+    def _new_index(self, dim: int, capacity: int) -> GraphFlatIndex:
+        degree, K = self._degrees(capacity)
+        return GraphFlatIndex(dim, degree=degree, intermediate_degree=K, ef_search=self.hnsw_ef_search, capacity=capacity)
+
+    def load(self, input_dir: str, prefix: str = "my-index", ext: Optional[str] = None):
+        super().load(input_dir, prefix, ext)
+        idx = self.faiss_index.index
+        self.hnsw_store_n, self.hnsw_ef_search, self.hnsw_ef_construction = idx.degree // 2, idx.ef_search, idx.intermediate_degree
+
+    def get_index_name(self):
+        return "hnsw_faiss_index"
+
+
 class ImpactSearch:
     """The sparse engine HybridSearch calls, with the reference's AnseriniSearch interface (`index(corpus_emb, corpus_ids)`,
     `retrieve_with_emb(query_emb, query_ids, top_k)`, `_clear()`), over an HBM-resident ImpactIndex instead of Lucene behind a JVM: impact
@@ -875,20 +940,23 @@ class HybridSearch:
         # faiss_search_map (hybrid_search.py:32-70): "flat" (default), "sq" (QT_fp16 / QT_8bit_uniform), "pq" (IndexPQ), "binary" (IndexBinaryFlat + rerank),
         # "pca" (IndexPreTransform(PCAMatrix, base)), "refine" (IndexRefineFlat over a pq / sq / pca / ivfpq / ivfsq base), "ivf" (IndexIVFFlat), "ivfpq"
         # (IndexIVFPQ), "ivfsq" (IndexIVFScalarQuantizer, QT_fp16) and "ivfsq8" (IndexIVFScalarQuantizer, QT_8bit / QT_8bit_uniform) are served;
+        # "graph" (HNSWFaissSearch: a fixed-degree graph + beam search over GraphFlatIndex, the native way to the reference's hnsw_* arguments);
         # anything else ("hnsw", "hnswsq") is served flat
         faiss_search_map = kwargs.get("faiss_search_map", "flat")
         den_cls = {"sq": SQFaissSearch, "pq": PQFaissSearch, "binary": BinaryFaissSearch, "pca": PCAFaissSearch,
                    "refine": RefineFaissSearch, "ivf": IVFFaissSearch, "ivfpq": IVFPQFaissSearch, "ivfsq": IVFSQFaissSearch,
-                   "ivfsq8": IVFSQ8FaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
-        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine", "ivf", "ivfpq", "ivfsq", "ivfsq8"):
-            logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index", faiss_search_map)
+                   "ivfsq8": IVFSQ8FaissSearch, "graph": HNSWFaissSearch}.get(faiss_search_map, FlatIPFaissSearch)
+        if faiss_search_map not in ("flat", "sq", "pq", "binary", "pca", "refine", "ivf", "ivfpq", "ivfsq", "ivfsq8", "graph"):
+            logger.warning("HybridSearch: faiss_search_map=%r is not served; the dense half runs on the flat index (the graph index is "
+                           "faiss_search_map='graph')", faiss_search_map)
         # (the reference passes its **kwargs through to the searcher)
         passed = {"pq": ("num_of_centroids", "code_size", "use_rotation", "similarity_metric"), "sq": ("quantizer_type", "similarity_metric"),
                   "binary": ("binary_k", "threshold"), "pca": ("output_dimension", "base_index", "pca_matrix", "eigen_power", "random_rotation"),
                   "ivf": ("nlist", "nprobe", "similarity_metric"),
                   "ivfpq": ("nlist", "nprobe", "num_of_centroids", "code_size", "by_residual", "similarity_metric"),
                   "ivfsq": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric"),
-                  "ivfsq8": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric")}
+                  "ivfsq8": ("nlist", "nprobe", "quantizer_type", "by_residual", "similarity_metric"),
+                  "graph": ("hnsw_store_n", "hnsw_ef_search", "hnsw_ef_construction", "similarity_metric")}
         den_kwargs = {a: kwargs[a] for a in passed.get(faiss_search_map, ()) if a in kwargs}
         if faiss_search_map == "pca" and kwargs.get("output_dimension") is None:
             raise ValueError("HybridSearch: faiss_search_map='pca' needs output_dimension (the dimension after the PCA)")
