@@ -482,7 +482,10 @@ int lrx_flat_ip_search(const float* X, int64_t n_rows, int64_t ldx, int32_t dim,
  * flags: LRX_SEARCH_FILTER_* below (A/B runs and tests; the result does not depend on it).  Per call -- there is no process-wide
  * search state, calls from several host threads (the reference's RPC server threads) do not interact.
  * Queries are processed in chunks of 256 (128 without X_shadow) over the same workspace, whose size therefore stops growing at
- * 256 queries: min(Q,128) * rows * 4 bytes for the gated fallback plus Q candidate lists.                                          */
+ * 256 queries: min(Q,128) * rows * 4 bytes for the gated fallback plus Q candidate lists.
+ * dim has no upper limit here, nor in lrx_flat_ip_search, lrx_flat_ip_range_search, lrx_flat_ip_rerank and their lrx_sq_fp16_* forms:
+ * query rows of up to 8192 floats are staged in LDS by the rescoring kernels, longer ones are read from global memory -- slower, the same
+ * bits (served and tested at 8224 and 12288).  The inverted-file and graph entries refuse dim > 8192.                                 */
 enum {
   LRX_SEARCH_FILTER_AUTO = 0,            /* score-free filter from 16 Ki rows on, score-matrix filter below                         */
   LRX_SEARCH_FILTER_MATRIX = 1,          /* always the score-matrix filter                                                           */
@@ -652,7 +655,8 @@ int lrx_shard_commit_rows(const float* X, int64_t ldx, int64_t n_rows, int32_t d
  * lrx_pq_ip_search: LUT (lrx_pq_lut) -> k_pq_scan (the query's table in LDS, per-row lookups, [Q, rows] fp32 score matrix of a row chunk of
  * up to 4 Mi rows + 128-row block maxima) -> the flat index's exact top-k selection; row chunks are merged with lrx_merge_topk's kernel.
  * out_ids: id_base + row, or row_map[row] when row_map != NULL (a shard-local row -> its global row, as lrx_pack_topk).  Queries are walked
- * in chunks of lrx_pq_ip_chunk_queries (score matrices of <= 1 GiB); the workspace (lrx_pq_ip_workspace_bytes) holds one chunk.  flags: 0. */
+ * in chunks of lrx_pq_ip_chunk_queries (score matrices of <= 1 GiB, at most 65535 queries: the scan's grid.y); the workspace
+ * (lrx_pq_ip_workspace_bytes) holds one chunk.  flags: 0. */
 size_t lrx_pq_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k);
 int32_t lrx_pq_ip_chunk_queries(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k);
 int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* centroids, int32_t dim, int32_t M, const float* q, int32_t n_queries,
@@ -677,7 +681,8 @@ int lrx_pq_lut(const float* q, int32_t n_queries, const float* centroids, int32_
  *                 library's: faiss's depends on which of its kernels runs.)
  *   rerank        candidates = the Hamming top-min(binary_k, n_rows) under that rule; s(q, r) = (float) sum_j (double) q[j] * (bits(r)[j] ? +1 : -1),
  *                 fp64 accumulation, one rounding; result = the top-k candidates by s descending, ties to the lower row, (-FLT_MAX, -1) padding.
- *   limits        1 <= k <= binary_k <= 2048.
+ *   limits        1 <= k <= binary_k <= 2048.  dim = 16384 is served (the widest histogram tile takes 131 088 B of LDS).  Any number of
+ *                 queries the workspace holds: the rerank scores them 65535 per launch (grid.y).
  * THE CODE LAYOUT: the product-quantised index's, with M = dim / 8 bytes per row: G = ceil(dim / 128) 16-byte groups per row; the codes are an
  *   array of 128-row blocks of 2048 G bytes, each block group major [G][128 rows][16 bytes]: byte i of row r sits at
  *   (r / 128) 2048 G + (i / 16) 2048 + (r % 128) 16 + i % 16.  Bytes i >= dim / 8 of a row are ZERO (the writers below write them; the scan

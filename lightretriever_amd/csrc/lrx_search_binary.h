@@ -22,6 +22,7 @@
 #define BIN_MAX_BITS 16384
 #define BIN_HIST_FLUSH 63       // tiles between two flushes of the LDS histogram: its bins are 16 bits wide, 63 x 1024 < 65536
 #define BIN_RR_CAND 16          // candidates per workgroup of the rerank (4 waves x 4)
+#define BIN_RR_QMAX 65535       // queries per launch of the rerank scoring (grid.y)
 
 static __host__ __device__ __forceinline__ int bin_groups(int d) { return (d + 127) / 128; }      // 16-byte groups per row
 static __host__ __device__ __forceinline__ int64_t bin_code_off(int64_t r, int byte, int G) {
@@ -340,8 +341,8 @@ struct BinPlan {
 
 static int bin_query_tile(int32_t dim, int32_t n_queries) {
   if (n_queries <= 4 || dim > 4096) return 4;
-  return dim > 2048 ? 16 : 32;       // the LDS histogram of a tile: QT x (d / 2 + 1) words <= 128 KiB
-}
+  return dim > 2048 ? 16 : 32;       // the LDS histogram of a tile: QT x (d / 2 + 1) words -- at most 128 KiB + 128 B (32 x 2048 bits; 4 x 16384 =
+}                                    // BIN_MAX_BITS: 128 KiB + 16 B), of the 160 KiB a gfx950 workgroup may hold
 
 static BinPlan bin_plan(int64_t n_rows, int32_t dim, int32_t n_queries) {
   BinPlan p;
@@ -498,9 +499,11 @@ extern "C" int lrx_binary_ip_search(const void* codes, int64_t n_rows, int32_t d
   const int kk = (int)(n_rows < binary_k ? n_rows : binary_k);
   if ((rc = bin_candidates(p, codes, n_rows, dim, q, n_queries, threshold, threshold_vec, kk, ws, s)) != LRX_OK) return rc;
   if (flags & LRX_BINARY_SELECT_ONLY) return LRX_OK;
-  if (kk > 0) {
-    hipLaunchKernelGGL(k_bin_rerank_score, dim3((unsigned)lrx_cdiv(kk, BIN_RR_CAND), (unsigned)n_queries), dim3(256), (size_t)((dim + 31) / 32) * 32 * 4, s,
-                       (const uint8_t*)codes, dim, p.G, q, (const unsigned long long*)(ws + p.keys_off), kk, (float*)(ws + p.sc_off));
+  for (int32_t q0 = 0; kk > 0 && q0 < n_queries; q0 += BIN_RR_QMAX) {          // (keys and scores are strided per query: a launch takes its slice)
+    const int nq = n_queries - q0 < BIN_RR_QMAX ? n_queries - q0 : BIN_RR_QMAX;
+    hipLaunchKernelGGL(k_bin_rerank_score, dim3((unsigned)lrx_cdiv(kk, BIN_RR_CAND), (unsigned)nq), dim3(256), (size_t)((dim + 31) / 32) * 32 * 4, s,
+                       (const uint8_t*)codes, dim, p.G, q + (int64_t)q0 * dim, (const unsigned long long*)(ws + p.keys_off) + (int64_t)q0 * BIN_MAXK, kk,
+                       (float*)(ws + p.sc_off) + (int64_t)q0 * BIN_MAXK);
     LRX_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_bin_rerank_sort, dim3((unsigned)n_queries), dim3(SEL_THREADS), 0, s, (const unsigned long long*)(ws + p.keys_off),

@@ -20,6 +20,7 @@
 #define PQ_ENC_MAX_DSUB 64
 #define PQ_ROW_CHUNK (1ll << 22)       // rows per score matrix (16 MiB per query)
 #define PQ_MATRIX_BYTES (1ll << 30)    // score matrix budget of one query chunk
+#define PQ_QC_MAX 65535                // queries per chunk at most (grid.y of k_pq_scan)
 
 static __host__ __device__ __forceinline__ int pq_mp(int M) { return (M + PQ_GRP - 1) / PQ_GRP * PQ_GRP; }
 // byte offset of code m of row r in the blocked layout (include/lrx.h): block r / 128, 16-sub-space group m / 16, row r % 128, byte m % 16
@@ -161,7 +162,7 @@ k_pq_decode(const uint8_t* __restrict__ codes, int64_t row0, int64_t n_rows, con
 // ---------------------------------------------------------------------------------------------------------------
 // the leading region of the workspace is the chunk's lookup tables [qc, M, 256] fp32
 static ScanPlan pq_plan(int64_t n_rows, int32_t M, int32_t n_queries, int32_t k) {
-  return scan_plan(n_rows, n_queries, k, PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, INT32_MAX, [&](int qc) { return align256((size_t)qc * M * PQ_KSUB * 4); });
+  return scan_plan(n_rows, n_queries, k, PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, PQ_QC_MAX, [&](int qc) { return align256((size_t)qc * M * PQ_KSUB * 4); });
 }
 
 extern "C" size_t lrx_pq_ip_workspace_bytes(int64_t n_rows, int32_t dim, int32_t M, int32_t n_queries, int32_t k) {
@@ -243,7 +244,7 @@ extern "C" int lrx_pq_ip_search(const void* codes, int64_t n_rows, const float* 
 
 // ---- range search: every row with s(q, r) > radius (the contract of lrx_flat_ip_range_search; include/lrx.h) ----
 static ScanRangePlan pq_range_plan(int64_t n_rows, int32_t M, int32_t n_queries, int64_t row_chunk) {
-  return scan_range_plan(n_rows, n_queries, row_chunk > 0 ? row_chunk : PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, 65535,
+  return scan_range_plan(n_rows, n_queries, row_chunk > 0 ? row_chunk : PQ_ROW_CHUNK, 64, PQ_MATRIX_BYTES, PQ_QC_MAX,
                          [&](int qc) { return align256((size_t)qc * M * PQ_KSUB * 4); });
 }
 
