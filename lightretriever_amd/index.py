@@ -148,7 +148,9 @@ class _TiledIPIndex:
       _search_ws_bytes(flags)                     -> f(ntotal, d, nq, k): workspace bytes of one library call of nq queries
       _search_rows()                              -> (row stride of the fp32 rows, the tiled fp16 rows the search streams or None)
       _lib_chunk_queries(n, k, flags, has_xb)     -> queries per library chunk of a call of n queries
-      _search_chunk(qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire)   one library call over queries qc on `stream`"""
+      _search_chunk(qc, Dc, Ic, k, ws, stream, xb, ldx, flags, row_map, wire)   one library call over queries qc on `stream`
+    The rows, the tiled fp16 rows and the bounds an index holds, and what it returns, are a function of the committed rows in arrival order and
+    of nothing else that happened to it -- reserve, slots that were never committed, reset, reload, shadow_f16 / two_pass toggles."""
     # lrx_flat_ip_search_bounded flags (_lib.SEARCH_FILTER_*): which filter the bounded search runs.  A class-level default that tests and A/B
     # tools override (per index or for all); the hits do not depend on it.  (Round 2 had a process-global switch inside the library.)
     search_flags = _lib.SEARCH_FILTER_AUTO
@@ -686,7 +688,9 @@ class _CodeIndex:
     of append_slot(n) / commit(n) -- commit() trains an untrained index on the staged rows, add()s them and releases the staging; reset()
     (drops the rows, keeps the training); the search prologue and the search workspace `_ws`.  A subclass checks its arguments BEFORE it
     calls this constructor (no GPU is needed to refuse them) and keeps what is its own: training, _encode_into (or add), the decode call of
-    reconstruct_n, the layout permutation (_layout), persistence and the library calls of search."""
+    reconstruct_n, the layout permutation (_layout), persistence and the library calls of search.
+    The codes an index holds, and what it returns, are a function of its training and of the committed rows in arrival order, and of nothing
+    else that happened to it: reset() leaves old codes in the last block, and every kernel is handed ntotal, never the capacity."""
     MAX_K = 2048
     is_trained = True          # (faiss: an index that needs no training is trained; PQIndex / SQ8Index start untrained)
     _capture_ws_error = None   # SQ8Index: the message that refuses to allocate the search workspace under HIP-graph capture

@@ -49,7 +49,10 @@ class _IVFCells:
     The three cell-major indexes keep their rows or codes in `_store`, row-major [capacity, d] by stored position (_init_store), which is
     reserved, permuted and mapped here; IVFPQIndex overrides _reserve / _permute over the blocked codes of its PQIndex.  A subclass brings
     _put (rows [a, b) into the store: a copy, or an encode), IVF_FAMILY / CODED / _store_operands (what _cells_op, the one place that picks the
-    wrapper and lists its operands, needs to know of it), set_contents, reconstruct_n and persistence."""
+    wrapper and lists its operands, needs to know of it), set_contents, reconstruct_n and persistence.
+    After _finalize the cell order, the stored rows or codes and every result are a function of the centroids (and the subclass's training) and
+    of the added rows in arrival order, and of nothing else that happened to the index -- how the adds were split, when a search rebuilt the
+    order, reset, reload."""
 
     NITER = 10
     MAX_POINTS_PER_CENTROID = 256
